@@ -21,12 +21,17 @@ on 127.0.0.1) unless it already runs under ``torch.distributed.run`` (WORLD_SIZE
 
 Prints ONE JSON line on rank 0.  ``roofline``: the dominant kernel (the solve kernel, launched alone with
 CRT_FLAG_SKIP_PRECOMPUTE between two HIP events on its own stream) against the 8 TB/s HBM3E peak; algorithmic bytes per solve
-as SURVEY section 8(d) / BASELINE.md section 3.  The timed block of K steps is repeated ``--repeats`` times: ``ms_per_step`` /
-``value`` come from the MEDIAN block, min and max are reported beside it.  ``cpu_baseline``: the NumPy oracle (a port of the
+as SURVEY section 8(d) / BASELINE.md section 3.  ``--steps K`` is the number of timed steps in all, split into ``--repeats`` blocks
+(at most K): ``ms_per_step`` / ``value`` come from the MEDIAN block, min and max are reported beside it.  ``cpu_baseline``: the NumPy oracle (a port of the
 reference algorithm; the reference itself is pure Python and cannot travel to the GPU box) timed on this box's host cores on a
 bounded sample of the same workload, rank 0, N = 1 only; ``cpu_baseline.reference_shaped`` is a per-band Python loop with the
 reference's structure and the here-measured ratio to the real reference (oracle/ref_ratio.json).  ``pcie_inclusive``: the same
 step with H2D of the inputs and D2H of the profiles (never ``value``).
+
+``--dump-outputs DIR`` (rank 0) writes what the timed path returned in its LAST timed step, before anything else touches those buffers, as
+``DIR/<name>.npy`` (float64, or float32 for f32 storage): at most 64 MB in all, so a larger output is sampled by a fixed seed along its
+column axis (``DIR/sample_rows_<n>.npy``: the sampled rows of the arrays with n columns).  The inputs depend only on the arguments, so two
+builds run with the same arguments can be compared file by file.
 """
 
 import argparse
@@ -40,7 +45,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec
 
 # algorithmic bytes per (column x band) solve: s * [n_in + n_full * nz + n_mid * (nz - 1)], s = 8 (fp64)
 # (each compulsory byte once: per-band inputs read, full profiles written)
@@ -360,9 +365,10 @@ def launch_ranks(n, argv, timeout_s):
 def parse_args(argv):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None, help="steps per timed block (default 100; 10 with --partition band)")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps in all (default 100; 10 with --partition band)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps first (default 20; 3 with --partition band)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps; the median block is reported")
+    ap.add_argument("--repeats", type=int, default=5, help="the --steps timed steps are split into this many blocks (at most one per step); "
+                    "the median block is reported")
     ap.add_argument("--scheme", default=None, choices=sorted(N_IO))
     ap.add_argument("--partition", default="column", choices=["column", "band"],
                     help="'column': column blocks per rank, no data-path collective (weak scaling, the headline); 'band': band blocks "
@@ -394,6 +400,8 @@ def parse_args(argv):
                     "rehearsal on a one-GPU box: torch.distributed.run --nproc-per-node 1 bench.py --gpus 1 --force-pg)")
     ap.add_argument("--launch-timeout", type=float, default=1500.0)
     ap.add_argument("--cpu-budget", type=float, default=15.0)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy "
+                    "(at most 64 MB in all; larger outputs are a seeded sample of columns)")
     a = ap.parse_args(argv)
     band = a.partition == "band"
     if a.scheme is None:
@@ -406,7 +414,56 @@ def parse_args(argv):
         a.steps = 10 if band else 100
     if a.warmup is None:
         a.warmup = 3 if band else 20
+    if a.steps < 1 or a.warmup < 0 or a.repeats < 1:
+        ap.error("--steps and --repeats must be >= 1, --warmup >= 0")
     return a
+
+
+DUMP_BYTES = 64 * 10 ** 6
+DUMP_SEED = 20240611
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES, seed=DUMP_SEED):
+    """Write `arrays` (name -> tensor whose first axis is columns) as `path/<name>.npy`, float32 arrays as float32 and everything else as
+    float64.  If they exceed `budget` bytes, the same fraction of rows is kept from every array, chosen by `seed` among the arrays'
+    row count n (arrays with the same n share their rows) and written as `path/sample_rows_<n>.npy`.  Returns a summary for the JSON line."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v for k, v in arrays.items() if isinstance(v, torch.Tensor) and v.dim() >= 1}
+    isz = {k: 4 if v.dtype == torch.float32 else 8 for k, v in arrays.items()}
+    row_bytes = {k: v[0].numel() * isz[k] if v.shape[0] else 0 for k, v in arrays.items()}
+    total = sum(row_bytes[k] * v.shape[0] for k, v in arrays.items())
+    counts = sorted({v.shape[0] for v in arrays.values()})
+    keep = {n: n for n in counts}
+    if total > budget:
+        frac = budget / total
+        keep = {n: max(1, int(n * frac)) for n in counts}
+
+        def size():  # the data, the float64 row lists and a .npy header per file
+            return sum(row_bytes[k] * keep[v.shape[0]] + 256 for k, v in arrays.items()) + sum(8 * keep[n] + 256 for n in counts)
+
+        while size() > budget and any(k > 1 for k in keep.values()):
+            n = max(keep, key=lambda m: keep[m])
+            keep[n] -= 1
+    rows, files = {}, []
+    for n in counts:
+        if keep[n] < n:
+            rows[n] = np.sort(np.random.default_rng(seed + n).choice(n, keep[n], replace=False))
+            files.append(os.path.join(path, f"sample_rows_{n}.npy"))
+            np.save(files[-1], rows[n].astype(np.float64))
+    written = {}
+    for k, v in arrays.items():
+        n = v.shape[0]
+        if n in rows:
+            v = v.index_select(0, torch.as_tensor(rows[n], device=v.device))
+        x = v.detach().cpu().numpy().astype(np.float32 if isz[k] == 4 else np.float64)
+        files.append(os.path.join(path, f"{k}.npy"))
+        np.save(files[-1], x)
+        written[k] = list(x.shape)
+    return {"dir": path, "arrays": written, "sampled_rows": {str(n): int(keep[n]) for n in rows}, "seed": seed if rows else None,
+            "bytes": int(sum(os.path.getsize(f) for f in files))}
 
 
 def kernel_name(lib):
@@ -486,28 +543,31 @@ def main():
         return x
 
     def timed_blocks(step, finish=None):
-        """--warmup untimed steps, then --repeats blocks of EXACTLY --steps steps, each bracketed by barrier + synchronize on both
-        sides; per block the max over ranks."""
+        """--warmup untimed steps, then EXACTLY --steps timed steps in all, split as evenly as possible into min(--repeats, --steps)
+        blocks, each bracketed by barrier + synchronize on both sides.  Returns the seconds PER STEP of every block (max over ranks)."""
         for _ in range(a.warmup):
             step()
         if finish:
             finish()
-        blocks = []
-        for _ in range(max(1, a.repeats)):
+        nblk = max(1, min(a.repeats, a.steps))
+        sizes = [a.steps // nblk + (1 if i < a.steps % nblk else 0) for i in range(nblk)]
+        per_step = []
+        for n in sizes:
             barrier()
             t0 = time.perf_counter()
-            for _ in range(a.steps):
+            for _ in range(n):
                 step()
             if finish:
                 finish()
             barrier()
-            blocks.append(max_over_ranks(time.perf_counter() - t0))
-        return blocks
+            per_step.append(max_over_ranks(time.perf_counter() - t0) / n)
+        return per_step
 
     f32 = a.dtype == "f32"
     band = a.partition == "band"
     extra = {}
     check, check_int = None, None
+    dumped = None  # summary of --dump-outputs
     if band:
         # ---------------------------------------------------------------- band partition: BASELINE configs[3]
         from crt1d_amd import dist as cdist
@@ -531,6 +591,13 @@ def main():
             res_holder["r"] = plan.wait()
 
         blocks = timed_blocks(step)
+        if a.dump_outputs and rank == 0:  # now: compute_only below reuses the message buffers these results live in
+            r = res_holder["r"]
+            arrays = {k: v for k, v in r.items() if k not in ("profiles", "columns")}
+            prof = r.get("profiles")
+            prof = prof[-1] if isinstance(prof, list) else prof  # the output set is shared: it holds the last column tile
+            arrays.update({f"profiles_last_tile_{k}": v for k, v in (prof or {}).items()})
+            dumped = dump_outputs(a.dump_outputs, arrays)
         solves_per_step = ncol * nb  # the whole problem, whatever N is
         # compute only (no collective), and the collective alone on the same messages
         def compute_only():
@@ -563,7 +630,7 @@ def main():
                 "backend": "RCCL (nccl)" if a.backend == "nccl" else "gloo (rehearsal)", "ranks_seen": ranks_seen,
                 "message_bytes_per_step": plan.message_bytes, "messages_per_step": plan.ntile,
                 "collective_ms_alone": coll_ms,
-                "compute_only_ms_per_step": sorted(compute_blocks)[len(compute_blocks) // 2] / a.steps * 1e3,
+                "compute_only_ms_per_step": sorted(compute_blocks)[len(compute_blocks) // 2] * 1e3,
                 "semantics": "sum over bands of w * X (crt1d/diagnostics.py:81); reflectance = reflected / incoming after the reduce (:510-511)",
             },
             "kernels_per_rank": knames,
@@ -602,6 +669,8 @@ def main():
             # output buffers are allocated once, before the timed region (placement="auto": crt_hip_buffer_alloc_set)
             main_plan = batched.Plan(scheme, cols, bands, placement=a.placement)
         blocks = timed_blocks(lambda: main_plan())
+        if a.dump_outputs and rank == 0:  # before any probe below overwrites the output buffers
+            dumped = dump_outputs(a.dump_outputs, main_plan.out)
         solves_per_step = ncol * nb * world
         if not a.no_check:
             try:  # the buffers as the timed region left them, before any probe overwrites them
@@ -655,8 +724,8 @@ def main():
             del msg
 
     blocks_sorted = sorted(blocks)
-    el = blocks_sorted[len(blocks_sorted) // 2]  # median block
-    value = solves_per_step * a.steps / el
+    el = blocks_sorted[len(blocks_sorted) // 2]  # seconds per step of the median block
+    value = solves_per_step / el
 
     # ---- dominant kernel alone, HIP events on the stream it is launched on ----
     roof = None
@@ -807,7 +876,7 @@ def main():
         except Exception as e:
             print(f"pcie-inclusive measurement failed: {e!r}", file=sys.stderr)
 
-    per_step = [b / a.steps * 1e3 for b in blocks]
+    per_step = [b * 1e3 for b in blocks]
     out = {
         "metric": ("(column x band) solves/sec at 60 layers" if nz == 60 else f"(column x band) solves/sec at {nz} layers")
                   + (" [integrated outputs only]" if a.variant == "integrated" else ""),
@@ -816,8 +885,8 @@ def main():
         "n_gpus": world,
         "steps": a.steps,
         "warmup": a.warmup,
-        "ms_per_step": el / a.steps * 1e3,
-        "ms_per_step_blocks": {"repeats": len(blocks), "median": el / a.steps * 1e3, "min": min(per_step), "max": max(per_step), "all": per_step},
+        "ms_per_step": el * 1e3,
+        "ms_per_step_blocks": {"repeats": len(blocks), "median": el * 1e3, "min": min(per_step), "max": max(per_step), "all": per_step},
         "higher_is_better": True,
         "scaling": "strong" if band else "weak",
         "vs_baseline": None,
@@ -840,6 +909,8 @@ def main():
         out["roofline"] = roof
     if pcie is not None:
         out["pcie_inclusive"] = pcie
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(scheme, nb, nz, a.cpu_budget, cpu_workers)
     stop_cpu_workers(cpu_workers)
