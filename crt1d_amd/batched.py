@@ -585,7 +585,7 @@ class IntegratedPlan:
 
     def __init__(self, scheme, cols: Columns, bands: Bands, band_w, *, mu_s=0.501, tau_d_method="quad", workspace=None, out=None,
                  profiles=False):
-        if scheme not in _lib.SCHEME_IDS or scheme == "zq_pa":
+        if scheme not in _lib.SCHEME_IDS:
             raise ValueError(f"scheme {scheme!r} has no integrated kernel")
         if tau_d_method not in _lib.TAU_D_METHODS:
             raise ValueError("invalid `method`. Valid options are 'quad' and '9sky'.")

@@ -1087,7 +1087,7 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
   sa.f32 = f32;
   for (int i = 0; i < CRT_NTUNE; ++i) sa.tune[i] = tune[i];
   if (integ) {
-    if (scheme == CRT_SCHEME_ZQ_PA) return CRT_ERR_UNSUPPORTED;
+    if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_int(sa, *integ, s);
     return tri ? launch_tridiag_int(scheme, sa, *integ, s) : launch_closed_int(scheme, sa, *integ, s);
   }
   if (scheme == CRT_SCHEME_ZQ_PA)

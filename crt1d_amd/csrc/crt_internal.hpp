@@ -593,6 +593,7 @@ int launch_tri_int_n79_f32(const SolveArgs& a, const IntArgs& ia, hipStream_t s)
 int launch_tri_int_zq_f64(const SolveArgs& a, const IntArgs& ia, hipStream_t s);
 int launch_tri_int_zq_f32(const SolveArgs& a, const IntArgs& ia, hipStream_t s);
 int launch_zqpa(const SolveArgs& a, double* scratch, hipStream_t s);
+int launch_zqpa_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s);  // integrated outputs, no scratch (tri_zqpa.hip)
 int launch_zqpa_wave(const SolveArgs& g, hipStream_t s);  // per-wave fallback of the computational-grid solve
 __host__ __device__ inline int zqpa_M(int nz) { return nz < 100 ? nz : 100; }
 void host_quad_nodes(double mu_s, double* psi_nodes);

@@ -619,7 +619,306 @@ int launch_zqpa_fused(const SolveArgs& a, hipStream_t s, int nsw, size_t lds_cap
   return nthr <= 512 ? go(k_zqpa_pipe<TIO, M, T, 512, false>) : go(k_zqpa_pipe<TIO, M, T, 1024, false>);
 }
 
+// ------------------------------------------------------------------------------------------
+// Integrated outputs only (crt_hip_integrated_f64 / crt_hip_integrated2_f64, IntArgs): no profile and no scratch reaches HBM.
+// The interpolation back to the caller's levels is linear with band-independent weights (kidx[j], wgt[j] of the record), so the
+// band sums can be interpolated instead of the profiles.  The sweep reduces over the bands, into ngroup weighted sums per computational
+// row (wave_sum4; partials per wave in LDS, sized by Mg <= 100, not by the caller's nz), and the finish interpolates those sums to the
+// caller's levels with k_zqpa_interp's index arithmetic (clamps SWd[0] := SWd[1], SWu[Mg] := SWu[Mg-1] of :310 / :335 included).  The
+// direct beam factorises, R_g(j) = ekl[j] sum_b w_g[b] I_dr0[b]: one more reduction per column.
+//   profiles requested: SWd[k+1] and SWu[k] of every row (two wave_sum4), the level sums D_g, U_g are interpolated separately;
+//   otherwise only Phi = R + D - U is needed, and D, U interpolate between the SAME interfaces (ka - 1, ka) with the same weight: ONE
+//   wave_sum4 per row of the net flux N[i] = SWd[i] - SWu[i] (the lane keeps SWu of the row above), plus separate D, U sums at the <= 4
+//   interfaces the top and ground levels interpolate from (totals).  The second reduction per row cost 17 % (1e4 x 300 x 60: 1.06 ->
+//   0.88 ms measured without it).
+// Equal to the band sums of the profile path up to rounding.
+struct ZqPaIntLds {
+  double* lev;   // SPLIT: [Mg][nwave][2][INT_MAXG] wave sums of w SWd[k+1] (q = 0), w SWu[k] (q = 1);  else [Mg + 1][nwave][INT_MAXG] of w N[i]
+  double* ends;  // !SPLIT: [4][nwave][2][INT_MAXG] wave sums of w SWd[i], w SWu[i] at the interfaces ka - 1, ka of the ground and top levels
+  double* pdr;   // [nwave][INT_MAXG]: wave sums of w (1 - r - t) I_dr0
+  double* pi0;   // [nwave][INT_MAXG]: wave sums of w I_dr0
+};  // (after the fold, wave slot 0 of every sum holds the total)
+__host__ __device__ inline size_t zqpa_int_lds_doubles(int Mg, int nwave, bool split) {
+  const size_t per_wave = split ? (size_t)Mg * 2 * INT_MAXG : (size_t)(Mg + 1) * INT_MAXG + 4 * 2 * INT_MAXG;
+  return (per_wave + 2 * INT_MAXG) * nwave;
+}
+
+// PROF: level profiles requested (needs SPLIT); SPLIT: separate D, U sums per row (the net-flux form has fewer, see above)
+template <int M, int MAXT, bool PROF, bool SPLIT>
+__global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4))) void k_zqpa_int(SolveArgs g, IntArgs ia, int nzo, int off_ck,
+                                                                                           int off_int) {
+  typedef TriZq S;
+  static_assert(SPLIT || !PROF, "the level profiles need the separate sums");
+  extern __shared__ double lds[];
+  {
+    const double* src = g.ws + (long long)blockIdx.x * g.reclen;
+    for (int i = threadIdx.x; i < g.reclen; i += blockDim.x) lds[i] = src[i];
+  }
+  __syncthreads();
+  const int nb = g.nb, Mg = g.nz, ng = ia.ngroup;
+  const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, nwave = nthr >> 6;
+  const int c = blockIdx.x;
+  const double* rec = lds;
+  const double* ekl = rec + REC_HDR + nzo;
+  const double* kidx = ekl + nzo;
+  const double* wgt = kidx + nzo;
+  auto ka_of = [&](int j) { return min(max((int)kidx[j], 1), Mg); };  // (1 <= kidx <= Mg for every record K0 writes)
+  double* ck = lds + off_ck + tid;  // [nck][2][nthr]
+  ZqPaIntLds L;
+  L.lev = lds + off_int;
+  L.ends = L.lev + (SPLIT ? (size_t)Mg * nwave * 2 * INT_MAXG : (size_t)(Mg + 1) * nwave * INT_MAXG);
+  L.pdr = L.ends + (SPLIT ? 0 : (size_t)4 * nwave * 2 * INT_MAXG);
+  L.pi0 = L.pdr + (size_t)nwave * INT_MAXG;
+  const bool active = tid < nb;
+  const int b = active ? tid : 0;
+  S st;
+  st.template init<double>(rec, g, c, b);
+  const double bc = st.band_const();  // I_dr0
+  const long long ib = (long long)c * g.col_stride + b;
+  const double leaf_a = 1 - (ldio<double>(g.leaf_r, ib) + ldio<double>(g.leaf_t, ib));
+  double w[INT_MAXG];
+#pragma unroll
+  for (int q = 0; q < INT_MAXG; ++q) w[q] = (q < ng && active) ? ia.band_w[(long long)q * nb + b] : 0.0;
+#pragma unroll
+  for (int q = 0; q < INT_MAXG; ++q)
+    if (q < ng) {
+      const double t = wave_sum_all(w[q] * leaf_a * bc);
+      const double t0 = wave_sum_all(w[q] * bc);
+      if (lane == 0) {
+        L.pdr[wave * INT_MAXG + q] = t;
+        L.pi0[wave * INT_MAXG + q] = t0;
+      }
+    }
+  // !SPLIT: interfaces whose separate D, U sums the totals need: ka - 1, ka of the ground level (slots 0, 1) and of the top level (2, 3)
+  const int kag = __builtin_amdgcn_readfirstlane(ka_of(0)), kat = __builtin_amdgcn_readfirstlane(ka_of(nzo - 1));  // (scalar registers)
+  const int eif[4] = {kag - 1, kag, kat - 1, kat};
+  // ---- the zq sweep on the computational grid (rows 0 .. Mg; row Mg is the top boundary), checkpointed as in tri_int_body ----
+  const int K = S::rows(Mg);
+  static_assert(M % S::RENORM == 0, "checkpoints must fall on re-seeding levels");
+  typename S::St fs;
+  st.first(rec, Mg, fs);
+  {
+    double e, f;
+    st.pair(fs, e, f);
+    ck[0] = e;
+    ck[nthr] = f;
+  }
+  tri_forward<S, M>(st, rec, Mg, fs, K - 1, [&](int level, const typename S::St& cs) {
+    const int sidx = level / M;
+    double e, f;
+    st.pair(cs, e, f);
+    ck[(2 * sidx) * nthr] = e;
+    ck[(2 * sidx + 1) * nthr] = f;
+  });
+  const int gslot = wave_sum4_slot(lane >> 4);
+  const bool writer = (lane & 15) == 0 && gslot < ng;
+  // !SPLIT: band sums at interface i from the lane's SWd'[i], SWu'[i] (clamped): the net flux always, D and U at the end interfaces
+  auto net_interface = [&](int i, double dd, double uu) {
+    const double nn = dd - uu;
+    const double z = wave_sum4(w[0] * nn, w[1] * nn, w[2] * nn, w[3] * nn);
+    if (writer) L.lev[(i * nwave + wave) * INT_MAXG + gslot] = z;
+    if (i == eif[0] || i == eif[1] || i == eif[2] || i == eif[3]) {  // (wave-uniform)
+      const double zd = wave_sum4(w[0] * dd, w[1] * dd, w[2] * dd, w[3] * dd);
+      const double zu = wave_sum4(w[0] * uu, w[1] * uu, w[2] * uu, w[3] * uu);
+      if (writer)
+        for (int e = 0; e < 4; ++e)
+          if (eif[e] == i) {
+            L.ends[((e * nwave + wave) * 2 + 0) * INT_MAXG + gslot] = zd;
+            L.ends[((e * nwave + wave) * 2 + 1) * INT_MAXG + gslot] = zu;
+          }
+    }
+  };
+  double u_above = 0.0;  // !SPLIT: SWu[k + 1] of the row substituted back before row k (rows come from the top)
+  for (int seg = (K - 1) / M; seg >= 0; --seg) {
+    const int k0 = seg * M;
+    const int kend = min(k0 + M - 1, K - 1);
+    double be[M], bf[M];
+    be[0] = ck[(2 * seg) * nthr];
+    bf[0] = ck[(2 * seg + 1) * nthr];
+    typename S::St rs;
+    st.seed(rs, be[0], bf[0]);
+#pragma unroll
+    for (int i = 1; i < M; ++i) {
+      be[i] = be[i - 1];
+      bf[i] = bf[i - 1];
+      if (k0 + i <= kend) tri_step(st, k0 + i - 1, rec, Mg, rs, be[i], bf[i]);
+    }
+#pragma unroll
+    for (int i = M - 1; i >= 0; --i) {
+      const int k = k0 + i;
+      if (k <= kend) {
+        double o[S::NST];
+        if (k == K - 1) {
+          st.top(rec, Mg, be[i], bf[i], o);  // boundary only, no row of the grid's fluxes
+        } else {
+          st.back(k, rec, Mg, be[i], bf[i], o);
+          const double dd = active ? o[0] : 0.0, uu = active ? o[1] : 0.0;  // SWd[k+1], SWu[k]
+          if constexpr (SPLIT) {
+            const double zd = wave_sum4(w[0] * dd, w[1] * dd, w[2] * dd, w[3] * dd);
+            const double zu = wave_sum4(w[0] * uu, w[1] * uu, w[2] * uu, w[3] * uu);
+            if (writer) {
+              L.lev[((k * nwave + wave) * 2 + 0) * INT_MAXG + gslot] = zd;
+              L.lev[((k * nwave + wave) * 2 + 1) * INT_MAXG + gslot] = zu;
+            }
+          } else {
+            if (k == K - 2) u_above = uu;  // SWu[Mg] := SWu[Mg-1] (:335)
+            net_interface(k + 1, dd, u_above);
+            u_above = uu;
+            if (k == 0) net_interface(0, dd, uu);  // SWd[0] := SWd[1] (:310)
+          }
+        }
+      }
+    }
+  }
+  // ---- finish: fold the wave partials (in place, into wave slot 0), then interpolate the group sums to the caller's levels ----
+  __syncthreads();
+  {
+    const int nlev = SPLIT ? 2 * Mg : Mg + 1 + 8;  // rows of sums per wave besides pdr, pi0
+    for (int i = tid; i < (nlev + 2) * ng; i += nthr) {
+      const int r = i / ng, q = i - r * ng;
+      double* p;
+      int stride;
+      if (r >= nlev) {
+        p = (r == nlev ? L.pdr : L.pi0) + q;
+        stride = INT_MAXG;
+      } else if (SPLIT) {
+        p = L.lev + ((r >> 1) * nwave * 2 + (r & 1)) * INT_MAXG + q;
+        stride = 2 * INT_MAXG;
+      } else if (r <= Mg) {
+        p = L.lev + r * nwave * INT_MAXG + q;
+        stride = INT_MAXG;
+      } else {
+        const int e = (r - Mg - 1) >> 1, qq = (r - Mg - 1) & 1;
+        p = L.ends + (e * nwave * 2 + qq) * INT_MAXG + q;
+        stride = 2 * INT_MAXG;
+      }
+      double t = p[0];
+      for (int wv = 1; wv < nwave; ++wv) t += p[wv * stride];
+      p[0] = t;
+    }
+  }
+  __syncthreads();
+  // SPLIT: band sums of I_dr, I_df_d, I_df_u at caller level j, group q (k_zqpa_interp's expressions on the group sums)
+  const int rs2 = nwave * 2 * INT_MAXG;  // row stride of the folded sums
+  auto level = [&](int j, int q, double& R, double& D, double& U) {
+    const int ka = ka_of(j), kb = ka - 1;
+    const double wj = wgt[j];
+    const double da = L.lev[(max(ka, 1) - 1) * rs2 + q], db = L.lev[(max(kb, 1) - 1) * rs2 + q];
+    const double ua = L.lev[min(ka, Mg - 1) * rs2 + INT_MAXG + q], ub = L.lev[min(kb, Mg - 1) * rs2 + INT_MAXG + q];
+    D = da + (db - da) * wj;  // :360
+    U = ua + (ub - ua) * wj;  // :361
+    R = ekl[j] * L.pi0[q];    // :354-355
+  };
+  // net downward flux Phi = R + D - U at caller level j, group q
+  auto phi = [&](int j, int q) -> double {
+    if constexpr (SPLIT) {
+      double R, D, U;
+      level(j, q, R, D, U);
+      return R + D - U;
+    } else {
+      const int ka = ka_of(j);
+      const double na = L.lev[ka * nwave * INT_MAXG + q], nb_ = L.lev[(ka - 1) * nwave * INT_MAXG + q];
+      return ekl[j] * L.pi0[q] + (na + (nb_ - na) * wgt[j]);
+    }
+  };
+  if constexpr (PROF) {
+    const double invmu = rec[S_INVMU];
+    for (int i = tid; i < nzo * ng; i += nthr) {
+      const int j = i / ng, q = i - j * ng;
+      double R, D, U;
+      level(j, q, R, D, U);
+      const long long o = ((long long)c * nzo + j) * ng + q;
+      ia.L_dr[o] = R;
+      ia.L_dn[o] = D;
+      ia.L_up[o] = U;
+      ia.L_F[o] = R * invmu + 2 * (U + D);
+      ia.L_Id[o] = R + D;
+    }
+  }
+  const double Kb = rec[S_KB];
+  const double* lai = ia.lai + (long long)c * nzo;
+  for (int i = tid; i < (nzo - 1) * ng; i += nthr) {
+    const int k = i / ng, q = i - k * ng;
+    const double dl = lai[k] - lai[k + 1];
+    const double fsl = exp(-Kb * ((lai[k] + lai[k + 1]) / 2));                 // model.py:601-602
+    const double adr = (1 - exp(-Kb * dl)) * exp(-Kb * lai[k + 1]) * L.pdr[q];  // :617-621
+    const double a = phi(k + 1, q) - phi(k, q);                                 // :609
+    const double adf = a - adr;
+    const long long o = ((long long)c * (nzo - 1) + k) * ng + q;
+    ia.aI[o] = a;
+    ia.aI_sl[o] = adf * fsl + adr;
+    ia.aI_sh[o] = adf * (1 - fsl);
+    if constexpr (PROF) ia.aI_dr[o] = adr;
+  }
+  if (ia.totals) {
+    for (int i = tid; i < ng * 4; i += nthr) {
+      const int q = i >> 2, t = i & 3;  // incoming (top, I_d), reflected (top, up), transmitted (ground, I_d), soil-reflected
+      const int j = t < 2 ? nzo - 1 : 0;
+      double R, D, U;
+      if constexpr (SPLIT) {
+        level(j, q, R, D, U);
+      } else {
+        const int e = t < 2 ? 2 : 0;  // slots of interfaces ka - 1, ka of level j
+        auto E = [&](int s, int qq) { return L.ends[(s * nwave * 2 + qq) * INT_MAXG + q]; };
+        const double wj = wgt[j];
+        D = E(e + 1, 0) + (E(e, 0) - E(e + 1, 0)) * wj;
+        U = E(e + 1, 1) + (E(e, 1) - E(e + 1, 1)) * wj;
+        R = ekl[j] * L.pi0[q];
+      }
+      ia.totals[((long long)c * ng + q) * 4 + t] = (t & 1) ? U : R + D;
+    }
+  }
+}
+
+// LDS of k_zqpa_int in bytes: record | checkpoints [Mg / M + 1][2][nthr] (K = Mg + 1 rows, one every M) | partial sums
+inline size_t zqpa_int_lds_bytes(const SolveArgs& a, int M, int nthr, bool split, int* off_ck = nullptr, int* off_int = nullptr) {
+  const int Mg = zqpa_M(a.nz);
+  const int ock = (a.reclen + 1) & ~1;
+  const int oint = ock + 2 * (Mg / M + 1) * nthr;
+  if (off_ck) *off_ck = ock;
+  if (off_int) *off_int = oint;
+  return ((size_t)oint + zqpa_int_lds_doubles(Mg, nthr / 64, split)) * sizeof(double);
+}
+
+template <int M, bool PROF, bool SPLIT>
+int launch_zqpa_int_m(const SolveArgs& a, const IntArgs& ia, hipStream_t s, int nthr) {
+  const int Mg = zqpa_M(a.nz);
+  int off_ck, off_int;
+  const size_t sh = zqpa_int_lds_bytes(a, M, nthr, SPLIT, &off_ck, &off_int);
+  if (sh > MAX_WG_LDS) return CRT_ERR_UNSUPPORTED;
+  SolveArgs g = a;  // computational-grid solve: nz := Mg (the record keeps the caller's nz: passed separately)
+  g.nz = Mg;
+  for (int i = 0; i < 7; ++i) g.o[i] = nullptr;
+  auto go = [&](auto kern) {
+    if (sh > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
+      return (int)CRT_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(a.ncol), dim3(nthr), sh, s, g, ia, a.nz, off_ck, off_int);
+    if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+    note_kernel("k_zqpa_int<zq_pa> M=%d grid=%d%s", M, Mg, PROF ? " + level profiles" : "");  // (only a launch that succeeded is reported)
+    return (int)CRT_OK;
+  };
+  if (nthr <= 256) return go(k_zqpa_int<M, 256, PROF, SPLIT>);
+  if (nthr <= 512) return go(k_zqpa_int<M, 512, PROF, SPLIT>);
+  return go(k_zqpa_int<M, 1024, PROF, SPLIT>);
+}
+
 }  // namespace
+
+// integrated path of zq_pa (float64 spectra): one kernel, no workspace beyond the K0 record
+int launch_zqpa_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
+  if (a.nb > 1024 || a.f32) return CRT_ERR_UNSUPPORTED;
+  const int nthr = ((a.nb + 63) / 64) * 64;
+  // M = 8 (104 / 114 VGPRs) or M = 12 (124 VGPRs): four waves per SIMD with no scratch, also in the 1024-thread form (M = 16 there: 128
+  // VGPRs + 56 B of scratch; the net-flux form at M = 12: 128 + 24 B).  The LDS decides how many workgroups share a CU: the form that fits
+  // more of them is taken, the smaller M and (without profiles) the net-flux form on a tie.  Measured (1e4 x 300 x 60 / 6e3 x 300 x 100):
+  // net-flux M = 8 0.956 / 1.323 ms (three / one workgroups per CU), separate sums M = 12 1.056 / 1.013 (three / two)
+  const bool prof = ia.L_dr != nullptr;
+  const size_t s8 = zqpa_int_lds_bytes(a, 8, nthr, prof), s12 = zqpa_int_lds_bytes(a, 12, nthr, true);
+  auto fits = [](size_t sh) -> size_t { return sh <= MAX_WG_LDS ? MAX_WG_LDS / sh : 0; };
+  if (fits(s12) > fits(s8)) return prof ? launch_zqpa_int_m<12, true, true>(a, ia, s, nthr) : launch_zqpa_int_m<12, false, true>(a, ia, s, nthr);
+  return prof ? launch_zqpa_int_m<8, true, true>(a, ia, s, nthr) : launch_zqpa_int_m<8, false, false>(a, ia, s, nthr);
+}
 
 int launch_zqpa(const SolveArgs& a, double* scratch, hipStream_t s) {
   const int* g_tri_tune = a.tune + 8;  // this call's overrides

@@ -235,7 +235,7 @@ int crt_hip_integrated2_f64(int scheme, const crt_columns* cols, const crt_bands
 /*
  * Fused solve + epilogue: the integrated outputs of crt_hip_absorb_bandsum_f64 (same shapes and meaning) straight from
  * the inputs, WITHOUT writing any profile to memory (bytes per solve drop from ~2 kB to ~40 B; the variant SURVEY.md
- * section 8(d) asks to report separately).  Schemes: 2s, 4s, bl, g77, bf, n79, zq; nb <= 1024.
+ * section 8(d) asks to report separately).  Schemes: 2s, 4s, bl, g77, bf, n79, zq, zq_pa; nb <= 1024.
  */
 int crt_hip_integrated_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts,
                            const double* band_w, int32_t ngroup, double* aI, double* aI_sl, double* aI_sh, double* totals,
