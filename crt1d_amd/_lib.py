@@ -108,6 +108,11 @@ EXPORTS = [
     "crt_hip_integrated_f64",
     "crt_hip_integrated2_f64",
     "crt_hip_absorb_f64",
+    "crt_hip_absorb_bandsum_f32",
+    "crt_hip_absorb_bandsum2_f32",
+    "crt_hip_integrated_f32",
+    "crt_hip_integrated2_f32",
+    "crt_hip_absorb_f32",
     "crt_hip_band_reduce_f64",
     "crt_hip_tau_d_f64",
     "crt_hip_smear_tuv_f64",
@@ -177,28 +182,32 @@ def load():
             f = getattr(lib, f"crt_hip_{s}_{suffix}")
             f.restype = ctypes.c_int
             f.argtypes = solve_args
-    lib.crt_hip_absorb_bandsum_f64.restype = ctypes.c_int
-    lib.crt_hip_absorb_bandsum_f64.argtypes = [
-        ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp,
-    ]
-    lib.crt_hip_integrated_f64.restype = ctypes.c_int
-    lib.crt_hip_integrated_f64.argtypes = [
-        ctypes.c_int, ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), ctypes.POINTER(CrtOptions), _vp, ctypes.c_int32,
-        _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp,
-    ]
-    lib.crt_hip_absorb_bandsum2_f64.restype = ctypes.c_int
-    lib.crt_hip_absorb_bandsum2_f64.argtypes = [
-        ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.POINTER(CrtBandsumOut), _vp,
-    ]
-    lib.crt_hip_integrated2_f64.restype = ctypes.c_int
-    lib.crt_hip_integrated2_f64.argtypes = [
-        ctypes.c_int, ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), ctypes.POINTER(CrtOptions), _vp, ctypes.c_int32,
-        ctypes.POINTER(CrtBandsumOut), _vp, ctypes.c_size_t, _vp,
-    ]
+    for suffix in ("f64", "f32"):  # the epilogue and integrated entries of both storage types (crt_bands_f32 shares the layout)
+        f = getattr(lib, f"crt_hip_absorb_bandsum_{suffix}")
+        f.restype = ctypes.c_int
+        f.argtypes = [ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]
+        f = getattr(lib, f"crt_hip_integrated_{suffix}")
+        f.restype = ctypes.c_int
+        f.argtypes = [
+            ctypes.c_int, ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), ctypes.POINTER(CrtOptions), _vp, ctypes.c_int32,
+            _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp,
+        ]
+        f = getattr(lib, f"crt_hip_absorb_bandsum2_{suffix}")
+        f.restype = ctypes.c_int
+        f.argtypes = [
+            ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.POINTER(CrtBandsumOut), _vp,
+        ]
+        f = getattr(lib, f"crt_hip_integrated2_{suffix}")
+        f.restype = ctypes.c_int
+        f.argtypes = [
+            ctypes.c_int, ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), ctypes.POINTER(CrtOptions), _vp, ctypes.c_int32,
+            ctypes.POINTER(CrtBandsumOut), _vp, ctypes.c_size_t, _vp,
+        ]
+        f = getattr(lib, f"crt_hip_absorb_{suffix}")
+        f.restype = ctypes.c_int
+        f.argtypes = [ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), _vp, _vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _vp]
     lib.crt_hip_band_reduce_f64.restype = ctypes.c_int
     lib.crt_hip_band_reduce_f64.argtypes = [_vp, ctypes.c_int64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp]
-    lib.crt_hip_absorb_f64.restype = ctypes.c_int
-    lib.crt_hip_absorb_f64.argtypes = [ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), _vp, _vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _vp]
     lib.crt_hip_tau_d_f64.restype = ctypes.c_int
     lib.crt_hip_tau_d_f64.argtypes = [_vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp, _vp]
     lib.crt_hip_smear_tuv_f64.restype = ctypes.c_int

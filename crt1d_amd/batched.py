@@ -465,18 +465,25 @@ def solve(scheme, cols: Columns, bands: Bands, *, mu_s=0.501, tau_d_method="quad
         return Plan(scheme, cols, bands, mu_s=mu_s, tau_d_method=tau_d_method, out=out, workspace=workspace, placement=placement)()
 
 
+def _io_suffix(bands):
+    """Entry-point suffix of the storage type of ``bands``: ``"f64"`` or ``"f32"`` (f32 storage: float spectra / profiles, fp64 arithmetic)."""
+    return "f32" if bands.dtype == torch.float32 else "f64"
+
+
 def _check_epilogue_inputs(cols, bands, sol):
-    """The epilogue entry points are fp64 only (``crt_hip_absorb*_f64``): float32 profiles (the output of an f32 solve) read as
-    double would run past the end of the allocation."""
-    if bands.dtype != torch.float64:
-        raise TypeError("the epilogue kernels take float64 spectra and profiles (got float32 bands); upcast first")
+    """The epilogue reads the leaf optics of ``bands`` and the three profiles with ONE element type: float64 bands with float64
+    profiles (``crt_hip_absorb*_f64``) or float32 bands with float32 profiles, e.g. the output of an f32 solve
+    (``crt_hip_absorb*_f32``).  Mixed precision is a TypeError: a profile read with the wrong element size would run past the end of
+    its allocation."""
     _check_band_device(bands, cols.device)
     bands.col_stride(cols.ncol)
     cols.check_tables()
     for k in ("I_dr", "I_df_d", "I_df_u"):
         if k not in sol:
             raise ValueError(f"`sol` lacks {k!r}")
-        _check_profile(sol[k], f"sol[{k!r}]", (cols.ncol, cols.nz, bands.nb), cols.device)
+        if isinstance(sol[k], torch.Tensor) and sol[k].dtype != bands.dtype:
+            raise TypeError(f"sol[{k!r}] is {sol[k].dtype} but the bands are {bands.dtype}: profiles and bands must share one storage type")
+        _check_profile(sol[k], f"sol[{k!r}]", (cols.ncol, cols.nz, bands.nb), cols.device, bands.dtype)
 
 
 BANDSUM_KEYS = ("aI", "aI_sl", "aI_sh", "totals")
@@ -508,9 +515,10 @@ def absorption_from_bandsums(res):
 
 
 class BandSumPlan:
-    """Pre-validated launch of the epilogue (``crt_hip_absorb_bandsum_f64``) on fixed buffers: ``plan()`` enqueues the kernel with
-    no allocation and no host synchronisation.  ``out`` may hold caller-owned output tensors (e.g. views into one packed
-    message buffer, :class:`crt1d_amd.dist.BandShardPlan`)."""
+    """Pre-validated launch of the epilogue (``crt_hip_absorb_bandsum2_f64``, or ``_f32`` for float32 bands and profiles) on fixed
+    buffers: ``plan()`` enqueues the kernel with no allocation and no host synchronisation.  ``out`` may hold caller-owned output
+    tensors (e.g. views into one packed message buffer, :class:`crt1d_amd.dist.BandShardPlan`); they are float64 for both storage
+    types, and the f32 band sums equal the f64 band sums of the upcast profiles bit for bit."""
 
     def __init__(self, cols: Columns, bands: Bands, sol, band_w, out=None, profiles=False):
         self.lib = _lib.load()
@@ -531,16 +539,17 @@ class BandSumPlan:
         self.cols, self.bands, self.sol, self.band_w, self.out, self.ng, self.profiles = cols, bands, sol, band_w, out, ng, profiles
         self._c, self._b = cols.c_struct(), bands.c_struct(ncol)
         self._o = _bandsum_out_struct(out, profiles)
+        self._entry = f"crt_hip_absorb_bandsum2_{_io_suffix(bands)}"
+        self._fn = getattr(self.lib, self._entry)
 
     def __call__(self, stream=None):
         dev = self.cols.device
         s = torch.cuda.current_stream(dev) if stream is None else stream
         sol = self.sol
         with torch.cuda.device(dev):
-            st = self.lib.crt_hip_absorb_bandsum2_f64(
-                ctypes.byref(self._c), ctypes.byref(self._b), sol["I_dr"].data_ptr(), sol["I_df_d"].data_ptr(), sol["I_df_u"].data_ptr(),
-                self.band_w.data_ptr(), self.ng, ctypes.byref(self._o), s.cuda_stream)
-        _lib.check(st, "crt_hip_absorb_bandsum2_f64")
+            st = self._fn(ctypes.byref(self._c), ctypes.byref(self._b), sol["I_dr"].data_ptr(), sol["I_df_d"].data_ptr(),
+                          sol["I_df_u"].data_ptr(), self.band_w.data_ptr(), self.ng, ctypes.byref(self._o), s.cuda_stream)
+        _lib.check(st, self._entry)
         return self.out
 
 
@@ -550,7 +559,8 @@ def absorb_bandsum(cols: Columns, bands: Bands, sol, band_w, out=None, profiles=
     energy-balance terms ``totals (ncol, ngroup, 4)`` = incoming, reflected, transmitted, soil-reflected.
     ``profiles=True`` adds everything else ``diagnostics.band`` returns (``PROFILE_KEYS``): the band-integrated level profiles
     ``I_dr, I_df_d, I_df_u, F, I_d (ncol, nz, ngroup)`` and ``aI_dr (ncol, nz-1, ngroup)`` (:func:`absorption_from_bandsums`).
-    Photon-flux variants (``calc_PFD``) are a choice of weights: ``spectra.band_weights(..., wl=..., pfd=True)``."""
+    Photon-flux variants (``calc_PFD``) are a choice of weights: ``spectra.band_weights(..., wl=..., pfd=True)``.
+    ``bands`` and the profiles ``sol`` are both float64 or both float32 (f32 storage); the outputs are float64 either way."""
     return dict(BandSumPlan(cols, bands, sol, band_w, out=out, profiles=profiles)())
 
 
@@ -559,29 +569,33 @@ ABSORPTION_KEYS = ("aI", "aI_df", "aI_dr", "aI_sh", "aI_sl", "aI_df_sl", "aI_df_
 
 def absorb(cols: Columns, bands: Bands, sol):
     """Per-band layerwise absorption: the reference's ``Model.absorption`` dict (``model.py:573-647``), batched.
-    Returns the seven ``(ncol, nz-1, nb)`` arrays plus ``laim``, ``f_slm`` ``(ncol, nz-1)``."""
+    Returns the seven ``(ncol, nz-1, nb)`` arrays plus ``laim``, ``f_slm`` ``(ncol, nz-1)``.
+    ``bands`` and ``sol`` are both float64 or both float32; with float32 (f32 storage) the seven per-band arrays are float32 -- the
+    fp64 result rounded once -- and ``laim``, ``f_slm`` stay float64."""
     lib = _lib.load()
     ncol, nz, nb = cols.ncol, cols.nz, bands.nb
     dev = cols.device
     _check_epilogue_inputs(cols, bands, sol)
-    out = {k: torch.empty((ncol, nz - 1, nb), dtype=torch.float64, device=dev) for k in ABSORPTION_KEYS}
+    entry = f"crt_hip_absorb_{_io_suffix(bands)}"
+    out = {k: torch.empty((ncol, nz - 1, nb), dtype=bands.dtype, device=dev) for k in ABSORPTION_KEYS}
     laim = torch.empty((ncol, nz - 1), dtype=torch.float64, device=dev)
     f_slm = torch.empty_like(laim)
     ptrs = (ctypes.c_void_p * 7)(*[out[k].data_ptr() for k in ABSORPTION_KEYS])
     c, b = cols.c_struct(), bands.c_struct(ncol)
     with torch.cuda.device(dev):
-        st = lib.crt_hip_absorb_f64(ctypes.byref(c), ctypes.byref(b), sol["I_dr"].data_ptr(), sol["I_df_d"].data_ptr(),
-                                    sol["I_df_u"].data_ptr(), ptrs, laim.data_ptr(), f_slm.data_ptr(),
-                                    torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(st, "crt_hip_absorb_f64")
+        st = getattr(lib, entry)(ctypes.byref(c), ctypes.byref(b), sol["I_dr"].data_ptr(), sol["I_df_d"].data_ptr(),
+                                 sol["I_df_u"].data_ptr(), ptrs, laim.data_ptr(), f_slm.data_ptr(),
+                                 torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(st, entry)
     out["laim"] = laim
     out["f_slm"] = f_slm
     return out
 
 
 class IntegratedPlan:
-    """Fused solve + absorption + band integrals (``crt_hip_integrated_f64``): no profile ever reaches HBM.
-    Outputs as :func:`absorb_bandsum`: ``aI, aI_sl, aI_sh (ncol, nz-1, ngroup)``, ``totals (ncol, ngroup, 4)``."""
+    """Fused solve + absorption + band integrals (``crt_hip_integrated2_f64``, or ``_f32`` for float32 bands): no profile ever
+    reaches HBM.  Outputs as :func:`absorb_bandsum`: ``aI, aI_sl, aI_sh (ncol, nz-1, ngroup)``, ``totals (ncol, ngroup, 4)``; float64
+    for both storage types."""
 
     def __init__(self, scheme, cols: Columns, bands: Bands, band_w, *, mu_s=0.501, tau_d_method="quad", workspace=None, out=None,
                  profiles=False):
@@ -589,8 +603,6 @@ class IntegratedPlan:
             raise ValueError(f"scheme {scheme!r} has no integrated kernel")
         if tau_d_method not in _lib.TAU_D_METHODS:
             raise ValueError("invalid `method`. Valid options are 'quad' and '9sky'.")
-        if bands.dtype != torch.float64:
-            raise TypeError("the integrated path takes float64 spectra")
         self.lib = _lib.load()
         self.scheme, self.cols, self.bands = scheme, cols, bands
         band_w = _f64(band_w, "band_w")
@@ -621,17 +633,23 @@ class IntegratedPlan:
         self.workspace = _check_workspace(workspace, need, dev)
         self._c, self._b = cols.c_struct(), bands.c_struct(ncol)
         self._o = _lib.CrtOptions(float(mu_s), _lib.TAU_D_METHODS[tau_d_method], 0)
+        self._entry = f"crt_hip_integrated2_{_io_suffix(bands)}"
+        self._fn = getattr(self.lib, self._entry)
+
+    def last_kernel(self):
+        """Name / configuration of the fused kernel this thread's most recent call launched (``crt_hip_last_kernel``)."""
+        return self.lib.crt_hip_last_kernel().decode()
 
     def __call__(self, stream=None, *, flags=0):
         dev = self.cols.device
         s = torch.cuda.current_stream(dev) if stream is None else stream
         self._o.flags = int(flags)
         with torch.cuda.device(dev):
-            st = self.lib.crt_hip_integrated2_f64(
+            st = self._fn(
                 _lib.SCHEME_IDS[self.scheme], ctypes.byref(self._c), ctypes.byref(self._b), ctypes.byref(self._o), self.band_w.data_ptr(),
                 self.band_w.shape[0], ctypes.byref(self._out), self.workspace.data_ptr(),
                 self.workspace.numel() * self.workspace.element_size(), s.cuda_stream)
-        _lib.check(st, "crt_hip_integrated2_f64")
+        _lib.check(st, self._entry)
         return self.out
 
 

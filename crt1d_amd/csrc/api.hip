@@ -27,7 +27,10 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 constexpr int MAXG = 4;
 constexpr int BS_CH = 8;
 
-struct EpiArgs {
+// TIO = double | float: element type of the spectra and profiles the epilogue reads (crt_hip_absorb_bandsum*_f64 / _f32).  Every load
+// converts to double at once; band_w, the geometry, the arithmetic and all band-sum outputs are fp64 for both.
+template <typename TIO>
+struct EpiArgsT {
   int ncol, nb, nz, ngroup;
   long long col_stride;
   const double* psi;
@@ -35,11 +38,11 @@ struct EpiArgs {
   const int32_t* g_kind;
   const double* g_param;
   const double* g_at_psi;
-  const double* leaf_r;
-  const double* leaf_t;
-  const double* I_dr;
-  const double* I_df_d;
-  const double* I_df_u;
+  const TIO* leaf_r;
+  const TIO* leaf_t;
+  const TIO* I_dr;
+  const TIO* I_df_d;
+  const TIO* I_df_u;
   const double* band_w;
   double* aI;
   double* aI_sl;
@@ -54,10 +57,12 @@ struct EpiArgs {
   double* L_F;
   double* L_Id;
 };
+typedef EpiArgsT<double> EpiArgs;
 
 // level outputs from the three level sums: F = I_dr / mu + 2 I_df_u + 2 I_df_d is linear in the profiles (every scheme forms its F this
 // way, e.g. _solve_2s.py:156), so its band sum is the same combination of the band sums; I_d = I_dr + I_df_d (model.py:425)
-__device__ inline void store_level_profiles(const EpiArgs& a, long long o, double R, double Dn, double Up, double invmu, bool accumulate) {
+template <class A>
+__device__ inline void store_level_profiles(const A& a, long long o, double R, double Dn, double Up, double invmu, bool accumulate) {
   if (accumulate) {
     a.L_dr[o] += R;
     a.L_dn[o] += Dn;
@@ -73,8 +78,8 @@ __device__ inline void store_level_profiles(const EpiArgs& a, long long o, doubl
   }
 }
 
-template <int MAXT, bool PROF>
-__global__ __launch_bounds__(MAXT) void k_absorb_bandsum(EpiArgs a, int b0, int nbs, int accumulate) {
+template <typename TIO, int MAXT, bool PROF>
+__global__ __launch_bounds__(MAXT) void k_absorb_bandsum(EpiArgsT<TIO> a, int b0, int nbs, int accumulate) {
   // bands [b0, b0 + nbs) of every row (nbs <= blockDim.x <= 1024; spectra wider than 1024 bands take several launches, the
   // later ones adding to the outputs of the first)
   extern __shared__ double lds[];
@@ -87,9 +92,9 @@ __global__ __launch_bounds__(MAXT) void k_absorb_bandsum(EpiArgs a, int b0, int 
   const double Kb = G / cos(psi);
   const double* __restrict__ lai = a.lai + (long long)c * nz;
   const long long cb = (long long)c * nz * nb + b0;
-  const double* __restrict__ R = a.I_dr + cb;
-  const double* __restrict__ D = a.I_df_d + cb;
-  const double* __restrict__ U = a.I_df_u + cb;
+  const TIO* __restrict__ R = a.I_dr + cb;
+  const TIO* __restrict__ D = a.I_df_d + cb;
+  const TIO* __restrict__ U = a.I_df_u + cb;
   // LDS: part[2][BS_CH][nwave][NV][MAXG] (NV = 2 sums per level and group: A, D; PROF: + the level sums of I_dr, I_df_d, I_df_u),
   // ends[nwave][4][MAXG], PROF: lev0[nwave][3][MAXG] (the level sums of row 0)
   constexpr int NV = PROF ? 5 : 2;
@@ -104,7 +109,7 @@ __global__ __launch_bounds__(MAXT) void k_absorb_bandsum(EpiArgs a, int b0, int 
   double w[MAXG], wa[MAXG];
   {
     const long long ib = (long long)c * a.col_stride + b0 + bi;
-    const double la = act ? 1 - (a.leaf_r[ib] + a.leaf_t[ib]) : 0.0;  // :584
+    const double la = act ? 1 - ((double)a.leaf_r[ib] + (double)a.leaf_t[ib]) : 0.0;  // :584
 #pragma unroll
     for (int g = 0; g < MAXG; ++g) {
       w[g] = (g < ng && act) ? a.band_w[(long long)g * nb + b0 + bi] : 0.0;
@@ -259,14 +264,15 @@ __global__ __launch_bounds__(MAXT) void k_absorb_bandsum(EpiArgs a, int b0, int 
 
 // The per-column tail of the band-sum kernels below: raw band sums A_g(k), D_g(k) (LDS) -> the level outputs, lanes over (level, group).
 // Streaming stores: the outputs are not read again by this kernel (1e5 x 38 x 100: 2.05 -> 1.91 ms).
-__device__ inline double column_kb(const EpiArgs& a, int c) {
+template <class A>
+__device__ inline double column_kb(const A& a, int c) {
   const double psi = a.psi[c];
   const int kind = a.g_kind[c];
   const double G = (kind == CRT_G_TABLE) ? a.g_at_psi[c] : G_closed(kind, a.g_param ? a.g_param[c] : 0.0, cos(psi), sin(psi));
   return G / cos(psi);
 }
-template <int NGT, bool PROF = false>
-__device__ inline void bandsum_finish(const EpiArgs& a, int c, const double* raw, const double* ends, const double* __restrict__ lai, double Kb, int l,
+template <int NGT, bool PROF = false, class EA>
+__device__ inline void bandsum_finish(const EA& a, int c, const double* raw, const double* ends, const double* __restrict__ lai, double Kb, int l,
                                       int nlanes, const double* lev = nullptr) {
   const int ng = a.ngroup, nl = a.nz - 1;
   const long long ob = (long long)c * nl * ng;
@@ -303,8 +309,8 @@ __device__ inline void bandsum_finish(const EpiArgs& a, int c, const double* raw
 // crt_internal.hpp: 5 instructions per value instead of 18).  No barriers, no cross-wave traffic: the waves of a workgroup are
 // independent columns.  The raw band sums A_g(k), D_g(k) go to LDS; at the end the lanes turn them into the level outputs
 // (level factors f_sl(k), 1 - e^{-K_b dlai_k} evaluated there, lanes over levels) and write them coalesced.
-template <int NBT, int CH, int NGT, bool PF = false, bool PROF = false>
-__global__ __launch_bounds__(256) void k_absorb_bandsum_w(EpiArgs a, int wpb, int per_wave) {
+template <typename TIO, int NBT, int CH, int NGT, bool PF = false, bool PROF = false>
+__global__ __launch_bounds__(256) void k_absorb_bandsum_w(EpiArgsT<TIO> a, int wpb, int per_wave) {
   extern __shared__ double lds[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // wave-uniform column index in a scalar register: the profile pointers below then are scalar bases, and every load is
@@ -316,9 +322,9 @@ __global__ __launch_bounds__(256) void k_absorb_bandsum_w(EpiArgs a, int wpb, in
   double* ends = raw + 2 * NGT * nl;            // [2][NGT][2]: ground (I_d, I_df_u), top (I_d, I_df_u)
   double* lev = ends + 4 * NGT;                 // PROF: [nz][NGT][3] level sums of I_dr, I_df_d, I_df_u
   const long long cb = (long long)c * nz * nb;
-  const double* __restrict__ R = a.I_dr + cb;
-  const double* __restrict__ D = a.I_df_d + cb;
-  const double* __restrict__ U = a.I_df_u + cb;
+  const TIO* __restrict__ R = a.I_dr + cb;
+  const TIO* __restrict__ D = a.I_df_d + cb;
+  const TIO* __restrict__ U = a.I_df_u + cb;
   int bi[NBT];
   double w[NBT][NGT], la[NBT], r0[NBT], d0[NBT], u0[NBT];  // NGT >= ngroup: weight registers for the groups in use only
 #pragma unroll
@@ -327,7 +333,7 @@ __global__ __launch_bounds__(256) void k_absorb_bandsum_w(EpiArgs a, int wpb, in
     const bool act = b < nb;
     bi[i] = act ? b : 0;
     const long long ib = (long long)c * a.col_stride + bi[i];
-    la[i] = act ? 1 - (a.leaf_r[ib] + a.leaf_t[ib]) : 0.0;  // :584
+    la[i] = act ? 1 - ((double)a.leaf_r[ib] + (double)a.leaf_t[ib]) : 0.0;  // :584
 #pragma unroll
     for (int g = 0; g < NGT; ++g) w[i][g] = (g < ng && act) ? a.band_w[(long long)g * nb + bi[i]] : 0.0;
     r0[i] = R[bi[i]];
@@ -465,8 +471,12 @@ __global__ __launch_bounds__(256) void k_absorb_bandsum_w(EpiArgs a, int wpb, in
 //     trips), 3.3 us per further slab, then 2.2 + 2.6 + 0.9 us (last reduction, tail arithmetic, store acknowledgement).
 //     (A persistent form -- waves walking columns w, w + G, ... with the next column's first slab prefetched -- was tried: the
 //     loop-carried state costs 316 registers, one wave per SIMD, 3.3 ms instead of 2.0; capped at 256 it spills, 2.3 ms.)
-template <int NGT>
-__global__ __launch_bounds__(64) void k_absorb_bandsum_l(EpiArgs a, int nbp) {
+//   * float storage (TIO = float): the same pieces of two bands, 8 bytes per lane, widened to d2 as they go to LDS.  A column of
+//     nz * nb floats starts on an 8-byte boundary only (nz * nb is even, not a multiple of four), and the layer sums must keep the fp64
+//     kernel's order (f32 band sums are the f64 band sums of the upcast profiles, bit for bit).
+template <typename TIO, int NGT>
+__global__ __launch_bounds__(64) void k_absorb_bandsum_l(EpiArgsT<TIO> a, int nbp) {
+  typedef TIO tio2 __attribute__((ext_vector_type(2)));  // one piece: two bands of a row
   constexpr int LS = 16, NP = 4, NLD = 9;  // NLD 16-byte loads per lane cover 17 rows of <= 64 bands: 17 * 32 <= 9 * 64
   constexpr int NLAI = 5;                  // LAI levels per lane: nz <= 64 * 4 + 1 (the launcher checks)
   extern __shared__ double lds[];
@@ -491,15 +501,15 @@ __global__ __launch_bounds__(64) void k_absorb_bandsum_l(EpiArgs a, int nbp) {
   const int slot = wave_sum4_slot(p);
   const bool band_lane = lane < nb;
   // registers of the slab in flight, and of the column it opens (only loaded with a column's first slab)
-  d2 sr[NLD], sd[NLD], su[NLD];
+  tio2 sr[NLD], sd[NLD], su[NLD];
   double c_lr = 0.0, c_lt = 0.0, c_lai[NLAI], c_psi = 0.0, c_gp = 0.0, c_ga = 0.0;
   int c_kind = 0;
   const int c = blockIdx.x;
   auto fetch = [&](int k0) {
     const long long cb2 = (long long)c * nz * nb2;
-    const d2* __restrict__ R2 = reinterpret_cast<const d2*>(a.I_dr) + cb2;
-    const d2* __restrict__ D2 = reinterpret_cast<const d2*>(a.I_df_d) + cb2;
-    const d2* __restrict__ U2 = reinterpret_cast<const d2*>(a.I_df_u) + cb2;
+    const tio2* __restrict__ R2 = reinterpret_cast<const tio2*>(a.I_dr) + cb2;
+    const tio2* __restrict__ D2 = reinterpret_cast<const tio2*>(a.I_df_d) + cb2;
+    const tio2* __restrict__ U2 = reinterpret_cast<const tio2*>(a.I_df_u) + cb2;
     const int n2 = (min(LS, nl - k0) + 1) * nb2;
     const unsigned base = (unsigned)k0 * (unsigned)nb2;  // nz * nb < 2^31 (checked by the launcher)
 #pragma unroll
@@ -550,9 +560,9 @@ __global__ __launch_bounds__(64) void k_absorb_bandsum_l(EpiArgs a, int nbp) {
 #pragma unroll
       for (int i = 0; i < NLD; ++i)
         if (lane + 64 * i < n2) {
-          *reinterpret_cast<d2*>(slab + dst[i]) = sr[i];
-          *reinterpret_cast<d2*>(slab + SS + dst[i]) = sd[i];
-          *reinterpret_cast<d2*>(slab + 2 * SS + dst[i]) = su[i];
+          *reinterpret_cast<d2*>(slab + dst[i]) = __builtin_convertvector(sr[i], d2);
+          *reinterpret_cast<d2*>(slab + SS + dst[i]) = __builtin_convertvector(sd[i], d2);
+          *reinterpret_cast<d2*>(slab + 2 * SS + dst[i]) = __builtin_convertvector(su[i], d2);
         }
     }
     if (k0 == 0) {  // ... and the column it opens
@@ -623,8 +633,8 @@ __global__ __launch_bounds__(64) void k_absorb_bandsum_l(EpiArgs a, int nbp) {
 // k_absorb_bandsum_h: very narrow spectra (nb <= 32): a column per HALF wave (lane l of a
 // half owns band l), so a wave instruction serves two columns instead of leaving half of the lanes idle;
 // the reductions stay inside the halves (half_sum2).  Otherwise the same pass.
-template <int NBT, int CH, int NGT>
-__global__ __launch_bounds__(256) void k_absorb_bandsum_h(EpiArgs a, int wpb, int per_col) {
+template <typename TIO, int NBT, int CH, int NGT>
+__global__ __launch_bounds__(256) void k_absorb_bandsum_h(EpiArgsT<TIO> a, int wpb, int per_col) {
   extern __shared__ double lds[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, half = lane >> 5, l = lane & 31;
   const int c0 = 2 * (blockIdx.x * wpb + wave);
@@ -635,9 +645,9 @@ __global__ __launch_bounds__(256) void k_absorb_bandsum_h(EpiArgs a, int wpb, in
   double* raw = lds + (size_t)(2 * wave + half) * per_col;  // [nl][NGT][2]
   double* ends = raw + 2 * NGT * nl;                        // [2][NGT][2]
   const long long cb = (long long)c * nz * nb;
-  const double* __restrict__ R = a.I_dr + cb;
-  const double* __restrict__ D = a.I_df_d + cb;
-  const double* __restrict__ U = a.I_df_u + cb;
+  const TIO* __restrict__ R = a.I_dr + cb;
+  const TIO* __restrict__ D = a.I_df_d + cb;
+  const TIO* __restrict__ U = a.I_df_u + cb;
   int bi[NBT];
   double w[NBT][NGT], la[NBT], r0[NBT], d0[NBT], u0[NBT];
 #pragma unroll
@@ -646,7 +656,7 @@ __global__ __launch_bounds__(256) void k_absorb_bandsum_h(EpiArgs a, int wpb, in
     const bool act = b < nb;
     bi[i] = act ? b : 0;
     const long long ib = (long long)c * a.col_stride + bi[i];
-    la[i] = act ? 1 - (a.leaf_r[ib] + a.leaf_t[ib]) : 0.0;  // :584
+    la[i] = act ? 1 - ((double)a.leaf_r[ib] + (double)a.leaf_t[ib]) : 0.0;  // :584
 #pragma unroll
     for (int g = 0; g < NGT; ++g) w[i][g] = (g < ng && act) ? a.band_w[(long long)g * nb + bi[i]] : 0.0;
     r0[i] = R[bi[i]];
@@ -714,7 +724,10 @@ __global__ __launch_bounds__(256) void k_absorb_bandsum_h(EpiArgs a, int wpb, in
 // ------------------------------------------------------------------------------------------
 // Per-band layer absorption, model.py:573-647: the seven (nz-1, nb) arrays + laim, f_slm of the reference's
 // `Model.absorption` dict.  One workgroup per column, lanes over bands, previous level kept in registers.
-struct AbsArgs {
+// TIO = double | float: the three input profiles, the leaf optics and the seven outputs (crt_hip_absorb_f64 / _f32).  The arithmetic is
+// fp64 for both: a float output is the fp64 value rounded once.  laim and f_slm are fp64.
+template <typename TIO>
+struct AbsArgsT {
   int ncol, nb, nz;
   long long col_stride;
   const double* psi;
@@ -722,17 +735,18 @@ struct AbsArgs {
   const int32_t* g_kind;
   const double* g_param;
   const double* g_at_psi;
-  const double* leaf_r;
-  const double* leaf_t;
-  const double* I_dr;
-  const double* I_df_d;
-  const double* I_df_u;
-  double* o[7];  // aI, aI_df, aI_dr, aI_sh, aI_sl, aI_df_sl, aI_df_sh
+  const TIO* leaf_r;
+  const TIO* leaf_t;
+  const TIO* I_dr;
+  const TIO* I_df_d;
+  const TIO* I_df_u;
+  TIO* o[7];  // aI, aI_df, aI_dr, aI_sh, aI_sl, aI_df_sl, aI_df_sh
   double* laim;
   double* f_slm;
 };
 
-__global__ __launch_bounds__(256) void k_absorb(AbsArgs a) {
+template <typename TIO>
+__global__ __launch_bounds__(256) void k_absorb(AbsArgsT<TIO> a) {
   const int c = blockIdx.x;
   const int nz = a.nz, nb = a.nb;
   const double psi = a.psi[c];
@@ -743,7 +757,7 @@ __global__ __launch_bounds__(256) void k_absorb(AbsArgs a) {
   const long long cb = (long long)c * nz * nb;
   const long long cm = (long long)c * (nz - 1) * nb;
   for (int b = threadIdx.x; b < nb; b += 256) {
-    const double leaf_a = 1 - (a.leaf_r[(long long)c * a.col_stride + b] + a.leaf_t[(long long)c * a.col_stride + b]);  // :584
+    const double leaf_a = 1 - ((double)a.leaf_r[(long long)c * a.col_stride + b] + (double)a.leaf_t[(long long)c * a.col_stride + b]);  // :584
     double r0 = a.I_dr[cb + b], d0 = a.I_df_d[cb + b], u0 = a.I_df_u[cb + b];
     for (int k = 0; k < nz - 1; ++k) {
       const long long i1 = cb + (long long)(k + 1) * nb + b;
@@ -773,19 +787,25 @@ __global__ __launch_bounds__(256) void k_absorb(AbsArgs a) {
   }
 }
 
-// k_absorb_tile (even nb, 16-byte aligned arrays): a column's seven outputs are each ONE contiguous run of (nz-1) nb doubles, so
+// k_absorb_tile (nb a multiple of V = 16 / sizeof(TIO): 2 doubles or 4 floats; 16-byte aligned arrays): a column's seven outputs are each
+// ONE contiguous run of (nz-1) nb elements, so
 // the kernel walks the flat element index with 16 bytes per lane -- every wave store is a contiguous, line-aligned 1 KiB whatever nb
 // is (with lanes on bands a 300-band row starts and ends inside a 128-B line: 0.50 of the HBM peak).  The three input profiles go
 // through an LDS ring of T + 1 rows: each round loads T new rows (one contiguous run per array, 16 bytes per lane), the row on top
 // of the previous round stays where it is, so every input byte is read exactly once.  Level factors and (1 - r - t) come from LDS.
-__global__ __launch_bounds__(256) void k_absorb_tile(AbsArgs a, int T) {
+// The ring keeps the inputs as stored (TIO); the float form widens a piece to fp64 before any arithmetic.
+template <typename TIO>
+__global__ __launch_bounds__(256) void k_absorb_tile(AbsArgsT<TIO> a, int T) {
+  constexpr int V = 16 / sizeof(TIO), VS = V == 2 ? 1 : 2;  // elements per 16-byte piece, log2
+  typedef TIO vio __attribute__((ext_vector_type(V)));
+  typedef double d4 __attribute__((ext_vector_type(4)));
   extern __shared__ double lds[];
   const int c = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
-  const int nz = a.nz, nb = a.nb, nl = nz - 1, nb2 = nb >> 1, NS = T + 1;
+  const int nz = a.nz, nb = a.nb, nl = nz - 1, nb2 = nb >> VS, NS = T + 1;  // nb2: pieces per row
   double* fsl = lds;           // [nl]
   double* absd = lds + nl;     // [nl]
   double* la = lds + 2 * nl;   // [nb]
-  d2* ring = reinterpret_cast<d2*>(lds + 2 * nl + nb);  // [3][NS][nb2]
+  vio* ring = reinterpret_cast<vio*>(lds + 2 * nl + nb);  // [3][NS][nb2]
   const double psi = a.psi[c];
   const int kind = a.g_kind[c];
   const double G = (kind == CRT_G_TABLE) ? a.g_at_psi[c] : G_closed(kind, a.g_param ? a.g_param[c] : 0.0, cos(psi), sin(psi));
@@ -800,11 +820,11 @@ __global__ __launch_bounds__(256) void k_absorb_tile(AbsArgs a, int T) {
     a.f_slm[(long long)c * nl + k] = f;
   }
   for (int b = tid; b < nb; b += nthr)
-    la[b] = 1 - (a.leaf_r[(long long)c * a.col_stride + b] + a.leaf_t[(long long)c * a.col_stride + b]);  // :584
+    la[b] = 1 - ((double)a.leaf_r[(long long)c * a.col_stride + b] + (double)a.leaf_t[(long long)c * a.col_stride + b]);  // :584
   const long long cb = (long long)c * nz * nb, cm = (long long)c * nl * nb;
-  const d2* R2 = reinterpret_cast<const d2*>(a.I_dr + cb);
-  const d2* D2 = reinterpret_cast<const d2*>(a.I_df_d + cb);
-  const d2* U2 = reinterpret_cast<const d2*>(a.I_df_u + cb);
+  const vio* R2 = reinterpret_cast<const vio*>(a.I_dr + cb);
+  const vio* D2 = reinterpret_cast<const vio*>(a.I_df_d + cb);
+  const vio* U2 = reinterpret_cast<const vio*>(a.I_df_u + cb);
   const int dt = nthr / nb2, dp = nthr - dt * nb2;       // one round of the workgroup advances (dt rows, dp pairs)
   const int t00 = tid / nb2, p00 = tid - t00 * nb2;
   // row 0 of the column into slot 0
@@ -816,7 +836,7 @@ __global__ __launch_bounds__(256) void k_absorb_tile(AbsArgs a, int T) {
   int base = 0;  // ring slot of the row below the current chunk (level k0)
   for (int k0 = 0; k0 < nl; k0 += T) {
     const int nlev = min(T, nl - k0), n2 = nlev * nb2;
-    // rows k0+1 .. k0+nlev -> slots base+1 .. base+nlev (mod NS): one contiguous run of nlev * nb doubles per array
+    // rows k0+1 .. k0+nlev -> slots base+1 .. base+nlev (mod NS): one contiguous run of nlev * nb elements per array
     {
       const long long g0 = (long long)(k0 + 1) * nb2;
       int t = t00, p = p00;
@@ -838,38 +858,59 @@ __global__ __launch_bounds__(256) void k_absorb_tile(AbsArgs a, int T) {
     __syncthreads();
     {
       int t = t00, p = p00;
-      const long long o0 = (cm >> 1) + (long long)k0 * nb2;
+      const long long o0 = (cm >> VS) + (long long)k0 * nb2;
       for (int i2 = tid; i2 < n2; i2 += nthr) {
         int s0 = base + t;
         if (s0 >= NS) s0 -= NS;
         int s1 = s0 + 1;
         if (s1 >= NS) s1 -= NS;
         const int l0 = s0 * nb2 + p, l1 = s1 * nb2 + p;
-        const d2 r0 = ring[l0], r1 = ring[l1], d0 = ring[NS * nb2 + l0], d1 = ring[NS * nb2 + l1], u0 = ring[2 * NS * nb2 + l0],
-                 u1 = ring[2 * NS * nb2 + l1];
-        const double f = fsl[k0 + t], ab = absd[k0 + t];
-        const d2 l = reinterpret_cast<const d2*>(la)[p];
-        d2 av, adr, adf, sl, dsl, dsh;
-        av.x = r1.x - r0.x + d1.x - d0.x + u0.x - u1.x;   // :609
-        av.y = r1.y - r0.y + d1.y - d0.y + u0.y - u1.y;
-        adr.x = r1.x * ab * l.x;                          // :617-621
-        adr.y = r1.y * ab * l.y;
-        adf.x = av.x - adr.x;                             // :628
-        adf.y = av.y - adr.y;
-        dsl.x = adf.x * f;                                // :631-632
-        dsl.y = adf.y * f;
-        dsh.x = adf.x * (1 - f);
-        dsh.y = adf.y * (1 - f);
-        sl.x = dsl.x + adr.x;
-        sl.y = dsl.y + adr.y;
         const long long o = o0 + i2;
-        __builtin_nontemporal_store(av, reinterpret_cast<d2*>(a.o[0]) + o);
-        __builtin_nontemporal_store(adf, reinterpret_cast<d2*>(a.o[1]) + o);
-        __builtin_nontemporal_store(adr, reinterpret_cast<d2*>(a.o[2]) + o);
-        __builtin_nontemporal_store(dsh, reinterpret_cast<d2*>(a.o[3]) + o);
-        __builtin_nontemporal_store(sl, reinterpret_cast<d2*>(a.o[4]) + o);
-        __builtin_nontemporal_store(dsl, reinterpret_cast<d2*>(a.o[5]) + o);
-        __builtin_nontemporal_store(dsh, reinterpret_cast<d2*>(a.o[6]) + o);
+        if constexpr (V == 2) {
+          const d2 r0 = ring[l0], r1 = ring[l1], d0 = ring[NS * nb2 + l0], d1 = ring[NS * nb2 + l1], u0 = ring[2 * NS * nb2 + l0],
+                   u1 = ring[2 * NS * nb2 + l1];
+          const double f = fsl[k0 + t], ab = absd[k0 + t];
+          const d2 l = reinterpret_cast<const d2*>(la)[p];
+          d2 av, adr, adf, sl, dsl, dsh;
+          av.x = r1.x - r0.x + d1.x - d0.x + u0.x - u1.x;   // :609
+          av.y = r1.y - r0.y + d1.y - d0.y + u0.y - u1.y;
+          adr.x = r1.x * ab * l.x;                          // :617-621
+          adr.y = r1.y * ab * l.y;
+          adf.x = av.x - adr.x;                             // :628
+          adf.y = av.y - adr.y;
+          dsl.x = adf.x * f;                                // :631-632
+          dsl.y = adf.y * f;
+          dsh.x = adf.x * (1 - f);
+          dsh.y = adf.y * (1 - f);
+          sl.x = dsl.x + adr.x;
+          sl.y = dsl.y + adr.y;
+          __builtin_nontemporal_store(av, reinterpret_cast<d2*>(a.o[0]) + o);
+          __builtin_nontemporal_store(adf, reinterpret_cast<d2*>(a.o[1]) + o);
+          __builtin_nontemporal_store(adr, reinterpret_cast<d2*>(a.o[2]) + o);
+          __builtin_nontemporal_store(dsh, reinterpret_cast<d2*>(a.o[3]) + o);
+          __builtin_nontemporal_store(sl, reinterpret_cast<d2*>(a.o[4]) + o);
+          __builtin_nontemporal_store(dsl, reinterpret_cast<d2*>(a.o[5]) + o);
+          __builtin_nontemporal_store(dsh, reinterpret_cast<d2*>(a.o[6]) + o);
+        } else {  // four floats per piece: widened first, then the same expressions (d4 lanes = bands 4p .. 4p+3)
+          const d4 r0 = __builtin_convertvector(ring[l0], d4), r1 = __builtin_convertvector(ring[l1], d4);
+          const d4 d0 = __builtin_convertvector(ring[NS * nb2 + l0], d4), d1 = __builtin_convertvector(ring[NS * nb2 + l1], d4);
+          const d4 u0 = __builtin_convertvector(ring[2 * NS * nb2 + l0], d4), u1 = __builtin_convertvector(ring[2 * NS * nb2 + l1], d4);
+          const double f = fsl[k0 + t], ab = absd[k0 + t];
+          const d2 la0 = reinterpret_cast<const d2*>(la)[2 * p], la1 = reinterpret_cast<const d2*>(la)[2 * p + 1];
+          const d4 l = {la0.x, la0.y, la1.x, la1.y};
+          const d4 av = r1 - r0 + d1 - d0 + u0 - u1;      // :609
+          const d4 adr = r1 * ab * l;                     // :617-621
+          const d4 adf = av - adr;                        // :628
+          const d4 dsl = adf * f, dsh = adf * (1 - f);    // :631-632
+          const d4 sl = dsl + adr;
+          __builtin_nontemporal_store(__builtin_convertvector(av, vio), reinterpret_cast<vio*>(a.o[0]) + o);
+          __builtin_nontemporal_store(__builtin_convertvector(adf, vio), reinterpret_cast<vio*>(a.o[1]) + o);
+          __builtin_nontemporal_store(__builtin_convertvector(adr, vio), reinterpret_cast<vio*>(a.o[2]) + o);
+          __builtin_nontemporal_store(__builtin_convertvector(dsh, vio), reinterpret_cast<vio*>(a.o[3]) + o);
+          __builtin_nontemporal_store(__builtin_convertvector(sl, vio), reinterpret_cast<vio*>(a.o[4]) + o);
+          __builtin_nontemporal_store(__builtin_convertvector(dsl, vio), reinterpret_cast<vio*>(a.o[5]) + o);
+          __builtin_nontemporal_store(__builtin_convertvector(dsh, vio), reinterpret_cast<vio*>(a.o[6]) + o);
+        }
         p += dp;
         t += dt;
         if (p >= nb2) {
@@ -959,6 +1000,201 @@ bool scheme_ok(int s) { return s >= 0 && s < CRT_NUM_SCHEMES; }
 }  // namespace crt
 
 using namespace crt;
+
+// the epilogue launchers of both storage types (TIO = element type of the profiles and leaf optics): the kernel choice depends on
+// the shape and on alignment only, so an f32 call takes the form -- and the summation order -- of the f64 call on the upcast profiles
+template <typename TIO>
+static int bandsum_impl(const crt_columns* cols, int32_t nb, int64_t col_stride, const TIO* leaf_r, const TIO* leaf_t, const TIO* I_dr,
+                        const TIO* I_df_d, const TIO* I_df_u, const double* band_w, int32_t ngroup, const crt_bandsum_out* out,
+                        crt_stream_t stream) {
+  if (!cols || !I_dr || !I_df_d || !I_df_u || !band_w || !out || !out->aI || !out->aI_sl || !out->aI_sh) return CRT_ERR_BAD_ARG;
+  double *aI = out->aI, *aI_sl = out->aI_sl, *aI_sh = out->aI_sh, *totals = out->totals;
+  // the optional outputs come all together or not at all: the direct-beam part of the absorption + the five level profiles
+  const int nopt = (out->aI_dr != nullptr) + (out->I_dr != nullptr) + (out->I_df_d != nullptr) + (out->I_df_u != nullptr) + (out->F != nullptr) +
+                   (out->I_d != nullptr);
+  if (nopt != 0 && nopt != 6) return CRT_ERR_BAD_ARG;
+  const bool prof = nopt == 6;
+  if (cols->ncol <= 0 || cols->nz < 2 || nb <= 0 || ngroup <= 0 || ngroup > MAXG) return CRT_ERR_BAD_ARG;
+  if (!cols->psi || !cols->lai || !cols->g_kind || !leaf_r || !leaf_t) return CRT_ERR_BAD_ARG;
+  EpiArgsT<TIO> a;
+  a.ncol = cols->ncol;
+  a.nb = nb;
+  a.nz = cols->nz;
+  a.ngroup = ngroup;
+  a.col_stride = col_stride;
+  a.psi = cols->psi;
+  a.lai = cols->lai;
+  a.g_kind = cols->g_kind;
+  a.g_param = cols->g_param;
+  a.g_at_psi = cols->g_at_psi;
+  a.leaf_r = leaf_r;
+  a.leaf_t = leaf_t;
+  a.I_dr = I_dr;
+  a.I_df_d = I_df_d;
+  a.I_df_u = I_df_u;
+  a.band_w = band_w;
+  a.aI = aI;
+  a.aI_sl = aI_sl;
+  a.aI_sh = aI_sh;
+  a.totals = totals;
+  a.aI_dr = out->aI_dr;
+  a.L_dr = out->I_dr;
+  a.L_dn = out->I_df_d;
+  a.L_up = out->I_df_u;
+  a.L_F = out->F;
+  a.L_Id = out->I_d;
+  // measured (tools/epilogue_bench.py): nb = 20: 1.15 ms per wave-column vs 0.85 ms per half-wave-column; nb = 38: 1.11 vs 1.26 (the second band
+  // slot of a half is nearly empty and doubles the per-band work) -> halves only up to 32 bands
+  // k_absorb_bandsum_l moves pieces of two bands (16 bytes of double, 8 of float): the profiles must be aligned to one piece
+  const bool aligned16 = ((reinterpret_cast<uintptr_t>(I_dr) | reinterpret_cast<uintptr_t>(I_df_d) | reinterpret_cast<uintptr_t>(I_df_u)) &
+                          (2 * sizeof(TIO) - 1)) == 0;
+  // measured (tools/bandsum_shapes.py, 9.1 GB of profiles): lanes over layers vs lanes over bands (one band per lane, next chunk prefetched):
+  //   1e5 x 34 x 100: 1.69 vs 1.83 ms;  1e5 x 38 x 100: 1.89 vs 2.09;  1e5 x 48 x 80: 1.85 vs 1.88;  1e5 x 64 x 60: 2.02 vs 1.66 -> up to 48 bands
+  // (with the level profiles requested the band-lane kernels below serve every width: they hold each level's values in registers anyway)
+  if (!prof && a.nb > 32 && a.nb <= 48 && a.nb % 2 == 0 && aligned16 && a.nz <= 257 && (long long)a.nz * a.nb < (1ll << 31)) {  // lanes over layers
+    const int nl = a.nz - 1;
+    const int ngt = a.ngroup == 1 ? 1 : a.ngroup <= 3 ? 3 : 4;
+    const int nbp = (a.nb % 4 == 2) ? a.nb : a.nb + 2;
+    const size_t shl = (size_t)(3 * 17 * nbp + (ngt + 1) * nbp + 2 * ngt * nl + 4 * ngt + a.nz + 2 * nl) * sizeof(double);
+    if (shl <= 64 * 1024) {
+      hipStream_t sl = static_cast<hipStream_t>(stream);
+      const dim3 gl(a.ncol);
+      if (ngt == 1) hipLaunchKernelGGL((k_absorb_bandsum_l<TIO, 1>), gl, dim3(64), shl, sl, a, nbp);
+      else if (ngt == 3) hipLaunchKernelGGL((k_absorb_bandsum_l<TIO, 3>), gl, dim3(64), shl, sl, a, nbp);
+      else hipLaunchKernelGGL((k_absorb_bandsum_l<TIO, 4>), gl, dim3(64), shl, sl, a, nbp);
+      return hipGetLastError() == hipSuccess ? CRT_OK : CRT_ERR_LAUNCH;
+    }
+  }
+  if (!prof && a.nb <= 32 && (long long)a.nz * a.nb < (1ll << 31)) {  // a column per half wave
+    const int nl = a.nz - 1;
+    const int ngt = a.ngroup == 1 ? 1 : a.ngroup <= 3 ? 3 : 4;
+    const int per_col = 2 * ngt * nl + 4 * ngt;
+    int wpb = 4;
+    while (wpb > 1 && (size_t)2 * wpb * per_col * sizeof(double) > 60 * 1024) wpb >>= 1;
+    const size_t shw = (size_t)2 * wpb * per_col * sizeof(double);
+    if (shw <= 64 * 1024) {
+      const dim3 grid((a.ncol + 2 * wpb - 1) / (2 * wpb)), block(64 * wpb);
+      hipStream_t sw = static_cast<hipStream_t>(stream);
+      auto launch = [&](auto ngt_c) {
+        constexpr int NGT = decltype(ngt_c)::value;
+        if (a.nb <= 32) hipLaunchKernelGGL((k_absorb_bandsum_h<TIO, 1, 4, NGT>), grid, block, shw, sw, a, wpb, per_col);
+        else hipLaunchKernelGGL((k_absorb_bandsum_h<TIO, 2, 4, NGT>), grid, block, shw, sw, a, wpb, per_col);
+      };
+      if (a.ngroup == 1) launch(std::integral_constant<int, 1>{});
+      else if (a.ngroup <= 3) launch(std::integral_constant<int, 3>{});
+      else launch(std::integral_constant<int, 4>{});
+      return hipGetLastError() == hipSuccess ? CRT_OK : CRT_ERR_LAUNCH;
+    }
+  }
+  if (a.nb <= 512 && (long long)a.nz * a.nb < (1ll << 31)) {  // one wave per column
+    const int nl = a.nz - 1;
+    const int ngt = a.ngroup == 1 ? 1 : a.ngroup <= 3 ? 3 : 4;
+    const int per_wave = 2 * ngt * nl + 4 * ngt + (prof ? 3 * ngt * a.nz : 0);
+    int wpb = 4;
+    while (wpb > 1 && (size_t)wpb * per_wave * sizeof(double) > 60 * 1024) wpb >>= 1;
+    const size_t shw = (size_t)wpb * per_wave * sizeof(double);
+    if (shw <= 64 * 1024) {
+      const int nbt = (a.nb + 63) / 64;
+      const dim3 grid((a.ncol + wpb - 1) / wpb), block(64 * wpb);
+      hipStream_t sw = static_cast<hipStream_t>(stream);
+      auto launch_p = [&](auto ngt) {  // with the level profiles (chunks of two levels: the extra sums live in registers too)
+        constexpr int NGT = decltype(ngt)::value;
+        switch (nbt) {
+          case 1: hipLaunchKernelGGL((k_absorb_bandsum_w<TIO, 1, 2, NGT, false, true>), grid, block, shw, sw, a, wpb, per_wave); break;
+          case 2: hipLaunchKernelGGL((k_absorb_bandsum_w<TIO, 2, 2, NGT, false, true>), grid, block, shw, sw, a, wpb, per_wave); break;
+          case 3: hipLaunchKernelGGL((k_absorb_bandsum_w<TIO, 3, 2, NGT, false, true>), grid, block, shw, sw, a, wpb, per_wave); break;
+          case 4: hipLaunchKernelGGL((k_absorb_bandsum_w<TIO, 4, 2, NGT, false, true>), grid, block, shw, sw, a, wpb, per_wave); break;
+          case 5: hipLaunchKernelGGL((k_absorb_bandsum_w<TIO, 5, 2, NGT, false, true>), grid, block, shw, sw, a, wpb, per_wave); break;
+          case 6: hipLaunchKernelGGL((k_absorb_bandsum_w<TIO, 6, 1, NGT, false, true>), grid, block, shw, sw, a, wpb, per_wave); break;
+          default: hipLaunchKernelGGL((k_absorb_bandsum_w<TIO, 8, 1, NGT, false, true>), grid, block, shw, sw, a, wpb, per_wave); break;
+        }
+      };
+      if (prof) {
+        if (a.ngroup == 1) launch_p(std::integral_constant<int, 1>{});
+        else if (a.ngroup <= 3) launch_p(std::integral_constant<int, 3>{});
+        else launch_p(std::integral_constant<int, 4>{});
+        return hipGetLastError() == hipSuccess ? CRT_OK : CRT_ERR_LAUNCH;
+      }
+      auto launch = [&](auto ngt) {
+        constexpr int NGT = decltype(ngt)::value;
+        switch (nbt) {
+          case 1: hipLaunchKernelGGL((k_absorb_bandsum_w<TIO, 1, 4, NGT, true>), grid, block, shw, sw, a, wpb, per_wave); break;
+          case 2: hipLaunchKernelGGL((k_absorb_bandsum_w<TIO, 2, 4, NGT>), grid, block, shw, sw, a, wpb, per_wave); break;
+          case 3: hipLaunchKernelGGL((k_absorb_bandsum_w<TIO, 3, 4, NGT>), grid, block, shw, sw, a, wpb, per_wave); break;
+          case 4: hipLaunchKernelGGL((k_absorb_bandsum_w<TIO, 4, 2, NGT>), grid, block, shw, sw, a, wpb, per_wave); break;
+          case 5: hipLaunchKernelGGL((k_absorb_bandsum_w<TIO, 5, 2, NGT>), grid, block, shw, sw, a, wpb, per_wave); break;
+          case 6: hipLaunchKernelGGL((k_absorb_bandsum_w<TIO, 6, 2, NGT>), grid, block, shw, sw, a, wpb, per_wave); break;
+          default: hipLaunchKernelGGL((k_absorb_bandsum_w<TIO, 8, 2, NGT>), grid, block, shw, sw, a, wpb, per_wave); break;
+        }
+      };
+      if (a.ngroup == 1) launch(std::integral_constant<int, 1>{});
+      else if (a.ngroup <= 3) launch(std::integral_constant<int, 3>{});
+      else launch(std::integral_constant<int, 4>{});
+      return hipGetLastError() == hipSuccess ? CRT_OK : CRT_ERR_LAUNCH;
+    }
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int b0 = 0; b0 < a.nb; b0 += 1024) {  // one launch per 1024 bands (the usual case: one)
+    const int nbs = std::min(1024, a.nb - b0);
+    const int nthr = ((nbs + 63) / 64) * 64;
+    const size_t sh = ((size_t)2 * BS_CH * (nthr / 64) * (prof ? 5 : 2) * MAXG + (size_t)(nthr / 64) * (4 + (prof ? 3 : 0)) * MAXG) * sizeof(double);
+    if (prof) {
+      if (nthr <= 256) hipLaunchKernelGGL((k_absorb_bandsum<TIO, 256, true>), dim3(a.ncol), dim3(nthr), sh, s, a, b0, nbs, b0 > 0);
+      else if (nthr <= 512) hipLaunchKernelGGL((k_absorb_bandsum<TIO, 512, true>), dim3(a.ncol), dim3(nthr), sh, s, a, b0, nbs, b0 > 0);
+      else hipLaunchKernelGGL((k_absorb_bandsum<TIO, 1024, true>), dim3(a.ncol), dim3(nthr), sh, s, a, b0, nbs, b0 > 0);
+    } else {
+      if (nthr <= 256) hipLaunchKernelGGL((k_absorb_bandsum<TIO, 256, false>), dim3(a.ncol), dim3(nthr), sh, s, a, b0, nbs, b0 > 0);
+      else if (nthr <= 512) hipLaunchKernelGGL((k_absorb_bandsum<TIO, 512, false>), dim3(a.ncol), dim3(nthr), sh, s, a, b0, nbs, b0 > 0);
+      else hipLaunchKernelGGL((k_absorb_bandsum<TIO, 1024, false>), dim3(a.ncol), dim3(nthr), sh, s, a, b0, nbs, b0 > 0);
+    }
+  }
+  return hipGetLastError() == hipSuccess ? CRT_OK : CRT_ERR_LAUNCH;
+}
+
+template <typename TIO>
+static int absorb_impl(const crt_columns* cols, int32_t nb, int64_t col_stride, const TIO* leaf_r, const TIO* leaf_t, const TIO* I_dr,
+                       const TIO* I_df_d, const TIO* I_df_u, TIO* const* out7, double* laim, double* f_slm, crt_stream_t stream) {
+  if (!cols || !I_dr || !I_df_d || !I_df_u || !out7 || !laim || !f_slm) return CRT_ERR_BAD_ARG;
+  if (cols->ncol <= 0 || cols->nz < 2 || nb <= 0) return CRT_ERR_BAD_ARG;
+  if (!cols->psi || !cols->lai || !cols->g_kind || !leaf_r || !leaf_t) return CRT_ERR_BAD_ARG;
+  AbsArgsT<TIO> a;
+  a.ncol = cols->ncol;
+  a.nb = nb;
+  a.nz = cols->nz;
+  a.col_stride = col_stride;
+  a.psi = cols->psi;
+  a.lai = cols->lai;
+  a.g_kind = cols->g_kind;
+  a.g_param = cols->g_param;
+  a.g_at_psi = cols->g_at_psi;
+  a.leaf_r = leaf_r;
+  a.leaf_t = leaf_t;
+  a.I_dr = I_dr;
+  a.I_df_d = I_df_d;
+  a.I_df_u = I_df_u;
+  for (int i = 0; i < 7; ++i) {
+    if (!out7[i]) return CRT_ERR_BAD_ARG;
+    a.o[i] = out7[i];
+  }
+  a.laim = laim;
+  a.f_slm = f_slm;
+  constexpr int V = 16 / sizeof(TIO);  // elements per 16-byte piece of k_absorb_tile
+  bool flat = a.nb % V == 0 && a.col_stride % V == 0 && (long long)a.nz * a.nb < (1ll << 31);
+  const void* ptrs[] = {I_dr, I_df_d, I_df_u, a.o[0], a.o[1], a.o[2], a.o[3], a.o[4], a.o[5], a.o[6]};
+  for (const void* q : ptrs)
+    if (reinterpret_cast<uintptr_t>(q) & 15) flat = false;
+  // ring of T + 1 rows of the three inputs (TIO): T rows per round, as many as keep the workgroup at ~40 KB of LDS (4 per CU).  The
+  // per-band outputs involve no reduction, so the float form may take the longer rounds its 4-byte rows allow.
+  const size_t fixed = (size_t)(2 * (a.nz - 1) + a.nb) * sizeof(double);
+  int T = (int)((40 * 1024 - std::min<size_t>(fixed, 40 * 1024)) / (3 * (size_t)a.nb * sizeof(TIO))) - 1;
+  T = std::max(1, std::min(T, std::min(16, a.nz - 1)));
+  const size_t shf = fixed + (size_t)3 * (T + 1) * a.nb * sizeof(TIO);
+  if (flat && a.nb >= V && shf <= 64 * 1024)
+    hipLaunchKernelGGL((k_absorb_tile<TIO>), dim3(a.ncol), dim3(256), shf, static_cast<hipStream_t>(stream), a, T);
+  else
+    hipLaunchKernelGGL((k_absorb<TIO>), dim3(a.ncol), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  return hipGetLastError() == hipSuccess ? CRT_OK : CRT_ERR_LAUNCH;
+}
 
 extern "C" {
 
@@ -1142,146 +1378,16 @@ CRT_ENTRY32(crt_hip_zq_pa_f32, CRT_SCHEME_ZQ_PA)
 
 int crt_hip_absorb_bandsum2_f64(const crt_columns* cols, const crt_bands* bands, const double* I_dr, const double* I_df_d,
                                 const double* I_df_u, const double* band_w, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream) {
-  if (!cols || !bands || !I_dr || !I_df_d || !I_df_u || !band_w || !out || !out->aI || !out->aI_sl || !out->aI_sh) return CRT_ERR_BAD_ARG;
-  double *aI = out->aI, *aI_sl = out->aI_sl, *aI_sh = out->aI_sh, *totals = out->totals;
-  // the optional outputs come all together or not at all: the direct-beam part of the absorption + the five level profiles
-  const int nopt = (out->aI_dr != nullptr) + (out->I_dr != nullptr) + (out->I_df_d != nullptr) + (out->I_df_u != nullptr) + (out->F != nullptr) +
-                   (out->I_d != nullptr);
-  if (nopt != 0 && nopt != 6) return CRT_ERR_BAD_ARG;
-  const bool prof = nopt == 6;
-  if (cols->ncol <= 0 || cols->nz < 2 || bands->nb <= 0 || ngroup <= 0 || ngroup > MAXG) return CRT_ERR_BAD_ARG;
-  if (!cols->psi || !cols->lai || !cols->g_kind || !bands->leaf_r || !bands->leaf_t) return CRT_ERR_BAD_ARG;
-  EpiArgs a;
-  a.ncol = cols->ncol;
-  a.nb = bands->nb;
-  a.nz = cols->nz;
-  a.ngroup = ngroup;
-  a.col_stride = bands->col_stride;
-  a.psi = cols->psi;
-  a.lai = cols->lai;
-  a.g_kind = cols->g_kind;
-  a.g_param = cols->g_param;
-  a.g_at_psi = cols->g_at_psi;
-  a.leaf_r = bands->leaf_r;
-  a.leaf_t = bands->leaf_t;
-  a.I_dr = I_dr;
-  a.I_df_d = I_df_d;
-  a.I_df_u = I_df_u;
-  a.band_w = band_w;
-  a.aI = aI;
-  a.aI_sl = aI_sl;
-  a.aI_sh = aI_sh;
-  a.totals = totals;
-  a.aI_dr = out->aI_dr;
-  a.L_dr = out->I_dr;
-  a.L_dn = out->I_df_d;
-  a.L_up = out->I_df_u;
-  a.L_F = out->F;
-  a.L_Id = out->I_d;
-  // measured (tools/epilogue_bench.py): nb = 20: 1.15 ms per wave-column vs 0.85 ms per half-wave-column; nb = 38: 1.11 vs 1.26 (the second band
-  // slot of a half is nearly empty and doubles the per-band work) -> halves only up to 32 bands
-  const bool aligned16 = ((reinterpret_cast<uintptr_t>(I_dr) | reinterpret_cast<uintptr_t>(I_df_d) | reinterpret_cast<uintptr_t>(I_df_u)) & 15) == 0;
-  // measured (tools/bandsum_shapes.py, 9.1 GB of profiles): lanes over layers vs lanes over bands (one band per lane, next chunk prefetched):
-  //   1e5 x 34 x 100: 1.69 vs 1.83 ms;  1e5 x 38 x 100: 1.89 vs 2.09;  1e5 x 48 x 80: 1.85 vs 1.88;  1e5 x 64 x 60: 2.02 vs 1.66 -> up to 48 bands
-  // (with the level profiles requested the band-lane kernels below serve every width: they hold each level's values in registers anyway)
-  if (!prof && a.nb > 32 && a.nb <= 48 && a.nb % 2 == 0 && aligned16 && a.nz <= 257 && (long long)a.nz * a.nb < (1ll << 31)) {  // lanes over layers
-    const int nl = a.nz - 1;
-    const int ngt = a.ngroup == 1 ? 1 : a.ngroup <= 3 ? 3 : 4;
-    const int nbp = (a.nb % 4 == 2) ? a.nb : a.nb + 2;
-    const size_t shl = (size_t)(3 * 17 * nbp + (ngt + 1) * nbp + 2 * ngt * nl + 4 * ngt + a.nz + 2 * nl) * sizeof(double);
-    if (shl <= 64 * 1024) {
-      hipStream_t sl = static_cast<hipStream_t>(stream);
-      const dim3 gl(a.ncol);
-      if (ngt == 1) hipLaunchKernelGGL((k_absorb_bandsum_l<1>), gl, dim3(64), shl, sl, a, nbp);
-      else if (ngt == 3) hipLaunchKernelGGL((k_absorb_bandsum_l<3>), gl, dim3(64), shl, sl, a, nbp);
-      else hipLaunchKernelGGL((k_absorb_bandsum_l<4>), gl, dim3(64), shl, sl, a, nbp);
-      return hipGetLastError() == hipSuccess ? CRT_OK : CRT_ERR_LAUNCH;
-    }
-  }
-  if (!prof && a.nb <= 32 && (long long)a.nz * a.nb < (1ll << 31)) {  // a column per half wave
-    const int nl = a.nz - 1;
-    const int ngt = a.ngroup == 1 ? 1 : a.ngroup <= 3 ? 3 : 4;
-    const int per_col = 2 * ngt * nl + 4 * ngt;
-    int wpb = 4;
-    while (wpb > 1 && (size_t)2 * wpb * per_col * sizeof(double) > 60 * 1024) wpb >>= 1;
-    const size_t shw = (size_t)2 * wpb * per_col * sizeof(double);
-    if (shw <= 64 * 1024) {
-      const dim3 grid((a.ncol + 2 * wpb - 1) / (2 * wpb)), block(64 * wpb);
-      hipStream_t sw = static_cast<hipStream_t>(stream);
-      auto launch = [&](auto ngt_c) {
-        constexpr int NGT = decltype(ngt_c)::value;
-        if (a.nb <= 32) hipLaunchKernelGGL((k_absorb_bandsum_h<1, 4, NGT>), grid, block, shw, sw, a, wpb, per_col);
-        else hipLaunchKernelGGL((k_absorb_bandsum_h<2, 4, NGT>), grid, block, shw, sw, a, wpb, per_col);
-      };
-      if (a.ngroup == 1) launch(std::integral_constant<int, 1>{});
-      else if (a.ngroup <= 3) launch(std::integral_constant<int, 3>{});
-      else launch(std::integral_constant<int, 4>{});
-      return hipGetLastError() == hipSuccess ? CRT_OK : CRT_ERR_LAUNCH;
-    }
-  }
-  if (a.nb <= 512 && (long long)a.nz * a.nb < (1ll << 31)) {  // one wave per column
-    const int nl = a.nz - 1;
-    const int ngt = a.ngroup == 1 ? 1 : a.ngroup <= 3 ? 3 : 4;
-    const int per_wave = 2 * ngt * nl + 4 * ngt + (prof ? 3 * ngt * a.nz : 0);
-    int wpb = 4;
-    while (wpb > 1 && (size_t)wpb * per_wave * sizeof(double) > 60 * 1024) wpb >>= 1;
-    const size_t shw = (size_t)wpb * per_wave * sizeof(double);
-    if (shw <= 64 * 1024) {
-      const int nbt = (a.nb + 63) / 64;
-      const dim3 grid((a.ncol + wpb - 1) / wpb), block(64 * wpb);
-      hipStream_t sw = static_cast<hipStream_t>(stream);
-      auto launch_p = [&](auto ngt) {  // with the level profiles (chunks of two levels: the extra sums live in registers too)
-        constexpr int NGT = decltype(ngt)::value;
-        switch (nbt) {
-          case 1: hipLaunchKernelGGL((k_absorb_bandsum_w<1, 2, NGT, false, true>), grid, block, shw, sw, a, wpb, per_wave); break;
-          case 2: hipLaunchKernelGGL((k_absorb_bandsum_w<2, 2, NGT, false, true>), grid, block, shw, sw, a, wpb, per_wave); break;
-          case 3: hipLaunchKernelGGL((k_absorb_bandsum_w<3, 2, NGT, false, true>), grid, block, shw, sw, a, wpb, per_wave); break;
-          case 4: hipLaunchKernelGGL((k_absorb_bandsum_w<4, 2, NGT, false, true>), grid, block, shw, sw, a, wpb, per_wave); break;
-          case 5: hipLaunchKernelGGL((k_absorb_bandsum_w<5, 2, NGT, false, true>), grid, block, shw, sw, a, wpb, per_wave); break;
-          case 6: hipLaunchKernelGGL((k_absorb_bandsum_w<6, 1, NGT, false, true>), grid, block, shw, sw, a, wpb, per_wave); break;
-          default: hipLaunchKernelGGL((k_absorb_bandsum_w<8, 1, NGT, false, true>), grid, block, shw, sw, a, wpb, per_wave); break;
-        }
-      };
-      if (prof) {
-        if (a.ngroup == 1) launch_p(std::integral_constant<int, 1>{});
-        else if (a.ngroup <= 3) launch_p(std::integral_constant<int, 3>{});
-        else launch_p(std::integral_constant<int, 4>{});
-        return hipGetLastError() == hipSuccess ? CRT_OK : CRT_ERR_LAUNCH;
-      }
-      auto launch = [&](auto ngt) {
-        constexpr int NGT = decltype(ngt)::value;
-        switch (nbt) {
-          case 1: hipLaunchKernelGGL((k_absorb_bandsum_w<1, 4, NGT, true>), grid, block, shw, sw, a, wpb, per_wave); break;
-          case 2: hipLaunchKernelGGL((k_absorb_bandsum_w<2, 4, NGT>), grid, block, shw, sw, a, wpb, per_wave); break;
-          case 3: hipLaunchKernelGGL((k_absorb_bandsum_w<3, 4, NGT>), grid, block, shw, sw, a, wpb, per_wave); break;
-          case 4: hipLaunchKernelGGL((k_absorb_bandsum_w<4, 2, NGT>), grid, block, shw, sw, a, wpb, per_wave); break;
-          case 5: hipLaunchKernelGGL((k_absorb_bandsum_w<5, 2, NGT>), grid, block, shw, sw, a, wpb, per_wave); break;
-          case 6: hipLaunchKernelGGL((k_absorb_bandsum_w<6, 2, NGT>), grid, block, shw, sw, a, wpb, per_wave); break;
-          default: hipLaunchKernelGGL((k_absorb_bandsum_w<8, 2, NGT>), grid, block, shw, sw, a, wpb, per_wave); break;
-        }
-      };
-      if (a.ngroup == 1) launch(std::integral_constant<int, 1>{});
-      else if (a.ngroup <= 3) launch(std::integral_constant<int, 3>{});
-      else launch(std::integral_constant<int, 4>{});
-      return hipGetLastError() == hipSuccess ? CRT_OK : CRT_ERR_LAUNCH;
-    }
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  for (int b0 = 0; b0 < a.nb; b0 += 1024) {  // one launch per 1024 bands (the usual case: one)
-    const int nbs = std::min(1024, a.nb - b0);
-    const int nthr = ((nbs + 63) / 64) * 64;
-    const size_t sh = ((size_t)2 * BS_CH * (nthr / 64) * (prof ? 5 : 2) * MAXG + (size_t)(nthr / 64) * (4 + (prof ? 3 : 0)) * MAXG) * sizeof(double);
-    if (prof) {
-      if (nthr <= 256) hipLaunchKernelGGL((k_absorb_bandsum<256, true>), dim3(a.ncol), dim3(nthr), sh, s, a, b0, nbs, b0 > 0);
-      else if (nthr <= 512) hipLaunchKernelGGL((k_absorb_bandsum<512, true>), dim3(a.ncol), dim3(nthr), sh, s, a, b0, nbs, b0 > 0);
-      else hipLaunchKernelGGL((k_absorb_bandsum<1024, true>), dim3(a.ncol), dim3(nthr), sh, s, a, b0, nbs, b0 > 0);
-    } else {
-      if (nthr <= 256) hipLaunchKernelGGL((k_absorb_bandsum<256, false>), dim3(a.ncol), dim3(nthr), sh, s, a, b0, nbs, b0 > 0);
-      else if (nthr <= 512) hipLaunchKernelGGL((k_absorb_bandsum<512, false>), dim3(a.ncol), dim3(nthr), sh, s, a, b0, nbs, b0 > 0);
-      else hipLaunchKernelGGL((k_absorb_bandsum<1024, false>), dim3(a.ncol), dim3(nthr), sh, s, a, b0, nbs, b0 > 0);
-    }
-  }
-  return hipGetLastError() == hipSuccess ? CRT_OK : CRT_ERR_LAUNCH;
+  if (!bands) return CRT_ERR_BAD_ARG;
+  return bandsum_impl<double>(cols, bands->nb, bands->col_stride, bands->leaf_r, bands->leaf_t, I_dr, I_df_d, I_df_u, band_w, ngroup, out,
+                              stream);
+}
+
+int crt_hip_absorb_bandsum2_f32(const crt_columns* cols, const crt_bands_f32* bands, const float* I_dr, const float* I_df_d,
+                                const float* I_df_u, const double* band_w, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream) {
+  if (!bands) return CRT_ERR_BAD_ARG;
+  return bandsum_impl<float>(cols, bands->nb, bands->col_stride, bands->leaf_r, bands->leaf_t, I_dr, I_df_d, I_df_u, band_w, ngroup, out,
+                             stream);
 }
 
 int crt_hip_absorb_bandsum_f64(const crt_columns* cols, const crt_bands* bands, const double* I_dr, const double* I_df_d,
@@ -1295,9 +1401,20 @@ int crt_hip_absorb_bandsum_f64(const crt_columns* cols, const crt_bands* bands, 
   return crt_hip_absorb_bandsum2_f64(cols, bands, I_dr, I_df_d, I_df_u, band_w, ngroup, &o, stream);
 }
 
-int crt_hip_integrated2_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts,
-                            const double* band_w, int32_t ngroup, const crt_bandsum_out* out, void* workspace, size_t workspace_bytes,
-                            crt_stream_t stream) {
+int crt_hip_absorb_bandsum_f32(const crt_columns* cols, const crt_bands_f32* bands, const float* I_dr, const float* I_df_d,
+                               const float* I_df_u, const double* band_w, int32_t ngroup, double* aI, double* aI_sl,
+                               double* aI_sh, double* totals, crt_stream_t stream) {
+  crt_bandsum_out o = {};
+  o.aI = aI;
+  o.aI_sl = aI_sl;
+  o.aI_sh = aI_sh;
+  o.totals = totals;
+  return crt_hip_absorb_bandsum2_f32(cols, bands, I_dr, I_df_d, I_df_u, band_w, ngroup, &o, stream);
+}
+
+// f32: crt_bands_f32 has the layout of crt_bands (crt_hip_solve_f32); the fused kernels read the spectra as TIO = float
+static int integrated_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const double* band_w,
+                           int32_t ngroup, const crt_bandsum_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream, int f32) {
   if (!band_w || !out || !out->aI || !out->aI_sl || !out->aI_sh || ngroup <= 0 || ngroup > INT_MAXG || !cols) return CRT_ERR_BAD_ARG;
   const int nopt = (out->aI_dr != nullptr) + (out->I_dr != nullptr) + (out->I_df_d != nullptr) + (out->I_df_u != nullptr) + (out->F != nullptr) +
                    (out->I_d != nullptr);
@@ -1317,7 +1434,20 @@ int crt_hip_integrated2_f64(int scheme, const crt_columns* cols, const crt_bands
   ia.L_F = out->F;
   ia.L_Id = out->I_d;
   crt_outputs none = {};
-  return solve_impl(scheme, cols, bands, opts, &none, workspace, workspace_bytes, stream, 0, &ia);
+  return solve_impl(scheme, cols, bands, opts, &none, workspace, workspace_bytes, stream, f32, &ia);
+}
+
+int crt_hip_integrated2_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts,
+                            const double* band_w, int32_t ngroup, const crt_bandsum_out* out, void* workspace, size_t workspace_bytes,
+                            crt_stream_t stream) {
+  return integrated_impl(scheme, cols, bands, opts, band_w, ngroup, out, workspace, workspace_bytes, stream, 0);
+}
+
+int crt_hip_integrated2_f32(int scheme, const crt_columns* cols, const crt_bands_f32* bands, const crt_options* opts,
+                            const double* band_w, int32_t ngroup, const crt_bandsum_out* out, void* workspace, size_t workspace_bytes,
+                            crt_stream_t stream) {
+  return integrated_impl(scheme, cols, reinterpret_cast<const crt_bands*>(bands), opts, band_w, ngroup, out, workspace, workspace_bytes,
+                         stream, 1);
 }
 
 int crt_hip_integrated_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts,
@@ -1331,6 +1461,17 @@ int crt_hip_integrated_f64(int scheme, const crt_columns* cols, const crt_bands*
   return crt_hip_integrated2_f64(scheme, cols, bands, opts, band_w, ngroup, &o, workspace, workspace_bytes, stream);
 }
 
+int crt_hip_integrated_f32(int scheme, const crt_columns* cols, const crt_bands_f32* bands, const crt_options* opts,
+                           const double* band_w, int32_t ngroup, double* aI, double* aI_sl, double* aI_sh, double* totals,
+                           void* workspace, size_t workspace_bytes, crt_stream_t stream) {
+  crt_bandsum_out o = {};
+  o.aI = aI;
+  o.aI_sl = aI_sl;
+  o.aI_sh = aI_sh;
+  o.totals = totals;
+  return crt_hip_integrated2_f32(scheme, cols, bands, opts, band_w, ngroup, &o, workspace, workspace_bytes, stream);
+}
+
 int crt_hip_band_reduce_f64(const double* X, int64_t nrow, int32_t nb, const double* band_w, int32_t ngroup, double* out, crt_stream_t stream) {
   if (!X || !band_w || !out || nrow < 0 || nb <= 0 || ngroup <= 0 || ngroup > 4) return CRT_ERR_BAD_ARG;
   if (nrow == 0) return CRT_OK;
@@ -1342,43 +1483,14 @@ int crt_hip_band_reduce_f64(const double* X, int64_t nrow, int32_t nb, const dou
 
 int crt_hip_absorb_f64(const crt_columns* cols, const crt_bands* bands, const double* I_dr, const double* I_df_d,
                        const double* I_df_u, double* const* out7, double* laim, double* f_slm, crt_stream_t stream) {
-  if (!cols || !bands || !I_dr || !I_df_d || !I_df_u || !out7 || !laim || !f_slm) return CRT_ERR_BAD_ARG;
-  if (cols->ncol <= 0 || cols->nz < 2 || bands->nb <= 0) return CRT_ERR_BAD_ARG;
-  if (!cols->psi || !cols->lai || !cols->g_kind || !bands->leaf_r || !bands->leaf_t) return CRT_ERR_BAD_ARG;
-  AbsArgs a;
-  a.ncol = cols->ncol;
-  a.nb = bands->nb;
-  a.nz = cols->nz;
-  a.col_stride = bands->col_stride;
-  a.psi = cols->psi;
-  a.lai = cols->lai;
-  a.g_kind = cols->g_kind;
-  a.g_param = cols->g_param;
-  a.g_at_psi = cols->g_at_psi;
-  a.leaf_r = bands->leaf_r;
-  a.leaf_t = bands->leaf_t;
-  a.I_dr = I_dr;
-  a.I_df_d = I_df_d;
-  a.I_df_u = I_df_u;
-  for (int i = 0; i < 7; ++i) {
-    if (!out7[i]) return CRT_ERR_BAD_ARG;
-    a.o[i] = out7[i];
-  }
-  a.laim = laim;
-  a.f_slm = f_slm;
-  bool flat = a.nb % 2 == 0 && a.col_stride % 2 == 0 && (long long)a.nz * a.nb < (1ll << 31);
-  const void* ptrs[] = {I_dr, I_df_d, I_df_u, a.o[0], a.o[1], a.o[2], a.o[3], a.o[4], a.o[5], a.o[6]};
-  for (const void* q : ptrs)
-    if (reinterpret_cast<uintptr_t>(q) & 15) flat = false;
-  // ring of T + 1 rows of the three inputs: T rows per round, as many as keep the workgroup at ~40 KB of LDS (4 per CU)
-  int T = (int)((40 * 1024 / sizeof(double) - 2 * (a.nz - 1) - a.nb) / (3 * (size_t)a.nb)) - 1;
-  T = std::max(1, std::min(T, std::min(16, a.nz - 1)));
-  const size_t shf = (size_t)(2 * (a.nz - 1) + a.nb + 3 * (T + 1) * a.nb) * sizeof(double);
-  if (flat && a.nb >= 2 && shf <= 64 * 1024)
-    hipLaunchKernelGGL(k_absorb_tile, dim3(a.ncol), dim3(256), shf, static_cast<hipStream_t>(stream), a, T);
-  else
-    hipLaunchKernelGGL(k_absorb, dim3(a.ncol), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  return hipGetLastError() == hipSuccess ? CRT_OK : CRT_ERR_LAUNCH;
+  if (!bands) return CRT_ERR_BAD_ARG;
+  return absorb_impl<double>(cols, bands->nb, bands->col_stride, bands->leaf_r, bands->leaf_t, I_dr, I_df_d, I_df_u, out7, laim, f_slm, stream);
+}
+
+int crt_hip_absorb_f32(const crt_columns* cols, const crt_bands_f32* bands, const float* I_dr, const float* I_df_d,
+                       const float* I_df_u, float* const* out7, double* laim, double* f_slm, crt_stream_t stream) {
+  if (!bands) return CRT_ERR_BAD_ARG;
+  return absorb_impl<float>(cols, bands->nb, bands->col_stride, bands->leaf_r, bands->leaf_t, I_dr, I_df_d, I_df_u, out7, laim, f_slm, stream);
 }
 
 int crt_hip_tau_d_f64(const double* kb_nodes, const double* L, int64_t n, int32_t method, double* out, crt_stream_t stream) {

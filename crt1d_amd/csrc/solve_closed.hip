@@ -1177,7 +1177,7 @@ int launch_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
       return (int)CRT_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(a.ncol), dim3(nthr), sh, s, a, ia, rec_dbl);
     if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
-    note_kernel("k_int<%s>%s", S::NAME, prof ? " + level profiles" : " wave totals");  // (only a launch that succeeded is reported)
+    note_kernel("k_int<%s>%s%s", S::NAME, sizeof(TIO) == 8 ? "" : " f32", prof ? " + level profiles" : " wave totals");  // (only a launch that succeeded is reported)
     return (int)CRT_OK;
   };
   if (prof) {

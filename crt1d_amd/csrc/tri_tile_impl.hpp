@@ -610,7 +610,7 @@ int launch_int_m(const SolveArgs& a, const IntArgs& ia, hipStream_t s, int nthr)
       return (int)CRT_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(a.ncol), dim3(nthr), sh, s, a, ia, off_ck, off_int);
     if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
-    note_kernel("k_tri_int<%s> M=%d%s", S::NAME, M, prof ? " + level profiles" : "");  // (only a launch that succeeded is reported)
+    note_kernel("k_tri_int<%s>%s M=%d%s", S::NAME, sizeof(TIO) == 8 ? "" : " f32", M, prof ? " + level profiles" : "");  // (only a launch that succeeded is reported)
     return (int)CRT_OK;
   };
   if (prof) {

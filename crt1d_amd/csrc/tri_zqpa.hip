@@ -644,7 +644,7 @@ __host__ __device__ inline size_t zqpa_int_lds_doubles(int Mg, int nwave, bool s
 }
 
 // PROF: level profiles requested (needs SPLIT); SPLIT: separate D, U sums per row (the net-flux form has fewer, see above)
-template <int M, int MAXT, bool PROF, bool SPLIT>
+template <typename TIO, int M, int MAXT, bool PROF, bool SPLIT>
 __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4))) void k_zqpa_int(SolveArgs g, IntArgs ia, int nzo, int off_ck,
                                                                                            int off_int) {
   typedef TriZq S;
@@ -672,10 +672,10 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4))) void 
   const bool active = tid < nb;
   const int b = active ? tid : 0;
   S st;
-  st.template init<double>(rec, g, c, b);
+  st.template init<TIO>(rec, g, c, b);
   const double bc = st.band_const();  // I_dr0
   const long long ib = (long long)c * g.col_stride + b;
-  const double leaf_a = 1 - (ldio<double>(g.leaf_r, ib) + ldio<double>(g.leaf_t, ib));
+  const double leaf_a = 1 - (ldio<TIO>(g.leaf_r, ib) + ldio<TIO>(g.leaf_t, ib));
   double w[INT_MAXG];
 #pragma unroll
   for (int q = 0; q < INT_MAXG; ++q) w[q] = (q < ng && active) ? ia.band_w[(long long)q * nb + b] : 0.0;
@@ -880,7 +880,7 @@ inline size_t zqpa_int_lds_bytes(const SolveArgs& a, int M, int nthr, bool split
   return ((size_t)oint + zqpa_int_lds_doubles(Mg, nthr / 64, split)) * sizeof(double);
 }
 
-template <int M, bool PROF, bool SPLIT>
+template <typename TIO, int M, bool PROF, bool SPLIT>
 int launch_zqpa_int_m(const SolveArgs& a, const IntArgs& ia, hipStream_t s, int nthr) {
   const int Mg = zqpa_M(a.nz);
   int off_ck, off_int;
@@ -895,29 +895,36 @@ int launch_zqpa_int_m(const SolveArgs& a, const IntArgs& ia, hipStream_t s, int 
       return (int)CRT_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(a.ncol), dim3(nthr), sh, s, g, ia, a.nz, off_ck, off_int);
     if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
-    note_kernel("k_zqpa_int<zq_pa> M=%d grid=%d%s", M, Mg, PROF ? " + level profiles" : "");  // (only a launch that succeeded is reported)
+    note_kernel("k_zqpa_int<zq_pa>%s M=%d grid=%d%s", sizeof(TIO) == 8 ? "" : " f32", M, Mg, PROF ? " + level profiles" : "");  // (only a launch that succeeded is reported)
     return (int)CRT_OK;
   };
-  if (nthr <= 256) return go(k_zqpa_int<M, 256, PROF, SPLIT>);
-  if (nthr <= 512) return go(k_zqpa_int<M, 512, PROF, SPLIT>);
-  return go(k_zqpa_int<M, 1024, PROF, SPLIT>);
+  if (nthr <= 256) return go(k_zqpa_int<TIO, M, 256, PROF, SPLIT>);
+  if (nthr <= 512) return go(k_zqpa_int<TIO, M, 512, PROF, SPLIT>);
+  return go(k_zqpa_int<TIO, M, 1024, PROF, SPLIT>);
 }
 
-}  // namespace
-
-// integrated path of zq_pa (float64 spectra): one kernel, no workspace beyond the K0 record
-int launch_zqpa_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
-  if (a.nb > 1024 || a.f32) return CRT_ERR_UNSUPPORTED;
+// integrated path of zq_pa (float64 or float32 spectra, TIO): one kernel, no workspace beyond the K0 record
+template <typename TIO>
+int launch_zqpa_int_io(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
   const int nthr = ((a.nb + 63) / 64) * 64;
   // M = 8 (104 / 114 VGPRs) or M = 12 (124 VGPRs): four waves per SIMD with no scratch, also in the 1024-thread form (M = 16 there: 128
   // VGPRs + 56 B of scratch; the net-flux form at M = 12: 128 + 24 B).  The LDS decides how many workgroups share a CU: the form that fits
   // more of them is taken, the smaller M and (without profiles) the net-flux form on a tie.  Measured (1e4 x 300 x 60 / 6e3 x 300 x 100):
-  // net-flux M = 8 0.956 / 1.323 ms (three / one workgroups per CU), separate sums M = 12 1.056 / 1.013 (three / two)
+  // net-flux M = 8 0.956 / 1.323 ms (three / one workgroups per CU), separate sums M = 12 1.056 / 1.013 (three / two).  The LDS holds fp64
+  // only (record, checkpoints, partial sums): the choice is the same for both storage types.
   const bool prof = ia.L_dr != nullptr;
   const size_t s8 = zqpa_int_lds_bytes(a, 8, nthr, prof), s12 = zqpa_int_lds_bytes(a, 12, nthr, true);
   auto fits = [](size_t sh) -> size_t { return sh <= MAX_WG_LDS ? MAX_WG_LDS / sh : 0; };
-  if (fits(s12) > fits(s8)) return prof ? launch_zqpa_int_m<12, true, true>(a, ia, s, nthr) : launch_zqpa_int_m<12, false, true>(a, ia, s, nthr);
-  return prof ? launch_zqpa_int_m<8, true, true>(a, ia, s, nthr) : launch_zqpa_int_m<8, false, false>(a, ia, s, nthr);
+  if (fits(s12) > fits(s8))
+    return prof ? launch_zqpa_int_m<TIO, 12, true, true>(a, ia, s, nthr) : launch_zqpa_int_m<TIO, 12, false, true>(a, ia, s, nthr);
+  return prof ? launch_zqpa_int_m<TIO, 8, true, true>(a, ia, s, nthr) : launch_zqpa_int_m<TIO, 8, false, false>(a, ia, s, nthr);
+}
+
+}  // namespace
+
+int launch_zqpa_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
+  if (a.nb > 1024) return CRT_ERR_UNSUPPORTED;
+  return a.f32 ? launch_zqpa_int_io<float>(a, ia, s) : launch_zqpa_int_io<double>(a, ia, s);
 }
 
 int launch_zqpa(const SolveArgs& a, double* scratch, hipStream_t s) {

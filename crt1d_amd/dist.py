@@ -229,8 +229,9 @@ def solve_sharded(scheme, cols, bands, band_w, *, partition="column", group=None
       ``aI, aI_sl, aI_sh``  ``(ncol_local, nz-1, ngroup)``, ``totals (ncol_local, ngroup, 4)``, ``reflectance (ncol_local, ngroup)``,
       ``columns`` = (lo, hi) of the columns these rows describe, and ``profiles`` = this rank's full (unreduced) solver outputs.
     With ``partition="band"`` every rank ends up with the complete integrated result for all columns (:class:`BandShardPlan`).
-    ``keep_profiles=False`` uses the fused kernel (``crt_hip_integrated_f64``): no profile is ever written to HBM and
-    ``profiles`` is ``None``.
+    ``keep_profiles=False`` uses the fused kernel (``crt_hip_integrated2_f64``, ``_f32`` for float32 bands): no profile is ever written
+    to HBM and ``profiles`` is ``None``.  Float32 bands (f32 storage) work in both partitions; the integrated results and the message
+    stay float64.
     ``column_tiles > 1`` (band partition): the columns are processed in that many tiles and the all-reduce of tile i is
     issued asynchronously while tile i+1 is being solved; ``profiles`` is then a list with one entry per tile.
     """

@@ -13,7 +13,9 @@
  *   solve_bf   crt1d/solvers/_solve_bf.py:7-154      ->  crt_hip_bf_f64
  *   solve_zq_pa crt1d/solvers/_solve_zq_pa.py:24-418 ->  crt_hip_zq_pa_f64
  *
- * which `Model.run` dispatches to at crt1d/model.py:305-310.  The reference has no FFI of
+ * which `Model.run` dispatches to at crt1d/model.py:305-310.  Every scheme also has an f32 storage entry (crt_hip_<scheme>_f32),
+ * and f32 storage reaches the epilogue (crt_hip_absorb_f32, crt_hip_absorb_bandsum{,2}_f32) and the fused integrated path
+ * (crt_hip_integrated{,2}_f32): float spectra and profiles, fp64 arithmetic and band sums.  The reference has no FFI of
  * its own (pure Python); INTEGRATION.md shows the ctypes stub a maintainer would add.
  *
  * Conventions
@@ -132,7 +134,9 @@ typedef struct crt_outputs {
 } crt_outputs;
 
 /* f32 storage variants: spectra read and profiles written as float (half the HBM bytes).  Geometry (crt_columns), the
- * workspace and ALL arithmetic stay fp64: results are the fp64 results rounded once to fp32. */
+ * workspace and ALL arithmetic stay fp64: results are the fp64 results rounded once to fp32.  They reach every step after the
+ * solve as well: the epilogue (crt_hip_absorb_f32, crt_hip_absorb_bandsum{,2}_f32) and the fused integrated path
+ * (crt_hip_integrated{,2}_f32), whose band sums and other reduced outputs stay fp64. */
 typedef struct crt_bands_f32 {
   int32_t nb;
   int64_t col_stride;
@@ -202,6 +206,12 @@ int crt_hip_zq_pa_f32(const crt_columns*, const crt_bands_f32*, const crt_option
 int crt_hip_absorb_bandsum_f64(const crt_columns* cols, const crt_bands* bands, const double* I_dr, const double* I_df_d,
                                const double* I_df_u, const double* band_w, int32_t ngroup, double* aI, double* aI_sl,
                                double* aI_sh, double* totals, crt_stream_t stream);
+/* f32 storage: bands->leaf_r / leaf_t and the three profiles I_dr, I_df_d, I_df_u are float; band_w and every output stay double.
+ * Loads widen to double at once and the kernel choice depends on the shape only, so the outputs are the bits
+ * crt_hip_absorb_bandsum_f64 gives for the same values upcast. */
+int crt_hip_absorb_bandsum_f32(const crt_columns* cols, const crt_bands_f32* bands, const float* I_dr, const float* I_df_d,
+                               const float* I_df_u, const double* band_w, int32_t ngroup, double* aI, double* aI_sl,
+                               double* aI_sh, double* totals, crt_stream_t stream);
 
 /*
  * The complete output of diagnostics.band (crt1d/diagnostics.py:39-108) for up to four band groups at once: besides the layer
@@ -227,9 +237,16 @@ typedef struct crt_bandsum_out {
 } crt_bandsum_out;
 int crt_hip_absorb_bandsum2_f64(const crt_columns* cols, const crt_bands* bands, const double* I_dr, const double* I_df_d,
                                 const double* I_df_u, const double* band_w, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream);
+/* f32 storage: float leaf optics and profiles, double band_w and crt_bandsum_out (bitwise equal to the f64 call on upcast values) */
+int crt_hip_absorb_bandsum2_f32(const crt_columns* cols, const crt_bands_f32* bands, const float* I_dr, const float* I_df_d,
+                                const float* I_df_u, const double* band_w, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream);
 /* ... and the same complete output from the fused solve + epilogue (crt_hip_integrated_f64): no profile is written to memory, the
  * level sums the kernel forms anyway are kept instead of thrown away. */
 int crt_hip_integrated2_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const double* band_w,
+                            int32_t ngroup, const crt_bandsum_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream);
+/* f32 storage: the five spectra of crt_bands_f32 are float; band_w, the workspace and crt_bandsum_out stay double.  All eight schemes,
+ * nb <= 1024 (else CRT_ERR_UNSUPPORTED); crt_hip_last_kernel names the float instantiation with an " f32" tag. */
+int crt_hip_integrated2_f32(int scheme, const crt_columns* cols, const crt_bands_f32* bands, const crt_options* opts, const double* band_w,
                             int32_t ngroup, const crt_bandsum_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream);
 
 /*
@@ -238,6 +255,10 @@ int crt_hip_integrated2_f64(int scheme, const crt_columns* cols, const crt_bands
  * section 8(d) asks to report separately).  Schemes: 2s, 4s, bl, g77, bf, n79, zq, zq_pa; nb <= 1024.
  */
 int crt_hip_integrated_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts,
+                           const double* band_w, int32_t ngroup, double* aI, double* aI_sl, double* aI_sh, double* totals,
+                           void* workspace, size_t workspace_bytes, crt_stream_t stream);
+/* f32 storage: float spectra (crt_bands_f32); band_w, aI, aI_sl, aI_sh, totals and the workspace stay double */
+int crt_hip_integrated_f32(int scheme, const crt_columns* cols, const crt_bands_f32* bands, const crt_options* opts,
                            const double* band_w, int32_t ngroup, double* aI, double* aI_sl, double* aI_sh, double* totals,
                            void* workspace, size_t workspace_bytes, crt_stream_t stream);
 
@@ -255,6 +276,9 @@ int crt_hip_band_reduce_f64(const double* X, int64_t nrow, int32_t nb, const dou
  */
 int crt_hip_absorb_f64(const crt_columns* cols, const crt_bands* bands, const double* I_dr, const double* I_df_d,
                        const double* I_df_u, double* const* out7, double* laim, double* f_slm, crt_stream_t stream);
+/* f32 storage: float leaf optics, profiles and out7 (each output is the fp64 value rounded once); laim and f_slm stay double */
+int crt_hip_absorb_f32(const crt_columns* cols, const crt_bands_f32* bands, const float* I_dr, const float* I_df_d, const float* I_df_u,
+                       float* const* out7, double* laim, double* f_slm, crt_stream_t stream);
 
 /*
  * tau_d(L) = 2 int_0^{pi/2} exp(-K_b(psi) L) sin(psi) cos(psi) dpsi for n values of L: crt1d/solvers/common.py:56-87 `tau_df_fn`
