@@ -380,7 +380,11 @@ class Plan:
                  placement="auto", tune=None):
         """``placement``: ``"auto"`` allocates output sets of 1 GB and more through the class-interleaving allocator
         (``crt_hip_buffer_alloc_set``: deterministic ~7 TB/s store mode); ``"none"`` uses ``torch.empty``
-        (the store rate then depends on where the driver happens to put the arrays).  Ignored when ``out`` is given."""
+        (the store rate then depends on where the driver happens to put the arrays).  Ignored when ``out`` is given.
+
+        ``out``: caller-owned output arrays (contiguous, of the bands' dtype), at any element offset.  One exception: zq_pa with
+        float32 storage needs every output array to start on an 8-byte boundary (its kernels store band pairs and it has no
+        other path in f32); a float32 array that starts at an odd element of an aligned allocation is a ValueError."""
         if scheme not in _lib.SCHEME_IDS:
             raise ValueError(f"unknown scheme {scheme!r}; valid: {', '.join(SCHEMES)}")
         if tau_d_method not in _lib.TAU_D_METHODS:
@@ -404,6 +408,8 @@ class Plan:
                 raise ValueError(f"`out` lacks {k!r}")
             rows = nz - 1 if k in _MID_KEYS.get(scheme, ()) else nz
             _check_profile(self.out[k], f"output {k!r}", (ncol, rows, nb), cols.device, bands.dtype)
+            if scheme == "zq_pa" and bands.dtype == torch.float32 and self.out[k].data_ptr() % 8:
+                raise ValueError(f"output {k!r}: zq_pa with float32 storage needs output arrays that start on an 8-byte boundary")
         need = workspace_bytes(scheme, ncol, nz, nb)
         workspace = _check_workspace(workspace, need, cols.device)
         self.workspace = workspace

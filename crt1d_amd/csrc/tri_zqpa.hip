@@ -1,3 +1,5 @@
+#include <cstdio>
+
 #include "tri_tile_impl.hpp"
 
 // ------------------------------------------------------------------------------------------
@@ -939,6 +941,7 @@ int launch_zqpa(const SolveArgs& a, double* scratch, hipStream_t s) {
       st = launch_zqpa_fused<float, 16, 4>(a, s, nsw, HALF);
       if (st == CRT_ERR_UNSUPPORTED) st = launch_zqpa_fused<float, 15, 3>(a, s, nsw, HALF);
       if (st == CRT_ERR_UNSUPPORTED) st = launch_zqpa_fused<float, 16, 4>(a, s, nsw);
+      if (st == CRT_ERR_UNSUPPORTED) st = launch_zqpa_fused<float, 15, 3>(a, s, nsw);  // (wide spectra near 100 levels: 601 x 99 needs it)
       if (st == CRT_ERR_UNSUPPORTED) st = launch_zqpa_fused<float, 12, 4>(a, s, nsw);
       return st;  // f32 storage exists in the fused kernel only (the two-kernel path keeps its computational-grid scratch in fp64)
     }
@@ -991,6 +994,8 @@ int launch_zqpa(const SolveArgs& a, double* scratch, hipStream_t s) {
   int st = launch_scheme<TriZqPa, double>(g, s, done, 1);
   if (st != CRT_OK) return st;
   if (!done && (st = launch_zqpa_wave(g, s)) != CRT_OK) return st;  // nb > 1024: per-wave kernel (solve_tridiag.hip)
+  char grid_kernel[160];  // the grid solve's own report, kept for the combined one below
+  snprintf(grid_kernel, sizeof grid_kernel, "%s", last_kernel());
   InterpArgs ia;
   ia.ncol = a.ncol;
   ia.nb = a.nb;
@@ -1010,7 +1015,7 @@ int launch_zqpa(const SolveArgs& a, double* scratch, hipStream_t s) {
     return CRT_ERR_LAUNCH;
   hipLaunchKernelGGL((k_zqpa_interp<double>), dim3(a.ncol), dim3(256), sh, s, ia);
   if (hipGetLastError() != hipSuccess) return CRT_ERR_LAUNCH;
-  note_kernel("zq_pa two-kernel path: grid solve + k_zqpa_interp");  // (only a launch that succeeded is reported)
+  note_kernel("zq_pa two-kernel path: grid solve %s + k_zqpa_interp", grid_kernel);  // (only a launch that succeeded is reported)
   return CRT_OK;
 }
 

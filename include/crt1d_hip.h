@@ -191,8 +191,10 @@ int crt_hip_zq_f32(const crt_columns*, const crt_bands_f32*, const crt_options*,
 int crt_hip_bl_f32(const crt_columns*, const crt_bands_f32*, const crt_options*, const crt_outputs_f32*, void*, size_t, crt_stream_t);
 int crt_hip_g77_f32(const crt_columns*, const crt_bands_f32*, const crt_options*, const crt_outputs_f32*, void*, size_t, crt_stream_t);
 int crt_hip_bf_f32(const crt_columns*, const crt_bands_f32*, const crt_options*, const crt_outputs_f32*, void*, size_t, crt_stream_t);
-/* zq_pa with f32 storage runs in the single-kernel form only: 16 <= nb <= 832 (even or odd: the reference's default 107 bands are
- * covered), else CRT_ERR_UNSUPPORTED */
+/* zq_pa with f32 storage runs in the single-kernel form only: nb >= 16 (even or odd: the reference's default 107 bands are covered)
+ * and as many bands as its LDS holds -- 832 at a dozen levels, about 600 from 60 levels up -- else CRT_ERR_UNSUPPORTED.  Its four output arrays must start on an 8-byte boundary (a float array may not start at an
+ * odd element of an aligned allocation), else CRT_ERR_UNSUPPORTED: every form stores band pairs, and there is no two-kernel
+ * fallback in f32.  The f64 entry accepts any 8-byte aligned outputs (misaligned ones take the two-kernel path). */
 int crt_hip_zq_pa_f32(const crt_columns*, const crt_bands_f32*, const crt_options*, const crt_outputs_f32*, void*, size_t, crt_stream_t);
 
 /*

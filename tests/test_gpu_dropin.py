@@ -327,19 +327,54 @@ def test_model_to_dataset():
 
 # (tune key, value) settings that select each kernel family through crt_options.tune (per call; keys in csrc/crt_internal.hpp)
 _CLOSED_PATHS = {"k_pipe (default)": {}, "k_tile": {2: 4}, "k_tile generic flush": {2: 4 | 2}, "k_pipe generic flush": {2: 2},
-                 "k_pipe 1 store wave, T=2": {3: 1, 4: 2}, "k_pipe 4 store waves, T=8": {3: 4, 4: 8}}
+                 "k_pipe 1 store wave, T=2": {3: 1, 4: 2}, "k_pipe 4 store waves, T=8": {3: 4, 4: 8},
+                 "k_pipe, packing off": {5: 1}, "k_tile, packing off": {5: 1, 2: 4}, "k_pipe generic flush, packing off": {5: 1, 2: 2},
+                 "k_pipe_pack forced": {5: 2}, "k_pipe_pack 1 compute wave": {5: 2, 6: 1}, "k_pipe_pack 2 compute waves": {5: 2, 6: 2},
+                 "k_pipe_pack 3 compute waves": {5: 2, 6: 3}, "k_pipe_pack 4 compute waves": {5: 2, 6: 4}}
 _TRI_PATHS = {"default": {}, "k_tri_tile": {10: 1}, "k_tri_tile M8 T8": {10: 1, 8: 8, 9: 8}, "double-buffer pipeline": {10: 2},
-              "register-staged pipeline": {10: 3}, "generic-flush pipeline": {10: 4}, "pipeline M16 T4, 2 store waves": {8: 16, 9: 4, 11: 2}}
+              "register-staged pipeline": {10: 3}, "generic-flush pipeline": {10: 4}, "pipeline M16 T4, 2 store waves": {8: 16, 9: 4, 11: 2},
+              "default, packing off": {5: 1}}
+
+
+def _closed_family(tune, nb, nz, dtype):
+    """The kernel families launch_tile (csrc/solve_closed.hip) may pick for these overrides, as substrings of crt_hip_last_kernel."""
+    vw = 2 if dtype == "f64" else 4  # elements per 16-B piece
+    if nb < 4:
+        return ("k_direct<",)
+    t5 = tune.get(5, 0)
+    if (nb <= 32 or t5 == 2) and nb <= 128 and t5 != 1 and nb % vw == 0 and (nz * nb) % vw == 0:
+        # (three or four compute waves of narrow columns: as many columns per workgroup as fit its LDS, else the unpacked pipeline)
+        return ("k_pipe_pack<",) if tune.get(6, 0) <= 2 else ("k_pipe_pack<", "k_pipe<")
+    if tune.get(2, 0) & 4:
+        return ("k_tile<",)
+    return ("k_pipe<",) if nb <= 128 else ("k_pipe<", "k_tile<")  # (wide spectra: the pipeline only where its tiles fit the LDS budget)
+
+
+def _tri_family(tune, nb, dtype):
+    """The same for launch_scheme (csrc/tri_tile_impl.hpp); None where the choice depends on the LDS budget."""
+    if tune.get(5, 0) != 1 and tune.get(8, 0) == 0 and tune.get(10, 0) == 0 and nb % 2 == 0 and nb <= 32:
+        return ("packed",)
+    if nb < 10:
+        return ("k_tri_wave<",)
+    if tune.get(10) == 1:  # (beyond 300 bands M8 T8 exceeds the LDS: the per-wave kernel)
+        return ("k_tri_tile<",) if nb <= 300 or 8 not in tune else ("k_tri_tile<", "k_tri_wave<")
+    if nb % 2 == 0 and 16 <= nb <= 128 and tune.get(10) == 2:
+        return ("double-buffered",)
+    if nb % 2 == 0 and 16 <= nb <= 128 and (tune.get(8, 0) > 0 or tune.get(5) == 1):
+        return ("k_tri_pipe<",)
+    return None
 
 
 @pytest.mark.parametrize("scheme", ["2s", "4s", "bl", "g77", "bf", "n79", "zq"])
 @pytest.mark.parametrize("shape", [(23, 300, 60), (9, 107, 61), (6, 64, 13), (5, 128, 60), (3, 600, 33), (4, 255, 100), (7, 300, 7),
                                    (9, 38, 100), (7, 37, 60), (130, 36, 61), (5, 16, 30), (6, 21, 12),  # + the narrow band shards
-                                   (40, 12, 60), (33, 6, 20), (21, 11, 33), (50, 4, 9), (17, 14, 100)])  # + very narrow spectra
+                                   (40, 12, 60), (33, 6, 20), (21, 11, 33), (50, 4, 9), (17, 14, 100),  # + very narrow spectra
+                                   (9, 32, 20), (11, 96, 33)])  # + the widest packed spectrum, and one packed only on request
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 def test_every_kernel_family_gives_the_same_bits(scheme, shape, dtype):
-    """The wave-specialised pipelines (double-buffered, register-staged, generic flush), the all-waves tile kernels and the
-    per-wave / direct kernels share the per-lane arithmetic; whichever the heuristics pick, the outputs are BITWISE equal."""
+    """The wave-specialised pipelines (double-buffered, register-staged, generic flush), the all-waves tile kernels, the kernels that pack
+    several columns into a wave and the per-wave / direct kernels share the per-lane arithmetic; whichever the heuristics pick, the outputs
+    are BITWISE equal.  Each setting must also have selected the family it names."""
     import torch
 
     from crt1d_amd import _lib, batched, synth
@@ -351,14 +386,24 @@ def test_every_kernel_family_gives_the_same_bits(scheme, shape, dtype):
     cols, bands = batched.Columns.from_host(d), batched.Bands.from_host(d)
     ref = batched.Plan(scheme, cols, bands)
     ref(flags=_lib.FLAG_DIRECT_STORES)
-    paths = _TRI_PATHS if scheme in ("n79", "zq") else _CLOSED_PATHS
+    tri = scheme in ("n79", "zq")
+    paths = _TRI_PATHS if tri else _CLOSED_PATHS
     names = set()
     for name, tune in paths.items():
         p = batched.Plan(scheme, cols, bands, tune=tune)  # the overrides travel with the plan's calls: no global state to restore
         for v in p.out.values():
             v.fill_(float("nan"))
         p()
-        names.add(p.last_kernel())
+        kernel = p.last_kernel()
+        names.add(kernel)
+        want = _tri_family(tune, nb, dtype) if tri else _closed_family(tune, nb, nz, dtype)
+        assert want is None or any(w in kernel for w in want), (name, want, kernel)
+        if tri and tune.get(5) == 1:
+            assert "packed" not in kernel, (name, kernel)
+        if not tri and want == ("k_pipe_pack<",) and 6 in tune:
+            assert f"compute_waves={max(tune[6], (nb + 63) // 64)} " in kernel, (name, kernel)
+        if not tri and want != ("k_pipe_pack<",) and tune.get(2, 0) & 2:
+            assert "generic-flush" in kernel, (name, kernel)
         torch.cuda.synchronize()
         for k in p.out:
             assert bool(torch.isfinite(p.out[k]).all()), (name, k)
@@ -548,3 +593,190 @@ def test_device_exp_and_sincos_accuracy():
     xl = xs.astype(np.longdouble)
     assert float(np.abs(sn.cpu().numpy() - np.sin(xl)).max()) <= 3e-16
     assert float(np.abs(cs.cpu().numpy() - np.cos(xl)).max()) <= 3e-16
+
+
+def test_common_tau_functions_vs_reference():
+    """Row a7 as public API: tau_b_fn, tau_df_fn ('quad' / '9sky'), K_df_fn of crt1d.solvers.common (golden g9_common.npz from the
+    reference).  '9sky' involves no quadrature: 1e-13; 'quad' is bounded by the reference's QUADPACK error (<= 2e-7 here)."""
+    from crt1d_amd import leaf_angle
+    from crt1d_amd.solvers import common
+
+    g = load_golden("g9_common")
+    lai = g["lai"]
+    gfs = {"spherical": leaf_angle.G_spherical, "horizontal": leaf_angle.G_horizontal, "vertical": leaf_angle.G_vertical,
+           "ellipsoidal_x2": lambda p: leaf_angle.G_ellipsoidal(p, 2.0),
+           "ellipsoidal_approx_x0.96": lambda p: leaf_angle.G_ellipsoidal_approx(p, 0.9632)}
+    for name, G in gfs.items():
+        K = lambda p, G=G: G(p) / np.cos(p)  # noqa: E731  (a plain lambda, as the reference's Model builds it)
+        np.testing.assert_allclose(common.tau_b_fn(K, 0.35, lai), g[f"{name}__tau_b"], rtol=1e-15)
+        np.testing.assert_allclose(common.tau_df_fn(K, lai, method="9sky"), g[f"{name}__tau_d_9sky"], rtol=1e-13, err_msg=name)
+        np.testing.assert_allclose(common.tau_df_fn(K, lai, method="quad"), g[f"{name}__tau_d_quad"], rtol=2e-7, err_msg=name)
+        np.testing.assert_allclose(common.tau_df_fn(K, lai), g[f"{name}__tau_d_quad"], rtol=2e-7)  # default method
+        s = common.tau_df_fn(K, 2.5)
+        assert isinstance(s, float) and s == pytest.approx(float(g[f"{name}__tau_d_quad_scalar"]), rel=2e-7)
+        assert common.K_df_fn(K, 4.0) == pytest.approx(float(g[f"{name}__K_d_quad"]), rel=2e-7)
+        assert common.K_df_fn(K, 4.0, method="9sky") == pytest.approx(float(g[f"{name}__K_d_9sky"]), rel=1e-13)
+    with pytest.raises(ValueError):
+        common.tau_df_fn(lambda p: 0.5 / np.cos(p), lai, method="simpson")
+
+
+@pytest.mark.parametrize("scheme", ["2s", "n79", "zq"])
+def test_g6_epilogue_kernels_vs_reference_golden(scheme):
+    """Rows a11 / a12 pinned on the reference itself: crt_hip_absorb_f64 and crt_hip_absorb_bandsum_f64 fed with the REFERENCE's
+    profiles (g1) against the reference's own `_calc_absorption` (model.py:573-647) outputs and the band sums formed with its
+    `_x_frac_in_bounds` weights (fixture g6, oracle/gen_golden.py)."""
+    import torch
+
+    from crt1d_amd import batched, spectra
+
+    g1, g6 = load_golden("g1_default"), load_golden("g6_absorption")
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    cols = batched.Columns(t([float(g1["psi"])]), t(g1["lai"][None]), torch.tensor([4], dtype=torch.int32).cuda(), t([float(g1["x"])]))
+    bands = batched.Bands(t(g1["I_dr0_all"]), t(g1["I_df0_all"]), t(g1["leaf_r"]), t(g1["leaf_t"]), t(g1["soil_r"]))
+    sol = {k: t(g1[f"{scheme}__{k}"][None]) for k in ("I_dr", "I_df_d", "I_df_u")}
+    per = batched.absorb(cols, bands, sol)
+    scale = np.abs(g6[f"{scheme}__aI"]).max()
+    for k in batched.ABSORPTION_KEYS + ("laim", "f_slm"):
+        ref = g6[f"{scheme}__{k}"]
+        assert np.max(np.abs(per[k].cpu().numpy()[0] - ref)) <= 1e-13 * max(scale, np.abs(ref).max()), k
+    # weights: the host-side restatement of _x_frac_in_bounds is bit-exact against the reference's
+    names = [str(n) for n in g6["band_names"]]
+    W = np.stack([spectra.x_frac_in_bounds(g6["wle"], tuple(g6["band_bounds"][i])) for i in range(len(names))])
+    np.testing.assert_array_equal(W, g6["w_default"])
+    res = batched.absorb_bandsum(cols, bands, sol, t(W))
+    for k in ("aI", "aI_sl", "aI_sh"):
+        ref = g6[f"{scheme}__{k}__bandsum"]  # (ngroup, nz-1)
+        got = res[k].cpu().numpy()[0].T
+        assert np.max(np.abs(got - ref)) <= 1e-12 * np.abs(ref).max(), k
+
+
+def test_g6_epilogue_ragged_columns():
+    import torch
+
+    from crt1d_amd import batched
+
+    g4, g6 = load_golden("g4_ragged"), load_golden("g6_absorption")
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    cols = batched.Columns(t(g4["psi"]), t(g4["lai"]), t(g4["g_kind"].astype(np.int32)), t(g4["g_param"]))
+    bands = batched.Bands(t(g4["I_dr0"]), t(g4["I_df0"]), t(g4["leaf_r"]), t(g4["leaf_t"]), t(g4["soil_r"]))
+    sol = {k: t(g4[f"2s__{k}"]) for k in ("I_dr", "I_df_d", "I_df_u")}
+    per = batched.absorb(cols, bands, sol)
+    for k in batched.ABSORPTION_KEYS + ("laim", "f_slm"):
+        ref = g6[f"ragged2s__{k}"]
+        assert np.max(np.abs(per[k].cpu().numpy() - ref)) <= 1e-13 * max(1.0, np.abs(ref).max()), k
+    res = batched.absorb_bandsum(cols, bands, sol, t(g6["w_synth"]))
+    for k in ("aI", "aI_sl", "aI_sh"):
+        ref = np.einsum("czb,gb->czg", g6[f"ragged2s__{k}"], g6["w_synth"])
+        assert np.max(np.abs(res[k].cpu().numpy() - ref)) <= 1e-12 * np.abs(ref).max(), k
+
+
+def test_argument_checks_at_the_python_boundary():
+    """The C ABI takes bare pointers; everything a kernel assumes about caller-supplied arrays is checked before the call
+    (round-1 advisor findings): dtype / shape / device of outputs, profiles, workspace, band_w; missing G tables."""
+    import torch
+
+    from crt1d_amd import batched, spectra, synth
+
+    d = synth.make_columns(6, 40, 12, seed=1)
+    cols, bands = batched.Columns.from_host(d), batched.Bands.from_host(d)
+    w = torch.as_tensor(spectra.band_weights(d["wle"])).cuda()
+    # mixed storage types: a float profile read as double (or the reverse) would run past its allocation
+    b32 = batched.Bands(*[t.float() for t in (bands.I_dr0, bands.I_df0, bands.leaf_r, bands.leaf_t, bands.soil_r)])
+    s32 = batched.solve("2s", cols, b32)
+    s64 = batched.solve("2s", cols, bands)
+    with pytest.raises(TypeError):
+        batched.absorb(cols, bands, s32)  # f64 spectra but f32 profiles
+    with pytest.raises(TypeError):
+        batched.absorb_bandsum(cols, bands, s32, w)
+    with pytest.raises(TypeError):
+        batched.absorb_bandsum(cols, b32, s64, w)  # f32 spectra but f64 profiles
+    sol = batched.solve("n79", cols, bands)
+    with pytest.raises(ValueError):
+        batched.absorb_bandsum(cols, bands, {k: v[:, :-1] for k, v in sol.items()}, w)  # wrong shape (and non-contiguous)
+    with pytest.raises(ValueError):
+        batched.absorb_bandsum(cols, bands, sol, w[:, :-1].contiguous())  # band_w of the wrong width
+    # caller-supplied outputs: n79's mid-level arrays are (ncol, nz-1, nb) -- an (ncol, nz, nb) array in their place is an error
+    out = {k: torch.empty((6, 12, 40), dtype=torch.float64, device="cuda") for k in batched.OUT_KEYS["n79"]}
+    with pytest.raises(ValueError):
+        batched.Plan("n79", cols, bands, out=out)
+    out["aI_lsl"] = torch.empty((6, 11, 40), dtype=torch.float64, device="cuda")
+    out["aI_lsh"] = torch.empty((6, 11, 40), dtype=torch.float64, device="cuda")
+    p = batched.Plan("n79", cols, bands, out=out)
+    p()
+    torch.cuda.synchronize()
+    for k in sol:
+        assert torch.equal(out[k], sol[k]), k
+    with pytest.raises(TypeError):
+        batched.Plan("n79", cols, bands, out={k: v.float() for k, v in out.items()})
+    with pytest.raises(ValueError):
+        batched.Plan("n79", cols, bands, workspace=torch.empty(16, dtype=torch.uint8, device="cuda"))
+    with pytest.raises(ValueError):
+        batched.Plan("n79", cols, bands, workspace=torch.empty(1 << 20, dtype=torch.uint8))  # host memory
+    with pytest.raises(ValueError):
+        batched.IntegratedPlan("n79", cols, bands, w, workspace=torch.empty(16, dtype=torch.uint8, device="cuda"))
+    # columns that ask for a sampled G table without bringing one
+    d6 = dict(d, g_kind=np.full(6, 6, dtype=np.int32))
+    c6 = batched.Columns.from_host(d6)
+    with pytest.raises(ValueError):
+        batched.Plan("2s", c6, bands)
+    with pytest.raises(ValueError):
+        batched.absorb_bandsum(c6, bands, batched.solve("2s", cols, bands), w)
+
+
+@pytest.mark.parametrize("scheme,shape", [("2s", (200, 300, 60)), ("zq", (60, 300, 100)), ("n79", (40, 107, 60))])
+def test_plan_is_capturable_into_a_hip_graph(scheme, shape):
+    """After the first call on a device (which uploads the quadrature tables) a Plan's launches are stream-only: K0 + solve can be
+    captured into a hipGraph (torch.cuda.CUDAGraph) and replayed, bitwise the same outputs, also after the inputs change in place."""
+    import torch
+
+    from crt1d_amd import batched, synth
+
+    d = synth.make_columns(*shape, seed=3)
+    cols, bands = batched.Columns.from_host(d), batched.Bands.from_host(d)
+    plan = batched.Plan(scheme, cols, bands, placement="none")
+    plan()
+    torch.cuda.synchronize()
+    ref = {k: v.clone() for k, v in plan.out.items()}
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        plan()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        plan()
+    for v in plan.out.values():
+        v.zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    for k in ref:
+        assert torch.equal(plan.out[k], ref[k]), k
+    bands.I_df0.mul_(2.0)  # same buffers, new spectra: the replay reads them through the captured pointers
+    g.replay()
+    torch.cuda.synchronize()
+    fresh = batched.Plan(scheme, cols, bands, placement="none")()
+    torch.cuda.synchronize()
+    for k in ref:
+        assert torch.equal(plan.out[k], fresh[k]), k
+
+
+def test_store_set_probe():
+    """crt_hip_probe_store_set_f64 (the flush pattern of the solve kernels on a set of arrays): fills every array with the value, rejects bad
+    arguments."""
+    import ctypes
+
+    import torch
+
+    from crt1d_amd import _lib
+
+    lib = _lib.load()
+    ncol, col, run = 37, 60 * 38, 8 * 38
+    arrs = [torch.zeros(ncol * col, dtype=torch.float64, device="cuda") for _ in range(3)]
+    ptrs = (ctypes.c_void_p * 3)(*[a.data_ptr() for a in arrs])
+    st = torch.cuda.current_stream().cuda_stream
+    assert lib.crt_hip_probe_store_set_f64(ptrs, 3, ncol, col, run, 2.5, st) == 0
+    torch.cuda.synchronize()
+    for a in arrs:
+        assert bool((a == 2.5).all())
+    assert lib.crt_hip_probe_store_set_f64(ptrs, 0, ncol, col, run, 2.5, st) != 0
+    assert lib.crt_hip_probe_store_set_f64(ptrs, 3, ncol, col + 1, run, 2.5, st) != 0
+    assert lib.crt_hip_probe_store_set_f64(ptrs, 3, ncol, col, 3, 2.5, st) != 0
