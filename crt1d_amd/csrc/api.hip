@@ -1263,7 +1263,7 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
   {  // crt_options.tune is a measurement aid, but it is part of the ABI: out-of-range values are rejected here, before any launch,
      // instead of reaching the kernel configurations (keys: crt_internal.hpp, SolveArgs::tune)
     static const struct { int key, lo, hi; } range[] = {
-        {0, 0, 160 * 1024}, {1, 0, 64}, {2, 0, 255}, {3, 0, 12}, {4, 0, 32}, {8, 0, 16}, {9, 0, 12}, {10, 0, 7}, {11, 0, 12}, {12, 0, 1024}, {13, 0, 3}, {5, 0, 2}, {6, 0, 4}};
+        {0, 0, 160 * 1024}, {1, 0, 64}, {2, 0, 255}, {3, 0, 12}, {4, 0, 32}, {8, 0, 16}, {9, 0, 12}, {10, 0, 7}, {11, 0, 12}, {12, 0, 1024}, {13, 0, 3}, {5, 0, 2}, {6, 0, 4}, {15, 0, 1}};
     bool known[CRT_NTUNE] = {};
     for (const auto& r : range) {
       known[r.key] = true;
@@ -1294,7 +1294,14 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
   ca.g_at_psi = cols->g_at_psi;
   ca.g_table = cols->g_table;
   ca.ws = static_cast<double*>(workspace);
-  if (!(flags & CRT_FLAG_SKIP_PRECOMPUTE)) {
+  // 2s profiles: the closed-form launcher forms the records inside k_pipe when it picks that kernel (one launch per call), and runs
+  // k_colpre in front of any other kernel.  SKIP_PRECOMPUTE / PRECOMPUTE_ONLY and tune key 15 keep k_colpre as a kernel of its own.
+  const bool k0_in_solve = scheme == CRT_SCHEME_2S && !integ && !(flags & (CRT_FLAG_SKIP_PRECOMPUTE | CRT_FLAG_PRECOMPUTE_ONLY)) &&
+                           tune[15] == 0;
+  if (k0_in_solve) {
+    const int st = init_quadrature(s);
+    if (st != CRT_OK) return st;
+  } else if (!(flags & CRT_FLAG_SKIP_PRECOMPUTE)) {
     int st = launch_colpre(ca, s);
     if (st != CRT_OK) return st;
   }
@@ -1329,7 +1336,7 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
   if (scheme == CRT_SCHEME_ZQ_PA)
     return launch_zqpa(sa, static_cast<double*>(workspace) + (size_t)ncol * sa.reclen, s);
   const int force = (flags & CRT_FLAG_DIRECT_STORES) ? 1 : 0;
-  return tri ? launch_tridiag(scheme, sa, s, force) : launch_closed(scheme, sa, s, force);
+  return tri ? launch_tridiag(scheme, sa, s, force) : launch_closed(scheme, sa, s, force, k0_in_solve ? &ca : nullptr);
 }
 
 

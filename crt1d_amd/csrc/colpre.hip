@@ -3,33 +3,28 @@
 // Everything the reference computes once per `solve_*` call before its band loop -- K_b, mu_bar,
 // the G integrals, tau_d of every layer/level, exp(-K_b lai) -- is band-independent, so it is
 // computed once per column here (one 128-thread workgroup per column) and written as a small
-// record into the caller's workspace; the solve kernels stage it into LDS.
+// record into the caller's workspace; the solve kernels stage it into LDS.  The 2s record is
+// formed by the functions of col_record.hpp, which the 2s k_pipe also calls to build its
+// column's record itself (solve_closed.hip).
 //
 // The reference evaluates its integrals with adaptive QUADPACK (scipy.integrate.quad) over
-// arbitrary Python callables.  On device the integrals use FIXED nodes:
-//   * tau_d(L) = 2 int_0^{pi/2} exp(-K_b(psi) L) sin cos dpsi   (common.py:30-37)
-//     mu_bar   =   int_0^{pi/2} cos sin / G(psi) dpsi           (_solve_2s.py:32)
-//       6 panels x 16-point Gauss-Legendre on psi in [0, pi/2], panel edges at decades of pi/2 - psi toward
+// arbitrary Python callables.  On device the integrals use FIXED nodes (col_record.hpp):
+//   * tau_d and mu_bar: 6 panels x 16-point Gauss-Legendre on psi in [0, pi/2], panel edges at decades of pi/2 - psi toward
 //       pi/2 where exp(-G L / cos psi) has its essential singularity: 1 - tau_d <= 2.3e-12 relative for
 //       L in [3e-4, 20], mu_bar <= 3e-13 (the reference's own quad error is up to ~3e-8 in tau_d).
-//   * G_int_1 = int_0^{mu_s} G(acos m) dm,  G_int_2 = int_{mu_s}^1   (_solve_4s.py:148-149)
-//       16-point Gauss-Legendre each, in psi (dm = -sin psi dpsi).
+//   * G_int_1, G_int_2: 16-point Gauss-Legendre each, in psi (dm = -sin psi dpsi).
 //   * '9sky': the reference's own 9 fixed angles                 (common.py:40-53)
-// A CRT_G_TABLE column brings G sampled at exactly these nodes (crt_hip_quad_nodes).
 #include <math.h>
 
 #include <mutex>
 
-#include "crt_internal.hpp"
+#include "col_record.hpp"
 
 namespace crt {
 
 namespace {
 
-constexpr int NQT = CRT_NQ_TAU;
-constexpr int NQG = CRT_NQ_G4;
 constexpr int NPAN = 6;
-constexpr int NGL = 16;
 // Panel edges in t = pi/2 - psi, as fractions of pi/2: decades towards psi = pi/2, where e^{-G L / cos psi} has its boundary layer (at
 // cos psi ~ G L), and a split of the wide end, where 1/G of an ellipsoidal distribution with small x has its own structure at psi -> 0
 // (mu_bar).  Chosen by a scan over edge sets against 30-digit quadrature, ellipsoidal-approx G with x in {0.2, 0.3, 0.96, 3}
@@ -40,15 +35,6 @@ constexpr double PAN_EDGE[NPAN + 1] = {0.0, 1e-4, 1e-3, 1e-2, 0.1, 0.6, 1.0};
 static_assert(NPAN * NGL == NQT, "tau_d rule size");
 static_assert(2 * NGL == NQG, "4s rule size");
 
-struct QuadConst {
-  double psi[NQT], cs[NQT], sn[NQT];
-  double w[NQT];     // plain weights in psi
-  double w2sc[NQT];  // 2 w sin cos  (tau_d weights)
-  double gx[NGL], gw[NGL];
-  double cs9[CRT_NQ_9SKY], sn9[CRT_NQ_9SKY], sc9[CRT_NQ_9SKY];
-};
-
-__constant__ QuadConst qc;
 QuadConst h_qc;
 std::once_flag h_once;
 bool dev_inited[64] = {};
@@ -143,12 +129,6 @@ __device__ inline double tau_d_9sky(const double* k9, double L) {
   return s * (2.0 * 0.17453292519943295);  // * 2 radians(10), common.py:51
 }
 
-__device__ inline double wave_sum64(double v) {  // fixed tree order -> bitwise reproducible
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return __shfl(v, 0, 64);
-}
-
 __global__ __launch_bounds__(K0_BLOCK) void k_colpre(ColArgs a) {
   __shared__ double kq[NQT];    // K_b(psi_q) = G/cos at the tau_d nodes
   __shared__ double pmb[NQT];   // mu_bar terms, later tau_d(dlai_mean) terms
@@ -167,19 +147,15 @@ __global__ __launch_bounds__(K0_BLOCK) void k_colpre(ColArgs a) {
   const int c = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nz = a.nz;
-  const int kind = a.g_kind[c];
-  const double param = a.g_param ? a.g_param[c] : 0.0;
-  const double* tab = (kind == CRT_G_TABLE) ? a.g_table + (long long)c * CRT_NQ : nullptr;
-  const double* lai = a.lai + (long long)c * nz;
+  const ColIn in = col_in(a, c);  // (the angle-independent part of G once per thread)
+  const int kind = in.kind;
+  const double param = in.param, gden = in.gden;
+  const double* tab = in.tab;
+  const double* lai = in.lai;
   const int reclen = rec_len(a.scheme, nz);
   double* rec = a.ws + (long long)c * reclen;
 
-  const double gden = tab ? 0.0 : G_den(kind, param);  // angle-independent part of G, once per thread
-  for (int q = tid; q < NQT; q += K0_BLOCK) {
-    const double g = tab ? tab[q] : G_eval(kind, param, gden, qc.cs[q], qc.sn[q]);
-    kq[q] = g / qc.cs[q];
-    pmb[q] = qc.w[q] * qc.cs[q] * qc.sn[q] / g;
-  }
+  for (int q = tid; q < NQT; q += K0_BLOCK) col_node(in, q, kq[q], pmb[q]);
   if (a.scheme == CRT_SCHEME_4S && tid < NQG) {
     const int iv = tid / NGL, i = tid % NGL;
     double lo, hi;
@@ -196,58 +172,24 @@ __global__ __launch_bounds__(K0_BLOCK) void k_colpre(ColArgs a) {
 
   // ---- header: wave 0, reductions by shuffles ----
   if (wave == 0) {
-    const double psi = a.psi[c];
-    const double cs = cos(psi), sn = sin(psi);
-    const double G = tab ? a.g_at_psi[c] : G_eval(kind, param, gden, cs, sn);
-    const double Kb = G / cs;
-    // uniform-dlai detection (lets the solve kernels advance exponentials by recurrence)
-    const double dl = (lai[0] - lai[nz - 1]) / (nz - 1);
-    const double tol = 4.0 * 2.220446049250313e-16 * fabs(lai[0]);
-    bool ok = dl > 0.0;
-    double dsum = 0.0;  // zq: sum and count of the non-zero diff(lai)   _solve_zq.py:30,50
-    double dcnt = 0.0;
-    for (int j = lane; j + 1 < nz; j += 64) {
-      const double d = lai[j] - lai[j + 1];
-      ok = ok && fabs(d - dl) <= tol;
-      if (d != 0.0) {
-        dsum -= d;  // diff(lai) = lai[j+1] - lai[j]
-        dcnt += 1.0;
-      }
-    }
-    const bool unif = __all(ok);
+    const ColSun sun = col_sun(a, c, in);
+    const ColDl dls = col_dl(in, nz, lane);
+    const double Kb = sun.Kb;
     double mubar = 0.0, g1 = 0.0, g2 = 0.0, dlm = 0.0;
-    if (a.scheme == CRT_SCHEME_2S) mubar = wave_sum64(pmb[lane] + (lane < NQT - 64 ? pmb[64 + lane] : 0.0));
+    if (a.scheme == CRT_SCHEME_2S) mubar = col_mubar(pmb[lane], lane < NQT - 64 ? pmb[64 + lane] : 0.0, lane);
     if (a.scheme == CRT_SCHEME_4S) {
       g1 = wave_sum64(lane < NGL ? pg[lane] : 0.0);
       g2 = wave_sum64(lane < NGL ? pg[NGL + lane] : 0.0);
     }
-    if (a.scheme == CRT_SCHEME_ZQ) dlm = fabs(wave_sum64(dsum) / wave_sum64(dcnt));
+    if (a.scheme == CRT_SCHEME_ZQ) dlm = fabs(wave_sum64(dls.dsum) / wave_sum64(dls.dcnt));
     if (lane == 0) {
-      rec[S_KB] = Kb;
-      rec[S_MU] = cs;
-      rec[S_G] = G;
-      rec[S_MUBAR] = mubar;
-      rec[S_GINT1] = g1;
-      rec[S_GINT2] = g2;
-      rec[S_DLM] = dlm;
-      rec[S_TAUI] = 0.0;
-      rec[S_TPSI] = a.scheme == CRT_SCHEME_ZQ ? fexp(-Kb * dlm) : 0.0;  // _solve_zq.py:52
-      double cos2 = 0.0;
-      if (a.scheme == CRT_SCHEME_2S) {
-        const double cm = cos(a.mla[c] * (M_PI / 180.0));
-        cos2 = cm * cm;
-      }
-      rec[S_COS2] = cos2;
-      rec[S_LT] = lai[0];
-      rec[S_INVMU] = 1.0 / cs;
-      rec[S_UNIF] = unif ? 1.0 : 0.0;
-      rec[S_DL] = dl;
-      rec[S_M] = (double)zqpa_M(nz);
-      rec[15] = 0.0;
+      const double tpsi = a.scheme == CRT_SCHEME_ZQ ? fexp(-Kb * dlm) : 0.0;  // _solve_zq.py:52
+      const double cos2 = a.scheme == CRT_SCHEME_2S ? col_cos2(a.mla[c]) : 0.0;
+      col_header(rec, sun, dls, mubar, g1, g2, dlm, tpsi, cos2, lai[0], nz);
       sh_kb = Kb;
       sh_dlm = dlm;
-      sh_dl = dl;
-      sh_unif = unif ? 1 : 0;
+      sh_dl = dls.dl;
+      sh_unif = dls.unif ? 1 : 0;
     }
   }
   __syncthreads();
@@ -348,7 +290,7 @@ __global__ __launch_bounds__(K0_BLOCK) void k_colpre(ColArgs a) {
   double* v = rec + REC_HDR;
   for (int j = tid; j < nz; j += K0_BLOCK) {
     const double L = lai[j];
-    const double ekl = fexp(-Kb * L);
+    const double ekl = col_ekl(Kb, L);
     switch (a.scheme) {
       case CRT_SCHEME_ZQ:
         v[j] = ekl;
@@ -451,9 +393,11 @@ int init_quadrature(hipStream_t s) {
   if (dev < 0 || dev >= 64) return CRT_ERR_UNSUPPORTED;
   std::lock_guard<std::mutex> lk(dev_mu);
   if (!dev_inited[dev]) {
-    // first call on this device only; not capturable into a hipGraph (documented in DESIGN.md)
+    // first call on this device only; not capturable into a hipGraph (documented in DESIGN.md).  Every unit whose kernels read the
+    // tables has its own copy (col_record.hpp): this one (k_colpre, k_tau_d) and solve_closed.hip (the 2s k_pipe's record prologue).
     if (hipMemcpyToSymbolAsync(HIP_SYMBOL(qc), &h_qc, sizeof(QuadConst), 0, hipMemcpyHostToDevice, s) != hipSuccess)
       return CRT_ERR_LAUNCH;
+    if (upload_quad_closed(h_qc, s) != CRT_OK) return CRT_ERR_LAUNCH;
     if (hipStreamSynchronize(s) != hipSuccess) return CRT_ERR_LAUNCH;
     dev_inited[dev] = true;
   }

@@ -89,7 +89,8 @@ struct SolveArgs {
   // waves (<= 12) (tri_tile_impl.hpp, tri_zqpa.hip); [12] smallest nb that takes the tile / pipeline kernels (0 = default);
   // [13] 1 = no flat fused flush for odd nb (per-array generic flush instead), 2 / 3 = its part-line / whole-line form (0: whole lines for
   // zq and zq_pa, part-lines for n79); [5] column packing of narrow spectra (k_pipe_pack, packed k_tri_pipe): 1 = off, 2 = closed forms also
-  // above 32 bands, [6] compute waves of a pack (<= 4); [7], [14], [15] reserved (zero)
+  // above 32 bands, [6] compute waves of a pack (<= 4); [15] 1 = k_colpre in front of the 2s k_pipe instead of its record prologue; [7], [14]
+  // reserved (zero)
   int tune[CRT_NTUNE];
 };
 
@@ -578,7 +579,8 @@ int launch_tridiag_int(int scheme, const SolveArgs& a, const IntArgs& ia, hipStr
 
 // launchers implemented in the .hip files
 int launch_colpre(const ColArgs& a, hipStream_t s);
-int launch_closed(int scheme, const SolveArgs& a, hipStream_t s, int force);
+// k0: column records still to be formed (2s: by the k_pipe prologue when k_pipe is picked; otherwise k_colpre runs first), or nullptr
+int launch_closed(int scheme, const SolveArgs& a, hipStream_t s, int force, const ColArgs* k0);
 int launch_tridiag(int scheme, const SolveArgs& a, hipStream_t s, int force);
 int init_quadrature(hipStream_t s);
 int launch_tau_d(const double* kb_nodes, const double* L, long long n, int method, double* out, hipStream_t s);

@@ -18,14 +18,15 @@
 //           band) fill a T-level LDS tile laid out exactly like the output run ([ncol][nz][nb] with bands contiguous:
 //           T consecutive levels of a column are ONE contiguous run of T*nb elements) while 1-3 STORE WAVES stream the
 //           previous tile out with 16-B-per-lane non-temporal stores (whole 128-B lines; double-buffered, one LDS-only
-//           barrier per tile).  Odd nb: the generic flush carries the part-line across tiles (whole lines only).
+//           barrier per tile).  Odd nb: the generic flush carries the part-line across tiles (whole lines only).  2s: the workgroup
+//           forms its column's K0 record itself (col_record.hpp) unless the call skips the precompute: one launch per call.
 //  k_tile   (tiles too large for two buffers -- g77 / bf at 300 bands -- or several narrow columns per workgroup): the same
 //           tile, all waves alternate between the level arithmetic and the flush.
 //  k_direct (nb < 4, or no tile fits in LDS): lanes store their own band per level.
 #include <algorithm>
 #include <type_traits>
 
-#include "crt_internal.hpp"
+#include "col_record.hpp"
 
 namespace crt {
 namespace {
@@ -660,8 +661,11 @@ struct PipeTileCfg {
   int rec_dbl;  // doubles reserved for the staged column record
 };
 
-template <class S, typename TIO, int MAXT, bool FUSED>
-__global__ __launch_bounds__(MAXT) void k_pipe(SolveArgs a, PipeTileCfg cfg) {
+// K0 (2s only): the workgroup forms its column's record itself (col_record_2s) instead of reading what k_colpre wrote -- one kernel per
+// solve step instead of two.  The band spectra are requested first, so that their latency overlaps the record's arithmetic.
+template <class S, typename TIO, int MAXT, bool FUSED, bool K0 = false>
+__global__ __launch_bounds__(MAXT) void k_pipe(SolveArgs a, PipeTileCfg cfg, ColArgs ca) {
+  static_assert(!K0 || std::is_same<S, Sch2s>::value, "the record prologue forms the 2s record only");
   constexpr int VW = 16 / (int)sizeof(TIO);
   typedef TIO vt __attribute__((ext_vector_type(VW)));
   extern __shared__ double lds[];
@@ -680,7 +684,9 @@ __global__ __launch_bounds__(MAXT) void k_pipe(SolveArgs a, PipeTileCfg cfg) {
   // instead of two before the first level can be formed
   BandIn bin = {};
   if (tid < cfg.ncomp) bin = load_band<TIO>(a, c, tid < nb ? tid : 0, S::SOIL);
-  {
+  if constexpr (K0) {
+    col_record_2s(ca, c, lds, tid, blockDim.x);
+  } else {
     const double* src = a.ws + (long long)c * a.reclen;
     for (int i = threadIdx.x; i < a.reclen; i += blockDim.x) lds[i] = src[i];
   }
@@ -930,8 +936,12 @@ constexpr int MIN_TILE_NB = 4;
 
 int gcd(int x, int y) { return y ? gcd(y, x % y) : x; }
 
+// k0 != nullptr: the caller left the column precompute to this launcher.  The 2s k_pipe forms the records itself (K0 prologue); every
+// other kernel reads them from the workspace, so k_colpre runs first -- launched right before that kernel, once it is certain to run.
+int k0_before(const ColArgs* k0, hipStream_t s) { return k0 ? launch_colpre(*k0, s) : (int)CRT_OK; }
+
 template <class S, typename TIO>
-int launch_tile(const SolveArgs& a, hipStream_t s, bool& done) {
+int launch_tile(const SolveArgs& a, hipStream_t s, bool& done, const ColArgs* k0) {
   done = false;
   const int nb = a.nb;
   int g_tune[8];  // this call's overrides (crt_options.tune); [0] = 0 means the default LDS budget
@@ -964,6 +974,7 @@ int launch_tile(const SolveArgs& a, hipStream_t s, bool& done) {
         if (shp > 64 * 1024 &&
             hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shp) != hipSuccess)
           return (int)CRT_ERR_LAUNCH;
+        if (const int st = k0_before(k0, s)) return st;
         hipLaunchKernelGGL(kern, dim3((a.ncol + cpw - 1) / cpw), dim3(thr), shp, s, a, pc);
         if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
         note_kernel("k_pipe_pack<%s,%s> columns=%d compute_waves=%d T=%d store_waves=%d lds=%zu", S::NAME, sizeof(TIO) == 8 ? "f64" : "f32", pc.cpw,
@@ -1044,18 +1055,29 @@ int launch_tile(const SolveArgs& a, hipStream_t s, bool& done) {
     const size_t psh = pc.rec_dbl * sizeof(double) + 2 * plevel * Tp + (fused ? 0 : 2 * S::NARR * 128);
     if (nsw >= 1 && Tp >= 2 && psh <= 160 * 1024 && (fused ? (2 * plevel * Ta <= target || g_tune[4] > 0) : true)) {
       const int pthr = pcomp + 64 * nsw;
+      // the 2s record prologue (tune key 15 = 1 keeps k_colpre in front of the solve: A/B; solve_impl passes no k0 then)
+      constexpr bool can_k0 = std::is_same<S, Sch2s>::value;
+      const bool own_k0 = can_k0 && k0 != nullptr;
       auto gop = [&](auto kern) {
         if (psh > 64 * 1024 &&
             hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)psh) != hipSuccess)
           return (int)CRT_ERR_LAUNCH;
-        hipLaunchKernelGGL(kern, dim3(a.ncol), dim3(pthr), psh, s, a, pc);
+        if (!own_k0)
+          if (const int st = k0_before(k0, s)) return st;
+        hipLaunchKernelGGL(kern, dim3(a.ncol), dim3(pthr), psh, s, a, pc, own_k0 ? *k0 : ColArgs{});
         if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
-        note_kernel("k_pipe<%s,%s>%s T=%d store_waves=%d lds=%zu", S::NAME, sizeof(TIO) == 8 ? "f64" : "f32", fused ? "" : " generic-flush", Tp, nsw, psh);  // (only a launch that succeeded is reported)
+        note_kernel("k_pipe<%s,%s>%s T=%d store_waves=%d lds=%zu%s", S::NAME, sizeof(TIO) == 8 ? "f64" : "f32", fused ? "" : " generic-flush", Tp, nsw, psh,
+                    own_k0 ? " k0=fused" : "");  // (only a launch that succeeded is reported)
         return (int)CRT_OK;
       };
       int st;
-      if (fused) st = pthr <= 512 ? gop(k_pipe<S, TIO, 512, true>) : gop(k_pipe<S, TIO, 1024, true>);
-      else st = pthr <= 512 ? gop(k_pipe<S, TIO, 512, false>) : gop(k_pipe<S, TIO, 1024, false>);
+      if (own_k0) {
+        if (fused) st = pthr <= 512 ? gop(k_pipe<S, TIO, 512, true, can_k0>) : gop(k_pipe<S, TIO, 1024, true, can_k0>);
+        else st = pthr <= 512 ? gop(k_pipe<S, TIO, 512, false, can_k0>) : gop(k_pipe<S, TIO, 1024, false, can_k0>);
+      } else {
+        if (fused) st = pthr <= 512 ? gop(k_pipe<S, TIO, 512, true>) : gop(k_pipe<S, TIO, 1024, true>);
+        else st = pthr <= 512 ? gop(k_pipe<S, TIO, 512, false>) : gop(k_pipe<S, TIO, 1024, false>);
+      }
       done = st == CRT_OK;
       return st;
     }
@@ -1064,6 +1086,7 @@ int launch_tile(const SolveArgs& a, hipStream_t s, bool& done) {
     if (sh > 64 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
       return (int)CRT_ERR_LAUNCH;
+    if (const int st = k0_before(k0, s)) return st;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(nthr), sh, s, a, cfg);
     if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
     note_kernel("k_tile<%s,%s>%s CB=%d T=%d lds=%zu", S::NAME, sizeof(TIO) == 8 ? "f64" : "f32", fused ? "" : " generic-flush", CB, T, sh);  // (only a launch that succeeded is reported)
@@ -1095,12 +1118,13 @@ int launch_direct_v(const SolveArgs& a, size_t lds_bytes, hipStream_t s) {
 }
 
 template <class S, typename TIO>
-int launch_scheme(const SolveArgs& a, hipStream_t s, int force) {
+int launch_scheme(const SolveArgs& a, hipStream_t s, int force, const ColArgs* k0) {
   if (force != 1) {
     bool done;
-    int st = launch_tile<S, TIO>(a, s, done);
+    int st = launch_tile<S, TIO>(a, s, done, k0);
     if (st != CRT_OK || done) return st;
   }
+  if (const int st = k0_before(k0, s)) return st;
   // two bands per lane when rows keep the alignment of a 2-element vector, else one
   bool vec2 = (a.nb % 2 == 0) && (a.col_stride % 2 == 0);
   for (int i = 0; i < S::NARR && vec2; ++i)
@@ -1115,8 +1139,8 @@ int launch_scheme(const SolveArgs& a, hipStream_t s, int force) {
 }
 
 template <class S>
-int launch_io(const SolveArgs& a, hipStream_t s, int force) {
-  return a.f32 ? launch_scheme<S, float>(a, s, force) : launch_scheme<S, double>(a, s, force);
+int launch_io(const SolveArgs& a, hipStream_t s, int force, const ColArgs* k0) {
+  return a.f32 ? launch_scheme<S, float>(a, s, force, k0) : launch_scheme<S, double>(a, s, force, k0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1208,16 +1232,21 @@ int launch_closed_int(int scheme, const SolveArgs& a, const IntArgs& ia, hipStre
   }
 }
 
-// force: 0 = pick (tile when it applies), 1 = direct-store kernel (kept selectable for A/B measurements)
-int launch_closed(int scheme, const SolveArgs& a, hipStream_t s, int force) {
+// force: 0 = pick (tile when it applies), 1 = direct-store kernel (kept selectable for A/B measurements).  k0: see k0_before.
+int launch_closed(int scheme, const SolveArgs& a, hipStream_t s, int force, const ColArgs* k0) {
   switch (scheme) {
-    case CRT_SCHEME_2S: return launch_io<Sch2s>(a, s, force);
-    case CRT_SCHEME_4S: return launch_io<Sch4s>(a, s, force);
-    case CRT_SCHEME_BL: return launch_io<SchBl>(a, s, force);
-    case CRT_SCHEME_G77: return launch_io<SchG77<false>>(a, s, force);
-    case CRT_SCHEME_BF: return launch_io<SchG77<true>>(a, s, force);
+    case CRT_SCHEME_2S: return launch_io<Sch2s>(a, s, force, k0);
+    case CRT_SCHEME_4S: return launch_io<Sch4s>(a, s, force, k0);
+    case CRT_SCHEME_BL: return launch_io<SchBl>(a, s, force, k0);
+    case CRT_SCHEME_G77: return launch_io<SchG77<false>>(a, s, force, k0);
+    case CRT_SCHEME_BF: return launch_io<SchG77<true>>(a, s, force, k0);
     default: return CRT_ERR_BAD_ARG;
   }
+}
+
+int upload_quad_closed(const QuadConst& h, hipStream_t s) {
+  return hipMemcpyToSymbolAsync(HIP_SYMBOL(qc), &h, sizeof(QuadConst), 0, hipMemcpyHostToDevice, s) == hipSuccess ? (int)CRT_OK
+                                                                                                                   : (int)CRT_ERR_LAUNCH;
 }
 
 }  // namespace crt
