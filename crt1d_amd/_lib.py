@@ -60,9 +60,59 @@ class CrtBands(ctypes.Structure):
 
 NTUNE = 16
 
+# crt_options.tune: keys (enum crt_tune_key; what each one selects is documented there) and the named values of some of them.
+# 0 is automatic for every key; 7 and 14 are reserved.
+TUNE_TILE_LDS = 0
+TUNE_TILE_T = 1
+TUNE_TILE_FLAGS = 2
+TUNE_CLOSED_STORE_WAVES = 3
+TUNE_CLOSED_PIPE_T = 4
+TUNE_PACK = 5
+TUNE_PACK_COMPUTE_WAVES = 6
+TUNE_TRI_M = 8
+TUNE_TRI_T = 9
+TUNE_TRI_FAMILY = 10
+TUNE_TRI_STORE_WAVES = 11
+TUNE_MIN_TILE_NB = 12
+TUNE_FLAT_FLUSH = 13
+TUNE_K0_SEPARATE = 15
+# TUNE_TILE_FLAGS bits (enum crt_tune_tile_flag)
+TILE_FLAG_SYNC_BARRIERS = 1
+TILE_FLAG_GENERIC_FLUSH = 2
+TILE_FLAG_NO_PIPELINE = 4
+TILE_FLAG_NO_GENERIC_PIPELINE = 8
+TILE_FLAG_FOUR_PAIR_STORE = 16
+# TUNE_PACK values (enum crt_tune_pack)
+PACK_OFF = 1
+PACK_FORCE = 2
+# TUNE_TRI_FAMILY values (enum crt_tune_tri_family); zq_pa reads 1 as its two-kernel path
+TRI_FAMILY_NO_PIPELINE = 1
+TRI_FAMILY_DOUBLE_BUFFERED = 2
+TRI_FAMILY_REG_STAGED = 3
+TRI_FAMILY_GENERIC_PIPELINE = 4
+TRI_FAMILY_ZQPA_TWO_KERNEL = 1
+TRI_FAMILY_ZQPA_PIPE = 5
+TRI_FAMILY_ZQPA_PIPE2_DB = 6
+TRI_FAMILY_ZQPA_PIPE2_RS = 7
+# TUNE_FLAT_FLUSH values (enum crt_tune_flat_flush)
+FLAT_FLUSH_OFF = 1
+FLAT_FLUSH_PART_LINE = 2
+FLAT_FLUSH_WHOLE_LINE = 3
+
 
 class CrtOptions(ctypes.Structure):
     _fields_ = [("mu_s", ctypes.c_double), ("tau_d_method", ctypes.c_int32), ("flags", ctypes.c_int32), ("tune", ctypes.c_int32 * NTUNE)]
+
+
+def set_tune(opts, tune):
+    """Write the overrides ``{key: value}`` (keys ``TUNE_*``) into ``opts.tune``; keys not given are 0 (automatic).  A key outside
+    ``range(NTUNE)`` is a ValueError; the values are checked by the library, at the call."""
+    for k in tune:
+        if not isinstance(k, int) or not 0 <= k < NTUNE:
+            raise ValueError(f"unknown crt_options.tune key {k!r}: keys are the TUNE_* constants, 0 .. {NTUNE - 1}")
+    for k in range(NTUNE):
+        opts.tune[k] = int(tune.get(k, 0))
+    return opts
 
 
 class CrtOutputs(ctypes.Structure):

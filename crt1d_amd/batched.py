@@ -428,10 +428,9 @@ class Plan:
         self.placement_report = {"allocator": "crt_hip_buffer_alloc_set", "classes": cls} if any(cls.values()) else None
 
     def set_tune(self, tune):
-        """Measurement aid: per-plan overrides of the kernel-selection heuristics (``crt_options.tune``; keys in
-        csrc/crt_internal.hpp).  ``{}`` = automatic.  They travel with every call of this plan -- no process-global state."""
-        for k in range(_lib.NTUNE):
-            self._o.tune[k] = int(tune.get(k, 0))
+        """Measurement aid: per-plan overrides of the kernel-selection heuristics (``crt_options.tune``; keys ``_lib.TUNE_*``,
+        documented in include/crt1d_hip.h).  ``{}`` = automatic.  They travel with every call of this plan -- no process-global state."""
+        _lib.set_tune(self._o, tune)
         return self
 
     def last_kernel(self):

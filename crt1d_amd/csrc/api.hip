@@ -3,6 +3,7 @@
 #include <math.h>
 
 #include <algorithm>
+#include <cstring>
 #include <type_traits>
 
 #include "crt_internal.hpp"
@@ -1253,26 +1254,32 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
   if (scheme == CRT_SCHEME_N79 && nz < 3) return CRT_ERR_SHAPE;  // td[1]/tb[1] of _solve_n79.py:85-92
   double mu_s = 0.501;
   int method = CRT_TAU_D_QUAD, flags = 0;
-  int tune[CRT_NTUNE] = {};
+  int32_t tune[CRT_NTUNE] = {};
   if (opts) {
     mu_s = opts->mu_s;
     method = opts->tau_d_method;
     flags = opts->flags;
-    for (int i = 0; i < CRT_NTUNE; ++i) tune[i] = opts->tune[i];
+    std::memcpy(tune, opts->tune, sizeof tune);
   }
-  {  // crt_options.tune is a measurement aid, but it is part of the ABI: out-of-range values are rejected here, before any launch,
-     // instead of reaching the kernel configurations (keys: crt_internal.hpp, SolveArgs::tune)
-    static const struct { int key, lo, hi; } range[] = {
-        {0, 0, 160 * 1024}, {1, 0, 64}, {2, 0, 255}, {3, 0, 12}, {4, 0, 32}, {8, 0, 16}, {9, 0, 12}, {10, 0, 7}, {11, 0, 12}, {12, 0, 1024}, {13, 0, 3}, {5, 0, 2}, {6, 0, 4}, {15, 0, 1}};
+  {  // crt_options.tune is a measurement aid, but it is part of the ABI: values out of range are rejected here, before any launch,
+     // instead of reaching the kernel configurations.  A key takes 0 (automatic) or lo, lo + step, ... up to hi; a key absent from the
+     // table is reserved and stays 0.
+    static const struct { int key, lo, hi, step; } accepted[] = {
+        {CRT_TUNE_TILE_LDS, 1, 160 * 1024, 1},           {CRT_TUNE_TILE_T, 1, 64, 1},
+        {CRT_TUNE_TILE_FLAGS, 1, 255, 1},                {CRT_TUNE_CLOSED_STORE_WAVES, 1, 12, 1},
+        {CRT_TUNE_CLOSED_PIPE_T, 1, 32, 1},              {CRT_TUNE_PACK, CRT_PACK_OFF, CRT_PACK_FORCE, 1},
+        {CRT_TUNE_PACK_COMPUTE_WAVES, 1, 4, 1},          {CRT_TUNE_TRI_M, 8, 16, 4},
+        {CRT_TUNE_TRI_T, 4, 12, 4},                      {CRT_TUNE_TRI_FAMILY, 1, CRT_TRI_FAMILY_ZQPA_PIPE2_RS, 1},
+        {CRT_TUNE_TRI_STORE_WAVES, 1, 12, 1},            {CRT_TUNE_MIN_TILE_NB, 1, 1024, 1},
+        {CRT_TUNE_FLAT_FLUSH, CRT_FLAT_FLUSH_OFF, CRT_FLAT_FLUSH_WHOLE_LINE, 1}, {CRT_TUNE_K0_SEPARATE, 1, 1, 1}};
     bool known[CRT_NTUNE] = {};
-    for (const auto& r : range) {
+    for (const auto& r : accepted) {
+      const int v = tune[r.key];
       known[r.key] = true;
-      if (tune[r.key] < r.lo || tune[r.key] > r.hi) return CRT_ERR_BAD_ARG;
+      if (v != 0 && (v < r.lo || v > r.hi || (v - r.lo) % r.step != 0)) return CRT_ERR_BAD_ARG;
     }
-    if (tune[8] != 0 && tune[8] != 8 && tune[8] != 12 && tune[8] != 16) return CRT_ERR_BAD_ARG;
-    if (tune[9] != 0 && tune[9] != 4 && tune[9] != 8 && tune[9] != 12) return CRT_ERR_BAD_ARG;
     for (int i = 0; i < CRT_NTUNE; ++i)
-      if (!known[i] && tune[i] != 0) return CRT_ERR_BAD_ARG;  // reserved keys stay zero
+      if (!known[i] && tune[i] != 0) return CRT_ERR_BAD_ARG;
   }
   if (scheme == CRT_SCHEME_4S && !(mu_s > 0.0 && mu_s < 1.0)) return CRT_ERR_BAD_ARG;
   if (method != CRT_TAU_D_QUAD && method != CRT_TAU_D_9SKY) return CRT_ERR_BAD_ARG;  // ValueError, common.py:78
@@ -1295,9 +1302,9 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
   ca.g_table = cols->g_table;
   ca.ws = static_cast<double*>(workspace);
   // 2s profiles: the closed-form launcher forms the records inside k_pipe when it picks that kernel (one launch per call), and runs
-  // k_colpre in front of any other kernel.  SKIP_PRECOMPUTE / PRECOMPUTE_ONLY and tune key 15 keep k_colpre as a kernel of its own.
+  // k_colpre in front of any other kernel.  SKIP_PRECOMPUTE / PRECOMPUTE_ONLY and CRT_TUNE_K0_SEPARATE keep k_colpre as a kernel of its own.
   const bool k0_in_solve = scheme == CRT_SCHEME_2S && !integ && !(flags & (CRT_FLAG_SKIP_PRECOMPUTE | CRT_FLAG_PRECOMPUTE_ONLY)) &&
-                           tune[15] == 0;
+                           tune[CRT_TUNE_K0_SEPARATE] == 0;
   if (k0_in_solve) {
     const int st = init_quadrature(s);
     if (st != CRT_OK) return st;
@@ -1328,7 +1335,7 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
   sa.o[6] = out->x2;
   sa.mu_s = mu_s;
   sa.f32 = f32;
-  for (int i = 0; i < CRT_NTUNE; ++i) sa.tune[i] = tune[i];
+  std::memcpy(&sa.tune, tune, sizeof sa.tune);
   if (integ) {
     if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_int(sa, *integ, s);
     return tri ? launch_tridiag_int(scheme, sa, *integ, s) : launch_closed_int(scheme, sa, *integ, s);

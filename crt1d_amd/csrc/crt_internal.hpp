@@ -1,6 +1,7 @@
 // Internal declarations shared by the gfx950 kernels of libcrt1d_hip.so.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "crt1d_hip.h"
@@ -65,6 +66,27 @@ struct ColArgs {
   double* ws;  // [ncol][rec_len]
 };
 
+// Kernel-selection overrides of one call: crt_options.tune with a field per key (include/crt1d_hip.h, enum crt_tune_key), validated by
+// solve_impl (api.hip).  0 = automatic everywhere.
+struct Tune {
+  int32_t tile_lds, tile_t, tile_flags, closed_store_waves, closed_pipe_t, pack, pack_compute_waves, reserved7;
+  int32_t tri_m, tri_t, tri_family, tri_store_waves, min_tile_nb, flat_flush, reserved14, k0_separate;
+  // smallest nb that takes the tile / pipeline kernels: CRT_TUNE_MIN_TILE_NB, or the launcher's own default when that is 0
+  int min_nb(int launcher_default) const { return min_tile_nb > 0 ? min_tile_nb : launcher_default; }
+};
+// the fields lie in key order, so that SolveArgs keeps the layout it had with int tune[CRT_NTUNE] (and the kernels their ISA)
+static_assert(sizeof(Tune) == CRT_NTUNE * sizeof(int32_t), "Tune is crt_options.tune");
+static_assert(offsetof(Tune, tile_lds) == 4 * CRT_TUNE_TILE_LDS && offsetof(Tune, tile_t) == 4 * CRT_TUNE_TILE_T &&
+                  offsetof(Tune, tile_flags) == 4 * CRT_TUNE_TILE_FLAGS &&
+                  offsetof(Tune, closed_store_waves) == 4 * CRT_TUNE_CLOSED_STORE_WAVES &&
+                  offsetof(Tune, closed_pipe_t) == 4 * CRT_TUNE_CLOSED_PIPE_T && offsetof(Tune, pack) == 4 * CRT_TUNE_PACK &&
+                  offsetof(Tune, pack_compute_waves) == 4 * CRT_TUNE_PACK_COMPUTE_WAVES &&
+                  offsetof(Tune, tri_m) == 4 * CRT_TUNE_TRI_M && offsetof(Tune, tri_t) == 4 * CRT_TUNE_TRI_T &&
+                  offsetof(Tune, tri_family) == 4 * CRT_TUNE_TRI_FAMILY && offsetof(Tune, tri_store_waves) == 4 * CRT_TUNE_TRI_STORE_WAVES &&
+                  offsetof(Tune, min_tile_nb) == 4 * CRT_TUNE_MIN_TILE_NB && offsetof(Tune, flat_flush) == 4 * CRT_TUNE_FLAT_FLUSH &&
+                  offsetof(Tune, k0_separate) == 4 * CRT_TUNE_K0_SEPARATE,
+              "every field of Tune lies at its key");
+
 // Spectra and output profiles are stored as TIO = double (crt_hip_*_f64) or float (crt_hip_*_f32); the per-column
 // geometry, the K0 records and ALL arithmetic are fp64 in both cases (the f32 entry points halve the HBM bytes, they
 // do not lower the precision of the solve: results are the fp64 results rounded once to fp32).
@@ -80,18 +102,7 @@ struct SolveArgs {
   void* o[7];  // I_dr, I_df_d, I_df_u, F, x0, x1, x2
   double mu_s;
   int f32;     // 0: TIO = double, 1: TIO = float
-  // kernel-selection overrides of THIS call (crt_options.tune; 0 = automatic; validated by solve_impl, api.hip: out-of-range values and
-  // non-zero reserved keys are CRT_ERR_BAD_ARG): [0] LDS bytes a closed-form tile may take (<= 160 KB), [1] force T of k_tile (<= 64),
-  // [2] flags (bit0 __syncthreads barriers, bit1 generic flush, bit2 no pipeline, bit3 no generic-flush pipeline, value 16: four-pair
-  // store role for narrow tridiagonal pipelines), [3] store waves of k_pipe (<= 12), [4] T of k_pipe (<= 32); [8] M (8 / 12 / 16),
-  // [9] T (4 / 8 / 12), [10] kernel family of the tridiagonal kernels (1 no pipeline, 2 double-buffered, 3 register-staged, 4 generic
-  // pipeline; zq_pa: 1 two-kernel path, 5 round-2 fused kernel, 6 / 7 double-buffered / register-staged k_zqpa_pipe2), [11] their store
-  // waves (<= 12) (tri_tile_impl.hpp, tri_zqpa.hip); [12] smallest nb that takes the tile / pipeline kernels (0 = default);
-  // [13] 1 = no flat fused flush for odd nb (per-array generic flush instead), 2 / 3 = its part-line / whole-line form (0: whole lines for
-  // zq and zq_pa, part-lines for n79); [5] column packing of narrow spectra (k_pipe_pack, packed k_tri_pipe): 1 = off, 2 = closed forms also
-  // above 32 bands, [6] compute waves of a pack (<= 4); [15] 1 = k_colpre in front of the 2s k_pipe instead of its record prologue; [7], [14]
-  // reserved (zero)
-  int tune[CRT_NTUNE];
+  Tune tune;   // this call's kernel-selection overrides
 };
 
 // name of the solve kernel the last launch_* call of this thread chose (crt_hip_last_kernel; reporting only)

@@ -554,7 +554,7 @@ struct TileCfg {
   int CB;        // columns per workgroup
   int T;         // levels per LDS tile
   int rec_dbl;   // doubles reserved for the staged column records (CB * reclen, rounded up to even)
-  int flags;     // bit0: full __syncthreads() barriers (A/B aid)
+  int flags;     // CRT_TUNE_TILE_FLAGS (k_tile reads CRT_TILE_FLAG_SYNC_BARRIERS: A/B aid)
 };
 
 
@@ -603,7 +603,7 @@ __global__ __launch_bounds__(MAXT) void k_tile(SolveArgs a, TileCfg cfg) {
         for (int k = 0; k < S::NARR; ++k) tl[k * (CB * colrun) + t * nb] = (TIO)val[k];
       }
     }
-    if (cfg.flags & 1) __syncthreads(); else lds_barrier();
+    if (cfg.flags & CRT_TILE_FLAG_SYNC_BARRIERS) __syncthreads(); else lds_barrier();
     if constexpr (FUSED) {
       if (f_toff < f_rpi) {
         const vt* tv = reinterpret_cast<const vt*>(tile);
@@ -645,7 +645,7 @@ __global__ __launch_bounds__(MAXT) void k_tile(SolveArgs a, TileCfg cfg) {
       }
     }
     }
-    if (cfg.flags & 1) __syncthreads(); else lds_barrier();
+    if (cfg.flags & CRT_TILE_FLAG_SYNC_BARRIERS) __syncthreads(); else lds_barrier();
   }
 }
 
@@ -923,8 +923,7 @@ __global__ __launch_bounds__(MAXT) void k_pipe_pack(SolveArgs a, PackCfg cfg) {
 
 // ------------------------------------------------------------------------------------------
 constexpr int MAX_DIRECT_LDS = 64 * 1024;
-// tunables (crt_options.tune, per call): [0] LDS bytes a tile may take per workgroup, [1] force T (0 = automatic),
-// [2] TileCfg.flags (bit0: __syncthreads barriers, bit1: generic instead of fused flush).  Measured on MI355X, 2s at 1e4 x 300 x 60 (tools/ab_tile.py, interleaved rounds):
+// LDS a tile may take per workgroup (CRT_TUNE_TILE_LDS overrides it).  Measured on MI355X, 2s at 1e4 x 300 x 60 (tools/ab_tile.py, interleaved rounds):
 //   T=2 (not line aligned) 1.66 ms | T=4, 4 WG/CU 1.20 ms | T=8, 2 WG/CU 1.03 ms | T=12, 1 WG/CU 1.25 ms
 // -> take the longest line-aligned run that still leaves two workgroups resident per CU (160 KB LDS).
 constexpr int DEFAULT_TILE_LDS = 78 * 1024;
@@ -944,29 +943,26 @@ template <class S, typename TIO>
 int launch_tile(const SolveArgs& a, hipStream_t s, bool& done, const ColArgs* k0) {
   done = false;
   const int nb = a.nb;
-  int g_tune[8];  // this call's overrides (crt_options.tune); [0] = 0 means the default LDS budget
-  for (int i = 0; i < 8; ++i) g_tune[i] = a.tune[i];
-  if (g_tune[0] <= 0) g_tune[0] = DEFAULT_TILE_LDS;
-  const int min_nb = a.tune[12] > 0 ? a.tune[12] : MIN_TILE_NB;
-  if (nb < min_nb || nb > 1024) return CRT_OK;
-  // very narrow spectra: several columns per compute wave (tune key 5 = 1 keeps one column per workgroup: A/B)
-  if ((nb <= 32 || a.tune[5] == 2) && nb <= 128 && a.tune[5] != 1) {
+  const Tune& tune = a.tune;
+  if (nb < tune.min_nb(MIN_TILE_NB) || nb > 1024) return CRT_OK;
+  // very narrow spectra: several columns per compute wave (CRT_PACK_OFF keeps one column per workgroup: A/B)
+  if ((nb <= 32 || tune.pack == CRT_PACK_FORCE) && nb <= 128 && tune.pack != CRT_PACK_OFF) {
     constexpr int VWp = 16 / (int)sizeof(TIO);
     bool ok = nb % VWp == 0 && (a.nz * nb) % VWp == 0;
     for (int i = 0; i < S::NARR && ok; ++i)
       if (reinterpret_cast<uintptr_t>(a.o[i]) & 15) ok = false;
     if (ok) {
       PackCfg pc;
-      pc.ncw = a.tune[6] > 0 ? a.tune[6] : (nb <= 32 ? 1 : 2);
+      pc.ncw = tune.pack_compute_waves > 0 ? tune.pack_compute_waves : (nb <= 32 ? 1 : 2);
       if (64 * pc.ncw < nb) pc.ncw = (nb + 63) / 64;
       pc.cpw = 64 * pc.ncw / nb;
       const int linep = 128 / (int)sizeof(TIO);
       const int Tap = linep / gcd(nb, linep);  // levels per line-aligned run
-      int Tp = a.tune[4] > 0 ? a.tune[4] : std::max(4, Tap);
+      int Tp = tune.closed_pipe_t > 0 ? tune.closed_pipe_t : std::max(4, Tap);
       if (Tp > a.nz) Tp = a.nz;
       pc.T = Tp;
       const int cpw = pc.cpw;
-      const int nswp = a.tune[3] > 0 ? a.tune[3] : 1;
+      const int nswp = tune.closed_store_waves > 0 ? tune.closed_store_waves : 1;
       const size_t shp = (size_t)((cpw * a.reclen + 1) & ~1) * sizeof(double) + (size_t)2 * cpw * S::NARR * Tp * nb * sizeof(TIO);
       const int thr = 64 * (pc.ncw + nswp);
       if (shp <= 160 * 1024 && thr <= 512 && (Tp * nb) % VWp == 0) {
@@ -989,7 +985,7 @@ int launch_tile(const SolveArgs& a, hipStream_t s, bool& done, const ColArgs* k0
   const int line = 128 / (int)sizeof(TIO);  // elements per 128-B line
   const int Ta = line / gcd(nb, line);      // levels per line-aligned run
   const size_t per_level = (size_t)S::NARR * CB * nb * sizeof(TIO);
-  const size_t target = (size_t)g_tune[0];
+  const size_t target = (size_t)(tune.tile_lds > 0 ? tune.tile_lds : DEFAULT_TILE_LDS);
   int T = Ta;
   if (per_level * Ta > target) {
     // aligned runs do not fit: fall back to the largest run that does (only its two end lines are partial)
@@ -998,26 +994,26 @@ int launch_tile(const SolveArgs& a, hipStream_t s, bool& done, const ColArgs* k0
   } else {
     while (per_level * (T + Ta) <= target && T + Ta <= a.nz) T += Ta;
   }
-  if (g_tune[1] > 0) T = g_tune[1];
+  if (tune.tile_t > 0) T = tune.tile_t;
   if (T > a.nz) T = a.nz;
   TileCfg cfg;
   cfg.CB = CB;
   cfg.T = T;
   cfg.rec_dbl = (CB * a.reclen + 1) & ~1;
-  cfg.flags = g_tune[2];
+  cfg.flags = tune.tile_flags;
   const size_t sh = cfg.rec_dbl * sizeof(double) + (size_t)S::NARR * CB * T * nb * sizeof(TIO);
   if (sh > 160 * 1024) return CRT_OK;
   constexpr int VW = 16 / (int)sizeof(TIO);
-  bool fused = CB == 1 && nb % VW == 0 && !(g_tune[2] & 2);
+  bool fused = CB == 1 && nb % VW == 0 && !(tune.tile_flags & CRT_TILE_FLAG_GENERIC_FLUSH);
   for (int i = 0; i < S::NARR && fused; ++i)
     if (reinterpret_cast<uintptr_t>(a.o[i]) & 15) fused = false;
   const int grid = (a.ncol + CB - 1) / CB;
-  // wave-specialised pipeline, always one column per workgroup (tune [2] bit2 disables it, bit3 disables its generic-flush
-  // form [odd nb, several columns per k_tile workgroup]; [3] = store waves, [4] = its T)
-  bool pfused = nb % VW == 0 && !(g_tune[2] & 2);  // the pipeline always has one column per workgroup
+  // wave-specialised pipeline, always one column per workgroup (CRT_TILE_FLAG_NO_PIPELINE disables it, CRT_TILE_FLAG_NO_GENERIC_PIPELINE
+  // its generic-flush form [odd nb, several columns per k_tile workgroup])
+  bool pfused = nb % VW == 0 && !(tune.tile_flags & CRT_TILE_FLAG_GENERIC_FLUSH);  // the pipeline always has one column per workgroup
   for (int i = 0; i < S::NARR && pfused; ++i)
     if (reinterpret_cast<uintptr_t>(a.o[i]) & 15) pfused = false;
-  if (!(g_tune[2] & 4) && (pfused || !(g_tune[2] & 8))) {
+  if (!(tune.tile_flags & CRT_TILE_FLAG_NO_PIPELINE) && (pfused || !(tune.tile_flags & CRT_TILE_FLAG_NO_GENERIC_PIPELINE))) {
     const bool fused = pfused;  // (shadows k_tile's flag inside this block)
     const int pcomp = ((nb + 63) / 64) * 64;
     const size_t plevel = (size_t)S::NARR * nb * sizeof(TIO);
@@ -1025,7 +1021,7 @@ int launch_tile(const SolveArgs& a, hipStream_t s, bool& done, const ColArgs* k0
     // stores: 2e5 x 38 x 60 2s 2.53 -> 2.47 ms, g77 4.53 -> 4.27; 4e5 x 16 x 60 2s 3.39 -> 2.87, g77 4.52 -> 4.20; 4s already had one)
     // (4s -- heavy per-band set-up -- also takes one store wave with two compute waves and the whole-line generic flush:
     // tools/ab_closed_107.py, 3e4 x 107 x 60 1.09 -> 1.03 ms; not with the fused flush: 25000 x 128 x 60 0.95 -> 0.99)
-    int nsw = g_tune[3] > 0 ? g_tune[3] : (pcomp <= 64 || (S::HEAVY_INIT && pcomp <= 128 && !fused) ? 1 : pcomp <= 128 ? 2 : 3);
+    int nsw = tune.closed_store_waves > 0 ? tune.closed_store_waves : (pcomp <= 64 || (S::HEAVY_INIT && pcomp <= 128 && !fused) ? 1 : pcomp <= 128 ? 2 : 3);
     if (pcomp + 64 * nsw > 1024) nsw = (1024 - pcomp) / 64;
     // Two tile buffers of up to 8 levels, line-aligned runs when they fit, at least two workgroups per CU -- and about four
     // for a scheme with a heavy per-band set-up when the spectrum is narrow enough to allow it.  Measured (tools/ab_shapes.py,
@@ -1045,7 +1041,7 @@ int launch_tile(const SolveArgs& a, hipStream_t s, bool& done, const ColArgs* k0
     if (fused && pcomp <= 64 && nb >= 32 && Tmax > 4) Tmax = 4;  // 32..64 bands: tiles of 4 levels (same measurement: 38 bands, T = 8 -> 4: 2s 2.52 -> 2.47, g77 4.41 -> 4.27)
     if (Tmax < 4 && 2 * plevel * 4 <= target) Tmax = 4;  // not below 4 levels while two workgroups still fit (g77 at nb = 107: T=2 1.96 ms, T=4 1.87)
     int Tp = Ta <= Tmax ? (Tmax / Ta) * Ta : Tmax;
-    if (g_tune[4] > 0) Tp = g_tune[4];
+    if (tune.closed_pipe_t > 0) Tp = tune.closed_pipe_t;
     if (Tp > a.nz) Tp = a.nz;
     PipeTileCfg pc;
     pc.ncomp = pcomp;
@@ -1053,9 +1049,9 @@ int launch_tile(const SolveArgs& a, hipStream_t s, bool& done, const ColArgs* k0
     pc.rec_dbl = (a.reclen + 1) & ~1;
     // two tile buffers (the generic flush adds one line of head-room per array and buffer)
     const size_t psh = pc.rec_dbl * sizeof(double) + 2 * plevel * Tp + (fused ? 0 : 2 * S::NARR * 128);
-    if (nsw >= 1 && Tp >= 2 && psh <= 160 * 1024 && (fused ? (2 * plevel * Ta <= target || g_tune[4] > 0) : true)) {
+    if (nsw >= 1 && Tp >= 2 && psh <= 160 * 1024 && (fused ? (2 * plevel * Ta <= target || tune.closed_pipe_t > 0) : true)) {
       const int pthr = pcomp + 64 * nsw;
-      // the 2s record prologue (tune key 15 = 1 keeps k_colpre in front of the solve: A/B; solve_impl passes no k0 then)
+      // the 2s record prologue (CRT_TUNE_K0_SEPARATE keeps k_colpre in front of the solve: A/B; solve_impl passes no k0 then)
       constexpr bool can_k0 = std::is_same<S, Sch2s>::value;
       const bool own_k0 = can_k0 && k0 != nullptr;
       auto gop = [&](auto kern) {

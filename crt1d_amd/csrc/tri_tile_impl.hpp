@@ -480,7 +480,7 @@ int launch_mt(const SolveArgs& a, hipStream_t s, int nthr) {
   cfg.off_bc = (a.reclen + 1) & ~1;
   cfg.off_ck = cfg.off_bc + ((a.nb + 1) & ~1);
   cfg.off_tile = cfg.off_ck + 2 * cfg.nck * nthr;
-  cfg.flat = (!FUSED && a.tune[13] != 1) ? flat_flush_ok<S, TIO>(a) : 0;
+  cfg.flat = (!FUSED && a.tune.flat_flush != CRT_FLAT_FLUSH_OFF) ? flat_flush_ok<S, TIO>(a) : 0;
   const size_t sh = ((size_t)cfg.off_tile + (size_t)S::NST * T * a.nb) * sizeof(double);
   if (sh > MAX_WG_LDS) return CRT_ERR_UNSUPPORTED;
   const void* fn = nthr <= 256 ? (const void*)k_tri_tile<S, TIO, M, T, 256, FUSED> : nthr <= 512 ? (const void*)k_tri_tile<S, TIO, M, T, 512, FUSED>
@@ -631,8 +631,6 @@ int launch_int_scheme(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
   if (st == CRT_ERR_UNSUPPORTED) st = launch_int_m<S, TIO, 16>(a, ia, s, nthr);
   return st;
 }
-
-// crt_options.tune[8..11]: [8] force M (8/12/16), [9] force T (4/8), [10] kernel family, [11] store waves
 
 // instantiated (M, T) pairs
 template <class S, typename TIO, bool FUSED>
@@ -1074,14 +1072,15 @@ int launch_pipe_generic(const SolveArgs& a, hipStream_t s, int nstore_waves) {
   cfg.off_bc = (a.reclen + 1) & ~1;
   cfg.off_ck = cfg.off_bc + ((a.nb + 1) & ~1);
   cfg.off_tile = cfg.off_ck + 2 * cfg.nck * ncomp;
-  cfg.flat = a.tune[13] != 1 ? flat_flush_ok<S, TIO>(a) : 0;
+  cfg.flat = a.tune.flat_flush != CRT_FLAT_FLUSH_OFF ? flat_flush_ok<S, TIO>(a) : 0;
   cfg.off_park = cfg.off_tile + 2 * S::NST * T * a.nb;
   // Whole lines only -- for schemes whose arrays all have nz rows (zq).  Measured at 3e4 x 107 x 60 (tools/ragged_sweep.py --tune=13:2 /
   // 13:3, same process): zq 1.797 -> 1.709 ms (0.759 -> 0.798 of the peak), uniform and ragged alike; n79, whose two layer arrays need a
   // second pass per tile, 1.530 -> 1.507 ms on equal-dLAI columns but 1.60 -> 1.72 ms on ragged ones (stamps: the store role then takes
-  // 3 us per tile against 2 us of arithmetic, profiles/r03/nb107/): n79 keeps the part-line form.  tune key 13: 2 / 3 force either form.
+  // 3 us per tile against 2 us of arithmetic, profiles/r03/nb107/): n79 keeps the part-line form.  CRT_TUNE_FLAT_FLUSH forces either form.
   const bool wl_default = flush_classes<S>() == 1;
-  if (cfg.flat == 2 && a.nb >= 128 / (int)sizeof(TIO) && (a.tune[13] == 3 || (a.tune[13] == 0 && wl_default))) cfg.flat = 3;
+  const int ff = a.tune.flat_flush;
+  if (cfg.flat == 2 && a.nb >= 128 / (int)sizeof(TIO) && (ff == CRT_FLAT_FLUSH_WHOLE_LINE || (ff == 0 && wl_default))) cfg.flat = 3;
   const size_t sh = ((size_t)cfg.off_park + (cfg.flat == 3 ? park_doubles<S, TIO>() : 0)) * sizeof(double);
   if (sh > MAX_WG_LDS) return CRT_ERR_UNSUPPORTED;
   auto kern = k_tri_pipe<S, TIO, M, T, 512, -1>;
@@ -1102,8 +1101,8 @@ int launch_tri_pack(const SolveArgs& a, hipStream_t s) {
   {
     // up to 32 bands: 64 / nb columns on one compute wave; 33 .. 42 bands (the 36-38-band shards of an 8-rank band partition): three
     // columns on two compute waves (a column may straddle the waves) -- beyond that a pack fills no more lanes than a column by itself
-    const int ncw = a.tune[6] > 0 ? a.tune[6] : (a.nb <= 32 ? 1 : 2);
-    if (a.nb % 2 || a.nb < 2 || 64 * ncw / a.nb < 2 || (a.nb > 42 && a.tune[6] == 0)) return CRT_ERR_UNSUPPORTED;
+    const int ncw_set = a.tune.pack_compute_waves, ncw = ncw_set > 0 ? ncw_set : (a.nb <= 32 ? 1 : 2);
+    if (a.nb % 2 || a.nb < 2 || 64 * ncw / a.nb < 2 || (a.nb > 42 && ncw_set == 0)) return CRT_ERR_UNSUPPORTED;
     for (int i = 0; i < S::NOUT; ++i)
       if (reinterpret_cast<uintptr_t>(a.o[i]) & (2 * sizeof(TIO) - 1)) return CRT_ERR_UNSUPPORTED;
     const int K = S::rows(a.nz);
@@ -1121,7 +1120,7 @@ int launch_tri_pack(const SolveArgs& a, hipStream_t s) {
     // 33 .. 42 bands, measured (tools/ragged_sweep.py --tune=5:1 / 5:0, profiles/r03/narrow/tri_pack_38_bands_ab.txt): n79 1.5e5 x 38 x 60
     // 0.695 -> 0.775 (ragged 0.63 -> 0.72), but 1e5 x 38 x 100 0.71 -> 0.71 / 0.60 -> 0.57 (55 KB of LDS per pack); zq 1e5 x 38 x 100 0.80 -> 0.83,
     // 1.5e5 x 38 x 60 0.78 -> 0.78, 36 bands 0.83 -> 0.81: taken for n79 while the pack stays below 40 KB, not for zq
-    if (a.nb > 32 && a.tune[6] == 0 && (std::is_same<S, typename UniformOf<S>::type>::value || sh > 40 * 1024)) return CRT_ERR_UNSUPPORTED;
+    if (a.nb > 32 && ncw_set == 0 && (std::is_same<S, typename UniformOf<S>::type>::value || sh > 40 * 1024)) return CRT_ERR_UNSUPPORTED;
     auto kern = k_tri_pipe<S, TIO, M, T, 512, 3>;
     if (sh > 64 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
@@ -1150,7 +1149,8 @@ int launch_pipe_mt(const SolveArgs& a, hipStream_t s, int nstore_waves, bool reg
   const size_t sh = ((size_t)cfg.off_tile + (size_t)(regstage ? 1 : 2) * S::NST * T * a.nb) * sizeof(double);
   if (sh > (regstage ? MAX_WG_LDS / 2 : MAX_WG_LDS)) return CRT_ERR_UNSUPPORTED;  // register staging only pays with 2 WG/CU
   // (M = 8 only: at M = 12 the n79 compute role does not fit the 96 registers of five waves per SIMD and spills -- 3.45 -> 4.51 ms)
-  const bool narrow_rs = T == 4 && M == 8 && regstage && nthr <= 512 && T * (a.nb / 2) <= 2 * 64 * nstore_waves && a.tune[2] != 16;
+  const bool narrow_rs = T == 4 && M == 8 && regstage && nthr <= 512 && T * (a.nb / 2) <= 2 * 64 * nstore_waves &&
+                         !(a.tune.tile_flags & CRT_TILE_FLAG_FOUR_PAIR_STORE);
   auto go = [&](auto kern) {
     if (sh > 64 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
@@ -1162,7 +1162,7 @@ int launch_pipe_mt(const SolveArgs& a, hipStream_t s, int nstore_waves, bool reg
     return (int)CRT_OK;
   };
   if constexpr (T == 4 && M == 8) {  // narrow spectra: two staged pairs per store thread cover the tile
-    if (narrow_rs) return go(k_tri_pipe<S, TIO, M, T, 512, 2>);  // (crt_options.tune[2] = 16 keeps the four-pair form: A/B)
+    if (narrow_rs) return go(k_tri_pipe<S, TIO, M, T, 512, 2>);  // (CRT_TILE_FLAG_FOUR_PAIR_STORE keeps the four-pair form: A/B)
   }
   if (regstage) return nthr <= 512 ? go(k_tri_pipe<S, TIO, M, T, 512, PIPE_RS>) : go(k_tri_pipe<S, TIO, M, T, 1024, PIPE_RS>);
   return nthr <= 512 ? go(k_tri_pipe<S, TIO, M, T, 512, 0>) : go(k_tri_pipe<S, TIO, M, T, 1024, 0>);
@@ -1185,16 +1185,17 @@ int launch_pipe(const SolveArgs& a, hipStream_t s, int M, int T, int nsw, bool r
 template <class S, typename TIO>
 int launch_scheme(const SolveArgs& a, hipStream_t s, bool& done, int min_nb = 10) {
   done = false;
-  const int* g_tri_tune = a.tune + 8;  // this call's overrides (crt_options.tune[8..11])
-  if (a.tune[12] > 0) min_nb = a.tune[12];
-  if (a.nb <= 64 && a.tune[5] != 1 && g_tri_tune[0] == 0 && g_tri_tune[2] == 0) {  // several columns per compute wave (tune key 5 = 1: off)
+  const Tune& tune = a.tune;
+  const int family = tune.tri_family;
+  // several columns per compute wave, unless packing is off or the family or M is forced
+  if (a.nb <= 64 && tune.pack != CRT_PACK_OFF && tune.tri_m == 0 && family == 0) {
     const int st = launch_tri_pack<S, TIO>(a, s);
     if (st != CRT_ERR_UNSUPPORTED) {
       done = st == CRT_OK;
       return st;
     }
   }
-  if (a.nb < min_nb || a.nb > 1024) return CRT_OK;  // narrow spectra: the per-wave kernels fill their lanes better
+  if (a.nb < tune.min_nb(min_nb) || a.nb > 1024) return CRT_OK;  // narrow spectra: the per-wave kernels fill their lanes better
   const int nthr = ((a.nb + 63) / 64) * 64;
   const int K = S::rows(a.nz);
   auto lds_bytes = [&](int M, int T) {
@@ -1215,9 +1216,9 @@ int launch_scheme(const SolveArgs& a, hipStream_t s, bool& done, int min_nb = 10
     const size_t budget = pref[i][1] == 4 && i == 0 ? 78 * 1024 : MAX_WG_LDS;
     if (need <= budget) { M = pref[i][0]; T = pref[i][1]; }
   }
-  if (g_tri_tune[0] > 0) {
-    M = g_tri_tune[0];
-    T = g_tri_tune[1] > 0 ? g_tri_tune[1] : 4;
+  if (tune.tri_m > 0) {
+    M = tune.tri_m;
+    T = tune.tri_t > 0 ? tune.tri_t : 4;
     if (lds_bytes(M, T) > MAX_WG_LDS) return CRT_OK;
   }
   if (!M) return CRT_OK;
@@ -1228,12 +1229,13 @@ int launch_scheme(const SolveArgs& a, hipStream_t s, bool& done, int min_nb = 10
   // odd nb / unaligned outputs: pipeline with the generic flush.  The per-element flush is too much work for a few store
   // waves once the spectrum is wide (tools/ab_tri_odd.py, k_tri_tile -> pipeline with 2 store waves: nb=107 n79 1.81 -> 1.90 ms,
   // zq 2.35 -> 2.29, zq nz=100 3.00 -> 2.22; nb=255 n79 1.60 -> 2.39, zq 2.25 -> 2.86), so only zq on narrow spectra takes it
-  // (tune key 10 = 4 forces it for any scheme and nb).
+  // (CRT_TRI_FAMILY_GENERIC_PIPELINE forces it for any scheme and nb).
   // With the fused flat flush (round 2; tools/ab_flat.py, 3e4 x 107 x 60: zq 2.25 -> 1.80 ms, n79 1.77 -> 1.61 in k_tri_tile, 1.57 in
   // the pipeline) the narrow pipeline pays for n79 as well.
-  const bool flat_ok = a.tune[13] != 1 && flat_flush_ok<S, TIO>(a);
-  if (!fused && g_tri_tune[2] != 1 && g_tri_tune[0] == 0 && ((nthr <= 128 && a.nb >= 16 && (S::NOUT == 7 || flat_ok)) || g_tri_tune[2] == 4)) {
-    const int nsw = g_tri_tune[3] > 0 ? g_tri_tune[3] : (nthr == 64 ? 1 : 2);
+  const bool flat_ok = tune.flat_flush != CRT_FLAT_FLUSH_OFF && flat_flush_ok<S, TIO>(a);
+  if (!fused && family != CRT_TRI_FAMILY_NO_PIPELINE && tune.tri_m == 0 &&
+      ((nthr <= 128 && a.nb >= 16 && (S::NOUT == 7 || flat_ok)) || family == CRT_TRI_FAMILY_GENERIC_PIPELINE)) {
+    const int nsw = tune.tri_store_waves > 0 ? tune.tri_store_waves : (nthr == 64 ? 1 : 2);
     int st = launch_pipe_generic<S, TIO, 12, 4>(a, s, nsw);
     if (st == CRT_ERR_UNSUPPORTED) st = launch_pipe_generic<S, TIO, 16, 4>(a, s, nsw);
     if (st != CRT_ERR_UNSUPPORTED) {
@@ -1241,21 +1243,21 @@ int launch_scheme(const SolveArgs& a, hipStream_t s, bool& done, int min_nb = 10
       return st;
     }
   }
-  if (fused && g_tri_tune[2] != 1 && (a.nb >= 16 || g_tri_tune[2] >= 2)) {  // wave-specialised pipeline first (tune key 10 = 1 disables, key 11 = store waves)
+  // wave-specialised pipeline first (below 16 bands only when a pipeline family is forced)
+  if (fused && family != CRT_TRI_FAMILY_NO_PIPELINE && (a.nb >= 16 || family >= CRT_TRI_FAMILY_DOUBLE_BUFFERED)) {
     // Measured on MI355X at 1e4 x 300 (tools/ab_tri.py, profiles/r01/ab_tri_pipe_*.txt; fill probe 6.3-6.8 TB/s):
     //                best k_tri_tile -> double-buffer pipeline (1 WG/CU) -> register-staged pipeline (2 WG/CU)
     //   n79 nz=60 :  1.649 ms        -> 1.522 (M12/T4, 4 store waves)    -> 1.384 (M12/T4, 3 store waves) = 0.93 of the fill rate
     //   zq  nz=60 :  1.852           -> 1.771 (M8/T4, 3)                 -> 1.607 (M12/T4, 3)             = 0.95
     //   zq  nz=100:  3.115           -> 2.902 (M16/T4, 4)                -> 2.857 (M16/T4, 3)             = 0.93
-    int nsw = g_tri_tune[3] > 0 ? g_tri_tune[3] : 4;
+    int nsw = tune.tri_store_waves > 0 ? tune.tri_store_waves : 4;
     if (nthr + 64 * nsw > 1024) nsw = (1024 - nthr) / 64;
     int st = CRT_ERR_UNSUPPORTED;
     if (nsw >= 1) {
-      // tune key 10: 0 = automatic, 1 = no pipeline, 2 = double-buffer pipeline only, 3 = register-staged only
-      const bool try_rs = g_tri_tune[2] != 2, try_db = g_tri_tune[2] != 3;
+      const bool try_rs = family != CRT_TRI_FAMILY_DOUBLE_BUFFERED, try_db = family != CRT_TRI_FAMILY_REG_STAGED;
       // register-staged: 5 compute + 3 store waves = 8 waves per workgroup, two workgroups fill the 16 wave slots of a CU at <= 128 VGPRs
-      const int nsw_rs = g_tri_tune[3] > 0 ? nsw : (nthr == 64 ? 1 : min(nsw, 3));
-      if (g_tri_tune[0] > 0) {
+      const int nsw_rs = tune.tri_store_waves > 0 ? nsw : (nthr == 64 ? 1 : min(nsw, 3));
+      if (tune.tri_m > 0) {
         if (try_rs) st = launch_pipe<S, TIO>(a, s, M, T, nsw_rs, true);
         if (st == CRT_ERR_UNSUPPORTED && try_db) st = launch_pipe<S, TIO>(a, s, M, T, nsw, false);
       } else {

@@ -483,7 +483,7 @@ template <typename TIO, int M, int T>
 int launch_zqpa_generic2(const SolveArgs& a, hipStream_t s, int nsw) {
   if (a.nb < 65 || a.nb > 256) return CRT_ERR_UNSUPPORTED;
   SolveArgs ao = a;  // (flat_flush_ok looks at the first ZqPaOut::NOUT output arrays)
-  const int flat = a.tune[13] != 1 ? flat_flush_ok<ZqPaOut, TIO>(ao) : 0;
+  const int flat = a.tune.flat_flush != CRT_FLAT_FLUSH_OFF ? flat_flush_ok<ZqPaOut, TIO>(ao) : 0;
   if (!flat) return CRT_ERR_UNSUPPORTED;
   const int Mg = zqpa_M(a.nz);
   const int ncomp = ((a.nb + 63) / 64) * 64;
@@ -500,7 +500,7 @@ int launch_zqpa_generic2(const SolveArgs& a, hipStream_t s, int nsw) {
   cfg.off_ck = cfg.off_bc + ((a.nb + 1) & ~1);
   cfg.off_tile = cfg.off_ck + 2 * cfg.nck * ncomp;
   cfg.off_park = cfg.off_tile + 2 * ZqPaOut::NST * T * a.nb;
-  cfg.flat = (flat == 2 && a.nb >= 128 / (int)sizeof(TIO) && a.tune[13] != 2) ? 3 : flat;
+  cfg.flat = (flat == 2 && a.nb >= 128 / (int)sizeof(TIO) && a.tune.flat_flush != CRT_FLAT_FLUSH_PART_LINE) ? 3 : flat;
   cfg.nz_out = a.nz;
   for (int i = 0; i < 4; ++i) cfg.out[i] = a.o[i];
   const size_t sh = ((size_t)cfg.off_park + (cfg.flat == 3 ? park_doubles<ZqPaOut, TIO>() : 0)) * sizeof(double);
@@ -519,7 +519,7 @@ int launch_zqpa_generic2(const SolveArgs& a, hipStream_t s, int nsw) {
 // returns CRT_ERR_UNSUPPORTED when the shape does not fit
 template <typename TIO, int M, int T, bool REGSTAGE>
 int launch_zqpa_fused2(const SolveArgs& a, hipStream_t s, int nsw, size_t lds_cap = MAX_WG_LDS) {
-  if (a.nb < (a.tune[12] > 0 ? a.tune[12] : 16) || a.nb % 2) return CRT_ERR_UNSUPPORTED;  // even nb: the fused (row, band pair) flush
+  if (a.nb < a.tune.min_nb(16) || a.nb % 2) return CRT_ERR_UNSUPPORTED;  // even nb: the fused (row, band pair) flush
   for (int i = 0; i < 4; ++i)
     if (reinterpret_cast<uintptr_t>(a.o[i]) & (2 * sizeof(TIO) - 1)) return CRT_ERR_UNSUPPORTED;
   const int Mg = zqpa_M(a.nz);
@@ -579,9 +579,9 @@ __global__ __launch_bounds__(MAXT) void k_zqpa_pipe(SolveArgs a, PipeCfg cfg) {
 // returns CRT_ERR_UNSUPPORTED when the shape does not fit (caller falls back to the two-kernel path)
 template <typename TIO, int M, int T>
 int launch_zqpa_fused(const SolveArgs& a, hipStream_t s, int nsw, size_t lds_cap = MAX_WG_LDS) {
-  if (a.nb < (a.tune[12] > 0 ? a.tune[12] : 16)) return CRT_ERR_UNSUPPORTED;  // (tune 12: smallest nb, as for the other pipelines)
+  if (a.nb < a.tune.min_nb(16)) return CRT_ERR_UNSUPPORTED;
   const bool flat = a.nb % 2;  // odd nb: rows are not pair-aligned -> flat store role
-  if (flat && a.tune[13] == 1) return CRT_ERR_UNSUPPORTED;
+  if (flat && a.tune.flat_flush == CRT_FLAT_FLUSH_OFF) return CRT_ERR_UNSUPPORTED;
   for (int i = 0; i < 4; ++i)
     if (reinterpret_cast<uintptr_t>(a.o[i]) & (2 * sizeof(TIO) - 1)) return CRT_ERR_UNSUPPORTED;
   const int Mg = zqpa_M(a.nz);
@@ -930,9 +930,15 @@ int launch_zqpa_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
 }
 
 int launch_zqpa(const SolveArgs& a, double* scratch, hipStream_t s) {
-  const int* g_tri_tune = a.tune + 8;  // this call's overrides
-  if (g_tri_tune[2] != 1 || a.f32) {  // fused interpolation first (tune key 10 = 1: the two-kernel path with workspace scratch)
-    const int nsw = g_tri_tune[3];
+  const Tune& tune = a.tune;
+  const int family = tune.tri_family;
+  // CRT_TRI_FAMILY_ZQPA_TWO_KERNEL is the value of CRT_TRI_FAMILY_NO_PIPELINE, and the grid solve below gets this call's overrides: that
+  // grid solve then runs in k_tri_tile, at the M and T of CRT_TUNE_TRI_M / CRT_TUNE_TRI_T when they are given
+  if (family != CRT_TRI_FAMILY_ZQPA_TWO_KERNEL || a.f32) {  // fused interpolation first
+    const int nsw = tune.tri_store_waves;
+    const bool short_segments = tune.tri_m == 8;   // A/B: M = 8 in k_zqpa_pipe2 (fewer registers: five waves per SIMD, three WG per CU)
+    const bool narrow_m12 = tune.tri_m != 16;      // narrow spectra take k_zqpa_pipe at M = 12 unless M = 16 is asked for
+    const bool try_rs = family != CRT_TRI_FAMILY_ZQPA_PIPE2_DB, try_db = family != CRT_TRI_FAMILY_ZQPA_PIPE2_RS;
     int st;
     // two workgroups per CU first (half of the LDS each): M = 16, T = 4, or -- above ~85 levels at 300 bands -- tiles of 3 levels
     // (M = 15), which is what brings 100 levels from 84 KB to 74 KB; then whatever fits at all
@@ -946,38 +952,34 @@ int launch_zqpa(const SolveArgs& a, double* scratch, hipStream_t s) {
       return st;  // f32 storage exists in the fused kernel only (the two-kernel path keeps its computational-grid scratch in fp64)
     }
     st = CRT_ERR_UNSUPPORTED;
-    // round 3: interpolation in the compute lanes + the plain fused store role (even nb; tune key 10 = 5 keeps the kernel below; key 10 = 6 /
-    // 7 force the double-buffered / register-staged form)
+    // round 3: interpolation in the compute lanes + the plain fused store role (even nb; CRT_TRI_FAMILY_ZQPA_PIPE keeps the kernel below,
+    // CRT_TRI_FAMILY_ZQPA_PIPE2_DB / _RS force the double-buffered / register-staged form)
     // Measured (tools/ragged_sweep.py, round 3; both kernels on the division-free sweep): 1e4 x 300 x 60 1.10 (below) vs 1.11-1.13 ms,
     // 6000 x 300 x 100 1.23 vs 1.12-1.15, 3e4 x 106 x 60 1.23 vs 2.67, 1e5 x 38 x 100 3.00 vs 3.58 -> the new form above 128 bands only.
     // Three workgroups per CU (M = 8 capped at 80 registers, 40 B of scratch) gave 1.19 ms: occupancy is not what binds it.
     // (round 3, after the level emission was rewritten: also 65 .. 128 even bands with ONE store wave -- 3e4 x 106 x 60 1.21 -> 1.13 ms; below
     //  65 bands the older kernel stays ahead, 1e5 x 38 x 100 3.01 vs 3.15 ms: profiles/r03/zqpa_pipe2_narrow_tune.txt)
-    if (g_tri_tune[2] != 5 && (a.nb > 64 || g_tri_tune[2] >= 6 || g_tri_tune[0] == 8)) {
+    if (family != CRT_TRI_FAMILY_ZQPA_PIPE && (a.nb > 64 || family >= CRT_TRI_FAMILY_ZQPA_PIPE2_DB || short_segments)) {
       constexpr size_t HALF2 = MAX_WG_LDS / 2;
-      const int mode = g_tri_tune[2];
-      if (g_tri_tune[0] == 8) {  // A/B: short segments (fewer registers: five waves per SIMD, three workgroups per CU)
-        if (mode != 6) st = launch_zqpa_fused2<double, 8, 4, true>(a, s, nsw, MAX_WG_LDS / 3);
-        if (st == CRT_ERR_UNSUPPORTED && mode != 7) st = launch_zqpa_fused2<double, 8, 4, false>(a, s, nsw, MAX_WG_LDS / 3);
+      if (short_segments) {
+        if (try_rs) st = launch_zqpa_fused2<double, 8, 4, true>(a, s, nsw, MAX_WG_LDS / 3);
+        if (st == CRT_ERR_UNSUPPORTED && try_db) st = launch_zqpa_fused2<double, 8, 4, false>(a, s, nsw, MAX_WG_LDS / 3);
         if (st == CRT_ERR_UNSUPPORTED) st = launch_zqpa_fused2<double, 8, 4, true>(a, s, nsw, HALF2);
-      } else if (a.nz <= 64) {  // few checkpoints: M = 16 keeps the LDS small; above, M = 16 as well (registers cap M)
-        if (mode != 6) st = launch_zqpa_fused2<double, 16, 4, true>(a, s, nsw, HALF2);
-        if (st == CRT_ERR_UNSUPPORTED && mode != 7) st = launch_zqpa_fused2<double, 16, 4, false>(a, s, nsw, HALF2);
-      } else {
-        if (mode != 6) st = launch_zqpa_fused2<double, 16, 4, true>(a, s, nsw, HALF2);
-        if (st == CRT_ERR_UNSUPPORTED && mode != 7) st = launch_zqpa_fused2<double, 16, 4, false>(a, s, nsw, HALF2);
+      } else {  // M = 16 at any depth: it keeps the LDS small with few checkpoints, and registers cap M with many
+        if (try_rs) st = launch_zqpa_fused2<double, 16, 4, true>(a, s, nsw, HALF2);
+        if (st == CRT_ERR_UNSUPPORTED && try_db) st = launch_zqpa_fused2<double, 16, 4, false>(a, s, nsw, HALF2);
       }
-      if (st == CRT_ERR_UNSUPPORTED && mode != 6) st = launch_zqpa_fused2<double, 16, 4, true>(a, s, nsw);
-      if (st == CRT_ERR_UNSUPPORTED && mode != 7) st = launch_zqpa_fused2<double, 16, 4, false>(a, s, nsw);
+      if (st == CRT_ERR_UNSUPPORTED && try_rs) st = launch_zqpa_fused2<double, 16, 4, true>(a, s, nsw);
+      if (st == CRT_ERR_UNSUPPORTED && try_db) st = launch_zqpa_fused2<double, 16, 4, false>(a, s, nsw);
       if (st != CRT_ERR_UNSUPPORTED) return st;
     }
-    if (a.nb % 2 == 1 && g_tri_tune[2] != 5) {  // odd band counts: the new compute role with the flat flush (tune key 10 = 5: the kernel below)
+    if (a.nb % 2 == 1 && family != CRT_TRI_FAMILY_ZQPA_PIPE) {  // odd band counts: the new compute role with the flat flush
       st = launch_zqpa_generic2<double, 16, 4>(a, s, nsw);
       if (st != CRT_ERR_UNSUPPORTED) return st;
     }
     // narrow spectra (one compute wave per column): M = 12 needs 92 registers, five waves per SIMD instead of four (1e5 x 38 x 100:
-    // 3.74 -> 3.64 ms, 2e5 x 16 x 60 3.23 -> 3.16; at 62 bands the other way, 2.61 -> 2.64).  (tune key 8 = 16 keeps M = 16.)
-    if (a.nb <= 48 && g_tri_tune[0] != 16) st = launch_zqpa_fused<double, 12, 4>(a, s, nsw, HALF);
+    // 3.74 -> 3.64 ms, 2e5 x 16 x 60 3.23 -> 3.16; at 62 bands the other way, 2.61 -> 2.64)
+    if (a.nb <= 48 && narrow_m12) st = launch_zqpa_fused<double, 12, 4>(a, s, nsw, HALF);
     if (st == CRT_ERR_UNSUPPORTED) st = launch_zqpa_fused<double, 16, 4>(a, s, nsw, HALF);
     if (st == CRT_ERR_UNSUPPORTED) st = launch_zqpa_fused<double, 15, 3>(a, s, nsw, HALF);
     if (st == CRT_ERR_UNSUPPORTED) st = launch_zqpa_fused<double, 16, 4>(a, s, nsw);

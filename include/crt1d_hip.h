@@ -111,15 +111,71 @@ typedef struct crt_bands {
 #define CRT_FLAG_DIRECT_STORES 4   /* measurement aid: use the direct-store solve kernel even where the LDS-tiled,
                                       line-aligned one applies (same results, different store pattern) */
 
+/* crt_options.tune: keys.  Every value is 0 = automatic (the launcher's own heuristic); any other value outside the range given
+ * here is CRT_ERR_BAD_ARG, checked before any launch.  "Closed forms" are 2s, 4s, bl, g77 and bf; the tridiagonal schemes are n79
+ * and zq; zq_pa has launchers of its own and hands the same overrides to the grid solve of its two-kernel path.  Keys 7 and 14 are
+ * reserved and must stay 0. */
+enum crt_tune_key {
+  CRT_TUNE_TILE_LDS = 0,           /* closed forms: LDS bytes a tile may take per workgroup, <= 160 KiB */
+  CRT_TUNE_TILE_T = 1,             /* closed forms: levels per k_tile tile, <= 64 */
+  CRT_TUNE_TILE_FLAGS = 2,         /* bit set of crt_tune_tile_flag, <= 255 */
+  CRT_TUNE_CLOSED_STORE_WAVES = 3, /* closed forms: store waves of k_pipe / k_pipe_pack, <= 12 */
+  CRT_TUNE_CLOSED_PIPE_T = 4,      /* closed forms: levels per k_pipe / k_pipe_pack tile, <= 32 */
+  CRT_TUNE_PACK = 5,               /* several columns per compute wave (k_pipe_pack, packed k_tri_pipe): crt_tune_pack */
+  CRT_TUNE_PACK_COMPUTE_WAVES = 6, /* compute waves of one pack, <= 4 */
+  CRT_TUNE_TRI_M = 8,              /* tridiagonal and zq_pa: rows per segment M, 8 / 12 / 16 */
+  CRT_TUNE_TRI_T = 9,              /* tridiagonal: levels per tile T, 4 / 8 / 12; read only with CRT_TUNE_TRI_M (0 there: 4) */
+  CRT_TUNE_TRI_FAMILY = 10,        /* tridiagonal and zq_pa: kernel family, crt_tune_tri_family */
+  CRT_TUNE_TRI_STORE_WAVES = 11,   /* tridiagonal and zq_pa: store waves of the pipelines, <= 12 */
+  CRT_TUNE_MIN_TILE_NB = 12,       /* smallest nb that takes the tile / pipeline kernels, <= 1024 (0: 4 for the closed forms, 10 for
+                                      the tridiagonal schemes, 16 for zq_pa's single-kernel forms, 1 for its grid solve) */
+  CRT_TUNE_FLAT_FLUSH = 13,        /* flat flush of rows that are not pair-aligned (odd nb): crt_tune_flat_flush */
+  CRT_TUNE_K0_SEPARATE = 15        /* 2s: 1 = k_colpre in front of k_pipe instead of the record prologue inside it */
+};
 #define CRT_NTUNE 16
+
+/* CRT_TUNE_TILE_FLAGS bits */
+enum crt_tune_tile_flag {
+  CRT_TILE_FLAG_SYNC_BARRIERS = 1,       /* k_tile: full __syncthreads() barriers */
+  CRT_TILE_FLAG_GENERIC_FLUSH = 2,       /* closed forms: generic flush instead of the fused one */
+  CRT_TILE_FLAG_NO_PIPELINE = 4,         /* closed forms: no k_pipe (k_tile instead) */
+  CRT_TILE_FLAG_NO_GENERIC_PIPELINE = 8, /* closed forms: no generic-flush k_pipe */
+  CRT_TILE_FLAG_FOUR_PAIR_STORE = 16     /* tridiagonal, narrow spectra: the four-pair instead of the two-pair register-staged store role */
+};
+
+/* CRT_TUNE_PACK values */
+enum crt_tune_pack {
+  CRT_PACK_OFF = 1,  /* one column per workgroup */
+  CRT_PACK_FORCE = 2 /* closed forms: pack also above 32 bands (up to 128) */
+};
+
+/* CRT_TUNE_TRI_FAMILY values (any of them, like CRT_TUNE_TRI_M, also keeps n79 and zq from packing columns).  1 reads as NO_PIPELINE
+ * for n79 and zq and as ZQPA_TWO_KERNEL for zq_pa, whose grid solve then reads it as NO_PIPELINE. */
+enum crt_tune_tri_family {
+  CRT_TRI_FAMILY_NO_PIPELINE = 1,      /* k_tri_tile */
+  CRT_TRI_FAMILY_DOUBLE_BUFFERED = 2,  /* double-buffered k_tri_pipe only */
+  CRT_TRI_FAMILY_REG_STAGED = 3,       /* register-staged k_tri_pipe only */
+  CRT_TRI_FAMILY_GENERIC_PIPELINE = 4, /* generic-flush k_tri_pipe wherever the fused flush does not apply, for any nb */
+  CRT_TRI_FAMILY_ZQPA_TWO_KERNEL = 1,  /* zq_pa: grid solve into workspace scratch + k_zqpa_interp (f64 only) */
+  CRT_TRI_FAMILY_ZQPA_PIPE = 5,        /* zq_pa: k_zqpa_pipe (interpolation in the store waves) */
+  CRT_TRI_FAMILY_ZQPA_PIPE2_DB = 6,    /* zq_pa: double-buffered k_zqpa_pipe2 (interpolation in the compute lanes) */
+  CRT_TRI_FAMILY_ZQPA_PIPE2_RS = 7     /* zq_pa: register-staged k_zqpa_pipe2 */
+};
+
+/* CRT_TUNE_FLAT_FLUSH values (0: whole lines for zq and zq_pa, part lines for n79) */
+enum crt_tune_flat_flush {
+  CRT_FLAT_FLUSH_OFF = 1,       /* per-array generic flush instead */
+  CRT_FLAT_FLUSH_PART_LINE = 2,
+  CRT_FLAT_FLUSH_WHOLE_LINE = 3
+};
+
 typedef struct crt_options {
   double mu_s;            /* 4s: cosine of the dividing angle, default 0.501 (_solve_4s.py:9) */
   int32_t tau_d_method;   /* n79: crt_tau_d_method, default CRT_TAU_D_QUAD (_solve_n79.py:19) */
   int32_t flags;          /* CRT_FLAG_* */
-  int32_t tune[CRT_NTUNE];/* measurement aid, all zero in production: per-CALL overrides of the kernel-selection heuristics
-                             (tile height, store waves, kernel family; keys in csrc/crt_internal.hpp).  Part of the call's
-                             arguments, so there is no process-global tuning state: calls with different settings may run
-                             concurrently */
+  int32_t tune[CRT_NTUNE];/* measurement aid, all zero in production: per-CALL overrides of the kernel-selection heuristics,
+                             indexed by crt_tune_key.  Part of the call's arguments, so there is no process-global tuning state:
+                             calls with different settings may run concurrently */
 } crt_options;
 
 /* outputs; each [ncol][nz][nb] unless noted.  Unused slots may be NULL. */

@@ -138,12 +138,45 @@ def test_tune_values_are_validated_before_any_launch(lib):
     out = _lib.CrtOutputs(fake, fake, fake, fake, fake, fake, fake)
 
     def call(tune):
-        o = _lib.CrtOptions(0.501, 0, 0)
-        for k, v in tune.items():
-            o.tune[k] = v
+        o = _lib.set_tune(_lib.CrtOptions(0.501, 0, 0), tune)
         return lib.crt_hip_zq_f64(ctypes.byref(c), ctypes.byref(b), ctypes.byref(o), ctypes.byref(out), None, 0, None)
 
     assert call({}) == _lib.CRT_ERR_WORKSPACE
-    assert call({8: 16, 9: 4, 11: 2, 10: 3, 13: 1}) == _lib.CRT_ERR_WORKSPACE
-    for bad in ({3: 99}, {4: -1}, {8: 10}, {9: 5}, {10: 8}, {11: 13}, {12: 5000}, {13: 4}, {0: 1 << 20}, {5: 3}, {7: 1}, {14: 7}, {2: 256}):
+    assert call({_lib.TUNE_TRI_M: 16, _lib.TUNE_TRI_T: 4, _lib.TUNE_TRI_STORE_WAVES: 2, _lib.TUNE_TRI_FAMILY: _lib.TRI_FAMILY_REG_STAGED,
+                 _lib.TUNE_FLAT_FLUSH: _lib.FLAT_FLUSH_OFF}) == _lib.CRT_ERR_WORKSPACE
+    for bad in ({_lib.TUNE_CLOSED_STORE_WAVES: 99}, {_lib.TUNE_CLOSED_PIPE_T: -1}, {_lib.TUNE_TRI_M: 10}, {_lib.TUNE_TRI_T: 5},
+                {_lib.TUNE_TRI_FAMILY: 8}, {_lib.TUNE_TRI_STORE_WAVES: 13}, {_lib.TUNE_MIN_TILE_NB: 5000}, {_lib.TUNE_FLAT_FLUSH: 4},
+                {_lib.TUNE_TILE_LDS: 1 << 20}, {_lib.TUNE_PACK: 3}, {7: 1}, {14: 7}, {_lib.TUNE_TILE_FLAGS: 256}):  # (7, 14: reserved)
         assert call(bad) == _lib.CRT_ERR_BAD_ARG, bad
+
+
+def test_tune_names_match_header():
+    """The _lib names of the crt_options.tune keys and values are the header's enumerators without the CRT_ prefix, with the same values."""
+    from crt1d_amd import _lib
+
+    text = open(os.path.join(ROOT, "include", "crt1d_hip.h")).read()
+    assert int(re.search(r"#define CRT_NTUNE (\d+)", text).group(1)) == _lib.NTUNE
+    prefixes = ("TUNE_", "TILE_FLAG_", "PACK_", "TRI_FAMILY_", "FLAT_FLUSH_")
+    header = {}
+    for enum in ("crt_tune_key", "crt_tune_tile_flag", "crt_tune_pack", "crt_tune_tri_family", "crt_tune_flat_flush"):
+        body = re.sub(r"/\*.*?\*/", "", re.search(r"enum %s \{(.*?)\};" % enum, text, flags=re.S).group(1), flags=re.S)
+        for name, value in re.findall(r"\bCRT_(\w+) = (\d+)", body):
+            assert name.startswith(prefixes), name
+            header[name] = int(value)
+    assert len(header) == 14 + 5 + 2 + 8 + 3
+    assert {k: v for k, v in vars(_lib).items() if k.startswith(prefixes)} == header
+    assert sorted(header[k] for k in header if k.startswith("TUNE_")) == sorted(set(range(_lib.NTUNE)) - {7, 14})  # 7, 14: reserved
+
+
+def test_set_tune_rejects_unknown_keys():
+    """_lib.set_tune writes every key (0 where none is given) and refuses a key that crt_options.tune does not have; values are left to
+    the library (test_tune_values_are_validated_before_any_launch)."""
+    from crt1d_amd import _lib
+
+    o = _lib.CrtOptions(0.501, 0, 0)
+    o.tune[_lib.TUNE_TRI_T] = 8
+    _lib.set_tune(o, {_lib.TUNE_TRI_FAMILY: _lib.TRI_FAMILY_ZQPA_PIPE, 7: -3})
+    assert list(o.tune) == [_lib.TRI_FAMILY_ZQPA_PIPE if k == _lib.TUNE_TRI_FAMILY else -3 if k == 7 else 0 for k in range(_lib.NTUNE)]
+    for bad in (_lib.NTUNE, -1, "TUNE_TRI_M", 8.0, None):
+        with pytest.raises(ValueError, match="unknown crt_options.tune key"):
+            _lib.set_tune(o, {bad: 1})

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, rel_profile_err
+from crt1d_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
@@ -325,15 +326,27 @@ def test_model_to_dataset():
         assert set(m.to_xr().data_vars) == expected
 
 
-# (tune key, value) settings that select each kernel family through crt_options.tune (per call; keys in csrc/crt_internal.hpp)
-_CLOSED_PATHS = {"k_pipe (default)": {}, "k_tile": {2: 4}, "k_tile generic flush": {2: 4 | 2}, "k_pipe generic flush": {2: 2},
-                 "k_pipe 1 store wave, T=2": {3: 1, 4: 2}, "k_pipe 4 store waves, T=8": {3: 4, 4: 8},
-                 "k_pipe, packing off": {5: 1}, "k_tile, packing off": {5: 1, 2: 4}, "k_pipe generic flush, packing off": {5: 1, 2: 2},
-                 "k_pipe_pack forced": {5: 2}, "k_pipe_pack 1 compute wave": {5: 2, 6: 1}, "k_pipe_pack 2 compute waves": {5: 2, 6: 2},
-                 "k_pipe_pack 3 compute waves": {5: 2, 6: 3}, "k_pipe_pack 4 compute waves": {5: 2, 6: 4}}
-_TRI_PATHS = {"default": {}, "k_tri_tile": {10: 1}, "k_tri_tile M8 T8": {10: 1, 8: 8, 9: 8}, "double-buffer pipeline": {10: 2},
-              "register-staged pipeline": {10: 3}, "generic-flush pipeline": {10: 4}, "pipeline M16 T4, 2 store waves": {8: 16, 9: 4, 11: 2},
-              "default, packing off": {5: 1}}
+# settings that select each kernel family through crt_options.tune (per call; keys and values in include/crt1d_hip.h)
+_CLOSED_PATHS = {"k_pipe (default)": {}, "k_tile": {_lib.TUNE_TILE_FLAGS: _lib.TILE_FLAG_NO_PIPELINE},
+                 "k_tile generic flush": {_lib.TUNE_TILE_FLAGS: _lib.TILE_FLAG_NO_PIPELINE | _lib.TILE_FLAG_GENERIC_FLUSH},
+                 "k_pipe generic flush": {_lib.TUNE_TILE_FLAGS: _lib.TILE_FLAG_GENERIC_FLUSH},
+                 "k_pipe 1 store wave, T=2": {_lib.TUNE_CLOSED_STORE_WAVES: 1, _lib.TUNE_CLOSED_PIPE_T: 2},
+                 "k_pipe 4 store waves, T=8": {_lib.TUNE_CLOSED_STORE_WAVES: 4, _lib.TUNE_CLOSED_PIPE_T: 8},
+                 "k_pipe, packing off": {_lib.TUNE_PACK: _lib.PACK_OFF},
+                 "k_tile, packing off": {_lib.TUNE_PACK: _lib.PACK_OFF, _lib.TUNE_TILE_FLAGS: _lib.TILE_FLAG_NO_PIPELINE},
+                 "k_pipe generic flush, packing off": {_lib.TUNE_PACK: _lib.PACK_OFF, _lib.TUNE_TILE_FLAGS: _lib.TILE_FLAG_GENERIC_FLUSH},
+                 "k_pipe_pack forced": {_lib.TUNE_PACK: _lib.PACK_FORCE},
+                 "k_pipe_pack 1 compute wave": {_lib.TUNE_PACK: _lib.PACK_FORCE, _lib.TUNE_PACK_COMPUTE_WAVES: 1},
+                 "k_pipe_pack 2 compute waves": {_lib.TUNE_PACK: _lib.PACK_FORCE, _lib.TUNE_PACK_COMPUTE_WAVES: 2},
+                 "k_pipe_pack 3 compute waves": {_lib.TUNE_PACK: _lib.PACK_FORCE, _lib.TUNE_PACK_COMPUTE_WAVES: 3},
+                 "k_pipe_pack 4 compute waves": {_lib.TUNE_PACK: _lib.PACK_FORCE, _lib.TUNE_PACK_COMPUTE_WAVES: 4}}
+_TRI_PATHS = {"default": {}, "k_tri_tile": {_lib.TUNE_TRI_FAMILY: _lib.TRI_FAMILY_NO_PIPELINE},
+              "k_tri_tile M8 T8": {_lib.TUNE_TRI_FAMILY: _lib.TRI_FAMILY_NO_PIPELINE, _lib.TUNE_TRI_M: 8, _lib.TUNE_TRI_T: 8},
+              "double-buffer pipeline": {_lib.TUNE_TRI_FAMILY: _lib.TRI_FAMILY_DOUBLE_BUFFERED},
+              "register-staged pipeline": {_lib.TUNE_TRI_FAMILY: _lib.TRI_FAMILY_REG_STAGED},
+              "generic-flush pipeline": {_lib.TUNE_TRI_FAMILY: _lib.TRI_FAMILY_GENERIC_PIPELINE},
+              "pipeline M16 T4, 2 store waves": {_lib.TUNE_TRI_M: 16, _lib.TUNE_TRI_T: 4, _lib.TUNE_TRI_STORE_WAVES: 2},
+              "default, packing off": {_lib.TUNE_PACK: _lib.PACK_OFF}}
 
 
 def _closed_family(tune, nb, nz, dtype):
@@ -341,26 +354,27 @@ def _closed_family(tune, nb, nz, dtype):
     vw = 2 if dtype == "f64" else 4  # elements per 16-B piece
     if nb < 4:
         return ("k_direct<",)
-    t5 = tune.get(5, 0)
-    if (nb <= 32 or t5 == 2) and nb <= 128 and t5 != 1 and nb % vw == 0 and (nz * nb) % vw == 0:
+    pack = tune.get(_lib.TUNE_PACK, 0)
+    if (nb <= 32 or pack == _lib.PACK_FORCE) and nb <= 128 and pack != _lib.PACK_OFF and nb % vw == 0 and (nz * nb) % vw == 0:
         # (three or four compute waves of narrow columns: as many columns per workgroup as fit its LDS, else the unpacked pipeline)
-        return ("k_pipe_pack<",) if tune.get(6, 0) <= 2 else ("k_pipe_pack<", "k_pipe<")
-    if tune.get(2, 0) & 4:
+        return ("k_pipe_pack<",) if tune.get(_lib.TUNE_PACK_COMPUTE_WAVES, 0) <= 2 else ("k_pipe_pack<", "k_pipe<")
+    if tune.get(_lib.TUNE_TILE_FLAGS, 0) & _lib.TILE_FLAG_NO_PIPELINE:
         return ("k_tile<",)
     return ("k_pipe<",) if nb <= 128 else ("k_pipe<", "k_tile<")  # (wide spectra: the pipeline only where its tiles fit the LDS budget)
 
 
 def _tri_family(tune, nb, dtype):
     """The same for launch_scheme (csrc/tri_tile_impl.hpp); None where the choice depends on the LDS budget."""
-    if tune.get(5, 0) != 1 and tune.get(8, 0) == 0 and tune.get(10, 0) == 0 and nb % 2 == 0 and nb <= 32:
+    if (tune.get(_lib.TUNE_PACK, 0) != _lib.PACK_OFF and tune.get(_lib.TUNE_TRI_M, 0) == 0 and tune.get(_lib.TUNE_TRI_FAMILY, 0) == 0
+            and nb % 2 == 0 and nb <= 32):
         return ("packed",)
     if nb < 10:
         return ("k_tri_wave<",)
-    if tune.get(10) == 1:  # (beyond 300 bands M8 T8 exceeds the LDS: the per-wave kernel)
-        return ("k_tri_tile<",) if nb <= 300 or 8 not in tune else ("k_tri_tile<", "k_tri_wave<")
-    if nb % 2 == 0 and 16 <= nb <= 128 and tune.get(10) == 2:
+    if tune.get(_lib.TUNE_TRI_FAMILY) == _lib.TRI_FAMILY_NO_PIPELINE:  # (beyond 300 bands M8 T8 exceeds the LDS: the per-wave kernel)
+        return ("k_tri_tile<",) if nb <= 300 or _lib.TUNE_TRI_M not in tune else ("k_tri_tile<", "k_tri_wave<")
+    if nb % 2 == 0 and 16 <= nb <= 128 and tune.get(_lib.TUNE_TRI_FAMILY) == _lib.TRI_FAMILY_DOUBLE_BUFFERED:
         return ("double-buffered",)
-    if nb % 2 == 0 and 16 <= nb <= 128 and (tune.get(8, 0) > 0 or tune.get(5) == 1):
+    if nb % 2 == 0 and 16 <= nb <= 128 and (tune.get(_lib.TUNE_TRI_M, 0) > 0 or tune.get(_lib.TUNE_PACK) == _lib.PACK_OFF):
         return ("k_tri_pipe<",)
     return None
 
@@ -398,11 +412,11 @@ def test_every_kernel_family_gives_the_same_bits(scheme, shape, dtype):
         names.add(kernel)
         want = _tri_family(tune, nb, dtype) if tri else _closed_family(tune, nb, nz, dtype)
         assert want is None or any(w in kernel for w in want), (name, want, kernel)
-        if tri and tune.get(5) == 1:
+        if tri and tune.get(_lib.TUNE_PACK) == _lib.PACK_OFF:
             assert "packed" not in kernel, (name, kernel)
-        if not tri and want == ("k_pipe_pack<",) and 6 in tune:
-            assert f"compute_waves={max(tune[6], (nb + 63) // 64)} " in kernel, (name, kernel)
-        if not tri and want != ("k_pipe_pack<",) and tune.get(2, 0) & 2:
+        if not tri and want == ("k_pipe_pack<",) and _lib.TUNE_PACK_COMPUTE_WAVES in tune:
+            assert f"compute_waves={max(tune[_lib.TUNE_PACK_COMPUTE_WAVES], (nb + 63) // 64)} " in kernel, (name, kernel)
+        if not tri and want != ("k_pipe_pack<",) and tune.get(_lib.TUNE_TILE_FLAGS, 0) & _lib.TILE_FLAG_GENERIC_FLUSH:
             assert "generic-flush" in kernel, (name, kernel)
         torch.cuda.synchronize()
         for k in p.out:

@@ -2,14 +2,16 @@
 
 A default 2s call that picks k_pipe runs no k_colpre: each workgroup forms its column's record and writes it to the workspace as well.
 The record must be k_colpre's to the last bit -- every other kernel family, SKIP_PRECOMPUTE calls and PRECOMPUTE_ONLY read what k_colpre
-writes -- and so must every output.  ``crt_options.tune[15] = 1`` keeps k_colpre in front of the same k_pipe (the A/B setting)."""
+writes -- and so must every output.  ``CRT_TUNE_K0_SEPARATE = 1`` keeps k_colpre in front of the same k_pipe (the A/B setting)."""
 import numpy as np
 import pytest
+
+from crt1d_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
 _IO = ("I_dr0", "I_df0", "leaf_r", "leaf_t", "soil_r")
-_K0_OFF = {15: 1}
+_K0_OFF = {_lib.TUNE_K0_SEPARATE: 1}
 
 
 def _columns(ncol, nb, nz, seed, uniform, g_kind=None, mla=None):
@@ -217,10 +219,10 @@ def test_fused_plan_replays_from_a_hip_graph():
 
 
 def test_tune_key_15_is_validated():
-    """tune[15] is 0 or 1; other values are CRT_ERR_BAD_ARG (ValueError from the plan)."""
+    """CRT_TUNE_K0_SEPARATE (key 15) is 0 or 1; other values are CRT_ERR_BAD_ARG (ValueError from the plan)."""
     d = _columns(8, 64, 10, seed=1, uniform=True)
     from crt1d_amd import batched
 
     cols, bands = batched.Columns.from_host(d), batched.Bands.from_host(d)
     with pytest.raises(ValueError):
-        batched.Plan("2s", cols, bands, placement="none", tune={15: 2})()
+        batched.Plan("2s", cols, bands, placement="none", tune={_lib.TUNE_K0_SEPARATE: 2})()

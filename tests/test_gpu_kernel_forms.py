@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_profile_err
+from crt1d_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
@@ -50,14 +51,19 @@ def _nan_fill(out):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
-# 1. zq_pa: every form against the two-kernel path (grid solve into workspace scratch + k_zqpa_interp, crt_options.tune[10] = 1)
+# 1. zq_pa: every form against the two-kernel path (grid solve into workspace scratch + k_zqpa_interp)
 
-_ZQPA_ANCHOR = {10: 1}
-# the default heuristics; k_zqpa_pipe (10:5); k_zqpa_pipe2 double-buffered / register-staged (10:6 / 10:7); M = 8 and M = 16 (8:8 / 8:16),
-# with either staging at M = 8; no flat flush / no whole-line flush (13:1 / 13:2); one and four store waves (11:1 / 11:4); the grid solve
-# of the two-kernel path through k_tri_tile M8 T8
-_ZQPA_SETTINGS = ({}, {10: 5}, {10: 6}, {10: 7}, {8: 8}, {8: 8, 10: 6}, {8: 8, 10: 7}, {8: 16}, {13: 1}, {13: 2}, {11: 1}, {11: 4},
-                  {10: 1, 8: 8, 9: 8})
+_ZQPA_ANCHOR = {_lib.TUNE_TRI_FAMILY: _lib.TRI_FAMILY_ZQPA_TWO_KERNEL}
+# the default heuristics; k_zqpa_pipe; k_zqpa_pipe2 double-buffered / register-staged; M = 8 and M = 16, with either staging at M = 8; no
+# flat flush / no whole-line flush; one and four store waves; the grid solve of the two-kernel path through k_tri_tile M8 T8 (the grid
+# solve reads ZQPA_TWO_KERNEL as NO_PIPELINE, csrc/tri_zqpa.hip)
+_ZQPA_SETTINGS = ({}, {_lib.TUNE_TRI_FAMILY: _lib.TRI_FAMILY_ZQPA_PIPE}, {_lib.TUNE_TRI_FAMILY: _lib.TRI_FAMILY_ZQPA_PIPE2_DB},
+                  {_lib.TUNE_TRI_FAMILY: _lib.TRI_FAMILY_ZQPA_PIPE2_RS}, {_lib.TUNE_TRI_M: 8},
+                  {_lib.TUNE_TRI_M: 8, _lib.TUNE_TRI_FAMILY: _lib.TRI_FAMILY_ZQPA_PIPE2_DB},
+                  {_lib.TUNE_TRI_M: 8, _lib.TUNE_TRI_FAMILY: _lib.TRI_FAMILY_ZQPA_PIPE2_RS}, {_lib.TUNE_TRI_M: 16},
+                  {_lib.TUNE_FLAT_FLUSH: _lib.FLAT_FLUSH_OFF}, {_lib.TUNE_FLAT_FLUSH: _lib.FLAT_FLUSH_PART_LINE},
+                  {_lib.TUNE_TRI_STORE_WAVES: 1}, {_lib.TUNE_TRI_STORE_WAVES: 4},
+                  {_lib.TUNE_TRI_FAMILY: _lib.TRI_FAMILY_ZQPA_TWO_KERNEL, _lib.TUNE_TRI_M: 8, _lib.TUNE_TRI_T: 8})
 # (ncol, nb, nz, uniform dLAI, check the anchor against the oracle): nb across every threshold of launch_zqpa (16, 48 / 49, 64 / 65, 128,
 # 256 / 257, one compute wave, odd / even, 1000 = no single-kernel form fits, 1025 = per-wave grid solve); nz below, at and above the
 # 100-row computational grid
@@ -118,7 +124,7 @@ def test_zq_pa_every_form_equals_two_kernel_path(oracle, shape):
     _ZQPA_SEEN[shape] = _zqpa_f64_matrix(shape, oracle if shape[4] else None)
 
 
-_ZQPA_F32_SETTINGS = ({}, {11: 1}, {11: 4})
+_ZQPA_F32_SETTINGS = ({}, {_lib.TUNE_TRI_STORE_WAVES: 1}, {_lib.TUNE_TRI_STORE_WAVES: 4})
 _ZQPA_F32_SHAPES = [s for s in _ZQPA_SHAPES if 16 <= s[1] <= 832 and s[0] < 130] + [(3, 832, 13, False, False), (3, 832, 60, False, False)]
 _ZQPA_F32_TOO_WIDE = {(3, 832, 60, False, False)}  # no f32 form fits the LDS (include/crt1d_hip.h): refused, nothing launched
 
@@ -219,7 +225,10 @@ def _offset_cases(dt, nkeys):
     return [(o,) * nkeys for o in OFFSETS[dt]] + [tuple(MIXED[dt][i % len(MIXED[dt])] for i in range(nkeys))]
 
 
-_FORCED = {"n79": {10: 1}, "zq": {10: 1}, "zq_pa": {10: 5}}  # one forced family per scheme; the closed forms: k_tile
+# one forced family per scheme: k_tri_tile, k_zqpa_pipe, and k_tile for the closed forms
+_FORCED = {"n79": {_lib.TUNE_TRI_FAMILY: _lib.TRI_FAMILY_NO_PIPELINE}, "zq": {_lib.TUNE_TRI_FAMILY: _lib.TRI_FAMILY_NO_PIPELINE},
+           "zq_pa": {_lib.TUNE_TRI_FAMILY: _lib.TRI_FAMILY_ZQPA_PIPE}}
+_FORCED_CLOSED = {_lib.TUNE_TILE_FLAGS: _lib.TILE_FLAG_NO_PIPELINE}
 _ALIGN_SHAPES = [(3, 20, 33), (3, 37, 33), (3, 64, 13), (3, 107, 61), (2, 300, 33)]  # an even width <= 32 (packed), odd, 64, 107, 300
 
 
@@ -236,7 +245,7 @@ def test_solve_outputs_at_any_offset(scheme, dtype):
         ref = batched.Plan(scheme, cols, bands)
         ref()
         torch.cuda.synchronize()
-        for tune in ({}, _FORCED.get(scheme, {2: 4})):
+        for tune in ({}, _FORCED.get(scheme, _FORCED_CLOSED)):
             for offs in _offset_cases(dtype, len(ref.out)):
                 g = _guarded_like(ref.out, offs)
                 out = {k: v.view for k, v in g.items()}
