@@ -163,6 +163,7 @@ EXPORTS = [
     "crt_hip_integrated_f32",
     "crt_hip_integrated2_f32",
     "crt_hip_absorb_f32",
+    "crt_hip_bandsum_finish_f64",
     "crt_hip_band_reduce_f64",
     "crt_hip_tau_d_f64",
     "crt_hip_smear_tuv_f64",
@@ -256,6 +257,8 @@ def load():
         f = getattr(lib, f"crt_hip_absorb_{suffix}")
         f.restype = ctypes.c_int
         f.argtypes = [ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), _vp, _vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _vp]
+    lib.crt_hip_bandsum_finish_f64.restype = ctypes.c_int
+    lib.crt_hip_bandsum_finish_f64.argtypes = [ctypes.POINTER(CrtColumns), ctypes.c_int32, ctypes.POINTER(CrtBandsumOut), _vp]
     lib.crt_hip_band_reduce_f64.restype = ctypes.c_int
     lib.crt_hip_band_reduce_f64.argtypes = [_vp, ctypes.c_int64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp]
     lib.crt_hip_tau_d_f64.restype = ctypes.c_int

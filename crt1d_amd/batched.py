@@ -569,6 +569,40 @@ def absorb_bandsum(cols: Columns, bands: Bands, sol, band_w, out=None, profiles=
     return dict(BandSumPlan(cols, bands, sol, band_w, out=out, profiles=profiles)())
 
 
+class BandSumFinishPlan:
+    """Pre-validated launch of ``crt_hip_bandsum_finish_f64`` on fixed ``profiles=True`` band-sum buffers ``out``: re-forms, in place,
+    ``aI = aI_sl + aI_sh`` and the level profiles ``F``, ``I_d`` from the level sums ``I_dr, I_df_d, I_df_u`` -- the outputs
+    :class:`crt1d_amd.dist.BandShardPlan` does not send, after the all-reduce of the others.  ``F`` and ``I_d`` are the bits the
+    epilogue writes for the same sums."""
+
+    def __init__(self, cols: Columns, out):
+        self.lib = _lib.load()
+        ncol, nz, dev = cols.ncol, cols.nz, cols.device
+        ng = out["aI"].shape[-1] if out["aI"].ndim == 3 else 0
+        if not 1 <= ng <= 4:
+            raise ValueError("out['aI'] must be (ncol, nz-1, ngroup <= 4)")
+        for k, sh in bandsum_shapes(ncol, nz, ng, profiles=True).items():
+            if k not in ("totals", "aI_dr"):
+                _check_profile(out[k], f"out[{k!r}]", sh, dev)
+        self.cols, self.out, self.ng = cols, out, ng
+        self._c = cols.c_struct()
+        self._o = _lib.CrtBandsumOut(**{k: out[k].data_ptr() for k in ("aI", "aI_sl", "aI_sh", "I_dr", "I_df_d", "I_df_u", "F", "I_d")})
+
+    def __call__(self, stream=None):
+        dev = self.cols.device
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.device(dev):
+            st = self.lib.crt_hip_bandsum_finish_f64(ctypes.byref(self._c), self.ng, ctypes.byref(self._o), s.cuda_stream)
+        _lib.check(st, "crt_hip_bandsum_finish_f64")
+        return self.out
+
+
+def bandsum_finish(cols: Columns, out):
+    """``aI``, ``F`` and ``I_d`` of the ``profiles=True`` band sums ``out`` re-formed in place from ``aI_sl, aI_sh, I_dr, I_df_d, I_df_u``
+    (:class:`BandSumFinishPlan`); returns ``out``."""
+    return BandSumFinishPlan(cols, out)()
+
+
 ABSORPTION_KEYS = ("aI", "aI_df", "aI_dr", "aI_sh", "aI_sl", "aI_df_sl", "aI_df_sh")  # model.py:637-647
 
 

@@ -61,19 +61,24 @@ struct EpiArgsT {
 typedef EpiArgsT<double> EpiArgs;
 
 // level outputs from the three level sums: F = I_dr / mu + 2 I_df_u + 2 I_df_d is linear in the profiles (every scheme forms its F this
-// way, e.g. _solve_2s.py:156), so its band sum is the same combination of the band sums; I_d = I_dr + I_df_d (model.py:425)
-template <class A>
+// way, e.g. _solve_2s.py:156), so its band sum is the same combination of the band sums; I_d = I_dr + I_df_d (model.py:425).
+// SUMS = false stores F and I_d only (k_bandsum_finish: the three sums are its inputs), from the very same expressions.
+template <bool SUMS = true, class A>
 __device__ inline void store_level_profiles(const A& a, long long o, double R, double Dn, double Up, double invmu, bool accumulate) {
   if (accumulate) {
-    a.L_dr[o] += R;
-    a.L_dn[o] += Dn;
-    a.L_up[o] += Up;
+    if constexpr (SUMS) {
+      a.L_dr[o] += R;
+      a.L_dn[o] += Dn;
+      a.L_up[o] += Up;
+    }
     a.L_F[o] += R * invmu + 2 * (Up + Dn);
     a.L_Id[o] += R + Dn;
   } else {
-    __builtin_nontemporal_store(R, a.L_dr + o);
-    __builtin_nontemporal_store(Dn, a.L_dn + o);
-    __builtin_nontemporal_store(Up, a.L_up + o);
+    if constexpr (SUMS) {
+      __builtin_nontemporal_store(R, a.L_dr + o);
+      __builtin_nontemporal_store(Dn, a.L_dn + o);
+      __builtin_nontemporal_store(Up, a.L_up + o);
+    }
     __builtin_nontemporal_store(R * invmu + 2 * (Up + Dn), a.L_F + o);
     __builtin_nontemporal_store(R + Dn, a.L_Id + o);
   }
@@ -720,6 +725,43 @@ __global__ __launch_bounds__(256) void k_absorb_bandsum_h(EpiArgsT<TIO> a, int w
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   if (!colok) return;
   bandsum_finish<NGT>(a, c, raw, ends, a.lai + (long long)c * nz, column_kb(a, c), l, 32);
+}
+
+// ------------------------------------------------------------------------------------------
+// crt_hip_bandsum_finish_f64: the band-sum outputs that are NOT all-reduced by the band partition (crt1d_amd/dist.py), re-formed in
+// one pass from the reduced ones: aI = aI_sl + aI_sh (model.py:633-635), and per level F and I_d from the level sums of I_dr, I_df_d,
+// I_df_u through store_level_profiles with invmu = 1 / cos(psi) as the epilogue forms it -- so F and I_d are the bits the epilogue
+// writes for the same sums.  One wave per column (invmu once per column), lanes over (level, group): every access is coalesced; the
+// outputs are not read again here (streaming stores).  Waves stride over the columns.
+struct FinishArgs {
+  int ncol, nz, ngroup;
+  const double* psi;
+  const double* aI_sl;
+  const double* aI_sh;
+  const double* L_dr;
+  const double* L_dn;
+  const double* L_up;
+  double* aI;
+  double* L_F;
+  double* L_Id;
+};
+constexpr int FIN_WPB = 4;
+
+__global__ __launch_bounds__(64 * FIN_WPB) void k_bandsum_finish(FinishArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int nwaves = gridDim.x * FIN_WPB;
+  const int nl = (a.nz - 1) * a.ngroup, nv = a.nz * a.ngroup;
+  for (int c = __builtin_amdgcn_readfirstlane(blockIdx.x * FIN_WPB + (threadIdx.x >> 6)); c < a.ncol; c += nwaves) {
+    const double invmu = 1.0 / cos(a.psi[c]);  // as k_absorb_bandsum / bandsum_finish
+    const long long ol = (long long)c * nl, ov = (long long)c * nv;
+    for (int i = lane; i < nl; i += 64)
+      __builtin_nontemporal_store(__builtin_nontemporal_load(a.aI_sl + ol + i) + __builtin_nontemporal_load(a.aI_sh + ol + i), a.aI + ol + i);
+    for (int i = lane; i < nv; i += 64) {
+      const double R = __builtin_nontemporal_load(a.L_dr + ov + i), Dn = __builtin_nontemporal_load(a.L_dn + ov + i),
+                   Up = __builtin_nontemporal_load(a.L_up + ov + i);
+      store_level_profiles<false>(a, ov + i, R, Dn, Up, invmu, false);
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1484,6 +1526,30 @@ int crt_hip_integrated_f32(int scheme, const crt_columns* cols, const crt_bands_
   o.aI_sh = aI_sh;
   o.totals = totals;
   return crt_hip_integrated2_f32(scheme, cols, bands, opts, band_w, ngroup, &o, workspace, workspace_bytes, stream);
+}
+
+int crt_hip_bandsum_finish_f64(const crt_columns* cols, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream) {
+  if (!cols || !out || !cols->psi || ngroup <= 0 || ngroup > INT_MAXG) return CRT_ERR_BAD_ARG;
+  if (!out->aI || !out->aI_sl || !out->aI_sh || !out->I_dr || !out->I_df_d || !out->I_df_u || !out->F || !out->I_d) return CRT_ERR_BAD_ARG;
+  if (cols->ncol <= 0 || cols->nz < 2) return CRT_ERR_BAD_ARG;
+  if ((long long)cols->nz * ngroup > 0x7fffffffLL) return CRT_ERR_UNSUPPORTED;  // a column's (level, group) index is 32-bit
+  FinishArgs a;
+  a.ncol = cols->ncol;
+  a.nz = cols->nz;
+  a.ngroup = ngroup;
+  a.psi = cols->psi;
+  a.aI_sl = out->aI_sl;
+  a.aI_sh = out->aI_sh;
+  a.L_dr = out->I_dr;
+  a.L_dn = out->I_df_d;
+  a.L_up = out->I_df_u;
+  a.aI = out->aI;
+  a.L_F = out->F;
+  a.L_Id = out->I_d;
+  // 8192 workgroups of four waves fill every CU at full occupancy; more columns than waves are strided
+  const int nblk = (int)std::min<long long>(((long long)a.ncol + FIN_WPB - 1) / FIN_WPB, 8192);
+  hipLaunchKernelGGL(k_bandsum_finish, dim3(nblk), dim3(64 * FIN_WPB), 0, static_cast<hipStream_t>(stream), a);
+  return hipGetLastError() == hipSuccess ? CRT_OK : CRT_ERR_LAUNCH;
 }
 
 int crt_hip_band_reduce_f64(const double* X, int64_t nrow, int32_t nb, const double* band_w, int32_t ngroup, double* out, crt_stream_t stream) {

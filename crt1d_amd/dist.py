@@ -11,6 +11,9 @@ The (column x band) solves are independent units; nothing 
   layer absorption and of the energy-balance terms and ONE all-reduce(sum) of one packed fp64 buffer per column tile
   completes them (all band groups in a single call; xGMI rings are per-link bound, so fewer/larger messages).
   Ratios (reflectance = reflected / incoming, ``diagnostics.py:510-511``) are formed after the reduce.
+  ``level_profiles=True`` adds the band-integrated LEVEL profiles of ``diagnostics.band`` (``batched.PROFILE_KEYS``) to that one
+  reduce: the message carries the level sums of ``I_dr, I_df_d, I_df_u`` and ``aI_dr``; ``F``, ``I_d`` and ``aI`` are linear in what
+  travels and are re-formed after the reduce by one HIP kernel (``crt_hip_bandsum_finish_f64``).
 
 :class:`BandShardPlan` is the steady-state form of the band partition (buffers and launches planned once; ``bench.py
 --partition band`` times it); :func:`solve_sharded` is the one-shot form.  The compute functions are injectable so that the
@@ -26,6 +29,12 @@ KEYS = ("aI", "aI_sl", "aI_sh", "totals")
 # parts after the all-reduce (a third less on the wire; at 8 ranks the ring all-reduce of config 4's messages is comparable to a
 # rank's compute).  The re-formed sum differs from a directly reduced aI by rounding only (~1e-16 relative).
 MSG_KEYS = ("aI_sl", "aI_sh", "totals")
+# level_profiles=True: the band-integrated level profiles travel as well, but only those that cannot be re-formed exactly --
+# F = I_dr / mu + 2 (I_df_u + I_df_d) and I_d = I_dr + I_df_d are linear in the three level sums (api.hip store_level_profiles,
+# model.py:425) and are re-formed after the reduce with aI (crt_hip_bandsum_finish_f64): 1803 instead of 2403 doubles per column at
+# nz = 100, ngroup = 3
+PROFILE_KEYS = ("aI_dr", "I_dr", "I_df_d", "I_df_u", "F", "I_d")  # = batched.PROFILE_KEYS
+PROFILE_MSG_KEYS = ("aI_dr", "I_dr", "I_df_d", "I_df_u")
 
 
 def block_range(n, rank, world, unit=1):
@@ -53,16 +62,22 @@ def _world(group):
     return 1, 0
 
 
-def _shapes(ncol, nz, ng):
-    return {"aI": (ncol, nz - 1, ng), "aI_sl": (ncol, nz - 1, ng), "aI_sh": (ncol, nz - 1, ng), "totals": (ncol, ng, 4)}
+def _shapes(ncol, nz, ng, profiles=False):
+    sh = {"aI": (ncol, nz - 1, ng), "aI_sl": (ncol, nz - 1, ng), "aI_sh": (ncol, nz - 1, ng), "totals": (ncol, ng, 4)}
+    if profiles:  # batched.bandsum_shapes(..., profiles=True)
+        sh["aI_dr"] = (ncol, nz - 1, ng)
+        for k in PROFILE_KEYS[1:]:
+            sh[k] = (ncol, nz, ng)
+    return sh
 
 
 class _Tile:
     """One column tile of a band-sharded step: its packed message buffer, views into it, and the launch closure."""
 
-    def __init__(self, clo, chi, nz, ng, like):
+    def __init__(self, clo, chi, nz, ng, like, profiles=False):
         self.clo, self.chi = clo, chi
-        shapes = _shapes(chi - clo, nz, ng)
+        shapes = _shapes(chi - clo, nz, ng, profiles)
+        msg = MSG_KEYS + (PROFILE_MSG_KEYS if profiles else ())
 
         def numel(k):
             m = 1
@@ -70,13 +85,15 @@ class _Tile:
                 m *= s
             return m
 
-        self.flat = torch.empty(sum(numel(k) for k in MSG_KEYS), dtype=torch.float64, device=like.device)  # the all-reduce message
+        self.flat = torch.empty(sum(numel(k) for k in msg), dtype=torch.float64, device=like.device)  # the all-reduce message
         self.views, off = {}, 0
-        for k in MSG_KEYS:
+        for k in msg:
             self.views[k] = self.flat[off:off + numel(k)].view(shapes[k])
             off += numel(k)
-        self.views["aI"] = torch.empty(shapes["aI"], dtype=torch.float64, device=like.device)  # local; re-formed after a reduce
-        self.launch = None   # () -> profiles or None; fills self.flat and views["aI"]
+        for k in ("aI", "F", "I_d") if profiles else ("aI",):  # local; re-formed after a reduce
+            self.views[k] = torch.empty(shapes[k], dtype=torch.float64, device=like.device)
+        self.launch = None   # () -> profiles or None; fills self.flat and the local views
+        self.finish = None   # () -> None: re-forms the local views from the reduced message (level_profiles=True)
         self.work = None
         self.reduced = False
         self.profiles = None
@@ -96,11 +113,18 @@ class BandShardPlan:
 
     ``share_profiles=True``: all tiles write their profiles into ONE set of output buffers (memory of one tile instead of all
     of them; config 4 on one GPU is 168 GB otherwise).  The profiles of earlier tiles are then gone after the step.
+
+    ``level_profiles=True``: the results also hold the band-integrated level profiles ``batched.PROFILE_KEYS`` of all columns.  The
+    kernels (or ``epilogue_fn`` / ``integrated_fn``, called with ``profiles=True``) write ``aI_dr, I_dr, I_df_d, I_df_u`` into the
+    message too; after a tile's reduce ``finish_fn(cols, views)`` (default: the HIP ``crt_hip_bandsum_finish_f64``) re-forms ``aI``,
+    ``F`` and ``I_d`` from the reduced sums.
     """
 
     def __init__(self, scheme, cols, bands, band_w, *, group=None, column_tiles=1, keep_profiles=True, share_profiles=False,
-                 solve_fn=None, epilogue_fn=None, integrated_fn=None, placement="auto", always_reduce=False, **opts):
+                 solve_fn=None, epilogue_fn=None, integrated_fn=None, placement="auto", always_reduce=False, level_profiles=False,
+                 finish_fn=None, **opts):
         self.scheme, self.group = scheme, group
+        self.level_profiles = bool(level_profiles)
         self.always_reduce = always_reduce  # issue the all-reduces even in a world of one rank (API rehearsal)
         self.world, self.rank = _world(group)
         self.ncol, self.nz = cols.ncol, cols.nz
@@ -119,7 +143,9 @@ class BandShardPlan:
         for t in range(self.ntile):
             clo, chi = block_range(cols.ncol, t, self.ntile)
             ct, bt = (cols, b) if self.ntile == 1 else (cols.slice(clo, chi), b.slice(clo, chi))
-            tile = _Tile(clo, chi, self.nz, self.ng, bw)
+            tile = _Tile(clo, chi, self.nz, self.ng, bw, profiles=self.level_profiles)
+            if self.level_profiles and self.world > 1:  # only a reduced tile is finished
+                tile.finish = self._finish(tile, ct, finish_fn)
             if functional:
                 tile.launch = self._functional_launch(tile, ct, bt, bw, solve_fn, epilogue_fn, integrated_fn, opts)
             else:
@@ -133,11 +159,11 @@ class BandShardPlan:
                     plan = batched.Plan(scheme, ct, bt, out=out, placement=placement, **opts)
                     if share_profiles and shared is None:
                         shared = (chi - clo, plan.out)
-                    epi = batched.BandSumPlan(ct, bt, plan.out, bw, out=tile.views)
+                    epi = batched.BandSumPlan(ct, bt, plan.out, bw, out=tile.views, profiles=self.level_profiles)
                     tile.launch = self._planned_launch(plan, epi)
                     tile.kernel_plan = plan
                 else:
-                    ip = batched.IntegratedPlan(scheme, ct, bt, bw, out=tile.views, **opts)
+                    ip = batched.IntegratedPlan(scheme, ct, bt, bw, out=tile.views, profiles=self.level_profiles, **opts)
                     tile.launch = lambda ip=ip: (ip(), None)[1]
                     tile.kernel_plan = ip
             self.tiles.append(tile)
@@ -151,15 +177,26 @@ class BandShardPlan:
 
         return go
 
+    @staticmethod
+    def _finish(tile, ct, finish_fn):
+        if finish_fn is not None:
+            return lambda: finish_fn(ct, tile.views)
+        from . import batched
+
+        return batched.BandSumFinishPlan(ct, tile.views)
+
     def _functional_launch(self, tile, ct, bt, bw, solve_fn, epilogue_fn, integrated_fn, opts):
+        prof = {"profiles": True} if self.level_profiles else {}  # the four-argument test doubles keep working without level profiles
+        keys = KEYS + (PROFILE_KEYS if self.level_profiles else ())
+
         def go():
             if self.keep_profiles:
                 sol = solve_fn(self.scheme, ct, bt, **opts)
-                res = epilogue_fn(ct, bt, sol, bw)
+                res = epilogue_fn(ct, bt, sol, bw, **prof)
             else:
                 sol = None
-                res = dict(integrated_fn(self.scheme, ct, bt, bw, **opts))
-            for k in KEYS:
+                res = dict(integrated_fn(self.scheme, ct, bt, bw, **prof, **opts))
+            for k in keys:
                 tile.views[k].copy_(res[k])
             return sol
 
@@ -191,19 +228,23 @@ class BandShardPlan:
 
     def wait(self):
         """Complete the step's collectives; returns ``aI, aI_sl, aI_sh (ncol, nz-1, ngroup)``, ``totals (ncol, ngroup, 4)``,
-        ``reflectance (ncol, ngroup)`` for ALL columns, plus ``columns`` and ``profiles`` (this rank's bands; a list per tile)."""
+        ``reflectance (ncol, ngroup)`` for ALL columns, plus ``columns`` and ``profiles`` (this rank's bands; a list per tile); with
+        ``level_profiles=True`` also ``aI_dr (ncol, nz-1, ngroup)`` and ``I_dr, I_df_d, I_df_u, F, I_d (ncol, nz, ngroup)``."""
         for tile in self.tiles:
             if tile.work is not None:
                 tile.work.wait()
                 tile.work = None
-            if tile.reduced:  # the total from its reduced parts (the local aI held this rank's partial sum only)
-                torch.add(tile.views["aI_sl"], tile.views["aI_sh"], out=tile.views["aI"])
+            if tile.reduced:  # the local outputs held this rank's partial sums only: re-form them from the reduced message
+                if tile.finish is not None:
+                    tile.finish()  # aI, F, I_d; stream-ordered after the collective
+                else:
+                    torch.add(tile.views["aI_sl"], tile.views["aI_sh"], out=tile.views["aI"])
                 tile.reduced = False
         if self.ntile == 1:
             res = dict(self.tiles[0].views)
             prof = self.tiles[0].profiles
         else:
-            res = {k: torch.cat([t.views[k] for t in self.tiles], dim=0) for k in KEYS}
+            res = {k: torch.cat([t.views[k] for t in self.tiles], dim=0) for k in KEYS + (PROFILE_KEYS if self.level_profiles else ())}
             prof = [t.profiles for t in self.tiles]
         tot = res["totals"]
         res["reflectance"] = tot[..., 1] / tot[..., 0]  # I_df_u[top] / I_d[top]  (diagnostics.py:510-511)
@@ -219,7 +260,7 @@ def _default_fns():
 
 
 def solve_sharded(scheme, cols, bands, band_w, *, partition="column", group=None, solve_fn=None, epilogue_fn=None,
-                  keep_profiles=True, integrated_fn=None, column_tiles=1, **opts):
+                  keep_profiles=True, integrated_fn=None, column_tiles=1, level_profiles=False, finish_fn=None, **opts):
     """Solve this rank's shard once and return spectrally integrated results.
 
     ``cols`` / ``bands``: the FULL problem (objects with ``.ncol``, ``.nb``, ``.slice(lo, hi)``, ``.band_slice(lo, hi)``;
@@ -234,6 +275,9 @@ def solve_sharded(scheme, cols, bands, band_w, *, partition="column", group=None
     stay float64.
     ``column_tiles > 1`` (band partition): the columns are processed in that many tiles and the all-reduce of tile i is
     issued asynchronously while tile i+1 is being solved; ``profiles`` is then a list with one entry per tile.
+    ``level_profiles=True`` adds the band-integrated level profiles ``batched.PROFILE_KEYS`` (``aI_dr (ncol_local, nz-1, ngroup)``,
+    ``I_dr, I_df_d, I_df_u, F, I_d (ncol_local, nz, ngroup)``; ``epilogue_fn`` / ``integrated_fn`` are called with ``profiles=True``);
+    in the band partition they are all-reduced with the other sums (:class:`BandShardPlan`, ``finish_fn``).
     """
     if partition == "band":
         if keep_profiles and solve_fn is None and epilogue_fn is None:
@@ -247,7 +291,8 @@ def solve_sharded(scheme, cols, bands, band_w, *, partition="column", group=None
             integrated_fn = batched.solve_integrated
         plan = BandShardPlan(scheme, cols, bands, band_w, group=group, column_tiles=column_tiles, keep_profiles=keep_profiles,
                              solve_fn=solve_fn if keep_profiles else None, epilogue_fn=epilogue_fn if keep_profiles else None,
-                             integrated_fn=None if keep_profiles else integrated_fn, **opts)
+                             integrated_fn=None if keep_profiles else integrated_fn, level_profiles=level_profiles, finish_fn=finish_fn,
+                             **opts)
         return plan().wait()
     if partition != "column":
         raise ValueError("partition must be 'column' or 'band'")
@@ -258,16 +303,17 @@ def solve_sharded(scheme, cols, bands, band_w, *, partition="column", group=None
     world, rank = _world(group)
     lo, hi = block_range(cols.ncol, rank, world)
     c, b = cols.slice(lo, hi), bands.slice(lo, hi)
+    prof = {"profiles": True} if level_profiles else {}
     if keep_profiles:
         sol = solve_fn(scheme, c, b, **opts)
-        res = dict(epilogue_fn(c, b, sol, band_w))
+        res = dict(epilogue_fn(c, b, sol, band_w, **prof))
     else:
         if integrated_fn is None:
             from . import batched
 
             integrated_fn = batched.solve_integrated
         sol = None
-        res = dict(integrated_fn(scheme, c, b, band_w, **opts))
+        res = dict(integrated_fn(scheme, c, b, band_w, **prof, **opts))
     tot = res["totals"]
     res["reflectance"] = tot[..., 1] / tot[..., 0]  # I_df_u[top] / I_d[top]  (diagnostics.py:510-511)
     res["columns"] = (lo, hi)
@@ -279,8 +325,10 @@ def grid_mean(res, ncol_total, group=None):
     """Domain means of the integrated results of a COLUMN-partitioned run: every rank sums its own columns' ``aI, aI_sl, aI_sh
     (ncol_local, nz-1, ngroup)`` and ``totals (ncol_local, ngroup, 4)``, ONE small all-reduce (RCCL) adds the ranks' sums, and the
     means and the grid reflectance (reflected / incoming, ``diagnostics.py:510-511``) are formed after it -- "the final reduce of
-    spectrally-integrated absorption / reflectance" of the column partition.  Every rank gets the same result."""
-    keys = ("aI", "aI_sl", "aI_sh", "totals")
+    spectrally-integrated absorption / reflectance" of the column partition.  Every rank gets the same result.
+    A result that carries the level profiles (``level_profiles=True``: ``batched.PROFILE_KEYS``) has their domain means in the same
+    all-reduce."""
+    keys = ("aI", "aI_sl", "aI_sh", "totals") + (PROFILE_KEYS if all(k in res for k in PROFILE_KEYS) else ())
     flat = torch.cat([res[k].sum(dim=0).reshape(-1) for k in keys])
     world, _ = _world(group)
     if world > 1 or (dist.is_available() and dist.is_initialized()):

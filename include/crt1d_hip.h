@@ -306,6 +306,13 @@ int crt_hip_integrated2_f64(int scheme, const crt_columns* cols, const crt_bands
  * nb <= 1024 (else CRT_ERR_UNSUPPORTED); crt_hip_last_kernel names the float instantiation with an " f32" tag. */
 int crt_hip_integrated2_f32(int scheme, const crt_columns* cols, const crt_bands_f32* bands, const crt_options* opts, const double* band_w,
                             int32_t ngroup, const crt_bandsum_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream);
+/* The outputs of crt_bandsum_out that follow from the others, re-formed in place in one pass (after the band sums of partial spectra
+ * have been added up, e.g. by an all-reduce that carried only aI_sl, aI_sh and the level sums I_dr, I_df_d, I_df_u):
+ *     aI = aI_sl + aI_sh,   F = I_dr / cos(psi) + 2 (I_df_u + I_df_d),   I_d = I_dr + I_df_d
+ * F and I_d are bitwise what crt_hip_absorb_bandsum2_* (nb <= 1024; wider spectra add F in pieces) / crt_hip_integrated2_* write for
+ * the same level sums.  Reads cols->psi (ncol, nz),
+ * aI_sl, aI_sh, I_dr, I_df_d, I_df_u; writes aI, F, I_d; aI_dr and totals are ignored.  ngroup 1..4. */
+int crt_hip_bandsum_finish_f64(const crt_columns* cols, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream);
 
 /*
  * Fused solve + epilogue: the integrated outputs of crt_hip_absorb_bandsum_f64 (same shapes and meaning) straight from
