@@ -22,6 +22,9 @@ FLAG_SKIP_PRECOMPUTE = 1
 FLAG_PRECOMPUTE_ONLY = 2
 FLAG_DIRECT_STORES = 4
 
+# crt_hip_levels_*: most levels one call serves (CRT_MAX_LEVEL_SELECT)
+MAX_LEVEL_SELECT = 64
+
 CRT_OK = 0
 CRT_ERR_BAD_ARG = -1
 CRT_ERR_WORKSPACE = -2
@@ -162,6 +165,8 @@ EXPORTS = [
     "crt_hip_absorb_bandsum2_f32",
     "crt_hip_integrated_f32",
     "crt_hip_integrated2_f32",
+    "crt_hip_levels_f64",
+    "crt_hip_levels_f32",
     "crt_hip_absorb_f32",
     "crt_hip_bandsum_finish_f64",
     "crt_hip_band_reduce_f64",
@@ -257,6 +262,13 @@ def load():
         f = getattr(lib, f"crt_hip_absorb_{suffix}")
         f.restype = ctypes.c_int
         f.argtypes = [ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), _vp, _vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _vp]
+    for suffix in ("f64", "f32"):  # level-subset solve (crt_bands_f32 / crt_outputs_f32 share the f64 layouts)
+        f = getattr(lib, f"crt_hip_levels_{suffix}")
+        f.restype = ctypes.c_int
+        f.argtypes = [
+            ctypes.c_int, ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), ctypes.POINTER(CrtOptions), ctypes.POINTER(ctypes.c_int32),
+            ctypes.c_int32, ctypes.POINTER(CrtOutputs), _vp, ctypes.c_size_t, _vp,
+        ]
     lib.crt_hip_bandsum_finish_f64.restype = ctypes.c_int
     lib.crt_hip_bandsum_finish_f64.argtypes = [ctypes.POINTER(CrtColumns), ctypes.c_int32, ctypes.POINTER(CrtBandsumOut), _vp]
     lib.crt_hip_band_reduce_f64.restype = ctypes.c_int

@@ -695,3 +695,117 @@ class IntegratedPlan:
 def solve_integrated(scheme, cols: Columns, bands: Bands, band_w, **kw):
     with torch.cuda.device(cols.device):
         return IntegratedPlan(scheme, cols, bands, band_w, **kw)()
+
+
+LEVEL_KEYS = ("I_dr", "I_df_d", "I_df_u", "F")  # the profiles a level-subset solve serves, in crt_outputs slot order
+
+
+def normalize_levels(levels, nz):
+    """The level selection of :class:`LevelsPlan` as a sorted tuple of distinct indices in ``[0, nz)``.  ``levels`` is an int or an
+    iterable of ints; negative values count from the top as in NumPy (``-1`` = ``nz - 1``, the canopy top).  ValueError for an empty
+    or too long selection (more than ``_lib.MAX_LEVEL_SELECT``), a non-integer, a level outside ``[-nz, nz)`` and a level given twice."""
+    import operator
+
+    if hasattr(levels, "tolist"):  # NumPy / torch integers and arrays
+        levels = levels.tolist()
+    if not hasattr(levels, "__iter__"):
+        levels = [levels]
+    try:
+        raw = [operator.index(v) for v in levels]
+    except TypeError as e:
+        raise ValueError(f"levels must be integers: {e}") from None
+    if not raw:
+        raise ValueError("levels is empty: select at least one level")
+    out = []
+    for v in raw:
+        if not -nz <= v < nz:
+            raise ValueError(f"level {v} is out of range for nz = {nz} (valid: {-nz} .. {nz - 1})")
+        out.append(v + nz if v < 0 else v)
+    if len(set(out)) != len(out):
+        dup = sorted({v for v in out if out.count(v) > 1})
+        raise ValueError(f"level(s) {dup} selected more than once (negative indices count from nz = {nz})")
+    if len(out) > _lib.MAX_LEVEL_SELECT:
+        raise ValueError(f"{len(out)} levels selected; one call serves at most {_lib.MAX_LEVEL_SELECT}")
+    return tuple(sorted(out))
+
+
+class LevelsPlan:
+    """Pre-validated level-subset solve (``crt_hip_levels_f64``, or ``_f32`` for float32 bands): the spectra of ``keys`` (any of
+    ``I_dr, I_df_d, I_df_u, F``) at the levels ``levels`` only, each ``(ncol, nsel, nb)`` in the dtype of ``bands``; row ``r`` is level
+    ``self.levels[r]`` (sorted, negatives resolved: :func:`normalize_levels`).  Every row is bitwise the row of :func:`solve`'s profile
+    for the same inputs; the other levels are never written (at 60 levels and two selected, 3 % of the bytes)."""
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, levels, *, keys=LEVEL_KEYS, mu_s=0.501, tau_d_method="quad", out=None,
+                 workspace=None):
+        if scheme not in _lib.SCHEME_IDS:
+            raise ValueError(f"unknown scheme {scheme!r}; valid: {', '.join(SCHEMES)}")
+        if tau_d_method not in _lib.TAU_D_METHODS:
+            raise ValueError("invalid `method`. Valid options are 'quad' and '9sky'.")  # common.py:78
+        keys = (keys,) if isinstance(keys, str) else tuple(keys)
+        if not keys or any(k not in LEVEL_KEYS for k in keys) or len(set(keys)) != len(keys):
+            raise ValueError(f"keys must be distinct names out of {LEVEL_KEYS}, got {keys!r}")
+        self.lib = _lib.load()
+        self.scheme, self.cols, self.bands = scheme, cols, bands
+        ncol, nz, nb, dev = cols.ncol, cols.nz, bands.nb, cols.device
+        self.levels = normalize_levels(levels, nz)
+        self.keys = keys
+        if scheme == "2s" and cols.mla is None:
+            raise ValueError("solve_2s needs `mla`")
+        if scheme != "bl" and bands.soil_r is None:
+            raise ValueError(f"solve_{scheme} needs `soil_r`")
+        cols.check_tables()
+        _check_band_device(bands, dev)
+        shape = (ncol, len(self.levels), nb)
+        if out is None:
+            out = {k: torch.empty(shape, dtype=bands.dtype, device=dev) for k in keys}
+        else:
+            for k in keys:
+                if k not in out:
+                    raise ValueError(f"`out` lacks {k!r}")
+                _check_profile(out[k], f"output {k!r}", shape, dev, bands.dtype)
+            out = {k: out[k] for k in keys}
+        self.out = out
+        self._out = _lib.CrtOutputs(*[out[k].data_ptr() if k in out else None for k in LEVEL_KEYS], None, None, None)
+        self._lev = (ctypes.c_int32 * len(self.levels))(*self.levels)
+        need = workspace_bytes(scheme, ncol, nz, nb)
+        self.workspace = _check_workspace(workspace, need, dev)
+        self._wsb = self.workspace.numel() * self.workspace.element_size()
+        self._c, self._b = cols.c_struct(), bands.c_struct(ncol)
+        self._o = _lib.CrtOptions(float(mu_s), _lib.TAU_D_METHODS[tau_d_method], 0)
+        self._entry = f"crt_hip_levels_{_io_suffix(bands)}"
+        self._fn = getattr(self.lib, self._entry)
+
+    def last_kernel(self):
+        """Name / configuration of the kernel this thread's most recent call launched (``crt_hip_last_kernel``)."""
+        return self.lib.crt_hip_last_kernel().decode()
+
+    def __call__(self, stream=None, *, flags=0):
+        """Enqueue on ``stream`` (default: torch's current stream); ``flags`` as for :class:`Plan`."""
+        dev = self.cols.device
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        self._o.flags = int(flags)
+        with torch.cuda.device(dev):
+            st = self._fn(_lib.SCHEME_IDS[self.scheme], ctypes.byref(self._c), ctypes.byref(self._b), ctypes.byref(self._o), self._lev,
+                          len(self.levels), ctypes.byref(self._out), self.workspace.data_ptr(), self._wsb, s.cuda_stream)
+        _lib.check(st, self._entry)
+        return self.out
+
+
+def solve_levels(scheme, cols: Columns, bands: Bands, levels, **kw):
+    """One-shot :class:`LevelsPlan`: ``{key: (ncol, nsel, nb)}`` at the sorted levels ``normalize_levels(levels, nz)``."""
+    with torch.cuda.device(cols.device):
+        return LevelsPlan(scheme, cols, bands, levels, **kw)()
+
+
+def spectral_totals(scheme, cols: Columns, bands: Bands, **kw):
+    """The per-band terms of the reference's energy balance (``compare_ebal``, diagnostics.py:510-522) before their band integral:
+    ``(ncol, nb, 4)`` float64 with, in the order of ``totals``, the incoming ``I_d[top]``, reflected ``I_df_u[top]``, transmitted
+    ``I_d[0]`` and soil-reflected ``I_df_u[0]`` spectra (``I_d = I_dr + I_df_d``), from one level-subset solve at the ground and the top.
+    Contracted with band weights ``w`` (``torch.einsum("cbq,gb->cgq", t, w)``) it gives :class:`IntegratedPlan`'s ``totals``.  The
+    canopy albedo spectrum is ``t[..., 1] / t[..., 0]``, the canopy transmittance ``t[..., 2] / t[..., 0]``.  ``kw`` as for
+    :class:`LevelsPlan` (``levels`` and ``keys`` are fixed here)."""
+    nz = cols.nz
+    r = solve_levels(scheme, cols, bands, (0, nz - 1), keys=("I_dr", "I_df_d", "I_df_u"), **kw)
+    dr, dn, up = (r[k].to(torch.float64) for k in ("I_dr", "I_df_d", "I_df_u"))
+    i_d = dr + dn
+    return torch.stack((i_d[:, 1], up[:, 1], i_d[:, 0], up[:, 0]), dim=-1)

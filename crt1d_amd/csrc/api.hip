@@ -1275,7 +1275,7 @@ int crt_hip_quad_nodes(double mu_s, double* psi_nodes) {
 
 static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts,
                       const crt_outputs* out, void* workspace, size_t workspace_bytes, crt_stream_t stream, int f32,
-                      const IntArgs* integ = nullptr) {
+                      const IntArgs* integ = nullptr, const LevArgs* lev = nullptr) {
   if (!scheme_ok(scheme) || !cols || !bands || !out) return CRT_ERR_BAD_ARG;
   const int ncol = cols->ncol, nz = cols->nz, nb = bands->nb;
   if (ncol <= 0 || nz <= 0 || nb <= 0) return CRT_ERR_BAD_ARG;
@@ -1284,10 +1284,10 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
   if (!bands->I_dr0 || !bands->I_df0 || !bands->leaf_r || !bands->leaf_t) return CRT_ERR_BAD_ARG;
   if (scheme != CRT_SCHEME_BL && !bands->soil_r) return CRT_ERR_BAD_ARG;
   if (bands->col_stride != 0 && bands->col_stride < nb) return CRT_ERR_BAD_ARG;
-  if (!integ && (!out->I_dr || !out->I_df_d || !out->I_df_u || !out->F)) return CRT_ERR_BAD_ARG;
+  if (!integ && !lev && (!out->I_dr || !out->I_df_d || !out->I_df_u || !out->F)) return CRT_ERR_BAD_ARG;
   const bool tri = scheme == CRT_SCHEME_N79 || scheme == CRT_SCHEME_ZQ;
   const int nextra = scheme == CRT_SCHEME_N79 ? 2 : (scheme == CRT_SCHEME_ZQ || scheme == CRT_SCHEME_G77 || scheme == CRT_SCHEME_BF) ? 3 : 0;
-  if (!integ) {
+  if (!integ && !lev) {
     if (nextra >= 1 && !out->x0) return CRT_ERR_BAD_ARG;
     if (nextra >= 2 && !out->x1) return CRT_ERR_BAD_ARG;
     if (nextra >= 3 && !out->x2) return CRT_ERR_BAD_ARG;
@@ -1345,7 +1345,7 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
   ca.ws = static_cast<double*>(workspace);
   // 2s profiles: the closed-form launcher forms the records inside k_pipe when it picks that kernel (one launch per call), and runs
   // k_colpre in front of any other kernel.  SKIP_PRECOMPUTE / PRECOMPUTE_ONLY and CRT_TUNE_K0_SEPARATE keep k_colpre as a kernel of its own.
-  const bool k0_in_solve = scheme == CRT_SCHEME_2S && !integ && !(flags & (CRT_FLAG_SKIP_PRECOMPUTE | CRT_FLAG_PRECOMPUTE_ONLY)) &&
+  const bool k0_in_solve = scheme == CRT_SCHEME_2S && !integ && !lev && !(flags & (CRT_FLAG_SKIP_PRECOMPUTE | CRT_FLAG_PRECOMPUTE_ONLY)) &&
                            tune[CRT_TUNE_K0_SEPARATE] == 0;
   if (k0_in_solve) {
     const int st = init_quadrature(s);
@@ -1381,6 +1381,10 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
   if (integ) {
     if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_int(sa, *integ, s);
     return tri ? launch_tridiag_int(scheme, sa, *integ, s) : launch_closed_int(scheme, sa, *integ, s);
+  }
+  if (lev) {
+    if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_lev(sa, *lev, s);
+    return tri ? launch_tridiag_lev(scheme, sa, *lev, s) : launch_closed_lev(scheme, sa, *lev, s);
   }
   if (scheme == CRT_SCHEME_ZQ_PA)
     return launch_zqpa(sa, static_cast<double*>(workspace) + (size_t)ncol * sa.reclen, s);
@@ -1526,6 +1530,40 @@ int crt_hip_integrated_f32(int scheme, const crt_columns* cols, const crt_bands_
   o.aI_sh = aI_sh;
   o.totals = totals;
   return crt_hip_integrated2_f32(scheme, cols, bands, opts, band_w, ngroup, &o, workspace, workspace_bytes, stream);
+}
+
+// f32: crt_bands_f32 / crt_outputs_f32 have the layouts of crt_bands / crt_outputs (crt_hip_solve_f32).  Every argument error is found here
+// or in solve_impl's checks, before any launch.
+static int levels_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
+                       int32_t nsel, const crt_outputs* out, void* workspace, size_t workspace_bytes, crt_stream_t stream, int f32) {
+  if (!scheme_ok(scheme) || !cols || !levels || !out) return CRT_ERR_BAD_ARG;
+  if (nsel < 1 || nsel > CRT_MAX_LEVEL_SELECT) return CRT_ERR_BAD_ARG;
+  if (out->x0 || out->x1 || out->x2) return CRT_ERR_BAD_ARG;
+  if (!out->I_dr && !out->I_df_d && !out->I_df_u && !out->F) return CRT_ERR_BAD_ARG;
+  LevArgs la = {};
+  la.o[0] = out->I_dr;
+  la.o[1] = out->I_df_d;
+  la.o[2] = out->I_df_u;
+  la.o[3] = out->F;
+  la.nsel = nsel;
+  for (int r = 0; r < nsel; ++r) {
+    if (levels[r] < 0 || levels[r] >= cols->nz) return CRT_ERR_BAD_ARG;
+    if (r > 0 && levels[r] <= levels[r - 1]) return CRT_ERR_BAD_ARG;  // strictly ascending: no duplicates
+    la.lev[r] = levels[r];
+  }
+  crt_outputs none = {};
+  return solve_impl(scheme, cols, bands, opts, &none, workspace, workspace_bytes, stream, f32, nullptr, &la);
+}
+
+int crt_hip_levels_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
+                       int32_t nsel, const crt_outputs* out, void* workspace, size_t workspace_bytes, crt_stream_t stream) {
+  return levels_impl(scheme, cols, bands, opts, levels, nsel, out, workspace, workspace_bytes, stream, 0);
+}
+
+int crt_hip_levels_f32(int scheme, const crt_columns* cols, const crt_bands_f32* bands, const crt_options* opts, const int32_t* levels,
+                       int32_t nsel, const crt_outputs_f32* out, void* workspace, size_t workspace_bytes, crt_stream_t stream) {
+  return levels_impl(scheme, cols, reinterpret_cast<const crt_bands*>(bands), opts, levels, nsel, reinterpret_cast<const crt_outputs*>(out),
+                     workspace, workspace_bytes, stream, 1);
 }
 
 int crt_hip_bandsum_finish_f64(const crt_columns* cols, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream) {

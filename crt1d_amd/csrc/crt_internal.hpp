@@ -588,6 +588,36 @@ __host__ __device__ inline size_t int_lds_doubles(int nz, int nwave, bool rows =
 int launch_closed_int(int scheme, const SolveArgs& a, const IntArgs& ia, hipStream_t s);
 int launch_tridiag_int(int scheme, const SolveArgs& a, const IntArgs& ia, hipStream_t s);
 
+// ------------------------------------------------------------------------------------------
+// Level-subset outputs (crt_hip_levels_*): rows lev[0..nsel) of I_dr, I_df_d, I_df_u, F, each [ncol][nsel][nb] or NULL.  The levels
+// travel by value in the kernel arguments (strictly ascending, validated by the entry point).  A workgroup owns one column and one
+// slice of `per` bands (grid: ncol x nslice), one lane per band: nothing is reduced across bands, so any nb works.
+struct LevArgs {
+  void* o[4];
+  int nsel;
+  int32_t lev[CRT_MAX_LEVEL_SELECT];
+};
+
+struct LevSlices {
+  int nslice, per, nthr;  // workgroups per column, bands per workgroup, lanes per workgroup (multiple of 64, >= per)
+};
+// balanced band slices of at most wmax lanes
+inline LevSlices lev_slices(int nb, int wmax) {
+  LevSlices ls;
+  ls.nslice = (nb + wmax - 1) / wmax;
+  ls.per = (nb + ls.nslice - 1) / ls.nslice;
+  ls.nthr = ((ls.per + 63) / 64) * 64;
+  return ls;
+}
+
+int launch_closed_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s);
+int launch_tridiag_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s);
+int launch_zqpa_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s);
+int launch_tri_lev_n79_f64(const SolveArgs& a, const LevArgs& la, hipStream_t s);
+int launch_tri_lev_n79_f32(const SolveArgs& a, const LevArgs& la, hipStream_t s);
+int launch_tri_lev_zq_f64(const SolveArgs& a, const LevArgs& la, hipStream_t s);
+int launch_tri_lev_zq_f32(const SolveArgs& a, const LevArgs& la, hipStream_t s);
+
 // launchers implemented in the .hip files
 int launch_colpre(const ColArgs& a, hipStream_t s);
 // k0: column records still to be formed (2s: by the k_pipe prologue when k_pipe is picked; otherwise k_colpre runs first), or nullptr

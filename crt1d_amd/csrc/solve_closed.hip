@@ -1215,7 +1215,85 @@ int launch_int_io(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
   return a.f32 ? launch_int<S, float>(a, ia, s) : launch_int<S, double>(a, ia, s);
 }
 
+// ------------------------------------------------------------------------------------------
+// k_lev: the rows lev[0..nsel) of the four contract profiles (LevArgs, crt_internal.hpp).  One workgroup per (column, band slice), one
+// lane per band.  Every scheme's level() restarts its per-level exponentials at exact_level(j) ((j & 7) == 0) on a uniform column and
+// evaluates them at every level of a ragged one, and nothing else of its state depends on earlier levels: a level j is reproduced
+// bitwise by walking from 8 floor(j / 8) (uniform) or from j itself (ragged).  Selected levels in one block of 8 share the walk.
+template <class S, typename TIO, int MAXT, bool USE_LDS>
+__global__ __launch_bounds__(MAXT) void k_lev(SolveArgs a, LevArgs la, int per) {
+  extern __shared__ double lds[];
+  const int c = blockIdx.x, nz = a.nz, nb = a.nb;
+  const double* rec = a.ws + (long long)c * a.reclen;
+  if constexpr (USE_LDS) {
+    for (int i = threadIdx.x; i < a.reclen; i += blockDim.x) lds[i] = rec[i];
+    __syncthreads();
+    rec = lds;
+  }
+  const int b = blockIdx.y * per + threadIdx.x;
+  if ((int)threadIdx.x >= per || b >= nb) return;  // (no barrier below)
+  S st;
+  st.init(rec, load_band<TIO>(a, c, b, S::SOIL), a);
+  const bool unif = rec[S_UNIF] != 0.0;
+  const int nsel = la.nsel;
+  int next = 0;  // the state has been advanced through level next - 1
+  for (int r = 0; r < nsel; ++r) {
+    const int j = la.lev[r];
+    const int j0 = max(unif ? (j & ~7) : j, next);  // next > j & ~7: level next - 1 lies in j's block, continue from there
+    double val[S::NARR];
+    for (int jj = j0; jj <= j; ++jj) st.level(jj, rec, nz, val);
+    next = j + 1;
+    const long long o = ((long long)c * nsel + r) * nb + b;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (la.o[q]) __builtin_nontemporal_store((TIO)val[q], outp<TIO>(la.o[q]) + o);
+  }
+}
+
+template <class S, typename TIO>
+int launch_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
+  const LevSlices ls = lev_slices(a.nb, 1024);  // the record is all the LDS a workgroup needs
+  if (ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
+  const size_t sh = (size_t)a.reclen * sizeof(double);
+  const bool use_lds = sh <= 160 * 1024;  // deeper columns read their record from the workspace (every nz the profile path serves)
+  auto go = [&](auto kern) {
+    const size_t shk = use_lds ? sh : 0;
+    if (shk > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shk) != hipSuccess)
+      return (int)CRT_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(a.ncol, ls.nslice), dim3(ls.nthr), shk, s, a, la, ls.per);
+    if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+    note_kernel("k_lev<%s>%s nsel=%d slice=%d%s", S::NAME, sizeof(TIO) == 8 ? "" : " f32", la.nsel, ls.per,
+                use_lds ? "" : " record in HBM");  // (only a launch that succeeded is reported)
+    return (int)CRT_OK;
+  };
+  if (!use_lds) {
+    if (ls.nthr <= 256) return go(k_lev<S, TIO, 256, false>);
+    if (ls.nthr <= 512) return go(k_lev<S, TIO, 512, false>);
+    return go(k_lev<S, TIO, 1024, false>);
+  }
+  if (ls.nthr <= 256) return go(k_lev<S, TIO, 256, true>);
+  if (ls.nthr <= 512) return go(k_lev<S, TIO, 512, true>);
+  return go(k_lev<S, TIO, 1024, true>);
+}
+
+template <class S>
+int launch_lev_io(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
+  return a.f32 ? launch_lev<S, float>(a, la, s) : launch_lev<S, double>(a, la, s);
+}
+
 }  // namespace
+
+int launch_closed_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s) {
+  switch (scheme) {
+    case CRT_SCHEME_2S: return launch_lev_io<Sch2s>(a, la, s);
+    case CRT_SCHEME_4S: return launch_lev_io<Sch4s>(a, la, s);
+    case CRT_SCHEME_BL: return launch_lev_io<SchBl>(a, la, s);
+    case CRT_SCHEME_G77: return launch_lev_io<SchG77<false>>(a, la, s);
+    case CRT_SCHEME_BF: return launch_lev_io<SchG77<true>>(a, la, s);
+    default: return CRT_ERR_BAD_ARG;
+  }
+}
 
 int launch_closed_int(int scheme, const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
   switch (scheme) {

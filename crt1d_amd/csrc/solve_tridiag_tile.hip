@@ -25,6 +25,12 @@ int launch_tridiag_int(int scheme, const SolveArgs& a, const IntArgs& ia, hipStr
   return CRT_ERR_BAD_ARG;
 }
 
+int launch_tridiag_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s) {
+  if (scheme == CRT_SCHEME_N79) return a.f32 ? launch_tri_lev_n79_f32(a, la, s) : launch_tri_lev_n79_f64(a, la, s);
+  if (scheme == CRT_SCHEME_ZQ) return a.f32 ? launch_tri_lev_zq_f32(a, la, s) : launch_tri_lev_zq_f64(a, la, s);
+  return CRT_ERR_BAD_ARG;
+}
+
 // returns CRT_OK with done = false when the column-tile kernel does not apply (caller falls back)
 int launch_tridiag_tile(int scheme, const SolveArgs& a, hipStream_t s, bool& done) {
   if (scheme == CRT_SCHEME_N79) return a.f32 ? launch_tri_tile_n79_f32(a, s, done) : launch_tri_tile_n79_f64(a, s, done);

@@ -633,6 +633,140 @@ int launch_int_scheme(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
 }
 
 // instantiated (M, T) pairs
+// ------------------------------------------------------------------------------------------
+// Level-subset outputs (LevArgs, crt_internal.hpp): the same checkpointed sweep as tri_int_body, on one band slice; where that kernel
+// reduces a level, this one stores the row if the level is selected.  The rows come from the top and the selected levels ascend, so a
+// cursor from the last selected level down is the (wave-uniform) selection test.  Row values are the profile kernels' expressions
+// (S::value<>: I_dr = bc rec[k], F formed in the scheme's own order) on the same back-substituted pair: the same bits.
+template <class S, typename TIO, int M>
+__device__ __forceinline__ void tri_lev_body(const SolveArgs& a, const LevArgs& la, int per, int off_ck, double* lds) {
+  const int nb = a.nb, nz = a.nz, nsel = la.nsel;
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int c = blockIdx.x;
+  const int b = blockIdx.y * per + tid;
+  if (tid >= per || b >= nb) return;  // (no barrier below)
+  const double* rec = lds;
+  double* ck = lds + off_ck + tid;  // [nck][2][nthr]
+  S st;
+  st.template init<TIO>(rec, a, c, b);
+  const double bc = st.band_const();
+  const double invmu = rec[S_INVMU];
+  const int K = S::rows(nz);
+  static_assert(S::RENORM == 0 || M % S::RENORM == 0, "checkpoints must fall on re-seeding levels");
+  typename S::St fs;
+  st.first(rec, nz, fs);
+  {
+    double e, f;
+    st.pair(fs, e, f);
+    ck[0] = e;
+    ck[nthr] = f;
+  }
+  tri_forward<S, M>(st, rec, nz, fs, K - 1, [&](int level, const typename S::St& cs) {
+    const int sidx = level / M;
+    double e, f;
+    st.pair(cs, e, f);
+    ck[(2 * sidx) * nthr] = e;
+    ck[(2 * sidx + 1) * nthr] = f;
+  });
+  // the back substitution carries its state from row to row: every segment from the top down to the lowest selected level is walked
+  int r = nsel - 1;  // next selected level to meet, from the top
+  for (int seg = (K - 1) / M; seg >= 0 && r >= 0; --seg) {
+    const int k0 = seg * M;
+    const int kend = min(k0 + M - 1, K - 1);
+    double be[M], bf[M];
+    be[0] = ck[(2 * seg) * nthr];
+    bf[0] = ck[(2 * seg + 1) * nthr];
+    typename S::St rs;
+    st.seed(rs, be[0], bf[0]);
+#pragma unroll
+    for (int i = 1; i < M; ++i) {
+      be[i] = be[i - 1];
+      bf[i] = bf[i - 1];
+      if (k0 + i <= kend) tri_step(st, k0 + i - 1, rec, nz, rs, be[i], bf[i]);
+    }
+#pragma unroll
+    for (int i = M - 1; i >= 0; --i) {
+      const int k = k0 + i;
+      if (k <= kend) {
+        double o[S::NST];
+        if (k == K - 1)
+          st.top(rec, nz, be[i], bf[i], o);
+        else
+          st.back(k, rec, nz, be[i], bf[i], o);
+        if (r >= 0 && la.lev[r] == k) {
+          const double t[2] = {o[0], o[1]};  // the staged I_df_d, I_df_u of the profile kernels' tile
+          const double v[4] = {S::template value<0>(rec, nz, k, bc, invmu, t, 1, 0), t[0], t[1],
+                               S::template value<3>(rec, nz, k, bc, invmu, t, 1, 0)};
+          const long long oo = ((long long)c * nsel + r) * nb + b;
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (la.o[q]) __builtin_nontemporal_store((TIO)v[q], outp<TIO>(la.o[q]) + oo);
+          --r;
+        }
+      }
+    }
+  }
+}
+
+template <class S, typename TIO, int M, int MAXT>
+__global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(M <= 8 ? 5 : 3))) void k_tri_lev(SolveArgs a, LevArgs la, int per,
+                                                                                                        int off_ck) {
+  extern __shared__ double lds[];
+  {
+    const double* src = a.ws + (long long)blockIdx.x * a.reclen;
+    for (int i = threadIdx.x; i < a.reclen; i += blockDim.x) lds[i] = src[i];
+  }
+  __syncthreads();
+  typedef typename UniformOf<S>::type SU;
+  if constexpr (!std::is_same<S, SU>::value) {
+    if (lds[S_UNIF] != 0.0) {
+      tri_lev_body<SU, TIO, M>(a, la, per, off_ck, lds);
+      return;
+    }
+  }
+  tri_lev_body<S, TIO, M>(a, la, per, off_ck, lds);
+}
+
+// LDS of k_tri_lev in bytes: record | checkpoints [nck][2][nthr]
+template <class S>
+inline size_t tri_lev_lds_bytes(const SolveArgs& a, int M, int nthr, int* off_ck = nullptr) {
+  const int K = S::rows(a.nz);
+  const int nck = (K - 1) / M + 1;
+  const int ock = (a.reclen + 1) & ~1;
+  if (off_ck) *off_ck = ock;
+  return ((size_t)ock + 2 * (size_t)nck * nthr) * sizeof(double);
+}
+
+template <class S, typename TIO, int M>
+int launch_lev_m(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
+  int wmax = 1024;  // widest slice whose checkpoints fit
+  while (wmax >= 64 && tri_lev_lds_bytes<S>(a, M, wmax) > MAX_WG_LDS) wmax >>= 1;
+  if (wmax < 64) return CRT_ERR_UNSUPPORTED;
+  const LevSlices ls = lev_slices(a.nb, wmax);
+  if (ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
+  int off_ck;
+  const size_t sh = tri_lev_lds_bytes<S>(a, M, ls.nthr, &off_ck);
+  auto go = [&](auto kern) {
+    if (sh > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
+      return (int)CRT_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(a.ncol, ls.nslice), dim3(ls.nthr), sh, s, a, la, ls.per, off_ck);
+    if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+    note_kernel("k_tri_lev<%s>%s M=%d nsel=%d slice=%d", S::NAME, sizeof(TIO) == 8 ? "" : " f32", M, la.nsel, ls.per);  // (only a launch that succeeded is reported)
+    return (int)CRT_OK;
+  };
+  if (ls.nthr <= 256) return go(k_tri_lev<S, TIO, M, 256>);
+  if (ls.nthr <= 512) return go(k_tri_lev<S, TIO, M, 512>);
+  return go(k_tri_lev<S, TIO, M, 1024>);
+}
+
+template <class S, typename TIO>
+int launch_lev_scheme(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
+  int st = launch_lev_m<S, TIO, 8>(a, la, s);  // M = 16 (half the checkpoints) only where M = 8 does not fit a 64-band slice
+  if (st == CRT_ERR_UNSUPPORTED) st = launch_lev_m<S, TIO, 16>(a, la, s);
+  return st;
+}
+
 template <class S, typename TIO, bool FUSED>
 int launch_cfg(const SolveArgs& a, hipStream_t s, int M, int T, int nthr) {
   if (M == 8 && T == 4) return launch_mt<S, TIO, 8, 4, FUSED>(a, s, nthr);

@@ -922,7 +922,173 @@ int launch_zqpa_int_io(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
   return prof ? launch_zqpa_int_m<TIO, 8, true, true>(a, ia, s, nthr) : launch_zqpa_int_m<TIO, 8, false, false>(a, ia, s, nthr);
 }
 
+// ------------------------------------------------------------------------------------------
+// Level-subset outputs (LevArgs, crt_internal.hpp): the zq sweep on the computational grid as in k_zqpa_int, on one band slice.  A
+// selected caller level j interpolates between the interfaces ka - 1 and ka (ka = kidx[j]) with k_zqpa_interp's index arithmetic, which
+// reads the grid rows ka - 1, max(ka - 1, 1) - 1 and min(ka, Mg - 1) (clamps SWd[0] := SWd[1], SWu[Mg] := SWu[Mg-1] of :310 / :335).
+// Before the sweep the workgroup marks those rows (at most 3 nsel of the Mg) and gives each a slot; the back substitution keeps the
+// lane's (SWd[k+1], SWu[k]) of a marked row k in its slot, and the interpolation after the sweep applies k_zqpa_interp's expressions
+// to them: the same bits as the profile path.  The slots take LDS in proportion to the marked rows: with many levels selected, the band
+// slices narrow.
+template <typename TIO, int M, int MAXT>
+__global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4))) void k_zqpa_lev(SolveArgs g, LevArgs la, int nzo, int per,
+                                                                                           int off_map, int off_ck, int off_val) {
+  typedef TriZq S;
+  extern __shared__ double lds[];
+  const int Mg = g.nz, nb = g.nb, nsel = la.nsel;
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int c = blockIdx.x;
+  {
+    const double* src = g.ws + (long long)c * g.reclen;
+    for (int i = tid; i < g.reclen; i += nthr) lds[i] = src[i];
+  }
+  int* slot = reinterpret_cast<int*>(lds + off_map);  // [Mg]: slot of grid row k, or -1; slot[Mg]: lowest marked row
+  for (int k = tid; k < Mg; k += nthr) slot[k] = -1;
+  __syncthreads();
+  const double* rec = lds;
+  const double* ekl = rec + REC_HDR + nzo;
+  const double* kidx = ekl + nzo;
+  const double* wgt = kidx + nzo;
+  auto ka_of = [&](int j) { return min(max((int)kidx[j], 1), Mg); };  // (1 <= kidx <= Mg for every record K0 writes)
+  if (tid < nsel) {  // (distinct lanes may mark the same row: they all store -2)
+    const int ka = ka_of(la.lev[tid]);
+    slot[ka - 1] = -2;
+    slot[max(ka - 1, 1) - 1] = -2;
+    slot[min(ka, Mg - 1)] = -2;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int n = 0, lowest = Mg;
+    for (int k = Mg - 1; k >= 0; --k)
+      if (slot[k] == -2) lowest = k;
+    for (int k = 0; k < Mg; ++k)
+      if (slot[k] == -2) slot[k] = n++;
+    slot[Mg] = lowest;
+  }
+  __syncthreads();
+  const int b = blockIdx.y * per + tid;
+  if (tid >= per || b >= nb) return;  // (no barrier below)
+  double* val = lds + off_val + tid;  // [nslot][2][nthr]
+  double* ck = lds + off_ck + tid;    // [nck][2][nthr]
+  S st;
+  st.template init<TIO>(rec, g, c, b);
+  const double bc = st.band_const();  // I_dr0
+  const int K = S::rows(Mg);
+  const int klow = slot[Mg];  // the back substitution stops below the lowest row a selected level reads
+  static_assert(M % S::RENORM == 0, "checkpoints must fall on re-seeding levels");
+  typename S::St fs;
+  st.first(rec, Mg, fs);
+  {
+    double e, f;
+    st.pair(fs, e, f);
+    ck[0] = e;
+    ck[nthr] = f;
+  }
+  tri_forward<S, M>(st, rec, Mg, fs, K - 1, [&](int level, const typename S::St& cs) {
+    const int sidx = level / M;
+    double e, f;
+    st.pair(cs, e, f);
+    ck[(2 * sidx) * nthr] = e;
+    ck[(2 * sidx + 1) * nthr] = f;
+  });
+  for (int seg = (K - 1) / M; seg >= 0 && seg * M + M - 1 >= klow; --seg) {
+    const int k0 = seg * M;
+    const int kend = min(k0 + M - 1, K - 1);
+    double be[M], bf[M];
+    be[0] = ck[(2 * seg) * nthr];
+    bf[0] = ck[(2 * seg + 1) * nthr];
+    typename S::St rs;
+    st.seed(rs, be[0], bf[0]);
+#pragma unroll
+    for (int i = 1; i < M; ++i) {
+      be[i] = be[i - 1];
+      bf[i] = bf[i - 1];
+      if (k0 + i <= kend) tri_step(st, k0 + i - 1, rec, Mg, rs, be[i], bf[i]);
+    }
+#pragma unroll
+    for (int i = M - 1; i >= 0; --i) {
+      const int k = k0 + i;
+      if (k <= kend) {
+        double o[S::NST];
+        if (k == K - 1) {
+          st.top(rec, Mg, be[i], bf[i], o);  // boundary only, no row of the grid's fluxes
+        } else {
+          st.back(k, rec, Mg, be[i], bf[i], o);
+          const int sl = slot[k];
+          if (sl >= 0) {
+            val[(2 * sl) * nthr] = o[0];      // SWd[k+1]
+            val[(2 * sl + 1) * nthr] = o[1];  // SWu[k]
+          }
+        }
+      }
+    }
+  }
+  const double invmu = rec[S_INVMU];
+  for (int r = 0; r < nsel; ++r) {
+    const int j = la.lev[r];
+    const int ka = ka_of(j), kb = ka - 1;
+    const double w = wgt[j];
+    const double da = val[(2 * slot[max(ka, 1) - 1]) * nthr], db = val[(2 * slot[max(kb, 1) - 1]) * nthr];
+    const double ua = val[(2 * slot[min(ka, Mg - 1)] + 1) * nthr], ub = val[(2 * slot[min(kb, Mg - 1)] + 1) * nthr];
+    const double dn = da + (db - da) * w;  // :360
+    const double up = ua + (ub - ua) * w;  // :361
+    const double idr = bc * ekl[j];        // :354-355
+    const double v[4] = {idr, dn, up, idr * invmu + 2 * up + 2 * dn};  // :412
+    const long long oo = ((long long)c * nsel + r) * nb + b;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (la.o[q]) __builtin_nontemporal_store((TIO)v[q], outp<TIO>(la.o[q]) + oo);
+  }
+}
+
+// LDS of k_zqpa_lev in doubles: record | row slots [Mg + 1] (int) | checkpoints [Mg / M + 1][2][nthr] | kept rows [nslot][2][nthr]
+struct ZqPaLevLds {
+  int off_map, off_ck, off_val;
+  size_t bytes;
+};
+inline ZqPaLevLds zqpa_lev_lds(const SolveArgs& a, int M, int nthr, int nsel) {
+  const int Mg = zqpa_M(a.nz);
+  const int nslot = min(Mg, 3 * nsel);
+  ZqPaLevLds L;
+  L.off_map = (a.reclen + 1) & ~1;
+  L.off_ck = L.off_map + (((Mg + 2) / 2 + 1) & ~1);
+  L.off_val = L.off_ck + 2 * (Mg / M + 1) * nthr;
+  L.bytes = ((size_t)L.off_val + 2 * (size_t)nslot * nthr) * sizeof(double);
+  return L;
+}
+
+template <typename TIO>
+int launch_zqpa_lev_io(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
+  constexpr int M = 8;
+  int wmax = 1024;  // widest slice whose checkpoints and kept rows fit
+  while (wmax >= 64 && zqpa_lev_lds(a, M, wmax, la.nsel).bytes > MAX_WG_LDS) wmax >>= 1;
+  if (wmax < 64) return CRT_ERR_UNSUPPORTED;
+  const LevSlices ls = lev_slices(a.nb, wmax);
+  if (ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
+  const ZqPaLevLds L = zqpa_lev_lds(a, M, ls.nthr, la.nsel);
+  const int Mg = zqpa_M(a.nz);
+  SolveArgs g = a;  // computational-grid solve: nz := Mg (the record keeps the caller's nz: passed separately)
+  g.nz = Mg;
+  for (int i = 0; i < 7; ++i) g.o[i] = nullptr;
+  auto go = [&](auto kern) {
+    if (L.bytes > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.bytes) != hipSuccess)
+      return (int)CRT_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(a.ncol, ls.nslice), dim3(ls.nthr), L.bytes, s, g, la, a.nz, ls.per, L.off_map, L.off_ck, L.off_val);
+    if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+    note_kernel("k_zqpa_lev<zq_pa>%s M=%d grid=%d nsel=%d slice=%d", sizeof(TIO) == 8 ? "" : " f32", M, Mg, la.nsel, ls.per);  // (only a launch that succeeded is reported)
+    return (int)CRT_OK;
+  };
+  if (ls.nthr <= 256) return go(k_zqpa_lev<TIO, M, 256>);
+  if (ls.nthr <= 512) return go(k_zqpa_lev<TIO, M, 512>);
+  return go(k_zqpa_lev<TIO, M, 1024>);
+}
+
 }  // namespace
+
+int launch_zqpa_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
+  return a.f32 ? launch_zqpa_lev_io<float>(a, la, s) : launch_zqpa_lev_io<double>(a, la, s);
+}
 
 int launch_zqpa_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
   if (a.nb > 1024) return CRT_ERR_UNSUPPORTED;

@@ -328,6 +328,34 @@ int crt_hip_integrated_f32(int scheme, const crt_columns* cols, const crt_bands_
                            void* workspace, size_t workspace_bytes, crt_stream_t stream);
 
 /*
+ * Level-subset solve: the SPECTRA of the four contract profiles at a few chosen levels, without writing the other levels.  These are
+ * the per-band terms of the reference's compare_ebal (crt1d/diagnostics.py:510-522) before their band integral -- top-of-canopy
+ * reflectance I_df_u[nz-1], ground-level transmission I_dr[0] + I_df_d[0], spectra at sensor heights -- and the rows
+ * levels[r] of the I_dr, I_df_d, I_df_u, F arrays of the solver return dicts (_solve_2s.py:158-163, _solve_4s.py:293,
+ * _solve_n79.py:157-164, _solve_zq.py:221-229, _solve_bl.py:93, _solve_g77.py:127-135, _solve_bf.py:144-153, _solve_zq_pa.py:413-418).
+ *
+ *  - levels: HOST array of nsel level indices, 1 <= nsel <= CRT_MAX_LEVEL_SELECT, strictly ascending, each in [0, nz).  Copied by value
+ *    into the kernel arguments: the caller's array may go away once the call returns, and the launch is capturable into a hipGraph.
+ *  - out: I_dr, I_df_d, I_df_u, F, each [ncol][nsel][nb] (bands contiguous; row r = level levels[r]) or NULL when not wanted; at least
+ *    one of the four is given.  x0, x1, x2 must be NULL (the scheme-specific extras are not served).
+ *  - every row is BITWISE the row levels[r] that crt_hip_solve_f64 / _f32 writes for the same inputs (same scheme objects, same
+ *    arithmetic), for all eight schemes; the f32 entry writes those rows rounded once to float, also where the f32 profile path of
+ *    zq_pa is CRT_ERR_UNSUPPORTED.
+ *  - workspace and opts as for crt_hip_solve_f64 (crt_hip_workspace_bytes_nb; CRT_FLAG_SKIP_PRECOMPUTE, CRT_FLAG_PRECOMPUTE_ONLY keep
+ *    their meaning; tune is validated, its keys do not apply).
+ *  - CRT_ERR_BAD_ARG before any launch for null, unsorted, duplicate or out-of-range levels, nsel outside 1..CRT_MAX_LEVEL_SELECT, all
+ *    four outputs NULL or an extra non-NULL.  Any nb.  Shape limit: the K0 record and the checkpoints of the tridiagonal sweep (zq_pa:
+ *    on its grid of min(100, nz) rows, plus the grid rows the selected levels read) must fit in LDS for a 64-band slice -- n79 serves
+ *    nz <= 1360, zq nz <= 2271, zq_pa nz <= 1487 (64 levels) to 4495 (two levels) -- else CRT_ERR_UNSUPPORTED with nothing written.
+ *    The closed forms (2s, 4s, bl, g77, bf) serve every nz.
+ */
+#define CRT_MAX_LEVEL_SELECT 64
+int crt_hip_levels_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
+                       int32_t nsel, const crt_outputs* out, void* workspace, size_t workspace_bytes, crt_stream_t stream);
+int crt_hip_levels_f32(int scheme, const crt_columns* cols, const crt_bands_f32* bands, const crt_options* opts, const int32_t* levels,
+                       int32_t nsel, const crt_outputs_f32* out, void* workspace, size_t workspace_bytes, crt_stream_t stream);
+
+/*
  * diagnostics.band's reduction for ANY variable with a trailing wavelength axis (diagnostics.py:81, `(da * w).sum(dim="wl")`):
  * out[row][g] = sum_b band_w[g][b] X[row][b], X = [nrow][nb], band_w = [ngroup <= 4][nb], out = [nrow][ngroup].  Used by
  * crt1d_amd.diagnostics.band for the variables of a single Model's dataset (incl. the schemes' own aI_*_scheme outputs); the batched
