@@ -61,6 +61,19 @@ class CrtBands(ctypes.Structure):
     ]
 
 
+class CrtSunSeries(ctypes.Structure):
+    """crt_sun_series: nt sun states (psi, g_at_psi, I_dr0, I_df0) per column for crt_hip_integrated_series_f64."""
+
+    _fields_ = [
+        ("nt", ctypes.c_int32),
+        ("psi", _vp),
+        ("g_at_psi", _vp),
+        ("col_stride", ctypes.c_int64),
+        ("I_dr0", _vp),
+        ("I_df0", _vp),
+    ]
+
+
 NTUNE = 16
 
 # crt_options.tune: keys (enum crt_tune_key; what each one selects is documented there) and the named values of some of them.
@@ -165,6 +178,8 @@ EXPORTS = [
     "crt_hip_absorb_bandsum2_f32",
     "crt_hip_integrated_f32",
     "crt_hip_integrated2_f32",
+    "crt_hip_series_workspace_bytes",
+    "crt_hip_integrated_series_f64",
     "crt_hip_levels_f64",
     "crt_hip_levels_f32",
     "crt_hip_absorb_f32",
@@ -269,6 +284,13 @@ def load():
             ctypes.c_int, ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), ctypes.POINTER(CrtOptions), ctypes.POINTER(ctypes.c_int32),
             ctypes.c_int32, ctypes.POINTER(CrtOutputs), _vp, ctypes.c_size_t, _vp,
         ]
+    lib.crt_hip_series_workspace_bytes.restype = ctypes.c_size_t
+    lib.crt_hip_series_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+    lib.crt_hip_integrated_series_f64.restype = ctypes.c_int
+    lib.crt_hip_integrated_series_f64.argtypes = [
+        ctypes.c_int, ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), ctypes.POINTER(CrtSunSeries), ctypes.POINTER(CrtOptions), _vp,
+        ctypes.c_int32, ctypes.POINTER(CrtBandsumOut), _vp, ctypes.c_size_t, _vp,
+    ]
     lib.crt_hip_bandsum_finish_f64.restype = ctypes.c_int
     lib.crt_hip_bandsum_finish_f64.argtypes = [ctypes.POINTER(CrtColumns), ctypes.c_int32, ctypes.POINTER(CrtBandsumOut), _vp]
     lib.crt_hip_band_reduce_f64.restype = ctypes.c_int

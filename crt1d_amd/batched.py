@@ -697,6 +697,168 @@ def solve_integrated(scheme, cols: Columns, bands: Bands, band_w, **kw):
         return IntegratedPlan(scheme, cols, bands, band_w, **kw)()
 
 
+@dataclass
+class SunSeries:
+    """``nt`` sun states per column on one canopy (``crt_sun_series``): ``psi (ncol, nt)`` solar zenith angles in radians and the
+    incoming spectra ``I_dr0``, ``I_df0`` ``(ncol, nt, nb)`` -- or ``(nt, nb)`` / ``(1, nt, nb)`` to share one series of spectra over all
+    columns.  ``g_at_psi (ncol, nt)`` = G(psi) for columns of kind G_TABLE.  What the reference passes step by step through
+    ``update_p(psi=...)`` and ``I_dr0_all`` / ``I_df0_all``."""
+
+    psi: torch.Tensor
+    I_dr0: torch.Tensor
+    I_df0: torch.Tensor
+    g_at_psi: Optional[torch.Tensor] = None
+
+    def __post_init__(self):
+        self.psi = _f64(self.psi, "psi")
+        if self.psi.ndim != 2 or self.psi.shape[1] < 1:
+            raise ValueError("psi must be (ncol, nt) with nt >= 1")
+        if self.g_at_psi is not None:
+            self.g_at_psi = _f64(self.g_at_psi, "g_at_psi")
+            if self.g_at_psi.shape != self.psi.shape:
+                raise ValueError("g_at_psi must be (ncol, nt)")
+        shape = None
+        for name in ("I_dr0", "I_df0"):
+            v = _f64(getattr(self, name), name)
+            if v.ndim == 2:
+                v = v[None]
+            if v.ndim != 3 or v.shape[1] != self.nt or v.shape[0] not in (1, self.ncol):
+                raise ValueError(f"{name} must be (ncol, nt, nb) or (nt, nb) with ncol = {self.ncol}, nt = {self.nt}")
+            if shape is None:
+                shape = v.shape
+            elif v.shape != shape:
+                raise ValueError("I_dr0 and I_df0 must have the same shape")
+            setattr(self, name, v)
+        for name in ("I_dr0", "I_df0", "g_at_psi"):
+            v = getattr(self, name)
+            if v is not None and v.device != self.psi.device:
+                raise ValueError(f"{name} lives on {v.device} but psi on {self.psi.device}")
+
+    @property
+    def ncol(self):
+        return self.psi.shape[0]
+
+    @property
+    def nt(self):
+        return self.psi.shape[1]
+
+    @property
+    def nb(self):
+        return self.I_dr0.shape[2]
+
+    @property
+    def col_stride(self):
+        return 0 if (self.I_dr0.shape[0] == 1 and self.ncol != 1) else self.nt * self.nb
+
+    def slice(self, lo, hi):
+        """Columns [lo, hi) as a view."""
+        g = lambda t: t if t.shape[0] == 1 else t[lo:hi]  # noqa: E731
+        return SunSeries(self.psi[lo:hi], g(self.I_dr0), g(self.I_df0), None if self.g_at_psi is None else self.g_at_psi[lo:hi])
+
+    def c_struct(self):
+        return _lib.CrtSunSeries(self.nt, self.psi.data_ptr(), None if self.g_at_psi is None else self.g_at_psi.data_ptr(), self.col_stride,
+                                 self.I_dr0.data_ptr(), self.I_df0.data_ptr())
+
+    @classmethod
+    def from_host(cls, d, device="cuda"):
+        """From a dict of NumPy arrays (:func:`crt1d_amd.synth.make_sun_series`)."""
+        t = lambda k: None if d.get(k) is None else torch.as_tensor(d[k]).to(device)  # noqa: E731
+        return cls(t("psi"), t("I_dr0"), t("I_df0"), t("g_at_psi"))
+
+
+def series_workspace_bytes(scheme, ncol, nz, nb, nt):
+    """Device workspace of a series call: the canopy records of the columns and the sun records of every (column, t)."""
+    return int(_lib.load().crt_hip_series_workspace_bytes(_lib.SCHEME_IDS[scheme], ncol, nz, nb, nt))
+
+
+def series_shapes(ncol, nt, nz, ngroup, profiles=False):
+    """Shapes of the series outputs: :func:`bandsum_shapes` with ``nt`` inserted at axis 1."""
+    return {k: (sh[0], nt) + tuple(sh[1:]) for k, sh in bandsum_shapes(ncol, nz, ngroup, profiles).items()}
+
+
+class IntegratedSeriesPlan:
+    """The outputs of :class:`IntegratedPlan` for ``sun.nt`` sun states of every column in one call
+    (``crt_hip_integrated_series_f64``): ``out[k][:, t]`` is bitwise what ``IntegratedPlan`` returns with ``psi = sun.psi[:, t]`` and
+    the incoming spectra of step ``t``.  The canopy-only part of the column precompute runs once per column, the sun-dependent part
+    once per (column, t).  ``cols.psi``, ``cols.g_at_psi`` and ``bands.I_dr0`` / ``I_df0`` are not read (``bands`` may be built with
+    ``None`` for the two).  float64 only."""
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, sun: SunSeries, band_w, *, mu_s=0.501, tau_d_method="quad", workspace=None,
+                 out=None, profiles=False):
+        if scheme not in _lib.SCHEME_IDS:
+            raise ValueError(f"scheme {scheme!r} has no integrated kernel")
+        if tau_d_method not in _lib.TAU_D_METHODS:
+            raise ValueError("invalid `method`. Valid options are 'quad' and '9sky'.")
+        if not isinstance(sun, SunSeries):
+            raise TypeError("sun must be a SunSeries")
+        self.lib = _lib.load()
+        self.scheme, self.cols, self.bands, self.sun = scheme, cols, bands, sun
+        band_w = _f64(band_w, "band_w")
+        if band_w.ndim == 1:
+            band_w = band_w[None, :]
+        if band_w.shape[1] != bands.nb or not 1 <= band_w.shape[0] <= 4:
+            raise ValueError("band_w must be (ngroup <= 4, nb)")
+        self.band_w = band_w
+        ncol, nz, ng, dev = cols.ncol, cols.nz, band_w.shape[0], cols.device
+        if bands.dtype != torch.float64:
+            raise TypeError("the sun-angle series has no f32 storage form: bands must be float64")
+        if sun.ncol != ncol or sun.nb != bands.nb:
+            raise ValueError(f"sun must have ncol = {ncol} rows and nb = {bands.nb} bands, got {sun.ncol} and {sun.nb}")
+        if sun.psi.device != dev:
+            raise ValueError(f"sun lives on {sun.psi.device} but the columns on {dev}")
+        if (cols.g_table is not None or cols.g_at_psi is not None) and sun.g_at_psi is None and bool((cols.g_kind == 6).any()):
+            raise ValueError("columns with g_kind = G_TABLE need sun.g_at_psi (ncol, nt)")
+        if cols.g_table is None and bool((cols.g_kind == 6).any()):
+            raise ValueError("columns with g_kind = G_TABLE need g_table")
+        shapes = series_shapes(ncol, sun.nt, nz, ng, profiles)
+        if out is None:
+            out = {k: torch.empty(sh, dtype=torch.float64, device=dev) for k, sh in shapes.items()}
+        else:
+            for k, sh in shapes.items():
+                _check_profile(out[k], f"out[{k!r}]", sh, dev)
+        self.out = out
+        self.profiles = profiles
+        self._out = _bandsum_out_struct(out, profiles)
+        _check_band_device(bands, dev)
+        if band_w.device != dev:
+            raise ValueError(f"band_w lives on {band_w.device} but the columns on {dev}")
+        if bands.leaf_r is None or bands.leaf_t is None:
+            raise ValueError("bands needs leaf_r and leaf_t")
+        if scheme == "2s" and cols.mla is None:
+            raise ValueError("solve_2s needs `mla`")
+        if scheme != "bl" and bands.soil_r is None:
+            raise ValueError(f"solve_{scheme} needs `soil_r`")
+        need = series_workspace_bytes(scheme, ncol, nz, bands.nb, sun.nt)
+        self.workspace = _check_workspace(workspace, need, dev)
+        self._c, self._b, self._s = cols.c_struct(), bands.c_struct(ncol), sun.c_struct()
+        if cols.g_table is None:
+            self._c.g_table = None
+        self._o = _lib.CrtOptions(float(mu_s), _lib.TAU_D_METHODS[tau_d_method], 0)
+        self._entry = "crt_hip_integrated_series_f64"
+        self._fn = self.lib.crt_hip_integrated_series_f64
+
+    def last_kernel(self):
+        """K0 forms and series kernel of this thread's most recent call (``crt_hip_last_kernel``)."""
+        return self.lib.crt_hip_last_kernel().decode()
+
+    def __call__(self, stream=None, *, flags=0):
+        dev = self.cols.device
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        self._o.flags = int(flags)
+        with torch.cuda.device(dev):
+            st = self._fn(
+                _lib.SCHEME_IDS[self.scheme], ctypes.byref(self._c), ctypes.byref(self._b), ctypes.byref(self._s), ctypes.byref(self._o),
+                self.band_w.data_ptr(), self.band_w.shape[0], ctypes.byref(self._out), self.workspace.data_ptr(),
+                self.workspace.numel() * self.workspace.element_size(), s.cuda_stream)
+        _lib.check(st, self._entry)
+        return self.out
+
+
+def solve_integrated_series(scheme, cols: Columns, bands: Bands, sun: SunSeries, band_w, **kw):
+    with torch.cuda.device(cols.device):
+        return IntegratedSeriesPlan(scheme, cols, bands, sun, band_w, **kw)()
+
+
 LEVEL_KEYS = ("I_dr", "I_df_d", "I_df_u", "F")  # the profiles a level-subset solve serves, in crt_outputs slot order
 
 

@@ -1267,6 +1267,19 @@ size_t crt_hip_workspace_bytes_nb(int scheme, int32_t ncol, int32_t nz, int32_t 
   return n;
 }
 
+size_t crt_hip_series_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nt) {
+  // Layout: canopy records [ncol][can_len] from the start, the sun records [ncol * nt][sun_len] right behind them.  The size is at least
+  // the per-step workspace (so that one buffer serves both entries): where that is larger than the canopy records (zq_pa's scratch share
+  // for its grid fluxes, which no integrated kernel uses), the difference is unused padding at the end.
+  const size_t base = crt_hip_workspace_bytes_nb(scheme, ncol, nz, nb);
+  if (base == 0 || nt < 1) return 0;
+  const size_t can = (size_t)ncol * (size_t)can_len(scheme, nz) * sizeof(double);
+  const size_t per = (size_t)sun_len(scheme, nz) * sizeof(double);
+  const size_t nsun = (size_t)ncol * (size_t)nt;
+  if (nsun > (SIZE_MAX - (base > can ? base : can)) / per) return 0;
+  return (base > can ? base : can) + nsun * per;
+}
+
 int crt_hip_quad_nodes(double mu_s, double* psi_nodes) {
   if (!psi_nodes || !(mu_s > 0.0 && mu_s < 1.0)) return CRT_ERR_BAD_ARG;
   host_quad_nodes(mu_s, psi_nodes);
@@ -1275,13 +1288,20 @@ int crt_hip_quad_nodes(double mu_s, double* psi_nodes) {
 
 static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts,
                       const crt_outputs* out, void* workspace, size_t workspace_bytes, crt_stream_t stream, int f32,
-                      const IntArgs* integ = nullptr, const LevArgs* lev = nullptr) {
+                      const IntArgs* integ = nullptr, const LevArgs* lev = nullptr, const crt_sun_series* ser = nullptr) {
   if (!scheme_ok(scheme) || !cols || !bands || !out) return CRT_ERR_BAD_ARG;
   const int ncol = cols->ncol, nz = cols->nz, nb = bands->nb;
   if (ncol <= 0 || nz <= 0 || nb <= 0) return CRT_ERR_BAD_ARG;
-  if (!cols->psi || !cols->lai || !cols->g_kind) return CRT_ERR_BAD_ARG;
+  if (!cols->lai || !cols->g_kind) return CRT_ERR_BAD_ARG;
   if (scheme == CRT_SCHEME_2S && !cols->mla) return CRT_ERR_BAD_ARG;
-  if (!bands->I_dr0 || !bands->I_df0 || !bands->leaf_r || !bands->leaf_t) return CRT_ERR_BAD_ARG;
+  if (!bands->leaf_r || !bands->leaf_t) return CRT_ERR_BAD_ARG;
+  if (ser) {  // sun-angle series (integrated outputs only): the sun and the incoming spectra come from `ser`, not from cols / bands
+    if (!integ || !ser->psi || !ser->I_dr0 || !ser->I_df0 || ser->nt < 1) return CRT_ERR_BAD_ARG;
+    if (ser->col_stride != 0 && ser->col_stride < (int64_t)ser->nt * nb) return CRT_ERR_BAD_ARG;
+    if (cols->g_table && !ser->g_at_psi) return CRT_ERR_BAD_ARG;
+  } else if (!cols->psi || !bands->I_dr0 || !bands->I_df0) {
+    return CRT_ERR_BAD_ARG;
+  }
   if (scheme != CRT_SCHEME_BL && !bands->soil_r) return CRT_ERR_BAD_ARG;
   if (bands->col_stride != 0 && bands->col_stride < nb) return CRT_ERR_BAD_ARG;
   if (!integ && !lev && (!out->I_dr || !out->I_df_d || !out->I_df_u || !out->F)) return CRT_ERR_BAD_ARG;
@@ -1325,8 +1345,10 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
   }
   if (scheme == CRT_SCHEME_4S && !(mu_s > 0.0 && mu_s < 1.0)) return CRT_ERR_BAD_ARG;
   if (method != CRT_TAU_D_QUAD && method != CRT_TAU_D_9SKY) return CRT_ERR_BAD_ARG;  // ValueError, common.py:78
-  const size_t need = crt_hip_workspace_bytes_nb(scheme, ncol, nz, nb);
+  const size_t need = ser ? crt_hip_series_workspace_bytes(scheme, ncol, nz, nb, ser->nt) : crt_hip_workspace_bytes_nb(scheme, ncol, nz, nb);
+  if (need == 0) return CRT_ERR_UNSUPPORTED;  // (series: a size beyond size_t)
   if (!workspace || workspace_bytes < need) return CRT_ERR_WORKSPACE;
+  if (ser && nb > 1024) return CRT_ERR_UNSUPPORTED;  // as the per-step entry, but before K0 has written anything
 
   hipStream_t s = static_cast<hipStream_t>(stream);
   ColArgs ca;
@@ -1343,6 +1365,49 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
   ca.g_at_psi = cols->g_at_psi;
   ca.g_table = cols->g_table;
   ca.ws = static_cast<double*>(workspace);
+  if (ser) {
+    // workspace: canopy records [ncol][can_len], then sun records [ncol * nt][sun_len] (SeriesArgs, crt_internal.hpp)
+    double* const sunrec = static_cast<double*>(workspace) + (size_t)ncol * can_len(scheme, nz);
+    ca.psi = ser->psi;
+    ca.g_at_psi = ser->g_at_psi;
+    if (!(flags & CRT_FLAG_SKIP_PRECOMPUTE)) {
+      const int st = launch_colpre_series(ca, ser->nt, sunrec, s);
+      if (st != CRT_OK) return st;
+    } else {
+      const int st = init_quadrature(s);
+      if (st != CRT_OK) return st;
+    }
+    if (flags & CRT_FLAG_PRECOMPUTE_ONLY) {
+      note_kernel("k_colpre<canopy> + k_colsun nt=%d", ser->nt);
+      return CRT_OK;
+    }
+    SolveArgs sa = {};
+    sa.ncol = ncol;
+    sa.nb = nb;
+    sa.nz = nz;
+    sa.reclen = rec_len(scheme, nz);
+    sa.col_stride = bands->col_stride;
+    sa.ws = static_cast<const double*>(workspace);
+    sa.leaf_r = bands->leaf_r;
+    sa.leaf_t = bands->leaf_t;
+    sa.soil_r = bands->soil_r;
+    sa.mu_s = mu_s;
+    std::memcpy(&sa.tune, tune, sizeof sa.tune);
+    SeriesArgs sr;
+    sr.nt = ser->nt;
+    sr.scheme = scheme;
+    sr.nz = nz;
+    sr.canlen = can_len(scheme, nz);
+    sr.sunlen = sun_len(scheme, nz);
+    sr.can = sa.ws;
+    sr.sun = sunrec;
+    sr.col_stride = ser->col_stride;
+    sr.I_dr0 = ser->I_dr0;
+    sr.I_df0 = ser->I_df0;
+    if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_int(sa, *integ, s, &sr);
+    return (scheme == CRT_SCHEME_N79 || scheme == CRT_SCHEME_ZQ) ? launch_tridiag_int(scheme, sa, *integ, s, &sr)
+                                                                   : launch_closed_int(scheme, sa, *integ, s, &sr);
+  }
   // 2s profiles: the closed-form launcher forms the records inside k_pipe when it picks that kernel (one launch per call), and runs
   // k_colpre in front of any other kernel.  SKIP_PRECOMPUTE / PRECOMPUTE_ONLY and CRT_TUNE_K0_SEPARATE keep k_colpre as a kernel of its own.
   const bool k0_in_solve = scheme == CRT_SCHEME_2S && !integ && !lev && !(flags & (CRT_FLAG_SKIP_PRECOMPUTE | CRT_FLAG_PRECOMPUTE_ONLY)) &&
@@ -1474,7 +1539,8 @@ int crt_hip_absorb_bandsum_f32(const crt_columns* cols, const crt_bands_f32* ban
 
 // f32: crt_bands_f32 has the layout of crt_bands (crt_hip_solve_f32); the fused kernels read the spectra as TIO = float
 static int integrated_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const double* band_w,
-                           int32_t ngroup, const crt_bandsum_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream, int f32) {
+                           int32_t ngroup, const crt_bandsum_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream, int f32,
+                           const crt_sun_series* ser = nullptr) {
   if (!band_w || !out || !out->aI || !out->aI_sl || !out->aI_sh || ngroup <= 0 || ngroup > INT_MAXG || !cols) return CRT_ERR_BAD_ARG;
   const int nopt = (out->aI_dr != nullptr) + (out->I_dr != nullptr) + (out->I_df_d != nullptr) + (out->I_df_u != nullptr) + (out->F != nullptr) +
                    (out->I_d != nullptr);
@@ -1494,7 +1560,14 @@ static int integrated_impl(int scheme, const crt_columns* cols, const crt_bands*
   ia.L_F = out->F;
   ia.L_Id = out->I_d;
   crt_outputs none = {};
-  return solve_impl(scheme, cols, bands, opts, &none, workspace, workspace_bytes, stream, f32, &ia);
+  return solve_impl(scheme, cols, bands, opts, &none, workspace, workspace_bytes, stream, f32, &ia, nullptr, ser);
+}
+
+int crt_hip_integrated_series_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_sun_series* sun,
+                                  const crt_options* opts, const double* band_w, int32_t ngroup, const crt_bandsum_out* out, void* workspace,
+                                  size_t workspace_bytes, crt_stream_t stream) {
+  if (!sun) return CRT_ERR_BAD_ARG;
+  return integrated_impl(scheme, cols, bands, opts, band_w, ngroup, out, workspace, workspace_bytes, stream, 0, sun);
 }
 
 int crt_hip_integrated2_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts,

@@ -129,6 +129,44 @@ __device__ inline double tau_d_9sky(const double* k9, double L) {
   return s * (2.0 * 0.17453292519943295);  // * 2 radians(10), common.py:51
 }
 
+// zq_pa: linear interpolation of the interface fluxes back to cumulative LAI L (:357-362, np.interp semantics) on the computational
+// interfaces xi[0 .. M]: interface index (0 = ground) of the node above L, and the weight
+struct ZqPaInterp {
+  double k, w;
+};
+__device__ inline ZqPaInterp zqpa_interp(const double* xi, int M, double L) {
+  int lo = 0;
+  for (int i = 1; i < M; ++i)
+    if (xi[i] <= L) lo = i;
+  const double x0 = xi[lo], x1 = xi[lo + 1];
+  double w = (L - x0) / (x1 - x0);
+  if (L >= x1) w = 1.0;  // at or beyond the last node: np.interp returns fp[-1]
+  return {(double)(M - lo), w};
+}
+// zq_pa: beam fraction seen by computational layer li = j+1 (:164-168): f_sl[li] = exp(-K_b xi[M+1-li])
+__device__ inline double zqpa_fsl(double Kb, const double* xi, int M, int j) { return (j < M) ? fexp(-Kb * xi[M - j]) : 0.0; }
+
+// n79: 1 - td of a layer of thickness dl
+__device__ inline double n79_omtd(int method, const double* k9, const double* kq, double dl) {
+  return (method == CRT_TAU_D_9SKY) ? 1.0 - tau_d_9sky(k9, dl) : one_minus_tau_d_quad(kq, dl);  // 1 - td, :53
+}
+// n79: what follows the sun in the layer between L = lai[j] and Ln = lai[j+1]: 1 - tb, fs / (fs dlai), 1 / (fs dlai), (1 - fs) / ((1 - fs) dlai)
+struct N79Sun {
+  double omtb, fsisl, isl, fhish;
+};
+__device__ inline N79Sun n79_sun(double Kb, double L, double Ln, bool unif, double dlu) {
+  const double dl = L - Ln;                                // :40
+  const double omtb = -fexpm1(-Kb * (unif ? dlu : dl));    // 1 - tb, :45
+  const double fs = fexp(-Kb * ((L + Ln) / 2));            // :57-58
+  const double isl = 1.0 / (fs * dl);                      // :154
+  const double ish = 1.0 / ((1.0 - fs) * dl);              // :155
+  return {omtb, fs * isl, isl, (1.0 - fs) * ish};
+}
+
+// CAN (sun-angle series, SeriesArgs in crt_internal.hpp): the canopy record only -- every entry that does not follow the sun, in the
+// record's own layout with a stride of can_len, the sun's slots left as placeholders for k_colsun's records, and for zq_pa the cumulative
+// LAI of the computational interfaces behind it.  The per-step kernel is k_colpre<false>.
+template <bool CAN>
 __global__ __launch_bounds__(K0_BLOCK) void k_colpre(ColArgs a) {
   __shared__ double kq[NQT];    // K_b(psi_q) = G/cos at the tau_d nodes
   __shared__ double pmb[NQT];   // mu_bar terms, later tau_d(dlai_mean) terms
@@ -152,7 +190,7 @@ __global__ __launch_bounds__(K0_BLOCK) void k_colpre(ColArgs a) {
   const double param = in.param, gden = in.gden;
   const double* tab = in.tab;
   const double* lai = in.lai;
-  const int reclen = rec_len(a.scheme, nz);
+  const int reclen = CAN ? can_len(a.scheme, nz) : rec_len(a.scheme, nz);
   double* rec = a.ws + (long long)c * reclen;
 
   for (int q = tid; q < NQT; q += K0_BLOCK) col_node(in, q, kq[q], pmb[q]);
@@ -172,7 +210,14 @@ __global__ __launch_bounds__(K0_BLOCK) void k_colpre(ColArgs a) {
 
   // ---- header: wave 0, reductions by shuffles ----
   if (wave == 0) {
-    const ColSun sun = col_sun(a, c, in);
+    ColSun sun;
+    if constexpr (CAN) {  // placeholders in the sun's header slots (k_colsun's record supplies them): cos psi = 1, G = 0, K_b = 0
+      sun.cs = 1.0;
+      sun.G = 0.0;
+      sun.Kb = 0.0;
+    } else {
+      sun = col_sun(a, c, in);
+    }
     const ColDl dls = col_dl(in, nz, lane);
     const double Kb = sun.Kb;
     double mubar = 0.0, g1 = 0.0, g2 = 0.0, dlm = 0.0;
@@ -183,7 +228,7 @@ __global__ __launch_bounds__(K0_BLOCK) void k_colpre(ColArgs a) {
     }
     if (a.scheme == CRT_SCHEME_ZQ) dlm = fabs(wave_sum64(dls.dsum) / wave_sum64(dls.dcnt));
     if (lane == 0) {
-      const double tpsi = a.scheme == CRT_SCHEME_ZQ ? fexp(-Kb * dlm) : 0.0;  // _solve_zq.py:52
+      const double tpsi = a.scheme == CRT_SCHEME_ZQ && !CAN ? fexp(-Kb * dlm) : 0.0;  // _solve_zq.py:52
       const double cos2 = a.scheme == CRT_SCHEME_2S ? col_cos2(a.mla[c]) : 0.0;
       col_header(rec, sun, dls, mubar, g1, g2, dlm, tpsi, cos2, lai[0], nz);
       sh_kb = Kb;
@@ -204,7 +249,7 @@ __global__ __launch_bounds__(K0_BLOCK) void k_colpre(ColArgs a) {
       const double t = wave_sum64(pmb[lane] + (lane < NQT - 64 ? pmb[64 + lane] : 0.0));
       if (lane == 0) {
         rec[S_TAUI] = t;
-        rec[S_TPSI] = fexp(-Kb * Lm);
+        if constexpr (!CAN) rec[S_TPSI] = fexp(-Kb * Lm);
         // xi[i] = cumulative LAI of computational interface i from the top, built by repeated addition as np.cumsum
         // does (_solve_zq_pa.py:159): xi[0] = 0, xi[i] = xi[i-1] + Lm
         double sacc = 0.0;
@@ -213,6 +258,8 @@ __global__ __launch_bounds__(K0_BLOCK) void k_colpre(ColArgs a) {
           sacc += Lm;
           xis[i] = sacc;
         }
+        if constexpr (CAN)
+          for (int i = 0; i <= M; ++i) rec[rec_len(a.scheme, nz) + i] = xis[i];
       }
     }
     __syncthreads();
@@ -290,6 +337,34 @@ __global__ __launch_bounds__(K0_BLOCK) void k_colpre(ColArgs a) {
   double* v = rec + REC_HDR;
   for (int j = tid; j < nz; j += K0_BLOCK) {
     const double L = lai[j];
+    if constexpr (CAN) {
+      switch (a.scheme) {
+        case CRT_SCHEME_ZQ:
+          break;
+        case CRT_SCHEME_ZQ_PA: {
+          const int M = zqpa_M(nz);
+          const ZqPaInterp ip = zqpa_interp(xis, M, L);
+          v[2 * nz + j] = ip.k;
+          v[3 * nz + j] = ip.w;
+          break;
+        }
+        case CRT_SCHEME_BL:
+          v[j] = L;
+          v[2 * nz + j] = blu ? bl_td[j] : tau_d_quad(kq, L);  // _solve_bl.py:35-37
+          break;
+        case CRT_SCHEME_N79: {
+          double omtd = 1;  // 1 - td
+          if (j + 1 < nz) omtd = n79u ? sh_tdu : n79_omtd(a.tau_d_method, k9, kq, L - lai[j + 1]);
+          v[2 * nz + j] = omtd;
+          v[6 * nz + j] = 1.0 / omtd;
+          break;
+        }
+        default:
+          v[j] = L;
+          break;
+      }
+      continue;
+    }
     const double ekl = col_ekl(Kb, L);
     switch (a.scheme) {
       case CRT_SCHEME_ZQ:
@@ -297,19 +372,12 @@ __global__ __launch_bounds__(K0_BLOCK) void k_colpre(ColArgs a) {
         break;
       case CRT_SCHEME_ZQ_PA: {
         const int M = zqpa_M(nz);
-        auto xi = [&](int i) { return xis[i]; };
         // beam fraction seen by computational layer li = j+1 (:164-168): f_sl[li] = exp(-K_b xi[M+1-li])
-        v[j] = (j < M) ? fexp(-Kb * xi(M - j)) : 0.0;
+        v[j] = zqpa_fsl(Kb, xis, M, j);
         v[nz + j] = ekl;
-        // linear interpolation of the interface fluxes back to lai[j] (:357-362, np.interp semantics)
-        int lo = 0;
-        for (int i = 1; i < M; ++i)
-          if (xi(i) <= L) lo = i;
-        const double x0 = xi(lo), x1 = xi(lo + 1);
-        double w = (L - x0) / (x1 - x0);
-        if (L >= x1) w = 1.0;  // at or beyond the last node: np.interp returns fp[-1]
-        v[2 * nz + j] = (double)(M - lo);  // interface index (0 = ground) of the node above lai[j]
-        v[3 * nz + j] = w;
+        const ZqPaInterp ip = zqpa_interp(xis, M, L);
+        v[2 * nz + j] = ip.k;
+        v[3 * nz + j] = ip.w;
         break;
       }
       case CRT_SCHEME_BL:
@@ -319,34 +387,81 @@ __global__ __launch_bounds__(K0_BLOCK) void k_colpre(ColArgs a) {
         break;
       case CRT_SCHEME_N79: {
         v[j] = ekl;  // tbcum  _solve_n79.py:46
-        double omtb = 1, omtd = 1, fs = 0, isl = 0, ish = 0;  // 1 - tb, 1 - td
+        double omtd = 1;  // 1 - td
+        N79Sun ns = {1, 0, 0, 0};
         if (j + 1 < nz) {
           const double Ln = lai[j + 1];
-          const double dl = L - Ln;                                             // :40
-          if (n79u) {
-            omtb = -fexpm1(-Kb * sh_dl);
-            omtd = sh_tdu;
-          } else {
-            omtb = -fexpm1(-Kb * dl);                                            // 1 - tb, :45
-            omtd = (a.tau_d_method == CRT_TAU_D_9SKY) ? 1.0 - tau_d_9sky(k9, dl) : one_minus_tau_d_quad(kq, dl);  // 1 - td, :53
-          }
-          fs = fexp(-Kb * ((L + Ln) / 2));                                       // :57-58
-          isl = 1.0 / (fs * dl);                                                // :154
-          ish = 1.0 / ((1.0 - fs) * dl);                                        // :155
+          omtd = n79u ? sh_tdu : n79_omtd(a.tau_d_method, k9, kq, L - Ln);
+          ns = n79_sun(Kb, L, Ln, n79u, sh_dl);
         }
         // what the level loops multiply by, formed once per column (tri_schemes.hpp, TriN79): 1 - tb, 1 - td, fs / (fs dlai), 1 / (fs dlai),
         // (1 - fs) / ((1 - fs) dlai), 1 / (1 - td)
-        v[nz + j] = omtb;
+        v[nz + j] = ns.omtb;
         v[2 * nz + j] = omtd;
-        v[3 * nz + j] = fs * isl;
-        v[4 * nz + j] = isl;
-        v[5 * nz + j] = (1.0 - fs) * ish;
+        v[3 * nz + j] = ns.fsisl;
+        v[4 * nz + j] = ns.isl;
+        v[5 * nz + j] = ns.fhish;
         v[6 * nz + j] = 1.0 / omtd;  // refld = (1 - td) rho  ->  1/refld = (1/rho) * this
         break;
       }
       default:  // 2s, 4s, g77, bf
         v[j] = L;
         v[nz + j] = ekl;
+        break;
+    }
+  }
+}
+
+// The sun record of (column, t) (SeriesArgs, crt_internal.hpp): what k_colpre forms from K_b = G(psi) / cos psi, by the same functions.  One
+// wave per record.  a.psi / a.g_at_psi are [ncol][nt]; a.ws holds the canopy records (dlai statistics, zq_pa's interfaces).
+__global__ __launch_bounds__(64) void k_colsun(ColArgs a, int nt, long long nitem, double* __restrict__ sunrec) {
+  const long long v = blockIdx.x;
+  if (v >= nitem) return;
+  const int c = (int)(v / nt), lane = threadIdx.x, nz = a.nz;
+  const ColIn in = col_in(a, c);
+  const double* can = a.ws + (long long)c * can_len(a.scheme, nz);
+  const double* lai = in.lai;
+  ColArgs at = a;  // col_sun reads psi[c], g_at_psi[c]: point them at state t of this column
+  at.psi = a.psi + (v - c);
+  at.g_at_psi = a.g_at_psi ? a.g_at_psi + (v - c) : nullptr;
+  const ColSun sun = col_sun(at, c, in);
+  const double Kb = sun.Kb;
+  double* rec = sunrec + v * sun_len(a.scheme, nz);
+  if (lane == 0) {
+    double tpsi = 0.0;
+    if (a.scheme == CRT_SCHEME_ZQ) tpsi = fexp(-Kb * can[S_DLM]);                     // _solve_zq.py:52
+    if (a.scheme == CRT_SCHEME_ZQ_PA) tpsi = fexp(-Kb * (lai[0] / zqpa_M(nz)));       // _solve_zq_pa.py:174
+    rec[0] = Kb;
+    rec[1] = sun.cs;
+    rec[2] = sun.G;
+    rec[3] = 1.0 / sun.cs;
+    rec[4] = tpsi;
+    rec[5] = rec[6] = rec[7] = 0.0;
+  }
+  double* sv = rec + SUN_HDR;
+  const bool n79u = a.scheme == CRT_SCHEME_N79 && can[S_UNIF] != 0.0 && nz >= 3;
+  const double dlu = can[S_DL];
+  const double* xis = can + rec_len(a.scheme, nz);
+  for (int j = lane; j < nz; j += 64) {
+    const double L = lai[j];
+    const double ekl = col_ekl(Kb, L);
+    switch (a.scheme) {
+      case CRT_SCHEME_ZQ_PA:
+        sv[j] = zqpa_fsl(Kb, xis, zqpa_M(nz), j);
+        sv[nz + j] = ekl;
+        break;
+      case CRT_SCHEME_N79: {
+        N79Sun ns = {1, 0, 0, 0};
+        if (j + 1 < nz) ns = n79_sun(Kb, L, lai[j + 1], n79u, dlu);
+        sv[j] = ekl;
+        sv[nz + j] = ns.omtb;
+        sv[2 * nz + j] = ns.fsisl;
+        sv[3 * nz + j] = ns.isl;
+        sv[4 * nz + j] = ns.fhish;
+        break;
+      }
+      default:
+        sv[j] = ekl;
         break;
     }
   }
@@ -408,7 +523,19 @@ int launch_colpre(const ColArgs& a, hipStream_t s) {
   int st = init_quadrature(s);
   if (st != CRT_OK) return st;
   const size_t dyn = a.scheme == CRT_SCHEME_BL ? (NQT * (BL_CHUNK + 1) + 8 * BL_CHUNK + BL_UNIF_MAX_NZ) * sizeof(double) : 0;
-  hipLaunchKernelGGL(k_colpre, dim3(a.ncol), dim3(K0_BLOCK), dyn, s, a);
+  hipLaunchKernelGGL(k_colpre<false>, dim3(a.ncol), dim3(K0_BLOCK), dyn, s, a);
+  return hipGetLastError() == hipSuccess ? CRT_OK : CRT_ERR_LAUNCH;
+}
+
+int launch_colpre_series(const ColArgs& a, int nt, double* sun, hipStream_t s) {
+  int st = init_quadrature(s);
+  if (st != CRT_OK) return st;
+  const long long nitem = (long long)a.ncol * nt;
+  if (nitem > 0x7fffffffLL) return CRT_ERR_UNSUPPORTED;
+  const size_t dyn = a.scheme == CRT_SCHEME_BL ? (NQT * (BL_CHUNK + 1) + 8 * BL_CHUNK + BL_UNIF_MAX_NZ) * sizeof(double) : 0;
+  hipLaunchKernelGGL(k_colpre<true>, dim3(a.ncol), dim3(K0_BLOCK), dyn, s, a);
+  if (hipGetLastError() != hipSuccess) return CRT_ERR_LAUNCH;
+  hipLaunchKernelGGL(k_colsun, dim3((unsigned)nitem), dim3(64), 0, s, a, nt, nitem, sun);
   return hipGetLastError() == hipSuccess ? CRT_OK : CRT_ERR_LAUNCH;
 }
 

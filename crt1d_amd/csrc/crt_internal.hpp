@@ -585,8 +585,131 @@ __host__ __device__ inline size_t int_lds_doubles(int nz, int nwave, bool rows =
          (prof ? (size_t)nz * nwave * 2 * INT_MAXG + (size_t)nwave * INT_MAXG : 0);
 }
 
-int launch_closed_int(int scheme, const SolveArgs& a, const IntArgs& ia, hipStream_t s);
-int launch_tridiag_int(int scheme, const SolveArgs& a, const IntArgs& ia, hipStream_t s);
+// ------------------------------------------------------------------------------------------
+// Sun-angle series (crt_hip_integrated_series_f64): nt sun states (psi, I_dr0, I_df0) per column on one canopy.  The workspace holds
+//   canopy records  [ncol][canlen]     the K0 record with every entry that does not follow the sun (the sun's slots are placeholders),
+//                                      canlen = rec_len (+ SER_XI for zq_pa: the cumulative LAI of its computational interfaces)
+//   sun records     [ncol * nt][sunlen] SUN_HDR scalars (K_b, cos psi, G, 1 / cos psi, tau_psi) + sun_nvec(scheme) vectors of nz doubles
+// written by k_colpre<canopy> (one workgroup per column) and k_colsun (one wave per (column, t)).  A series kernel assembles the record of
+// its (column, t) in LDS from the two (series_step): the scheme objects read the record k_colpre would have written for that sun
+// state.  What the series shares is K0 alone: on the solve side a workgroup serves one sun state, as in the per-step kernels.
+constexpr int SUN_HDR = 8;
+constexpr int SER_XI = 104;
+__host__ __device__ inline int sun_nvec(int scheme) {
+  switch (scheme) {
+    case CRT_SCHEME_N79: return 5;
+    case CRT_SCHEME_ZQ_PA: return 2;
+    default: return 1;
+  }
+}
+// record vector that sun vector sv fills
+__host__ __device__ inline int sun_vec_slot(int scheme, int sv) {
+  switch (scheme) {
+    case CRT_SCHEME_N79: return sv < 2 ? sv : sv + 1;  // ekl, 1 - tb | fracsun / (fracsun dlai), 1 / (fracsun dlai), fracsha / (fracsha dlai)
+    case CRT_SCHEME_ZQ: return 0;                       // ekl
+    case CRT_SCHEME_ZQ_PA: return sv;                   // beam fraction of the computational layers, ekl
+    default: return 1;                                  // ekl (2s, 4s, bl, g77, bf)
+  }
+}
+__host__ __device__ inline int sun_len(int scheme, int nz) { return SUN_HDR + sun_nvec(scheme) * nz; }
+__host__ __device__ inline int can_len(int scheme, int nz) { return rec_len(scheme, nz) + (scheme == CRT_SCHEME_ZQ_PA ? SER_XI : 0); }
+// header slot of sun scalar i < 5
+__device__ inline int sun_hdr_slot(int i) { return i == 0 ? S_KB : i == 1 ? S_MU : i == 2 ? S_G : i == 3 ? S_INVMU : S_TPSI; }
+
+// sun vector that fills record vector `vec`, or -1 for a canopy vector (the inverse of sun_vec_slot)
+__host__ __device__ inline int rec_vec_sun(int scheme, int vec) {
+  switch (scheme) {
+    case CRT_SCHEME_N79: return vec < 2 ? vec : (vec >= 3 && vec <= 5) ? vec - 1 : -1;
+    case CRT_SCHEME_ZQ: return vec == 0 ? 0 : -1;
+    case CRT_SCHEME_ZQ_PA: return vec < 2 ? vec : -1;
+    default: return vec == 1 ? 0 : -1;
+  }
+}
+
+struct SeriesArgs {
+  int nt, scheme, nz;    // sun states per column, scheme, caller's nz
+  int canlen, sunlen;
+  const double* can;     // canopy records
+  const double* sun;     // sun records
+  long long col_stride;  // of I_dr0 / I_df0 (crt_sun_series)
+  const double* I_dr0;
+  const double* I_df0;
+};
+
+// sun-record form of K0 (colpre.hip): ca.psi / ca.g_at_psi are [ncol][nt], ca.ws the canopy records, `sun` the sun records
+int launch_colpre_series(const ColArgs& ca, int nt, double* sun, hipStream_t s);
+
+// Grid of a series kernel: one workgroup per (column, t).  The column is blockIdx.x, as in the per-step kernels; t = blockIdx.z * gridDim.y +
+// blockIdx.y, so that any nt fits (65535 x 65535 states per column).
+inline dim3 series_grid(int ncol, int nt) {
+  const unsigned gy = nt < 65535 ? (unsigned)nt : 65535u;
+  return dim3((unsigned)ncol, gy, (unsigned)((nt + (long long)gy - 1) / gy));
+}
+
+// set the dynamic-LDS attribute where needed, launch, check: the launch sequence of the series kernels
+template <class K, class... Args>
+inline int launch_series(K kern, dim3 grid, int nthr, size_t sh, hipStream_t s, Args... args) {
+  if (sh > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
+    return (int)CRT_ERR_LAUNCH;
+  hipLaunchKernelGGL(kern, grid, dim3(nthr), sh, s, args...);
+  return hipGetLastError() == hipSuccess ? (int)CRT_OK : (int)CRT_ERR_LAUNCH;
+}
+
+// One sun state of one column per workgroup.  Assembles the record of (column, t) in lds[0 .. reclen) -- each header slot and each vector
+// from the canopy record or from the sun record, in one pass -- and calls `body(a_t, ia_t)`, the per-step kernel's body, with argument
+// blocks whose spectra and output pointers are shifted so that the body's own indexing by the COLUMN reaches I_dr0 / I_df0 of (column, t)
+// and slice [column][t] of every output.  The shifts are workgroup-uniform; there is no loop over sun states, so the body keeps the
+// registers it has in the per-step kernel.
+template <class Body>
+__device__ __forceinline__ void series_step(const SolveArgs& a, const IntArgs& ia, const SeriesArgs& sr, double* lds, Body body) {
+  const int c = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x, nz = sr.nz, ng = ia.ngroup;
+  const long long tl = (long long)blockIdx.z * gridDim.y + blockIdx.y;
+  if (tl >= sr.nt) return;  // (whole workgroup, before any barrier)
+  const int t = (int)tl;
+  const long long v = (long long)c * sr.nt + t;
+  {
+    const double* can = sr.can + (long long)c * sr.canlen;
+    const double* sun = sr.sun + v * sr.sunlen;
+    if (tid < REC_HDR) {
+      int si = -1;
+#pragma unroll
+      for (int i = 0; i < 5; ++i)
+        if (sun_hdr_slot(i) == tid) si = i;
+      lds[tid] = si >= 0 ? sun[si] : can[tid];
+    }
+    const int nvec = (a.reclen - REC_HDR) / nz;
+    for (int vec = 0; vec < nvec; ++vec) {
+      const int sv = rec_vec_sun(sr.scheme, vec);
+      const double* src = sv >= 0 ? sun + SUN_HDR + sv * nz : can + REC_HDR + vec * nz;
+      for (int j = tid; j < nz; j += nthr) lds[REC_HDR + vec * nz + j] = src[j];
+    }
+  }
+  __syncthreads();
+  SolveArgs at = a;
+  IntArgs it = ia;
+  const long long din = (long long)c * sr.col_stride + (long long)t * a.nb - (long long)c * a.col_stride;
+  at.I_dr0 = sr.I_dr0 + din;
+  at.I_df0 = sr.I_df0 + din;
+  const long long sh = v - c, sa = sh * (nz - 1) * ng, sl = sh * nz * ng;
+  it.aI += sa;
+  it.aI_sl += sa;
+  it.aI_sh += sa;
+  if (it.totals) it.totals += sh * ng * 4;
+  if (it.L_dr) {
+    it.aI_dr += sa;
+    it.L_dr += sl;
+    it.L_dn += sl;
+    it.L_up += sl;
+    it.L_F += sl;
+    it.L_Id += sl;
+  }
+  body(at, it);
+}
+
+// sr: nullptr = the per-step kernel; else the series kernel of the same form (same LDS layout, same choice of M / sums)
+int launch_closed_int(int scheme, const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr = nullptr);
+int launch_tridiag_int(int scheme, const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr = nullptr);
 
 // ------------------------------------------------------------------------------------------
 // Level-subset outputs (crt_hip_levels_*): rows lev[0..nsel) of I_dr, I_df_d, I_df_u, F, each [ncol][nsel][nb] or NULL.  The levels
@@ -631,12 +754,12 @@ int launch_tri_tile_n79_f64(const SolveArgs& a, hipStream_t s, bool& done);
 int launch_tri_tile_n79_f32(const SolveArgs& a, hipStream_t s, bool& done);
 int launch_tri_tile_zq_f64(const SolveArgs& a, hipStream_t s, bool& done);
 int launch_tri_tile_zq_f32(const SolveArgs& a, hipStream_t s, bool& done);
-int launch_tri_int_n79_f64(const SolveArgs& a, const IntArgs& ia, hipStream_t s);
-int launch_tri_int_n79_f32(const SolveArgs& a, const IntArgs& ia, hipStream_t s);
-int launch_tri_int_zq_f64(const SolveArgs& a, const IntArgs& ia, hipStream_t s);
-int launch_tri_int_zq_f32(const SolveArgs& a, const IntArgs& ia, hipStream_t s);
+int launch_tri_int_n79_f64(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr);
+int launch_tri_int_n79_f32(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr);
+int launch_tri_int_zq_f64(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr);
+int launch_tri_int_zq_f32(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr);
 int launch_zqpa(const SolveArgs& a, double* scratch, hipStream_t s);
-int launch_zqpa_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s);  // integrated outputs, no scratch (tri_zqpa.hip)
+int launch_zqpa_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr = nullptr);  // integrated outputs, no scratch (tri_zqpa.hip)
 int launch_zqpa_wave(const SolveArgs& g, hipStream_t s);  // per-wave fallback of the computational-grid solve
 __host__ __device__ inline int zqpa_M(int nz) { return nz < 100 ? nz : 100; }
 void host_quad_nodes(double mu_s, double* psi_nodes);

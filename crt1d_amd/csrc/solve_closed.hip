@@ -1142,17 +1142,11 @@ int launch_io(const SolveArgs& a, hipStream_t s, int force, const ColArgs* k0) {
 // ------------------------------------------------------------------------------------------
 // k_int: integrated outputs only (see IntArgs in crt_internal.hpp).  One workgroup per column, one lane per band; the
 // level values never leave the registers, the only cross-lane traffic is ngroup shuffle reductions per level.
-template <class S, typename TIO, int MAXT, bool PROF>
-__global__ __launch_bounds__(MAXT) void k_int(SolveArgs a, IntArgs ia, int rec_dbl) {
-  extern __shared__ double lds[];
+template <class S, typename TIO, bool PROF>
+__device__ __forceinline__ void int_body(const SolveArgs& a, const IntArgs& ia, int rec_dbl, double* lds) {
   const int nb = a.nb, nz = a.nz, ng = ia.ngroup;
   const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, nwave = nthr >> 6;
   const int c = blockIdx.x;
-  {
-    const double* src = a.ws + (long long)c * a.reclen;
-    for (int i = tid; i < a.reclen; i += nthr) lds[i] = src[i];
-  }
-  __syncthreads();
   const double* rec = lds;
   const IntLds L = int_lds_carve(lds + rec_dbl, nz, nwave, PROF);
   const bool active = tid < nb;
@@ -1181,8 +1175,27 @@ __global__ __launch_bounds__(MAXT) void k_int(SolveArgs a, IntArgs ia, int rec_d
   int_finish<false, PROF>(L, ia, nwave, nz, c, rec[S_KB], rec[S_INVMU]);
 }
 
+template <class S, typename TIO, int MAXT, bool PROF>
+__global__ __launch_bounds__(MAXT) void k_int(SolveArgs a, IntArgs ia, int rec_dbl) {
+  extern __shared__ double lds[];
+  {
+    const double* src = a.ws + (long long)blockIdx.x * a.reclen;
+    for (int i = threadIdx.x; i < a.reclen; i += blockDim.x) lds[i] = src[i];
+  }
+  __syncthreads();
+  int_body<S, TIO, PROF>(a, ia, rec_dbl, lds);
+}
+
+// k_int over a sun-angle series (SeriesArgs, crt_internal.hpp): one workgroup per (column, sun state); the record is assembled from the
+// column's canopy record and the state's sun record, and k_int's body runs on it.
+template <class S, int MAXT, bool PROF>
+__global__ __launch_bounds__(MAXT) void k_int_series(SolveArgs a, IntArgs ia, SeriesArgs sr, int rec_dbl) {
+  extern __shared__ double lds[];
+  series_step(a, ia, sr, lds, [&](const SolveArgs& at, const IntArgs& it) { int_body<S, double, PROF>(at, it, rec_dbl, lds); });
+}
+
 template <class S, typename TIO>
-int launch_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
+int launch_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr) {
   if (a.nb > 1024) return CRT_ERR_UNSUPPORTED;
   const int nthr = ((a.nb + 63) / 64) * 64;
   const int rec_dbl = (a.reclen + 1) & ~1;
@@ -1191,6 +1204,18 @@ int launch_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
   const bool prof = ia.L_dr != nullptr;
   const size_t sh = (rec_dbl + int_lds_doubles(a.nz, nthr / 64, false, prof)) * sizeof(double);
   if (sh > 160 * 1024) return CRT_ERR_UNSUPPORTED;
+  if (sr) {
+    if constexpr (sizeof(TIO) == 8) {
+      auto gos = [&](auto kern) {
+        const int st = launch_series(kern, series_grid(a.ncol, sr->nt), nthr, sh, s, a, ia, *sr, rec_dbl);
+        if (st == CRT_OK) note_kernel("k_colpre<canopy> + k_colsun + k_int_series<%s>%s nt=%d", S::NAME, prof ? " + level profiles" : " wave totals", sr->nt);
+        return st;
+      };
+      if (prof) return nthr <= 256 ? gos(k_int_series<S, 256, true>) : nthr <= 512 ? gos(k_int_series<S, 512, true>) : gos(k_int_series<S, 1024, true>);
+      return nthr <= 256 ? gos(k_int_series<S, 256, false>) : nthr <= 512 ? gos(k_int_series<S, 512, false>) : gos(k_int_series<S, 1024, false>);
+    }
+    return CRT_ERR_UNSUPPORTED;  // no f32 form of the series
+  }
   auto go = [&](auto kern) {
     if (sh > 64 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
@@ -1211,8 +1236,8 @@ int launch_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
 }
 
 template <class S>
-int launch_int_io(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
-  return a.f32 ? launch_int<S, float>(a, ia, s) : launch_int<S, double>(a, ia, s);
+int launch_int_io(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr) {
+  return a.f32 ? launch_int<S, float>(a, ia, s, sr) : launch_int<S, double>(a, ia, s, sr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1295,13 +1320,13 @@ int launch_closed_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStre
   }
 }
 
-int launch_closed_int(int scheme, const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
+int launch_closed_int(int scheme, const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr) {
   switch (scheme) {
-    case CRT_SCHEME_2S: return launch_int_io<Sch2s>(a, ia, s);
-    case CRT_SCHEME_4S: return launch_int_io<Sch4s>(a, ia, s);
-    case CRT_SCHEME_BL: return launch_int_io<SchBl>(a, ia, s);
-    case CRT_SCHEME_G77: return launch_int_io<SchG77<false>>(a, ia, s);
-    case CRT_SCHEME_BF: return launch_int_io<SchG77<true>>(a, ia, s);
+    case CRT_SCHEME_2S: return launch_int_io<Sch2s>(a, ia, s, sr);
+    case CRT_SCHEME_4S: return launch_int_io<Sch4s>(a, ia, s, sr);
+    case CRT_SCHEME_BL: return launch_int_io<SchBl>(a, ia, s, sr);
+    case CRT_SCHEME_G77: return launch_int_io<SchG77<false>>(a, ia, s, sr);
+    case CRT_SCHEME_BF: return launch_int_io<SchG77<true>>(a, ia, s, sr);
     default: return CRT_ERR_BAD_ARG;
   }
 }

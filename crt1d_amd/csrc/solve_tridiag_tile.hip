@@ -19,9 +19,9 @@ void note_kernel(const char* fmt, ...) {
 }
 const char* last_kernel() { return g_last_kernel; }
 
-int launch_tridiag_int(int scheme, const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
-  if (scheme == CRT_SCHEME_N79) return a.f32 ? launch_tri_int_n79_f32(a, ia, s) : launch_tri_int_n79_f64(a, ia, s);
-  if (scheme == CRT_SCHEME_ZQ) return a.f32 ? launch_tri_int_zq_f32(a, ia, s) : launch_tri_int_zq_f64(a, ia, s);
+int launch_tridiag_int(int scheme, const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr) {
+  if (scheme == CRT_SCHEME_N79) return a.f32 ? launch_tri_int_n79_f32(a, ia, s, sr) : launch_tri_int_n79_f64(a, ia, s, sr);
+  if (scheme == CRT_SCHEME_ZQ) return a.f32 ? launch_tri_int_zq_f32(a, ia, s, sr) : launch_tri_int_zq_f64(a, ia, s, sr);
   return CRT_ERR_BAD_ARG;
 }
 

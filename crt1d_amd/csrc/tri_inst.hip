@@ -12,8 +12,8 @@ int TRI_CAT(launch_tri_tile_, TRI_TAG, TRI_TIOTAG, )(const SolveArgs& a, hipStre
   return launch_scheme<TRI_SCHEME, TRI_TIO>(a, s, done);
 }
 
-int TRI_CAT(launch_tri_int_, TRI_TAG, TRI_TIOTAG, )(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
-  return launch_int_scheme<TRI_SCHEME, TRI_TIO>(a, ia, s);
+int TRI_CAT(launch_tri_int_, TRI_TAG, TRI_TIOTAG, )(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr) {
+  return launch_int_scheme<TRI_SCHEME, TRI_TIO>(a, ia, s, sr);
 }
 
 int TRI_CAT(launch_tri_lev_, TRI_TAG, TRI_TIOTAG, )(const SolveArgs& a, const LevArgs& la, hipStream_t s) {

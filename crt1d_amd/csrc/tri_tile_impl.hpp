@@ -595,8 +595,26 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(M <= 8 ? 5
   tri_int_body<S, TIO, M, PROF>(a, ia, off_ck, off_int, lds);
 }
 
+// k_tri_int over a sun-angle series (SeriesArgs, crt_internal.hpp): one workgroup per (column, sun state); the record is assembled from the
+// column's canopy record and the state's sun record, and tri_int_body runs on it (S_UNIF is the canopy's).
+template <class S, int M, int MAXT, bool PROF>
+__global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(M <= 8 ? 5 : 3))) void k_tri_int_series(SolveArgs a, IntArgs ia, SeriesArgs sr,
+                                                                                                          int off_ck, int off_int) {
+  extern __shared__ double lds[];
+  typedef typename UniformOf<S>::type SU;
+  series_step(a, ia, sr, lds, [&](const SolveArgs& at, const IntArgs& it) {
+    if constexpr (!std::is_same<S, SU>::value) {
+      if (lds[S_UNIF] != 0.0) {
+        tri_int_body<SU, double, M, PROF>(at, it, off_ck, off_int, lds);
+        return;
+      }
+    }
+    tri_int_body<S, double, M, PROF>(at, it, off_ck, off_int, lds);
+  });
+}
+
 template <class S, typename TIO, int M>
-int launch_int_m(const SolveArgs& a, const IntArgs& ia, hipStream_t s, int nthr) {
+int launch_int_m(const SolveArgs& a, const IntArgs& ia, hipStream_t s, int nthr, const SeriesArgs* sr) {
   const int K = S::rows(a.nz);
   const int nck = (K - 1) / M + 1;
   const int off_ck = (a.reclen + 1) & ~1;
@@ -613,6 +631,18 @@ int launch_int_m(const SolveArgs& a, const IntArgs& ia, hipStream_t s, int nthr)
     note_kernel("k_tri_int<%s>%s M=%d%s", S::NAME, sizeof(TIO) == 8 ? "" : " f32", M, prof ? " + level profiles" : "");  // (only a launch that succeeded is reported)
     return (int)CRT_OK;
   };
+  if (sr) {
+    if constexpr (sizeof(TIO) == 8) {
+      auto gos = [&](auto kern) {
+        const int st = launch_series(kern, series_grid(a.ncol, sr->nt), nthr, sh, s, a, ia, *sr, off_ck, off_int);
+        if (st == CRT_OK) note_kernel("k_colpre<canopy> + k_colsun + k_tri_int_series<%s> M=%d%s nt=%d", S::NAME, M, prof ? " + level profiles" : "", sr->nt);
+        return st;
+      };
+      if (prof) return nthr <= 256 ? gos(k_tri_int_series<S, M, 256, true>) : nthr <= 512 ? gos(k_tri_int_series<S, M, 512, true>) : gos(k_tri_int_series<S, M, 1024, true>);
+      return nthr <= 256 ? gos(k_tri_int_series<S, M, 256, false>) : nthr <= 512 ? gos(k_tri_int_series<S, M, 512, false>) : gos(k_tri_int_series<S, M, 1024, false>);
+    }
+    return CRT_ERR_UNSUPPORTED;  // no f32 form of the series
+  }
   if (prof) {
     if (nthr <= 256) return go(k_tri_int<S, TIO, M, 256, true>);
     if (nthr <= 512) return go(k_tri_int<S, TIO, M, 512, true>);
@@ -624,11 +654,11 @@ int launch_int_m(const SolveArgs& a, const IntArgs& ia, hipStream_t s, int nthr)
 }
 
 template <class S, typename TIO>
-int launch_int_scheme(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
+int launch_int_scheme(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr) {
   if (a.nb > 1024) return CRT_ERR_UNSUPPORTED;
   const int nthr = ((a.nb + 63) / 64) * 64;
-  int st = launch_int_m<S, TIO, 8>(a, ia, s, nthr);  // small M: fewer registers, LDS is not the constraint here
-  if (st == CRT_ERR_UNSUPPORTED) st = launch_int_m<S, TIO, 16>(a, ia, s, nthr);
+  int st = launch_int_m<S, TIO, 8>(a, ia, s, nthr, sr);  // small M: fewer registers, LDS is not the constraint here
+  if (st == CRT_ERR_UNSUPPORTED) st = launch_int_m<S, TIO, 16>(a, ia, s, nthr, sr);
   return st;
 }
 

@@ -646,17 +646,10 @@ __host__ __device__ inline size_t zqpa_int_lds_doubles(int Mg, int nwave, bool s
 }
 
 // PROF: level profiles requested (needs SPLIT); SPLIT: separate D, U sums per row (the net-flux form has fewer, see above)
-template <typename TIO, int M, int MAXT, bool PROF, bool SPLIT>
-__global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4))) void k_zqpa_int(SolveArgs g, IntArgs ia, int nzo, int off_ck,
-                                                                                           int off_int) {
+template <typename TIO, int M, bool PROF, bool SPLIT>
+__device__ __forceinline__ void zqpa_int_body(const SolveArgs& g, const IntArgs& ia, int nzo, int off_ck, int off_int, double* lds) {
   typedef TriZq S;
   static_assert(SPLIT || !PROF, "the level profiles need the separate sums");
-  extern __shared__ double lds[];
-  {
-    const double* src = g.ws + (long long)blockIdx.x * g.reclen;
-    for (int i = threadIdx.x; i < g.reclen; i += blockDim.x) lds[i] = src[i];
-  }
-  __syncthreads();
   const int nb = g.nb, Mg = g.nz, ng = ia.ngroup;
   const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, nwave = nthr >> 6;
   const int c = blockIdx.x;
@@ -872,6 +865,28 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4))) void 
   }
 }
 
+template <typename TIO, int M, int MAXT, bool PROF, bool SPLIT>
+__global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4))) void k_zqpa_int(SolveArgs g, IntArgs ia, int nzo, int off_ck,
+                                                                                           int off_int) {
+  extern __shared__ double lds[];
+  {
+    const double* src = g.ws + (long long)blockIdx.x * g.reclen;
+    for (int i = threadIdx.x; i < g.reclen; i += blockDim.x) lds[i] = src[i];
+  }
+  __syncthreads();
+  zqpa_int_body<TIO, M, PROF, SPLIT>(g, ia, nzo, off_ck, off_int, lds);
+}
+
+// k_zqpa_int over a sun-angle series (SeriesArgs, crt_internal.hpp): one workgroup per (column, sun state); the record is assembled from the
+// column's canopy record (interpolation index and weight, tau_i) and the state's sun record, and zqpa_int_body runs on it.
+template <int M, int MAXT, bool PROF, bool SPLIT>
+__global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4))) void k_zqpa_int_series(SolveArgs g, IntArgs ia, SeriesArgs sr, int off_ck,
+                                                                                                  int off_int) {
+  extern __shared__ double lds[];
+  series_step(g, ia, sr, lds,
+              [&](const SolveArgs& gt, const IntArgs& it) { zqpa_int_body<double, M, PROF, SPLIT>(gt, it, sr.nz, off_ck, off_int, lds); });
+}
+
 // LDS of k_zqpa_int in bytes: record | checkpoints [Mg / M + 1][2][nthr] (K = Mg + 1 rows, one every M) | partial sums
 inline size_t zqpa_int_lds_bytes(const SolveArgs& a, int M, int nthr, bool split, int* off_ck = nullptr, int* off_int = nullptr) {
   const int Mg = zqpa_M(a.nz);
@@ -883,7 +898,7 @@ inline size_t zqpa_int_lds_bytes(const SolveArgs& a, int M, int nthr, bool split
 }
 
 template <typename TIO, int M, bool PROF, bool SPLIT>
-int launch_zqpa_int_m(const SolveArgs& a, const IntArgs& ia, hipStream_t s, int nthr) {
+int launch_zqpa_int_m(const SolveArgs& a, const IntArgs& ia, hipStream_t s, int nthr, const SeriesArgs* sr) {
   const int Mg = zqpa_M(a.nz);
   int off_ck, off_int;
   const size_t sh = zqpa_int_lds_bytes(a, M, nthr, SPLIT, &off_ck, &off_int);
@@ -900,6 +915,19 @@ int launch_zqpa_int_m(const SolveArgs& a, const IntArgs& ia, hipStream_t s, int 
     note_kernel("k_zqpa_int<zq_pa>%s M=%d grid=%d%s", sizeof(TIO) == 8 ? "" : " f32", M, Mg, PROF ? " + level profiles" : "");  // (only a launch that succeeded is reported)
     return (int)CRT_OK;
   };
+  if (sr) {
+    if constexpr (sizeof(TIO) == 8) {
+      auto gos = [&](auto kern) {
+        const int st = launch_series(kern, series_grid(a.ncol, sr->nt), nthr, sh, s, g, ia, *sr, off_ck, off_int);
+        if (st == CRT_OK)
+          note_kernel("k_colpre<canopy> + k_colsun + k_zqpa_int_series<zq_pa> M=%d grid=%d%s%s nt=%d", M, Mg, PROF ? " + level profiles" : "",
+                      SPLIT ? "" : " net flux", sr->nt);
+        return st;
+      };
+      return nthr <= 256 ? gos(k_zqpa_int_series<M, 256, PROF, SPLIT>) : nthr <= 512 ? gos(k_zqpa_int_series<M, 512, PROF, SPLIT>) : gos(k_zqpa_int_series<M, 1024, PROF, SPLIT>);
+    }
+    return CRT_ERR_UNSUPPORTED;  // no f32 form of the series
+  }
   if (nthr <= 256) return go(k_zqpa_int<TIO, M, 256, PROF, SPLIT>);
   if (nthr <= 512) return go(k_zqpa_int<TIO, M, 512, PROF, SPLIT>);
   return go(k_zqpa_int<TIO, M, 1024, PROF, SPLIT>);
@@ -907,7 +935,7 @@ int launch_zqpa_int_m(const SolveArgs& a, const IntArgs& ia, hipStream_t s, int 
 
 // integrated path of zq_pa (float64 or float32 spectra, TIO): one kernel, no workspace beyond the K0 record
 template <typename TIO>
-int launch_zqpa_int_io(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
+int launch_zqpa_int_io(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr) {
   const int nthr = ((a.nb + 63) / 64) * 64;
   // M = 8 (104 / 114 VGPRs) or M = 12 (124 VGPRs): four waves per SIMD with no scratch, also in the 1024-thread form (M = 16 there: 128
   // VGPRs + 56 B of scratch; the net-flux form at M = 12: 128 + 24 B).  The LDS decides how many workgroups share a CU: the form that fits
@@ -918,8 +946,8 @@ int launch_zqpa_int_io(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
   const size_t s8 = zqpa_int_lds_bytes(a, 8, nthr, prof), s12 = zqpa_int_lds_bytes(a, 12, nthr, true);
   auto fits = [](size_t sh) -> size_t { return sh <= MAX_WG_LDS ? MAX_WG_LDS / sh : 0; };
   if (fits(s12) > fits(s8))
-    return prof ? launch_zqpa_int_m<TIO, 12, true, true>(a, ia, s, nthr) : launch_zqpa_int_m<TIO, 12, false, true>(a, ia, s, nthr);
-  return prof ? launch_zqpa_int_m<TIO, 8, true, true>(a, ia, s, nthr) : launch_zqpa_int_m<TIO, 8, false, false>(a, ia, s, nthr);
+    return prof ? launch_zqpa_int_m<TIO, 12, true, true>(a, ia, s, nthr, sr) : launch_zqpa_int_m<TIO, 12, false, true>(a, ia, s, nthr, sr);
+  return prof ? launch_zqpa_int_m<TIO, 8, true, true>(a, ia, s, nthr, sr) : launch_zqpa_int_m<TIO, 8, false, false>(a, ia, s, nthr, sr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1090,9 +1118,9 @@ int launch_zqpa_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
   return a.f32 ? launch_zqpa_lev_io<float>(a, la, s) : launch_zqpa_lev_io<double>(a, la, s);
 }
 
-int launch_zqpa_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s) {
+int launch_zqpa_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr) {
   if (a.nb > 1024) return CRT_ERR_UNSUPPORTED;
-  return a.f32 ? launch_zqpa_int_io<float>(a, ia, s) : launch_zqpa_int_io<double>(a, ia, s);
+  return a.f32 ? launch_zqpa_int_io<float>(a, ia, s, sr) : launch_zqpa_int_io<double>(a, ia, s, sr);
 }
 
 int launch_zqpa(const SolveArgs& a, double* scratch, hipStream_t s) {

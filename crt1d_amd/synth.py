@@ -63,3 +63,21 @@ def make_columns(ncol, nb, nz, *, seed=1234, uniform_dlai=True, per_column_optic
         I_df0=f(I_df0),
         wle=wle,
     )
+
+
+def make_sun_series(d, nt, *, seed=4321, shared=False):
+    """``nt`` sun states for the columns of ``d`` (a :func:`make_columns` dict), for :class:`crt1d_amd.batched.SunSeries`.
+
+    Keys: ``psi (ncol, nt)`` in the generator's range (0 to 75 degrees), ``I_dr0``, ``I_df0`` ``(ncol, nt, nb)`` in
+    :func:`make_columns`' ranges -- or ``(1, nt, nb)`` with ``shared=True``: one series of spectra for every column.
+    """
+    rng = np.random.default_rng(seed)
+    ncol = d["lai"].shape[0]
+    nb = d["leaf_r"].shape[-1]
+    dtype = d["lai"].dtype
+    psi = np.deg2rad(rng.uniform(0.0, 75.0, (ncol, nt)))
+    nc = 1 if shared else ncol
+    I_dr0 = rng.uniform(0.0, 10.0, (nc, nt, nb))
+    I_df0 = rng.uniform(0.0, 5.0, (nc, nt, nb))
+    f = lambda a: np.ascontiguousarray(a, dtype=dtype)  # noqa: E731
+    return dict(psi=f(psi), I_dr0=f(I_dr0), I_df0=f(I_df0))

@@ -306,6 +306,46 @@ int crt_hip_integrated2_f64(int scheme, const crt_columns* cols, const crt_bands
  * nb <= 1024 (else CRT_ERR_UNSUPPORTED); crt_hip_last_kernel names the float instantiation with an " f32" tag. */
 int crt_hip_integrated2_f32(int scheme, const crt_columns* cols, const crt_bands_f32* bands, const crt_options* opts, const double* band_w,
                             int32_t ngroup, const crt_bandsum_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream);
+/*
+ * Sun-angle series: the complete output of crt_hip_integrated2_f64 for `nt` sun states of every column in ONE call -- the same canopy
+ * (lai, leaf angle, leaf and soil optics) under many sun positions psi and incoming spectra I_dr0, I_df0: what the reference does with
+ * `update_p(psi=...)` + `run()` in a loop over a day or a season (model.py:118-176, 295-331).
+ *
+ *  - cols->psi, cols->g_at_psi, bands->I_dr0, bands->I_df0 are NOT read and may be NULL; everything else in crt_columns / crt_bands
+ *    (leaf_r, leaf_t, soil_r and their own col_stride) keeps its meaning and is constant over the series.
+ *  - every array of crt_bandsum_out gains a time axis after the column axis: aI, aI_sl, aI_sh, aI_dr [ncol][nt][nz-1][ngroup];
+ *    I_dr, I_df_d, I_df_u, F, I_d [ncol][nt][nz][ngroup]; totals [ncol][nt][ngroup][4].  Optional pointers as crt_hip_integrated2_f64.
+ *  - CONTRACT: for every t, slice [:, t] of every output is BITWISE what crt_hip_integrated2_f64 writes for the same columns with
+ *    psi = sun.psi[:, t], g_at_psi = sun.g_at_psi[:, t], I_dr0 = sun.I_dr0[:, t], I_df0 = sun.I_df0[:, t].  All eight schemes, nb <= 1024
+ *    (beyond: CRT_ERR_UNSUPPORTED, nothing written).  The series kernels run the per-step kernels' bodies on the same records and pick
+ *    between their forms (zq_pa: net-flux or separate sums, M = 8 / 12) by the same rule, which depends on nz, nb and the requested
+ *    outputs only.
+ *  - what is shared: the column precompute (K0), and nothing else.  Per column, once per call (k_colpre<canopy>): the K_b node table,
+ *    every tau_d / 1 - tau_d quadrature, mu_bar, G_int_1/2, the dLAI analysis, zq_pa's grid and interpolation record.  Per (column, t)
+ *    (k_colsun): K_b, cos psi, G, tau_psi and the vectors built from exp(-K_b lai).  The workspace holds [ncol] canopy records and
+ *    [ncol][nt] sun records.  The solve side shares nothing between sun states: one workgroup per (column, t) assembles its record from
+ *    the two and runs the per-step kernel's body; leaf_r, leaf_t, soil_r are read again for every state (a kernel that walked the
+ *    states of a column with the optics in registers was measured slower than the per-step loop and dropped).
+ *  - CRT_FLAG_PRECOMPUTE_ONLY fills the workspace (both kinds of record) and launches no solve; CRT_FLAG_SKIP_PRECOMPUTE: the workspace
+ *    holds the records of an earlier series call with the same scheme, columns, options and sun.psi (only the spectra changed).
+ *  - CRT_ERR_BAD_ARG before any launch: NULL sun, sun->psi, I_dr0 or I_df0; nt < 1; col_stride neither 0 nor >= nt * nb; g_at_psi NULL
+ *    while cols->g_table is given; everything crt_hip_integrated2_f64 rejects.  CRT_ERR_WORKSPACE below crt_hip_series_workspace_bytes
+ *    (which is 0 for sizes it cannot express).  Any nt: t is spread over two grid dimensions (65535 x 65535 states per column); ncol * nt < 2^31.
+ *  - capturable into a hipGraph after the first call per device; crt_hip_last_kernel names the K0 forms and the series kernel.
+ */
+typedef struct crt_sun_series {
+  int32_t nt;               /* sun states per column, >= 1 */
+  const double* psi;        /* [ncol][nt] solar zenith angle, radians */
+  const double* g_at_psi;   /* [ncol][nt] G(psi[c][t]); read for CRT_G_TABLE columns only (else may be NULL) */
+  int64_t col_stride;       /* of I_dr0 / I_df0: nt*nb (or larger) per column, 0 = one series for every column */
+  const double* I_dr0;      /* element (c, t, b) at p[c*col_stride + t*nb + b] */
+  const double* I_df0;
+} crt_sun_series;
+
+size_t crt_hip_series_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nt);
+int crt_hip_integrated_series_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_sun_series* sun,
+                                  const crt_options* opts, const double* band_w, int32_t ngroup, const crt_bandsum_out* out,
+                                  void* workspace, size_t workspace_bytes, crt_stream_t stream);
 /* The outputs of crt_bandsum_out that follow from the others, re-formed in place in one pass (after the band sums of partial spectra
  * have been added up, e.g. by an all-reduce that carried only aI_sl, aI_sh and the level sums I_dr, I_df_d, I_df_u):
  *     aI = aI_sl + aI_sh,   F = I_dr / cos(psi) + 2 (I_df_u + I_df_d),   I_d = I_dr + I_df_d
