@@ -74,6 +74,10 @@ class CrtSunSeries(ctypes.Structure):
     ]
 
 
+class CrtSunSeriesF32(CrtSunSeries):
+    """crt_sun_series_f32: the layout of crt_sun_series with float I_dr0 / I_df0 behind the pointers (crt_hip_levels_series_f32)."""
+
+
 NTUNE = 16
 
 # crt_options.tune: keys (enum crt_tune_key; what each one selects is documented there) and the named values of some of them.
@@ -182,6 +186,9 @@ EXPORTS = [
     "crt_hip_integrated_series_f64",
     "crt_hip_levels_f64",
     "crt_hip_levels_f32",
+    "crt_hip_levels_series_workspace_bytes",
+    "crt_hip_levels_series_f64",
+    "crt_hip_levels_series_f32",
     "crt_hip_absorb_f32",
     "crt_hip_bandsum_finish_f64",
     "crt_hip_band_reduce_f64",
@@ -291,6 +298,15 @@ def load():
         ctypes.c_int, ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), ctypes.POINTER(CrtSunSeries), ctypes.POINTER(CrtOptions), _vp,
         ctypes.c_int32, ctypes.POINTER(CrtBandsumOut), _vp, ctypes.c_size_t, _vp,
     ]
+    lib.crt_hip_levels_series_workspace_bytes.restype = ctypes.c_size_t
+    lib.crt_hip_levels_series_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+    for suffix, sun_t in (("f64", CrtSunSeries), ("f32", CrtSunSeriesF32)):  # level spectra over a sun-angle series
+        f = getattr(lib, f"crt_hip_levels_series_{suffix}")
+        f.restype = ctypes.c_int
+        f.argtypes = [
+            ctypes.c_int, ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), ctypes.POINTER(sun_t), ctypes.POINTER(CrtOptions),
+            ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(CrtOutputs), _vp, ctypes.c_size_t, _vp,
+        ]
     lib.crt_hip_bandsum_finish_f64.restype = ctypes.c_int
     lib.crt_hip_bandsum_finish_f64.argtypes = [ctypes.POINTER(CrtColumns), ctypes.c_int32, ctypes.POINTER(CrtBandsumOut), _vp]
     lib.crt_hip_band_reduce_f64.restype = ctypes.c_int

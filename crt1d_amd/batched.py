@@ -709,6 +709,12 @@ class SunSeries:
     I_df0: torch.Tensor
     g_at_psi: Optional[torch.Tensor] = None
 
+    _c_type = _lib.CrtSunSeries
+
+    @staticmethod
+    def _spectrum(t, name):  # check of I_dr0 / I_df0 (SunSeriesF32: float32)
+        return _f64(t, name)
+
     def __post_init__(self):
         self.psi = _f64(self.psi, "psi")
         if self.psi.ndim != 2 or self.psi.shape[1] < 1:
@@ -719,7 +725,7 @@ class SunSeries:
                 raise ValueError("g_at_psi must be (ncol, nt)")
         shape = None
         for name in ("I_dr0", "I_df0"):
-            v = _f64(getattr(self, name), name)
+            v = self._spectrum(getattr(self, name), name)
             if v.ndim == 2:
                 v = v[None]
             if v.ndim != 3 or v.shape[1] != self.nt or v.shape[0] not in (1, self.ncol):
@@ -753,10 +759,10 @@ class SunSeries:
     def slice(self, lo, hi):
         """Columns [lo, hi) as a view."""
         g = lambda t: t if t.shape[0] == 1 else t[lo:hi]  # noqa: E731
-        return SunSeries(self.psi[lo:hi], g(self.I_dr0), g(self.I_df0), None if self.g_at_psi is None else self.g_at_psi[lo:hi])
+        return type(self)(self.psi[lo:hi], g(self.I_dr0), g(self.I_df0), None if self.g_at_psi is None else self.g_at_psi[lo:hi])
 
     def c_struct(self):
-        return _lib.CrtSunSeries(self.nt, self.psi.data_ptr(), None if self.g_at_psi is None else self.g_at_psi.data_ptr(), self.col_stride,
+        return self._c_type(self.nt, self.psi.data_ptr(), None if self.g_at_psi is None else self.g_at_psi.data_ptr(), self.col_stride,
                                  self.I_dr0.data_ptr(), self.I_df0.data_ptr())
 
     @classmethod
@@ -764,6 +770,34 @@ class SunSeries:
         """From a dict of NumPy arrays (:func:`crt1d_amd.synth.make_sun_series`)."""
         t = lambda k: None if d.get(k) is None else torch.as_tensor(d[k]).to(device)  # noqa: E731
         return cls(t("psi"), t("I_dr0"), t("I_df0"), t("g_at_psi"))
+
+
+def _f32(t, name):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32, got {t.dtype}")
+    if not t.is_cuda:
+        raise ValueError(f"{name} must live on the GPU (got {t.device}); crt1d_amd has no CPU path")
+    return t.contiguous()
+
+
+@dataclass
+class SunSeriesF32(SunSeries):
+    """:class:`SunSeries` with float32 incoming spectra ``I_dr0``, ``I_df0`` (``crt_sun_series_f32``, for float32 :class:`Bands`): half
+    the bytes, widened on load; ``psi`` and ``g_at_psi`` stay float64.  Served by :class:`LevelsSeriesPlan` only."""
+
+    _c_type = _lib.CrtSunSeriesF32
+
+    @staticmethod
+    def _spectrum(t, name):
+        return _f32(t, name)
+
+    @classmethod
+    def from_host(cls, d, device="cuda"):
+        """From a dict of NumPy arrays (:func:`crt1d_amd.synth.make_sun_series`); the spectra are rounded to float32."""
+        t = lambda k: None if d.get(k) is None else torch.as_tensor(d[k]).to(device)  # noqa: E731
+        return cls(t("psi"), t("I_dr0").to(torch.float32), t("I_df0").to(torch.float32), t("g_at_psi"))
 
 
 def series_workspace_bytes(scheme, ncol, nz, nb, nt):
@@ -789,8 +823,8 @@ class IntegratedSeriesPlan:
             raise ValueError(f"scheme {scheme!r} has no integrated kernel")
         if tau_d_method not in _lib.TAU_D_METHODS:
             raise ValueError("invalid `method`. Valid options are 'quad' and '9sky'.")
-        if not isinstance(sun, SunSeries):
-            raise TypeError("sun must be a SunSeries")
+        if not isinstance(sun, SunSeries) or isinstance(sun, SunSeriesF32):
+            raise TypeError("sun must be a SunSeries (float64 spectra)")
         self.lib = _lib.load()
         self.scheme, self.cols, self.bands, self.sun = scheme, cols, bands, sun
         band_w = _f64(band_w, "band_w")
@@ -971,3 +1005,107 @@ def spectral_totals(scheme, cols: Columns, bands: Bands, **kw):
     dr, dn, up = (r[k].to(torch.float64) for k in ("I_dr", "I_df_d", "I_df_u"))
     i_d = dr + dn
     return torch.stack((i_d[:, 1], up[:, 1], i_d[:, 0], up[:, 0]), dim=-1)
+
+
+def levels_series_workspace_bytes(scheme, ncol, nz, nt):
+    """Device workspace of a :class:`LevelsSeriesPlan` call: the canopy records of the columns and the sun records of every (column, t).
+    Never larger than :func:`series_workspace_bytes`, and laid out the same way: one buffer of that size serves both series plans."""
+    return int(_lib.load().crt_hip_levels_series_workspace_bytes(_lib.SCHEME_IDS[scheme], ncol, nz, nt))
+
+
+class LevelsSeriesPlan:
+    """The outputs of :class:`LevelsPlan` for ``sun.nt`` sun states of every column in one call (``crt_hip_levels_series_f64``, or
+    ``_f32`` for float32 bands and a :class:`SunSeriesF32`): the spectra of ``keys`` at the levels ``levels``, each
+    ``(ncol, nt, nsel, nb)`` in the dtype of ``bands``.  ``out[k][:, t]`` is bitwise what ``LevelsPlan`` returns with
+    ``psi = sun.psi[:, t]`` and the incoming spectra of step ``t`` -- hence bitwise rows of :func:`solve` of that step.  The canopy-only part
+    of the column precompute runs once per column, the sun-dependent part once per (column, t).  ``cols.psi``, ``cols.g_at_psi`` and
+    ``bands.I_dr0`` / ``I_df0`` are not read (``bands`` may be built with ``None`` for the two).  Any ``nb``."""
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, *, keys=LEVEL_KEYS, mu_s=0.501, tau_d_method="quad",
+                 out=None, workspace=None):
+        if scheme not in _lib.SCHEME_IDS:
+            raise ValueError(f"unknown scheme {scheme!r}; valid: {', '.join(SCHEMES)}")
+        if tau_d_method not in _lib.TAU_D_METHODS:
+            raise ValueError("invalid `method`. Valid options are 'quad' and '9sky'.")  # common.py:78
+        if not isinstance(sun, SunSeries):
+            raise TypeError("sun must be a SunSeries or a SunSeriesF32")
+        keys = (keys,) if isinstance(keys, str) else tuple(keys)
+        if not keys or any(k not in LEVEL_KEYS for k in keys) or len(set(keys)) != len(keys):
+            raise ValueError(f"keys must be distinct names out of {LEVEL_KEYS}, got {keys!r}")
+        self.lib = _lib.load()
+        self.scheme, self.cols, self.bands, self.sun = scheme, cols, bands, sun
+        ncol, nz, nb, dev = cols.ncol, cols.nz, bands.nb, cols.device
+        self.levels = normalize_levels(levels, nz)
+        self.keys = keys
+        if bands.dtype != sun.I_dr0.dtype:
+            want = "SunSeriesF32" if bands.dtype == torch.float32 else "SunSeries"
+            raise TypeError(f"{bands.dtype} bands need a {want}: the spectra of sun are {sun.I_dr0.dtype}")
+        if sun.ncol != ncol or sun.nb != nb:
+            raise ValueError(f"sun must have ncol = {ncol} rows and nb = {nb} bands, got {sun.ncol} and {sun.nb}")
+        if sun.psi.device != dev:
+            raise ValueError(f"sun lives on {sun.psi.device} but the columns on {dev}")
+        if (cols.g_table is not None or cols.g_at_psi is not None) and sun.g_at_psi is None and bool((cols.g_kind == 6).any()):
+            raise ValueError("columns with g_kind = G_TABLE need sun.g_at_psi (ncol, nt)")
+        if cols.g_table is None and bool((cols.g_kind == 6).any()):
+            raise ValueError("columns with g_kind = G_TABLE need g_table")
+        _check_band_device(bands, dev)
+        if bands.leaf_r is None or bands.leaf_t is None:
+            raise ValueError("bands needs leaf_r and leaf_t")
+        if scheme == "2s" and cols.mla is None:
+            raise ValueError("solve_2s needs `mla`")
+        if scheme != "bl" and bands.soil_r is None:
+            raise ValueError(f"solve_{scheme} needs `soil_r`")
+        shape = (ncol, sun.nt, len(self.levels), nb)
+        if out is None:
+            out = {k: torch.empty(shape, dtype=bands.dtype, device=dev) for k in keys}
+        else:
+            for k in keys:
+                if k not in out:
+                    raise ValueError(f"`out` lacks {k!r}")
+                _check_profile(out[k], f"output {k!r}", shape, dev, bands.dtype)
+            out = {k: out[k] for k in keys}
+        self.out = out
+        self._out = _lib.CrtOutputs(*[out[k].data_ptr() if k in out else None for k in LEVEL_KEYS], None, None, None)
+        self._lev = (ctypes.c_int32 * len(self.levels))(*self.levels)
+        need = levels_series_workspace_bytes(scheme, ncol, nz, sun.nt)
+        self.workspace = _check_workspace(workspace, need, dev)
+        self._wsb = self.workspace.numel() * self.workspace.element_size()
+        self._c, self._b, self._s = cols.c_struct(), bands.c_struct(ncol), sun.c_struct()
+        if cols.g_table is None:
+            self._c.g_table = None
+        self._o = _lib.CrtOptions(float(mu_s), _lib.TAU_D_METHODS[tau_d_method], 0)
+        self._entry = f"crt_hip_levels_series_{_io_suffix(bands)}"
+        self._fn = getattr(self.lib, self._entry)
+
+    def last_kernel(self):
+        """K0 forms and series level kernel of this thread's most recent call (``crt_hip_last_kernel``)."""
+        return self.lib.crt_hip_last_kernel().decode()
+
+    def __call__(self, stream=None, *, flags=0):
+        """Enqueue on ``stream`` (default: torch's current stream); ``flags`` as for :class:`IntegratedSeriesPlan`."""
+        dev = self.cols.device
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        self._o.flags = int(flags)
+        with torch.cuda.device(dev):
+            st = self._fn(_lib.SCHEME_IDS[self.scheme], ctypes.byref(self._c), ctypes.byref(self._b), ctypes.byref(self._s),
+                          ctypes.byref(self._o), self._lev, len(self.levels), ctypes.byref(self._out), self.workspace.data_ptr(), self._wsb,
+                          s.cuda_stream)
+        _lib.check(st, self._entry)
+        return self.out
+
+
+def solve_levels_series(scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, **kw):
+    """One-shot :class:`LevelsSeriesPlan`: ``{key: (ncol, nt, nsel, nb)}`` at the sorted levels ``normalize_levels(levels, nz)``."""
+    with torch.cuda.device(cols.device):
+        return LevelsSeriesPlan(scheme, cols, bands, sun, levels, **kw)()
+
+
+def spectral_totals_series(scheme, cols: Columns, bands: Bands, sun: SunSeries, **kw):
+    """:func:`spectral_totals` with a time axis: ``(ncol, nt, nb, 4)`` float64 -- incoming ``I_d[top]``, reflected ``I_df_u[top]``,
+    transmitted ``I_d[0]`` and soil-reflected ``I_df_u[0]`` spectra of every sun state -- from one level-series call at the ground and the
+    top.  Slice ``[:, t]`` is bitwise :func:`spectral_totals` of step ``t``.  ``kw`` as for :class:`LevelsSeriesPlan`."""
+    nz = cols.nz
+    r = solve_levels_series(scheme, cols, bands, sun, (0, nz - 1), keys=("I_dr", "I_df_d", "I_df_u"), **kw)
+    dr, dn, up = (r[k].to(torch.float64) for k in ("I_dr", "I_df_d", "I_df_u"))
+    i_d = dr + dn
+    return torch.stack((i_d[:, :, 1], up[:, :, 1], i_d[:, :, 0], up[:, :, 0]), dim=-1)

@@ -1280,6 +1280,16 @@ size_t crt_hip_series_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int3
   return (base > can ? base : can) + nsun * per;
 }
 
+size_t crt_hip_levels_series_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nt) {
+  // the records of crt_hip_series_workspace_bytes at the same offsets, and nothing behind them: no nb
+  if (!scheme_ok(scheme) || ncol <= 0 || nz <= 0 || nt < 1) return 0;
+  const size_t can = (size_t)ncol * (size_t)can_len(scheme, nz) * sizeof(double);
+  const size_t per = (size_t)sun_len(scheme, nz) * sizeof(double);
+  const size_t nsun = (size_t)ncol * (size_t)nt;
+  if (nsun > (SIZE_MAX - can) / per) return 0;
+  return can + nsun * per;
+}
+
 int crt_hip_quad_nodes(double mu_s, double* psi_nodes) {
   if (!psi_nodes || !(mu_s > 0.0 && mu_s < 1.0)) return CRT_ERR_BAD_ARG;
   host_quad_nodes(mu_s, psi_nodes);
@@ -1295,8 +1305,8 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
   if (!cols->lai || !cols->g_kind) return CRT_ERR_BAD_ARG;
   if (scheme == CRT_SCHEME_2S && !cols->mla) return CRT_ERR_BAD_ARG;
   if (!bands->leaf_r || !bands->leaf_t) return CRT_ERR_BAD_ARG;
-  if (ser) {  // sun-angle series (integrated outputs only): the sun and the incoming spectra come from `ser`, not from cols / bands
-    if (!integ || !ser->psi || !ser->I_dr0 || !ser->I_df0 || ser->nt < 1) return CRT_ERR_BAD_ARG;
+  if (ser) {  // sun-angle series (integrated outputs or level spectra): the sun and the incoming spectra come from `ser`, not from cols / bands
+    if ((!integ && !lev) || !ser->psi || !ser->I_dr0 || !ser->I_df0 || ser->nt < 1) return CRT_ERR_BAD_ARG;
     if (ser->col_stride != 0 && ser->col_stride < (int64_t)ser->nt * nb) return CRT_ERR_BAD_ARG;
     if (cols->g_table && !ser->g_at_psi) return CRT_ERR_BAD_ARG;
   } else if (!cols->psi || !bands->I_dr0 || !bands->I_df0) {
@@ -1345,10 +1355,13 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
   }
   if (scheme == CRT_SCHEME_4S && !(mu_s > 0.0 && mu_s < 1.0)) return CRT_ERR_BAD_ARG;
   if (method != CRT_TAU_D_QUAD && method != CRT_TAU_D_9SKY) return CRT_ERR_BAD_ARG;  // ValueError, common.py:78
-  const size_t need = ser ? crt_hip_series_workspace_bytes(scheme, ncol, nz, nb, ser->nt) : crt_hip_workspace_bytes_nb(scheme, ncol, nz, nb);
+  const size_t need = !ser ? crt_hip_workspace_bytes_nb(scheme, ncol, nz, nb)
+                      : lev ? crt_hip_levels_series_workspace_bytes(scheme, ncol, nz, ser->nt)
+                            : crt_hip_series_workspace_bytes(scheme, ncol, nz, nb, ser->nt);
   if (need == 0) return CRT_ERR_UNSUPPORTED;  // (series: a size beyond size_t)
   if (!workspace || workspace_bytes < need) return CRT_ERR_WORKSPACE;
-  if (ser && nb > 1024) return CRT_ERR_UNSUPPORTED;  // as the per-step entry, but before K0 has written anything
+  if (ser && integ && nb > 1024) return CRT_ERR_UNSUPPORTED;  // as the per-step entry, but before K0 has written anything
+  if (ser && lev && (long long)ncol * ser->nt > 0x7fffffffLL) return CRT_ERR_UNSUPPORTED;  // (column, t) is a 32-bit index in K0
 
   hipStream_t s = static_cast<hipStream_t>(stream);
   ColArgs ca;
@@ -1370,17 +1383,6 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
     double* const sunrec = static_cast<double*>(workspace) + (size_t)ncol * can_len(scheme, nz);
     ca.psi = ser->psi;
     ca.g_at_psi = ser->g_at_psi;
-    if (!(flags & CRT_FLAG_SKIP_PRECOMPUTE)) {
-      const int st = launch_colpre_series(ca, ser->nt, sunrec, s);
-      if (st != CRT_OK) return st;
-    } else {
-      const int st = init_quadrature(s);
-      if (st != CRT_OK) return st;
-    }
-    if (flags & CRT_FLAG_PRECOMPUTE_ONLY) {
-      note_kernel("k_colpre<canopy> + k_colsun nt=%d", ser->nt);
-      return CRT_OK;
-    }
     SolveArgs sa = {};
     sa.ncol = ncol;
     sa.nb = nb;
@@ -1392,6 +1394,7 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
     sa.leaf_t = bands->leaf_t;
     sa.soil_r = bands->soil_r;
     sa.mu_s = mu_s;
+    sa.f32 = f32;
     std::memcpy(&sa.tune, tune, sizeof sa.tune);
     SeriesArgs sr;
     sr.nt = ser->nt;
@@ -1404,9 +1407,28 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
     sr.col_stride = ser->col_stride;
     sr.I_dr0 = ser->I_dr0;
     sr.I_df0 = ser->I_df0;
+    auto lev_series = [&](bool probe) {
+      if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_lev(sa, *lev, s, &sr, probe);
+      return tri ? launch_tridiag_lev(scheme, sa, *lev, s, &sr, probe) : launch_closed_lev(scheme, sa, *lev, s, &sr, probe);
+    };
+    if (lev) {  // every shape the level series cannot serve is found here, before K0 has written anything
+      const int st = lev_series(true);
+      if (st != CRT_OK) return st;
+    }
+    if (!(flags & CRT_FLAG_SKIP_PRECOMPUTE)) {
+      const int st = launch_colpre_series(ca, ser->nt, sunrec, s);
+      if (st != CRT_OK) return st;
+    } else {
+      const int st = init_quadrature(s);
+      if (st != CRT_OK) return st;
+    }
+    if (flags & CRT_FLAG_PRECOMPUTE_ONLY) {
+      note_kernel("k_colpre<canopy> + k_colsun nt=%d", ser->nt);
+      return CRT_OK;
+    }
+    if (lev) return lev_series(false);
     if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_int(sa, *integ, s, &sr);
-    return (scheme == CRT_SCHEME_N79 || scheme == CRT_SCHEME_ZQ) ? launch_tridiag_int(scheme, sa, *integ, s, &sr)
-                                                                   : launch_closed_int(scheme, sa, *integ, s, &sr);
+    return tri ? launch_tridiag_int(scheme, sa, *integ, s, &sr) : launch_closed_int(scheme, sa, *integ, s, &sr);
   }
   // 2s profiles: the closed-form launcher forms the records inside k_pipe when it picks that kernel (one launch per call), and runs
   // k_colpre in front of any other kernel.  SKIP_PRECOMPUTE / PRECOMPUTE_ONLY and CRT_TUNE_K0_SEPARATE keep k_colpre as a kernel of its own.
@@ -1608,7 +1630,8 @@ int crt_hip_integrated_f32(int scheme, const crt_columns* cols, const crt_bands_
 // f32: crt_bands_f32 / crt_outputs_f32 have the layouts of crt_bands / crt_outputs (crt_hip_solve_f32).  Every argument error is found here
 // or in solve_impl's checks, before any launch.
 static int levels_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
-                       int32_t nsel, const crt_outputs* out, void* workspace, size_t workspace_bytes, crt_stream_t stream, int f32) {
+                       int32_t nsel, const crt_outputs* out, void* workspace, size_t workspace_bytes, crt_stream_t stream, int f32,
+                       const crt_sun_series* ser = nullptr) {
   if (!scheme_ok(scheme) || !cols || !levels || !out) return CRT_ERR_BAD_ARG;
   if (nsel < 1 || nsel > CRT_MAX_LEVEL_SELECT) return CRT_ERR_BAD_ARG;
   if (out->x0 || out->x1 || out->x2) return CRT_ERR_BAD_ARG;
@@ -1625,7 +1648,27 @@ static int levels_impl(int scheme, const crt_columns* cols, const crt_bands* ban
     la.lev[r] = levels[r];
   }
   crt_outputs none = {};
-  return solve_impl(scheme, cols, bands, opts, &none, workspace, workspace_bytes, stream, f32, nullptr, &la);
+  return solve_impl(scheme, cols, bands, opts, &none, workspace, workspace_bytes, stream, f32, nullptr, &la, ser);
+}
+
+// crt_sun_series_f32 has the layout of crt_sun_series (the element type behind I_dr0 / I_df0 differs: SeriesArgs carries them untyped)
+int crt_hip_levels_series_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_sun_series* sun, const crt_options* opts,
+                              const int32_t* levels, int32_t nsel, const crt_outputs* out, void* workspace, size_t workspace_bytes,
+                              crt_stream_t stream) {
+  if (!sun) return CRT_ERR_BAD_ARG;
+  return levels_impl(scheme, cols, bands, opts, levels, nsel, out, workspace, workspace_bytes, stream, 0, sun);
+}
+
+int crt_hip_levels_series_f32(int scheme, const crt_columns* cols, const crt_bands_f32* bands, const crt_sun_series_f32* sun,
+                              const crt_options* opts, const int32_t* levels, int32_t nsel, const crt_outputs_f32* out, void* workspace,
+                              size_t workspace_bytes, crt_stream_t stream) {
+  static_assert(sizeof(crt_sun_series_f32) == sizeof(crt_sun_series) && offsetof(crt_sun_series_f32, I_dr0) == offsetof(crt_sun_series, I_dr0) &&
+                    offsetof(crt_sun_series_f32, I_df0) == offsetof(crt_sun_series, I_df0) &&
+                    offsetof(crt_sun_series_f32, col_stride) == offsetof(crt_sun_series, col_stride),
+                "layout");
+  if (!sun) return CRT_ERR_BAD_ARG;
+  return levels_impl(scheme, cols, reinterpret_cast<const crt_bands*>(bands), opts, levels, nsel, reinterpret_cast<const crt_outputs*>(out),
+                     workspace, workspace_bytes, stream, 1, reinterpret_cast<const crt_sun_series*>(sun));
 }
 
 int crt_hip_levels_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,

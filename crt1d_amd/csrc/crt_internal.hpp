@@ -632,8 +632,8 @@ struct SeriesArgs {
   const double* can;     // canopy records
   const double* sun;     // sun records
   long long col_stride;  // of I_dr0 / I_df0 (crt_sun_series)
-  const double* I_dr0;
-  const double* I_df0;
+  const void* I_dr0;     // double (crt_sun_series) or float (crt_sun_series_f32: the level series with f32 storage)
+  const void* I_df0;
 };
 
 // sun-record form of K0 (colpre.hip): ca.psi / ca.g_at_psi are [ncol][nt], ca.ws the canopy records, `sun` the sun records
@@ -656,18 +656,10 @@ inline int launch_series(K kern, dim3 grid, int nthr, size_t sh, hipStream_t s, 
   return hipGetLastError() == hipSuccess ? (int)CRT_OK : (int)CRT_ERR_LAUNCH;
 }
 
-// One sun state of one column per workgroup.  Assembles the record of (column, t) in lds[0 .. reclen) -- each header slot and each vector
-// from the canopy record or from the sun record, in one pass -- and calls `body(a_t, ia_t)`, the per-step kernel's body, with argument
-// blocks whose spectra and output pointers are shifted so that the body's own indexing by the COLUMN reaches I_dr0 / I_df0 of (column, t)
-// and slice [column][t] of every output.  The shifts are workgroup-uniform; there is no loop over sun states, so the body keeps the
-// registers it has in the per-step kernel.
-template <class Body>
-__device__ __forceinline__ void series_step(const SolveArgs& a, const IntArgs& ia, const SeriesArgs& sr, double* lds, Body body) {
-  const int c = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x, nz = sr.nz, ng = ia.ngroup;
-  const long long tl = (long long)blockIdx.z * gridDim.y + blockIdx.y;
-  if (tl >= sr.nt) return;  // (whole workgroup, before any barrier)
-  const int t = (int)tl;
-  const long long v = (long long)c * sr.nt + t;
+// The record of sun state v = c * nt + t of column c in lds[0 .. reclen): each header slot and each vector from the canopy record or from
+// the sun record, in one pass, and the barrier behind it (call with every thread of the workgroup).
+__device__ __forceinline__ void series_assemble(const SeriesArgs& sr, int reclen, int c, long long v, double* lds) {
+  const int tid = threadIdx.x, nthr = blockDim.x, nz = sr.nz;
   {
     const double* can = sr.can + (long long)c * sr.canlen;
     const double* sun = sr.sun + v * sr.sunlen;
@@ -678,7 +670,7 @@ __device__ __forceinline__ void series_step(const SolveArgs& a, const IntArgs& i
         if (sun_hdr_slot(i) == tid) si = i;
       lds[tid] = si >= 0 ? sun[si] : can[tid];
     }
-    const int nvec = (a.reclen - REC_HDR) / nz;
+    const int nvec = (reclen - REC_HDR) / nz;
     for (int vec = 0; vec < nvec; ++vec) {
       const int sv = rec_vec_sun(sr.scheme, vec);
       const double* src = sv >= 0 ? sun + SUN_HDR + sv * nz : can + REC_HDR + vec * nz;
@@ -686,11 +678,26 @@ __device__ __forceinline__ void series_step(const SolveArgs& a, const IntArgs& i
     }
   }
   __syncthreads();
+}
+
+// One sun state of one column per workgroup.  Assembles the record of (column, t) in lds[0 .. reclen) (series_assemble) and calls
+// `body(a_t, ia_t)`, the per-step kernel's body, with argument
+// blocks whose spectra and output pointers are shifted so that the body's own indexing by the COLUMN reaches I_dr0 / I_df0 of (column, t)
+// and slice [column][t] of every output.  The shifts are workgroup-uniform; there is no loop over sun states, so the body keeps the
+// registers it has in the per-step kernel.
+template <class Body>
+__device__ __forceinline__ void series_step(const SolveArgs& a, const IntArgs& ia, const SeriesArgs& sr, double* lds, Body body) {
+  const int c = blockIdx.x, nz = sr.nz, ng = ia.ngroup;
+  const long long tl = (long long)blockIdx.z * gridDim.y + blockIdx.y;
+  if (tl >= sr.nt) return;  // (whole workgroup, before any barrier)
+  const int t = (int)tl;
+  const long long v = (long long)c * sr.nt + t;
+  series_assemble(sr, a.reclen, c, v, lds);
   SolveArgs at = a;
   IntArgs it = ia;
   const long long din = (long long)c * sr.col_stride + (long long)t * a.nb - (long long)c * a.col_stride;
-  at.I_dr0 = sr.I_dr0 + din;
-  at.I_df0 = sr.I_df0 + din;
+  at.I_dr0 = static_cast<const double*>(sr.I_dr0) + din;
+  at.I_df0 = static_cast<const double*>(sr.I_df0) + din;
   const long long sh = v - c, sa = sh * (nz - 1) * ng, sl = sh * nz * ng;
   it.aI += sa;
   it.aI_sl += sa;
@@ -733,13 +740,46 @@ inline LevSlices lev_slices(int nb, int wmax) {
   return ls;
 }
 
-int launch_closed_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s);
-int launch_tridiag_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s);
-int launch_zqpa_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s);
-int launch_tri_lev_n79_f64(const SolveArgs& a, const LevArgs& la, hipStream_t s);
-int launch_tri_lev_n79_f32(const SolveArgs& a, const LevArgs& la, hipStream_t s);
-int launch_tri_lev_zq_f64(const SolveArgs& a, const LevArgs& la, hipStream_t s);
-int launch_tri_lev_zq_f32(const SolveArgs& a, const LevArgs& la, hipStream_t s);
+// Level-subset outputs over a sun-angle series (crt_hip_levels_series_*): one workgroup per (column, band slice, sun state).  The column is
+// blockIdx.x as in the per-step level kernels; t = (blockIdx.z / nslice) * gridDim.y + blockIdx.y and the band slice blockIdx.z % nslice, so
+// that any nt fits as long as nslice * ceil(nt / 65535) <= 65535.
+inline bool lev_series_grid(int ncol, int nt, int nslice, dim3* grid) {
+  const unsigned gy = nt < 65535 ? (unsigned)nt : 65535u;
+  const long long gz = (long long)nslice * ((nt + (long long)gy - 1) / gy);
+  if (gz > 65535) return false;
+  *grid = dim3((unsigned)ncol, gy, (unsigned)gz);
+  return true;
+}
+
+// Assembles the record of (column, t) in lds[0 .. reclen) and calls `body(a_t, slice, oshift)`, the per-step level kernel's body: a_t has
+// its spectra shifted so that the body's indexing by the COLUMN reaches I_dr0 / I_df0 of (column, t) (TIO elements: the series spectra have
+// the storage type of the call), and oshift (elements) moves its [column][nsel][nb] output index to slice [column][t].  Both are
+// workgroup-uniform.  LevArgs is passed on untouched: its level list stays in the kernel arguments.
+template <typename TIO, class Body>
+__device__ __forceinline__ void series_lev_step(const SolveArgs& a, const LevArgs& la, const SeriesArgs& sr, int nslice, double* lds, Body body) {
+  const int c = blockIdx.x;
+  const int zt = blockIdx.z / nslice, slice = blockIdx.z - zt * nslice;
+  const long long tl = (long long)zt * gridDim.y + blockIdx.y;
+  if (tl >= sr.nt) return;  // (whole workgroup, before any barrier)
+  const int t = (int)tl;
+  const long long v = (long long)c * sr.nt + t;
+  series_assemble(sr, a.reclen, c, v, lds);
+  SolveArgs at = a;
+  const long long din = (long long)c * sr.col_stride + (long long)t * a.nb - (long long)c * a.col_stride;
+  at.I_dr0 = static_cast<const TIO*>(sr.I_dr0) + din;
+  at.I_df0 = static_cast<const TIO*>(sr.I_df0) + din;
+  body(at, slice, (v - c) * la.nsel * a.nb);
+}
+
+// sr: nullptr = the per-step kernel; else the series kernel of the same form (same slices, same LDS layout, same M).  probe: choose the
+// configuration and return its status (CRT_OK / CRT_ERR_UNSUPPORTED) without launching anything.
+int launch_closed_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr = nullptr, bool probe = false);
+int launch_tridiag_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr = nullptr, bool probe = false);
+int launch_zqpa_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr = nullptr, bool probe = false);
+int launch_tri_lev_n79_f64(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe);
+int launch_tri_lev_n79_f32(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe);
+int launch_tri_lev_zq_f64(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe);
+int launch_tri_lev_zq_f32(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe);
 
 // launchers implemented in the .hip files
 int launch_colpre(const ColArgs& a, hipStream_t s);

@@ -1245,17 +1245,12 @@ int launch_int_io(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const Se
 // lane per band.  Every scheme's level() restarts its per-level exponentials at exact_level(j) ((j & 7) == 0) on a uniform column and
 // evaluates them at every level of a ragged one, and nothing else of its state depends on earlier levels: a level j is reproduced
 // bitwise by walking from 8 floor(j / 8) (uniform) or from j itself (ragged).  Selected levels in one block of 8 share the walk.
-template <class S, typename TIO, int MAXT, bool USE_LDS>
-__global__ __launch_bounds__(MAXT) void k_lev(SolveArgs a, LevArgs la, int per) {
-  extern __shared__ double lds[];
+// lev_body: the walk and the stores, on the record `rec` of the workgroup's column (blockIdx.x), for band slice `slice`; oshift (elements,
+// workgroup-uniform) is added to the [column][nsel][nb] output index: 0 in k_lev, the offset of slice [column][t] in k_lev_series.
+template <class S, typename TIO>
+__device__ __forceinline__ void lev_body(const SolveArgs& a, const LevArgs& la, int per, const double* rec, int slice, long long oshift) {
   const int c = blockIdx.x, nz = a.nz, nb = a.nb;
-  const double* rec = a.ws + (long long)c * a.reclen;
-  if constexpr (USE_LDS) {
-    for (int i = threadIdx.x; i < a.reclen; i += blockDim.x) lds[i] = rec[i];
-    __syncthreads();
-    rec = lds;
-  }
-  const int b = blockIdx.y * per + threadIdx.x;
+  const int b = slice * per + threadIdx.x;
   if ((int)threadIdx.x >= per || b >= nb) return;  // (no barrier below)
   S st;
   st.init(rec, load_band<TIO>(a, c, b, S::SOIL), a);
@@ -1268,19 +1263,54 @@ __global__ __launch_bounds__(MAXT) void k_lev(SolveArgs a, LevArgs la, int per) 
     double val[S::NARR];
     for (int jj = j0; jj <= j; ++jj) st.level(jj, rec, nz, val);
     next = j + 1;
-    const long long o = ((long long)c * nsel + r) * nb + b;
+    const long long o = ((long long)c * nsel + r) * nb + b + oshift;
 #pragma unroll
     for (int q = 0; q < 4; ++q)
       if (la.o[q]) __builtin_nontemporal_store((TIO)val[q], outp<TIO>(la.o[q]) + o);
   }
 }
 
+template <class S, typename TIO, int MAXT, bool USE_LDS>
+__global__ __launch_bounds__(MAXT) void k_lev(SolveArgs a, LevArgs la, int per) {
+  extern __shared__ double lds[];
+  const double* rec = a.ws + (long long)blockIdx.x * a.reclen;
+  if constexpr (USE_LDS) {
+    for (int i = threadIdx.x; i < a.reclen; i += blockDim.x) lds[i] = rec[i];
+    __syncthreads();
+    rec = lds;
+  }
+  lev_body<S, TIO>(a, la, per, rec, blockIdx.y, 0);
+}
+
+// k_lev over a sun-angle series (series_lev_step, crt_internal.hpp): one workgroup per (column, band slice, sun state); the record is
+// assembled in LDS from the column's canopy record and the state's sun record, and k_lev's body runs on it.
+template <class S, typename TIO, int MAXT>
+__global__ __launch_bounds__(MAXT) void k_lev_series(SolveArgs a, LevArgs la, SeriesArgs sr, int per, int nslice) {
+  extern __shared__ double lds[];
+  series_lev_step<TIO>(a, la, sr, nslice, lds,
+                       [&](const SolveArgs& at, int slice, long long oshift) { lev_body<S, TIO>(at, la, per, lds, slice, oshift); });
+}
+
 template <class S, typename TIO>
-int launch_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
+int launch_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
   const LevSlices ls = lev_slices(a.nb, 1024);  // the record is all the LDS a workgroup needs
   if (ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
   const size_t sh = (size_t)a.reclen * sizeof(double);
   const bool use_lds = sh <= 160 * 1024;  // deeper columns read their record from the workspace (every nz the profile path serves)
+  if (sr) {  // the series has no assembled record in the workspace: LDS only
+    dim3 grid;
+    if (!use_lds || !lev_series_grid(a.ncol, sr->nt, ls.nslice, &grid)) return CRT_ERR_UNSUPPORTED;
+    if (probe) return CRT_OK;
+    auto gos = [&](auto kern) {
+      const int st = launch_series(kern, grid, ls.nthr, sh, s, a, la, *sr, ls.per, ls.nslice);
+      if (st == CRT_OK)
+        note_kernel("k_colpre<canopy> + k_colsun + k_lev_series<%s>%s nsel=%d slice=%d nt=%d", S::NAME, sizeof(TIO) == 8 ? "" : " f32", la.nsel,
+                    ls.per, sr->nt);
+      return st;
+    };
+    return ls.nthr <= 256 ? gos(k_lev_series<S, TIO, 256>) : ls.nthr <= 512 ? gos(k_lev_series<S, TIO, 512>) : gos(k_lev_series<S, TIO, 1024>);
+  }
+  if (probe) return CRT_OK;
   auto go = [&](auto kern) {
     const size_t shk = use_lds ? sh : 0;
     if (shk > 64 * 1024 &&
@@ -1303,19 +1333,19 @@ int launch_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
 }
 
 template <class S>
-int launch_lev_io(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
-  return a.f32 ? launch_lev<S, float>(a, la, s) : launch_lev<S, double>(a, la, s);
+int launch_lev_io(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
+  return a.f32 ? launch_lev<S, float>(a, la, s, sr, probe) : launch_lev<S, double>(a, la, s, sr, probe);
 }
 
 }  // namespace
 
-int launch_closed_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s) {
+int launch_closed_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
   switch (scheme) {
-    case CRT_SCHEME_2S: return launch_lev_io<Sch2s>(a, la, s);
-    case CRT_SCHEME_4S: return launch_lev_io<Sch4s>(a, la, s);
-    case CRT_SCHEME_BL: return launch_lev_io<SchBl>(a, la, s);
-    case CRT_SCHEME_G77: return launch_lev_io<SchG77<false>>(a, la, s);
-    case CRT_SCHEME_BF: return launch_lev_io<SchG77<true>>(a, la, s);
+    case CRT_SCHEME_2S: return launch_lev_io<Sch2s>(a, la, s, sr, probe);
+    case CRT_SCHEME_4S: return launch_lev_io<Sch4s>(a, la, s, sr, probe);
+    case CRT_SCHEME_BL: return launch_lev_io<SchBl>(a, la, s, sr, probe);
+    case CRT_SCHEME_G77: return launch_lev_io<SchG77<false>>(a, la, s, sr, probe);
+    case CRT_SCHEME_BF: return launch_lev_io<SchG77<true>>(a, la, s, sr, probe);
     default: return CRT_ERR_BAD_ARG;
   }
 }

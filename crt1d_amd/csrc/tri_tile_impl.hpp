@@ -669,11 +669,12 @@ int launch_int_scheme(const SolveArgs& a, const IntArgs& ia, hipStream_t s, cons
 // cursor from the last selected level down is the (wave-uniform) selection test.  Row values are the profile kernels' expressions
 // (S::value<>: I_dr = bc rec[k], F formed in the scheme's own order) on the same back-substituted pair: the same bits.
 template <class S, typename TIO, int M>
-__device__ __forceinline__ void tri_lev_body(const SolveArgs& a, const LevArgs& la, int per, int off_ck, double* lds) {
+__device__ __forceinline__ void tri_lev_body(const SolveArgs& a, const LevArgs& la, int per, int off_ck, double* lds, int slice,
+                                             long long oshift) {  // oshift: 0, or the offset of slice [column][t] (series, workgroup-uniform)
   const int nb = a.nb, nz = a.nz, nsel = la.nsel;
   const int tid = threadIdx.x, nthr = blockDim.x;
   const int c = blockIdx.x;
-  const int b = blockIdx.y * per + tid;
+  const int b = slice * per + tid;
   if (tid >= per || b >= nb) return;  // (no barrier below)
   const double* rec = lds;
   double* ck = lds + off_ck + tid;  // [nck][2][nthr]
@@ -727,7 +728,7 @@ __device__ __forceinline__ void tri_lev_body(const SolveArgs& a, const LevArgs& 
           const double t[2] = {o[0], o[1]};  // the staged I_df_d, I_df_u of the profile kernels' tile
           const double v[4] = {S::template value<0>(rec, nz, k, bc, invmu, t, 1, 0), t[0], t[1],
                                S::template value<3>(rec, nz, k, bc, invmu, t, 1, 0)};
-          const long long oo = ((long long)c * nsel + r) * nb + b;
+          const long long oo = ((long long)c * nsel + r) * nb + b + oshift;
 #pragma unroll
           for (int q = 0; q < 4; ++q)
             if (la.o[q]) __builtin_nontemporal_store((TIO)v[q], outp<TIO>(la.o[q]) + oo);
@@ -750,11 +751,29 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(M <= 8 ? 5
   typedef typename UniformOf<S>::type SU;
   if constexpr (!std::is_same<S, SU>::value) {
     if (lds[S_UNIF] != 0.0) {
-      tri_lev_body<SU, TIO, M>(a, la, per, off_ck, lds);
+      tri_lev_body<SU, TIO, M>(a, la, per, off_ck, lds, blockIdx.y, 0);
       return;
     }
   }
-  tri_lev_body<S, TIO, M>(a, la, per, off_ck, lds);
+  tri_lev_body<S, TIO, M>(a, la, per, off_ck, lds, blockIdx.y, 0);
+}
+
+// k_tri_lev over a sun-angle series (series_lev_step, crt_internal.hpp): one workgroup per (column, band slice, sun state); the record is
+// assembled from the column's canopy record and the state's sun record, and tri_lev_body runs on it (S_UNIF is the canopy's).
+template <class S, typename TIO, int M, int MAXT>
+__global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(M <= 8 ? 5 : 3))) void k_tri_lev_series(SolveArgs a, LevArgs la, SeriesArgs sr,
+                                                                                                               int per, int off_ck, int nslice) {
+  extern __shared__ double lds[];
+  typedef typename UniformOf<S>::type SU;
+  series_lev_step<TIO>(a, la, sr, nslice, lds, [&](const SolveArgs& at, int slice, long long oshift) {
+    if constexpr (!std::is_same<S, SU>::value) {
+      if (lds[S_UNIF] != 0.0) {
+        tri_lev_body<SU, TIO, M>(at, la, per, off_ck, lds, slice, oshift);
+        return;
+      }
+    }
+    tri_lev_body<S, TIO, M>(at, la, per, off_ck, lds, slice, oshift);
+  });
 }
 
 // LDS of k_tri_lev in bytes: record | checkpoints [nck][2][nthr]
@@ -768,7 +787,7 @@ inline size_t tri_lev_lds_bytes(const SolveArgs& a, int M, int nthr, int* off_ck
 }
 
 template <class S, typename TIO, int M>
-int launch_lev_m(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
+int launch_lev_m(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
   int wmax = 1024;  // widest slice whose checkpoints fit
   while (wmax >= 64 && tri_lev_lds_bytes<S>(a, M, wmax) > MAX_WG_LDS) wmax >>= 1;
   if (wmax < 64) return CRT_ERR_UNSUPPORTED;
@@ -776,6 +795,22 @@ int launch_lev_m(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
   if (ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
   int off_ck;
   const size_t sh = tri_lev_lds_bytes<S>(a, M, ls.nthr, &off_ck);
+  if (sr) {
+    dim3 grid;
+    if (!lev_series_grid(a.ncol, sr->nt, ls.nslice, &grid)) return CRT_ERR_UNSUPPORTED;
+    if (probe) return CRT_OK;
+    auto gos = [&](auto kern) {
+      const int st = launch_series(kern, grid, ls.nthr, sh, s, a, la, *sr, ls.per, off_ck, ls.nslice);
+      if (st == CRT_OK)
+        note_kernel("k_colpre<canopy> + k_colsun + k_tri_lev_series<%s>%s M=%d nsel=%d slice=%d nt=%d", S::NAME, sizeof(TIO) == 8 ? "" : " f32", M,
+                    la.nsel, ls.per, sr->nt);
+      return st;
+    };
+    return ls.nthr <= 256   ? gos(k_tri_lev_series<S, TIO, M, 256>)
+           : ls.nthr <= 512 ? gos(k_tri_lev_series<S, TIO, M, 512>)
+                            : gos(k_tri_lev_series<S, TIO, M, 1024>);
+  }
+  if (probe) return CRT_OK;
   auto go = [&](auto kern) {
     if (sh > 64 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
@@ -791,9 +826,9 @@ int launch_lev_m(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
 }
 
 template <class S, typename TIO>
-int launch_lev_scheme(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
-  int st = launch_lev_m<S, TIO, 8>(a, la, s);  // M = 16 (half the checkpoints) only where M = 8 does not fit a 64-band slice
-  if (st == CRT_ERR_UNSUPPORTED) st = launch_lev_m<S, TIO, 16>(a, la, s);
+int launch_lev_scheme(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
+  int st = launch_lev_m<S, TIO, 8>(a, la, s, sr, probe);  // M = 16 (half the checkpoints) only where M = 8 does not fit a 64-band slice
+  if (st == CRT_ERR_UNSUPPORTED) st = launch_lev_m<S, TIO, 16>(a, la, s, sr, probe);
   return st;
 }
 

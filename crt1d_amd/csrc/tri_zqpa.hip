@@ -958,18 +958,17 @@ int launch_zqpa_int_io(const SolveArgs& a, const IntArgs& ia, hipStream_t s, con
 // lane's (SWd[k+1], SWu[k]) of a marked row k in its slot, and the interpolation after the sweep applies k_zqpa_interp's expressions
 // to them: the same bits as the profile path.  The slots take LDS in proportion to the marked rows: with many levels selected, the band
 // slices narrow.
-template <typename TIO, int M, int MAXT>
-__global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4))) void k_zqpa_lev(SolveArgs g, LevArgs la, int nzo, int per,
-                                                                                           int off_map, int off_ck, int off_val) {
+//
+// zqpa_lev_body runs on the record in lds[0 .. reclen), which the caller has written but not yet synchronised (the barrier behind the slot
+// initialisation below covers it); oshift (elements, workgroup-uniform) is added to the [column][nsel][nb] output index: 0 in
+// k_zqpa_lev, the offset of slice [column][t] in k_zqpa_lev_series.
+template <typename TIO, int M>
+__device__ __forceinline__ void zqpa_lev_body(const SolveArgs& g, const LevArgs& la, int nzo, int per, int off_map, int off_ck, int off_val,
+                                              double* lds, int slice, long long oshift) {
   typedef TriZq S;
-  extern __shared__ double lds[];
   const int Mg = g.nz, nb = g.nb, nsel = la.nsel;
   const int tid = threadIdx.x, nthr = blockDim.x;
   const int c = blockIdx.x;
-  {
-    const double* src = g.ws + (long long)c * g.reclen;
-    for (int i = tid; i < g.reclen; i += nthr) lds[i] = src[i];
-  }
   int* slot = reinterpret_cast<int*>(lds + off_map);  // [Mg]: slot of grid row k, or -1; slot[Mg]: lowest marked row
   for (int k = tid; k < Mg; k += nthr) slot[k] = -1;
   __syncthreads();
@@ -994,7 +993,7 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4))) void 
     slot[Mg] = lowest;
   }
   __syncthreads();
-  const int b = blockIdx.y * per + tid;
+  const int b = slice * per + tid;
   if (tid >= per || b >= nb) return;  // (no barrier below)
   double* val = lds + off_val + tid;  // [nslot][2][nthr]
   double* ck = lds + off_ck + tid;    // [nck][2][nthr]
@@ -1062,11 +1061,33 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4))) void 
     const double up = ua + (ub - ua) * w;  // :361
     const double idr = bc * ekl[j];        // :354-355
     const double v[4] = {idr, dn, up, idr * invmu + 2 * up + 2 * dn};  // :412
-    const long long oo = ((long long)c * nsel + r) * nb + b;
+    const long long oo = ((long long)c * nsel + r) * nb + b + oshift;
 #pragma unroll
     for (int q = 0; q < 4; ++q)
       if (la.o[q]) __builtin_nontemporal_store((TIO)v[q], outp<TIO>(la.o[q]) + oo);
   }
+}
+
+template <typename TIO, int M, int MAXT>
+__global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4))) void k_zqpa_lev(SolveArgs g, LevArgs la, int nzo, int per,
+                                                                                           int off_map, int off_ck, int off_val) {
+  extern __shared__ double lds[];
+  {
+    const double* src = g.ws + (long long)blockIdx.x * g.reclen;
+    for (int i = threadIdx.x; i < g.reclen; i += blockDim.x) lds[i] = src[i];
+  }
+  zqpa_lev_body<TIO, M>(g, la, nzo, per, off_map, off_ck, off_val, lds, blockIdx.y, 0);
+}
+
+// k_zqpa_lev over a sun-angle series (series_lev_step, crt_internal.hpp): one workgroup per (column, band slice, sun state); the record is
+// assembled from the column's canopy record (interpolation index and weight, tau_i) and the state's sun record, and zqpa_lev_body runs on it.
+template <typename TIO, int M, int MAXT>
+__global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4))) void k_zqpa_lev_series(SolveArgs g, LevArgs la, SeriesArgs sr, int per,
+                                                                                                  int off_map, int off_ck, int off_val, int nslice) {
+  extern __shared__ double lds[];
+  series_lev_step<TIO>(g, la, sr, nslice, lds, [&](const SolveArgs& gt, int slice, long long oshift) {
+    zqpa_lev_body<TIO, M>(gt, la, sr.nz, per, off_map, off_ck, off_val, lds, slice, oshift);
+  });
 }
 
 // LDS of k_zqpa_lev in doubles: record | row slots [Mg + 1] (int) | checkpoints [Mg / M + 1][2][nthr] | kept rows [nslot][2][nthr]
@@ -1086,7 +1107,7 @@ inline ZqPaLevLds zqpa_lev_lds(const SolveArgs& a, int M, int nthr, int nsel) {
 }
 
 template <typename TIO>
-int launch_zqpa_lev_io(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
+int launch_zqpa_lev_io(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
   constexpr int M = 8;
   int wmax = 1024;  // widest slice whose checkpoints and kept rows fit
   while (wmax >= 64 && zqpa_lev_lds(a, M, wmax, la.nsel).bytes > MAX_WG_LDS) wmax >>= 1;
@@ -1098,6 +1119,20 @@ int launch_zqpa_lev_io(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
   SolveArgs g = a;  // computational-grid solve: nz := Mg (the record keeps the caller's nz: passed separately)
   g.nz = Mg;
   for (int i = 0; i < 7; ++i) g.o[i] = nullptr;
+  if (sr) {
+    dim3 grid;
+    if (!lev_series_grid(a.ncol, sr->nt, ls.nslice, &grid)) return CRT_ERR_UNSUPPORTED;
+    if (probe) return CRT_OK;
+    auto gos = [&](auto kern) {
+      const int st = launch_series(kern, grid, ls.nthr, L.bytes, s, g, la, *sr, ls.per, L.off_map, L.off_ck, L.off_val, ls.nslice);
+      if (st == CRT_OK)
+        note_kernel("k_colpre<canopy> + k_colsun + k_zqpa_lev_series<zq_pa>%s M=%d grid=%d nsel=%d slice=%d nt=%d", sizeof(TIO) == 8 ? "" : " f32", M,
+                    Mg, la.nsel, ls.per, sr->nt);
+      return st;
+    };
+    return ls.nthr <= 256 ? gos(k_zqpa_lev_series<TIO, M, 256>) : ls.nthr <= 512 ? gos(k_zqpa_lev_series<TIO, M, 512>) : gos(k_zqpa_lev_series<TIO, M, 1024>);
+  }
+  if (probe) return CRT_OK;
   auto go = [&](auto kern) {
     if (L.bytes > 64 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.bytes) != hipSuccess)
@@ -1114,8 +1149,8 @@ int launch_zqpa_lev_io(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
 
 }  // namespace
 
-int launch_zqpa_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s) {
-  return a.f32 ? launch_zqpa_lev_io<float>(a, la, s) : launch_zqpa_lev_io<double>(a, la, s);
+int launch_zqpa_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
+  return a.f32 ? launch_zqpa_lev_io<float>(a, la, s, sr, probe) : launch_zqpa_lev_io<double>(a, la, s, sr, probe);
 }
 
 int launch_zqpa_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr) {

@@ -396,6 +396,61 @@ int crt_hip_levels_f32(int scheme, const crt_columns* cols, const crt_bands_f32*
                        int32_t nsel, const crt_outputs_f32* out, void* workspace, size_t workspace_bytes, crt_stream_t stream);
 
 /*
+ * Sun-angle series of level spectra: what crt_hip_levels_f64 / _f32 writes, for `nt` sun states of every column in ONE call -- the diurnal
+ * or seasonal course of the spectral albedo I_df_u[nz-1] / I_d[nz-1], of the spectrum transmitted to the ground or of the spectrum at a
+ * sensor height: the per-band terms of compare_ebal (crt1d/diagnostics.py:510-522) per time step of the reference's `update_p(psi=...)` +
+ * `run()` loop.  The product of the two entries above: inputs as crt_hip_integrated_series_f64, levels and outputs as crt_hip_levels_*.
+ *
+ *  - cols->psi, cols->g_at_psi, bands->I_dr0, bands->I_df0 are NOT read and may be NULL.  The sun states come from `sun`, element
+ *    (c, t, b) of I_dr0 / I_df0 at p[c*col_stride + t*nb + b]; col_stride = 0 broadcasts one series over all columns.  The f32 entry takes
+ *    crt_sun_series_f32: float I_dr0 / I_df0 (widened on load, as the spectra of crt_bands_f32); psi and g_at_psi stay double.
+ *  - levels: as crt_hip_levels_f64 (HOST array copied by value, 1 <= nsel <= CRT_MAX_LEVEL_SELECT, strictly ascending, each in [0, nz)).
+ *  - out: I_dr, I_df_d, I_df_u, F, each [ncol][nt][nsel][nb] or NULL; at least one of the four is given; x0, x1, x2 must be NULL.
+ *  - CONTRACT: for every t, slice [:, t] of every output is BITWISE what crt_hip_levels_f64 (resp. _f32) writes for the same columns with
+ *    psi = sun.psi[:, t], g_at_psi = sun.g_at_psi[:, t], I_dr0 = sun.I_dr0[:, t], I_df0 = sun.I_df0[:, t]: all eight schemes, uniform and
+ *    ragged dLAI, CRT_G_TABLE columns; hence, through the contract of crt_hip_levels_*, bitwise a row of the full solve of that step.  The
+ *    series kernels run the per-step level kernels' bodies (same scheme objects, same level walk) on the same records, with the same band
+ *    slices and the same choice of M.
+ *  - what is shared: the column precompute (K0), as in crt_hip_integrated_series_f64 (k_colpre<canopy> once per column, k_colsun once per
+ *    (column, t)).  One workgroup per (column, band slice, t) assembles its record in LDS from the two and runs the per-step body.
+ *  - workspace: [ncol] canopy records and [ncol][nt] sun records, nothing else (zq_pa's level kernel sweeps its grid in LDS), so
+ *    crt_hip_levels_series_workspace_bytes takes no nb.  It is 0 for a bad scheme, non-positive sizes or a size beyond size_t.
+ *    The record layouts of the two series entries COINCIDE (canopy records from the start, the sun records right behind them): a workspace
+ *    filled by crt_hip_integrated_series_f64 for the same scheme, columns, options and sun.psi may be used here with
+ *    CRT_FLAG_SKIP_PRECOMPUTE, and the other way round; crt_hip_series_workspace_bytes is never smaller than this query, so a buffer of that
+ *    size serves both entries.
+ *  - CRT_FLAG_PRECOMPUTE_ONLY fills the workspace (both kinds of record) and launches no level kernel; CRT_FLAG_SKIP_PRECOMPUTE: the
+ *    workspace holds the records of an earlier series call with the same scheme, columns, options and sun.psi (only the spectra changed).
+ *  - any nb (band slices as crt_hip_levels_*).  Shape limits: every (nz, nsel) that crt_hip_levels_* serves with its record in LDS -- n79
+ *    nz <= 1360, zq nz <= 2271, zq_pa nz <= 1487 (64 levels) to 4495 (two levels); a closed-form column (2s, 4s, bl, g77, bf) whose K0
+ *    record exceeds 160 KB (nz > ~10000; bl ~6800) is CRT_ERR_UNSUPPORTED here: the per-step kernel reads such a record from the
+ *    workspace, the series has no assembled record there.  Any nt with ncol * nt < 2^31 and nslice * ceil(nt / 65535) <= 65535 (the grid
+ *    is ncol x min(nt, 65535) x nslice * ceil(nt / 65535)).  Every CRT_ERR_UNSUPPORTED is found before K0 runs: neither outputs nor
+ *    workspace are touched.
+ *  - CRT_ERR_BAD_ARG before any launch: NULL sun, sun->psi, I_dr0 or I_df0; nt < 1; col_stride neither 0 nor >= nt * nb; g_at_psi NULL
+ *    while cols->g_table is given; bad, unsorted or duplicate levels; all four outputs NULL; a non-NULL extra output; an out-of-range tune
+ *    value; everything else crt_hip_levels_* rejects.  CRT_ERR_WORKSPACE below crt_hip_levels_series_workspace_bytes.
+ *  - capturable into a hipGraph after the first call per device; crt_hip_last_kernel names the K0 forms and the series level kernel
+ *    (k_lev_series<...>, k_tri_lev_series<...>, k_zqpa_lev_series<...>).
+ */
+typedef struct crt_sun_series_f32 {
+  int32_t nt;               /* sun states per column, >= 1 */
+  const double* psi;        /* [ncol][nt] solar zenith angle, radians */
+  const double* g_at_psi;   /* [ncol][nt] G(psi[c][t]); read for CRT_G_TABLE columns only (else may be NULL) */
+  int64_t col_stride;       /* of I_dr0 / I_df0: nt*nb (or larger) per column, 0 = one series for every column */
+  const float* I_dr0;       /* element (c, t, b) at p[c*col_stride + t*nb + b] */
+  const float* I_df0;
+} crt_sun_series_f32;
+
+size_t crt_hip_levels_series_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nt);
+int crt_hip_levels_series_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_sun_series* sun, const crt_options* opts,
+                              const int32_t* levels, int32_t nsel, const crt_outputs* out, void* workspace, size_t workspace_bytes,
+                              crt_stream_t stream);
+int crt_hip_levels_series_f32(int scheme, const crt_columns* cols, const crt_bands_f32* bands, const crt_sun_series_f32* sun,
+                              const crt_options* opts, const int32_t* levels, int32_t nsel, const crt_outputs_f32* out, void* workspace,
+                              size_t workspace_bytes, crt_stream_t stream);
+
+/*
  * diagnostics.band's reduction for ANY variable with a trailing wavelength axis (diagnostics.py:81, `(da * w).sum(dim="wl")`):
  * out[row][g] = sum_b band_w[g][b] X[row][b], X = [nrow][nb], band_w = [ngroup <= 4][nb], out = [nrow][ngroup].  Used by
  * crt1d_amd.diagnostics.band for the variables of a single Model's dataset (incl. the schemes' own aI_*_scheme outputs); the batched
