@@ -149,65 +149,59 @@ class CrtBandsumOut(ctypes.Structure):
 ABI_VERSION = 3
 
 
-EXPORTS = [
-    "crt_hip_abi_version",
-    "crt_hip_strerror",
-    "crt_hip_workspace_bytes",
-    "crt_hip_workspace_bytes_nb",
-    "crt_hip_quad_nodes",
-    "crt_hip_solve_f64",
-    "crt_hip_2s_f64",
-    "crt_hip_4s_f64",
-    "crt_hip_n79_f64",
-    "crt_hip_zq_f64",
-    "crt_hip_bl_f64",
-    "crt_hip_g77_f64",
-    "crt_hip_bf_f64",
-    "crt_hip_zq_pa_f64",
-    "crt_hip_solve_f32",
-    "crt_hip_2s_f32",
-    "crt_hip_4s_f32",
-    "crt_hip_n79_f32",
-    "crt_hip_zq_f32",
-    "crt_hip_bl_f32",
-    "crt_hip_g77_f32",
-    "crt_hip_bf_f32",
-    "crt_hip_zq_pa_f32",
-    "crt_hip_absorb_bandsum_f64",
-    "crt_hip_absorb_bandsum2_f64",
-    "crt_hip_integrated_f64",
-    "crt_hip_integrated2_f64",
-    "crt_hip_absorb_f64",
-    "crt_hip_absorb_bandsum_f32",
-    "crt_hip_absorb_bandsum2_f32",
-    "crt_hip_integrated_f32",
-    "crt_hip_integrated2_f32",
-    "crt_hip_series_workspace_bytes",
-    "crt_hip_integrated_series_f64",
-    "crt_hip_levels_f64",
-    "crt_hip_levels_f32",
-    "crt_hip_levels_series_workspace_bytes",
-    "crt_hip_levels_series_f64",
-    "crt_hip_levels_series_f32",
-    "crt_hip_absorb_f32",
-    "crt_hip_bandsum_finish_f64",
-    "crt_hip_band_reduce_f64",
-    "crt_hip_tau_d_f64",
-    "crt_hip_smear_tuv_f64",
-    "crt_hip_lai_beta_f64",
-    "crt_hip_buffer_alloc_set",
-    "crt_hip_buffer_alloc",
-    "crt_hip_buffer_free",
-    "crt_hip_buffer_trim",
-    "crt_hip_buffer_set_retain",
-    "crt_hip_buffer_describe",
-    "crt_hip_buffer_stats",
-    "crt_hip_last_kernel",
-    "crt_hip_probe_fill_f64",
-    "crt_hip_probe_copy_f64",
-    "crt_hip_probe_store_set_f64",
-    "crt_hip_probe_math_f64",
-]
+def _signatures():
+    """``name -> (restype, argtypes)`` of every symbol of the C ABI (include/crt1d_hip.h): the one table :func:`load` applies and
+    ``EXPORTS`` lists.  The f32 structs share the layouts of the f64 ones, so both storage types of an entry take the same ``argtypes``
+    (except the sun series, whose two struct types are kept apart).  ``argtypes`` ``None``: left unset."""
+    P = ctypes.POINTER
+    i, i32, i64, sz, dbl, ok = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_double, ctypes.c_int
+    cols, bands, opts, outs, sums = P(CrtColumns), P(CrtBands), P(CrtOptions), P(CrtOutputs), P(CrtBandsumOut)
+    solve = [cols, bands, opts, outs, _vp, sz, _vp]
+    t = {
+        "crt_hip_abi_version": (i, None),
+        "crt_hip_strerror": (ctypes.c_char_p, [i]),
+        "crt_hip_workspace_bytes": (sz, [i, i32, i32]),
+        "crt_hip_workspace_bytes_nb": (sz, [i, i32, i32, i32]),
+        "crt_hip_series_workspace_bytes": (sz, [i, i32, i32, i32, i32]),
+        "crt_hip_levels_series_workspace_bytes": (sz, [i, i32, i32, i32]),
+        "crt_hip_quad_nodes": (ok, [dbl, P(dbl)]),
+        "crt_hip_integrated_series_f64": (ok, [i, cols, bands, P(CrtSunSeries), opts, _vp, i32, sums, _vp, sz, _vp]),
+    }
+    for suffix, sun_t in (("f64", CrtSunSeries), ("f32", CrtSunSeriesF32)):
+        t[f"crt_hip_solve_{suffix}"] = (ok, [i] + solve)
+        for s in SCHEME_IDS if suffix == "f64" else F32_SCHEMES:
+            t[f"crt_hip_{s}_{suffix}"] = (ok, solve)
+        t[f"crt_hip_absorb_{suffix}"] = (ok, [cols, bands, _vp, _vp, _vp, P(_vp), _vp, _vp, _vp])
+        t[f"crt_hip_absorb_bandsum_{suffix}"] = (ok, [cols, bands, _vp, _vp, _vp, _vp, i32, _vp, _vp, _vp, _vp, _vp])
+        t[f"crt_hip_absorb_bandsum2_{suffix}"] = (ok, [cols, bands, _vp, _vp, _vp, _vp, i32, sums, _vp])
+        t[f"crt_hip_integrated_{suffix}"] = (ok, [i, cols, bands, opts, _vp, i32, _vp, _vp, _vp, _vp, _vp, sz, _vp])
+        t[f"crt_hip_integrated2_{suffix}"] = (ok, [i, cols, bands, opts, _vp, i32, sums, _vp, sz, _vp])
+        t[f"crt_hip_levels_{suffix}"] = (ok, [i, cols, bands, opts, P(i32), i32, outs, _vp, sz, _vp])
+        t[f"crt_hip_levels_series_{suffix}"] = (ok, [i, cols, bands, P(sun_t), opts, P(i32), i32, outs, _vp, sz, _vp])
+    t.update({
+        "crt_hip_bandsum_finish_f64": (ok, [cols, i32, sums, _vp]),
+        "crt_hip_band_reduce_f64": (ok, [_vp, i64, i32, _vp, i32, _vp, _vp]),
+        "crt_hip_tau_d_f64": (ok, [_vp, _vp, i64, i32, _vp, _vp]),
+        "crt_hip_smear_tuv_f64": (ok, [_vp, i64, i32, _vp, i32, _vp, i32, _vp, _vp]),
+        "crt_hip_lai_beta_f64": (ok, [_vp, _vp, _vp, i32, i32, _vp, _vp, _vp, _vp]),
+        "crt_hip_buffer_alloc_set": (ok, [i32, P(sz), P(_vp)]),
+        "crt_hip_buffer_alloc": (ok, [sz, P(_vp)]),
+        "crt_hip_buffer_free": (ok, [_vp]),
+        "crt_hip_buffer_trim": (ok, []),
+        "crt_hip_buffer_set_retain": (ok, [sz]),
+        "crt_hip_buffer_describe": (ok, [_vp, ctypes.c_char_p, sz]),
+        "crt_hip_buffer_stats": (ok, [P(i64)]),
+        "crt_hip_last_kernel": (ctypes.c_char_p, []),
+        "crt_hip_probe_fill_f64": (ok, [_vp, sz, dbl, _vp]),
+        "crt_hip_probe_copy_f64": (ok, [_vp, _vp, sz, _vp]),
+        "crt_hip_probe_store_set_f64": (ok, [P(_vp), i32, i64, i64, i32, dbl, _vp]),
+        "crt_hip_probe_math_f64": (ok, [_vp, sz, _vp, _vp, _vp, _vp]),
+    })
+    return t
+
+
+_SIGNATURES = _signatures()
+EXPORTS = list(_SIGNATURES)
 
 _lib = None
 
@@ -231,116 +225,11 @@ def load():
     import torch  # noqa: F401
 
     lib = ctypes.CDLL(LIB_PATH)
-    lib.crt_hip_abi_version.restype = ctypes.c_int
-    lib.crt_hip_strerror.restype = ctypes.c_char_p
-    lib.crt_hip_strerror.argtypes = [ctypes.c_int]
-    lib.crt_hip_workspace_bytes.restype = ctypes.c_size_t
-    lib.crt_hip_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32]
-    lib.crt_hip_workspace_bytes_nb.restype = ctypes.c_size_t
-    lib.crt_hip_workspace_bytes_nb.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
-    lib.crt_hip_quad_nodes.restype = ctypes.c_int
-    lib.crt_hip_quad_nodes.argtypes = [ctypes.c_double, ctypes.POINTER(ctypes.c_double)]
-    solve_args = [
-        ctypes.POINTER(CrtColumns),
-        ctypes.POINTER(CrtBands),
-        ctypes.POINTER(CrtOptions),
-        ctypes.POINTER(CrtOutputs),
-        _vp,
-        ctypes.c_size_t,
-        _vp,
-    ]
-    lib.crt_hip_solve_f64.restype = ctypes.c_int
-    lib.crt_hip_solve_f64.argtypes = [ctypes.c_int] + solve_args
-    lib.crt_hip_solve_f32.restype = ctypes.c_int
-    lib.crt_hip_solve_f32.argtypes = [ctypes.c_int] + solve_args
-    for s in SCHEME_IDS:
-        for suffix in ("f64", "f32"):  # the f32 structs share the f64 layout (include/crt1d_hip.h)
-            if suffix == "f32" and s not in F32_SCHEMES:
-                continue
-            f = getattr(lib, f"crt_hip_{s}_{suffix}")
-            f.restype = ctypes.c_int
-            f.argtypes = solve_args
-    for suffix in ("f64", "f32"):  # the epilogue and integrated entries of both storage types (crt_bands_f32 shares the layout)
-        f = getattr(lib, f"crt_hip_absorb_bandsum_{suffix}")
-        f.restype = ctypes.c_int
-        f.argtypes = [ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]
-        f = getattr(lib, f"crt_hip_integrated_{suffix}")
-        f.restype = ctypes.c_int
-        f.argtypes = [
-            ctypes.c_int, ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), ctypes.POINTER(CrtOptions), _vp, ctypes.c_int32,
-            _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp,
-        ]
-        f = getattr(lib, f"crt_hip_absorb_bandsum2_{suffix}")
-        f.restype = ctypes.c_int
-        f.argtypes = [
-            ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.POINTER(CrtBandsumOut), _vp,
-        ]
-        f = getattr(lib, f"crt_hip_integrated2_{suffix}")
-        f.restype = ctypes.c_int
-        f.argtypes = [
-            ctypes.c_int, ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), ctypes.POINTER(CrtOptions), _vp, ctypes.c_int32,
-            ctypes.POINTER(CrtBandsumOut), _vp, ctypes.c_size_t, _vp,
-        ]
-        f = getattr(lib, f"crt_hip_absorb_{suffix}")
-        f.restype = ctypes.c_int
-        f.argtypes = [ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), _vp, _vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _vp]
-    for suffix in ("f64", "f32"):  # level-subset solve (crt_bands_f32 / crt_outputs_f32 share the f64 layouts)
-        f = getattr(lib, f"crt_hip_levels_{suffix}")
-        f.restype = ctypes.c_int
-        f.argtypes = [
-            ctypes.c_int, ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), ctypes.POINTER(CrtOptions), ctypes.POINTER(ctypes.c_int32),
-            ctypes.c_int32, ctypes.POINTER(CrtOutputs), _vp, ctypes.c_size_t, _vp,
-        ]
-    lib.crt_hip_series_workspace_bytes.restype = ctypes.c_size_t
-    lib.crt_hip_series_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
-    lib.crt_hip_integrated_series_f64.restype = ctypes.c_int
-    lib.crt_hip_integrated_series_f64.argtypes = [
-        ctypes.c_int, ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), ctypes.POINTER(CrtSunSeries), ctypes.POINTER(CrtOptions), _vp,
-        ctypes.c_int32, ctypes.POINTER(CrtBandsumOut), _vp, ctypes.c_size_t, _vp,
-    ]
-    lib.crt_hip_levels_series_workspace_bytes.restype = ctypes.c_size_t
-    lib.crt_hip_levels_series_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
-    for suffix, sun_t in (("f64", CrtSunSeries), ("f32", CrtSunSeriesF32)):  # level spectra over a sun-angle series
-        f = getattr(lib, f"crt_hip_levels_series_{suffix}")
-        f.restype = ctypes.c_int
-        f.argtypes = [
-            ctypes.c_int, ctypes.POINTER(CrtColumns), ctypes.POINTER(CrtBands), ctypes.POINTER(sun_t), ctypes.POINTER(CrtOptions),
-            ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(CrtOutputs), _vp, ctypes.c_size_t, _vp,
-        ]
-    lib.crt_hip_bandsum_finish_f64.restype = ctypes.c_int
-    lib.crt_hip_bandsum_finish_f64.argtypes = [ctypes.POINTER(CrtColumns), ctypes.c_int32, ctypes.POINTER(CrtBandsumOut), _vp]
-    lib.crt_hip_band_reduce_f64.restype = ctypes.c_int
-    lib.crt_hip_band_reduce_f64.argtypes = [_vp, ctypes.c_int64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp]
-    lib.crt_hip_tau_d_f64.restype = ctypes.c_int
-    lib.crt_hip_tau_d_f64.argtypes = [_vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp, _vp]
-    lib.crt_hip_smear_tuv_f64.restype = ctypes.c_int
-    lib.crt_hip_smear_tuv_f64.argtypes = [_vp, ctypes.c_int64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp]
-    lib.crt_hip_lai_beta_f64.restype = ctypes.c_int
-    lib.crt_hip_lai_beta_f64.argtypes = [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp]
-    lib.crt_hip_buffer_alloc.restype = ctypes.c_int
-    lib.crt_hip_buffer_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
-    lib.crt_hip_buffer_free.restype = ctypes.c_int
-    lib.crt_hip_buffer_free.argtypes = [ctypes.c_void_p]
-    lib.crt_hip_buffer_alloc_set.restype = ctypes.c_int
-    lib.crt_hip_buffer_alloc_set.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_void_p)]
-    lib.crt_hip_buffer_trim.restype = ctypes.c_int
-    lib.crt_hip_buffer_trim.argtypes = []
-    lib.crt_hip_buffer_set_retain.restype = ctypes.c_int
-    lib.crt_hip_buffer_set_retain.argtypes = [ctypes.c_size_t]
-    lib.crt_hip_buffer_describe.restype = ctypes.c_int
-    lib.crt_hip_buffer_describe.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
-    lib.crt_hip_buffer_stats.restype = ctypes.c_int
-    lib.crt_hip_buffer_stats.argtypes = [ctypes.POINTER(ctypes.c_int64)]
-    lib.crt_hip_last_kernel.restype = ctypes.c_char_p
-    lib.crt_hip_last_kernel.argtypes = []
-    lib.crt_hip_probe_fill_f64.restype = ctypes.c_int
-    lib.crt_hip_probe_fill_f64.argtypes = [_vp, ctypes.c_size_t, ctypes.c_double, _vp]
-    lib.crt_hip_probe_copy_f64.restype = ctypes.c_int
-    lib.crt_hip_probe_copy_f64.argtypes = [_vp, _vp, ctypes.c_size_t, _vp]
-    lib.crt_hip_probe_math_f64.restype = ctypes.c_int
-    lib.crt_hip_probe_math_f64.argtypes = [_vp, ctypes.c_size_t, _vp, _vp, _vp, _vp]
-    lib.crt_hip_probe_store_set_f64.restype = ctypes.c_int
-    lib.crt_hip_probe_store_set_f64.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, _vp]
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        f = getattr(lib, name)
+        f.restype = restype
+        if argtypes is not None:
+            f.argtypes = argtypes
     if lib.crt_hip_abi_version() != ABI_VERSION:
         raise HipLibraryMissing(f"{LIB_PATH}: ABI version mismatch, rebuild")
     _lib = lib

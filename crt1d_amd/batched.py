@@ -35,25 +35,34 @@ OUT_KEYS = {
 _MID_KEYS = {"n79": ("aI_lsl", "aI_lsh")}  # (ncol, nz-1, nb)
 
 
-def _f64(t, name):
+def _tensor(t, name, dtypes):
+    """A tensor the kernels read through a bare pointer: a contiguous CUDA tensor whose dtype is one of ``dtypes``."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
-    if t.dtype != torch.float64:
-        raise TypeError(f"{name} must be float64, got {t.dtype}")
+    if t.dtype not in dtypes:
+        raise TypeError(f"{name} must be {' or '.join(str(d)[len('torch.'):] for d in dtypes)}, got {t.dtype}")
     if not t.is_cuda:
         raise ValueError(f"{name} must live on the GPU (got {t.device}); crt1d_amd has no CPU path")
     return t.contiguous()
+
+
+def _f64(t, name):
+    return _tensor(t, name, (torch.float64,))
+
+
+def _f32(t, name):
+    return _tensor(t, name, (torch.float32,))
 
 
 def _fio(t, name):
     """Spectra may be float64 (crt_hip_*_f64) or float32 (crt_hip_*_f32: half the HBM bytes, fp64 arithmetic)."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if t.dtype not in (torch.float64, torch.float32):
-        raise TypeError(f"{name} must be float64 or float32, got {t.dtype}")
-    if not t.is_cuda:
-        raise ValueError(f"{name} must live on the GPU (got {t.device}); crt1d_amd has no CPU path")
-    return t.contiguous()
+    return _tensor(t, name, (torch.float64, torch.float32))
+
+
+def _host_reader(d, device):
+    """``k -> d[k]`` as a tensor on ``device``, ``None`` for an entry that is missing or ``None``: what the ``from_host`` constructors read
+    a dict of NumPy arrays with."""
+    return lambda k: None if d.get(k) is None else torch.as_tensor(d[k]).to(device)
 
 
 def _check_profile(t, name, shape, device, dtype=torch.float64):
@@ -158,7 +167,7 @@ class Columns:
     @classmethod
     def from_host(cls, d, device="cuda"):
         """From a dict of NumPy arrays (e.g. :func:`crt1d_amd.synth.make_columns`)."""
-        t = lambda k: None if d.get(k) is None else torch.as_tensor(d[k]).to(device)  # noqa: E731
+        t = _host_reader(d, device)
         return cls(t("psi"), t("lai"), t("g_kind"), t("g_param"), t("mla"), t("g_at_psi"), t("g_table"))
 
 
@@ -225,7 +234,7 @@ class Bands:
 
     @classmethod
     def from_host(cls, d, device="cuda"):
-        t = lambda k: None if d.get(k) is None else torch.as_tensor(d[k]).to(device)  # noqa: E731
+        t = _host_reader(d, device)
         return cls(t("I_dr0"), t("I_df0"), t("leaf_r"), t("leaf_t"), t("soil_r"))
 
 
@@ -244,6 +253,30 @@ def _check_workspace(workspace, need, device):
     if not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
         raise ValueError(f"workspace too small or not contiguous (need {need} bytes)")
     return workspace
+
+
+def _outputs(shapes, out, dtype, device, label="out[{!r}]", lacks=False):
+    """The output arrays ``{key: shape}``: allocated when ``out`` is ``None``, else the caller's ``out`` with every array checked.
+    ``lacks``: a missing key is a ValueError (not a KeyError)."""
+    if out is None:
+        return {k: torch.empty(sh, dtype=dtype, device=device) for k, sh in shapes.items()}
+    for k, sh in shapes.items():
+        if lacks and k not in out:
+            raise ValueError(f"`out` lacks {k!r}")
+        _check_profile(out[k], label.format(k), sh, device, dtype)
+    return out
+
+
+def _band_weights(band_w, nb, device):
+    """Band weights ``(nb,)`` or ``(ngroup <= 4, nb)`` as the ``(ngroup, nb)`` float64 tensor on ``device`` the kernels read."""
+    band_w = _f64(band_w, "band_w")
+    if band_w.ndim == 1:
+        band_w = band_w[None, :]
+    if band_w.shape[1] != nb or not 1 <= band_w.shape[0] <= 4:
+        raise ValueError("band_w must be (ngroup <= 4, nb)")
+    if band_w.device != device:
+        raise ValueError(f"band_w lives on {band_w.device} but the columns on {device}")
+    return band_w
 
 
 def workspace_bytes(scheme, ncol, nz, nb=1):
@@ -372,9 +405,80 @@ def alloc_outputs(scheme, ncol, nz, nb, device, dtype=torch.float64, placed=Fals
         return {k: torch.empty(s, dtype=dtype, device=device) for k, s in shapes.items()}
 
 
-class Plan:
+class _SolvePlan:
+    """What the solve plans share: the checks of scheme, method, geometry and spectra, the argument structs of the C entry, the
+    workspace, and the call.  A subclass's ``__init__`` runs ``_check_options`` (and its own checks that need no column) first, then
+    ``_bind``, builds ``out`` / ``_out``, and ends with ``_finish``; ``_tail`` gives the entry's arguments between the options and the
+    workspace."""
+
+    _bad_scheme = "unknown scheme {!r}; valid: " + ", ".join(SCHEMES)
+    _scheme_arg = True  # the entry takes the scheme id first (Plan's per-scheme entries do not)
+    _f32_series = False  # a sun series with float32 spectra is served (LevelsSeriesPlan)
+    _s = None  # crt_sun_series of the series plans
+
+    def _check_options(self, scheme, tau_d_method):
+        if scheme not in _lib.SCHEME_IDS:
+            raise ValueError(self._bad_scheme.format(scheme))
+        if tau_d_method not in _lib.TAU_D_METHODS:
+            raise ValueError("invalid `method`. Valid options are 'quad' and '9sky'.")  # common.py:78
+
+    def _bind(self, scheme, cols, bands, mu_s, tau_d_method, sun=None, tune=None):
+        """Check the columns and spectra (for a series: against ``sun``) and build the structs ``_c``, ``_b``, ``_s``, ``_o``."""
+        self.lib = _lib.load()
+        self.scheme, self.cols, self.bands = scheme, cols, bands
+        if scheme == "2s" and cols.mla is None:
+            raise ValueError("solve_2s needs `mla`")
+        if scheme != "bl" and bands.soil_r is None:
+            raise ValueError(f"solve_{scheme} needs `soil_r`")
+        if sun is None:
+            cols.check_tables()
+        else:
+            self.sun = sun
+            _check_sun(cols, bands, sun, self._f32_series)
+            self._s = sun.c_struct()
+        _check_band_device(bands, cols.device)
+        self._c, self._b = cols.c_struct(), bands.c_struct(cols.ncol)
+        self._o = _lib.CrtOptions(float(mu_s), _lib.TAU_D_METHODS[tau_d_method], 0)
+        self.set_tune(tune or {})
+
+    def _finish(self, entry, need, workspace):
+        self.workspace = _check_workspace(workspace, need, self.cols.device)
+        self._wsb = self.workspace.numel() * self.workspace.element_size()
+        self._entry = entry
+        self._fn = getattr(self.lib, entry)
+
+    def set_tune(self, tune):
+        """Measurement aid: per-plan overrides of the kernel-selection heuristics (``crt_options.tune``; keys ``_lib.TUNE_*``,
+        documented in include/crt1d_hip.h).  ``{}`` = automatic.  They travel with every call of this plan -- no process-global state."""
+        _lib.set_tune(self._o, tune)
+        return self
+
+    def last_kernel(self):
+        """Name / configuration of the kernel(s) this thread's most recent call launched (``crt_hip_last_kernel``)."""
+        return self.lib.crt_hip_last_kernel().decode()
+
+    def __call__(self, stream=None, *, flags=0):
+        """Enqueue on ``stream`` (default: torch's current stream).  ``flags``: ``_lib.FLAG_SKIP_PRECOMPUTE`` reuses
+        the column records already in the workspace (same geometry, new spectra); ``_lib.FLAG_PRECOMPUTE_ONLY``
+        runs only the column precompute."""
+        dev = self.cols.device
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        self._o.flags = int(flags)
+        c, b, o = ctypes.byref(self._c), ctypes.byref(self._b), ctypes.byref(self._o)
+        head = (c, b, o) if self._s is None else (c, b, ctypes.byref(self._s), o)
+        if self._scheme_arg:
+            head = (_lib.SCHEME_IDS[self.scheme],) + head
+        with torch.cuda.device(dev):  # the launch goes to the CURRENT device: make it the one the buffers live on
+            st = self._fn(*head, *self._tail(), self.workspace.data_ptr(), self._wsb, s.cuda_stream)
+        _lib.check(st, self._entry)
+        return self.out
+
+
+class Plan(_SolvePlan):
     """Pre-validated launch of one scheme on fixed buffers: ``plan()`` enqueues K0 + the solve kernel
     on the current stream with no allocation and no host synchronisation (bench / steady-state use)."""
+
+    _scheme_arg = False
 
     def __init__(self, scheme, cols: Columns, bands: Bands, *, mu_s=0.501, tau_d_method="quad", out=None, workspace=None,
                  placement="auto", tune=None):
@@ -385,57 +489,27 @@ class Plan:
         ``out``: caller-owned output arrays (contiguous, of the bands' dtype), at any element offset.  One exception: zq_pa with
         float32 storage needs every output array to start on an 8-byte boundary (its kernels store band pairs and it has no
         other path in f32); a float32 array that starts at an odd element of an aligned allocation is a ValueError."""
-        if scheme not in _lib.SCHEME_IDS:
-            raise ValueError(f"unknown scheme {scheme!r}; valid: {', '.join(SCHEMES)}")
-        if tau_d_method not in _lib.TAU_D_METHODS:
-            raise ValueError("invalid `method`. Valid options are 'quad' and '9sky'.")  # common.py:78
-        self.lib = _lib.load()
-        self.scheme = scheme
-        self.cols, self.bands = cols, bands
+        self._check_options(scheme, tau_d_method)
+        self._bind(scheme, cols, bands, mu_s, tau_d_method, tune=tune)
         ncol, nz, nb = cols.ncol, cols.nz, bands.nb
-        if scheme == "2s" and cols.mla is None:
-            raise ValueError("solve_2s needs `mla`")
-        if scheme != "bl" and bands.soil_r is None:
-            raise ValueError(f"solve_{scheme} needs `soil_r`")
-        cols.check_tables()
-        _check_band_device(bands, cols.device)
         if placement not in ("auto", "none"):
             raise ValueError("placement must be 'auto' or 'none'")
-        placed = placement == "auto" and os.environ.get("CRT1D_PLACEMENT", "auto") != "none"
-        self.out = alloc_outputs(scheme, ncol, nz, nb, cols.device, bands.dtype, placed=placed) if out is None else out
-        for k in OUT_KEYS[scheme]:
-            if k not in self.out:
-                raise ValueError(f"`out` lacks {k!r}")
-            rows = nz - 1 if k in _MID_KEYS.get(scheme, ()) else nz
-            _check_profile(self.out[k], f"output {k!r}", (ncol, rows, nb), cols.device, bands.dtype)
-            if scheme == "zq_pa" and bands.dtype == torch.float32 and self.out[k].data_ptr() % 8:
-                raise ValueError(f"output {k!r}: zq_pa with float32 storage needs output arrays that start on an 8-byte boundary")
-        need = workspace_bytes(scheme, ncol, nz, nb)
-        workspace = _check_workspace(workspace, need, cols.device)
-        self.workspace = workspace
-        self._c = cols.c_struct()
-        self._b = bands.c_struct(ncol)
-        self._o = _lib.CrtOptions(float(mu_s), _lib.TAU_D_METHODS[tau_d_method], 0)
-        self.set_tune(tune or {})
+        if out is None:
+            placed = placement == "auto" and os.environ.get("CRT1D_PLACEMENT", "auto") != "none"
+            out = alloc_outputs(scheme, ncol, nz, nb, cols.device, bands.dtype, placed=placed)
+        shapes = {k: (ncol, nz - 1 if k in _MID_KEYS.get(scheme, ()) else nz, nb) for k in OUT_KEYS[scheme]}
+        _outputs(shapes, out, bands.dtype, cols.device, "output {!r}", lacks=True)
+        if scheme == "zq_pa" and bands.dtype == torch.float32:
+            for k in shapes:
+                if out[k].data_ptr() % 8:
+                    raise ValueError(f"output {k!r}: zq_pa with float32 storage needs output arrays that start on an 8-byte boundary")
         if bands.dtype == torch.float32 and scheme not in _lib.F32_SCHEMES:
             raise TypeError(f"scheme {scheme!r} has no f32 storage variant yet")
-        self._entry = f"crt_hip_{scheme}_{'f32' if bands.dtype == torch.float32 else 'f64'}"
-        self._fn = getattr(self.lib, self._entry)
-        self._wsb = workspace.numel() * workspace.element_size()
-        self._point_at(self.out)
+        self._point_at(out)
+        self._finish(f"crt_hip_{scheme}_{_io_suffix(bands)}", workspace_bytes(scheme, ncol, nz, nb), workspace)
         # where the output arrays live: memory-class letters per 512 MB chunk for arrays from the set allocator (None = torch memory)
         cls = {k: buffer_classes(v) for k, v in self.out.items()}
         self.placement_report = {"allocator": "crt_hip_buffer_alloc_set", "classes": cls} if any(cls.values()) else None
-
-    def set_tune(self, tune):
-        """Measurement aid: per-plan overrides of the kernel-selection heuristics (``crt_options.tune``; keys ``_lib.TUNE_*``,
-        documented in include/crt1d_hip.h).  ``{}`` = automatic.  They travel with every call of this plan -- no process-global state."""
-        _lib.set_tune(self._o, tune)
-        return self
-
-    def last_kernel(self):
-        """Name / configuration of the solve kernel this thread's most recent call launched (``crt_hip_last_kernel``)."""
-        return self.lib.crt_hip_last_kernel().decode()
 
     def _point_at(self, out):
         self.out = out
@@ -443,18 +517,8 @@ class Plan:
         ptrs += [None] * (7 - len(ptrs))
         self._out = _lib.CrtOutputs(*ptrs)
 
-    def __call__(self, stream=None, *, flags=0):
-        """Enqueue on ``stream`` (default: torch's current stream).  ``flags``: ``_lib.FLAG_SKIP_PRECOMPUTE`` reuses
-        the column records already in the workspace (same geometry, new spectra); ``_lib.FLAG_PRECOMPUTE_ONLY``
-        runs only the column precompute."""
-        dev = self.cols.device
-        s = torch.cuda.current_stream(dev) if stream is None else stream
-        self._o.flags = int(flags)
-        with torch.cuda.device(dev):  # the launch goes to the CURRENT device: make it the one the buffers live on
-            st = self._fn(ctypes.byref(self._c), ctypes.byref(self._b), ctypes.byref(self._o), ctypes.byref(self._out),
-                          self.workspace.data_ptr(), self._wsb, s.cuda_stream)
-        _lib.check(st, self._entry)
-        return self.out
+    def _tail(self):
+        return (ctypes.byref(self._out),)
 
 
 def solve(scheme, cols: Columns, bands: Bands, *, mu_s=0.501, tau_d_method="quad", out=None, workspace=None, placement="none"):
@@ -527,20 +591,11 @@ class BandSumPlan:
 
     def __init__(self, cols: Columns, bands: Bands, sol, band_w, out=None, profiles=False):
         self.lib = _lib.load()
-        band_w = _f64(band_w, "band_w")
-        if band_w.ndim == 1:
-            band_w = band_w[None, :]
-        ng = band_w.shape[0]
         ncol, nz, dev = cols.ncol, cols.nz, cols.device
+        band_w = _band_weights(band_w, bands.nb, dev)
+        ng = band_w.shape[0]
         _check_epilogue_inputs(cols, bands, sol)
-        if band_w.shape[1] != bands.nb or not 1 <= ng <= 4 or band_w.device != dev:
-            raise ValueError(f"band_w must be (ngroup <= 4, nb = {bands.nb}) on {dev}")
-        shapes = bandsum_shapes(ncol, nz, ng, profiles)
-        if out is None:
-            out = {k: torch.empty(sh, dtype=torch.float64, device=dev) for k, sh in shapes.items()}
-        else:
-            for k, sh in shapes.items():
-                _check_profile(out[k], f"out[{k!r}]", sh, dev)
+        out = _outputs(bandsum_shapes(ncol, nz, ng, profiles), out, torch.float64, dev)
         self.cols, self.bands, self.sol, self.band_w, self.out, self.ng, self.profiles = cols, bands, sol, band_w, out, ng, profiles
         self._c, self._b = cols.c_struct(), bands.c_struct(ncol)
         self._o = _bandsum_out_struct(out, profiles)
@@ -631,65 +686,31 @@ def absorb(cols: Columns, bands: Bands, sol):
     return out
 
 
-class IntegratedPlan:
+class IntegratedPlan(_SolvePlan):
     """Fused solve + absorption + band integrals (``crt_hip_integrated2_f64``, or ``_f32`` for float32 bands): no profile ever
     reaches HBM.  Outputs as :func:`absorb_bandsum`: ``aI, aI_sl, aI_sh (ncol, nz-1, ngroup)``, ``totals (ncol, ngroup, 4)``; float64
     for both storage types."""
 
+    _bad_scheme = "scheme {!r} has no integrated kernel"
+
     def __init__(self, scheme, cols: Columns, bands: Bands, band_w, *, mu_s=0.501, tau_d_method="quad", workspace=None, out=None,
                  profiles=False):
-        if scheme not in _lib.SCHEME_IDS:
-            raise ValueError(f"scheme {scheme!r} has no integrated kernel")
-        if tau_d_method not in _lib.TAU_D_METHODS:
-            raise ValueError("invalid `method`. Valid options are 'quad' and '9sky'.")
-        self.lib = _lib.load()
-        self.scheme, self.cols, self.bands = scheme, cols, bands
-        band_w = _f64(band_w, "band_w")
-        if band_w.ndim == 1:
-            band_w = band_w[None, :]
-        if band_w.shape[1] != bands.nb or not 1 <= band_w.shape[0] <= 4:
-            raise ValueError("band_w must be (ngroup <= 4, nb)")
-        self.band_w = band_w
-        ncol, nz, ng, dev = cols.ncol, cols.nz, band_w.shape[0], cols.device
-        shapes = bandsum_shapes(ncol, nz, ng, profiles)
-        if out is None:
-            out = {k: torch.empty(sh, dtype=torch.float64, device=dev) for k, sh in shapes.items()}
-        else:
-            for k, sh in shapes.items():
-                _check_profile(out[k], f"out[{k!r}]", sh, dev)
-        self.out = out
+        self._check_options(scheme, tau_d_method)
+        self._bind_sums(scheme, cols, bands, band_w, mu_s, tau_d_method, out, profiles)
+        self._finish(f"crt_hip_integrated2_{_io_suffix(bands)}", workspace_bytes(scheme, cols.ncol, cols.nz, bands.nb), workspace)
+
+    def _bind_sums(self, scheme, cols, bands, band_w, mu_s, tau_d_method, out, profiles, sun=None):
+        """``_bind`` + the band weights and the band-sum outputs (with ``sun``: of every sun state)."""
+        self.band_w = _band_weights(band_w, bands.nb, cols.device)
+        self._bind(scheme, cols, bands, mu_s, tau_d_method, sun=sun)
+        ncol, nz, ng = cols.ncol, cols.nz, self.band_w.shape[0]
+        shapes = bandsum_shapes(ncol, nz, ng, profiles) if sun is None else series_shapes(ncol, sun.nt, nz, ng, profiles)
+        self.out = _outputs(shapes, out, torch.float64, cols.device)
         self.profiles = profiles
-        self._out = _bandsum_out_struct(out, profiles)
-        cols.check_tables()
-        _check_band_device(bands, dev)
-        if band_w.device != dev:
-            raise ValueError(f"band_w lives on {band_w.device} but the columns on {dev}")
-        if scheme == "2s" and cols.mla is None:
-            raise ValueError("solve_2s needs `mla`")
-        if scheme != "bl" and bands.soil_r is None:
-            raise ValueError(f"solve_{scheme} needs `soil_r`")
-        need = workspace_bytes(scheme, ncol, nz, bands.nb)
-        self.workspace = _check_workspace(workspace, need, dev)
-        self._c, self._b = cols.c_struct(), bands.c_struct(ncol)
-        self._o = _lib.CrtOptions(float(mu_s), _lib.TAU_D_METHODS[tau_d_method], 0)
-        self._entry = f"crt_hip_integrated2_{_io_suffix(bands)}"
-        self._fn = getattr(self.lib, self._entry)
+        self._out = _bandsum_out_struct(self.out, profiles)
 
-    def last_kernel(self):
-        """Name / configuration of the fused kernel this thread's most recent call launched (``crt_hip_last_kernel``)."""
-        return self.lib.crt_hip_last_kernel().decode()
-
-    def __call__(self, stream=None, *, flags=0):
-        dev = self.cols.device
-        s = torch.cuda.current_stream(dev) if stream is None else stream
-        self._o.flags = int(flags)
-        with torch.cuda.device(dev):
-            st = self._fn(
-                _lib.SCHEME_IDS[self.scheme], ctypes.byref(self._c), ctypes.byref(self._b), ctypes.byref(self._o), self.band_w.data_ptr(),
-                self.band_w.shape[0], ctypes.byref(self._out), self.workspace.data_ptr(),
-                self.workspace.numel() * self.workspace.element_size(), s.cuda_stream)
-        _lib.check(st, self._entry)
-        return self.out
+    def _tail(self):
+        return self.band_w.data_ptr(), self.band_w.shape[0], ctypes.byref(self._out)
 
 
 def solve_integrated(scheme, cols: Columns, bands: Bands, band_w, **kw):
@@ -768,18 +789,30 @@ class SunSeries:
     @classmethod
     def from_host(cls, d, device="cuda"):
         """From a dict of NumPy arrays (:func:`crt1d_amd.synth.make_sun_series`)."""
-        t = lambda k: None if d.get(k) is None else torch.as_tensor(d[k]).to(device)  # noqa: E731
+        t = _host_reader(d, device)
         return cls(t("psi"), t("I_dr0"), t("I_df0"), t("g_at_psi"))
 
 
-def _f32(t, name):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32, got {t.dtype}")
-    if not t.is_cuda:
-        raise ValueError(f"{name} must live on the GPU (got {t.device}); crt1d_amd has no CPU path")
-    return t.contiguous()
+def _check_sun(cols, bands, sun, f32_ok):
+    """A sun series against the columns and spectra it is solved with: storage type, ``ncol`` / ``nb``, device, and the tables of
+    G_TABLE columns (``cols.psi`` / ``cols.g_at_psi`` are not read, so ``Columns.check_tables`` does not apply: up to two device->host
+    syncs, each only where a table is missing)."""
+    ncol, nb, dev = cols.ncol, bands.nb, cols.device
+    if bands.dtype != sun.I_dr0.dtype:
+        if not f32_ok:
+            raise TypeError("the sun-angle series has no f32 storage form: bands must be float64")
+        want = "SunSeriesF32" if bands.dtype == torch.float32 else "SunSeries"
+        raise TypeError(f"{bands.dtype} bands need a {want}: the spectra of sun are {sun.I_dr0.dtype}")
+    if sun.ncol != ncol or sun.nb != nb:
+        raise ValueError(f"sun must have ncol = {ncol} rows and nb = {nb} bands, got {sun.ncol} and {sun.nb}")
+    if sun.psi.device != dev:
+        raise ValueError(f"sun lives on {sun.psi.device} but the columns on {dev}")
+    if bands.leaf_r is None or bands.leaf_t is None:
+        raise ValueError("bands needs leaf_r and leaf_t")
+    if (cols.g_table is not None or cols.g_at_psi is not None) and sun.g_at_psi is None and bool((cols.g_kind == 6).any()):
+        raise ValueError("columns with g_kind = G_TABLE need sun.g_at_psi (ncol, nt)")
+    if cols.g_table is None and bool((cols.g_kind == 6).any()):
+        raise ValueError("columns with g_kind = G_TABLE need g_table")
 
 
 @dataclass
@@ -796,7 +829,7 @@ class SunSeriesF32(SunSeries):
     @classmethod
     def from_host(cls, d, device="cuda"):
         """From a dict of NumPy arrays (:func:`crt1d_amd.synth.make_sun_series`); the spectra are rounded to float32."""
-        t = lambda k: None if d.get(k) is None else torch.as_tensor(d[k]).to(device)  # noqa: E731
+        t = _host_reader(d, device)
         return cls(t("psi"), t("I_dr0").to(torch.float32), t("I_df0").to(torch.float32), t("g_at_psi"))
 
 
@@ -810,7 +843,7 @@ def series_shapes(ncol, nt, nz, ngroup, profiles=False):
     return {k: (sh[0], nt) + tuple(sh[1:]) for k, sh in bandsum_shapes(ncol, nz, ngroup, profiles).items()}
 
 
-class IntegratedSeriesPlan:
+class IntegratedSeriesPlan(IntegratedPlan):
     """The outputs of :class:`IntegratedPlan` for ``sun.nt`` sun states of every column in one call
     (``crt_hip_integrated_series_f64``): ``out[k][:, t]`` is bitwise what ``IntegratedPlan`` returns with ``psi = sun.psi[:, t]`` and
     the incoming spectra of step ``t``.  The canopy-only part of the column precompute runs once per column, the sun-dependent part
@@ -819,73 +852,11 @@ class IntegratedSeriesPlan:
 
     def __init__(self, scheme, cols: Columns, bands: Bands, sun: SunSeries, band_w, *, mu_s=0.501, tau_d_method="quad", workspace=None,
                  out=None, profiles=False):
-        if scheme not in _lib.SCHEME_IDS:
-            raise ValueError(f"scheme {scheme!r} has no integrated kernel")
-        if tau_d_method not in _lib.TAU_D_METHODS:
-            raise ValueError("invalid `method`. Valid options are 'quad' and '9sky'.")
+        self._check_options(scheme, tau_d_method)
         if not isinstance(sun, SunSeries) or isinstance(sun, SunSeriesF32):
             raise TypeError("sun must be a SunSeries (float64 spectra)")
-        self.lib = _lib.load()
-        self.scheme, self.cols, self.bands, self.sun = scheme, cols, bands, sun
-        band_w = _f64(band_w, "band_w")
-        if band_w.ndim == 1:
-            band_w = band_w[None, :]
-        if band_w.shape[1] != bands.nb or not 1 <= band_w.shape[0] <= 4:
-            raise ValueError("band_w must be (ngroup <= 4, nb)")
-        self.band_w = band_w
-        ncol, nz, ng, dev = cols.ncol, cols.nz, band_w.shape[0], cols.device
-        if bands.dtype != torch.float64:
-            raise TypeError("the sun-angle series has no f32 storage form: bands must be float64")
-        if sun.ncol != ncol or sun.nb != bands.nb:
-            raise ValueError(f"sun must have ncol = {ncol} rows and nb = {bands.nb} bands, got {sun.ncol} and {sun.nb}")
-        if sun.psi.device != dev:
-            raise ValueError(f"sun lives on {sun.psi.device} but the columns on {dev}")
-        if (cols.g_table is not None or cols.g_at_psi is not None) and sun.g_at_psi is None and bool((cols.g_kind == 6).any()):
-            raise ValueError("columns with g_kind = G_TABLE need sun.g_at_psi (ncol, nt)")
-        if cols.g_table is None and bool((cols.g_kind == 6).any()):
-            raise ValueError("columns with g_kind = G_TABLE need g_table")
-        shapes = series_shapes(ncol, sun.nt, nz, ng, profiles)
-        if out is None:
-            out = {k: torch.empty(sh, dtype=torch.float64, device=dev) for k, sh in shapes.items()}
-        else:
-            for k, sh in shapes.items():
-                _check_profile(out[k], f"out[{k!r}]", sh, dev)
-        self.out = out
-        self.profiles = profiles
-        self._out = _bandsum_out_struct(out, profiles)
-        _check_band_device(bands, dev)
-        if band_w.device != dev:
-            raise ValueError(f"band_w lives on {band_w.device} but the columns on {dev}")
-        if bands.leaf_r is None or bands.leaf_t is None:
-            raise ValueError("bands needs leaf_r and leaf_t")
-        if scheme == "2s" and cols.mla is None:
-            raise ValueError("solve_2s needs `mla`")
-        if scheme != "bl" and bands.soil_r is None:
-            raise ValueError(f"solve_{scheme} needs `soil_r`")
-        need = series_workspace_bytes(scheme, ncol, nz, bands.nb, sun.nt)
-        self.workspace = _check_workspace(workspace, need, dev)
-        self._c, self._b, self._s = cols.c_struct(), bands.c_struct(ncol), sun.c_struct()
-        if cols.g_table is None:
-            self._c.g_table = None
-        self._o = _lib.CrtOptions(float(mu_s), _lib.TAU_D_METHODS[tau_d_method], 0)
-        self._entry = "crt_hip_integrated_series_f64"
-        self._fn = self.lib.crt_hip_integrated_series_f64
-
-    def last_kernel(self):
-        """K0 forms and series kernel of this thread's most recent call (``crt_hip_last_kernel``)."""
-        return self.lib.crt_hip_last_kernel().decode()
-
-    def __call__(self, stream=None, *, flags=0):
-        dev = self.cols.device
-        s = torch.cuda.current_stream(dev) if stream is None else stream
-        self._o.flags = int(flags)
-        with torch.cuda.device(dev):
-            st = self._fn(
-                _lib.SCHEME_IDS[self.scheme], ctypes.byref(self._c), ctypes.byref(self._b), ctypes.byref(self._s), ctypes.byref(self._o),
-                self.band_w.data_ptr(), self.band_w.shape[0], ctypes.byref(self._out), self.workspace.data_ptr(),
-                self.workspace.numel() * self.workspace.element_size(), s.cuda_stream)
-        _lib.check(st, self._entry)
-        return self.out
+        self._bind_sums(scheme, cols, bands, band_w, mu_s, tau_d_method, out, profiles, sun=sun)
+        self._finish("crt_hip_integrated_series_f64", series_workspace_bytes(scheme, cols.ncol, cols.nz, bands.nb, sun.nt), workspace)
 
 
 def solve_integrated_series(scheme, cols: Columns, bands: Bands, sun: SunSeries, band_w, **kw):
@@ -925,7 +896,15 @@ def normalize_levels(levels, nz):
     return tuple(sorted(out))
 
 
-class LevelsPlan:
+def _level_keys(keys):
+    """The profile selection of the level plans as a tuple of distinct names out of ``LEVEL_KEYS``."""
+    keys = (keys,) if isinstance(keys, str) else tuple(keys)
+    if not keys or any(k not in LEVEL_KEYS for k in keys) or len(set(keys)) != len(keys):
+        raise ValueError(f"keys must be distinct names out of {LEVEL_KEYS}, got {keys!r}")
+    return keys
+
+
+class LevelsPlan(_SolvePlan):
     """Pre-validated level-subset solve (``crt_hip_levels_f64``, or ``_f32`` for float32 bands): the spectra of ``keys`` (any of
     ``I_dr, I_df_d, I_df_u, F``) at the levels ``levels`` only, each ``(ncol, nsel, nb)`` in the dtype of ``bands``; row ``r`` is level
     ``self.levels[r]`` (sorted, negatives resolved: :func:`normalize_levels`).  Every row is bitwise the row of :func:`solve`'s profile
@@ -933,58 +912,22 @@ class LevelsPlan:
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, *, keys=LEVEL_KEYS, mu_s=0.501, tau_d_method="quad", out=None,
                  workspace=None):
-        if scheme not in _lib.SCHEME_IDS:
-            raise ValueError(f"unknown scheme {scheme!r}; valid: {', '.join(SCHEMES)}")
-        if tau_d_method not in _lib.TAU_D_METHODS:
-            raise ValueError("invalid `method`. Valid options are 'quad' and '9sky'.")  # common.py:78
-        keys = (keys,) if isinstance(keys, str) else tuple(keys)
-        if not keys or any(k not in LEVEL_KEYS for k in keys) or len(set(keys)) != len(keys):
-            raise ValueError(f"keys must be distinct names out of {LEVEL_KEYS}, got {keys!r}")
-        self.lib = _lib.load()
-        self.scheme, self.cols, self.bands = scheme, cols, bands
-        ncol, nz, nb, dev = cols.ncol, cols.nz, bands.nb, cols.device
-        self.levels = normalize_levels(levels, nz)
-        self.keys = keys
-        if scheme == "2s" and cols.mla is None:
-            raise ValueError("solve_2s needs `mla`")
-        if scheme != "bl" and bands.soil_r is None:
-            raise ValueError(f"solve_{scheme} needs `soil_r`")
-        cols.check_tables()
-        _check_band_device(bands, dev)
-        shape = (ncol, len(self.levels), nb)
-        if out is None:
-            out = {k: torch.empty(shape, dtype=bands.dtype, device=dev) for k in keys}
-        else:
-            for k in keys:
-                if k not in out:
-                    raise ValueError(f"`out` lacks {k!r}")
-                _check_profile(out[k], f"output {k!r}", shape, dev, bands.dtype)
-            out = {k: out[k] for k in keys}
-        self.out = out
-        self._out = _lib.CrtOutputs(*[out[k].data_ptr() if k in out else None for k in LEVEL_KEYS], None, None, None)
+        self._check_options(scheme, tau_d_method)
+        self._bind_levels(scheme, cols, bands, levels, _level_keys(keys), mu_s, tau_d_method, out)
+        self._finish(f"crt_hip_levels_{_io_suffix(bands)}", workspace_bytes(scheme, cols.ncol, cols.nz, bands.nb), workspace)
+
+    def _bind_levels(self, scheme, cols, bands, levels, keys, mu_s, tau_d_method, out, sun=None):
+        """``_bind`` + the level list ``_lev`` and the outputs of ``keys`` (with ``sun``: of every sun state), NULL in ``_out`` for the rest."""
+        self.levels, self.keys = normalize_levels(levels, cols.nz), keys
+        self._bind(scheme, cols, bands, mu_s, tau_d_method, sun=sun)
+        shape = (cols.ncol,) + (() if sun is None else (sun.nt,)) + (len(self.levels), bands.nb)
+        out = _outputs({k: shape for k in keys}, out, bands.dtype, cols.device, "output {!r}", lacks=True)
+        self.out = {k: out[k] for k in keys}
+        self._out = _lib.CrtOutputs(*[out[k].data_ptr() if k in keys else None for k in LEVEL_KEYS], None, None, None)
         self._lev = (ctypes.c_int32 * len(self.levels))(*self.levels)
-        need = workspace_bytes(scheme, ncol, nz, nb)
-        self.workspace = _check_workspace(workspace, need, dev)
-        self._wsb = self.workspace.numel() * self.workspace.element_size()
-        self._c, self._b = cols.c_struct(), bands.c_struct(ncol)
-        self._o = _lib.CrtOptions(float(mu_s), _lib.TAU_D_METHODS[tau_d_method], 0)
-        self._entry = f"crt_hip_levels_{_io_suffix(bands)}"
-        self._fn = getattr(self.lib, self._entry)
 
-    def last_kernel(self):
-        """Name / configuration of the kernel this thread's most recent call launched (``crt_hip_last_kernel``)."""
-        return self.lib.crt_hip_last_kernel().decode()
-
-    def __call__(self, stream=None, *, flags=0):
-        """Enqueue on ``stream`` (default: torch's current stream); ``flags`` as for :class:`Plan`."""
-        dev = self.cols.device
-        s = torch.cuda.current_stream(dev) if stream is None else stream
-        self._o.flags = int(flags)
-        with torch.cuda.device(dev):
-            st = self._fn(_lib.SCHEME_IDS[self.scheme], ctypes.byref(self._c), ctypes.byref(self._b), ctypes.byref(self._o), self._lev,
-                          len(self.levels), ctypes.byref(self._out), self.workspace.data_ptr(), self._wsb, s.cuda_stream)
-        _lib.check(st, self._entry)
-        return self.out
+    def _tail(self):
+        return self._lev, len(self.levels), ctypes.byref(self._out)
 
 
 def solve_levels(scheme, cols: Columns, bands: Bands, levels, **kw):
@@ -1013,7 +956,7 @@ def levels_series_workspace_bytes(scheme, ncol, nz, nt):
     return int(_lib.load().crt_hip_levels_series_workspace_bytes(_lib.SCHEME_IDS[scheme], ncol, nz, nt))
 
 
-class LevelsSeriesPlan:
+class LevelsSeriesPlan(LevelsPlan):
     """The outputs of :class:`LevelsPlan` for ``sun.nt`` sun states of every column in one call (``crt_hip_levels_series_f64``, or
     ``_f32`` for float32 bands and a :class:`SunSeriesF32`): the spectra of ``keys`` at the levels ``levels``, each
     ``(ncol, nt, nsel, nb)`` in the dtype of ``bands``.  ``out[k][:, t]`` is bitwise what ``LevelsPlan`` returns with
@@ -1021,77 +964,15 @@ class LevelsSeriesPlan:
     of the column precompute runs once per column, the sun-dependent part once per (column, t).  ``cols.psi``, ``cols.g_at_psi`` and
     ``bands.I_dr0`` / ``I_df0`` are not read (``bands`` may be built with ``None`` for the two).  Any ``nb``."""
 
+    _f32_series = True
+
     def __init__(self, scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, *, keys=LEVEL_KEYS, mu_s=0.501, tau_d_method="quad",
                  out=None, workspace=None):
-        if scheme not in _lib.SCHEME_IDS:
-            raise ValueError(f"unknown scheme {scheme!r}; valid: {', '.join(SCHEMES)}")
-        if tau_d_method not in _lib.TAU_D_METHODS:
-            raise ValueError("invalid `method`. Valid options are 'quad' and '9sky'.")  # common.py:78
+        self._check_options(scheme, tau_d_method)
         if not isinstance(sun, SunSeries):
             raise TypeError("sun must be a SunSeries or a SunSeriesF32")
-        keys = (keys,) if isinstance(keys, str) else tuple(keys)
-        if not keys or any(k not in LEVEL_KEYS for k in keys) or len(set(keys)) != len(keys):
-            raise ValueError(f"keys must be distinct names out of {LEVEL_KEYS}, got {keys!r}")
-        self.lib = _lib.load()
-        self.scheme, self.cols, self.bands, self.sun = scheme, cols, bands, sun
-        ncol, nz, nb, dev = cols.ncol, cols.nz, bands.nb, cols.device
-        self.levels = normalize_levels(levels, nz)
-        self.keys = keys
-        if bands.dtype != sun.I_dr0.dtype:
-            want = "SunSeriesF32" if bands.dtype == torch.float32 else "SunSeries"
-            raise TypeError(f"{bands.dtype} bands need a {want}: the spectra of sun are {sun.I_dr0.dtype}")
-        if sun.ncol != ncol or sun.nb != nb:
-            raise ValueError(f"sun must have ncol = {ncol} rows and nb = {nb} bands, got {sun.ncol} and {sun.nb}")
-        if sun.psi.device != dev:
-            raise ValueError(f"sun lives on {sun.psi.device} but the columns on {dev}")
-        if (cols.g_table is not None or cols.g_at_psi is not None) and sun.g_at_psi is None and bool((cols.g_kind == 6).any()):
-            raise ValueError("columns with g_kind = G_TABLE need sun.g_at_psi (ncol, nt)")
-        if cols.g_table is None and bool((cols.g_kind == 6).any()):
-            raise ValueError("columns with g_kind = G_TABLE need g_table")
-        _check_band_device(bands, dev)
-        if bands.leaf_r is None or bands.leaf_t is None:
-            raise ValueError("bands needs leaf_r and leaf_t")
-        if scheme == "2s" and cols.mla is None:
-            raise ValueError("solve_2s needs `mla`")
-        if scheme != "bl" and bands.soil_r is None:
-            raise ValueError(f"solve_{scheme} needs `soil_r`")
-        shape = (ncol, sun.nt, len(self.levels), nb)
-        if out is None:
-            out = {k: torch.empty(shape, dtype=bands.dtype, device=dev) for k in keys}
-        else:
-            for k in keys:
-                if k not in out:
-                    raise ValueError(f"`out` lacks {k!r}")
-                _check_profile(out[k], f"output {k!r}", shape, dev, bands.dtype)
-            out = {k: out[k] for k in keys}
-        self.out = out
-        self._out = _lib.CrtOutputs(*[out[k].data_ptr() if k in out else None for k in LEVEL_KEYS], None, None, None)
-        self._lev = (ctypes.c_int32 * len(self.levels))(*self.levels)
-        need = levels_series_workspace_bytes(scheme, ncol, nz, sun.nt)
-        self.workspace = _check_workspace(workspace, need, dev)
-        self._wsb = self.workspace.numel() * self.workspace.element_size()
-        self._c, self._b, self._s = cols.c_struct(), bands.c_struct(ncol), sun.c_struct()
-        if cols.g_table is None:
-            self._c.g_table = None
-        self._o = _lib.CrtOptions(float(mu_s), _lib.TAU_D_METHODS[tau_d_method], 0)
-        self._entry = f"crt_hip_levels_series_{_io_suffix(bands)}"
-        self._fn = getattr(self.lib, self._entry)
-
-    def last_kernel(self):
-        """K0 forms and series level kernel of this thread's most recent call (``crt_hip_last_kernel``)."""
-        return self.lib.crt_hip_last_kernel().decode()
-
-    def __call__(self, stream=None, *, flags=0):
-        """Enqueue on ``stream`` (default: torch's current stream); ``flags`` as for :class:`IntegratedSeriesPlan`."""
-        dev = self.cols.device
-        s = torch.cuda.current_stream(dev) if stream is None else stream
-        self._o.flags = int(flags)
-        with torch.cuda.device(dev):
-            st = self._fn(_lib.SCHEME_IDS[self.scheme], ctypes.byref(self._c), ctypes.byref(self._b), ctypes.byref(self._s),
-                          ctypes.byref(self._o), self._lev, len(self.levels), ctypes.byref(self._out), self.workspace.data_ptr(), self._wsb,
-                          s.cuda_stream)
-        _lib.check(st, self._entry)
-        return self.out
+        self._bind_levels(scheme, cols, bands, levels, _level_keys(keys), mu_s, tau_d_method, out, sun=sun)
+        self._finish(f"crt_hip_levels_series_{_io_suffix(bands)}", levels_series_workspace_bytes(scheme, cols.ncol, cols.nz, sun.nt), workspace)
 
 
 def solve_levels_series(scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, **kw):

@@ -1046,16 +1046,31 @@ using namespace crt;
 
 // the epilogue launchers of both storage types (TIO = element type of the profiles and leaf optics): the kernel choice depends on
 // the shape and on alignment only, so an f32 call takes the form -- and the summation order -- of the f64 call on the upcast profiles
+// The optional outputs of a crt_bandsum_out come all together or not at all -- the direct-beam part of the absorption + the five level
+// profiles: 6 or 0, or -1 for a part of them (CRT_ERR_BAD_ARG).
+static int bandsum_nopt(const crt_bandsum_out& o) {
+  const int n = (o.aI_dr != nullptr) + (o.I_dr != nullptr) + (o.I_df_d != nullptr) + (o.I_df_u != nullptr) + (o.F != nullptr) + (o.I_d != nullptr);
+  return n == 0 || n == 6 ? n : -1;
+}
+
+// the crt_bandsum_out of the entries that take the four mandatory outputs as arguments
+static crt_bandsum_out bandsum_out4(double* aI, double* aI_sl, double* aI_sh, double* totals) {
+  crt_bandsum_out o = {};
+  o.aI = aI;
+  o.aI_sl = aI_sl;
+  o.aI_sh = aI_sh;
+  o.totals = totals;
+  return o;
+}
+
 template <typename TIO>
 static int bandsum_impl(const crt_columns* cols, int32_t nb, int64_t col_stride, const TIO* leaf_r, const TIO* leaf_t, const TIO* I_dr,
                         const TIO* I_df_d, const TIO* I_df_u, const double* band_w, int32_t ngroup, const crt_bandsum_out* out,
                         crt_stream_t stream) {
   if (!cols || !I_dr || !I_df_d || !I_df_u || !band_w || !out || !out->aI || !out->aI_sl || !out->aI_sh) return CRT_ERR_BAD_ARG;
   double *aI = out->aI, *aI_sl = out->aI_sl, *aI_sh = out->aI_sh, *totals = out->totals;
-  // the optional outputs come all together or not at all: the direct-beam part of the absorption + the five level profiles
-  const int nopt = (out->aI_dr != nullptr) + (out->I_dr != nullptr) + (out->I_df_d != nullptr) + (out->I_df_u != nullptr) + (out->F != nullptr) +
-                   (out->I_d != nullptr);
-  if (nopt != 0 && nopt != 6) return CRT_ERR_BAD_ARG;
+  const int nopt = bandsum_nopt(*out);
+  if (nopt < 0) return CRT_ERR_BAD_ARG;
   const bool prof = nopt == 6;
   if (cols->ncol <= 0 || cols->nz < 2 || nb <= 0 || ngroup <= 0 || ngroup > MAXG) return CRT_ERR_BAD_ARG;
   if (!cols->psi || !cols->lai || !cols->g_kind || !leaf_r || !leaf_t) return CRT_ERR_BAD_ARG;
@@ -1296,9 +1311,20 @@ int crt_hip_quad_nodes(double mu_s, double* psi_nodes) {
   return CRT_OK;
 }
 
-static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts,
-                      const crt_outputs* out, void* workspace, size_t workspace_bytes, crt_stream_t stream, int f32,
-                      const IntArgs* integ = nullptr, const LevArgs* lev = nullptr, const crt_sun_series* ser = nullptr) {
+// options of one solve call, resolved from crt_options (or the defaults when it is NULL) by check_solve
+struct SolveOpts {
+  double mu_s = 0.501;
+  int method = CRT_TAU_D_QUAD, flags = 0;
+  int32_t tune[CRT_NTUNE] = {};
+};
+
+static bool is_tri(int scheme) { return scheme == CRT_SCHEME_N79 || scheme == CRT_SCHEME_ZQ; }
+
+// Every argument check of a solve, in the order that decides which status a call with several faults gets; fills `o`.
+// integ / lev / ser: the integrated outputs, the level subset, the sun-angle series of the call (each NULL when it has none).
+static int check_solve(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const crt_outputs* out,
+                       const void* workspace, size_t workspace_bytes, const IntArgs* integ, const LevArgs* lev, const crt_sun_series* ser,
+                       SolveOpts& o) {
   if (!scheme_ok(scheme) || !cols || !bands || !out) return CRT_ERR_BAD_ARG;
   const int ncol = cols->ncol, nz = cols->nz, nb = bands->nb;
   if (ncol <= 0 || nz <= 0 || nb <= 0) return CRT_ERR_BAD_ARG;
@@ -1314,24 +1340,20 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
   }
   if (scheme != CRT_SCHEME_BL && !bands->soil_r) return CRT_ERR_BAD_ARG;
   if (bands->col_stride != 0 && bands->col_stride < nb) return CRT_ERR_BAD_ARG;
-  if (!integ && !lev && (!out->I_dr || !out->I_df_d || !out->I_df_u || !out->F)) return CRT_ERR_BAD_ARG;
-  const bool tri = scheme == CRT_SCHEME_N79 || scheme == CRT_SCHEME_ZQ;
-  const int nextra = scheme == CRT_SCHEME_N79 ? 2 : (scheme == CRT_SCHEME_ZQ || scheme == CRT_SCHEME_G77 || scheme == CRT_SCHEME_BF) ? 3 : 0;
   if (!integ && !lev) {
+    if (!out->I_dr || !out->I_df_d || !out->I_df_u || !out->F) return CRT_ERR_BAD_ARG;
+    const int nextra = scheme == CRT_SCHEME_N79 ? 2 : (scheme == CRT_SCHEME_ZQ || scheme == CRT_SCHEME_G77 || scheme == CRT_SCHEME_BF) ? 3 : 0;
     if (nextra >= 1 && !out->x0) return CRT_ERR_BAD_ARG;
     if (nextra >= 2 && !out->x1) return CRT_ERR_BAD_ARG;
     if (nextra >= 3 && !out->x2) return CRT_ERR_BAD_ARG;
   }
   if (nz < 2) return CRT_ERR_SHAPE;
   if (scheme == CRT_SCHEME_N79 && nz < 3) return CRT_ERR_SHAPE;  // td[1]/tb[1] of _solve_n79.py:85-92
-  double mu_s = 0.501;
-  int method = CRT_TAU_D_QUAD, flags = 0;
-  int32_t tune[CRT_NTUNE] = {};
   if (opts) {
-    mu_s = opts->mu_s;
-    method = opts->tau_d_method;
-    flags = opts->flags;
-    std::memcpy(tune, opts->tune, sizeof tune);
+    o.mu_s = opts->mu_s;
+    o.method = opts->tau_d_method;
+    o.flags = opts->flags;
+    std::memcpy(o.tune, opts->tune, sizeof o.tune);
   }
   {  // crt_options.tune is a measurement aid, but it is part of the ABI: values out of range are rejected here, before any launch,
      // instead of reaching the kernel configurations.  A key takes 0 (automatic) or lo, lo + step, ... up to hi; a key absent from the
@@ -1346,15 +1368,15 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
         {CRT_TUNE_FLAT_FLUSH, CRT_FLAT_FLUSH_OFF, CRT_FLAT_FLUSH_WHOLE_LINE, 1}, {CRT_TUNE_K0_SEPARATE, 1, 1, 1}};
     bool known[CRT_NTUNE] = {};
     for (const auto& r : accepted) {
-      const int v = tune[r.key];
+      const int v = o.tune[r.key];
       known[r.key] = true;
       if (v != 0 && (v < r.lo || v > r.hi || (v - r.lo) % r.step != 0)) return CRT_ERR_BAD_ARG;
     }
     for (int i = 0; i < CRT_NTUNE; ++i)
-      if (!known[i] && tune[i] != 0) return CRT_ERR_BAD_ARG;
+      if (!known[i] && o.tune[i] != 0) return CRT_ERR_BAD_ARG;
   }
-  if (scheme == CRT_SCHEME_4S && !(mu_s > 0.0 && mu_s < 1.0)) return CRT_ERR_BAD_ARG;
-  if (method != CRT_TAU_D_QUAD && method != CRT_TAU_D_9SKY) return CRT_ERR_BAD_ARG;  // ValueError, common.py:78
+  if (scheme == CRT_SCHEME_4S && !(o.mu_s > 0.0 && o.mu_s < 1.0)) return CRT_ERR_BAD_ARG;
+  if (o.method != CRT_TAU_D_QUAD && o.method != CRT_TAU_D_9SKY) return CRT_ERR_BAD_ARG;  // ValueError, common.py:78
   const size_t need = !ser ? crt_hip_workspace_bytes_nb(scheme, ncol, nz, nb)
                       : lev ? crt_hip_levels_series_workspace_bytes(scheme, ncol, nz, ser->nt)
                             : crt_hip_series_workspace_bytes(scheme, ncol, nz, nb, ser->nt);
@@ -1362,92 +1384,19 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
   if (!workspace || workspace_bytes < need) return CRT_ERR_WORKSPACE;
   if (ser && integ && nb > 1024) return CRT_ERR_UNSUPPORTED;  // as the per-step entry, but before K0 has written anything
   if (ser && lev && (long long)ncol * ser->nt > 0x7fffffffLL) return CRT_ERR_UNSUPPORTED;  // (column, t) is a 32-bit index in K0
+  return CRT_OK;
+}
 
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  ColArgs ca;
-  ca.ncol = ncol;
-  ca.nz = nz;
-  ca.scheme = scheme;
-  ca.tau_d_method = method;
-  ca.mu_s = mu_s;
-  ca.psi = cols->psi;
-  ca.lai = cols->lai;
-  ca.mla = cols->mla;
-  ca.g_kind = cols->g_kind;
-  ca.g_param = cols->g_param;
-  ca.g_at_psi = cols->g_at_psi;
-  ca.g_table = cols->g_table;
-  ca.ws = static_cast<double*>(workspace);
-  if (ser) {
-    // workspace: canopy records [ncol][can_len], then sun records [ncol * nt][sun_len] (SeriesArgs, crt_internal.hpp)
-    double* const sunrec = static_cast<double*>(workspace) + (size_t)ncol * can_len(scheme, nz);
-    ca.psi = ser->psi;
-    ca.g_at_psi = ser->g_at_psi;
-    SolveArgs sa = {};
-    sa.ncol = ncol;
-    sa.nb = nb;
-    sa.nz = nz;
-    sa.reclen = rec_len(scheme, nz);
-    sa.col_stride = bands->col_stride;
-    sa.ws = static_cast<const double*>(workspace);
-    sa.leaf_r = bands->leaf_r;
-    sa.leaf_t = bands->leaf_t;
-    sa.soil_r = bands->soil_r;
-    sa.mu_s = mu_s;
-    sa.f32 = f32;
-    std::memcpy(&sa.tune, tune, sizeof sa.tune);
-    SeriesArgs sr;
-    sr.nt = ser->nt;
-    sr.scheme = scheme;
-    sr.nz = nz;
-    sr.canlen = can_len(scheme, nz);
-    sr.sunlen = sun_len(scheme, nz);
-    sr.can = sa.ws;
-    sr.sun = sunrec;
-    sr.col_stride = ser->col_stride;
-    sr.I_dr0 = ser->I_dr0;
-    sr.I_df0 = ser->I_df0;
-    auto lev_series = [&](bool probe) {
-      if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_lev(sa, *lev, s, &sr, probe);
-      return tri ? launch_tridiag_lev(scheme, sa, *lev, s, &sr, probe) : launch_closed_lev(scheme, sa, *lev, s, &sr, probe);
-    };
-    if (lev) {  // every shape the level series cannot serve is found here, before K0 has written anything
-      const int st = lev_series(true);
-      if (st != CRT_OK) return st;
-    }
-    if (!(flags & CRT_FLAG_SKIP_PRECOMPUTE)) {
-      const int st = launch_colpre_series(ca, ser->nt, sunrec, s);
-      if (st != CRT_OK) return st;
-    } else {
-      const int st = init_quadrature(s);
-      if (st != CRT_OK) return st;
-    }
-    if (flags & CRT_FLAG_PRECOMPUTE_ONLY) {
-      note_kernel("k_colpre<canopy> + k_colsun nt=%d", ser->nt);
-      return CRT_OK;
-    }
-    if (lev) return lev_series(false);
-    if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_int(sa, *integ, s, &sr);
-    return tri ? launch_tridiag_int(scheme, sa, *integ, s, &sr) : launch_closed_int(scheme, sa, *integ, s, &sr);
-  }
-  // 2s profiles: the closed-form launcher forms the records inside k_pipe when it picks that kernel (one launch per call), and runs
-  // k_colpre in front of any other kernel.  SKIP_PRECOMPUTE / PRECOMPUTE_ONLY and CRT_TUNE_K0_SEPARATE keep k_colpre as a kernel of its own.
-  const bool k0_in_solve = scheme == CRT_SCHEME_2S && !integ && !lev && !(flags & (CRT_FLAG_SKIP_PRECOMPUTE | CRT_FLAG_PRECOMPUTE_ONLY)) &&
-                           tune[CRT_TUNE_K0_SEPARATE] == 0;
-  if (k0_in_solve) {
-    const int st = init_quadrature(s);
-    if (st != CRT_OK) return st;
-  } else if (!(flags & CRT_FLAG_SKIP_PRECOMPUTE)) {
-    int st = launch_colpre(ca, s);
-    if (st != CRT_OK) return st;
-  }
-  if (flags & CRT_FLAG_PRECOMPUTE_ONLY) return CRT_OK;
-
-  SolveArgs sa;
-  sa.ncol = ncol;
-  sa.nb = nb;
-  sa.nz = nz;
-  sa.reclen = rec_len(scheme, nz);
+// the K0 and solve argument blocks of a checked call, for the per-step and the series dispatch alike
+static void build_args(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_outputs* out, void* workspace, int f32,
+                       const SolveOpts& o, ColArgs& ca, SolveArgs& sa) {
+  ca = {cols->ncol, cols->nz, scheme, o.method, o.mu_s, cols->psi, cols->lai, cols->mla, cols->g_kind, cols->g_param, cols->g_at_psi,
+        cols->g_table, static_cast<double*>(workspace)};
+  sa = {};
+  sa.ncol = cols->ncol;
+  sa.nb = bands->nb;
+  sa.nz = cols->nz;
+  sa.reclen = rec_len(scheme, cols->nz);
   sa.col_stride = bands->col_stride;
   sa.ws = static_cast<const double*>(workspace);
   sa.I_dr0 = bands->I_dr0;
@@ -1455,16 +1404,57 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
   sa.leaf_r = bands->leaf_r;
   sa.leaf_t = bands->leaf_t;
   sa.soil_r = bands->soil_r;
-  sa.o[0] = out->I_dr;
-  sa.o[1] = out->I_df_d;
-  sa.o[2] = out->I_df_u;
-  sa.o[3] = out->F;
-  sa.o[4] = out->x0;
-  sa.o[5] = out->x1;
-  sa.o[6] = out->x2;
-  sa.mu_s = mu_s;
+  void* const o7[7] = {out->I_dr, out->I_df_d, out->I_df_u, out->F, out->x0, out->x1, out->x2};
+  std::memcpy(sa.o, o7, sizeof sa.o);
+  sa.mu_s = o.mu_s;
   sa.f32 = f32;
-  std::memcpy(&sa.tune, tune, sizeof sa.tune);
+  std::memcpy(&sa.tune, o.tune, sizeof sa.tune);
+}
+
+// sun-angle series: K0 per column and per (column, t), then one series kernel (integrated outputs or level spectra)
+static int dispatch_series(int scheme, ColArgs ca, SolveArgs sa, int flags, const IntArgs* integ, const LevArgs* lev, const crt_sun_series* ser,
+                           hipStream_t s) {
+  // workspace: canopy records [ncol][can_len], then sun records [ncol * nt][sun_len] (SeriesArgs, crt_internal.hpp)
+  double* const sunrec = ca.ws + (size_t)ca.ncol * can_len(scheme, ca.nz);
+  ca.psi = ser->psi;
+  ca.g_at_psi = ser->g_at_psi;
+  sa.I_dr0 = sa.I_df0 = nullptr;  // the spectra come from `sr`
+  const SeriesArgs sr = {ser->nt, scheme, ca.nz, can_len(scheme, ca.nz), sun_len(scheme, ca.nz), sa.ws, sunrec, ser->col_stride, ser->I_dr0, ser->I_df0};
+  const bool tri = is_tri(scheme);
+  auto lev_series = [&](bool probe) {
+    if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_lev(sa, *lev, s, &sr, probe);
+    return tri ? launch_tridiag_lev(scheme, sa, *lev, s, &sr, probe) : launch_closed_lev(scheme, sa, *lev, s, &sr, probe);
+  };
+  if (lev) {  // every shape the level series cannot serve is found here, before K0 has written anything
+    const int st = lev_series(true);
+    if (st != CRT_OK) return st;
+  }
+  const int st = (flags & CRT_FLAG_SKIP_PRECOMPUTE) ? init_quadrature(s) : launch_colpre_series(ca, ser->nt, sunrec, s);
+  if (st != CRT_OK) return st;
+  if (flags & CRT_FLAG_PRECOMPUTE_ONLY) {
+    note_kernel("k_colpre<canopy> + k_colsun nt=%d", ser->nt);
+    return CRT_OK;
+  }
+  if (lev) return lev_series(false);
+  if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_int(sa, *integ, s, &sr);
+  return tri ? launch_tridiag_int(scheme, sa, *integ, s, &sr) : launch_closed_int(scheme, sa, *integ, s, &sr);
+}
+
+// one sun state per column: K0, then the profile, integrated or level-subset kernel of the scheme
+static int dispatch_step(int scheme, const ColArgs& ca, const SolveArgs& sa, int flags, const IntArgs* integ, const LevArgs* lev, hipStream_t s) {
+  // 2s profiles: the closed-form launcher forms the records inside k_pipe when it picks that kernel (one launch per call), and runs
+  // k_colpre in front of any other kernel.  SKIP_PRECOMPUTE / PRECOMPUTE_ONLY and CRT_TUNE_K0_SEPARATE keep k_colpre as a kernel of its own.
+  const bool k0_in_solve = scheme == CRT_SCHEME_2S && !integ && !lev && !(flags & (CRT_FLAG_SKIP_PRECOMPUTE | CRT_FLAG_PRECOMPUTE_ONLY)) &&
+                           sa.tune.k0_separate == 0;
+  if (k0_in_solve) {
+    const int st = init_quadrature(s);
+    if (st != CRT_OK) return st;
+  } else if (!(flags & CRT_FLAG_SKIP_PRECOMPUTE)) {
+    const int st = launch_colpre(ca, s);
+    if (st != CRT_OK) return st;
+  }
+  if (flags & CRT_FLAG_PRECOMPUTE_ONLY) return CRT_OK;
+  const bool tri = is_tri(scheme);
   if (integ) {
     if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_int(sa, *integ, s);
     return tri ? launch_tridiag_int(scheme, sa, *integ, s) : launch_closed_int(scheme, sa, *integ, s);
@@ -1473,12 +1463,22 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
     if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_lev(sa, *lev, s);
     return tri ? launch_tridiag_lev(scheme, sa, *lev, s) : launch_closed_lev(scheme, sa, *lev, s);
   }
-  if (scheme == CRT_SCHEME_ZQ_PA)
-    return launch_zqpa(sa, static_cast<double*>(workspace) + (size_t)ncol * sa.reclen, s);
+  if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa(sa, ca.ws + (size_t)sa.ncol * sa.reclen, s);
   const int force = (flags & CRT_FLAG_DIRECT_STORES) ? 1 : 0;
   return tri ? launch_tridiag(scheme, sa, s, force) : launch_closed(scheme, sa, s, force, k0_in_solve ? &ca : nullptr);
 }
 
+static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts,
+                      const crt_outputs* out, void* workspace, size_t workspace_bytes, crt_stream_t stream, int f32,
+                      const IntArgs* integ = nullptr, const LevArgs* lev = nullptr, const crt_sun_series* ser = nullptr) {
+  SolveOpts o;
+  if (const int st = check_solve(scheme, cols, bands, opts, out, workspace, workspace_bytes, integ, lev, ser, o)) return st;
+  ColArgs ca;
+  SolveArgs sa;
+  build_args(scheme, cols, bands, out, workspace, f32, o, ca, sa);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return ser ? dispatch_series(scheme, ca, sa, o.flags, integ, lev, ser, s) : dispatch_step(scheme, ca, sa, o.flags, integ, lev, s);
+}
 
 int crt_hip_solve_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts,
                       const crt_outputs* out, void* workspace, size_t workspace_bytes, crt_stream_t stream) {
@@ -1540,22 +1540,14 @@ int crt_hip_absorb_bandsum2_f32(const crt_columns* cols, const crt_bands_f32* ba
 int crt_hip_absorb_bandsum_f64(const crt_columns* cols, const crt_bands* bands, const double* I_dr, const double* I_df_d,
                                const double* I_df_u, const double* band_w, int32_t ngroup, double* aI, double* aI_sl,
                                double* aI_sh, double* totals, crt_stream_t stream) {
-  crt_bandsum_out o = {};
-  o.aI = aI;
-  o.aI_sl = aI_sl;
-  o.aI_sh = aI_sh;
-  o.totals = totals;
+  const crt_bandsum_out o = bandsum_out4(aI, aI_sl, aI_sh, totals);
   return crt_hip_absorb_bandsum2_f64(cols, bands, I_dr, I_df_d, I_df_u, band_w, ngroup, &o, stream);
 }
 
 int crt_hip_absorb_bandsum_f32(const crt_columns* cols, const crt_bands_f32* bands, const float* I_dr, const float* I_df_d,
                                const float* I_df_u, const double* band_w, int32_t ngroup, double* aI, double* aI_sl,
                                double* aI_sh, double* totals, crt_stream_t stream) {
-  crt_bandsum_out o = {};
-  o.aI = aI;
-  o.aI_sl = aI_sl;
-  o.aI_sh = aI_sh;
-  o.totals = totals;
+  const crt_bandsum_out o = bandsum_out4(aI, aI_sl, aI_sh, totals);
   return crt_hip_absorb_bandsum2_f32(cols, bands, I_dr, I_df_d, I_df_u, band_w, ngroup, &o, stream);
 }
 
@@ -1564,9 +1556,7 @@ static int integrated_impl(int scheme, const crt_columns* cols, const crt_bands*
                            int32_t ngroup, const crt_bandsum_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream, int f32,
                            const crt_sun_series* ser = nullptr) {
   if (!band_w || !out || !out->aI || !out->aI_sl || !out->aI_sh || ngroup <= 0 || ngroup > INT_MAXG || !cols) return CRT_ERR_BAD_ARG;
-  const int nopt = (out->aI_dr != nullptr) + (out->I_dr != nullptr) + (out->I_df_d != nullptr) + (out->I_df_u != nullptr) + (out->F != nullptr) +
-                   (out->I_d != nullptr);
-  if (nopt != 0 && nopt != 6) return CRT_ERR_BAD_ARG;
+  if (bandsum_nopt(*out) < 0) return CRT_ERR_BAD_ARG;
   IntArgs ia;
   ia.lai = cols->lai;
   ia.band_w = band_w;
@@ -1608,22 +1598,14 @@ int crt_hip_integrated2_f32(int scheme, const crt_columns* cols, const crt_bands
 int crt_hip_integrated_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts,
                            const double* band_w, int32_t ngroup, double* aI, double* aI_sl, double* aI_sh, double* totals,
                            void* workspace, size_t workspace_bytes, crt_stream_t stream) {
-  crt_bandsum_out o = {};
-  o.aI = aI;
-  o.aI_sl = aI_sl;
-  o.aI_sh = aI_sh;
-  o.totals = totals;
+  const crt_bandsum_out o = bandsum_out4(aI, aI_sl, aI_sh, totals);
   return crt_hip_integrated2_f64(scheme, cols, bands, opts, band_w, ngroup, &o, workspace, workspace_bytes, stream);
 }
 
 int crt_hip_integrated_f32(int scheme, const crt_columns* cols, const crt_bands_f32* bands, const crt_options* opts,
                            const double* band_w, int32_t ngroup, double* aI, double* aI_sl, double* aI_sh, double* totals,
                            void* workspace, size_t workspace_bytes, crt_stream_t stream) {
-  crt_bandsum_out o = {};
-  o.aI = aI;
-  o.aI_sl = aI_sl;
-  o.aI_sh = aI_sh;
-  o.totals = totals;
+  const crt_bandsum_out o = bandsum_out4(aI, aI_sl, aI_sh, totals);
   return crt_hip_integrated2_f32(scheme, cols, bands, opts, band_w, ngroup, &o, workspace, workspace_bytes, stream);
 }
 

@@ -67,7 +67,7 @@ struct ColArgs {
 };
 
 // Kernel-selection overrides of one call: crt_options.tune with a field per key (include/crt1d_hip.h, enum crt_tune_key), validated by
-// solve_impl (api.hip).  0 = automatic everywhere.
+// check_solve (api.hip).  0 = automatic everywhere.
 struct Tune {
   int32_t tile_lds, tile_t, tile_flags, closed_store_waves, closed_pipe_t, pack, pack_compute_waves, reserved7;
   int32_t tri_m, tri_t, tri_family, tri_store_waves, min_tile_nb, flat_flush, reserved14, k0_separate;
@@ -646,9 +646,9 @@ inline dim3 series_grid(int ncol, int nt) {
   return dim3((unsigned)ncol, gy, (unsigned)((nt + (long long)gy - 1) / gy));
 }
 
-// set the dynamic-LDS attribute where needed, launch, check: the launch sequence of the series kernels
+// set the dynamic-LDS attribute where needed, launch, check: the one launch sequence (the caller reports the kernel when this returns CRT_OK)
 template <class K, class... Args>
-inline int launch_series(K kern, dim3 grid, int nthr, size_t sh, hipStream_t s, Args... args) {
+inline int launch_kernel(K kern, dim3 grid, int nthr, size_t sh, hipStream_t s, Args... args) {
   if (sh > 64 * 1024 &&
       hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
     return (int)CRT_ERR_LAUNCH;

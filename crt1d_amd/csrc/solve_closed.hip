@@ -966,13 +966,8 @@ int launch_tile(const SolveArgs& a, hipStream_t s, bool& done, const ColArgs* k0
       const size_t shp = (size_t)((cpw * a.reclen + 1) & ~1) * sizeof(double) + (size_t)2 * cpw * S::NARR * Tp * nb * sizeof(TIO);
       const int thr = 64 * (pc.ncw + nswp);
       if (shp <= 160 * 1024 && thr <= 512 && (Tp * nb) % VWp == 0) {
-        auto kern = k_pipe_pack<S, TIO, 512>;
-        if (shp > 64 * 1024 &&
-            hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shp) != hipSuccess)
-          return (int)CRT_ERR_LAUNCH;
         if (const int st = k0_before(k0, s)) return st;
-        hipLaunchKernelGGL(kern, dim3((a.ncol + cpw - 1) / cpw), dim3(thr), shp, s, a, pc);
-        if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+        if (const int st = launch_kernel(k_pipe_pack<S, TIO, 512>, dim3((a.ncol + cpw - 1) / cpw), thr, shp, s, a, pc)) return st;
         note_kernel("k_pipe_pack<%s,%s> columns=%d compute_waves=%d T=%d store_waves=%d lds=%zu", S::NAME, sizeof(TIO) == 8 ? "f64" : "f32", pc.cpw,
                     pc.ncw, Tp, nswp, shp);
         done = true;
@@ -1055,13 +1050,9 @@ int launch_tile(const SolveArgs& a, hipStream_t s, bool& done, const ColArgs* k0
       constexpr bool can_k0 = std::is_same<S, Sch2s>::value;
       const bool own_k0 = can_k0 && k0 != nullptr;
       auto gop = [&](auto kern) {
-        if (psh > 64 * 1024 &&
-            hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)psh) != hipSuccess)
-          return (int)CRT_ERR_LAUNCH;
         if (!own_k0)
           if (const int st = k0_before(k0, s)) return st;
-        hipLaunchKernelGGL(kern, dim3(a.ncol), dim3(pthr), psh, s, a, pc, own_k0 ? *k0 : ColArgs{});
-        if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+        if (const int st = launch_kernel(kern, dim3(a.ncol), pthr, psh, s, a, pc, own_k0 ? *k0 : ColArgs{})) return st;
         note_kernel("k_pipe<%s,%s>%s T=%d store_waves=%d lds=%zu%s", S::NAME, sizeof(TIO) == 8 ? "f64" : "f32", fused ? "" : " generic-flush", Tp, nsw, psh,
                     own_k0 ? " k0=fused" : "");  // (only a launch that succeeded is reported)
         return (int)CRT_OK;
@@ -1079,12 +1070,8 @@ int launch_tile(const SolveArgs& a, hipStream_t s, bool& done, const ColArgs* k0
     }
   }
   auto go = [&](auto kern) {
-    if (sh > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
-      return (int)CRT_ERR_LAUNCH;
     if (const int st = k0_before(k0, s)) return st;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(nthr), sh, s, a, cfg);
-    if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+    if (const int st = launch_kernel(kern, dim3(grid), nthr, sh, s, a, cfg)) return st;
     note_kernel("k_tile<%s,%s>%s CB=%d T=%d lds=%zu", S::NAME, sizeof(TIO) == 8 ? "f64" : "f32", fused ? "" : " generic-flush", CB, T, sh);  // (only a launch that succeeded is reported)
     return (int)CRT_OK;
   };
@@ -1207,7 +1194,7 @@ int launch_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const Serie
   if (sr) {
     if constexpr (sizeof(TIO) == 8) {
       auto gos = [&](auto kern) {
-        const int st = launch_series(kern, series_grid(a.ncol, sr->nt), nthr, sh, s, a, ia, *sr, rec_dbl);
+        const int st = launch_kernel(kern, series_grid(a.ncol, sr->nt), nthr, sh, s, a, ia, *sr, rec_dbl);
         if (st == CRT_OK) note_kernel("k_colpre<canopy> + k_colsun + k_int_series<%s>%s nt=%d", S::NAME, prof ? " + level profiles" : " wave totals", sr->nt);
         return st;
       };
@@ -1217,11 +1204,7 @@ int launch_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const Serie
     return CRT_ERR_UNSUPPORTED;  // no f32 form of the series
   }
   auto go = [&](auto kern) {
-    if (sh > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
-      return (int)CRT_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.ncol), dim3(nthr), sh, s, a, ia, rec_dbl);
-    if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+    if (const int st = launch_kernel(kern, dim3(a.ncol), nthr, sh, s, a, ia, rec_dbl)) return st;
     note_kernel("k_int<%s>%s%s", S::NAME, sizeof(TIO) == 8 ? "" : " f32", prof ? " + level profiles" : " wave totals");  // (only a launch that succeeded is reported)
     return (int)CRT_OK;
   };
@@ -1302,7 +1285,7 @@ int launch_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s, const Serie
     if (!use_lds || !lev_series_grid(a.ncol, sr->nt, ls.nslice, &grid)) return CRT_ERR_UNSUPPORTED;
     if (probe) return CRT_OK;
     auto gos = [&](auto kern) {
-      const int st = launch_series(kern, grid, ls.nthr, sh, s, a, la, *sr, ls.per, ls.nslice);
+      const int st = launch_kernel(kern, grid, ls.nthr, sh, s, a, la, *sr, ls.per, ls.nslice);
       if (st == CRT_OK)
         note_kernel("k_colpre<canopy> + k_colsun + k_lev_series<%s>%s nsel=%d slice=%d nt=%d", S::NAME, sizeof(TIO) == 8 ? "" : " f32", la.nsel,
                     ls.per, sr->nt);
@@ -1313,11 +1296,7 @@ int launch_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s, const Serie
   if (probe) return CRT_OK;
   auto go = [&](auto kern) {
     const size_t shk = use_lds ? sh : 0;
-    if (shk > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shk) != hipSuccess)
-      return (int)CRT_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.ncol, ls.nslice), dim3(ls.nthr), shk, s, a, la, ls.per);
-    if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+    if (const int st = launch_kernel(kern, dim3(a.ncol, ls.nslice), ls.nthr, shk, s, a, la, ls.per)) return st;
     note_kernel("k_lev<%s>%s nsel=%d slice=%d%s", S::NAME, sizeof(TIO) == 8 ? "" : " f32", la.nsel, ls.per,
                 use_lds ? "" : " record in HBM");  // (only a launch that succeeded is reported)
     return (int)CRT_OK;

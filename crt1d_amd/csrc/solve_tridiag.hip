@@ -146,15 +146,6 @@ __global__ __launch_bounds__(TB) void k_tri_wave(SolveArgs a, int rec_lds_double
 
 constexpr size_t MAX_WG_LDS = 160 * 1024;
 
-template <typename K>
-int set_lds_limit(K kern, size_t bytes) {
-  if (bytes <= 64 * 1024) return CRT_OK;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) ==
-                 hipSuccess
-             ? CRT_OK
-             : CRT_ERR_LAUNCH;
-}
-
 }  // namespace
 
 template <class S, typename TIO>
@@ -171,10 +162,7 @@ int launch_wave(const SolveArgs& a, hipStream_t s) {
   const size_t sh = (ef_in_lds ? ef_lds : 0) + rec_doubles * sizeof(double);
   if (!ef_in_lds && (S::NOUT < 4 || a.nz < S::rows(a.nz) - 1)) return CRT_ERR_UNSUPPORTED;  // nowhere to park the pairs
   auto go = [&](auto kern) {
-    const int st = set_lds_limit(kern, sh);
-    if (st != CRT_OK) return st;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(TB), sh, s, a, (int)rec_doubles);
-    if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+    if (const int st = launch_kernel(kern, dim3((unsigned)nblk), TB, sh, s, a, (int)rec_doubles)) return st;
     note_kernel("k_tri_wave<%s,%s> pairs in %s", S::NAME, sizeof(TIO) == 8 ? "f64" : "f32", ef_in_lds ? "LDS" : "output rows");  // (only a launch that succeeded is reported)
     return (int)CRT_OK;
   };

@@ -483,18 +483,10 @@ int launch_mt(const SolveArgs& a, hipStream_t s, int nthr) {
   cfg.flat = (!FUSED && a.tune.flat_flush != CRT_FLAT_FLUSH_OFF) ? flat_flush_ok<S, TIO>(a) : 0;
   const size_t sh = ((size_t)cfg.off_tile + (size_t)S::NST * T * a.nb) * sizeof(double);
   if (sh > MAX_WG_LDS) return CRT_ERR_UNSUPPORTED;
-  const void* fn = nthr <= 256 ? (const void*)k_tri_tile<S, TIO, M, T, 256, FUSED> : nthr <= 512 ? (const void*)k_tri_tile<S, TIO, M, T, 512, FUSED>
-                                                                                      : (const void*)k_tri_tile<S, TIO, M, T, 1024, FUSED>;
-  if (sh > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
-    return CRT_ERR_LAUNCH;
-  dim3 grid(a.ncol), block(nthr);
-  if (nthr <= 256)
-    hipLaunchKernelGGL((k_tri_tile<S, TIO, M, T, 256, FUSED>), grid, block, sh, s, a, cfg);
-  else if (nthr <= 512)
-    hipLaunchKernelGGL((k_tri_tile<S, TIO, M, T, 512, FUSED>), grid, block, sh, s, a, cfg);
-  else
-    hipLaunchKernelGGL((k_tri_tile<S, TIO, M, T, 1024, FUSED>), grid, block, sh, s, a, cfg);
-  if (hipGetLastError() != hipSuccess) return CRT_ERR_LAUNCH;
+  auto kern = k_tri_tile<S, TIO, M, T, 256, FUSED>;  // (instantiated in this order: the order of the kernels in the code object)
+  if (nthr > 256) kern = k_tri_tile<S, TIO, M, T, 512, FUSED>;
+  if (nthr > 512) kern = k_tri_tile<S, TIO, M, T, 1024, FUSED>;
+  if (const int st = launch_kernel(kern, dim3(a.ncol), nthr, sh, s, a, cfg)) return st;
   note_kernel("k_tri_tile<%s,%s>%s M=%d T=%d lds=%zu", S::NAME, sizeof(TIO) == 8 ? "f64" : "f32", FUSED ? "" : cfg.flat ? " flat-flush" : " generic-flush", M, T, sh);  // (only a launch that succeeded is reported)
   return CRT_OK;
 }
@@ -623,18 +615,14 @@ int launch_int_m(const SolveArgs& a, const IntArgs& ia, hipStream_t s, int nthr,
   const size_t sh = ((size_t)off_int + int_lds_doubles(a.nz, nthr / 64, false, prof)) * sizeof(double);
   if (sh > MAX_WG_LDS) return CRT_ERR_UNSUPPORTED;
   auto go = [&](auto kern) {
-    if (sh > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
-      return (int)CRT_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.ncol), dim3(nthr), sh, s, a, ia, off_ck, off_int);
-    if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+    if (const int st = launch_kernel(kern, dim3(a.ncol), nthr, sh, s, a, ia, off_ck, off_int)) return st;
     note_kernel("k_tri_int<%s>%s M=%d%s", S::NAME, sizeof(TIO) == 8 ? "" : " f32", M, prof ? " + level profiles" : "");  // (only a launch that succeeded is reported)
     return (int)CRT_OK;
   };
   if (sr) {
     if constexpr (sizeof(TIO) == 8) {
       auto gos = [&](auto kern) {
-        const int st = launch_series(kern, series_grid(a.ncol, sr->nt), nthr, sh, s, a, ia, *sr, off_ck, off_int);
+        const int st = launch_kernel(kern, series_grid(a.ncol, sr->nt), nthr, sh, s, a, ia, *sr, off_ck, off_int);
         if (st == CRT_OK) note_kernel("k_colpre<canopy> + k_colsun + k_tri_int_series<%s> M=%d%s nt=%d", S::NAME, M, prof ? " + level profiles" : "", sr->nt);
         return st;
       };
@@ -800,7 +788,7 @@ int launch_lev_m(const SolveArgs& a, const LevArgs& la, hipStream_t s, const Ser
     if (!lev_series_grid(a.ncol, sr->nt, ls.nslice, &grid)) return CRT_ERR_UNSUPPORTED;
     if (probe) return CRT_OK;
     auto gos = [&](auto kern) {
-      const int st = launch_series(kern, grid, ls.nthr, sh, s, a, la, *sr, ls.per, off_ck, ls.nslice);
+      const int st = launch_kernel(kern, grid, ls.nthr, sh, s, a, la, *sr, ls.per, off_ck, ls.nslice);
       if (st == CRT_OK)
         note_kernel("k_colpre<canopy> + k_colsun + k_tri_lev_series<%s>%s M=%d nsel=%d slice=%d nt=%d", S::NAME, sizeof(TIO) == 8 ? "" : " f32", M,
                     la.nsel, ls.per, sr->nt);
@@ -812,11 +800,7 @@ int launch_lev_m(const SolveArgs& a, const LevArgs& la, hipStream_t s, const Ser
   }
   if (probe) return CRT_OK;
   auto go = [&](auto kern) {
-    if (sh > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
-      return (int)CRT_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.ncol, ls.nslice), dim3(ls.nthr), sh, s, a, la, ls.per, off_ck);
-    if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+    if (const int st = launch_kernel(kern, dim3(a.ncol, ls.nslice), ls.nthr, sh, s, a, la, ls.per, off_ck)) return st;
     note_kernel("k_tri_lev<%s>%s M=%d nsel=%d slice=%d", S::NAME, sizeof(TIO) == 8 ? "" : " f32", M, la.nsel, ls.per);  // (only a launch that succeeded is reported)
     return (int)CRT_OK;
   };
@@ -1282,12 +1266,7 @@ int launch_pipe_generic(const SolveArgs& a, hipStream_t s, int nstore_waves) {
   if (cfg.flat == 2 && a.nb >= 128 / (int)sizeof(TIO) && (ff == CRT_FLAT_FLUSH_WHOLE_LINE || (ff == 0 && wl_default))) cfg.flat = 3;
   const size_t sh = ((size_t)cfg.off_park + (cfg.flat == 3 ? park_doubles<S, TIO>() : 0)) * sizeof(double);
   if (sh > MAX_WG_LDS) return CRT_ERR_UNSUPPORTED;
-  auto kern = k_tri_pipe<S, TIO, M, T, 512, -1>;
-  if (sh > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
-    return CRT_ERR_LAUNCH;
-  hipLaunchKernelGGL(kern, dim3(a.ncol), dim3(nthr), sh, s, a, cfg);
-  if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+  if (const int st = launch_kernel(k_tri_pipe<S, TIO, M, T, 512, -1>, dim3(a.ncol), nthr, sh, s, a, cfg)) return st;
   note_kernel("k_tri_pipe<%s,%s> %s M=%d T=%d store_waves=%d lds=%zu", S::NAME, sizeof(TIO) == 8 ? "f64" : "f32", cfg.flat == 3 ? "whole-line flat-flush" : cfg.flat ? "flat-flush" : "generic-flush", M, T,
               nstore_waves, sh);  // (only a launch that succeeded is reported)
   return (int)CRT_OK;
@@ -1320,12 +1299,7 @@ int launch_tri_pack(const SolveArgs& a, hipStream_t s) {
     // 0.695 -> 0.775 (ragged 0.63 -> 0.72), but 1e5 x 38 x 100 0.71 -> 0.71 / 0.60 -> 0.57 (55 KB of LDS per pack); zq 1e5 x 38 x 100 0.80 -> 0.83,
     // 1.5e5 x 38 x 60 0.78 -> 0.78, 36 bands 0.83 -> 0.81: taken for n79 while the pack stays below 40 KB, not for zq
     if (a.nb > 32 && ncw_set == 0 && (std::is_same<S, typename UniformOf<S>::type>::value || sh > 40 * 1024)) return CRT_ERR_UNSUPPORTED;
-    auto kern = k_tri_pipe<S, TIO, M, T, 512, 3>;
-    if (sh > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
-      return CRT_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3((a.ncol + cfg.cpw - 1) / cfg.cpw), dim3(cfg.ncomp + 64 * nsw), sh, s, a, cfg);
-    if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+    if (const int st = launch_kernel(k_tri_pipe<S, TIO, M, T, 512, 3>, dim3((a.ncol + cfg.cpw - 1) / cfg.cpw), cfg.ncomp + 64 * nsw, sh, s, a, cfg)) return st;
     note_kernel("k_tri_pipe<%s,%s> packed columns=%d compute_waves=%d register-staged(2 pairs) M=%d T=%d store_waves=%d lds=%zu", S::NAME,
                 sizeof(TIO) == 8 ? "f64" : "f32", cfg.cpw, ncw, M, T, nsw, sh);
     return (int)CRT_OK;
@@ -1351,11 +1325,7 @@ int launch_pipe_mt(const SolveArgs& a, hipStream_t s, int nstore_waves, bool reg
   const bool narrow_rs = T == 4 && M == 8 && regstage && nthr <= 512 && T * (a.nb / 2) <= 2 * 64 * nstore_waves &&
                          !(a.tune.tile_flags & CRT_TILE_FLAG_FOUR_PAIR_STORE);
   auto go = [&](auto kern) {
-    if (sh > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
-      return (int)CRT_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.ncol), dim3(nthr), sh, s, a, cfg);
-    if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+    if (const int st = launch_kernel(kern, dim3(a.ncol), nthr, sh, s, a, cfg)) return st;
     note_kernel("k_tri_pipe<%s,%s> %s M=%d T=%d store_waves=%d lds=%zu", S::NAME, sizeof(TIO) == 8 ? "f64" : "f32",
                 regstage ? (narrow_rs ? "register-staged(2 pairs)" : "register-staged") : "double-buffered", M, T, nstore_waves, sh);  // (only a launch that succeeded is reported)
     return (int)CRT_OK;

@@ -505,12 +505,7 @@ int launch_zqpa_generic2(const SolveArgs& a, hipStream_t s, int nsw) {
   for (int i = 0; i < 4; ++i) cfg.out[i] = a.o[i];
   const size_t sh = ((size_t)cfg.off_park + (cfg.flat == 3 ? park_doubles<ZqPaOut, TIO>() : 0)) * sizeof(double);
   if (sh > MAX_WG_LDS / 2) return CRT_ERR_UNSUPPORTED;
-  auto kern = k_zqpa_pipe2<TIO, M, T, 512, -1>;
-  if (sh > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
-    return (int)CRT_ERR_LAUNCH;
-  hipLaunchKernelGGL(kern, dim3(a.ncol), dim3(nthr), sh, s, g, cfg);
-  if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+  if (const int st = launch_kernel(k_zqpa_pipe2<TIO, M, T, 512, -1>, dim3(a.ncol), nthr, sh, s, g, cfg)) return st;
   note_kernel("k_zqpa_pipe2<%s> %s M=%d T=%d store_waves=%d lds=%zu", sizeof(TIO) == 8 ? "f64" : "f32", cfg.flat == 3 ? "whole-line flat-flush" : "flat-flush", M, T,
               nsw, sh);
   return (int)CRT_OK;
@@ -543,11 +538,7 @@ int launch_zqpa_fused2(const SolveArgs& a, hipStream_t s, int nsw, size_t lds_ca
   const size_t sh = ((size_t)cfg.off_tile + (size_t)(REGSTAGE ? 1 : 2) * 2 * T * a.nb) * sizeof(double);
   if (sh > lds_cap) return CRT_ERR_UNSUPPORTED;
   auto go = [&](auto kern) {
-    if (sh > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
-      return (int)CRT_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.ncol), dim3(nthr), sh, s, g, cfg);
-    if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+    if (const int st = launch_kernel(kern, dim3(a.ncol), nthr, sh, s, g, cfg)) return st;
     note_kernel("k_zqpa_pipe2<%s> %s M=%d T=%d store_waves=%d lds=%zu", sizeof(TIO) == 8 ? "f64" : "f32", REGSTAGE ? "register-staged" : "double-buffered",
                 M, T, nsw, sh);  // (only a launch that succeeded is reported)
     return (int)CRT_OK;
@@ -609,11 +600,7 @@ int launch_zqpa_fused(const SolveArgs& a, hipStream_t s, int nsw, size_t lds_cap
   const size_t sh = ((size_t)cfg.off_halo + 2 * 3 * a.nb) * sizeof(double);
   if (sh > lds_cap) return CRT_ERR_UNSUPPORTED;
   auto go = [&](auto kern) {
-    if (sh > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
-      return (int)CRT_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.ncol), dim3(nthr), sh, s, g, cfg);
-    if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+    if (const int st = launch_kernel(kern, dim3(a.ncol), nthr, sh, s, g, cfg)) return st;
     note_kernel("k_zqpa_pipe<%s%s> M=%d T=%d store_waves=%d lds=%zu", sizeof(TIO) == 8 ? "f64" : "f32", flat ? ",flat" : "", M, T, nsw, sh);  // (only a launch that succeeded is reported)
     return (int)CRT_OK;
   };
@@ -907,18 +894,14 @@ int launch_zqpa_int_m(const SolveArgs& a, const IntArgs& ia, hipStream_t s, int 
   g.nz = Mg;
   for (int i = 0; i < 7; ++i) g.o[i] = nullptr;
   auto go = [&](auto kern) {
-    if (sh > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
-      return (int)CRT_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.ncol), dim3(nthr), sh, s, g, ia, a.nz, off_ck, off_int);
-    if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+    if (const int st = launch_kernel(kern, dim3(a.ncol), nthr, sh, s, g, ia, a.nz, off_ck, off_int)) return st;
     note_kernel("k_zqpa_int<zq_pa>%s M=%d grid=%d%s", sizeof(TIO) == 8 ? "" : " f32", M, Mg, PROF ? " + level profiles" : "");  // (only a launch that succeeded is reported)
     return (int)CRT_OK;
   };
   if (sr) {
     if constexpr (sizeof(TIO) == 8) {
       auto gos = [&](auto kern) {
-        const int st = launch_series(kern, series_grid(a.ncol, sr->nt), nthr, sh, s, g, ia, *sr, off_ck, off_int);
+        const int st = launch_kernel(kern, series_grid(a.ncol, sr->nt), nthr, sh, s, g, ia, *sr, off_ck, off_int);
         if (st == CRT_OK)
           note_kernel("k_colpre<canopy> + k_colsun + k_zqpa_int_series<zq_pa> M=%d grid=%d%s%s nt=%d", M, Mg, PROF ? " + level profiles" : "",
                       SPLIT ? "" : " net flux", sr->nt);
@@ -1124,7 +1107,7 @@ int launch_zqpa_lev_io(const SolveArgs& a, const LevArgs& la, hipStream_t s, con
     if (!lev_series_grid(a.ncol, sr->nt, ls.nslice, &grid)) return CRT_ERR_UNSUPPORTED;
     if (probe) return CRT_OK;
     auto gos = [&](auto kern) {
-      const int st = launch_series(kern, grid, ls.nthr, L.bytes, s, g, la, *sr, ls.per, L.off_map, L.off_ck, L.off_val, ls.nslice);
+      const int st = launch_kernel(kern, grid, ls.nthr, L.bytes, s, g, la, *sr, ls.per, L.off_map, L.off_ck, L.off_val, ls.nslice);
       if (st == CRT_OK)
         note_kernel("k_colpre<canopy> + k_colsun + k_zqpa_lev_series<zq_pa>%s M=%d grid=%d nsel=%d slice=%d nt=%d", sizeof(TIO) == 8 ? "" : " f32", M,
                     Mg, la.nsel, ls.per, sr->nt);
@@ -1134,11 +1117,7 @@ int launch_zqpa_lev_io(const SolveArgs& a, const LevArgs& la, hipStream_t s, con
   }
   if (probe) return CRT_OK;
   auto go = [&](auto kern) {
-    if (L.bytes > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.bytes) != hipSuccess)
-      return (int)CRT_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.ncol, ls.nslice), dim3(ls.nthr), L.bytes, s, g, la, a.nz, ls.per, L.off_map, L.off_ck, L.off_val);
-    if (hipGetLastError() != hipSuccess) return (int)CRT_ERR_LAUNCH;
+    if (const int st = launch_kernel(kern, dim3(a.ncol, ls.nslice), ls.nthr, L.bytes, s, g, la, a.nz, ls.per, L.off_map, L.off_ck, L.off_val)) return st;
     note_kernel("k_zqpa_lev<zq_pa>%s M=%d grid=%d nsel=%d slice=%d", sizeof(TIO) == 8 ? "" : " f32", M, Mg, la.nsel, ls.per);  // (only a launch that succeeded is reported)
     return (int)CRT_OK;
   };
@@ -1241,11 +1220,7 @@ int launch_zqpa(const SolveArgs& a, double* scratch, hipStream_t s) {
   for (int i = 0; i < 4; ++i) ia.o[i] = a.o[i];
   const size_t sh = a.reclen * sizeof(double);
   if (sh > MAX_WG_LDS) return CRT_ERR_UNSUPPORTED;
-  if (sh > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(k_zqpa_interp<double>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) != hipSuccess)
-    return CRT_ERR_LAUNCH;
-  hipLaunchKernelGGL((k_zqpa_interp<double>), dim3(a.ncol), dim3(256), sh, s, ia);
-  if (hipGetLastError() != hipSuccess) return CRT_ERR_LAUNCH;
+  if ((st = launch_kernel(k_zqpa_interp<double>, dim3(a.ncol), 256, sh, s, ia)) != CRT_OK) return st;
   note_kernel("zq_pa two-kernel path: grid solve %s + k_zqpa_interp", grid_kernel);  // (only a launch that succeeded is reported)
   return CRT_OK;
 }

@@ -24,6 +24,8 @@ the HIP path.
 import torch
 import torch.distributed as dist
 
+from .batched import PROFILE_KEYS, bandsum_shapes  # (imports torch and ctypes only: the library is not loaded)
+
 KEYS = ("aI", "aI_sl", "aI_sh", "totals")
 # what travels: aI = aI_sl + aI_sh (model.py:633-635), so the total is NOT sent -- it is re-formed from the reduced sunlit and shaded
 # parts after the all-reduce (a third less on the wire; at 8 ranks the ring all-reduce of config 4's messages is comparable to a
@@ -33,7 +35,6 @@ MSG_KEYS = ("aI_sl", "aI_sh", "totals")
 # F = I_dr / mu + 2 (I_df_u + I_df_d) and I_d = I_dr + I_df_d are linear in the three level sums (api.hip store_level_profiles,
 # model.py:425) and are re-formed after the reduce with aI (crt_hip_bandsum_finish_f64): 1803 instead of 2403 doubles per column at
 # nz = 100, ngroup = 3
-PROFILE_KEYS = ("aI_dr", "I_dr", "I_df_d", "I_df_u", "F", "I_d")  # = batched.PROFILE_KEYS
 PROFILE_MSG_KEYS = ("aI_dr", "I_dr", "I_df_d", "I_df_u")
 
 
@@ -62,21 +63,12 @@ def _world(group):
     return 1, 0
 
 
-def _shapes(ncol, nz, ng, profiles=False):
-    sh = {"aI": (ncol, nz - 1, ng), "aI_sl": (ncol, nz - 1, ng), "aI_sh": (ncol, nz - 1, ng), "totals": (ncol, ng, 4)}
-    if profiles:  # batched.bandsum_shapes(..., profiles=True)
-        sh["aI_dr"] = (ncol, nz - 1, ng)
-        for k in PROFILE_KEYS[1:]:
-            sh[k] = (ncol, nz, ng)
-    return sh
-
-
 class _Tile:
     """One column tile of a band-sharded step: its packed message buffer, views into it, and the launch closure."""
 
     def __init__(self, clo, chi, nz, ng, like, profiles=False):
         self.clo, self.chi = clo, chi
-        shapes = _shapes(chi - clo, nz, ng, profiles)
+        shapes = bandsum_shapes(chi - clo, nz, ng, profiles)
         msg = MSG_KEYS + (PROFILE_MSG_KEYS if profiles else ())
 
         def numel(k):

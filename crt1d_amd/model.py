@@ -170,19 +170,13 @@ class Model:
         self.absorption = ab
         return self
 
-    def run_series(self, psi, I_dr0_all=None, I_df0_all=None, bands=("PAR", "NIR", "solar"), calc_PFD=False):
-        """The band-integrated outputs of this canopy for a series of sun states in ONE device call
-        (:class:`crt1d_amd.batched.IntegratedSeriesPlan`, ``ncol = 1``): what the loop
-
-            for t: m.update_p(psi=psi[t], I_dr0_all=..., I_df0_all=...); m.run(); m.calc_absorption(); diagnostics.band(m.to_dataset(), ...)
-
-        returns, stacked over a leading time axis.  ``psi``: ``(nt,)`` radians; ``I_dr0_all``, ``I_df0_all``: ``(nt, n_wl)``, ``(n_wl,)``
-        or ``None`` (the case's own spectra at every step).  Returns ``{band_name: {variable: array}}`` with the level profiles
-        ``I_dr, I_df_d, I_df_u, F, I_d`` ``(nt, nz)`` and the seven absorption entries ``(nt, nz-1)``; ``calc_PFD=True`` adds the
-        photon-flux variants under the reference's names (``I`` -> ``PFD``).  The model's own state (``psi``, ``out``) is not changed."""
+    def _series_inputs(self, psi, I_dr0_all, I_df0_all, what):
+        """``(scheme, cols, bands, sun)`` of a sun-angle series on this canopy (``ncol = 1``): the psi series and the spectra validated and
+        broadcast to ``(nt, n_wl)``, the leaf-angle description sampled per step.  ``what`` names the kernel in the error of a scheme
+        without one ("integrated" / "level")."""
         import torch
 
-        from . import _lib, batched, diagnostics, spectra
+        from . import _lib, batched
         from .solvers.common import _describe, _sample
 
         self._check_inputs()
@@ -201,7 +195,7 @@ class Model:
             series.append(np.ascontiguousarray(np.broadcast_to(v, (nt, nb))))
         scheme = self.scheme["name"] if self.scheme.get("name") in _lib.SCHEME_IDS else self.scheme.get("short_name")
         if scheme not in _lib.SCHEME_IDS:
-            raise ValueError(f"scheme {scheme!r} has no integrated kernel")
+            raise ValueError(f"scheme {scheme!r} has no {what} kernel")
         mu_s = 0.501  # the solvers' defaults, as `run()` without options
         G_fn, K_b_fn = p.get("G_fn"), p.get("K_b_fn")
         g = _describe(float(psi[0]), K_b_fn, G_fn, mu_s)
@@ -217,6 +211,25 @@ class Model:
         )
         b = batched.Bands(None, None, t(p["leaf_r"]), t(p["leaf_t"]), t(p["soil_r"]))
         sun = batched.SunSeries(t(psi)[None, :], t(series[0])[None], t(series[1])[None], None if g_at is None else t(g_at)[None, :])
+        return scheme, cols, b, sun
+
+    def run_series(self, psi, I_dr0_all=None, I_df0_all=None, bands=("PAR", "NIR", "solar"), calc_PFD=False):
+        """The band-integrated outputs of this canopy for a series of sun states in ONE device call
+        (:class:`crt1d_amd.batched.IntegratedSeriesPlan`, ``ncol = 1``): what the loop
+
+            for t: m.update_p(psi=psi[t], I_dr0_all=..., I_df0_all=...); m.run(); m.calc_absorption(); diagnostics.band(m.to_dataset(), ...)
+
+        returns, stacked over a leading time axis.  ``psi``: ``(nt,)`` radians; ``I_dr0_all``, ``I_df0_all``: ``(nt, n_wl)``, ``(n_wl,)``
+        or ``None`` (the case's own spectra at every step).  Returns ``{band_name: {variable: array}}`` with the level profiles
+        ``I_dr, I_df_d, I_df_u, F, I_d`` ``(nt, nz)`` and the seven absorption entries ``(nt, nz-1)``; ``calc_PFD=True`` adds the
+        photon-flux variants under the reference's names (``I`` -> ``PFD``).  The model's own state (``psi``, ``out``) is not changed."""
+        import torch
+
+        from . import _lib, batched, spectra
+
+        scheme, cols, b, sun = self._series_inputs(psi, I_dr0_all, I_df0_all, "integrated")
+        p = self._p
+        t = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float64)).to(cols.device)  # noqa: E731
         names = list(bands)
         wle = np.asarray(p["wle"], dtype=float)
         weights = [(n, "", w) for n, w in zip(names, spectra.band_weights(wle, names))]
@@ -247,43 +260,9 @@ class Model:
         ``I_df0_all`` as for :meth:`run_series`; ``levels`` as for :func:`crt1d_amd.batched.normalize_levels` (an int or ints, negatives
         from the top; returned rows are in ascending level order).  Returns ``{"I_dr", "I_df_d", "I_df_u", "F"}`` as NumPy arrays
         ``(nt, nsel, n_wl)``.  The model's own state (``psi``, ``out``) is not changed."""
-        import torch
+        from . import batched
 
-        from . import _lib, batched
-        from .solvers.common import _describe, _sample
-
-        self._check_inputs()
-        p = self._p
-        psi = np.atleast_1d(np.asarray(psi, dtype=np.float64))
-        if psi.ndim != 1 or psi.size < 1:
-            raise ValueError("`psi` must be a non-empty 1-D series of solar zenith angles")
-        if not np.all((psi >= 0) & (psi < np.pi / 2)):
-            raise ValueError("psi must be in [0, pi/2)")
-        nt, nb = psi.size, self.nwl
-        series = []
-        for name, v in (("I_dr0_all", I_dr0_all), ("I_df0_all", I_df0_all)):
-            v = np.asarray(p[name] if v is None else v, dtype=np.float64)
-            if v.shape not in ((nb,), (nt, nb)):
-                raise ValueError(f"`{name}` must be (n_wl,) or (nt, n_wl) = ({nt}, {nb})")
-            series.append(np.ascontiguousarray(np.broadcast_to(v, (nt, nb))))
-        scheme = self.scheme["name"] if self.scheme.get("name") in _lib.SCHEME_IDS else self.scheme.get("short_name")
-        if scheme not in _lib.SCHEME_IDS:
-            raise ValueError(f"scheme {scheme!r} has no level kernel")
-        mu_s = 0.501  # the solvers' defaults, as `run()` without options
-        G_fn, K_b_fn = p.get("G_fn"), p.get("K_b_fn")
-        g = _describe(float(psi[0]), K_b_fn, G_fn, mu_s)
-        g_at = None
-        if g["g_table"] is not None:  # a callable: sampled at the quadrature nodes once, G_fn(psi_t) per step
-            g_at = _sample(G_fn, psi) if G_fn is not None else _sample(K_b_fn, psi) * np.cos(psi)
-        dev = torch.device("cuda", torch.cuda.current_device())
-        t = lambda a: torch.as_tensor(np.atleast_1d(np.asarray(a, dtype=np.float64))).to(dev)  # noqa: E731
-        cols = batched.Columns(
-            psi=t(psi[:1]), lai=t(p["lai"])[None, :], g_kind=torch.tensor([g["g_kind"]], dtype=torch.int32, device=dev),
-            g_param=t(g["g_param"]), mla=None if p.get("mla") is None else t(float(p["mla"])),
-            g_at_psi=None if g_at is None else t(g_at[:1]), g_table=None if g["g_table"] is None else t(g["g_table"])[None, :],
-        )
-        b = batched.Bands(None, None, t(p["leaf_r"]), t(p["leaf_t"]), t(p["soil_r"]))
-        sun = batched.SunSeries(t(psi)[None, :], t(series[0])[None], t(series[1])[None], None if g_at is None else t(g_at)[None, :])
+        scheme, cols, b, sun = self._series_inputs(psi, I_dr0_all, I_df0_all, "level")
         out = batched.solve_levels_series(scheme, cols, b, sun, levels)
         return {k: v[0].cpu().numpy() for k, v in out.items()}
 

@@ -180,3 +180,83 @@ def test_set_tune_rejects_unknown_keys():
     for bad in (_lib.NTUNE, -1, "TUNE_TRI_M", 8.0, None):
         with pytest.raises(ValueError, match="unknown crt_options.tune key"):
             _lib.set_tune(o, {bad: 1})
+
+
+# restype and argtypes of every binding, by ctypes type name (``c_size_t`` is ``c_ulong`` and ``c_int64`` ``c_long`` on LP64 Linux, the only
+# platform ROCm has; ``LP_X`` = ``POINTER(X)``), recorded from the hand-written ``load()`` this table replaced.  ``None``: argtypes unset.
+_SOLVE = "LP_CrtColumns LP_CrtBands LP_CrtOptions LP_CrtOutputs c_void_p c_ulong c_void_p"
+_SIGNATURES = {
+    "crt_hip_abi_version": ("c_int", None),
+    "crt_hip_strerror": ("c_char_p", "c_int"),
+    "crt_hip_workspace_bytes": ("c_ulong", "c_int c_int c_int"),
+    "crt_hip_workspace_bytes_nb": ("c_ulong", "c_int c_int c_int c_int"),
+    "crt_hip_quad_nodes": ("c_int", "c_double LP_c_double"),
+    "crt_hip_solve_f64": ("c_int", "c_int " + _SOLVE),
+    "crt_hip_2s_f64": ("c_int", _SOLVE),
+    "crt_hip_4s_f64": ("c_int", _SOLVE),
+    "crt_hip_n79_f64": ("c_int", _SOLVE),
+    "crt_hip_zq_f64": ("c_int", _SOLVE),
+    "crt_hip_bl_f64": ("c_int", _SOLVE),
+    "crt_hip_g77_f64": ("c_int", _SOLVE),
+    "crt_hip_bf_f64": ("c_int", _SOLVE),
+    "crt_hip_zq_pa_f64": ("c_int", _SOLVE),
+    "crt_hip_solve_f32": ("c_int", "c_int " + _SOLVE),
+    "crt_hip_2s_f32": ("c_int", _SOLVE),
+    "crt_hip_4s_f32": ("c_int", _SOLVE),
+    "crt_hip_n79_f32": ("c_int", _SOLVE),
+    "crt_hip_zq_f32": ("c_int", _SOLVE),
+    "crt_hip_bl_f32": ("c_int", _SOLVE),
+    "crt_hip_g77_f32": ("c_int", _SOLVE),
+    "crt_hip_bf_f32": ("c_int", _SOLVE),
+    "crt_hip_zq_pa_f32": ("c_int", _SOLVE),
+    "crt_hip_absorb_bandsum_f64": ("c_int", "LP_CrtColumns LP_CrtBands c_void_p c_void_p c_void_p c_void_p c_int c_void_p c_void_p c_void_p c_void_p c_void_p"),
+    "crt_hip_absorb_bandsum2_f64": ("c_int", "LP_CrtColumns LP_CrtBands c_void_p c_void_p c_void_p c_void_p c_int LP_CrtBandsumOut c_void_p"),
+    "crt_hip_integrated_f64": ("c_int", "c_int LP_CrtColumns LP_CrtBands LP_CrtOptions c_void_p c_int c_void_p c_void_p c_void_p c_void_p c_void_p c_ulong c_void_p"),
+    "crt_hip_integrated2_f64": ("c_int", "c_int LP_CrtColumns LP_CrtBands LP_CrtOptions c_void_p c_int LP_CrtBandsumOut c_void_p c_ulong c_void_p"),
+    "crt_hip_absorb_f64": ("c_int", "LP_CrtColumns LP_CrtBands c_void_p c_void_p c_void_p LP_c_void_p c_void_p c_void_p c_void_p"),
+    "crt_hip_absorb_bandsum_f32": ("c_int", "LP_CrtColumns LP_CrtBands c_void_p c_void_p c_void_p c_void_p c_int c_void_p c_void_p c_void_p c_void_p c_void_p"),
+    "crt_hip_absorb_bandsum2_f32": ("c_int", "LP_CrtColumns LP_CrtBands c_void_p c_void_p c_void_p c_void_p c_int LP_CrtBandsumOut c_void_p"),
+    "crt_hip_integrated_f32": ("c_int", "c_int LP_CrtColumns LP_CrtBands LP_CrtOptions c_void_p c_int c_void_p c_void_p c_void_p c_void_p c_void_p c_ulong c_void_p"),
+    "crt_hip_integrated2_f32": ("c_int", "c_int LP_CrtColumns LP_CrtBands LP_CrtOptions c_void_p c_int LP_CrtBandsumOut c_void_p c_ulong c_void_p"),
+    "crt_hip_series_workspace_bytes": ("c_ulong", "c_int c_int c_int c_int c_int"),
+    "crt_hip_integrated_series_f64": ("c_int", "c_int LP_CrtColumns LP_CrtBands LP_CrtSunSeries LP_CrtOptions c_void_p c_int LP_CrtBandsumOut c_void_p c_ulong c_void_p"),
+    "crt_hip_levels_f64": ("c_int", "c_int LP_CrtColumns LP_CrtBands LP_CrtOptions LP_c_int c_int LP_CrtOutputs c_void_p c_ulong c_void_p"),
+    "crt_hip_levels_f32": ("c_int", "c_int LP_CrtColumns LP_CrtBands LP_CrtOptions LP_c_int c_int LP_CrtOutputs c_void_p c_ulong c_void_p"),
+    "crt_hip_levels_series_workspace_bytes": ("c_ulong", "c_int c_int c_int c_int"),
+    "crt_hip_levels_series_f64": ("c_int", "c_int LP_CrtColumns LP_CrtBands LP_CrtSunSeries LP_CrtOptions LP_c_int c_int LP_CrtOutputs c_void_p c_ulong c_void_p"),
+    "crt_hip_levels_series_f32": ("c_int", "c_int LP_CrtColumns LP_CrtBands LP_CrtSunSeriesF32 LP_CrtOptions LP_c_int c_int LP_CrtOutputs c_void_p c_ulong c_void_p"),
+    "crt_hip_absorb_f32": ("c_int", "LP_CrtColumns LP_CrtBands c_void_p c_void_p c_void_p LP_c_void_p c_void_p c_void_p c_void_p"),
+    "crt_hip_bandsum_finish_f64": ("c_int", "LP_CrtColumns c_int LP_CrtBandsumOut c_void_p"),
+    "crt_hip_band_reduce_f64": ("c_int", "c_void_p c_long c_int c_void_p c_int c_void_p c_void_p"),
+    "crt_hip_tau_d_f64": ("c_int", "c_void_p c_void_p c_long c_int c_void_p c_void_p"),
+    "crt_hip_smear_tuv_f64": ("c_int", "c_void_p c_long c_int c_void_p c_int c_void_p c_int c_void_p c_void_p"),
+    "crt_hip_lai_beta_f64": ("c_int", "c_void_p c_void_p c_void_p c_int c_int c_void_p c_void_p c_void_p c_void_p"),
+    "crt_hip_buffer_alloc_set": ("c_int", "c_int LP_c_ulong LP_c_void_p"),
+    "crt_hip_buffer_alloc": ("c_int", "c_ulong LP_c_void_p"),
+    "crt_hip_buffer_free": ("c_int", "c_void_p"),
+    "crt_hip_buffer_trim": ("c_int", ""),
+    "crt_hip_buffer_set_retain": ("c_int", "c_ulong"),
+    "crt_hip_buffer_describe": ("c_int", "c_void_p c_char_p c_ulong"),
+    "crt_hip_buffer_stats": ("c_int", "LP_c_long"),
+    "crt_hip_last_kernel": ("c_char_p", ""),
+    "crt_hip_probe_fill_f64": ("c_int", "c_void_p c_ulong c_double c_void_p"),
+    "crt_hip_probe_copy_f64": ("c_int", "c_void_p c_void_p c_ulong c_void_p"),
+    "crt_hip_probe_store_set_f64": ("c_int", "LP_c_void_p c_int c_long c_long c_int c_double c_void_p"),
+    "crt_hip_probe_math_f64": ("c_int", "c_void_p c_ulong c_void_p c_void_p c_void_p c_void_p"),
+}
+
+
+def test_ctypes_signatures_are_pinned(lib):
+    from crt1d_amd import _lib
+
+    assert isinstance(_lib.EXPORTS, list) and len(_lib.EXPORTS) == 57 == len(set(_lib.EXPORTS)) == len(_SIGNATURES)
+    assert sorted(_lib.EXPORTS) == sorted(_SIGNATURES) == _declared()  # the header, the binding table and this table name the same symbols
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        f = getattr(lib, name)
+        assert f.restype.__name__ == restype, name
+        got = None if f.argtypes is None else [t.__name__ for t in f.argtypes]
+        assert got == (None if argtypes is None else argtypes.split()), name
+    # the pointer types are the binding's own struct classes, not look-alikes
+    assert lib.crt_hip_levels_series_f32.argtypes[3] is ctypes.POINTER(_lib.CrtSunSeriesF32)
+    assert lib.crt_hip_levels_series_f64.argtypes[3] is ctypes.POINTER(_lib.CrtSunSeries)
+    assert lib.crt_hip_integrated2_f64.argtypes[6] is ctypes.POINTER(_lib.CrtBandsumOut)
