@@ -203,6 +203,22 @@ def _signatures():
 _SIGNATURES = _signatures()
 EXPORTS = list(_SIGNATURES)
 
+# leaf-inclination PDFs (include/crt1d_hip_leaf.h): the same library, a header and a table of their own -- EXPORTS stays the symbol set of
+# include/crt1d_hip.h.  (The PDF kind ids are leaf_angle.PDF_*.)
+LEAF_NGL, LEAF_NMLA = 48, 64
+
+
+def _leaf_signatures():
+    dp, i32, dbl, ok = ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.c_double, ctypes.c_int
+    return {
+        "crt_hip_leaf_pdf_nodes_f64": (ok, [dp, dp, dp, dp]),
+        "crt_hip_g_from_pdf_f64": (ok, [_vp, _vp, i32, dbl, _vp, i32, _vp, _vp, _vp, _vp]),
+    }
+
+
+_LEAF_SIGNATURES = _leaf_signatures()
+LEAF_EXPORTS = list(_LEAF_SIGNATURES)
+
 _lib = None
 
 
@@ -225,7 +241,7 @@ def load():
     import torch  # noqa: F401
 
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in _SIGNATURES.items():
+    for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:
@@ -260,3 +276,14 @@ def quad_nodes(mu_s=0.501):
     buf = (ctypes.c_double * NQ)()
     check(load().crt_hip_quad_nodes(float(mu_s), buf), "crt_hip_quad_nodes")
     return np.frombuffer(buf, dtype=np.float64).copy()
+
+
+def leaf_pdf_nodes():
+    """The Gauss-Legendre rules of ``crt_hip_g_from_pdf_f64`` on the unit interval: ``(x, w, x_mla, w_mla)``, the ``LEAF_NGL``-point rule
+    of each panel of G(psi) and the ``LEAF_NMLA``-point rule of the mean leaf angle (include/crt1d_hip_leaf.h)."""
+    import numpy as np
+
+    x, w = (ctypes.c_double * LEAF_NGL)(), (ctypes.c_double * LEAF_NGL)()
+    xm, wm = (ctypes.c_double * LEAF_NMLA)(), (ctypes.c_double * LEAF_NMLA)()
+    check(load().crt_hip_leaf_pdf_nodes_f64(x, w, xm, wm), "crt_hip_leaf_pdf_nodes_f64")
+    return tuple(np.frombuffer(b, dtype=np.float64).copy() for b in (x, w, xm, wm))

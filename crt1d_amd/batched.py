@@ -170,6 +170,54 @@ class Columns:
         t = _host_reader(d, device)
         return cls(t("psi"), t("lai"), t("g_kind"), t("g_param"), t("mla"), t("g_at_psi"), t("g_table"))
 
+    @classmethod
+    def from_leaf_pdf(cls, psi, lai, pdf_kind, pdf_param, mu_s=0.501):
+        """Columns described by their leaf-inclination PDFs (:func:`leaf_pdf_tables`): ``g_kind = G_TABLE`` with ``g_table``, ``g_at_psi``
+        and ``mla`` (the PDF's mean leaf angle) formed on the device.  ``mu_s`` must be the one the solve is given."""
+        psi = _f64(psi, "psi")
+        if psi.ndim != 1:
+            raise ValueError("psi must be (ncol,)")
+        g_table, g_at_psi, mla = leaf_pdf_tables(pdf_kind, pdf_param, mu_s=mu_s, psi=psi)
+        kind = torch.full((psi.shape[0],), 6, dtype=torch.int32, device=psi.device)
+        return cls(psi, lai, kind, torch.zeros_like(psi), mla, g_at_psi, g_table)
+
+
+def leaf_pdf_tables(pdf_kind, pdf_param, *, mu_s=0.501, psi=None):
+    """G(psi) of ``ncol`` leaf-inclination PDFs in one launch (``crt_hip_g_from_pdf_f64``, include/crt1d_hip_leaf.h).
+
+    ``pdf_kind`` ``(ncol,)``: ``leaf_angle.PDF_*`` ids; ``pdf_param`` ``(ncol, 2)``: ``x`` or ``(a, b)`` (see :class:`crt1d_amd.leaf_angle.LeafPDF`);
+    tensors on the GPU, or anything ``torch.as_tensor`` takes (moved there).  ``psi``: ``None``, ``(ncol,)`` -- each column's sun angle -- or
+    ``(ncol, nt)``, the sun angles of a series.  Returns CUDA tensors ``g_table (ncol, NQ)`` (G at ``_lib.quad_nodes(mu_s)``),
+    ``g_at_psi`` (the shape of ``psi``; ``(ncol, 0)`` without it) and ``mla (ncol,)`` in degrees: ``Columns.g_table / g_at_psi / mla``, and
+    for a series ``SunSeries.g_at_psi`` directly.  An unknown kind, ``x <= 0`` or a ``(a, b)`` whose PDF goes negative is a ValueError,
+    found by the library before the launch (it reads the descriptors back once: one stream synchronisation)."""
+    given = [t for t in (pdf_kind, pdf_param, psi) if isinstance(t, torch.Tensor) and t.is_cuda]
+    dev = given[0].device if given else torch.device("cuda", torch.cuda.current_device())
+    # (dtype given to as_tensor: Python floats would otherwise pass through torch's default float32 and x = 0.3 arrive as 0.30000001)
+    as_f64 = lambda v: (v if isinstance(v, torch.Tensor) else torch.as_tensor(v, dtype=torch.float64)).to(device=dev, dtype=torch.float64)  # noqa: E731
+    kind = torch.as_tensor(pdf_kind).to(device=dev, dtype=torch.int32).contiguous()
+    param = as_f64(pdf_param).contiguous()
+    if kind.ndim != 1 or param.shape != (kind.shape[0], 2):
+        raise ValueError("pdf_kind must be (ncol,) and pdf_param (ncol, 2)")
+    ncol = kind.shape[0]
+    if psi is None:
+        ps = torch.empty((ncol, 0), dtype=torch.float64, device=dev)
+    else:
+        ps = as_f64(psi).contiguous()
+        if ps.ndim not in (1, 2) or ps.shape[0] != ncol:
+            raise ValueError("psi must be (ncol,) or (ncol, nt)")
+    npsi = ps.numel() // ncol if ncol else 0
+    g_table = torch.empty((ncol, _lib.NQ), dtype=torch.float64, device=dev)
+    g_at_psi = torch.empty_like(ps)
+    mla = torch.empty((ncol,), dtype=torch.float64, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        st = lib.crt_hip_g_from_pdf_f64(kind.data_ptr(), param.data_ptr(), ncol, float(mu_s), ps.data_ptr() if npsi else None, npsi,
+                                        g_table.data_ptr(), g_at_psi.data_ptr() if npsi else None, mla.data_ptr(),
+                                        torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(st, "crt_hip_g_from_pdf_f64")
+    return g_table, g_at_psi, mla
+
 
 @dataclass
 class Bands:

@@ -5,8 +5,8 @@ NumPy ``(nz, nb)`` arrays back -- the ownership/return conventions of ``crt1d/so
 
 ``K_b_fn`` / ``G_fn`` are arbitrary callables in the reference (``variables.yml:137-162``).  A kernel cannot call
 them, so: a :class:`crt1d_amd.leaf_angle.GFunction` (or anything tagged with one) is evaluated in closed form on
-device; any other callable is sampled on the host at the library's fixed quadrature nodes
-(``crt_hip_quad_nodes``) and shipped as a table.
+device; a :class:`crt1d_amd.leaf_angle.LeafPDF` is integrated into its table by the device (``crt_hip_g_from_pdf_f64``); any other
+callable is sampled on the host at the library's fixed quadrature nodes (``crt_hip_quad_nodes``) and shipped as a table.
 """
 
 import math
@@ -15,7 +15,7 @@ import warnings
 import numpy as np
 
 from .. import _lib, batched
-from ..leaf_angle import G_TABLE, describe_G
+from ..leaf_angle import G_TABLE, LeafPDF, describe_G
 
 
 class KbFunction:
@@ -89,6 +89,10 @@ def _describe(psi, K_b_fn, G_fn, mu_s):
         d = describe_G(getattr(K_b_fn, "gfunction", None)) if hasattr(K_b_fn, "gfunction") else None
     if d is not None:
         return dict(g_kind=d[0], g_param=d[1], g_at_psi=None, g_table=None)
+    pdf = G_fn if G_fn is not None else getattr(K_b_fn, "G_fn", None)
+    if isinstance(pdf, LeafPDF):  # the table and G(psi) from the device, one launch
+        table, g_at_psi, _ = pdf.tables(psi, mu_s)
+        return dict(g_kind=G_TABLE, g_param=0.0, g_at_psi=float(g_at_psi[0]), g_table=table)
     nodes = _lib.quad_nodes(mu_s)
     if G_fn is not None:
         table = _sample(G_fn, nodes)
