@@ -219,6 +219,29 @@ def _leaf_signatures():
 _LEAF_SIGNATURES = _leaf_signatures()
 LEAF_EXPORTS = list(_LEAF_SIGNATURES)
 
+# spectral inputs (include/crt1d_hip_spectra.h): raw spectra -> Bands, again a header and a table of their own
+LIGHT_UNIFORM, LIGHT_PLANCK, LIGHT_TABLE = 0, 1, 2  # enum crt_light
+LIGHT_KINDS = {"uniform": LIGHT_UNIFORM, "planck": LIGHT_PLANCK, "table": LIGHT_TABLE}
+SPECTRA_NGL = 16
+SPECTRA_MAX_NB = 512
+SPECTRA_MAX_ITEMS = 65536
+SPECTRA_BLOCK = 512
+SPECTRA_LDS_BYTES = 160 * 1024
+
+
+def _spectra_signatures():
+    dp, ip, i32, i64, dbl, ok = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_int
+    return {
+        "crt_hip_planck_nodes_f64": (ok, [dp, dp]),
+        "crt_hip_avg_optical_prop_f64": (ok, [_vp, i32, _vp, i32, _vp, i32, ip, i32, dbl, _vp, i32, _vp, i32, i32, _vp, _vp, _vp]),
+        "crt_hip_bands_from_spectra_f64": (ok, [_vp, i32, _vp, i64, _vp, i64, _vp, i64, _vp, i32, _vp, i64, _vp, i64, i32, _vp, i32, ip, i32, dbl,
+                                                _vp, _vp, _vp, _vp, _vp, _vp]),
+    }
+
+
+_SPECTRA_SIGNATURES = _spectra_signatures()
+SPECTRA_EXPORTS = list(_SPECTRA_SIGNATURES)
+
 _lib = None
 
 
@@ -241,7 +264,7 @@ def load():
     import torch  # noqa: F401
 
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:
@@ -287,3 +310,13 @@ def leaf_pdf_nodes():
     xm, wm = (ctypes.c_double * LEAF_NMLA)(), (ctypes.c_double * LEAF_NMLA)()
     check(load().crt_hip_leaf_pdf_nodes_f64(x, w, xm, wm), "crt_hip_leaf_pdf_nodes_f64")
     return tuple(np.frombuffer(b, dtype=np.float64).copy() for b in (x, w, xm, wm))
+
+
+def planck_nodes():
+    """The ``SPECTRA_NGL``-point Gauss-Legendre rule on the unit interval that ``CRT_LIGHT_PLANCK`` integrates the Planck radiance over a
+    sub-bin with: ``(x, w)`` (include/crt1d_hip_spectra.h)."""
+    import numpy as np
+
+    x, w = (ctypes.c_double * SPECTRA_NGL)(), (ctypes.c_double * SPECTRA_NGL)()
+    check(load().crt_hip_planck_nodes_f64(x, w), "crt_hip_planck_nodes_f64")
+    return np.frombuffer(x, dtype=np.float64).copy(), np.frombuffer(w, dtype=np.float64).copy()

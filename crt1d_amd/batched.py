@@ -37,13 +37,17 @@ _MID_KEYS = {"n79": ("aI_lsl", "aI_lsh")}  # (ncol, nz-1, nb)
 
 def _tensor(t, name, dtypes):
     """A tensor the kernels read through a bare pointer: a contiguous CUDA tensor whose dtype is one of ``dtypes``."""
+    _check_type(t, name, dtypes)
+    if not t.is_cuda:
+        raise ValueError(f"{name} must live on the GPU (got {t.device}); crt1d_amd has no CPU path")
+    return t.contiguous()
+
+
+def _check_type(t, name, dtypes):
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
     if t.dtype not in dtypes:
         raise TypeError(f"{name} must be {' or '.join(str(d)[len('torch.'):] for d in dtypes)}, got {t.dtype}")
-    if not t.is_cuda:
-        raise ValueError(f"{name} must live on the GPU (got {t.device}); crt1d_amd has no CPU path")
-    return t.contiguous()
 
 
 def _f64(t, name):
@@ -284,6 +288,63 @@ class Bands:
     def from_host(cls, d, device="cuda"):
         t = _host_reader(d, device)
         return cls(t("I_dr0"), t("I_df0"), t("leaf_r"), t("leaf_t"), t("soil_r"))
+
+    @classmethod
+    def from_spectra(cls, x_opt, leaf_r, leaf_t, soil_r, x_si, SI_dr, SI_df, edges, *, light="table", T_K=6000, x_smear_nb=None):
+        """The five band arrays from raw spectra, in one launch for all columns (``crt_hip_bands_from_spectra_f64``,
+        include/crt1d_hip_spectra.h): what the reference prepares with ``smear_avg_optical_prop`` and ``smear_si``
+        (``crt1d/spectra.py:129-218, 366-390, 529-573``).
+
+        ``leaf_r``, ``leaf_t``, ``soil_r``: raw optics on the grid ``x_opt (nx,)``; ``SI_dr``, ``SI_df``: spectral irradiance
+        (W m-2 um-1) on ``x_si (nxs,)``; each a CUDA float64 tensor ``(ncol, n)``, or ``(n,)`` for one spectrum shared by all columns.
+        ``edges (nb+1,)``: band edges.  The grids and ``edges`` may be host arrays (the sub-bin counts are formed on the host from them,
+        :func:`crt1d_amd.spectra.sub_bin_counts`).  ``light``: what weights the optics -- ``"table"``: each column's own
+        ``SI_dr + SI_df``; ``"planck"`` (``T_K``); ``"uniform"``.  Returns ``Bands`` with ``(ncol, nb)`` arrays (``ncol = 1`` when every
+        input is shared)."""
+        from . import spectra as sp
+
+        kind = sp._light_kind(light)
+        xo_h, xs_h, ed_h = sp._host(x_opt), sp._host(x_si), sp._host(edges)
+        if xo_h.ndim != 1 or xs_h.ndim != 1 or ed_h.ndim != 1 or ed_h.size < 1:
+            raise ValueError("x_opt must be (nx,), x_si (nxs,) and edges (nb+1,)")
+        ncol, dev = None, None
+        rows = {}
+        given = (("leaf_r", leaf_r, xo_h.size), ("leaf_t", leaf_t, xo_h.size), ("soil_r", soil_r, xo_h.size), ("SI_dr", SI_dr, xs_h.size),
+                 ("SI_df", SI_df, xs_h.size))
+        for name, t, n in given:  # (type, dtype and shape of every input before the device of any)
+            _check_type(t, name, (torch.float64,))
+            if t.ndim not in (1, 2) or t.shape[-1] != n:
+                raise ValueError(f"{name} must be (ncol, {n}) or ({n},), got {tuple(t.shape)}")
+        for name, t, n in given:
+            t = _f64(t, name)
+            if dev is None:
+                dev = t.device
+            elif t.device != dev:
+                raise ValueError(f"{name} lives on {t.device} but leaf_r on {dev}")
+            if t.ndim == 2:
+                if ncol is None:
+                    ncol = t.shape[0]
+                elif t.shape[0] != ncol:
+                    raise ValueError(f"{name} has {t.shape[0]} rows but another input {ncol}")
+            rows[name] = t
+        ncol = 1 if ncol is None else ncol
+        off, off_p = sp._sub_offsets(xo_h, ed_h, x_smear_nb)
+        grid = lambda t: torch.as_tensor(t, dtype=torch.float64).to(dev).contiguous()  # noqa: E731
+        x_opt, x_si, edges = grid(x_opt), grid(x_si), grid(edges)
+        nb = ed_h.size - 1
+        out = [torch.empty((ncol, nb), dtype=torch.float64, device=dev) for _ in range(5)]
+        args = []
+        for name in ("leaf_r", "leaf_t", "soil_r"):
+            args += [rows[name].data_ptr(), xo_h.size if rows[name].ndim == 2 else 0]
+        args += [x_si.data_ptr(), xs_h.size]
+        for name in ("SI_dr", "SI_df"):
+            args += [rows[name].data_ptr(), xs_h.size if rows[name].ndim == 2 else 0]
+        with torch.cuda.device(dev):
+            st = _lib.load().crt_hip_bands_from_spectra_f64(x_opt.data_ptr(), xo_h.size, *args, ncol, edges.data_ptr(), nb, off_p, kind,
+                                                            float(T_K), *(o.data_ptr() for o in out),
+                                                            torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(st, "crt_hip_bands_from_spectra_f64")
+        return cls(*out)
 
 
 def _check_band_device(bands, device):

@@ -1,6 +1,7 @@
 // Internal declarations shared by the gfx950 kernels of libcrt1d_hip.so.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -644,6 +645,29 @@ int launch_colpre_series(const ColArgs& ca, int nt, double* sun, hipStream_t s);
 inline dim3 series_grid(int ncol, int nt) {
   const unsigned gy = nt < 65535 ? (unsigned)nt : 65535u;
   return dim3((unsigned)ncol, gy, (unsigned)((nt + (long long)gy - 1) / gy));
+}
+
+// n-point Gauss-Legendre on (0, 1): Newton on P_n from the Chebyshev guess, the usual recurrence; ~1e-16
+inline void gauss_unit(int n, double* x, double* w) {
+  for (int i = 0; i < (n + 1) / 2; ++i) {
+    double z = cos(3.14159265358979323846 * (i + 0.75) / (n + 0.5)), pp = 1.0;
+    for (int it = 0; it < 100; ++it) {
+      double p1 = 1.0, p2 = 0.0;
+      for (int j = 0; j < n; ++j) {
+        const double p3 = p2;
+        p2 = p1;
+        p1 = ((2.0 * j + 1.0) * z * p2 - j * p3) / (j + 1.0);
+      }
+      pp = n * (z * p1 - p2) / (z * z - 1.0);
+      const double dz = p1 / pp;
+      z -= dz;
+      if (fabs(dz) < 1e-16) break;
+    }
+    const double wt = 2.0 / ((1.0 - z * z) * pp * pp);
+    x[i] = 0.5 * (1.0 - z);
+    x[n - 1 - i] = 0.5 * (1.0 + z);
+    w[i] = w[n - 1 - i] = 0.5 * wt;
+  }
 }
 
 // set the dynamic-LDS attribute where needed, launch, check: the one launch sequence (the caller reports the kernel when this returns CRT_OK)

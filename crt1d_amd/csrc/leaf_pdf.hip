@@ -138,29 +138,6 @@ __global__ __launch_bounds__(LEAF_BLOCK) void k_g_from_pdf(const LeafArgs a) {
   }
 }
 
-// n-point Gauss-Legendre on (0, 1): Newton on P_n from the Chebyshev guess, the usual recurrence; ~1e-16
-void gauss_unit(int n, double* x, double* w) {
-  for (int i = 0; i < (n + 1) / 2; ++i) {
-    double z = cos(M_PI * (i + 0.75) / (n + 0.5)), pp = 1.0;
-    for (int it = 0; it < 100; ++it) {
-      double p1 = 1.0, p2 = 0.0;
-      for (int j = 0; j < n; ++j) {
-        const double p3 = p2;
-        p2 = p1;
-        p1 = ((2.0 * j + 1.0) * z * p2 - j * p3) / (j + 1.0);
-      }
-      pp = n * (z * p1 - p2) / (z * z - 1.0);
-      const double dz = p1 / pp;
-      z -= dz;
-      if (fabs(dz) < 1e-16) break;
-    }
-    const double wt = 2.0 / ((1.0 - z * z) * pp * pp);
-    x[i] = 0.5 * (1.0 - z);
-    x[n - 1 - i] = 0.5 * (1.0 + z);
-    w[i] = w[n - 1 - i] = 0.5 * wt;
-  }
-}
-
 LeafRule h_lr;
 std::once_flag h_lr_once;
 std::mutex lr_mu;
