@@ -32,7 +32,7 @@ KEYS = ("aI", "aI_sl", "aI_sh", "totals")
 # rank's compute).  The re-formed sum differs from a directly reduced aI by rounding only (~1e-16 relative).
 MSG_KEYS = ("aI_sl", "aI_sh", "totals")
 # level_profiles=True: the band-integrated level profiles travel as well, but only those that cannot be re-formed exactly --
-# F = I_dr / mu + 2 (I_df_u + I_df_d) and I_d = I_dr + I_df_d are linear in the three level sums (api.hip store_level_profiles,
+# F = I_dr / mu + 2 (I_df_u + I_df_d) and I_d = I_dr + I_df_d are linear in the three level sums (epilogue.hip store_level_profiles,
 # model.py:425) and are re-formed after the reduce with aI (crt_hip_bandsum_finish_f64): 1803 instead of 2403 doubles per column at
 # nz = 100, ngroup = 3
 PROFILE_MSG_KEYS = ("aI_dr", "I_dr", "I_df_d", "I_df_u")
