@@ -242,6 +242,37 @@ def _spectra_signatures():
 _SPECTRA_SIGNATURES = _spectra_signatures()
 SPECTRA_EXPORTS = list(_SPECTRA_SIGNATURES)
 
+# sensor-band outputs (include/crt1d_hip_sensor.h): level spectra folded with spectral responses, a header and a table of their own
+MAX_SENSOR_BANDS = 64  # CRT_MAX_SENSOR_BANDS
+
+
+class CrtSensorSet(ctypes.Structure):
+    """``crt_sensor_set``: ``first`` / ``count`` are HOST arrays, ``w`` the packed DEVICE weights."""
+
+    _fields_ = [("nsens", ctypes.c_int32), ("first", ctypes.POINTER(ctypes.c_int32)), ("count", ctypes.POINTER(ctypes.c_int32)), ("w", _vp)]
+
+
+class CrtSensorOut(ctypes.Structure):
+    _fields_ = [(k, _vp) for k in ("I_dr", "I_df_d", "I_df_u", "F")]
+
+
+def _sensor_signatures():
+    P = ctypes.POINTER
+    i, i32, sz, ok = ctypes.c_int, ctypes.c_int32, ctypes.c_size_t, ctypes.c_int
+    cols, bands, opts = P(CrtColumns), P(CrtBands), P(CrtOptions)
+    tail = [opts, P(i32), i32, P(CrtSensorSet), P(CrtSensorOut), _vp, sz, _vp]
+    return {
+        "crt_hip_sensor_workspace_bytes": (sz, [i, i32, i32, i32, i32, i32]),
+        "crt_hip_sensor_levels_f64": (ok, [i, cols, bands] + tail),
+        "crt_hip_sensor_levels_f32": (ok, [i, cols, bands] + tail),
+        "crt_hip_sensor_series_workspace_bytes": (sz, [i, i32, i32, i32, i32, i32, i32]),
+        "crt_hip_sensor_levels_series_f64": (ok, [i, cols, bands, P(CrtSunSeries)] + tail),
+    }
+
+
+_SENSOR_SIGNATURES = _sensor_signatures()
+SENSOR_EXPORTS = list(_SENSOR_SIGNATURES)
+
 _lib = None
 
 
@@ -264,7 +295,7 @@ def load():
     import torch  # noqa: F401
 
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES, **_SENSOR_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:

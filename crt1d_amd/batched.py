@@ -1099,3 +1099,192 @@ def spectral_totals_series(scheme, cols: Columns, bands: Bands, sun: SunSeries, 
     dr, dn, up = (r[k].to(torch.float64) for k in ("I_dr", "I_df_d", "I_df_u"))
     i_d = dr + dn
     return torch.stack((i_d[:, :, 1], up[:, :, 1], i_d[:, :, 0], up[:, :, 0]), dim=-1)
+
+
+# ---- sensor-band outputs (include/crt1d_hip_sensor.h) -------------------------------------------------------------------------------
+
+
+class SensorSet:
+    """The spectral responses of ``nsens <= _lib.MAX_SENSOR_BANDS`` sensor bands on the ``nb`` model bands, as the sensor plans read them
+    (``crt_sensor_set``): per sensor band the support ``[first, first + count)`` and its weights, packed one support after the other.
+
+    ``SensorSet(weights)``: dense ``(nsens, nb)`` weights (NumPy array or tensor); the support of a row is the span from its first to its
+    last nonzero weight -- zeros inside the span are kept, the zeros outside are never multiplied.  An all-zero row is a ValueError.
+    :meth:`from_supports` takes the supports as they are.  ``first`` / ``count`` live on the host (``np.int32``), ``w`` is the packed
+    float64 tensor on ``device`` (default: the current GPU)."""
+
+    def __init__(self, weights, device=None):
+        import numpy as np
+
+        dev = weights.device if isinstance(weights, torch.Tensor) and weights.is_cuda else device
+        w = weights.detach().cpu().numpy() if isinstance(weights, torch.Tensor) else weights
+        w = np.asarray(w, dtype=np.float64)
+        if w.ndim == 1:
+            w = w[None, :]
+        if w.ndim != 2 or w.shape[1] < 1:
+            raise ValueError("weights must be (nsens, nb)")
+        self._check_nsens(w.shape[0])
+        first, count, packed = [], [], []
+        for s, row in enumerate(w):
+            nzr = np.flatnonzero(row)
+            if nzr.size == 0:
+                raise ValueError(f"sensor band {s} has no nonzero weight")
+            first.append(int(nzr[0]))
+            count.append(int(nzr[-1]) - int(nzr[0]) + 1)
+            packed.append(row[nzr[0]:nzr[-1] + 1])
+        self._set(w.shape[1], first, count, np.concatenate(packed), dev)
+
+    @staticmethod
+    def _check_nsens(nsens):
+        if not 1 <= nsens <= _lib.MAX_SENSOR_BANDS:
+            raise ValueError(f"{nsens} sensor bands; one set holds 1 .. {_lib.MAX_SENSOR_BANDS}")
+
+    def _set(self, nb, first, count, packed, device):
+        import numpy as np
+
+        self.nb = None if nb is None else int(nb)
+        self.first = np.ascontiguousarray(first, dtype=np.int32)
+        self.count = np.ascontiguousarray(count, dtype=np.int32)
+        self.nsens = int(self.first.size)
+        if device is None:  # the current GPU; without one the set stays on the host (and no plan takes it)
+            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        if isinstance(packed, torch.Tensor):
+            self.w = _f64(packed, "packed_w")
+            if not self.w.is_cuda:
+                self.w = self.w.to(device)
+        else:
+            self.w = torch.as_tensor(np.ascontiguousarray(packed, dtype=np.float64)).to(device)
+
+    @classmethod
+    def from_supports(cls, first, count, packed_w, nb=None, device=None):
+        """``first``, ``count``: ``(nsens,)`` ints (``count >= 1``, ``first >= 0``; supports may overlap, in any order); ``packed_w``: the
+        ``sum(count)`` weights, those of sensor band ``s`` at ``off[s] .. off[s] + count[s]`` with ``off`` the exclusive prefix sum of
+        ``count``.  ``nb``: the model band count, when known (a plan checks the supports against its bands either way)."""
+        import numpy as np
+
+        first, count = np.atleast_1d(np.asarray(first)), np.atleast_1d(np.asarray(count))
+        if first.ndim != 1 or first.shape != count.shape or not (np.issubdtype(first.dtype, np.integer) and np.issubdtype(count.dtype, np.integer)):
+            raise ValueError("first and count must be integer arrays of one shape (nsens,)")
+        cls._check_nsens(first.size)
+        if (count < 1).any() or (first < 0).any():
+            raise ValueError("every support needs count >= 1 and first >= 0")
+        if nb is not None and (first.astype(np.int64) + count > nb).any():
+            raise ValueError(f"a support reaches beyond nb = {nb}")
+        n = int(count.astype(np.int64).sum())
+        if (packed_w.numel() if isinstance(packed_w, torch.Tensor) else np.size(packed_w)) != n or np.ndim(packed_w) != 1:
+            raise ValueError(f"packed_w must hold sum(count) = {n} weights in one dimension")
+        self = cls.__new__(cls)
+        self._set(nb, first, count, packed_w, device)
+        return self
+
+    @property
+    def offsets(self):
+        """Exclusive prefix sum of ``count``: where the weights of each sensor band start in ``w``."""
+        import numpy as np
+
+        return np.concatenate(([0], np.cumsum(self.count[:-1], dtype=np.int64)))
+
+    def dense(self, nb=None):
+        """The ``(nsens, nb)`` NumPy array of the weights (zeros outside the supports)."""
+        import numpy as np
+
+        nb = self.nb if nb is None else nb
+        if nb is None:
+            raise ValueError("nb is not known: pass it")
+        w, out = self.w.cpu().numpy(), np.zeros((self.nsens, nb))
+        for s, (f, n, o) in enumerate(zip(self.first, self.count, self.offsets)):
+            out[s, f:f + n] = w[o:o + n]
+        return out
+
+    def check(self, nb, device):
+        """The checks of a plan: the supports lie in ``[0, nb)`` and the weights on ``device``."""
+        if self.nb is not None and self.nb != nb:
+            raise ValueError(f"the sensor set was built for nb = {self.nb} bands, the spectra have {nb}")
+        if int((self.first.astype("int64") + self.count).max()) > nb:
+            raise ValueError(f"a sensor support reaches beyond nb = {nb}")
+        if self.w.device != device:
+            raise ValueError(f"the sensor weights live on {self.w.device} but the columns on {device}")
+
+    def c_struct(self):
+        P = ctypes.POINTER(ctypes.c_int32)
+        return _lib.CrtSensorSet(self.nsens, self.first.ctypes.data_as(P), self.count.ctypes.data_as(P), self.w.data_ptr())
+
+
+def sensor_workspace_bytes(scheme, ncol, nz, nb, nsel, nsens):
+    """Device workspace of a :class:`SensorLevelsPlan` call: the records of :func:`workspace_bytes` and, with several band slices, the
+    partial sums behind them."""
+    return int(_lib.load().crt_hip_sensor_workspace_bytes(_lib.SCHEME_IDS[scheme], ncol, nz, nb, nsel, nsens))
+
+
+def sensor_series_workspace_bytes(scheme, ncol, nz, nb, nt, nsel, nsens):
+    """Device workspace of a :class:`SensorLevelsSeriesPlan` call: the records of :func:`levels_series_workspace_bytes`, then partial sums."""
+    return int(_lib.load().crt_hip_sensor_series_workspace_bytes(_lib.SCHEME_IDS[scheme], ncol, nz, nb, nt, nsel, nsens))
+
+
+class SensorLevelsPlan(_SolvePlan):
+    """Pre-validated sensor-band solve (``crt_hip_sensor_levels_f64``, or ``_f32`` for float32 bands): ``out[k][c, r, s]`` is the sum over
+    the support of sensor band ``s`` of ``w_s[b] * X[c, levels[r], b]`` for ``X`` in ``keys`` (any of ``I_dr, I_df_d, I_df_u, F``), each
+    ``(ncol, nsel, nsens)`` float64 for both storage types.  ``X`` is the row :class:`LevelsPlan` gives; it is reduced inside the level
+    kernel and never written.  The summation order depends on the scheme, ``nz``, ``nb``, ``nsel`` and the sensor set only: a column's
+    sums are bitwise the same alone or in any batch."""
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, *, keys=LEVEL_KEYS, mu_s=0.501, tau_d_method="quad",
+                 out=None, workspace=None):
+        self._check_options(scheme, tau_d_method)
+        self._bind_sensors(scheme, cols, bands, levels, sensors, _level_keys(keys), mu_s, tau_d_method, out)
+        need = sensor_workspace_bytes(scheme, cols.ncol, cols.nz, bands.nb, len(self.levels), sensors.nsens)
+        self._finish(f"crt_hip_sensor_levels_{_io_suffix(bands)}", need, workspace)
+
+    def _bind_sensors(self, scheme, cols, bands, levels, sensors, keys, mu_s, tau_d_method, out, sun=None):
+        """``_bind`` + the level list, the sensor set and the outputs of ``keys`` (with ``sun``: of every sun state), NULL for the rest."""
+        if not isinstance(sensors, SensorSet):
+            raise TypeError("sensors must be a SensorSet")
+        self.levels, self.keys, self.sensors = normalize_levels(levels, cols.nz), keys, sensors
+        sensors.check(bands.nb, cols.device)
+        self._bind(scheme, cols, bands, mu_s, tau_d_method, sun=sun)
+        shape = (cols.ncol,) + (() if sun is None else (sun.nt,)) + (len(self.levels), sensors.nsens)
+        out = _outputs({k: shape for k in keys}, out, torch.float64, cols.device, "output {!r}", lacks=True)
+        self.out = {k: out[k] for k in keys}
+        self._out = _lib.CrtSensorOut(*[out[k].data_ptr() if k in keys else None for k in LEVEL_KEYS])
+        self._lev = (ctypes.c_int32 * len(self.levels))(*self.levels)
+        self._sens = sensors.c_struct()
+
+    def _tail(self):
+        return self._lev, len(self.levels), ctypes.byref(self._sens), ctypes.byref(self._out)
+
+
+def solve_sensor_levels(scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, **kw):
+    """One-shot :class:`SensorLevelsPlan`: ``{key: (ncol, nsel, nsens)}`` at the sorted levels ``normalize_levels(levels, nz)``."""
+    with torch.cuda.device(cols.device):
+        return SensorLevelsPlan(scheme, cols, bands, levels, sensors, **kw)()
+
+
+class SensorLevelsSeriesPlan(SensorLevelsPlan):
+    """The outputs of :class:`SensorLevelsPlan` for ``sun.nt`` sun states of every column in one call
+    (``crt_hip_sensor_levels_series_f64``): each ``(ncol, nt, nsel, nsens)`` float64, ``out[k][:, t]`` bitwise what
+    :class:`SensorLevelsPlan` returns with ``psi = sun.psi[:, t]`` and the incoming spectra of step ``t``.  Reads and ignores the inputs
+    :class:`LevelsSeriesPlan` does.  float64 bands only."""
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, sensors: SensorSet, *, keys=LEVEL_KEYS, mu_s=0.501,
+                 tau_d_method="quad", out=None, workspace=None):
+        self._check_options(scheme, tau_d_method)
+        keys = _level_keys(keys)
+        if not isinstance(sun, SunSeries) or isinstance(sun, SunSeriesF32):
+            raise TypeError("sun must be a SunSeries (float64 spectra)")
+        self._bind_sensors(scheme, cols, bands, levels, sensors, keys, mu_s, tau_d_method, out, sun=sun)
+        need = sensor_series_workspace_bytes(scheme, cols.ncol, cols.nz, bands.nb, sun.nt, len(self.levels), sensors.nsens)
+        self._finish("crt_hip_sensor_levels_series_f64", need, workspace)
+
+
+def solve_sensor_levels_series(scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, sensors: SensorSet, **kw):
+    """One-shot :class:`SensorLevelsSeriesPlan`: ``{key: (ncol, nt, nsel, nsens)}``."""
+    with torch.cuda.device(cols.device):
+        return SensorLevelsSeriesPlan(scheme, cols, bands, sun, levels, sensors, **kw)()
+
+
+def sensor_albedo(scheme, cols: Columns, bands: Bands, sensors: SensorSet, **kw):
+    """The canopy albedo in every sensor band, ``(ncol, nsens)`` float64: the sensor-weighted upwelling over the sensor-weighted incoming
+    irradiance at the canopy top, ``sum(w I_df_u) / sum(w (I_dr + I_df_d))``, from one sensor-band call at ``levels = (nz - 1,)``.  ``kw`` as
+    for :class:`SensorLevelsPlan` (``keys`` is fixed here)."""
+    r = solve_sensor_levels(scheme, cols, bands, (cols.nz - 1,), sensors, keys=("I_dr", "I_df_d", "I_df_u"), **kw)
+    return r["I_df_u"][:, 0] / (r["I_dr"][:, 0] + r["I_df_d"][:, 0])

@@ -221,7 +221,7 @@ static bool is_tri(int scheme) { return scheme == CRT_SCHEME_N79 || scheme == CR
 // integ / lev / ser: the integrated outputs, the level subset, the sun-angle series of the call (each NULL when it has none).
 static int check_solve(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const crt_outputs* out,
                        const void* workspace, size_t workspace_bytes, const IntArgs* integ, const LevArgs* lev, const crt_sun_series* ser,
-                       SolveOpts& o) {
+                       SolveOpts& o, size_t extra_ws = 0) {  // extra_ws: what the call keeps behind the records (sensor partial sums)
   if (!scheme_ok(scheme) || !cols || !bands || !out) return CRT_ERR_BAD_ARG;
   const int ncol = cols->ncol, nz = cols->nz, nb = bands->nb;
   if (ncol <= 0 || nz <= 0 || nb <= 0) return CRT_ERR_BAD_ARG;
@@ -277,8 +277,8 @@ static int check_solve(int scheme, const crt_columns* cols, const crt_bands* ban
   const size_t need = !ser ? crt_hip_workspace_bytes_nb(scheme, ncol, nz, nb)
                       : lev ? crt_hip_levels_series_workspace_bytes(scheme, ncol, nz, ser->nt)
                             : crt_hip_series_workspace_bytes(scheme, ncol, nz, nb, ser->nt);
-  if (need == 0) return CRT_ERR_UNSUPPORTED;  // (series: a size beyond size_t)
-  if (!workspace || workspace_bytes < need) return CRT_ERR_WORKSPACE;
+  if (need == 0 || extra_ws > SIZE_MAX - need) return CRT_ERR_UNSUPPORTED;  // (series: a size beyond size_t)
+  if (!workspace || workspace_bytes < need + extra_ws) return CRT_ERR_WORKSPACE;
   if (ser && integ && nb > 1024) return CRT_ERR_UNSUPPORTED;  // as the per-step entry, but before K0 has written anything
   if (ser && lev && (long long)ncol * ser->nt > 0x7fffffffLL) return CRT_ERR_UNSUPPORTED;  // (column, t) is a 32-bit index in K0
   return CRT_OK;
@@ -310,7 +310,7 @@ static void build_args(int scheme, const crt_columns* cols, const crt_bands* ban
 
 // sun-angle series: K0 per column and per (column, t), then one series kernel (integrated outputs or level spectra)
 static int dispatch_series(int scheme, ColArgs ca, SolveArgs sa, int flags, const IntArgs* integ, const LevArgs* lev, const crt_sun_series* ser,
-                           hipStream_t s) {
+                           hipStream_t s, SensLaunch* sl) {
   // workspace: canopy records [ncol][can_len], then sun records [ncol * nt][sun_len] (SeriesArgs, crt_internal.hpp)
   double* const sunrec = ca.ws + (size_t)ca.ncol * can_len(scheme, ca.nz);
   ca.psi = ser->psi;
@@ -319,8 +319,8 @@ static int dispatch_series(int scheme, ColArgs ca, SolveArgs sa, int flags, cons
   const SeriesArgs sr = {ser->nt, scheme, ca.nz, can_len(scheme, ca.nz), sun_len(scheme, ca.nz), sa.ws, sunrec, ser->col_stride, ser->I_dr0, ser->I_df0};
   const bool tri = is_tri(scheme);
   auto lev_series = [&](bool probe) {
-    if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_lev(sa, *lev, s, &sr, probe);
-    return tri ? launch_tridiag_lev(scheme, sa, *lev, s, &sr, probe) : launch_closed_lev(scheme, sa, *lev, s, &sr, probe);
+    if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_lev(sa, *lev, s, &sr, probe, sl);
+    return tri ? launch_tridiag_lev(scheme, sa, *lev, s, &sr, probe, sl) : launch_closed_lev(scheme, sa, *lev, s, &sr, probe, sl);
   };
   if (lev) {  // every shape the level series cannot serve is found here, before K0 has written anything
     const int st = lev_series(true);
@@ -338,7 +338,17 @@ static int dispatch_series(int scheme, ColArgs ca, SolveArgs sa, int flags, cons
 }
 
 // one sun state per column: K0, then the profile, integrated or level-subset kernel of the scheme
-static int dispatch_step(int scheme, const ColArgs& ca, const SolveArgs& sa, int flags, const IntArgs* integ, const LevArgs* lev, hipStream_t s) {
+static int dispatch_step(int scheme, const ColArgs& ca, const SolveArgs& sa, int flags, const IntArgs* integ, const LevArgs* lev, hipStream_t s,
+                         SensLaunch* sl) {
+  const bool tri = is_tri(scheme);
+  auto lev_step = [&](bool probe) {
+    if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_lev(sa, *lev, s, nullptr, probe, sl);
+    return tri ? launch_tridiag_lev(scheme, sa, *lev, s, nullptr, probe, sl) : launch_closed_lev(scheme, sa, *lev, s, nullptr, probe, sl);
+  };
+  if (sl) {  // sensor-band outputs: a shape their staging does not fit is found here, before K0 has written anything
+    const int st = lev_step(true);
+    if (st != CRT_OK) return st;
+  }
   // 2s profiles: the closed-form launcher forms the records inside k_pipe when it picks that kernel (one launch per call), and runs
   // k_colpre in front of any other kernel.  SKIP_PRECOMPUTE / PRECOMPUTE_ONLY and CRT_TUNE_K0_SEPARATE keep k_colpre as a kernel of its own.
   const bool k0_in_solve = scheme == CRT_SCHEME_2S && !integ && !lev && !(flags & (CRT_FLAG_SKIP_PRECOMPUTE | CRT_FLAG_PRECOMPUTE_ONLY)) &&
@@ -351,15 +361,11 @@ static int dispatch_step(int scheme, const ColArgs& ca, const SolveArgs& sa, int
     if (st != CRT_OK) return st;
   }
   if (flags & CRT_FLAG_PRECOMPUTE_ONLY) return CRT_OK;
-  const bool tri = is_tri(scheme);
   if (integ) {
     if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_int(sa, *integ, s);
     return tri ? launch_tridiag_int(scheme, sa, *integ, s) : launch_closed_int(scheme, sa, *integ, s);
   }
-  if (lev) {
-    if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_lev(sa, *lev, s);
-    return tri ? launch_tridiag_lev(scheme, sa, *lev, s) : launch_closed_lev(scheme, sa, *lev, s);
-  }
+  if (lev) return lev_step(false);
   if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa(sa, ca.ws + (size_t)sa.ncol * sa.reclen, s);
   const int force = (flags & CRT_FLAG_DIRECT_STORES) ? 1 : 0;
   return tri ? launch_tridiag(scheme, sa, s, force) : launch_closed(scheme, sa, s, force, k0_in_solve ? &ca : nullptr);
@@ -367,14 +373,15 @@ static int dispatch_step(int scheme, const ColArgs& ca, const SolveArgs& sa, int
 
 static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts,
                       const crt_outputs* out, void* workspace, size_t workspace_bytes, crt_stream_t stream, int f32,
-                      const IntArgs* integ = nullptr, const LevArgs* lev = nullptr, const crt_sun_series* ser = nullptr) {
+                      const IntArgs* integ = nullptr, const LevArgs* lev = nullptr, const crt_sun_series* ser = nullptr,
+                      SensLaunch* sl = nullptr, size_t extra_ws = 0) {
   SolveOpts o;
-  if (const int st = check_solve(scheme, cols, bands, opts, out, workspace, workspace_bytes, integ, lev, ser, o)) return st;
+  if (const int st = check_solve(scheme, cols, bands, opts, out, workspace, workspace_bytes, integ, lev, ser, o, extra_ws)) return st;
   ColArgs ca;
   SolveArgs sa;
   build_args(scheme, cols, bands, out, workspace, f32, o, ca, sa);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return ser ? dispatch_series(scheme, ca, sa, o.flags, integ, lev, ser, s) : dispatch_step(scheme, ca, sa, o.flags, integ, lev, s);
+  return ser ? dispatch_series(scheme, ca, sa, o.flags, integ, lev, ser, s, sl) : dispatch_step(scheme, ca, sa, o.flags, integ, lev, s, sl);
 }
 
 int crt_hip_solve_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts,
@@ -510,11 +517,11 @@ int crt_hip_integrated_f32(int scheme, const crt_columns* cols, const crt_bands_
 // or in solve_impl's checks, before any launch.
 static int levels_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
                        int32_t nsel, const crt_outputs* out, void* workspace, size_t workspace_bytes, crt_stream_t stream, int f32,
-                       const crt_sun_series* ser = nullptr) {
+                       const crt_sun_series* ser = nullptr, SensLaunch* sl = nullptr, size_t extra_ws = 0) {
   if (!scheme_ok(scheme) || !cols || !levels || !out) return CRT_ERR_BAD_ARG;
   if (nsel < 1 || nsel > CRT_MAX_LEVEL_SELECT) return CRT_ERR_BAD_ARG;
   if (out->x0 || out->x1 || out->x2) return CRT_ERR_BAD_ARG;
-  if (!out->I_dr && !out->I_df_d && !out->I_df_u && !out->F) return CRT_ERR_BAD_ARG;
+  if (!sl && !out->I_dr && !out->I_df_d && !out->I_df_u && !out->F) return CRT_ERR_BAD_ARG;  // (a sensor call has its outputs in sl)
   LevArgs la = {};
   la.o[0] = out->I_dr;
   la.o[1] = out->I_df_d;
@@ -527,7 +534,7 @@ static int levels_impl(int scheme, const crt_columns* cols, const crt_bands* ban
     la.lev[r] = levels[r];
   }
   crt_outputs none = {};
-  return solve_impl(scheme, cols, bands, opts, &none, workspace, workspace_bytes, stream, f32, nullptr, &la, ser);
+  return solve_impl(scheme, cols, bands, opts, &none, workspace, workspace_bytes, stream, f32, nullptr, &la, ser, sl, extra_ws);
 }
 
 // crt_sun_series_f32 has the layout of crt_sun_series (the element type behind I_dr0 / I_df0 differs: SeriesArgs carries them untyped)
@@ -559,6 +566,101 @@ int crt_hip_levels_f32(int scheme, const crt_columns* cols, const crt_bands_f32*
                        int32_t nsel, const crt_outputs_f32* out, void* workspace, size_t workspace_bytes, crt_stream_t stream) {
   return levels_impl(scheme, cols, reinterpret_cast<const crt_bands*>(bands), opts, levels, nsel, reinterpret_cast<const crt_outputs*>(out),
                      workspace, workspace_bytes, stream, 1);
+}
+
+// ------------------------------------------------------------------------------------------
+// Sensor-band outputs (include/crt1d_hip_sensor.h): crt_hip_levels_* with the sensor form of the level kernel.
+
+// bytes of the partial sums [ncol * nt][nslice][nsel][4][nsens] behind the records: 0 with one band slice, and 0 where the shape is not
+// served (the call then reports it) or the size is beyond size_t
+static size_t sens_partial_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nt, int32_t nsel, int32_t nsens) {
+  if (!scheme_ok(scheme) || ncol <= 0 || nz <= 0 || nb <= 0 || nt < 1 || nsel < 1 || nsel > CRT_MAX_LEVEL_SELECT || nsens < 1 ||
+      nsens > CRT_MAX_SENSOR_BANDS)
+    return 0;
+  SolveArgs sa = {};
+  sa.ncol = ncol;
+  sa.nb = nb;
+  sa.nz = nz;
+  sa.reclen = rec_len(scheme, nz);
+  LevArgs la = {};
+  la.nsel = nsel;
+  SensLaunch sl = {};
+  const int st = scheme == CRT_SCHEME_ZQ_PA ? launch_zqpa_lev(sa, la, nullptr, nullptr, true, &sl)
+                 : is_tri(scheme)           ? launch_tridiag_lev(scheme, sa, la, nullptr, nullptr, true, &sl)
+                                            : launch_closed_lev(scheme, sa, la, nullptr, nullptr, true, &sl);
+  if (st != CRT_OK || sl.nslice <= 1) return 0;
+  const size_t per = (size_t)sl.nslice * (size_t)nsel * 4 * (size_t)nsens * sizeof(double);
+  const size_t nv = (size_t)ncol * (size_t)nt;
+  return nv > SIZE_MAX / per ? 0 : nv * per;
+}
+
+size_t crt_hip_sensor_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nsel, int32_t nsens) {
+  const size_t rec = crt_hip_workspace_bytes_nb(scheme, ncol, nz, nb);
+  return rec == 0 ? 0 : rec + sens_partial_bytes(scheme, ncol, nz, nb, 1, nsel, nsens);
+}
+
+size_t crt_hip_sensor_series_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nt, int32_t nsel, int32_t nsens) {
+  const size_t rec = crt_hip_levels_series_workspace_bytes(scheme, ncol, nz, nt);
+  return rec == 0 || nb <= 0 ? 0 : rec + sens_partial_bytes(scheme, ncol, nz, nb, nt, nsel, nsens);
+}
+
+static int sensor_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels, int32_t nsel,
+                       const crt_sensor_set* sensors, const crt_sensor_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream,
+                       int f32, const crt_sun_series* ser = nullptr) {
+  if (!scheme_ok(scheme) || !cols || !bands || !sensors || !out) return CRT_ERR_BAD_ARG;
+  if (!sensors->first || !sensors->count || !sensors->w) return CRT_ERR_BAD_ARG;
+  const int nsens = sensors->nsens, nb = bands->nb;
+  if (nsens < 1 || nsens > CRT_MAX_SENSOR_BANDS || nb <= 0) return CRT_ERR_BAD_ARG;
+  if (!out->I_dr && !out->I_df_d && !out->I_df_u && !out->F) return CRT_ERR_BAD_ARG;
+  SensLaunch sl = {};
+  SensArgs& sn = sl.sn;
+  sn.o[0] = out->I_dr;
+  sn.o[1] = out->I_df_d;
+  sn.o[2] = out->I_df_u;
+  sn.o[3] = out->F;
+  sn.w = sensors->w;
+  sn.nsens = nsens;
+  for (int q = 0; q < 4; ++q)
+    if (sn.o[q]) sn.qs[sn.nq++] = q;
+  int64_t off = 0;
+  for (int k = 0; k < nsens; ++k) {
+    const int32_t f = sensors->first[k], n = sensors->count[k];
+    if (n < 1 || f < 0 || (int64_t)f + n > nb) return CRT_ERR_BAD_ARG;
+    sn.first[k] = f;
+    sn.count[k] = n;
+    sn.off[k] = (int32_t)off;
+    off += n;  // (<= 64 nb: no overflow)
+  }
+  if (off > 0x7fffffffLL) return CRT_ERR_BAD_ARG;
+  const int nt = ser ? ser->nt : 1;
+  size_t rec = 0, extra = 0;
+  if (cols->ncol > 0 && cols->nz > 0 && nt >= 1) {
+    rec = ser ? crt_hip_levels_series_workspace_bytes(scheme, cols->ncol, cols->nz, nt) : crt_hip_workspace_bytes_nb(scheme, cols->ncol, cols->nz, nb);
+    if (nsel >= 1 && nsel <= CRT_MAX_LEVEL_SELECT) extra = sens_partial_bytes(scheme, cols->ncol, cols->nz, nb, nt, nsel, nsens);
+  }
+  sn.part = workspace ? reinterpret_cast<double*>(static_cast<char*>(workspace) + rec) : nullptr;
+  const crt_outputs lev_out = {};  // no level spectra: LevArgs.o stays NULL, the sums go where `sl` says
+  return levels_impl(scheme, cols, bands, opts, levels, nsel, &lev_out, workspace, workspace_bytes, stream, f32, ser, &sl, extra);
+}
+
+int crt_hip_sensor_levels_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
+                              int32_t nsel, const crt_sensor_set* sensors, const crt_sensor_out* out, void* workspace,
+                              size_t workspace_bytes, crt_stream_t stream) {
+  return sensor_impl(scheme, cols, bands, opts, levels, nsel, sensors, out, workspace, workspace_bytes, stream, 0);
+}
+
+int crt_hip_sensor_levels_f32(int scheme, const crt_columns* cols, const crt_bands_f32* bands, const crt_options* opts, const int32_t* levels,
+                              int32_t nsel, const crt_sensor_set* sensors, const crt_sensor_out* out, void* workspace,
+                              size_t workspace_bytes, crt_stream_t stream) {
+  return sensor_impl(scheme, cols, reinterpret_cast<const crt_bands*>(bands), opts, levels, nsel, sensors, out, workspace, workspace_bytes,
+                     stream, 1);
+}
+
+int crt_hip_sensor_levels_series_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_sun_series* sun,
+                                     const crt_options* opts, const int32_t* levels, int32_t nsel, const crt_sensor_set* sensors,
+                                     const crt_sensor_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream) {
+  if (!sun) return CRT_ERR_BAD_ARG;
+  return sensor_impl(scheme, cols, bands, opts, levels, nsel, sensors, out, workspace, workspace_bytes, stream, 0, sun);
 }
 
 int crt_hip_bandsum_finish_f64(const crt_columns* cols, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream) {

@@ -5,7 +5,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "crt1d_hip.h"
+#include "crt1d_hip_sensor.h"
 
 namespace crt {
 
@@ -792,18 +795,111 @@ __device__ __forceinline__ void series_lev_step(const SolveArgs& a, const LevArg
   const long long din = (long long)c * sr.col_stride + (long long)t * a.nb - (long long)c * a.col_stride;
   at.I_dr0 = static_cast<const TIO*>(sr.I_dr0) + din;
   at.I_df0 = static_cast<const TIO*>(sr.I_df0) + din;
-  body(at, slice, (v - c) * la.nsel * a.nb);
+  if constexpr (std::is_invocable_v<Body, const SolveArgs&, int, long long, long long>)
+    body(at, slice, (v - c) * la.nsel * a.nb, v);  // (the sensor forms index their sums by v)
+  else
+    body(at, slice, (v - c) * la.nsel * a.nb);
 }
 
+// ------------------------------------------------------------------------------------------
+// Sensor-band outputs (crt_hip_sensor_levels_*, include/crt1d_hip_sensor.h): the level kernels with every selected row folded with a set
+// of spectral response functions before anything leaves the workgroup.  The supports travel by value, as the levels do.
+struct SensArgs {
+  double* o[4];       // I_dr, I_df_d, I_df_u, F: [nv][nsel][nsens] or NULL (nv = ncol, series: ncol * nt)
+  const double* w;    // packed weights: those of sensor band s at w[off[s] .. off[s] + count[s])
+  double* part;       // partial sums [nv][nslice][nsel][4][nsens] (several band slices only)
+  int nsens;
+  int nq;             // outputs asked for; qs[k] = index (0..3) of the k-th of them: only those are staged, multiplied and summed
+  int32_t qs[4];
+  int32_t first[CRT_MAX_SENSOR_BANDS], count[CRT_MAX_SENSOR_BANDS], off[CRT_MAX_SENSOR_BANDS];
+};
+// what a sensor call adds to a level launch; nslice: the band slices the launcher chose (written by a probe too)
+struct SensLaunch {
+  SensArgs sn;
+  int nslice;
+};
+constexpr int SENS_STAGE = 4;  // LDS doubles per lane of the staging row
+
+// One finished row r of the workgroup's (column or (column, t)) v and band slice `slice` = bands [slice * per, min(slice * per + per, nb)):
+// every lane stages its value of each output asked for (0 from a lane that owns no band of the slice), then wave w reduces the sensor bands
+// w, w + nwave, ... whose support meets the slice -- lane l adds the products of the bands lo + l, lo + l + 64, ... in ascending order,
+// wave_sum4 adds the 64 lane sums of up to four arrays -- and writes the sums (one slice) or the slice's partial sums.  The order depends
+// on the slice bounds and the support only; the total of an array does not depend on which other arrays share the wave_sum4.  Call with
+// every thread of the workgroup (two barriers).
+__device__ __forceinline__ void sens_row(const SensArgs& sn, double* stage, const double (&v)[4], bool live, int slice, int per, int nb,
+                                         int nslice, long long vcol, int nsel, int r) {
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  {
+    int k = 0;  // (uniform)
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (sn.o[q]) stage[k++ * nthr + tid] = live ? v[q] : 0.0;
+  }
+  __syncthreads();
+  const int lo_s = slice * per, hi_s = min(lo_s + per, nb);
+  const int lane = tid & 63, nsens = sn.nsens, nq = sn.nq;
+  const int k = wave_sum4_slot(lane >> 4);
+  for (int s = tid >> 6; s < nsens; s += nthr >> 6) {  // (wave-uniform)
+    const int f = sn.first[s];
+    const int lo = max(f, lo_s), hi = min(f + sn.count[s], hi_s);
+    if (lo >= hi) continue;
+    const double* w = sn.w + (sn.off[s] - f);
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = lo + lane; i < hi; i += 64) {
+      const double wi = w[i];
+      const double* x = stage + (i - lo_s);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < nq) acc[j] += wi * x[j * nthr];
+    }
+    const double z = wave_sum4(acc[0], acc[1], acc[2], acc[3]);
+    if ((lane & 15) == 0 && k < nq) {
+      const int q = sn.qs[k];
+      if (nslice == 1)
+        sn.o[q][(vcol * nsel + r) * nsens + s] = z;
+      else
+        sn.part[(((vcol * nslice + slice) * nsel + r) * 4 + q) * nsens + s] = z;
+    }
+  }
+  __syncthreads();
+}
+
+// Widest balanced band slices (lev_slices, at most 1024 lanes, halved down to 64) whose LDS `bytes(nthr)` fits `cap`; nslice = 0: none fits.
+template <class F>
+inline LevSlices lev_slices_fit(int nb, size_t cap, F bytes) {
+  int wmax = 1024;
+  while (wmax >= 64 && bytes(wmax) > cap) wmax >>= 1;
+  if (wmax < 64) return LevSlices{0, 0, 0};
+  return lev_slices(nb, wmax);
+}
+
+// What every sensor launcher does around its kernel.  sens_probe: records the slice count for the workspace query and refuses (before
+// any launch) a finish grid beyond 2^31 blocks; sens_finish: the finish kernel where several slices ran.
+inline int sens_probe(SensLaunch* sl, const LevSlices& ls, long long nv, int nsel) {
+  sl->nslice = ls.nslice;
+  if (ls.nslice > 1 && nv * nsel * 4 * sl->sn.nsens / 256 >= 0x7fffffffLL) return CRT_ERR_UNSUPPORTED;
+  return CRT_OK;
+}
+int launch_sens_finish(const SensArgs& sn, long long nv, int nslice, int per, int nb, int nsel, hipStream_t s);
+inline int sens_finish(const SensLaunch* sl, const LevSlices& ls, long long nv, int nb, int nsel, hipStream_t s) {
+  return ls.nslice > 1 ? launch_sens_finish(sl->sn, nv, ls.nslice, ls.per, nb, nsel, s) : (int)CRT_OK;
+}
+
+// (launch_sens_finish, sensor.hip: adds the slice partial sums of sens_row in ascending slice order; nv = ncol, series: ncol * nt)
+
 // sr: nullptr = the per-step kernel; else the series kernel of the same form (same slices, same LDS layout, same M).  probe: choose the
-// configuration and return its status (CRT_OK / CRT_ERR_UNSUPPORTED) without launching anything.
-int launch_closed_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr = nullptr, bool probe = false);
-int launch_tridiag_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr = nullptr, bool probe = false);
-int launch_zqpa_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr = nullptr, bool probe = false);
-int launch_tri_lev_n79_f64(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe);
-int launch_tri_lev_n79_f32(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe);
-int launch_tri_lev_zq_f64(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe);
-int launch_tri_lev_zq_f32(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe);
+// configuration and return its status (CRT_OK / CRT_ERR_UNSUPPORTED) without launching anything.  sl: nullptr = the level spectra; else the
+// sensor-band form of the same kernel (la.o unused), followed by the finish kernel where several slices ran.
+int launch_closed_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr = nullptr, bool probe = false,
+                      SensLaunch* sl = nullptr);
+int launch_tridiag_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr = nullptr, bool probe = false,
+                       SensLaunch* sl = nullptr);
+int launch_zqpa_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr = nullptr, bool probe = false,
+                    SensLaunch* sl = nullptr);
+int launch_tri_lev_n79_f64(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl);
+int launch_tri_lev_n79_f32(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl);
+int launch_tri_lev_zq_f64(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl);
+int launch_tri_lev_zq_f32(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl);
 
 // launchers implemented in the .hip files
 int launch_colpre(const ColArgs& a, hipStream_t s);

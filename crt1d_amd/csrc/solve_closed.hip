@@ -1230,11 +1230,20 @@ int launch_int_io(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const Se
 // bitwise by walking from 8 floor(j / 8) (uniform) or from j itself (ragged).  Selected levels in one block of 8 share the walk.
 // lev_body: the walk and the stores, on the record `rec` of the workgroup's column (blockIdx.x), for band slice `slice`; oshift (elements,
 // workgroup-uniform) is added to the [column][nsel][nb] output index: 0 in k_lev, the offset of slice [column][t] in k_lev_series.
-template <class S, typename TIO>
-__device__ __forceinline__ void lev_body(const SolveArgs& a, const LevArgs& la, int per, const double* rec, int slice, long long oshift) {
+// SENS (sensor-band outputs, SensArgs): no row is stored; sens_row reduces it against the sensor set, on the staging row `stage` in LDS.
+// Its barriers need every lane, so a lane without a band of the slice stays: it walks a valid band all the same (its own index where the
+// spectrum has that band -- a band of the next slice --, else the last band nb - 1) and stages zeros.
+template <class S, typename TIO, bool SENS = false>
+__device__ __forceinline__ void lev_body(const SolveArgs& a, const LevArgs& la, int per, const double* rec, int slice, long long oshift,
+                                         const SensArgs* sn = nullptr, double* stage = nullptr, int nslice = 1, long long vcol = 0) {
   const int c = blockIdx.x, nz = a.nz, nb = a.nb;
-  const int b = slice * per + threadIdx.x;
-  if ((int)threadIdx.x >= per || b >= nb) return;  // (no barrier below)
+  int b = slice * per + threadIdx.x;
+  const bool live = (int)threadIdx.x < per && b < nb;
+  if constexpr (!SENS) {
+    if (!live) return;  // (no barrier below)
+  } else {
+    b = min(b, nb - 1);
+  }
   S st;
   st.init(rec, load_band<TIO>(a, c, b, S::SOIL), a);
   const bool unif = rec[S_UNIF] != 0.0;
@@ -1246,10 +1255,15 @@ __device__ __forceinline__ void lev_body(const SolveArgs& a, const LevArgs& la, 
     double val[S::NARR];
     for (int jj = j0; jj <= j; ++jj) st.level(jj, rec, nz, val);
     next = j + 1;
-    const long long o = ((long long)c * nsel + r) * nb + b + oshift;
+    if constexpr (SENS) {
+      const double v4[4] = {val[0], val[1], val[2], val[3]};
+      sens_row(*sn, stage, v4, live, slice, per, nb, nslice, vcol, nsel, r);
+    } else {
+      const long long o = ((long long)c * nsel + r) * nb + b + oshift;
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if (la.o[q]) __builtin_nontemporal_store((TIO)val[q], outp<TIO>(la.o[q]) + o);
+      for (int q = 0; q < 4; ++q)
+        if (la.o[q]) __builtin_nontemporal_store((TIO)val[q], outp<TIO>(la.o[q]) + o);
+    }
   }
 }
 
@@ -1274,8 +1288,56 @@ __global__ __launch_bounds__(MAXT) void k_lev_series(SolveArgs a, LevArgs la, Se
                        [&](const SolveArgs& at, int slice, long long oshift) { lev_body<S, TIO>(at, la, per, lds, slice, oshift); });
 }
 
+// k_lev with sensor-band outputs: LDS = record | staging row [4][nthr] at off_st
+template <class S, typename TIO, int MAXT>
+__global__ __launch_bounds__(MAXT) void k_lev_sens(SolveArgs a, LevArgs la, SensArgs sn, int per, int off_st) {
+  extern __shared__ double lds[];
+  const double* rec = a.ws + (long long)blockIdx.x * a.reclen;
+  for (int i = threadIdx.x; i < a.reclen; i += blockDim.x) lds[i] = rec[i];
+  __syncthreads();
+  lev_body<S, TIO, true>(a, la, per, lds, blockIdx.y, 0, &sn, lds + off_st, gridDim.y, blockIdx.x);
+}
+
+template <class S, int MAXT>
+__global__ __launch_bounds__(MAXT) void k_lev_sens_series(SolveArgs a, LevArgs la, SensArgs sn, SeriesArgs sr, int per, int off_st, int nslice) {
+  extern __shared__ double lds[];
+  series_lev_step<double>(a, la, sr, nslice, lds, [&](const SolveArgs& at, int slice, long long, long long v) {
+    lev_body<S, double, true>(at, la, per, lds, slice, 0, &sn, lds + off_st, nslice, v);
+  });
+}
+
 template <class S, typename TIO>
-int launch_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
+int launch_lev_sens(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl) {
+  const LevSlices ls = lev_slices(a.nb, 1024);  // (no narrowing: the record and one staging row are all the LDS)
+  if (ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
+  const int off_st = (a.reclen + 1) & ~1;
+  const size_t sh = ((size_t)off_st + (size_t)SENS_STAGE * ls.nthr) * sizeof(double);
+  if (sh > 160 * 1024) return CRT_ERR_UNSUPPORTED;  // record and staging row in LDS
+  const long long nv = (long long)a.ncol * (sr ? sr->nt : 1);
+  dim3 grid(a.ncol, ls.nslice);
+  if (sr && (sizeof(TIO) != 8 || !lev_series_grid(a.ncol, sr->nt, ls.nslice, &grid))) return CRT_ERR_UNSUPPORTED;
+  int st = sens_probe(sl, ls, nv, la.nsel);
+  if (probe || st != CRT_OK) return st;
+  if (sr) {
+    if constexpr (sizeof(TIO) == 8) {
+      auto gos = [&](auto kern) { return launch_kernel(kern, grid, ls.nthr, sh, s, a, la, sl->sn, *sr, ls.per, off_st, ls.nslice); };
+      st = ls.nthr <= 256 ? gos(k_lev_sens_series<S, 256>) : ls.nthr <= 512 ? gos(k_lev_sens_series<S, 512>) : gos(k_lev_sens_series<S, 1024>);
+    } else {
+      return CRT_ERR_UNSUPPORTED;
+    }
+  } else {
+    auto go = [&](auto kern) { return launch_kernel(kern, grid, ls.nthr, sh, s, a, la, sl->sn, ls.per, off_st); };
+    st = ls.nthr <= 256 ? go(k_lev_sens<S, TIO, 256>) : ls.nthr <= 512 ? go(k_lev_sens<S, TIO, 512>) : go(k_lev_sens<S, TIO, 1024>);
+  }
+  if (st != CRT_OK || (st = sens_finish(sl, ls, nv, a.nb, la.nsel, s)) != CRT_OK) return st;
+  note_kernel("%sk_lev_sens%s<%s>%s nsel=%d nsens=%d slice=%d%s", sr ? "k_colpre<canopy> + k_colsun + " : "", sr ? "_series" : "", S::NAME,
+              sizeof(TIO) == 8 ? "" : " f32", la.nsel, sl->sn.nsens, ls.per, ls.nslice > 1 ? " + k_sens_finish" : "");
+  return CRT_OK;
+}
+
+template <class S, typename TIO>
+int launch_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl) {
+  if (sl) return launch_lev_sens<S, TIO>(a, la, s, sr, probe, sl);
   const LevSlices ls = lev_slices(a.nb, 1024);  // the record is all the LDS a workgroup needs
   if (ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
   const size_t sh = (size_t)a.reclen * sizeof(double);
@@ -1312,19 +1374,19 @@ int launch_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s, const Serie
 }
 
 template <class S>
-int launch_lev_io(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
-  return a.f32 ? launch_lev<S, float>(a, la, s, sr, probe) : launch_lev<S, double>(a, la, s, sr, probe);
+int launch_lev_io(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl) {
+  return a.f32 ? launch_lev<S, float>(a, la, s, sr, probe, sl) : launch_lev<S, double>(a, la, s, sr, probe, sl);
 }
 
 }  // namespace
 
-int launch_closed_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
+int launch_closed_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl) {
   switch (scheme) {
-    case CRT_SCHEME_2S: return launch_lev_io<Sch2s>(a, la, s, sr, probe);
-    case CRT_SCHEME_4S: return launch_lev_io<Sch4s>(a, la, s, sr, probe);
-    case CRT_SCHEME_BL: return launch_lev_io<SchBl>(a, la, s, sr, probe);
-    case CRT_SCHEME_G77: return launch_lev_io<SchG77<false>>(a, la, s, sr, probe);
-    case CRT_SCHEME_BF: return launch_lev_io<SchG77<true>>(a, la, s, sr, probe);
+    case CRT_SCHEME_2S: return launch_lev_io<Sch2s>(a, la, s, sr, probe, sl);
+    case CRT_SCHEME_4S: return launch_lev_io<Sch4s>(a, la, s, sr, probe, sl);
+    case CRT_SCHEME_BL: return launch_lev_io<SchBl>(a, la, s, sr, probe, sl);
+    case CRT_SCHEME_G77: return launch_lev_io<SchG77<false>>(a, la, s, sr, probe, sl);
+    case CRT_SCHEME_BF: return launch_lev_io<SchG77<true>>(a, la, s, sr, probe, sl);
     default: return CRT_ERR_BAD_ARG;
   }
 }

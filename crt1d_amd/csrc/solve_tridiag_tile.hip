@@ -25,9 +25,9 @@ int launch_tridiag_int(int scheme, const SolveArgs& a, const IntArgs& ia, hipStr
   return CRT_ERR_BAD_ARG;
 }
 
-int launch_tridiag_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
-  if (scheme == CRT_SCHEME_N79) return a.f32 ? launch_tri_lev_n79_f32(a, la, s, sr, probe) : launch_tri_lev_n79_f64(a, la, s, sr, probe);
-  if (scheme == CRT_SCHEME_ZQ) return a.f32 ? launch_tri_lev_zq_f32(a, la, s, sr, probe) : launch_tri_lev_zq_f64(a, la, s, sr, probe);
+int launch_tridiag_lev(int scheme, const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl) {
+  if (scheme == CRT_SCHEME_N79) return a.f32 ? launch_tri_lev_n79_f32(a, la, s, sr, probe, sl) : launch_tri_lev_n79_f64(a, la, s, sr, probe, sl);
+  if (scheme == CRT_SCHEME_ZQ) return a.f32 ? launch_tri_lev_zq_f32(a, la, s, sr, probe, sl) : launch_tri_lev_zq_f64(a, la, s, sr, probe, sl);
   return CRT_ERR_BAD_ARG;
 }
 

@@ -16,8 +16,9 @@ int TRI_CAT(launch_tri_int_, TRI_TAG, TRI_TIOTAG, )(const SolveArgs& a, const In
   return launch_int_scheme<TRI_SCHEME, TRI_TIO>(a, ia, s, sr);
 }
 
-int TRI_CAT(launch_tri_lev_, TRI_TAG, TRI_TIOTAG, )(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
-  return launch_lev_scheme<TRI_SCHEME, TRI_TIO>(a, la, s, sr, probe);
+int TRI_CAT(launch_tri_lev_, TRI_TAG, TRI_TIOTAG, )(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe,
+                                                  SensLaunch* sl) {
+  return launch_lev_scheme<TRI_SCHEME, TRI_TIO>(a, la, s, sr, probe, sl);
 }
 
 }  // namespace crt

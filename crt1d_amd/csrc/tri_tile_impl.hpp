@@ -656,14 +656,23 @@ int launch_int_scheme(const SolveArgs& a, const IntArgs& ia, hipStream_t s, cons
 // reduces a level, this one stores the row if the level is selected.  The rows come from the top and the selected levels ascend, so a
 // cursor from the last selected level down is the (wave-uniform) selection test.  Row values are the profile kernels' expressions
 // (S::value<>: I_dr = bc rec[k], F formed in the scheme's own order) on the same back-substituted pair: the same bits.
-template <class S, typename TIO, int M>
+// SENS (sensor-band outputs, SensArgs): a picked row is not stored; sens_row reduces it against the sensor set on the staging row `stage`
+// (the selection test is workgroup-uniform, and a lane without a band of the slice stays -- it walks a valid band all the same, its own
+// index where the spectrum has that band, else nb - 1, and stages zeros --: sens_row's barriers see every lane).
+template <class S, typename TIO, int M, bool SENS = false>
 __device__ __forceinline__ void tri_lev_body(const SolveArgs& a, const LevArgs& la, int per, int off_ck, double* lds, int slice,
-                                             long long oshift) {  // oshift: 0, or the offset of slice [column][t] (series, workgroup-uniform)
+                                             long long oshift,  // oshift: 0, or the offset of slice [column][t] (series, workgroup-uniform)
+                                             const SensArgs* sn = nullptr, double* stage = nullptr, int nslice = 1, long long vcol = 0) {
   const int nb = a.nb, nz = a.nz, nsel = la.nsel;
   const int tid = threadIdx.x, nthr = blockDim.x;
   const int c = blockIdx.x;
-  const int b = slice * per + tid;
-  if (tid >= per || b >= nb) return;  // (no barrier below)
+  int b = slice * per + tid;
+  const bool live = tid < per && b < nb;
+  if constexpr (!SENS) {
+    if (!live) return;  // (no barrier below)
+  } else {
+    b = min(b, nb - 1);
+  }
   const double* rec = lds;
   double* ck = lds + off_ck + tid;  // [nck][2][nthr]
   S st;
@@ -716,15 +725,56 @@ __device__ __forceinline__ void tri_lev_body(const SolveArgs& a, const LevArgs& 
           const double t[2] = {o[0], o[1]};  // the staged I_df_d, I_df_u of the profile kernels' tile
           const double v[4] = {S::template value<0>(rec, nz, k, bc, invmu, t, 1, 0), t[0], t[1],
                                S::template value<3>(rec, nz, k, bc, invmu, t, 1, 0)};
-          const long long oo = ((long long)c * nsel + r) * nb + b + oshift;
+          if constexpr (SENS) {
+            sens_row(*sn, stage, v, live, slice, per, nb, nslice, vcol, nsel, r);
+          } else {
+            const long long oo = ((long long)c * nsel + r) * nb + b + oshift;
 #pragma unroll
-          for (int q = 0; q < 4; ++q)
-            if (la.o[q]) __builtin_nontemporal_store((TIO)v[q], outp<TIO>(la.o[q]) + oo);
+            for (int q = 0; q < 4; ++q)
+              if (la.o[q]) __builtin_nontemporal_store((TIO)v[q], outp<TIO>(la.o[q]) + oo);
+          }
           --r;
         }
       }
     }
   }
+}
+
+// k_tri_lev with sensor-band outputs: LDS = record | checkpoints | staging row [4][nthr] at off_st.  Four waves per SIMD at M = 8 (128
+// registers) where k_tri_lev asks for five (96): at 96 the per-step form spills 36 bytes per lane.
+template <class S, typename TIO, int M, int MAXT>
+__global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(M <= 8 ? 4 : 3))) void k_tri_lev_sens(SolveArgs a, LevArgs la, SensArgs sn,
+                                                                                                             int per, int off_ck, int off_st) {
+  extern __shared__ double lds[];
+  {
+    const double* src = a.ws + (long long)blockIdx.x * a.reclen;
+    for (int i = threadIdx.x; i < a.reclen; i += blockDim.x) lds[i] = src[i];
+  }
+  __syncthreads();
+  typedef typename UniformOf<S>::type SU;
+  if constexpr (!std::is_same<S, SU>::value) {
+    if (lds[S_UNIF] != 0.0) {
+      tri_lev_body<SU, TIO, M, true>(a, la, per, off_ck, lds, blockIdx.y, 0, &sn, lds + off_st, gridDim.y, blockIdx.x);
+      return;
+    }
+  }
+  tri_lev_body<S, TIO, M, true>(a, la, per, off_ck, lds, blockIdx.y, 0, &sn, lds + off_st, gridDim.y, blockIdx.x);
+}
+
+template <class S, int M, int MAXT>
+__global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(M <= 8 ? 4 : 3))) void k_tri_lev_sens_series(
+    SolveArgs a, LevArgs la, SensArgs sn, SeriesArgs sr, int per, int off_ck, int off_st, int nslice) {
+  extern __shared__ double lds[];
+  typedef typename UniformOf<S>::type SU;
+  series_lev_step<double>(a, la, sr, nslice, lds, [&](const SolveArgs& at, int slice, long long, long long vcol) {
+    if constexpr (!std::is_same<S, SU>::value) {
+      if (lds[S_UNIF] != 0.0) {
+        tri_lev_body<SU, double, M, true>(at, la, per, off_ck, lds, slice, 0, &sn, lds + off_st, nslice, vcol);
+        return;
+      }
+    }
+    tri_lev_body<S, double, M, true>(at, la, per, off_ck, lds, slice, 0, &sn, lds + off_st, nslice, vcol);
+  });
 }
 
 template <class S, typename TIO, int M, int MAXT>
@@ -774,13 +824,43 @@ inline size_t tri_lev_lds_bytes(const SolveArgs& a, int M, int nthr, int* off_ck
   return ((size_t)ock + 2 * (size_t)nck * nthr) * sizeof(double);
 }
 
+// the sensor-band form: the staging row [4][nthr] behind the checkpoints, slices narrowed until both fit
+template <class S, typename TIO, int M>
+int launch_lev_sens_m(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl) {
+  auto bytes = [&](int nthr) { return tri_lev_lds_bytes<S>(a, M, nthr) + (size_t)SENS_STAGE * nthr * sizeof(double); };
+  const LevSlices ls = lev_slices_fit(a.nb, MAX_WG_LDS, bytes);
+  if (ls.nslice == 0 || ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
+  int off_ck;
+  const int off_st = (int)(tri_lev_lds_bytes<S>(a, M, ls.nthr, &off_ck) / sizeof(double));
+  const size_t sh = bytes(ls.nthr);
+  const long long nv = (long long)a.ncol * (sr ? sr->nt : 1);
+  dim3 grid(a.ncol, ls.nslice);
+  if (sr && (sizeof(TIO) != 8 || !lev_series_grid(a.ncol, sr->nt, ls.nslice, &grid))) return CRT_ERR_UNSUPPORTED;
+  int st = sens_probe(sl, ls, nv, la.nsel);
+  if (probe || st != CRT_OK) return st;
+  if (sr) {
+    if constexpr (sizeof(TIO) == 8) {
+      auto gos = [&](auto kern) { return launch_kernel(kern, grid, ls.nthr, sh, s, a, la, sl->sn, *sr, ls.per, off_ck, off_st, ls.nslice); };
+      st = ls.nthr <= 256   ? gos(k_tri_lev_sens_series<S, M, 256>)
+           : ls.nthr <= 512 ? gos(k_tri_lev_sens_series<S, M, 512>)
+                            : gos(k_tri_lev_sens_series<S, M, 1024>);
+    } else {
+      return CRT_ERR_UNSUPPORTED;
+    }
+  } else {
+    auto go = [&](auto kern) { return launch_kernel(kern, grid, ls.nthr, sh, s, a, la, sl->sn, ls.per, off_ck, off_st); };
+    st = ls.nthr <= 256 ? go(k_tri_lev_sens<S, TIO, M, 256>) : ls.nthr <= 512 ? go(k_tri_lev_sens<S, TIO, M, 512>) : go(k_tri_lev_sens<S, TIO, M, 1024>);
+  }
+  if (st != CRT_OK || (st = sens_finish(sl, ls, nv, a.nb, la.nsel, s)) != CRT_OK) return st;
+  note_kernel("%sk_tri_lev_sens%s<%s>%s M=%d nsel=%d nsens=%d slice=%d%s", sr ? "k_colpre<canopy> + k_colsun + " : "", sr ? "_series" : "", S::NAME,
+              sizeof(TIO) == 8 ? "" : " f32", M, la.nsel, sl->sn.nsens, ls.per, ls.nslice > 1 ? " + k_sens_finish" : "");
+  return CRT_OK;
+}
+
 template <class S, typename TIO, int M>
 int launch_lev_m(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
-  int wmax = 1024;  // widest slice whose checkpoints fit
-  while (wmax >= 64 && tri_lev_lds_bytes<S>(a, M, wmax) > MAX_WG_LDS) wmax >>= 1;
-  if (wmax < 64) return CRT_ERR_UNSUPPORTED;
-  const LevSlices ls = lev_slices(a.nb, wmax);
-  if (ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
+  const LevSlices ls = lev_slices_fit(a.nb, MAX_WG_LDS, [&](int nthr) { return tri_lev_lds_bytes<S>(a, M, nthr); });  // widest slice whose checkpoints fit
+  if (ls.nslice == 0 || ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
   int off_ck;
   const size_t sh = tri_lev_lds_bytes<S>(a, M, ls.nthr, &off_ck);
   if (sr) {
@@ -810,7 +890,12 @@ int launch_lev_m(const SolveArgs& a, const LevArgs& la, hipStream_t s, const Ser
 }
 
 template <class S, typename TIO>
-int launch_lev_scheme(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
+int launch_lev_scheme(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl) {
+  if (sl) {
+    int st = launch_lev_sens_m<S, TIO, 8>(a, la, s, sr, probe, sl);
+    if (st == CRT_ERR_UNSUPPORTED) st = launch_lev_sens_m<S, TIO, 16>(a, la, s, sr, probe, sl);
+    return st;
+  }
   int st = launch_lev_m<S, TIO, 8>(a, la, s, sr, probe);  // M = 16 (half the checkpoints) only where M = 8 does not fit a 64-band slice
   if (st == CRT_ERR_UNSUPPORTED) st = launch_lev_m<S, TIO, 16>(a, la, s, sr, probe);
   return st;

@@ -945,9 +945,14 @@ int launch_zqpa_int_io(const SolveArgs& a, const IntArgs& ia, hipStream_t s, con
 // zqpa_lev_body runs on the record in lds[0 .. reclen), which the caller has written but not yet synchronised (the barrier behind the slot
 // initialisation below covers it); oshift (elements, workgroup-uniform) is added to the [column][nsel][nb] output index: 0 in
 // k_zqpa_lev, the offset of slice [column][t] in k_zqpa_lev_series.
-template <typename TIO, int M>
+//
+// SENS (sensor-band outputs, SensArgs): an interpolated row is not stored; sens_row reduces it against the sensor set on the staging row
+// `stage` (a lane without a band of the slice stays -- it walks a valid band all the same, its own index where the spectrum has that band,
+// else nb - 1, and stages zeros --: sens_row's barriers see every lane).
+template <typename TIO, int M, bool SENS = false>
 __device__ __forceinline__ void zqpa_lev_body(const SolveArgs& g, const LevArgs& la, int nzo, int per, int off_map, int off_ck, int off_val,
-                                              double* lds, int slice, long long oshift) {
+                                              double* lds, int slice, long long oshift, const SensArgs* sn = nullptr, double* stage = nullptr,
+                                              int nslice = 1, long long vcol = 0) {
   typedef TriZq S;
   const int Mg = g.nz, nb = g.nb, nsel = la.nsel;
   const int tid = threadIdx.x, nthr = blockDim.x;
@@ -976,8 +981,13 @@ __device__ __forceinline__ void zqpa_lev_body(const SolveArgs& g, const LevArgs&
     slot[Mg] = lowest;
   }
   __syncthreads();
-  const int b = slice * per + tid;
-  if (tid >= per || b >= nb) return;  // (no barrier below)
+  int b = slice * per + tid;
+  const bool live = tid < per && b < nb;
+  if constexpr (!SENS) {
+    if (!live) return;  // (no barrier below)
+  } else {
+    b = min(b, nb - 1);
+  }
   double* val = lds + off_val + tid;  // [nslot][2][nthr]
   double* ck = lds + off_ck + tid;    // [nck][2][nthr]
   S st;
@@ -1044,11 +1054,37 @@ __device__ __forceinline__ void zqpa_lev_body(const SolveArgs& g, const LevArgs&
     const double up = ua + (ub - ua) * w;  // :361
     const double idr = bc * ekl[j];        // :354-355
     const double v[4] = {idr, dn, up, idr * invmu + 2 * up + 2 * dn};  // :412
-    const long long oo = ((long long)c * nsel + r) * nb + b + oshift;
+    if constexpr (SENS) {
+      sens_row(*sn, stage, v, live, slice, per, nb, nslice, vcol, nsel, r);
+    } else {
+      const long long oo = ((long long)c * nsel + r) * nb + b + oshift;
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if (la.o[q]) __builtin_nontemporal_store((TIO)v[q], outp<TIO>(la.o[q]) + oo);
+      for (int q = 0; q < 4; ++q)
+        if (la.o[q]) __builtin_nontemporal_store((TIO)v[q], outp<TIO>(la.o[q]) + oo);
+    }
   }
+}
+
+// k_zqpa_lev with sensor-band outputs: the staging row [4][nthr] at off_st, behind the kept rows
+template <typename TIO, int M, int MAXT>
+__global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4))) void k_zqpa_lev_sens(SolveArgs g, LevArgs la, SensArgs sn, int nzo, int per,
+                                                                                                int off_map, int off_ck, int off_val, int off_st) {
+  extern __shared__ double lds[];
+  {
+    const double* src = g.ws + (long long)blockIdx.x * g.reclen;
+    for (int i = threadIdx.x; i < g.reclen; i += blockDim.x) lds[i] = src[i];
+  }
+  zqpa_lev_body<TIO, M, true>(g, la, nzo, per, off_map, off_ck, off_val, lds, blockIdx.y, 0, &sn, lds + off_st, gridDim.y, blockIdx.x);
+}
+
+template <int M, int MAXT>
+__global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4))) void k_zqpa_lev_sens_series(SolveArgs g, LevArgs la, SensArgs sn,
+                                                                                                       SeriesArgs sr, int per, int off_map, int off_ck,
+                                                                                                       int off_val, int off_st, int nslice) {
+  extern __shared__ double lds[];
+  series_lev_step<double>(g, la, sr, nslice, lds, [&](const SolveArgs& gt, int slice, long long, long long vcol) {
+    zqpa_lev_body<double, M, true>(gt, la, sr.nz, per, off_map, off_ck, off_val, lds, slice, 0, &sn, lds + off_st, nslice, vcol);
+  });
 }
 
 template <typename TIO, int M, int MAXT>
@@ -1089,14 +1125,51 @@ inline ZqPaLevLds zqpa_lev_lds(const SolveArgs& a, int M, int nthr, int nsel) {
   return L;
 }
 
+// the sensor-band form: the staging row [4][nthr] behind the kept rows, slices narrowed until everything fits
+template <typename TIO>
+int launch_zqpa_lev_sens(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl) {
+  constexpr int M = 8;
+  auto bytes = [&](int nthr) { return zqpa_lev_lds(a, M, nthr, la.nsel).bytes + (size_t)SENS_STAGE * nthr * sizeof(double); };
+  const LevSlices ls = lev_slices_fit(a.nb, MAX_WG_LDS, bytes);
+  if (ls.nslice == 0 || ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
+  const ZqPaLevLds L = zqpa_lev_lds(a, M, ls.nthr, la.nsel);
+  const int off_st = (int)(L.bytes / sizeof(double));
+  const size_t sh = bytes(ls.nthr);
+  const int Mg = zqpa_M(a.nz);
+  SolveArgs g = a;  // computational-grid solve: nz := Mg (the record keeps the caller's nz: passed separately)
+  g.nz = Mg;
+  for (int i = 0; i < 7; ++i) g.o[i] = nullptr;
+  const long long nv = (long long)a.ncol * (sr ? sr->nt : 1);
+  dim3 grid(a.ncol, ls.nslice);
+  if (sr && (sizeof(TIO) != 8 || !lev_series_grid(a.ncol, sr->nt, ls.nslice, &grid))) return CRT_ERR_UNSUPPORTED;
+  int st = sens_probe(sl, ls, nv, la.nsel);
+  if (probe || st != CRT_OK) return st;
+  if (sr) {
+    if constexpr (sizeof(TIO) == 8) {
+      auto gos = [&](auto kern) {
+        return launch_kernel(kern, grid, ls.nthr, sh, s, g, la, sl->sn, *sr, ls.per, L.off_map, L.off_ck, L.off_val, off_st, ls.nslice);
+      };
+      st = ls.nthr <= 256   ? gos(k_zqpa_lev_sens_series<M, 256>)
+           : ls.nthr <= 512 ? gos(k_zqpa_lev_sens_series<M, 512>)
+                            : gos(k_zqpa_lev_sens_series<M, 1024>);
+    } else {
+      return CRT_ERR_UNSUPPORTED;
+    }
+  } else {
+    auto go = [&](auto kern) { return launch_kernel(kern, grid, ls.nthr, sh, s, g, la, sl->sn, a.nz, ls.per, L.off_map, L.off_ck, L.off_val, off_st); };
+    st = ls.nthr <= 256 ? go(k_zqpa_lev_sens<TIO, M, 256>) : ls.nthr <= 512 ? go(k_zqpa_lev_sens<TIO, M, 512>) : go(k_zqpa_lev_sens<TIO, M, 1024>);
+  }
+  if (st != CRT_OK || (st = sens_finish(sl, ls, nv, a.nb, la.nsel, s)) != CRT_OK) return st;
+  note_kernel("%sk_zqpa_lev_sens%s<zq_pa>%s M=%d grid=%d nsel=%d nsens=%d slice=%d%s", sr ? "k_colpre<canopy> + k_colsun + " : "", sr ? "_series" : "",
+              sizeof(TIO) == 8 ? "" : " f32", M, Mg, la.nsel, sl->sn.nsens, ls.per, ls.nslice > 1 ? " + k_sens_finish" : "");
+  return CRT_OK;
+}
+
 template <typename TIO>
 int launch_zqpa_lev_io(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
   constexpr int M = 8;
-  int wmax = 1024;  // widest slice whose checkpoints and kept rows fit
-  while (wmax >= 64 && zqpa_lev_lds(a, M, wmax, la.nsel).bytes > MAX_WG_LDS) wmax >>= 1;
-  if (wmax < 64) return CRT_ERR_UNSUPPORTED;
-  const LevSlices ls = lev_slices(a.nb, wmax);
-  if (ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
+  const LevSlices ls = lev_slices_fit(a.nb, MAX_WG_LDS, [&](int nthr) { return zqpa_lev_lds(a, M, nthr, la.nsel).bytes; });  // widest slice whose checkpoints and kept rows fit
+  if (ls.nslice == 0 || ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
   const ZqPaLevLds L = zqpa_lev_lds(a, M, ls.nthr, la.nsel);
   const int Mg = zqpa_M(a.nz);
   SolveArgs g = a;  // computational-grid solve: nz := Mg (the record keeps the caller's nz: passed separately)
@@ -1128,7 +1201,8 @@ int launch_zqpa_lev_io(const SolveArgs& a, const LevArgs& la, hipStream_t s, con
 
 }  // namespace
 
-int launch_zqpa_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
+int launch_zqpa_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl) {
+  if (sl) return a.f32 ? launch_zqpa_lev_sens<float>(a, la, s, sr, probe, sl) : launch_zqpa_lev_sens<double>(a, la, s, sr, probe, sl);
   return a.f32 ? launch_zqpa_lev_io<float>(a, la, s, sr, probe) : launch_zqpa_lev_io<double>(a, la, s, sr, probe);
 }
 

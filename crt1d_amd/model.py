@@ -266,6 +266,47 @@ class Model:
         out = batched.solve_levels_series(scheme, cols, b, sun, levels)
         return {k: v[0].cpu().numpy() for k, v in out.items()}
 
+    @staticmethod
+    def _sensor_set(weights, nb):
+        from . import batched
+
+        if isinstance(weights, batched.SensorSet):
+            return weights
+        w = weights.cpu().numpy() if hasattr(weights, "cpu") else np.asarray(weights, dtype=np.float64)
+        if w.ndim == 1:
+            w = w[None, :]
+        if w.ndim != 2 or w.shape[1] != nb:
+            raise ValueError(f"`weights` must be (nsens, n_wl) = (nsens, {nb})")
+        return batched.SensorSet(w)
+
+    def run_series_sensors(self, psi, weights, levels=(0, -1), I_dr0_all=None, I_df0_all=None):
+        """:meth:`run_series_levels` folded with spectral responses in the same device call
+        (:class:`crt1d_amd.batched.SensorLevelsSeriesPlan`, ``ncol = 1``): ``weights`` is a dense ``(nsens, n_wl)`` array (for instance
+        :func:`crt1d_amd.spectra.sensor_weights`) or a :class:`crt1d_amd.batched.SensorSet`.  Returns ``{"I_dr", "I_df_d", "I_df_u", "F"}``
+        as NumPy arrays ``(nt, nsel, nsens)``: the sensor-weighted sums of the rows ``levels``.  The model's own state is not changed."""
+        from . import batched
+
+        scheme, cols, b, sun = self._series_inputs(psi, I_dr0_all, I_df0_all, "level")
+        out = batched.solve_sensor_levels_series(scheme, cols, b, sun, levels, self._sensor_set(weights, self.nwl))
+        return {k: v[0].cpu().numpy() for k, v in out.items()}
+
+    def run_sensors(self, weights, levels=(0, -1)):
+        """The sensor-band sums of the rows ``levels`` of what :meth:`run` leaves in ``m.out``, at the model's own sun state and spectra
+        (:class:`crt1d_amd.batched.SensorLevelsPlan`): ``{"I_dr", "I_df_d", "I_df_u", "F"}`` as NumPy arrays ``(nsel, nsens)``.
+        ``weights`` as for :meth:`run_series_sensors`.  The model's own state (``out``) is not changed."""
+        import torch
+
+        from . import batched
+
+        self._check_inputs()
+        p = self._p
+        scheme, cols, b, sun = self._series_inputs(np.atleast_1d(float(p["psi"])), None, None, "level")
+        cols = batched.Columns(psi=sun.psi[:, 0].contiguous(), lai=cols.lai, g_kind=cols.g_kind, g_param=cols.g_param, mla=cols.mla,
+                               g_at_psi=None if sun.g_at_psi is None else sun.g_at_psi[:, 0].contiguous(), g_table=cols.g_table)
+        b = batched.Bands(sun.I_dr0[:, 0].contiguous(), sun.I_df0[:, 0].contiguous(), b.leaf_r, b.leaf_t, b.soil_r)
+        out = batched.solve_sensor_levels(scheme, cols, b, levels, self._sensor_set(weights, self.nwl))
+        return {k: v[0].cpu().numpy() for k, v in out.items()}
+
     # ---- output container -------------------------------------------------------------------
     def _scheme_absorption_vars(self, nz):
         """The scheme's own absorption outputs (``aI*_scheme``): on levels or on layers, by their leading size."""

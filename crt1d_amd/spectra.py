@@ -112,6 +112,32 @@ def smear_tuv(x, y, bins):
     return smear_tuv_batched(x, y[None, :], np.asarray(bins, dtype=np.float64)).cpu().numpy()[0]
 
 
+def sensor_weights(wle, srf_x, srf_y):
+    """Sensor-band weights on the model bands from tabulated spectral responses: ``srf_y`` ``(nsens, nx)`` responses on the grid ``srf_x``
+    (``(nx,)`` shared, or ``(nsens, nx)``), ``wle`` the ``(nb + 1,)`` model band edges.  Returns the ``(nsens, nb)`` CUDA tensor of the mean
+    of each response over each model band -- :func:`smear_tuv_batched` applied to the responses -- which
+    :class:`crt1d_amd.batched.SensorSet` takes as it is (bands a response does not reach get weight 0 and stay outside its support)."""
+    y = np.asarray(srf_y, dtype=np.float64) if not hasattr(srf_y, "is_cuda") else srf_y
+    if y.ndim != 2:
+        raise ValueError("srf_y must be (nsens, nx)")
+    if np.ndim(wle) != 1 or np.shape(wle)[0] < 2:
+        raise ValueError("wle must hold the nb + 1 band edges")
+    return smear_tuv_batched(srf_x, y, wle)
+
+
+def boxcar_sensor_weights(wle, bounds):
+    """Boxcar sensor bands: ``bounds`` ``(nsens, 2)`` wavelength intervals -> ``(nsens, nb)`` NumPy weights, the fraction of each model
+    band ``[wle[i], wle[i+1]]`` inside each interval (:func:`x_frac_in_bounds`)."""
+    bounds = np.asarray(bounds, dtype=float)
+    if bounds.ndim == 1:
+        bounds = bounds[None, :]
+    if bounds.ndim != 2 or bounds.shape[1] != 2:
+        raise ValueError("bounds must be (nsens, 2)")
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        return np.stack([x_frac_in_bounds(wle, (b1, b2)) for b1, b2 in bounds])
+
+
 # ---- light-weighted band optics and band irradiance on the device (include/crt1d_hip_spectra.h) --------------------------------------
 def sub_bin_counts(x, edges, x_smear_nb=None):
     """Sub-bins per band as ``avg_optical_prop`` chooses them (``crt1d/spectra.py:185-189``): ``x_smear_nb``, or
