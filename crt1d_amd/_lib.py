@@ -273,6 +273,27 @@ def _sensor_signatures():
 _SENSOR_SIGNATURES = _sensor_signatures()
 SENSOR_EXPORTS = list(_SENSOR_SIGNATURES)
 
+# optical-property Jacobians of the level spectra (include/crt1d_hip_jac.h), again a header and a table of their own
+JAC_NPARAM = 3  # CRT_JAC_NPARAM: leaf_r, leaf_t, soil_r
+JAC_MAX_NZ = {"n79": 1076, "zq": 1200}  # CRT_JAC_MAX_NZ_N79, CRT_JAC_MAX_NZ_ZQ
+
+
+class CrtJacOut(ctypes.Structure):
+    _fields_ = [(k, _vp) for k in ("I_df_d", "I_df_u", "F")]
+
+
+def _jac_signatures():
+    P = ctypes.POINTER
+    i, i32, sz, ok = ctypes.c_int, ctypes.c_int32, ctypes.c_size_t, ctypes.c_int
+    return {
+        "crt_hip_levels_jac_workspace_bytes": (sz, [i, i32, i32, i32, i32]),
+        "crt_hip_levels_jac_f64": (ok, [i, P(CrtColumns), P(CrtBands), P(CrtOptions), P(i32), i32, P(CrtJacOut), _vp, sz, _vp]),
+    }
+
+
+_JAC_SIGNATURES = _jac_signatures()
+JAC_EXPORTS = list(_JAC_SIGNATURES)
+
 _lib = None
 
 
@@ -295,7 +316,7 @@ def load():
     import torch  # noqa: F401
 
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES, **_SENSOR_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES, **_SENSOR_SIGNATURES, **_JAC_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:

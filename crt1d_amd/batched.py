@@ -1288,3 +1288,102 @@ def sensor_albedo(scheme, cols: Columns, bands: Bands, sensors: SensorSet, **kw)
     for :class:`SensorLevelsPlan` (``keys`` is fixed here)."""
     r = solve_sensor_levels(scheme, cols, bands, (cols.nz - 1,), sensors, keys=("I_dr", "I_df_d", "I_df_u"), **kw)
     return r["I_df_u"][:, 0] / (r["I_dr"][:, 0] + r["I_df_d"][:, 0])
+
+
+# ---- optical-property Jacobians of the level spectra (include/crt1d_hip_jac.h) --------------------------------------------------------
+
+JAC_PARAMS = ("leaf_r", "leaf_t", "soil_r")  # the parameter axis of every Jacobian, in this order
+JAC_KEYS = ("I_df_d", "I_df_u", "F")  # I_dr does not depend on the optics
+JAC_SCHEMES = ("2s", "bl", "g77", "bf", "n79", "zq")
+
+
+def _jac_keys(keys):
+    keys = (keys,) if isinstance(keys, str) else tuple(keys)
+    if not keys or any(k not in JAC_KEYS for k in keys) or len(set(keys)) != len(keys):
+        raise ValueError(f"keys must be distinct names out of {JAC_KEYS}, got {keys!r}")
+    return keys
+
+
+def levels_jac_workspace_bytes(scheme, ncol, nz, nb, nsel):
+    """Device workspace of a :class:`LevelsJacPlan` call: the records of :func:`workspace_bytes`, at the same offsets."""
+    return int(_lib.load().crt_hip_levels_jac_workspace_bytes(_lib.SCHEME_IDS[scheme], ncol, nz, nb, nsel))
+
+
+class LevelsJacPlan(_SolvePlan):
+    """Pre-validated Jacobian of the level spectra (``crt_hip_levels_jac_f64``): ``out[k][c, r, p, b]`` is the exact derivative of
+    ``X[c, levels[r], b]`` (``X`` in ``keys``, any of ``I_df_d, I_df_u, F``: what :class:`LevelsPlan` returns) with respect to parameter
+    ``JAC_PARAMS[p]`` of the SAME column and band -- bands are independent, so this diagonal is the whole Jacobian.  Each array is
+    ``(ncol, nsel, 3, nb)`` float64.  One K0 and one kernel; no finite differences.  Schemes: ``JAC_SCHEMES`` (``4s`` and ``zq_pa`` are a
+    ValueError; n79 / zq beyond ``_lib.JAC_MAX_NZ`` levels a RuntimeError from the call).  bl has no soil and no upward stream: those slabs
+    are zeros.  A column's result is bitwise the same alone or in any batch, for any subset of ``keys`` and of ``levels``."""
+
+    _bad_jac_scheme = "scheme {!r} has no Jacobian kernel; served: " + ", ".join(JAC_SCHEMES)
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, levels, *, keys=JAC_KEYS, mu_s=0.501, tau_d_method="quad", out=None,
+                 workspace=None):
+        self._check_options(scheme, tau_d_method)
+        if scheme not in JAC_SCHEMES:
+            raise ValueError(self._bad_jac_scheme.format(scheme))
+        keys = _jac_keys(keys)
+        if bands.dtype != torch.float64:
+            raise TypeError("the Jacobian has no f32 storage form: bands must be float64")
+        self.levels, self.keys = normalize_levels(levels, cols.nz), keys
+        self._bind(scheme, cols, bands, mu_s, tau_d_method)
+        shape = (cols.ncol, len(self.levels), _lib.JAC_NPARAM, bands.nb)
+        out = _outputs({k: shape for k in keys}, out, torch.float64, cols.device, "output {!r}", lacks=True)
+        self.out = {k: out[k] for k in keys}
+        self._out = _lib.CrtJacOut(*[out[k].data_ptr() if k in keys else None for k in JAC_KEYS])
+        self._lev = (ctypes.c_int32 * len(self.levels))(*self.levels)
+        need = levels_jac_workspace_bytes(scheme, cols.ncol, cols.nz, bands.nb, len(self.levels))
+        self._finish("crt_hip_levels_jac_f64", need, workspace)
+
+    def _tail(self):
+        return self._lev, len(self.levels), ctypes.byref(self._out)
+
+
+def solve_levels_jac(scheme, cols: Columns, bands: Bands, levels, **kw):
+    """One-shot :class:`LevelsJacPlan`: ``{key: (ncol, nsel, 3, nb)}`` at the sorted levels ``normalize_levels(levels, nz)``."""
+    with torch.cuda.device(cols.device):
+        return LevelsJacPlan(scheme, cols, bands, levels, **kw)()
+
+
+def _jvp_direction(d, name, ncol, nb, device):
+    """A direction ``(ntan, nb)`` or ``(ncol, ntan, nb)`` (``None``: zeros) as a float64 tensor on ``device`` that broadcasts over columns."""
+    if d is None:
+        return None
+    d = torch.as_tensor(d, dtype=torch.float64)
+    if d.ndim == 2:
+        d = d[None]
+    if d.ndim != 3 or d.shape[2] != nb or d.shape[0] not in (1, ncol):
+        raise ValueError(f"`{name}` must be (ntan, nb) or (ncol, ntan, nb) with nb = {nb}, ncol = {ncol}")
+    return d.to(device)
+
+
+def sensor_jvp(scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, d_leaf_r, d_leaf_t, d_soil_r, **kw):
+    """The derivative of :class:`SensorLevelsPlan`'s sums along ``ntan`` directions of a leaf or soil model's parameter space: per key
+    ``(ncol, nsel, nsens, ntan)`` with ``out[c, r, s, k] = sum_b w_s[b] * sum_p J_p[c, r, b] * d_p[c, k, b]``.  ``d_leaf_r``, ``d_leaf_t``,
+    ``d_soil_r``: ``(ntan, nb)`` (the same directions for every column) or ``(ncol, ntan, nb)``, the derivatives of the three spectra with
+    respect to the model's parameters; ``None`` stands for zeros.  The Jacobian ``J`` comes from one :class:`LevelsJacPlan` call
+    (``kw`` goes there); the contraction runs in torch on the device."""
+    if not isinstance(sensors, SensorSet):
+        raise TypeError("sensors must be a SensorSet")
+    dirs = [_jvp_direction(d, "d_" + n, cols.ncol, bands.nb, cols.device) for n, d in zip(JAC_PARAMS, (d_leaf_r, d_leaf_t, d_soil_r))]
+    given = [d for d in dirs if d is not None]
+    if not given:
+        raise ValueError("at least one direction must be given")
+    ntan = given[0].shape[1]
+    if any(d.shape[1] != ntan for d in given):
+        raise ValueError("the directions must share ntan")
+    sensors.check(bands.nb, cols.device)
+    jac = solve_levels_jac(scheme, cols, bands, levels, **kw)
+    w = torch.as_tensor(sensors.dense(bands.nb)).to(cols.device)
+    out = {}
+    for k, J in jac.items():
+        t = None
+        for p, d in enumerate(dirs):
+            if d is None:
+                continue
+            term = J[:, :, p, None, :] * d[:, None, :, :]  # (ncol, nsel, ntan, nb)
+            t = term if t is None else t + term
+        out[k] = torch.einsum("crkb,sb->crsk", t, w)
+    return out

@@ -663,6 +663,44 @@ int crt_hip_sensor_levels_series_f64(int scheme, const crt_columns* cols, const 
   return sensor_impl(scheme, cols, bands, opts, levels, nsel, sensors, out, workspace, workspace_bytes, stream, 0, sun);
 }
 
+// ------------------------------------------------------------------------------------------
+// Optical-property Jacobians of the level spectra (include/crt1d_hip_jac.h): the checks of crt_hip_levels_f64, K0, one kernel of jac.hip.
+
+size_t crt_hip_levels_jac_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nsel) {
+  if (nsel < 1 || nsel > CRT_MAX_LEVEL_SELECT) return 0;
+  return crt_hip_workspace_bytes_nb(scheme, ncol, nz, nb);  // the records; the kernels keep nothing behind them
+}
+
+int crt_hip_levels_jac_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
+                           int32_t nsel, const crt_jac_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream) {
+  if (!scheme_ok(scheme) || !cols || !levels || !out) return CRT_ERR_BAD_ARG;
+  if (nsel < 1 || nsel > CRT_MAX_LEVEL_SELECT) return CRT_ERR_BAD_ARG;
+  if (!out->I_df_d && !out->I_df_u && !out->F) return CRT_ERR_BAD_ARG;
+  LevArgs la = {};
+  la.nsel = nsel;
+  for (int r = 0; r < nsel; ++r) {
+    if (levels[r] < 0 || levels[r] >= cols->nz) return CRT_ERR_BAD_ARG;
+    if (r > 0 && levels[r] <= levels[r - 1]) return CRT_ERR_BAD_ARG;  // strictly ascending: no duplicates
+    la.lev[r] = levels[r];
+  }
+  SolveOpts o;
+  const crt_outputs none = {};
+  const int chk = check_solve(scheme, cols, bands, opts, &none, workspace, workspace_bytes, nullptr, &la, nullptr, o);
+  if (chk == CRT_ERR_BAD_ARG || chk == CRT_ERR_SHAPE) return chk;  // an argument error is one for every scheme
+  if (scheme == CRT_SCHEME_4S || scheme == CRT_SCHEME_ZQ_PA) return CRT_ERR_UNSUPPORTED;  // whatever the workspace (a follow-up: crt1d_hip_jac.h)
+  if (chk != CRT_OK) return chk;
+  ColArgs ca;
+  SolveArgs sa;
+  build_args(scheme, cols, bands, &none, workspace, 0, o, ca, sa);
+  const JacArgs jo = {{out->I_df_d, out->I_df_u, out->F}};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (const int st = launch_jac(scheme, sa, la, jo, s, true)) return st;  // a shape that is not served: before K0 has written anything
+  if (!(o.flags & CRT_FLAG_SKIP_PRECOMPUTE))
+    if (const int st = launch_colpre(ca, s)) return st;
+  if (o.flags & CRT_FLAG_PRECOMPUTE_ONLY) return CRT_OK;
+  return launch_jac(scheme, sa, la, jo, s, false);
+}
+
 int crt_hip_bandsum_finish_f64(const crt_columns* cols, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream) {
   if (!cols || !out || !cols->psi || ngroup <= 0 || ngroup > INT_MAXG) return CRT_ERR_BAD_ARG;
   if (!out->aI || !out->aI_sl || !out->aI_sh || !out->I_dr || !out->I_df_d || !out->I_df_u || !out->F || !out->I_d) return CRT_ERR_BAD_ARG;

@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "crt1d_hip.h"
+#include "crt1d_hip_jac.h"
 #include "crt1d_hip_sensor.h"
 
 namespace crt {
@@ -900,6 +901,33 @@ int launch_tri_lev_n79_f64(const SolveArgs& a, const LevArgs& la, hipStream_t s,
 int launch_tri_lev_n79_f32(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl);
 int launch_tri_lev_zq_f64(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl);
 int launch_tri_lev_zq_f32(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl);
+
+// ------------------------------------------------------------------------------------------
+// Optical-property Jacobians of the level spectra (crt_hip_levels_jac_f64, include/crt1d_hip_jac.h; kernels in jac.hip)
+struct JacArgs {
+  double* o[3];  // d I_df_d, d I_df_u, d F: [ncol][nsel][3][nb] or NULL
+};
+// n79 / zq: the leading doubles of the record the kernel stages (header + the vectors it reads), the level states it keeps (every
+// JAC_TRI_CP-th one, 4 doubles per lane each), its LDS bytes with W lanes per workgroup, and the widest W out of 64, 32, 16 that fits 160 KB (0: none)
+constexpr int JAC_TRI_CP = 4;
+constexpr int jac_tri_nrec(int scheme, int nz) { return REC_HDR + (scheme == CRT_SCHEME_N79 ? 3 : 1) * nz; }
+constexpr size_t jac_tri_lds_bytes(int scheme, int nz, int W) {
+  const size_t nst = scheme == CRT_SCHEME_N79 ? (size_t)nz : (size_t)nz + 1, ncp = (nst + JAC_TRI_CP - 1) / JAC_TRI_CP;
+  return ((((size_t)jac_tri_nrec(scheme, nz) + 1) & ~(size_t)1) + ncp * 4 * W) * sizeof(double);
+}
+constexpr int jac_tri_lanes(int scheme, int nz) {
+  for (int W = 64; W >= 16; W >>= 1)
+    if (jac_tri_lds_bytes(scheme, nz, W) <= 160 * 1024) return W;
+  return 0;
+}
+static_assert(jac_tri_lanes(CRT_SCHEME_N79, CRT_JAC_MAX_NZ_N79) == 16 && jac_tri_lanes(CRT_SCHEME_N79, CRT_JAC_MAX_NZ_N79 + 1) == 0 &&
+                  jac_tri_lanes(CRT_SCHEME_ZQ, CRT_JAC_MAX_NZ_ZQ) == 16 && jac_tri_lanes(CRT_SCHEME_ZQ, CRT_JAC_MAX_NZ_ZQ + 1) == 0,
+              "the depth limits of crt1d_hip_jac.h are those of the LDS layout");
+static_assert(jac_tri_lanes(CRT_SCHEME_N79, 304) == 64 && jac_tri_lanes(CRT_SCHEME_N79, 305) == 32 && jac_tri_lanes(CRT_SCHEME_ZQ, 311) == 64 &&
+                  jac_tri_lanes(CRT_SCHEME_ZQ, 312) == 32,
+              "whole waves up to 304 (n79) / 311 (zq) levels, as crt1d_hip_jac.h says");
+// probe: return the status (CRT_OK / CRT_ERR_UNSUPPORTED) of the configuration without launching anything
+int launch_jac(int scheme, const SolveArgs& a, const LevArgs& la, const JacArgs& jo, hipStream_t s, bool probe);
 
 // launchers implemented in the .hip files
 int launch_colpre(const ColArgs& a, hipStream_t s);
