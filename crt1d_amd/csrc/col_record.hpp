@@ -6,7 +6,8 @@
 // Quadrature (the reference evaluates its integrals with adaptive QUADPACK, scipy.integrate.quad; on device they use FIXED nodes):
 //   * tau_d(L) = 2 int_0^{pi/2} exp(-K_b(psi) L) sin cos dpsi   (common.py:30-37)
 //     mu_bar   =   int_0^{pi/2} cos sin / G(psi) dpsi           (_solve_2s.py:32)
-//       6 panels x 16-point Gauss-Legendre on psi in [0, pi/2] (panel edges: colpre.hip)
+//       6 panels x 16-point Gauss-Legendre on psi in [0, pi/2] (panel edges and measured accuracy per leaf-angle class and L: colpre.hip
+//       PAN_EDGE; tau_d <= 1e-12, mu_bar <= 1.5e-12, 1 - tau_d <= 2.3e-12 for L >= 0.1 on every class, larger below)
 //   * G_int_1 = int_0^{mu_s} G(acos m) dm,  G_int_2 = int_{mu_s}^1   (_solve_4s.py:148-149): 16-point Gauss-Legendre each, in psi
 //   * '9sky': the reference's own 9 fixed angles                 (common.py:40-53)
 // A CRT_G_TABLE column brings G sampled at exactly these nodes (crt_hip_quad_nodes).

@@ -112,11 +112,15 @@ class Columns:
 # quadrature (replaces QUADPACK)
 
 
-def _graded_rule(n=24, edges=(0.0, 3e-5, 3e-4, 3e-3, 0.03, 0.2, 0.45, 0.7, 1.0)):
-    """Composite Gauss-Legendre on psi in [0, pi/2]: panels (edges in t = pi/2 - psi, fractions of pi/2) graded toward pi/2, where
-    e^{-G L / cos psi} has its boundary layer, and split at the wide end for 1/G of small-x ellipsoidal distributions.  8 x 24 nodes:
-    1 - tau_d(L) and mu_bar to <= 3e-15 relative for L in [1e-4, 20], x in [0.2, 3] against 30-digit quadrature -- deliberately a different
-    and finer rule than the device's 6 x 16 (csrc/colpre.hip), so that HIP-vs-oracle parity also checks the device's quadrature."""
+def _graded_rule(n=24, edges=(0.0, 3e-9, 3e-8, 3e-7, 3e-6, 3e-5, 3e-4, 3e-3, 0.03, 0.2, 0.45, 0.7, 1.0)):
+    """Composite Gauss-Legendre on psi in [0, pi/2]: panels (edges in t = pi/2 - psi, fractions of pi/2) graded by decades toward pi/2,
+    where e^{-G L / cos psi} has its boundary layer (at cos psi ~ G(pi/2) L), and split at the wide end for 1/G of small-x ellipsoidal
+    distributions.  12 x 24 nodes.  Measured by tests/test_quadrature_domain_cpu.py against converged 30-digit mpmath integrals, on the
+    ten leaf-angle classes of tests/domain_cases.py (every closed-form kind; ellipsoidal x in [0.2, 10], Bonan chi_l in [-0.4, 0.6]) and
+    L in {1e-6, 1e-5, 1e-4, 3e-4, 1e-3, 1e-2, 0.1, 1, 12}: tau_d, 1 - tau_d(L) and mu_bar <= 2e-15 relative.  The 8-panel rule this
+    replaces stopped at 3e-5: 2.5e-11 in 1 - tau_d for Bonan chi_l = 0.6 (G(pi/2) = 0.0014) at L = 1e-4, and 2e-9 for every class at
+    L = 1e-6, the layer thickness of a ragged 60-level profile of total LAI 0.01.  Deliberately a different and finer rule than the
+    device's 6 x 16 (csrc/colpre.hip), so that HIP-vs-oracle parity also checks the device's quadrature."""
     x, w = leggauss(n)
     T = PI / 2
     e = [T * f for f in edges]

@@ -1,5 +1,9 @@
 """Random-shape parity fuzz (tools; GPU box): every scheme on random (ncol, nb, nz), uniform and ragged dLAI, f64 against the oracle and f32
-storage against the rounded f64 result, plus the epilogue kernels.  usage: python tools/fuzz_parity.py [n_cases] [seed]"""
+storage against the rounded f64 result, plus the epilogue kernels.  usage: python tools/fuzz_parity.py [n_cases] [seed]
+
+The columns are drawn from synth.make_columns only: ellipsoidal-approx leaves, sun zenith 0-75 degrees, total LAI 0.5-8.  The other
+leaf-angle classes, a low sun and thin or dense canopies are covered by the domain batch of tests/domain_cases.py
+(tests/test_gpu_domain.py), not here."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
