@@ -179,27 +179,26 @@ size_t crt_hip_workspace_bytes_nb(int scheme, int32_t ncol, int32_t nz, int32_t 
   return n;
 }
 
+// the records of a series: canopy records [ncol][can_len] -- or `base` bytes where that is more -- then the sun records [ncol * nt][sun_len];
+// 0 for a size beyond size_t (arguments checked by the caller)
+static size_t series_record_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nt, size_t base) {
+  const size_t can = std::max(base, (size_t)ncol * (size_t)can_len(scheme, nz) * sizeof(double));
+  const size_t per = (size_t)sun_len(scheme, nz) * sizeof(double);
+  const size_t nsun = (size_t)ncol * (size_t)nt;
+  return nsun > (SIZE_MAX - can) / per ? 0 : can + nsun * per;
+}
+
 size_t crt_hip_series_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nt) {
   // Layout: canopy records [ncol][can_len] from the start, the sun records [ncol * nt][sun_len] right behind them.  The size is at least
   // the per-step workspace (so that one buffer serves both entries): where that is larger than the canopy records (zq_pa's scratch share
   // for its grid fluxes, which no integrated kernel uses), the difference is unused padding at the end.
   const size_t base = crt_hip_workspace_bytes_nb(scheme, ncol, nz, nb);
-  if (base == 0 || nt < 1) return 0;
-  const size_t can = (size_t)ncol * (size_t)can_len(scheme, nz) * sizeof(double);
-  const size_t per = (size_t)sun_len(scheme, nz) * sizeof(double);
-  const size_t nsun = (size_t)ncol * (size_t)nt;
-  if (nsun > (SIZE_MAX - (base > can ? base : can)) / per) return 0;
-  return (base > can ? base : can) + nsun * per;
+  return base == 0 || nt < 1 ? 0 : series_record_bytes(scheme, ncol, nz, nt, base);
 }
 
 size_t crt_hip_levels_series_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nt) {
   // the records of crt_hip_series_workspace_bytes at the same offsets, and nothing behind them: no nb
-  if (!scheme_ok(scheme) || ncol <= 0 || nz <= 0 || nt < 1) return 0;
-  const size_t can = (size_t)ncol * (size_t)can_len(scheme, nz) * sizeof(double);
-  const size_t per = (size_t)sun_len(scheme, nz) * sizeof(double);
-  const size_t nsun = (size_t)ncol * (size_t)nt;
-  if (nsun > (SIZE_MAX - can) / per) return 0;
-  return can + nsun * per;
+  return !scheme_ok(scheme) || ncol <= 0 || nz <= 0 || nt < 1 ? 0 : series_record_bytes(scheme, ncol, nz, nt, 0);
 }
 
 int crt_hip_quad_nodes(double mu_s, double* psi_nodes) {
@@ -216,6 +215,16 @@ struct SolveOpts {
 };
 
 static bool is_tri(int scheme) { return scheme == CRT_SCHEME_N79 || scheme == CRT_SCHEME_ZQ; }
+
+// the level-subset and the integrated launcher of the scheme's kernel family: zq_pa, n79 / zq, the closed forms
+static int launch_family_lev(int scheme, const SolveArgs& sa, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl) {
+  if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_lev(sa, la, s, sr, probe, sl);
+  return is_tri(scheme) ? launch_tridiag_lev(scheme, sa, la, s, sr, probe, sl) : launch_closed_lev(scheme, sa, la, s, sr, probe, sl);
+}
+static int launch_family_int(int scheme, const SolveArgs& sa, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr) {
+  if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_int(sa, ia, s, sr);
+  return is_tri(scheme) ? launch_tridiag_int(scheme, sa, ia, s, sr) : launch_closed_int(scheme, sa, ia, s, sr);
+}
 
 // Every argument check of a solve, in the order that decides which status a call with several faults gets; fills `o`.
 // integ / lev / ser: the integrated outputs, the level subset, the sun-angle series of the call (each NULL when it has none).
@@ -317,58 +326,40 @@ static int dispatch_series(int scheme, ColArgs ca, SolveArgs sa, int flags, cons
   ca.g_at_psi = ser->g_at_psi;
   sa.I_dr0 = sa.I_df0 = nullptr;  // the spectra come from `sr`
   const SeriesArgs sr = {ser->nt, scheme, ca.nz, can_len(scheme, ca.nz), sun_len(scheme, ca.nz), sa.ws, sunrec, ser->col_stride, ser->I_dr0, ser->I_df0};
-  const bool tri = is_tri(scheme);
-  auto lev_series = [&](bool probe) {
-    if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_lev(sa, *lev, s, &sr, probe, sl);
-    return tri ? launch_tridiag_lev(scheme, sa, *lev, s, &sr, probe, sl) : launch_closed_lev(scheme, sa, *lev, s, &sr, probe, sl);
-  };
-  if (lev) {  // every shape the level series cannot serve is found here, before K0 has written anything
-    const int st = lev_series(true);
-    if (st != CRT_OK) return st;
-  }
+  if (lev)  // every shape the level series cannot serve is found here, before K0 has written anything
+    if (const int st = launch_family_lev(scheme, sa, *lev, s, &sr, true, sl)) return st;
   const int st = (flags & CRT_FLAG_SKIP_PRECOMPUTE) ? init_quadrature(s) : launch_colpre_series(ca, ser->nt, sunrec, s);
   if (st != CRT_OK) return st;
   if (flags & CRT_FLAG_PRECOMPUTE_ONLY) {
     note_kernel("k_colpre<canopy> + k_colsun nt=%d", ser->nt);
     return CRT_OK;
   }
-  if (lev) return lev_series(false);
-  if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_int(sa, *integ, s, &sr);
-  return tri ? launch_tridiag_int(scheme, sa, *integ, s, &sr) : launch_closed_int(scheme, sa, *integ, s, &sr);
+  return lev ? launch_family_lev(scheme, sa, *lev, s, &sr, false, sl) : launch_family_int(scheme, sa, *integ, s, &sr);
+}
+
+// The K0 step of a per-step call: k_colpre, unless the caller keeps the records of an earlier call (CRT_FLAG_SKIP_PRECOMPUTE) or the solve
+// kernel forms them itself (k0_in_solve: only the quadrature constants are set up).
+static int k0_step(const ColArgs& ca, int flags, bool k0_in_solve, hipStream_t s) {
+  if (k0_in_solve) return init_quadrature(s);
+  return (flags & CRT_FLAG_SKIP_PRECOMPUTE) ? (int)CRT_OK : launch_colpre(ca, s);
 }
 
 // one sun state per column: K0, then the profile, integrated or level-subset kernel of the scheme
 static int dispatch_step(int scheme, const ColArgs& ca, const SolveArgs& sa, int flags, const IntArgs* integ, const LevArgs* lev, hipStream_t s,
                          SensLaunch* sl) {
-  const bool tri = is_tri(scheme);
-  auto lev_step = [&](bool probe) {
-    if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_lev(sa, *lev, s, nullptr, probe, sl);
-    return tri ? launch_tridiag_lev(scheme, sa, *lev, s, nullptr, probe, sl) : launch_closed_lev(scheme, sa, *lev, s, nullptr, probe, sl);
-  };
-  if (sl) {  // sensor-band outputs: a shape their staging does not fit is found here, before K0 has written anything
-    const int st = lev_step(true);
-    if (st != CRT_OK) return st;
-  }
+  if (sl)  // sensor-band outputs: a shape their staging does not fit is found here, before K0 has written anything
+    if (const int st = launch_family_lev(scheme, sa, *lev, s, nullptr, true, sl)) return st;
   // 2s profiles: the closed-form launcher forms the records inside k_pipe when it picks that kernel (one launch per call), and runs
   // k_colpre in front of any other kernel.  SKIP_PRECOMPUTE / PRECOMPUTE_ONLY and CRT_TUNE_K0_SEPARATE keep k_colpre as a kernel of its own.
   const bool k0_in_solve = scheme == CRT_SCHEME_2S && !integ && !lev && !(flags & (CRT_FLAG_SKIP_PRECOMPUTE | CRT_FLAG_PRECOMPUTE_ONLY)) &&
                            sa.tune.k0_separate == 0;
-  if (k0_in_solve) {
-    const int st = init_quadrature(s);
-    if (st != CRT_OK) return st;
-  } else if (!(flags & CRT_FLAG_SKIP_PRECOMPUTE)) {
-    const int st = launch_colpre(ca, s);
-    if (st != CRT_OK) return st;
-  }
+  if (const int st = k0_step(ca, flags, k0_in_solve, s)) return st;
   if (flags & CRT_FLAG_PRECOMPUTE_ONLY) return CRT_OK;
-  if (integ) {
-    if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa_int(sa, *integ, s);
-    return tri ? launch_tridiag_int(scheme, sa, *integ, s) : launch_closed_int(scheme, sa, *integ, s);
-  }
-  if (lev) return lev_step(false);
+  if (integ) return launch_family_int(scheme, sa, *integ, s, nullptr);
+  if (lev) return launch_family_lev(scheme, sa, *lev, s, nullptr, false, sl);
   if (scheme == CRT_SCHEME_ZQ_PA) return launch_zqpa(sa, ca.ws + (size_t)sa.ncol * sa.reclen, s);
   const int force = (flags & CRT_FLAG_DIRECT_STORES) ? 1 : 0;
-  return tri ? launch_tridiag(scheme, sa, s, force) : launch_closed(scheme, sa, s, force, k0_in_solve ? &ca : nullptr);
+  return is_tri(scheme) ? launch_tridiag(scheme, sa, s, force) : launch_closed(scheme, sa, s, force, k0_in_solve ? &ca : nullptr);
 }
 
 static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts,
@@ -397,35 +388,24 @@ int crt_hip_solve_f32(int scheme, const crt_columns* cols, const crt_bands_f32* 
                     workspace_bytes, stream, 1);
 }
 
-#define CRT_ENTRY(name, id)                                                                                        \
-  int name(const crt_columns* c, const crt_bands* b, const crt_options* o, const crt_outputs* out, void* ws,       \
-           size_t wsb, crt_stream_t s) {                                                                           \
-    return crt_hip_solve_f64(id, c, b, o, out, ws, wsb, s);                                                        \
+#define CRT_ENTRY(tag, id)                                                                                                                    \
+  int crt_hip_##tag##_f64(const crt_columns* c, const crt_bands* b, const crt_options* o, const crt_outputs* out, void* ws, size_t wsb,         \
+                          crt_stream_t s) {                                                                                                     \
+    return crt_hip_solve_f64(id, c, b, o, out, ws, wsb, s);                                                                                     \
+  }                                                                                                                                             \
+  int crt_hip_##tag##_f32(const crt_columns* c, const crt_bands_f32* b, const crt_options* o, const crt_outputs_f32* out, void* ws, size_t wsb, \
+                          crt_stream_t s) {                                                                                                     \
+    return crt_hip_solve_f32(id, c, b, o, out, ws, wsb, s);                                                                                     \
   }
-CRT_ENTRY(crt_hip_2s_f64, CRT_SCHEME_2S)
-CRT_ENTRY(crt_hip_4s_f64, CRT_SCHEME_4S)
-CRT_ENTRY(crt_hip_n79_f64, CRT_SCHEME_N79)
-CRT_ENTRY(crt_hip_zq_f64, CRT_SCHEME_ZQ)
-CRT_ENTRY(crt_hip_bl_f64, CRT_SCHEME_BL)
-CRT_ENTRY(crt_hip_g77_f64, CRT_SCHEME_G77)
-CRT_ENTRY(crt_hip_bf_f64, CRT_SCHEME_BF)
-CRT_ENTRY(crt_hip_zq_pa_f64, CRT_SCHEME_ZQ_PA)
+CRT_ENTRY(2s, CRT_SCHEME_2S)
+CRT_ENTRY(4s, CRT_SCHEME_4S)
+CRT_ENTRY(n79, CRT_SCHEME_N79)
+CRT_ENTRY(zq, CRT_SCHEME_ZQ)
+CRT_ENTRY(bl, CRT_SCHEME_BL)
+CRT_ENTRY(g77, CRT_SCHEME_G77)
+CRT_ENTRY(bf, CRT_SCHEME_BF)
+CRT_ENTRY(zq_pa, CRT_SCHEME_ZQ_PA)
 #undef CRT_ENTRY
-
-#define CRT_ENTRY32(name, id)                                                                                      \
-  int name(const crt_columns* c, const crt_bands_f32* b, const crt_options* o, const crt_outputs_f32* out, void* ws, \
-           size_t wsb, crt_stream_t s) {                                                                           \
-    return crt_hip_solve_f32(id, c, b, o, out, ws, wsb, s);                                                        \
-  }
-CRT_ENTRY32(crt_hip_2s_f32, CRT_SCHEME_2S)
-CRT_ENTRY32(crt_hip_4s_f32, CRT_SCHEME_4S)
-CRT_ENTRY32(crt_hip_n79_f32, CRT_SCHEME_N79)
-CRT_ENTRY32(crt_hip_zq_f32, CRT_SCHEME_ZQ)
-CRT_ENTRY32(crt_hip_bl_f32, CRT_SCHEME_BL)
-CRT_ENTRY32(crt_hip_g77_f32, CRT_SCHEME_G77)
-CRT_ENTRY32(crt_hip_bf_f32, CRT_SCHEME_BF)
-CRT_ENTRY32(crt_hip_zq_pa_f32, CRT_SCHEME_ZQ_PA)
-#undef CRT_ENTRY32
 
 int crt_hip_absorb_bandsum2_f64(const crt_columns* cols, const crt_bands* bands, const double* I_dr, const double* I_df_d,
                                 const double* I_df_u, const double* band_w, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream) {
@@ -513,13 +493,23 @@ int crt_hip_integrated_f32(int scheme, const crt_columns* cols, const crt_bands_
   return crt_hip_integrated2_f32(scheme, cols, bands, opts, band_w, ngroup, &o, workspace, workspace_bytes, stream);
 }
 
+// the level list of a call into la.nsel / la.lev: 1 .. CRT_MAX_LEVEL_SELECT levels of the column, strictly ascending (no duplicates)
+static int parse_levels(const crt_columns* cols, const int32_t* levels, int32_t nsel, LevArgs& la) {
+  if (nsel < 1 || nsel > CRT_MAX_LEVEL_SELECT) return CRT_ERR_BAD_ARG;
+  la.nsel = nsel;
+  for (int r = 0; r < nsel; ++r) {
+    if (levels[r] < 0 || levels[r] >= cols->nz || (r > 0 && levels[r] <= levels[r - 1])) return CRT_ERR_BAD_ARG;
+    la.lev[r] = levels[r];
+  }
+  return CRT_OK;
+}
+
 // f32: crt_bands_f32 / crt_outputs_f32 have the layouts of crt_bands / crt_outputs (crt_hip_solve_f32).  Every argument error is found here
 // or in solve_impl's checks, before any launch.
 static int levels_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
                        int32_t nsel, const crt_outputs* out, void* workspace, size_t workspace_bytes, crt_stream_t stream, int f32,
                        const crt_sun_series* ser = nullptr, SensLaunch* sl = nullptr, size_t extra_ws = 0) {
   if (!scheme_ok(scheme) || !cols || !levels || !out) return CRT_ERR_BAD_ARG;
-  if (nsel < 1 || nsel > CRT_MAX_LEVEL_SELECT) return CRT_ERR_BAD_ARG;
   if (out->x0 || out->x1 || out->x2) return CRT_ERR_BAD_ARG;
   if (!sl && !out->I_dr && !out->I_df_d && !out->I_df_u && !out->F) return CRT_ERR_BAD_ARG;  // (a sensor call has its outputs in sl)
   LevArgs la = {};
@@ -527,12 +517,7 @@ static int levels_impl(int scheme, const crt_columns* cols, const crt_bands* ban
   la.o[1] = out->I_df_d;
   la.o[2] = out->I_df_u;
   la.o[3] = out->F;
-  la.nsel = nsel;
-  for (int r = 0; r < nsel; ++r) {
-    if (levels[r] < 0 || levels[r] >= cols->nz) return CRT_ERR_BAD_ARG;
-    if (r > 0 && levels[r] <= levels[r - 1]) return CRT_ERR_BAD_ARG;  // strictly ascending: no duplicates
-    la.lev[r] = levels[r];
-  }
+  if (const int st = parse_levels(cols, levels, nsel, la)) return st;
   crt_outputs none = {};
   return solve_impl(scheme, cols, bands, opts, &none, workspace, workspace_bytes, stream, f32, nullptr, &la, ser, sl, extra_ws);
 }
@@ -585,10 +570,7 @@ static size_t sens_partial_bytes(int scheme, int32_t ncol, int32_t nz, int32_t n
   LevArgs la = {};
   la.nsel = nsel;
   SensLaunch sl = {};
-  const int st = scheme == CRT_SCHEME_ZQ_PA ? launch_zqpa_lev(sa, la, nullptr, nullptr, true, &sl)
-                 : is_tri(scheme)           ? launch_tridiag_lev(scheme, sa, la, nullptr, nullptr, true, &sl)
-                                            : launch_closed_lev(scheme, sa, la, nullptr, nullptr, true, &sl);
-  if (st != CRT_OK || sl.nslice <= 1) return 0;
+  if (launch_family_lev(scheme, sa, la, nullptr, nullptr, true, &sl) != CRT_OK || sl.nslice <= 1) return 0;
   const size_t per = (size_t)sl.nslice * (size_t)nsel * 4 * (size_t)nsens * sizeof(double);
   const size_t nv = (size_t)ncol * (size_t)nt;
   return nv > SIZE_MAX / per ? 0 : nv * per;
@@ -674,15 +656,9 @@ size_t crt_hip_levels_jac_workspace_bytes(int scheme, int32_t ncol, int32_t nz, 
 int crt_hip_levels_jac_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
                            int32_t nsel, const crt_jac_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream) {
   if (!scheme_ok(scheme) || !cols || !levels || !out) return CRT_ERR_BAD_ARG;
-  if (nsel < 1 || nsel > CRT_MAX_LEVEL_SELECT) return CRT_ERR_BAD_ARG;
   if (!out->I_df_d && !out->I_df_u && !out->F) return CRT_ERR_BAD_ARG;
   LevArgs la = {};
-  la.nsel = nsel;
-  for (int r = 0; r < nsel; ++r) {
-    if (levels[r] < 0 || levels[r] >= cols->nz) return CRT_ERR_BAD_ARG;
-    if (r > 0 && levels[r] <= levels[r - 1]) return CRT_ERR_BAD_ARG;  // strictly ascending: no duplicates
-    la.lev[r] = levels[r];
-  }
+  if (const int st = parse_levels(cols, levels, nsel, la)) return st;
   SolveOpts o;
   const crt_outputs none = {};
   const int chk = check_solve(scheme, cols, bands, opts, &none, workspace, workspace_bytes, nullptr, &la, nullptr, o);
@@ -695,8 +671,7 @@ int crt_hip_levels_jac_f64(int scheme, const crt_columns* cols, const crt_bands*
   const JacArgs jo = {{out->I_df_d, out->I_df_u, out->F}};
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (const int st = launch_jac(scheme, sa, la, jo, s, true)) return st;  // a shape that is not served: before K0 has written anything
-  if (!(o.flags & CRT_FLAG_SKIP_PRECOMPUTE))
-    if (const int st = launch_colpre(ca, s)) return st;
+  if (const int st = k0_step(ca, o.flags, false, s)) return st;
   if (o.flags & CRT_FLAG_PRECOMPUTE_ONLY) return CRT_OK;
   return launch_jac(scheme, sa, la, jo, s, false);
 }

@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "epilogue.hpp"
+#include "launch_forms.hpp"
 
 namespace crt {
 namespace {
@@ -923,9 +924,7 @@ int launch_band_slice(const EpiArgsT<TIO>& a, int b0, int nbs, int nthr, hipStre
   const int nwave = nthr / 64;
   const size_t sh = ((size_t)2 * BS_CH * nwave * (PROF ? 5 : 2) * MAXG + (size_t)nwave * (4 + (PROF ? 3 : 0)) * MAXG) * sizeof(double);
   const dim3 grid(a.ncol);
-  if (nthr <= 256) return launch_kernel(k_absorb_bandsum<TIO, 256, PROF>, grid, nthr, sh, s, a, b0, nbs, (int)(b0 > 0));
-  if (nthr <= 512) return launch_kernel(k_absorb_bandsum<TIO, 512, PROF>, grid, nthr, sh, s, a, b0, nbs, (int)(b0 > 0));
-  return launch_kernel(k_absorb_bandsum<TIO, 1024, PROF>, grid, nthr, sh, s, a, b0, nbs, (int)(b0 > 0));
+  return with_bound(nthr, [&](auto B) { return launch_kernel(k_absorb_bandsum<TIO, B(), PROF>, grid, nthr, sh, s, a, b0, nbs, (int)(b0 > 0)); });
 }
 
 }  // namespace

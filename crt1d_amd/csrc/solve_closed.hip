@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "col_record.hpp"
+#include "launch_forms.hpp"
 
 namespace crt {
 namespace {
@@ -1057,14 +1058,14 @@ int launch_tile(const SolveArgs& a, hipStream_t s, bool& done, const ColArgs* k0
                     own_k0 ? " k0=fused" : "");  // (only a launch that succeeded is reported)
         return (int)CRT_OK;
       };
+      // (prologue and flush outside, the launch bound inside: the kernels are instantiated in this order, their order in the code object)
       int st;
-      if (own_k0) {
-        if (fused) st = pthr <= 512 ? gop(k_pipe<S, TIO, 512, true, can_k0>) : gop(k_pipe<S, TIO, 1024, true, can_k0>);
-        else st = pthr <= 512 ? gop(k_pipe<S, TIO, 512, false, can_k0>) : gop(k_pipe<S, TIO, 1024, false, can_k0>);
-      } else {
-        if (fused) st = pthr <= 512 ? gop(k_pipe<S, TIO, 512, true>) : gop(k_pipe<S, TIO, 1024, true>);
-        else st = pthr <= 512 ? gop(k_pipe<S, TIO, 512, false>) : gop(k_pipe<S, TIO, 1024, false>);
-      }
+      if (own_k0)
+        st = fused ? with_pipe_bound(pthr, [&](auto B) { return gop(k_pipe<S, TIO, B(), true, can_k0>); })
+                   : with_pipe_bound(pthr, [&](auto B) { return gop(k_pipe<S, TIO, B(), false, can_k0>); });
+      else
+        st = fused ? with_pipe_bound(pthr, [&](auto B) { return gop(k_pipe<S, TIO, B(), true>); })
+                   : with_pipe_bound(pthr, [&](auto B) { return gop(k_pipe<S, TIO, B(), false>); });
       done = st == CRT_OK;
       return st;
     }
@@ -1075,16 +1076,8 @@ int launch_tile(const SolveArgs& a, hipStream_t s, bool& done, const ColArgs* k0
     note_kernel("k_tile<%s,%s>%s CB=%d T=%d lds=%zu", S::NAME, sizeof(TIO) == 8 ? "f64" : "f32", fused ? "" : " generic-flush", CB, T, sh);  // (only a launch that succeeded is reported)
     return (int)CRT_OK;
   };
-  int st;
-  if (fused) {
-    if (nthr <= 256) st = go(k_tile<S, TIO, 256, true>);
-    else if (nthr <= 512) st = go(k_tile<S, TIO, 512, true>);
-    else st = go(k_tile<S, TIO, 1024, true>);
-  } else {
-    if (nthr <= 256) st = go(k_tile<S, TIO, 256, false>);
-    else if (nthr <= 512) st = go(k_tile<S, TIO, 512, false>);
-    else st = go(k_tile<S, TIO, 1024, false>);
-  }
+  const int st = fused ? with_bound(nthr, [&](auto B) { return go(k_tile<S, TIO, B(), true>); })
+                       : with_bound(nthr, [&](auto B) { return go(k_tile<S, TIO, B(), false>); });
   done = st == CRT_OK;
   return st;
 }
@@ -1181,41 +1174,34 @@ __global__ __launch_bounds__(MAXT) void k_int_series(SolveArgs a, IntArgs ia, Se
   series_step(a, ia, sr, lds, [&](const SolveArgs& at, const IntArgs& it) { int_body<S, double, PROF>(at, it, rec_dbl, lds); });
 }
 
+// the closed family's description of the integrated launch (launch_int_form, launch_forms.hpp): LDS = record | partial sums
+template <class S, typename TIO>
+struct ClosedInt {
+  const SolveArgs& a;
+  int rec_dbl() const { return (a.reclen + 1) & ~1; }
+  // wave totals of all band groups with one wave_sum4 per level (round 2; per-row partials and __shfl_xor butterflies before that:
+  // 2s 1e4 x 300 x 60 0.80 / 0.625 / 1.59 ms)
+  size_t lds_bytes(int nthr, bool prof) const { return (rec_dbl() + int_lds_doubles(a.nz, nthr / 64, false, prof)) * sizeof(double); }
+  template <int MAXT, bool SER, bool PROF>
+  int launch(const IntLaunch& L) const {
+    if constexpr (SER)
+      return launch_kernel(k_int_series<S, MAXT, PROF>, L.grid, L.nthr, L.sh, L.s, a, L.ia, *L.sr, rec_dbl());
+    else
+      return launch_kernel(k_int<S, TIO, MAXT, PROF>, L.grid, L.nthr, L.sh, L.s, a, L.ia, rec_dbl());
+  }
+  void note(const IntLaunch& L) const {
+    const char* sums = L.prof ? " + level profiles" : " wave totals";
+    if (L.sr)
+      note_kernel("k_colpre<canopy> + k_colsun + k_int_series<%s>%s nt=%d", S::NAME, sums, L.sr->nt);
+    else
+      note_kernel("k_int<%s>%s%s", S::NAME, sizeof(TIO) == 8 ? "" : " f32", sums);
+  }
+};
+
 template <class S, typename TIO>
 int launch_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr) {
   if (a.nb > 1024) return CRT_ERR_UNSUPPORTED;
-  const int nthr = ((a.nb + 63) / 64) * 64;
-  const int rec_dbl = (a.reclen + 1) & ~1;
-  // wave totals of all band groups with one wave_sum4 per level (round 2; per-row partials and __shfl_xor butterflies before that:
-  // 2s 1e4 x 300 x 60 0.80 / 0.625 / 1.59 ms)
-  const bool prof = ia.L_dr != nullptr;
-  const size_t sh = (rec_dbl + int_lds_doubles(a.nz, nthr / 64, false, prof)) * sizeof(double);
-  if (sh > 160 * 1024) return CRT_ERR_UNSUPPORTED;
-  if (sr) {
-    if constexpr (sizeof(TIO) == 8) {
-      auto gos = [&](auto kern) {
-        const int st = launch_kernel(kern, series_grid(a.ncol, sr->nt), nthr, sh, s, a, ia, *sr, rec_dbl);
-        if (st == CRT_OK) note_kernel("k_colpre<canopy> + k_colsun + k_int_series<%s>%s nt=%d", S::NAME, prof ? " + level profiles" : " wave totals", sr->nt);
-        return st;
-      };
-      if (prof) return nthr <= 256 ? gos(k_int_series<S, 256, true>) : nthr <= 512 ? gos(k_int_series<S, 512, true>) : gos(k_int_series<S, 1024, true>);
-      return nthr <= 256 ? gos(k_int_series<S, 256, false>) : nthr <= 512 ? gos(k_int_series<S, 512, false>) : gos(k_int_series<S, 1024, false>);
-    }
-    return CRT_ERR_UNSUPPORTED;  // no f32 form of the series
-  }
-  auto go = [&](auto kern) {
-    if (const int st = launch_kernel(kern, dim3(a.ncol), nthr, sh, s, a, ia, rec_dbl)) return st;
-    note_kernel("k_int<%s>%s%s", S::NAME, sizeof(TIO) == 8 ? "" : " f32", prof ? " + level profiles" : " wave totals");  // (only a launch that succeeded is reported)
-    return (int)CRT_OK;
-  };
-  if (prof) {
-    if (nthr <= 256) return go(k_int<S, TIO, 256, true>);
-    if (nthr <= 512) return go(k_int<S, TIO, 512, true>);
-    return go(k_int<S, TIO, 1024, true>);
-  }
-  if (nthr <= 256) return go(k_int<S, TIO, 256, false>);
-  if (nthr <= 512) return go(k_int<S, TIO, 512, false>);
-  return go(k_int<S, TIO, 1024, false>);
+  return launch_int_form<TIO>(ClosedInt<S, TIO>{a}, a, ia, s, ((a.nb + 63) / 64) * 64, sr);
 }
 
 template <class S>
@@ -1306,76 +1292,35 @@ __global__ __launch_bounds__(MAXT) void k_lev_sens_series(SolveArgs a, LevArgs l
   });
 }
 
+// the closed family's description of the level launch (launch_lev_form, launch_forms.hpp).  The record is all the LDS a workgroup needs
+// (the sensor forms add one staging row behind it, at off_st): no narrowing of the slices.  Deeper columns read their record from the
+// workspace (every nz the profile path serves): the per-step form only.
 template <class S, typename TIO>
-int launch_lev_sens(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl) {
-  const LevSlices ls = lev_slices(a.nb, 1024);  // (no narrowing: the record and one staging row are all the LDS)
-  if (ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
-  const int off_st = (a.reclen + 1) & ~1;
-  const size_t sh = ((size_t)off_st + (size_t)SENS_STAGE * ls.nthr) * sizeof(double);
-  if (sh > 160 * 1024) return CRT_ERR_UNSUPPORTED;  // record and staging row in LDS
-  const long long nv = (long long)a.ncol * (sr ? sr->nt : 1);
-  dim3 grid(a.ncol, ls.nslice);
-  if (sr && (sizeof(TIO) != 8 || !lev_series_grid(a.ncol, sr->nt, ls.nslice, &grid))) return CRT_ERR_UNSUPPORTED;
-  int st = sens_probe(sl, ls, nv, la.nsel);
-  if (probe || st != CRT_OK) return st;
-  if (sr) {
-    if constexpr (sizeof(TIO) == 8) {
-      auto gos = [&](auto kern) { return launch_kernel(kern, grid, ls.nthr, sh, s, a, la, sl->sn, *sr, ls.per, off_st, ls.nslice); };
-      st = ls.nthr <= 256 ? gos(k_lev_sens_series<S, 256>) : ls.nthr <= 512 ? gos(k_lev_sens_series<S, 512>) : gos(k_lev_sens_series<S, 1024>);
-    } else {
-      return CRT_ERR_UNSUPPORTED;
-    }
-  } else {
-    auto go = [&](auto kern) { return launch_kernel(kern, grid, ls.nthr, sh, s, a, la, sl->sn, ls.per, off_st); };
-    st = ls.nthr <= 256 ? go(k_lev_sens<S, TIO, 256>) : ls.nthr <= 512 ? go(k_lev_sens<S, TIO, 512>) : go(k_lev_sens<S, TIO, 1024>);
+struct ClosedLev {
+  static constexpr bool FIT = false, HBM_RECORD = true;
+  const SolveArgs& a;
+  int off_st() const { return (a.reclen + 1) & ~1; }
+  size_t lds_bytes(int nthr, bool sens) const {
+    return sens ? ((size_t)off_st() + (size_t)SENS_STAGE * nthr) * sizeof(double) : (size_t)a.reclen * sizeof(double);
   }
-  if (st != CRT_OK || (st = sens_finish(sl, ls, nv, a.nb, la.nsel, s)) != CRT_OK) return st;
-  note_kernel("%sk_lev_sens%s<%s>%s nsel=%d nsens=%d slice=%d%s", sr ? "k_colpre<canopy> + k_colsun + " : "", sr ? "_series" : "", S::NAME,
-              sizeof(TIO) == 8 ? "" : " f32", la.nsel, sl->sn.nsens, ls.per, ls.nslice > 1 ? " + k_sens_finish" : "");
-  return CRT_OK;
-}
-
-template <class S, typename TIO>
-int launch_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl) {
-  if (sl) return launch_lev_sens<S, TIO>(a, la, s, sr, probe, sl);
-  const LevSlices ls = lev_slices(a.nb, 1024);  // the record is all the LDS a workgroup needs
-  if (ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
-  const size_t sh = (size_t)a.reclen * sizeof(double);
-  const bool use_lds = sh <= 160 * 1024;  // deeper columns read their record from the workspace (every nz the profile path serves)
-  if (sr) {  // the series has no assembled record in the workspace: LDS only
-    dim3 grid;
-    if (!use_lds || !lev_series_grid(a.ncol, sr->nt, ls.nslice, &grid)) return CRT_ERR_UNSUPPORTED;
-    if (probe) return CRT_OK;
-    auto gos = [&](auto kern) {
-      const int st = launch_kernel(kern, grid, ls.nthr, sh, s, a, la, *sr, ls.per, ls.nslice);
-      if (st == CRT_OK)
-        note_kernel("k_colpre<canopy> + k_colsun + k_lev_series<%s>%s nsel=%d slice=%d nt=%d", S::NAME, sizeof(TIO) == 8 ? "" : " f32", la.nsel,
-                    ls.per, sr->nt);
-      return st;
-    };
-    return ls.nthr <= 256 ? gos(k_lev_series<S, TIO, 256>) : ls.nthr <= 512 ? gos(k_lev_series<S, TIO, 512>) : gos(k_lev_series<S, TIO, 1024>);
+  template <int MAXT, bool SER, bool SENS, bool IN_LDS>
+  int launch(const LevLaunch& L) const {
+    const LevSlices& ls = L.ls;
+    if constexpr (SER && SENS)
+      return launch_kernel(k_lev_sens_series<S, MAXT>, L.grid, ls.nthr, L.sh, L.s, a, L.la, L.sl->sn, *L.sr, ls.per, off_st(), ls.nslice);
+    else if constexpr (SENS)
+      return launch_kernel(k_lev_sens<S, TIO, MAXT>, L.grid, ls.nthr, L.sh, L.s, a, L.la, L.sl->sn, ls.per, off_st());
+    else if constexpr (SER)
+      return launch_kernel(k_lev_series<S, TIO, MAXT>, L.grid, ls.nthr, L.sh, L.s, a, L.la, *L.sr, ls.per, ls.nslice);
+    else
+      return launch_kernel(k_lev<S, TIO, MAXT, IN_LDS>, L.grid, ls.nthr, IN_LDS ? L.sh : 0, L.s, a, L.la, ls.per);
   }
-  if (probe) return CRT_OK;
-  auto go = [&](auto kern) {
-    const size_t shk = use_lds ? sh : 0;
-    if (const int st = launch_kernel(kern, dim3(a.ncol, ls.nslice), ls.nthr, shk, s, a, la, ls.per)) return st;
-    note_kernel("k_lev<%s>%s nsel=%d slice=%d%s", S::NAME, sizeof(TIO) == 8 ? "" : " f32", la.nsel, ls.per,
-                use_lds ? "" : " record in HBM");  // (only a launch that succeeded is reported)
-    return (int)CRT_OK;
-  };
-  if (!use_lds) {
-    if (ls.nthr <= 256) return go(k_lev<S, TIO, 256, false>);
-    if (ls.nthr <= 512) return go(k_lev<S, TIO, 512, false>);
-    return go(k_lev<S, TIO, 1024, false>);
-  }
-  if (ls.nthr <= 256) return go(k_lev<S, TIO, 256, true>);
-  if (ls.nthr <= 512) return go(k_lev<S, TIO, 512, true>);
-  return go(k_lev<S, TIO, 1024, true>);
-}
+  void note(const LevLaunch& L) const { lev_note(L, "k_lev", S::NAME, sizeof(TIO) == 4, ""); }
+};
 
 template <class S>
 int launch_lev_io(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl) {
-  return a.f32 ? launch_lev<S, float>(a, la, s, sr, probe, sl) : launch_lev<S, double>(a, la, s, sr, probe, sl);
+  return a.f32 ? launch_lev_form<float>(ClosedLev<S, float>{a}, a, la, s, sr, probe, sl) : launch_lev_form<double>(ClosedLev<S, double>{a}, a, la, s, sr, probe, sl);
 }
 
 }  // namespace

@@ -23,13 +23,11 @@
 // = 69 KB -> two workgroups (10 waves) per CU.
 #include <type_traits>
 
-#include "crt_internal.hpp"
+#include "launch_forms.hpp"
 #include "tri_schemes.hpp"
 
 namespace crt {
 namespace {
-
-constexpr size_t MAX_WG_LDS = 160 * 1024;
 
 struct TriCfg {
   int T;        // levels per flush tile (divides M)
@@ -483,9 +481,7 @@ int launch_mt(const SolveArgs& a, hipStream_t s, int nthr) {
   cfg.flat = (!FUSED && a.tune.flat_flush != CRT_FLAT_FLUSH_OFF) ? flat_flush_ok<S, TIO>(a) : 0;
   const size_t sh = ((size_t)cfg.off_tile + (size_t)S::NST * T * a.nb) * sizeof(double);
   if (sh > MAX_WG_LDS) return CRT_ERR_UNSUPPORTED;
-  auto kern = k_tri_tile<S, TIO, M, T, 256, FUSED>;  // (instantiated in this order: the order of the kernels in the code object)
-  if (nthr > 256) kern = k_tri_tile<S, TIO, M, T, 512, FUSED>;
-  if (nthr > 512) kern = k_tri_tile<S, TIO, M, T, 1024, FUSED>;
+  const auto kern = with_bound(nthr, [](auto B) { return k_tri_tile<S, TIO, M, T, B(), FUSED>; });  // (instantiated in this order: the order of the kernels in the code object)
   if (const int st = launch_kernel(kern, dim3(a.ncol), nthr, sh, s, a, cfg)) return st;
   note_kernel("k_tri_tile<%s,%s>%s M=%d T=%d lds=%zu", S::NAME, sizeof(TIO) == 8 ? "f64" : "f32", FUSED ? "" : cfg.flat ? " flat-flush" : " generic-flush", M, T, sh);  // (only a launch that succeeded is reported)
   return CRT_OK;
@@ -605,49 +601,35 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(M <= 8 ? 5
   });
 }
 
+// the n79 / zq description of the integrated launch (launch_int_form, launch_forms.hpp): LDS = record | checkpoints [nck][2][nthr] | partial sums
 template <class S, typename TIO, int M>
-int launch_int_m(const SolveArgs& a, const IntArgs& ia, hipStream_t s, int nthr, const SeriesArgs* sr) {
-  const int K = S::rows(a.nz);
-  const int nck = (K - 1) / M + 1;
-  const int off_ck = (a.reclen + 1) & ~1;
-  const int off_int = off_ck + 2 * nck * nthr;
-  const bool prof = ia.L_dr != nullptr;
-  const size_t sh = ((size_t)off_int + int_lds_doubles(a.nz, nthr / 64, false, prof)) * sizeof(double);
-  if (sh > MAX_WG_LDS) return CRT_ERR_UNSUPPORTED;
-  auto go = [&](auto kern) {
-    if (const int st = launch_kernel(kern, dim3(a.ncol), nthr, sh, s, a, ia, off_ck, off_int)) return st;
-    note_kernel("k_tri_int<%s>%s M=%d%s", S::NAME, sizeof(TIO) == 8 ? "" : " f32", M, prof ? " + level profiles" : "");  // (only a launch that succeeded is reported)
-    return (int)CRT_OK;
-  };
-  if (sr) {
-    if constexpr (sizeof(TIO) == 8) {
-      auto gos = [&](auto kern) {
-        const int st = launch_kernel(kern, series_grid(a.ncol, sr->nt), nthr, sh, s, a, ia, *sr, off_ck, off_int);
-        if (st == CRT_OK) note_kernel("k_colpre<canopy> + k_colsun + k_tri_int_series<%s> M=%d%s nt=%d", S::NAME, M, prof ? " + level profiles" : "", sr->nt);
-        return st;
-      };
-      if (prof) return nthr <= 256 ? gos(k_tri_int_series<S, M, 256, true>) : nthr <= 512 ? gos(k_tri_int_series<S, M, 512, true>) : gos(k_tri_int_series<S, M, 1024, true>);
-      return nthr <= 256 ? gos(k_tri_int_series<S, M, 256, false>) : nthr <= 512 ? gos(k_tri_int_series<S, M, 512, false>) : gos(k_tri_int_series<S, M, 1024, false>);
-    }
-    return CRT_ERR_UNSUPPORTED;  // no f32 form of the series
+struct TriInt {
+  const SolveArgs& a;
+  int off_ck() const { return (a.reclen + 1) & ~1; }
+  int off_int(int nthr) const { return off_ck() + 2 * ((S::rows(a.nz) - 1) / M + 1) * nthr; }
+  size_t lds_bytes(int nthr, bool prof) const { return ((size_t)off_int(nthr) + int_lds_doubles(a.nz, nthr / 64, false, prof)) * sizeof(double); }
+  template <int MAXT, bool SER, bool PROF>
+  int launch(const IntLaunch& L) const {
+    if constexpr (SER)
+      return launch_kernel(k_tri_int_series<S, M, MAXT, PROF>, L.grid, L.nthr, L.sh, L.s, a, L.ia, *L.sr, off_ck(), off_int(L.nthr));
+    else
+      return launch_kernel(k_tri_int<S, TIO, M, MAXT, PROF>, L.grid, L.nthr, L.sh, L.s, a, L.ia, off_ck(), off_int(L.nthr));
   }
-  if (prof) {
-    if (nthr <= 256) return go(k_tri_int<S, TIO, M, 256, true>);
-    if (nthr <= 512) return go(k_tri_int<S, TIO, M, 512, true>);
-    return go(k_tri_int<S, TIO, M, 1024, true>);
+  void note(const IntLaunch& L) const {
+    const char* prof = L.prof ? " + level profiles" : "";
+    if (L.sr)
+      note_kernel("k_colpre<canopy> + k_colsun + k_tri_int_series<%s> M=%d%s nt=%d", S::NAME, M, prof, L.sr->nt);
+    else
+      note_kernel("k_tri_int<%s>%s M=%d%s", S::NAME, sizeof(TIO) == 8 ? "" : " f32", M, prof);
   }
-  if (nthr <= 256) return go(k_tri_int<S, TIO, M, 256, false>);
-  if (nthr <= 512) return go(k_tri_int<S, TIO, M, 512, false>);
-  return go(k_tri_int<S, TIO, M, 1024, false>);
-}
+};
 
 template <class S, typename TIO>
 int launch_int_scheme(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr) {
   if (a.nb > 1024) return CRT_ERR_UNSUPPORTED;
   const int nthr = ((a.nb + 63) / 64) * 64;
-  int st = launch_int_m<S, TIO, 8>(a, ia, s, nthr, sr);  // small M: fewer registers, LDS is not the constraint here
-  if (st == CRT_ERR_UNSUPPORTED) st = launch_int_m<S, TIO, 16>(a, ia, s, nthr, sr);
-  return st;
+  return first_supported([&] { return launch_int_form<TIO>(TriInt<S, TIO, 8>{a}, a, ia, s, nthr, sr); },  // small M: fewer registers, LDS is not the constraint here
+                         [&] { return launch_int_form<TIO>(TriInt<S, TIO, 16>{a}, a, ia, s, nthr, sr); });
 }
 
 // instantiated (M, T) pairs
@@ -814,91 +796,40 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(M <= 8 ? 5
   });
 }
 
-// LDS of k_tri_lev in bytes: record | checkpoints [nck][2][nthr]
-template <class S>
-inline size_t tri_lev_lds_bytes(const SolveArgs& a, int M, int nthr, int* off_ck = nullptr) {
-  const int K = S::rows(a.nz);
-  const int nck = (K - 1) / M + 1;
-  const int ock = (a.reclen + 1) & ~1;
-  if (off_ck) *off_ck = ock;
-  return ((size_t)ock + 2 * (size_t)nck * nthr) * sizeof(double);
-}
-
-// the sensor-band form: the staging row [4][nthr] behind the checkpoints, slices narrowed until both fit
+// the n79 / zq description of the level launch (launch_lev_form, launch_forms.hpp): LDS = record | checkpoints [nck][2][nthr] at off_ck
+// (| the sensor forms' staging row [4][nthr] at off_st), the band slices narrowed until everything fits
 template <class S, typename TIO, int M>
-int launch_lev_sens_m(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl) {
-  auto bytes = [&](int nthr) { return tri_lev_lds_bytes<S>(a, M, nthr) + (size_t)SENS_STAGE * nthr * sizeof(double); };
-  const LevSlices ls = lev_slices_fit(a.nb, MAX_WG_LDS, bytes);
-  if (ls.nslice == 0 || ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
-  int off_ck;
-  const int off_st = (int)(tri_lev_lds_bytes<S>(a, M, ls.nthr, &off_ck) / sizeof(double));
-  const size_t sh = bytes(ls.nthr);
-  const long long nv = (long long)a.ncol * (sr ? sr->nt : 1);
-  dim3 grid(a.ncol, ls.nslice);
-  if (sr && (sizeof(TIO) != 8 || !lev_series_grid(a.ncol, sr->nt, ls.nslice, &grid))) return CRT_ERR_UNSUPPORTED;
-  int st = sens_probe(sl, ls, nv, la.nsel);
-  if (probe || st != CRT_OK) return st;
-  if (sr) {
-    if constexpr (sizeof(TIO) == 8) {
-      auto gos = [&](auto kern) { return launch_kernel(kern, grid, ls.nthr, sh, s, a, la, sl->sn, *sr, ls.per, off_ck, off_st, ls.nslice); };
-      st = ls.nthr <= 256   ? gos(k_tri_lev_sens_series<S, M, 256>)
-           : ls.nthr <= 512 ? gos(k_tri_lev_sens_series<S, M, 512>)
-                            : gos(k_tri_lev_sens_series<S, M, 1024>);
-    } else {
-      return CRT_ERR_UNSUPPORTED;
-    }
-  } else {
-    auto go = [&](auto kern) { return launch_kernel(kern, grid, ls.nthr, sh, s, a, la, sl->sn, ls.per, off_ck, off_st); };
-    st = ls.nthr <= 256 ? go(k_tri_lev_sens<S, TIO, M, 256>) : ls.nthr <= 512 ? go(k_tri_lev_sens<S, TIO, M, 512>) : go(k_tri_lev_sens<S, TIO, M, 1024>);
+struct TriLev {
+  static constexpr bool FIT = true, HBM_RECORD = false;
+  const SolveArgs& a;
+  int off_ck() const { return (a.reclen + 1) & ~1; }
+  size_t ck_end(int nthr) const { return (size_t)off_ck() + 2 * (size_t)((S::rows(a.nz) - 1) / M + 1) * nthr; }  // doubles (beyond int for absurd nz)
+  size_t lds_bytes(int nthr, bool sens) const { return (ck_end(nthr) + (sens ? (size_t)SENS_STAGE * nthr : 0)) * sizeof(double); }
+  template <int MAXT, bool SER, bool SENS, bool>
+  int launch(const LevLaunch& L) const {
+    const LevSlices& ls = L.ls;
+    const int ock = off_ck(), ost = (int)ck_end(ls.nthr);  // (fits: lds_bytes does)
+    if constexpr (SER && SENS)
+      return launch_kernel(k_tri_lev_sens_series<S, M, MAXT>, L.grid, ls.nthr, L.sh, L.s, a, L.la, L.sl->sn, *L.sr, ls.per, ock, ost, ls.nslice);
+    else if constexpr (SENS)
+      return launch_kernel(k_tri_lev_sens<S, TIO, M, MAXT>, L.grid, ls.nthr, L.sh, L.s, a, L.la, L.sl->sn, ls.per, ock, ost);
+    else if constexpr (SER)
+      return launch_kernel(k_tri_lev_series<S, TIO, M, MAXT>, L.grid, ls.nthr, L.sh, L.s, a, L.la, *L.sr, ls.per, ock, ls.nslice);
+    else
+      return launch_kernel(k_tri_lev<S, TIO, M, MAXT>, L.grid, ls.nthr, L.sh, L.s, a, L.la, ls.per, ock);
   }
-  if (st != CRT_OK || (st = sens_finish(sl, ls, nv, a.nb, la.nsel, s)) != CRT_OK) return st;
-  note_kernel("%sk_tri_lev_sens%s<%s>%s M=%d nsel=%d nsens=%d slice=%d%s", sr ? "k_colpre<canopy> + k_colsun + " : "", sr ? "_series" : "", S::NAME,
-              sizeof(TIO) == 8 ? "" : " f32", M, la.nsel, sl->sn.nsens, ls.per, ls.nslice > 1 ? " + k_sens_finish" : "");
-  return CRT_OK;
-}
-
-template <class S, typename TIO, int M>
-int launch_lev_m(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
-  const LevSlices ls = lev_slices_fit(a.nb, MAX_WG_LDS, [&](int nthr) { return tri_lev_lds_bytes<S>(a, M, nthr); });  // widest slice whose checkpoints fit
-  if (ls.nslice == 0 || ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
-  int off_ck;
-  const size_t sh = tri_lev_lds_bytes<S>(a, M, ls.nthr, &off_ck);
-  if (sr) {
-    dim3 grid;
-    if (!lev_series_grid(a.ncol, sr->nt, ls.nslice, &grid)) return CRT_ERR_UNSUPPORTED;
-    if (probe) return CRT_OK;
-    auto gos = [&](auto kern) {
-      const int st = launch_kernel(kern, grid, ls.nthr, sh, s, a, la, *sr, ls.per, off_ck, ls.nslice);
-      if (st == CRT_OK)
-        note_kernel("k_colpre<canopy> + k_colsun + k_tri_lev_series<%s>%s M=%d nsel=%d slice=%d nt=%d", S::NAME, sizeof(TIO) == 8 ? "" : " f32", M,
-                    la.nsel, ls.per, sr->nt);
-      return st;
-    };
-    return ls.nthr <= 256   ? gos(k_tri_lev_series<S, TIO, M, 256>)
-           : ls.nthr <= 512 ? gos(k_tri_lev_series<S, TIO, M, 512>)
-                            : gos(k_tri_lev_series<S, TIO, M, 1024>);
+  void note(const LevLaunch& L) const {
+    char mid[16];
+    snprintf(mid, sizeof mid, " M=%d", M);
+    lev_note(L, "k_tri_lev", S::NAME, sizeof(TIO) == 4, mid);
   }
-  if (probe) return CRT_OK;
-  auto go = [&](auto kern) {
-    if (const int st = launch_kernel(kern, dim3(a.ncol, ls.nslice), ls.nthr, sh, s, a, la, ls.per, off_ck)) return st;
-    note_kernel("k_tri_lev<%s>%s M=%d nsel=%d slice=%d", S::NAME, sizeof(TIO) == 8 ? "" : " f32", M, la.nsel, ls.per);  // (only a launch that succeeded is reported)
-    return (int)CRT_OK;
-  };
-  if (ls.nthr <= 256) return go(k_tri_lev<S, TIO, M, 256>);
-  if (ls.nthr <= 512) return go(k_tri_lev<S, TIO, M, 512>);
-  return go(k_tri_lev<S, TIO, M, 1024>);
-}
+};
 
 template <class S, typename TIO>
 int launch_lev_scheme(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl) {
-  if (sl) {
-    int st = launch_lev_sens_m<S, TIO, 8>(a, la, s, sr, probe, sl);
-    if (st == CRT_ERR_UNSUPPORTED) st = launch_lev_sens_m<S, TIO, 16>(a, la, s, sr, probe, sl);
-    return st;
-  }
-  int st = launch_lev_m<S, TIO, 8>(a, la, s, sr, probe);  // M = 16 (half the checkpoints) only where M = 8 does not fit a 64-band slice
-  if (st == CRT_ERR_UNSUPPORTED) st = launch_lev_m<S, TIO, 16>(a, la, s, sr, probe);
-  return st;
+  // M = 16 (half the checkpoints) only where M = 8 does not fit a 64-band slice
+  return first_supported([&] { return launch_lev_form<TIO>(TriLev<S, TIO, 8>{a}, a, la, s, sr, probe, sl); },
+                         [&] { return launch_lev_form<TIO>(TriLev<S, TIO, 16>{a}, a, la, s, sr, probe, sl); });
 }
 
 template <class S, typename TIO, bool FUSED>
@@ -1418,8 +1349,7 @@ int launch_pipe_mt(const SolveArgs& a, hipStream_t s, int nstore_waves, bool reg
   if constexpr (T == 4 && M == 8) {  // narrow spectra: two staged pairs per store thread cover the tile
     if (narrow_rs) return go(k_tri_pipe<S, TIO, M, T, 512, 2>);  // (CRT_TILE_FLAG_FOUR_PAIR_STORE keeps the four-pair form: A/B)
   }
-  if (regstage) return nthr <= 512 ? go(k_tri_pipe<S, TIO, M, T, 512, PIPE_RS>) : go(k_tri_pipe<S, TIO, M, T, 1024, PIPE_RS>);
-  return nthr <= 512 ? go(k_tri_pipe<S, TIO, M, T, 512, 0>) : go(k_tri_pipe<S, TIO, M, T, 1024, 0>);
+  return with_pipe_bound(nthr, [&](auto B) { return regstage ? go(k_tri_pipe<S, TIO, M, T, B(), PIPE_RS>) : go(k_tri_pipe<S, TIO, M, T, B(), 0>); });
 }
 
 template <class S, typename TIO>

@@ -477,6 +477,28 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(M <= 8 ? 5
   zqpa_compute<TIO, M, T, RS>(a, cfg, lds, band);
 }
 
+// the computational-grid solve of a call: nz := Mg, no output array (the outputs go through PipeCfg, IntArgs or LevArgs; the record keeps
+// the caller's nz, which the kernels that need it get separately)
+inline SolveArgs zqpa_grid_args(const SolveArgs& a) {
+  SolveArgs g = a;
+  g.nz = zqpa_M(a.nz);
+  for (int i = 0; i < 7; ++i) g.o[i] = nullptr;
+  return g;
+}
+// what the fused kernels' PipeCfg share: K = Mg + 1 rows, checkpoints for the segments 1 .. top-1 (see tri_pipe_compute), the offsets up
+// to the tiles (what lies behind off_tile is the launcher's), the caller's level count and output arrays
+inline PipeCfg zqpa_pipe_cfg(const SolveArgs& a, int M, int ncomp) {
+  PipeCfg cfg{};
+  cfg.ncomp = ncomp;
+  cfg.nck = std::max(zqpa_M(a.nz) / M - 1, 0);
+  cfg.off_bc = (a.reclen + 1) & ~1;
+  cfg.off_ck = cfg.off_bc + ((a.nb + 1) & ~1);
+  cfg.off_tile = cfg.off_ck + 2 * cfg.nck * ncomp;
+  cfg.nz_out = a.nz;
+  for (int i = 0; i < 4; ++i) cfg.out[i] = a.o[i];
+  return cfg;
+}
+
 // odd band counts (the reference's 107): the same compute role, double-buffered tile, flat flush in the store waves (whole lines when the
 // output arrays are line-aligned)
 template <typename TIO, int M, int T>
@@ -485,24 +507,14 @@ int launch_zqpa_generic2(const SolveArgs& a, hipStream_t s, int nsw) {
   SolveArgs ao = a;  // (flat_flush_ok looks at the first ZqPaOut::NOUT output arrays)
   const int flat = a.tune.flat_flush != CRT_FLAT_FLUSH_OFF ? flat_flush_ok<ZqPaOut, TIO>(ao) : 0;
   if (!flat) return CRT_ERR_UNSUPPORTED;
-  const int Mg = zqpa_M(a.nz);
   const int ncomp = ((a.nb + 63) / 64) * 64;
   if (nsw <= 0) nsw = ncomp <= 128 ? 1 : 2;  // (3e4 x 107 x 60: 1 / 2 / 3 store waves 1.27 / 1.33 / 2.29 ms; the older kernel 1.48)
   const int nthr = ncomp + 64 * nsw;
   if (nthr > 512) return CRT_ERR_UNSUPPORTED;
-  SolveArgs g = a;
-  g.nz = Mg;
-  for (int i = 0; i < 7; ++i) g.o[i] = nullptr;
-  PipeCfg cfg{};
-  cfg.ncomp = ncomp;
-  cfg.nck = std::max(Mg / M - 1, 0);
-  cfg.off_bc = (a.reclen + 1) & ~1;
-  cfg.off_ck = cfg.off_bc + ((a.nb + 1) & ~1);
-  cfg.off_tile = cfg.off_ck + 2 * cfg.nck * ncomp;
+  const SolveArgs g = zqpa_grid_args(a);
+  PipeCfg cfg = zqpa_pipe_cfg(a, M, ncomp);
   cfg.off_park = cfg.off_tile + 2 * ZqPaOut::NST * T * a.nb;
   cfg.flat = (flat == 2 && a.nb >= 128 / (int)sizeof(TIO) && a.tune.flat_flush != CRT_FLAT_FLUSH_PART_LINE) ? 3 : flat;
-  cfg.nz_out = a.nz;
-  for (int i = 0; i < 4; ++i) cfg.out[i] = a.o[i];
   const size_t sh = ((size_t)cfg.off_park + (cfg.flat == 3 ? park_doubles<ZqPaOut, TIO>() : 0)) * sizeof(double);
   if (sh > MAX_WG_LDS / 2) return CRT_ERR_UNSUPPORTED;
   if (const int st = launch_kernel(k_zqpa_pipe2<TIO, M, T, 512, -1>, dim3(a.ncol), nthr, sh, s, g, cfg)) return st;
@@ -517,24 +529,14 @@ int launch_zqpa_fused2(const SolveArgs& a, hipStream_t s, int nsw, size_t lds_ca
   if (a.nb < a.tune.min_nb(16) || a.nb % 2) return CRT_ERR_UNSUPPORTED;  // even nb: the fused (row, band pair) flush
   for (int i = 0; i < 4; ++i)
     if (reinterpret_cast<uintptr_t>(a.o[i]) & (2 * sizeof(TIO) - 1)) return CRT_ERR_UNSUPPORTED;
-  const int Mg = zqpa_M(a.nz);
   const int ncomp = ((a.nb + 63) / 64) * 64;
   if (nsw <= 0) nsw = ncomp <= 128 ? 1 : 3;  // (two compute waves: one store wave keeps up, 3e4 x 106 x 60 1.19 -> 1.13 ms)
   if (ncomp + 64 * nsw > 1024) nsw = (1024 - ncomp) / 64;
   if (nsw < 1) return CRT_ERR_UNSUPPORTED;
   if (REGSTAGE && T * (a.nb / 2) > PIPE_RS * 64 * nsw) return CRT_ERR_UNSUPPORTED;
   const int nthr = ncomp + 64 * nsw;
-  SolveArgs g = a;  // computational-grid solve: nz := Mg; the outputs go through PipeCfg
-  g.nz = Mg;
-  for (int i = 0; i < 7; ++i) g.o[i] = nullptr;
-  PipeCfg cfg{};
-  cfg.ncomp = ncomp;
-  cfg.nck = std::max(Mg / M - 1, 0);
-  cfg.off_bc = (a.reclen + 1) & ~1;
-  cfg.off_ck = cfg.off_bc + ((a.nb + 1) & ~1);
-  cfg.off_tile = cfg.off_ck + 2 * cfg.nck * ncomp;
-  cfg.nz_out = a.nz;
-  for (int i = 0; i < 4; ++i) cfg.out[i] = a.o[i];
+  const SolveArgs g = zqpa_grid_args(a);
+  const PipeCfg cfg = zqpa_pipe_cfg(a, M, ncomp);
   const size_t sh = ((size_t)cfg.off_tile + (size_t)(REGSTAGE ? 1 : 2) * 2 * T * a.nb) * sizeof(double);
   if (sh > lds_cap) return CRT_ERR_UNSUPPORTED;
   auto go = [&](auto kern) {
@@ -544,7 +546,7 @@ int launch_zqpa_fused2(const SolveArgs& a, hipStream_t s, int nsw, size_t lds_ca
     return (int)CRT_OK;
   };
   constexpr int RSV = REGSTAGE ? PIPE_RS : 0;
-  return nthr <= 512 ? go(k_zqpa_pipe2<TIO, M, T, 512, RSV>) : go(k_zqpa_pipe2<TIO, M, T, 1024, RSV>);
+  return with_pipe_bound(nthr, [&](auto B) { return go(k_zqpa_pipe2<TIO, M, T, B(), RSV>); });
 }
 
 template <typename TIO, int M, int T, int MAXT, bool FLAT>
@@ -585,18 +587,9 @@ int launch_zqpa_fused(const SolveArgs& a, hipStream_t s, int nsw, size_t lds_cap
   if (ncomp + 64 * nsw > 1024) nsw = (1024 - ncomp) / 64;
   if (nsw < 1) return CRT_ERR_UNSUPPORTED;
   const int nthr = ncomp + 64 * nsw;
-  SolveArgs g = a;  // computational-grid solve: nz := Mg; the outputs go through PipeCfg
-  g.nz = Mg;
-  for (int i = 0; i < 7; ++i) g.o[i] = nullptr;
-  PipeCfg cfg{};
-  cfg.ncomp = ncomp;
-  cfg.nck = std::max(Mg / M - 1, 0);  // K = Mg + 1 rows; checkpoints for the segments 1 .. top-1 (see tri_pipe_compute)
-  cfg.off_bc = (a.reclen + 1) & ~1;
-  cfg.off_ck = cfg.off_bc + ((a.nb + 1) & ~1);
-  cfg.off_tile = cfg.off_ck + 2 * cfg.nck * ncomp;
+  const SolveArgs g = zqpa_grid_args(a);
+  PipeCfg cfg = zqpa_pipe_cfg(a, M, ncomp);
   cfg.off_halo = cfg.off_tile + 2 * 2 * T * a.nb;
-  cfg.nz_out = a.nz;
-  for (int i = 0; i < 4; ++i) cfg.out[i] = a.o[i];
   const size_t sh = ((size_t)cfg.off_halo + 2 * 3 * a.nb) * sizeof(double);
   if (sh > lds_cap) return CRT_ERR_UNSUPPORTED;
   auto go = [&](auto kern) {
@@ -604,8 +597,7 @@ int launch_zqpa_fused(const SolveArgs& a, hipStream_t s, int nsw, size_t lds_cap
     note_kernel("k_zqpa_pipe<%s%s> M=%d T=%d store_waves=%d lds=%zu", sizeof(TIO) == 8 ? "f64" : "f32", flat ? ",flat" : "", M, T, nsw, sh);  // (only a launch that succeeded is reported)
     return (int)CRT_OK;
   };
-  if (flat) return nthr <= 512 ? go(k_zqpa_pipe<TIO, M, T, 512, true>) : go(k_zqpa_pipe<TIO, M, T, 1024, true>);
-  return nthr <= 512 ? go(k_zqpa_pipe<TIO, M, T, 512, false>) : go(k_zqpa_pipe<TIO, M, T, 1024, false>);
+  return with_pipe_bound(nthr, [&](auto B) { return flat ? go(k_zqpa_pipe<TIO, M, T, B(), true>) : go(k_zqpa_pipe<TIO, M, T, B(), false>); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -884,36 +876,33 @@ inline size_t zqpa_int_lds_bytes(const SolveArgs& a, int M, int nthr, bool split
   return ((size_t)oint + zqpa_int_lds_doubles(Mg, nthr / 64, split)) * sizeof(double);
 }
 
+// zq_pa's description of the integrated launch (launch_int_form, launch_forms.hpp); the kernels solve on the computational grid and get
+// the caller's nz separately (the series: in SeriesArgs)
+template <typename TIO, int M, bool PROF, bool SPLIT>
+struct ZqPaInt {
+  const SolveArgs& a;
+  size_t lds_bytes(int nthr, bool) const { return zqpa_int_lds_bytes(a, M, nthr, SPLIT); }
+  template <int MAXT, bool SER, bool>  // (profiles or not is this description's PROF: it decides SPLIT too)
+  int launch(const IntLaunch& L) const {
+    int off_ck, off_int;
+    zqpa_int_lds_bytes(a, M, L.nthr, SPLIT, &off_ck, &off_int);
+    const SolveArgs g = zqpa_grid_args(a);
+    if constexpr (SER)
+      return launch_kernel(k_zqpa_int_series<M, MAXT, PROF, SPLIT>, L.grid, L.nthr, L.sh, L.s, g, L.ia, *L.sr, off_ck, off_int);
+    else
+      return launch_kernel(k_zqpa_int<TIO, M, MAXT, PROF, SPLIT>, L.grid, L.nthr, L.sh, L.s, g, L.ia, a.nz, off_ck, off_int);
+  }
+  void note(const IntLaunch& L) const {
+    const char* prof = PROF ? " + level profiles" : "";
+    if (L.sr)
+      note_kernel("k_colpre<canopy> + k_colsun + k_zqpa_int_series<zq_pa> M=%d grid=%d%s%s nt=%d", M, zqpa_M(a.nz), prof, SPLIT ? "" : " net flux", L.sr->nt);
+    else
+      note_kernel("k_zqpa_int<zq_pa>%s M=%d grid=%d%s", sizeof(TIO) == 8 ? "" : " f32", M, zqpa_M(a.nz), prof);
+  }
+};
 template <typename TIO, int M, bool PROF, bool SPLIT>
 int launch_zqpa_int_m(const SolveArgs& a, const IntArgs& ia, hipStream_t s, int nthr, const SeriesArgs* sr) {
-  const int Mg = zqpa_M(a.nz);
-  int off_ck, off_int;
-  const size_t sh = zqpa_int_lds_bytes(a, M, nthr, SPLIT, &off_ck, &off_int);
-  if (sh > MAX_WG_LDS) return CRT_ERR_UNSUPPORTED;
-  SolveArgs g = a;  // computational-grid solve: nz := Mg (the record keeps the caller's nz: passed separately)
-  g.nz = Mg;
-  for (int i = 0; i < 7; ++i) g.o[i] = nullptr;
-  auto go = [&](auto kern) {
-    if (const int st = launch_kernel(kern, dim3(a.ncol), nthr, sh, s, g, ia, a.nz, off_ck, off_int)) return st;
-    note_kernel("k_zqpa_int<zq_pa>%s M=%d grid=%d%s", sizeof(TIO) == 8 ? "" : " f32", M, Mg, PROF ? " + level profiles" : "");  // (only a launch that succeeded is reported)
-    return (int)CRT_OK;
-  };
-  if (sr) {
-    if constexpr (sizeof(TIO) == 8) {
-      auto gos = [&](auto kern) {
-        const int st = launch_kernel(kern, series_grid(a.ncol, sr->nt), nthr, sh, s, g, ia, *sr, off_ck, off_int);
-        if (st == CRT_OK)
-          note_kernel("k_colpre<canopy> + k_colsun + k_zqpa_int_series<zq_pa> M=%d grid=%d%s%s nt=%d", M, Mg, PROF ? " + level profiles" : "",
-                      SPLIT ? "" : " net flux", sr->nt);
-        return st;
-      };
-      return nthr <= 256 ? gos(k_zqpa_int_series<M, 256, PROF, SPLIT>) : nthr <= 512 ? gos(k_zqpa_int_series<M, 512, PROF, SPLIT>) : gos(k_zqpa_int_series<M, 1024, PROF, SPLIT>);
-    }
-    return CRT_ERR_UNSUPPORTED;  // no f32 form of the series
-  }
-  if (nthr <= 256) return go(k_zqpa_int<TIO, M, 256, PROF, SPLIT>);
-  if (nthr <= 512) return go(k_zqpa_int<TIO, M, 512, PROF, SPLIT>);
-  return go(k_zqpa_int<TIO, M, 1024, PROF, SPLIT>);
+  return launch_int_form<TIO>(ZqPaInt<TIO, M, PROF, SPLIT>{a}, a, ia, s, nthr, sr);
 }
 
 // integrated path of zq_pa (float64 or float32 spectra, TIO): one kernel, no workspace beyond the K0 record
@@ -1125,85 +1114,44 @@ inline ZqPaLevLds zqpa_lev_lds(const SolveArgs& a, int M, int nthr, int nsel) {
   return L;
 }
 
-// the sensor-band form: the staging row [4][nthr] behind the kept rows, slices narrowed until everything fits
+// zq_pa's description of the level launch (launch_lev_form, launch_forms.hpp): the band slices narrowed until the checkpoints and kept
+// rows (and the sensor forms' staging row [4][nthr] behind them) fit; the kernels solve on the computational grid and get the caller's nz
+// separately (the series: in SeriesArgs)
 template <typename TIO>
-int launch_zqpa_lev_sens(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl) {
-  constexpr int M = 8;
-  auto bytes = [&](int nthr) { return zqpa_lev_lds(a, M, nthr, la.nsel).bytes + (size_t)SENS_STAGE * nthr * sizeof(double); };
-  const LevSlices ls = lev_slices_fit(a.nb, MAX_WG_LDS, bytes);
-  if (ls.nslice == 0 || ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
-  const ZqPaLevLds L = zqpa_lev_lds(a, M, ls.nthr, la.nsel);
-  const int off_st = (int)(L.bytes / sizeof(double));
-  const size_t sh = bytes(ls.nthr);
-  const int Mg = zqpa_M(a.nz);
-  SolveArgs g = a;  // computational-grid solve: nz := Mg (the record keeps the caller's nz: passed separately)
-  g.nz = Mg;
-  for (int i = 0; i < 7; ++i) g.o[i] = nullptr;
-  const long long nv = (long long)a.ncol * (sr ? sr->nt : 1);
-  dim3 grid(a.ncol, ls.nslice);
-  if (sr && (sizeof(TIO) != 8 || !lev_series_grid(a.ncol, sr->nt, ls.nslice, &grid))) return CRT_ERR_UNSUPPORTED;
-  int st = sens_probe(sl, ls, nv, la.nsel);
-  if (probe || st != CRT_OK) return st;
-  if (sr) {
-    if constexpr (sizeof(TIO) == 8) {
-      auto gos = [&](auto kern) {
-        return launch_kernel(kern, grid, ls.nthr, sh, s, g, la, sl->sn, *sr, ls.per, L.off_map, L.off_ck, L.off_val, off_st, ls.nslice);
-      };
-      st = ls.nthr <= 256   ? gos(k_zqpa_lev_sens_series<M, 256>)
-           : ls.nthr <= 512 ? gos(k_zqpa_lev_sens_series<M, 512>)
-                            : gos(k_zqpa_lev_sens_series<M, 1024>);
-    } else {
-      return CRT_ERR_UNSUPPORTED;
-    }
-  } else {
-    auto go = [&](auto kern) { return launch_kernel(kern, grid, ls.nthr, sh, s, g, la, sl->sn, a.nz, ls.per, L.off_map, L.off_ck, L.off_val, off_st); };
-    st = ls.nthr <= 256 ? go(k_zqpa_lev_sens<TIO, M, 256>) : ls.nthr <= 512 ? go(k_zqpa_lev_sens<TIO, M, 512>) : go(k_zqpa_lev_sens<TIO, M, 1024>);
+struct ZqPaLev {
+  static constexpr bool FIT = true, HBM_RECORD = false;
+  static constexpr int M = 8;
+  const SolveArgs& a;
+  int nsel;
+  size_t lds_bytes(int nthr, bool sens) const { return zqpa_lev_lds(a, M, nthr, nsel).bytes + (sens ? (size_t)SENS_STAGE * nthr * sizeof(double) : 0); }
+  template <int MAXT, bool SER, bool SENS, bool>
+  int launch(const LevLaunch& L) const {
+    const LevSlices& ls = L.ls;
+    const ZqPaLevLds Z = zqpa_lev_lds(a, M, ls.nthr, nsel);
+    const int off_st = (int)(Z.bytes / sizeof(double));
+    const SolveArgs g = zqpa_grid_args(a);
+    if constexpr (SER && SENS)
+      return launch_kernel(k_zqpa_lev_sens_series<M, MAXT>, L.grid, ls.nthr, L.sh, L.s, g, L.la, L.sl->sn, *L.sr, ls.per, Z.off_map, Z.off_ck, Z.off_val,
+                           off_st, ls.nslice);
+    else if constexpr (SENS)
+      return launch_kernel(k_zqpa_lev_sens<TIO, M, MAXT>, L.grid, ls.nthr, L.sh, L.s, g, L.la, L.sl->sn, a.nz, ls.per, Z.off_map, Z.off_ck, Z.off_val, off_st);
+    else if constexpr (SER)
+      return launch_kernel(k_zqpa_lev_series<TIO, M, MAXT>, L.grid, ls.nthr, L.sh, L.s, g, L.la, *L.sr, ls.per, Z.off_map, Z.off_ck, Z.off_val, ls.nslice);
+    else
+      return launch_kernel(k_zqpa_lev<TIO, M, MAXT>, L.grid, ls.nthr, L.sh, L.s, g, L.la, a.nz, ls.per, Z.off_map, Z.off_ck, Z.off_val);
   }
-  if (st != CRT_OK || (st = sens_finish(sl, ls, nv, a.nb, la.nsel, s)) != CRT_OK) return st;
-  note_kernel("%sk_zqpa_lev_sens%s<zq_pa>%s M=%d grid=%d nsel=%d nsens=%d slice=%d%s", sr ? "k_colpre<canopy> + k_colsun + " : "", sr ? "_series" : "",
-              sizeof(TIO) == 8 ? "" : " f32", M, Mg, la.nsel, sl->sn.nsens, ls.per, ls.nslice > 1 ? " + k_sens_finish" : "");
-  return CRT_OK;
-}
-
-template <typename TIO>
-int launch_zqpa_lev_io(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe) {
-  constexpr int M = 8;
-  const LevSlices ls = lev_slices_fit(a.nb, MAX_WG_LDS, [&](int nthr) { return zqpa_lev_lds(a, M, nthr, la.nsel).bytes; });  // widest slice whose checkpoints and kept rows fit
-  if (ls.nslice == 0 || ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
-  const ZqPaLevLds L = zqpa_lev_lds(a, M, ls.nthr, la.nsel);
-  const int Mg = zqpa_M(a.nz);
-  SolveArgs g = a;  // computational-grid solve: nz := Mg (the record keeps the caller's nz: passed separately)
-  g.nz = Mg;
-  for (int i = 0; i < 7; ++i) g.o[i] = nullptr;
-  if (sr) {
-    dim3 grid;
-    if (!lev_series_grid(a.ncol, sr->nt, ls.nslice, &grid)) return CRT_ERR_UNSUPPORTED;
-    if (probe) return CRT_OK;
-    auto gos = [&](auto kern) {
-      const int st = launch_kernel(kern, grid, ls.nthr, L.bytes, s, g, la, *sr, ls.per, L.off_map, L.off_ck, L.off_val, ls.nslice);
-      if (st == CRT_OK)
-        note_kernel("k_colpre<canopy> + k_colsun + k_zqpa_lev_series<zq_pa>%s M=%d grid=%d nsel=%d slice=%d nt=%d", sizeof(TIO) == 8 ? "" : " f32", M,
-                    Mg, la.nsel, ls.per, sr->nt);
-      return st;
-    };
-    return ls.nthr <= 256 ? gos(k_zqpa_lev_series<TIO, M, 256>) : ls.nthr <= 512 ? gos(k_zqpa_lev_series<TIO, M, 512>) : gos(k_zqpa_lev_series<TIO, M, 1024>);
+  void note(const LevLaunch& L) const {
+    char mid[32];
+    snprintf(mid, sizeof mid, " M=%d grid=%d", M, zqpa_M(a.nz));
+    lev_note(L, "k_zqpa_lev", "zq_pa", sizeof(TIO) == 4, mid);
   }
-  if (probe) return CRT_OK;
-  auto go = [&](auto kern) {
-    if (const int st = launch_kernel(kern, dim3(a.ncol, ls.nslice), ls.nthr, L.bytes, s, g, la, a.nz, ls.per, L.off_map, L.off_ck, L.off_val)) return st;
-    note_kernel("k_zqpa_lev<zq_pa>%s M=%d grid=%d nsel=%d slice=%d", sizeof(TIO) == 8 ? "" : " f32", M, Mg, la.nsel, ls.per);  // (only a launch that succeeded is reported)
-    return (int)CRT_OK;
-  };
-  if (ls.nthr <= 256) return go(k_zqpa_lev<TIO, M, 256>);
-  if (ls.nthr <= 512) return go(k_zqpa_lev<TIO, M, 512>);
-  return go(k_zqpa_lev<TIO, M, 1024>);
-}
+};
 
 }  // namespace
 
 int launch_zqpa_lev(const SolveArgs& a, const LevArgs& la, hipStream_t s, const SeriesArgs* sr, bool probe, SensLaunch* sl) {
-  if (sl) return a.f32 ? launch_zqpa_lev_sens<float>(a, la, s, sr, probe, sl) : launch_zqpa_lev_sens<double>(a, la, s, sr, probe, sl);
-  return a.f32 ? launch_zqpa_lev_io<float>(a, la, s, sr, probe) : launch_zqpa_lev_io<double>(a, la, s, sr, probe);
+  return a.f32 ? launch_lev_form<float>(ZqPaLev<float>{a, la.nsel}, a, la, s, sr, probe, sl)
+               : launch_lev_form<double>(ZqPaLev<double>{a, la.nsel}, a, la, s, sr, probe, sl);
 }
 
 int launch_zqpa_int(const SolveArgs& a, const IntArgs& ia, hipStream_t s, const SeriesArgs* sr) {
@@ -1221,19 +1169,15 @@ int launch_zqpa(const SolveArgs& a, double* scratch, hipStream_t s) {
     const bool short_segments = tune.tri_m == 8;   // A/B: M = 8 in k_zqpa_pipe2 (fewer registers: five waves per SIMD, three WG per CU)
     const bool narrow_m12 = tune.tri_m != 16;      // narrow spectra take k_zqpa_pipe at M = 12 unless M = 16 is asked for
     const bool try_rs = family != CRT_TRI_FAMILY_ZQPA_PIPE2_DB, try_db = family != CRT_TRI_FAMILY_ZQPA_PIPE2_RS;
-    int st;
     // two workgroups per CU first (half of the LDS each): M = 16, T = 4, or -- above ~85 levels at 300 bands -- tiles of 3 levels
     // (M = 15), which is what brings 100 levels from 84 KB to 74 KB; then whatever fits at all
     constexpr size_t HALF = MAX_WG_LDS / 2;
-    if (a.f32) {
-      st = launch_zqpa_fused<float, 16, 4>(a, s, nsw, HALF);
-      if (st == CRT_ERR_UNSUPPORTED) st = launch_zqpa_fused<float, 15, 3>(a, s, nsw, HALF);
-      if (st == CRT_ERR_UNSUPPORTED) st = launch_zqpa_fused<float, 16, 4>(a, s, nsw);
-      if (st == CRT_ERR_UNSUPPORTED) st = launch_zqpa_fused<float, 15, 3>(a, s, nsw);  // (wide spectra near 100 levels: 601 x 99 needs it)
-      if (st == CRT_ERR_UNSUPPORTED) st = launch_zqpa_fused<float, 12, 4>(a, s, nsw);
-      return st;  // f32 storage exists in the fused kernel only (the two-kernel path keeps its computational-grid scratch in fp64)
-    }
-    st = CRT_ERR_UNSUPPORTED;
+    if (a.f32)  // f32 storage exists in the fused kernel only (the two-kernel path keeps its computational-grid scratch in fp64)
+      return first_supported([&] { return launch_zqpa_fused<float, 16, 4>(a, s, nsw, HALF); }, [&] { return launch_zqpa_fused<float, 15, 3>(a, s, nsw, HALF); },
+                             [&] { return launch_zqpa_fused<float, 16, 4>(a, s, nsw); },
+                             [&] { return launch_zqpa_fused<float, 15, 3>(a, s, nsw); },  // (wide spectra near 100 levels: 601 x 99 needs it)
+                             [&] { return launch_zqpa_fused<float, 12, 4>(a, s, nsw); });
+    int st = CRT_ERR_UNSUPPORTED;
     // round 3: interpolation in the compute lanes + the plain fused store role (even nb; CRT_TRI_FAMILY_ZQPA_PIPE keeps the kernel below,
     // CRT_TRI_FAMILY_ZQPA_PIPE2_DB / _RS force the double-buffered / register-staged form)
     // Measured (tools/ragged_sweep.py, round 3; both kernels on the division-free sweep): 1e4 x 300 x 60 1.10 (below) vs 1.11-1.13 ms,
@@ -1242,17 +1186,18 @@ int launch_zqpa(const SolveArgs& a, double* scratch, hipStream_t s) {
     // (round 3, after the level emission was rewritten: also 65 .. 128 even bands with ONE store wave -- 3e4 x 106 x 60 1.21 -> 1.13 ms; below
     //  65 bands the older kernel stays ahead, 1e5 x 38 x 100 3.01 vs 3.15 ms: profiles/r03/zqpa_pipe2_narrow_tune.txt)
     if (family != CRT_TRI_FAMILY_ZQPA_PIPE && (a.nb > 64 || family >= CRT_TRI_FAMILY_ZQPA_PIPE2_DB || short_segments)) {
-      constexpr size_t HALF2 = MAX_WG_LDS / 2;
-      if (short_segments) {
-        if (try_rs) st = launch_zqpa_fused2<double, 8, 4, true>(a, s, nsw, MAX_WG_LDS / 3);
-        if (st == CRT_ERR_UNSUPPORTED && try_db) st = launch_zqpa_fused2<double, 8, 4, false>(a, s, nsw, MAX_WG_LDS / 3);
-        if (st == CRT_ERR_UNSUPPORTED) st = launch_zqpa_fused2<double, 8, 4, true>(a, s, nsw, HALF2);
-      } else {  // M = 16 at any depth: it keeps the LDS small with few checkpoints, and registers cap M with many
-        if (try_rs) st = launch_zqpa_fused2<double, 16, 4, true>(a, s, nsw, HALF2);
-        if (st == CRT_ERR_UNSUPPORTED && try_db) st = launch_zqpa_fused2<double, 16, 4, false>(a, s, nsw, HALF2);
-      }
-      if (st == CRT_ERR_UNSUPPORTED && try_rs) st = launch_zqpa_fused2<double, 16, 4, true>(a, s, nsw);
-      if (st == CRT_ERR_UNSUPPORTED && try_db) st = launch_zqpa_fused2<double, 16, 4, false>(a, s, nsw);
+      // an attempt the family override excludes (try_rs: register-staged, try_db: double-buffered) counts as unsupported
+      constexpr int SKIP = CRT_ERR_UNSUPPORTED;
+      if (short_segments)
+        st = first_supported([&] { return try_rs ? launch_zqpa_fused2<double, 8, 4, true>(a, s, nsw, MAX_WG_LDS / 3) : SKIP; },
+                             [&] { return try_db ? launch_zqpa_fused2<double, 8, 4, false>(a, s, nsw, MAX_WG_LDS / 3) : SKIP; },
+                             [&] { return launch_zqpa_fused2<double, 8, 4, true>(a, s, nsw, HALF); });
+      else  // M = 16 at any depth: it keeps the LDS small with few checkpoints, and registers cap M with many
+        st = first_supported([&] { return try_rs ? launch_zqpa_fused2<double, 16, 4, true>(a, s, nsw, HALF) : SKIP; },
+                             [&] { return try_db ? launch_zqpa_fused2<double, 16, 4, false>(a, s, nsw, HALF) : SKIP; });
+      if (st == CRT_ERR_UNSUPPORTED)
+        st = first_supported([&] { return try_rs ? launch_zqpa_fused2<double, 16, 4, true>(a, s, nsw) : SKIP; },
+                             [&] { return try_db ? launch_zqpa_fused2<double, 16, 4, false>(a, s, nsw) : SKIP; });
       if (st != CRT_ERR_UNSUPPORTED) return st;
     }
     if (a.nb % 2 == 1 && family != CRT_TRI_FAMILY_ZQPA_PIPE) {  // odd band counts: the new compute role with the flat flush
@@ -1261,19 +1206,15 @@ int launch_zqpa(const SolveArgs& a, double* scratch, hipStream_t s) {
     }
     // narrow spectra (one compute wave per column): M = 12 needs 92 registers, five waves per SIMD instead of four (1e5 x 38 x 100:
     // 3.74 -> 3.64 ms, 2e5 x 16 x 60 3.23 -> 3.16; at 62 bands the other way, 2.61 -> 2.64)
-    if (a.nb <= 48 && narrow_m12) st = launch_zqpa_fused<double, 12, 4>(a, s, nsw, HALF);
-    if (st == CRT_ERR_UNSUPPORTED) st = launch_zqpa_fused<double, 16, 4>(a, s, nsw, HALF);
-    if (st == CRT_ERR_UNSUPPORTED) st = launch_zqpa_fused<double, 15, 3>(a, s, nsw, HALF);
-    if (st == CRT_ERR_UNSUPPORTED) st = launch_zqpa_fused<double, 16, 4>(a, s, nsw);
-    if (st == CRT_ERR_UNSUPPORTED) st = launch_zqpa_fused<double, 12, 4>(a, s, nsw);
+    st = first_supported([&] { return a.nb <= 48 && narrow_m12 ? launch_zqpa_fused<double, 12, 4>(a, s, nsw, HALF) : (int)CRT_ERR_UNSUPPORTED; },
+                         [&] { return launch_zqpa_fused<double, 16, 4>(a, s, nsw, HALF); }, [&] { return launch_zqpa_fused<double, 15, 3>(a, s, nsw, HALF); },
+                         [&] { return launch_zqpa_fused<double, 16, 4>(a, s, nsw); }, [&] { return launch_zqpa_fused<double, 12, 4>(a, s, nsw); });
     if (st != CRT_ERR_UNSUPPORTED) return st;
   }
   const int M = zqpa_M(a.nz);
-  SolveArgs g = a;  // computational-grid solve: nz := M, outputs := scratch
-  g.nz = M;
+  SolveArgs g = zqpa_grid_args(a);  // outputs := scratch
   g.o[0] = scratch;
   g.o[1] = scratch + (size_t)a.ncol * M * a.nb;
-  for (int i = 2; i < 7; ++i) g.o[i] = nullptr;
   bool done = false;
   int st = launch_scheme<TriZqPa, double>(g, s, done, 1);
   if (st != CRT_OK) return st;
