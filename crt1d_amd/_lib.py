@@ -294,6 +294,27 @@ def _jac_signatures():
 _JAC_SIGNATURES = _jac_signatures()
 JAC_EXPORTS = list(_JAC_SIGNATURES)
 
+# LAI derivative of the level spectra (include/crt1d_hip_dlai.h), again a header and a table of their own
+DLAI_MAX_NZ = {"n79": 928, "zq": 1135}  # CRT_DLAI_MAX_NZ_N79, CRT_DLAI_MAX_NZ_ZQ
+
+
+class CrtDlaiOut(ctypes.Structure):
+    _fields_ = [(k, _vp) for k in ("I_dr", "I_df_d", "I_df_u", "F")]
+
+
+def _dlai_signatures():
+    P = ctypes.POINTER
+    i, i32, i64, sz, ok = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_int
+    return {
+        "crt_hip_levels_dlai_workspace_bytes": (sz, [i, i32, i32, i32, i32]),
+        "crt_hip_levels_dlai_f64": (ok, [i, P(CrtColumns), P(CrtBands), P(CrtOptions), P(i32), i32, P(CrtDlaiOut), _vp, sz, _vp]),
+        "crt_hip_dtau_d_f64": (ok, [_vp, _vp, i64, i32, _vp, _vp]),
+    }
+
+
+_DLAI_SIGNATURES = _dlai_signatures()
+DLAI_EXPORTS = list(_DLAI_SIGNATURES)
+
 _lib = None
 
 
@@ -316,7 +337,8 @@ def load():
     import torch  # noqa: F401
 
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES, **_SENSOR_SIGNATURES, **_JAC_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES, **_SENSOR_SIGNATURES, **_JAC_SIGNATURES,
+                                      **_DLAI_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:

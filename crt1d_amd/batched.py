@@ -1387,3 +1387,91 @@ def sensor_jvp(scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, 
             t = term if t is None else t + term
         out[k] = torch.einsum("crkb,sb->crsk", t, w)
     return out
+
+
+# ---- LAI derivative of the level spectra (include/crt1d_hip_dlai.h) --------------------------------------------------------------------
+
+DLAI_KEYS = LEVEL_KEYS  # every level quantity depends on the LAI, I_dr included
+DLAI_SCHEMES = ("2s", "bl", "g77", "bf", "n79", "zq")
+DLAI_PER = ("log", "lai")
+
+
+def _dlai_per(per):
+    if per not in DLAI_PER:
+        raise ValueError(f"per must be 'log' (dX / d ln LAI) or 'lai' (dX / d LAI), got {per!r}")
+    return per
+
+
+def levels_dlai_workspace_bytes(scheme, ncol, nz, nb, nsel):
+    """Device workspace of a :class:`LevelsDlaiPlan` call: the records of :func:`workspace_bytes` at the same offsets, then the side
+    records (the tangents of the record entries; bl, n79, zq)."""
+    return int(_lib.load().crt_hip_levels_dlai_workspace_bytes(_lib.SCHEME_IDS[scheme], ncol, nz, nb, nsel))
+
+
+class LevelsDlaiPlan(_SolvePlan):
+    """Pre-validated derivative of the level spectra with respect to the leaf area index (``crt_hip_levels_dlai_f64``).  Every column's
+    cumulative LAI profile is scaled as ``lai(s) = s * lai`` (the vertical distribution stays fixed); ``out[k][c, r, b]`` is the exact
+    derivative of ``X[c, levels[r], b]`` (``X`` in ``keys``, any of ``I_dr, I_df_d, I_df_u, F``: what :class:`LevelsPlan` returns) at
+    ``s = 1``, each ``(ncol, nsel, nb)`` float64.  ``per="log"``: ``dX / ds = dX / d ln(LAI)``; ``per="lai"``: divided by the column's total
+    LAI ``lai[c, 0]`` on the device, ``dX / dLAI``.  One column precompute and one kernel; no finite differences.  Schemes:
+    ``DLAI_SCHEMES`` (``4s`` and ``zq_pa`` are a ValueError; n79 / zq beyond ``_lib.DLAI_MAX_NZ`` levels a RuntimeError from the call).
+    ``FLAG_SKIP_PRECOMPUTE`` is valid only on a workspace a call of this plan's entry has filled (the side records).  A column's result
+    is bitwise the same alone or in any batch, for any subset of ``keys`` and of ``levels``."""
+
+    _bad_dlai_scheme = "scheme {!r} has no LAI-derivative kernel; served: " + ", ".join(DLAI_SCHEMES)
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, levels, *, keys=DLAI_KEYS, per="log", mu_s=0.501, tau_d_method="quad",
+                 out=None, workspace=None):
+        keys, self.per = self._check_dlai(scheme, tau_d_method, keys, per)
+        if bands.dtype != torch.float64:
+            raise TypeError("the LAI derivative has no f32 storage form: bands must be float64")
+        self.levels, self.keys = normalize_levels(levels, cols.nz), keys
+        self._bind(scheme, cols, bands, mu_s, tau_d_method)
+        shape = (cols.ncol, len(self.levels), bands.nb)
+        out = _outputs({k: shape for k in keys}, out, torch.float64, cols.device, "output {!r}", lacks=True)
+        self.out = {k: out[k] for k in keys}
+        self._out = _lib.CrtDlaiOut(*[out[k].data_ptr() if k in keys else None for k in DLAI_KEYS])
+        self._lev = (ctypes.c_int32 * len(self.levels))(*self.levels)
+        self._lai_total = cols.lai[:, 0].contiguous()[:, None, None] if per == "lai" else None
+        need = levels_dlai_workspace_bytes(scheme, cols.ncol, cols.nz, bands.nb, len(self.levels))
+        self._finish("crt_hip_levels_dlai_f64", need, workspace)
+
+    @classmethod
+    def _check_dlai(cls, scheme, tau_d_method="quad", keys=DLAI_KEYS, per="log", **_):
+        """The checks that need neither a column nor a device: scheme, method, keys, ``per``.  -> (keys, per)"""
+        cls._check_options(cls, scheme, tau_d_method)
+        if scheme not in DLAI_SCHEMES:
+            raise ValueError(cls._bad_dlai_scheme.format(scheme))
+        return _level_keys(keys), _dlai_per(per)
+
+    def _tail(self):
+        return self._lev, len(self.levels), ctypes.byref(self._out)
+
+    def __call__(self, stream=None, *, flags=0):
+        out = super().__call__(stream, flags=flags)
+        if self._lai_total is not None and not flags & _lib.FLAG_PRECOMPUTE_ONLY:
+            s = torch.cuda.current_stream(self.cols.device) if stream is None else stream
+            with torch.cuda.stream(s):
+                for v in out.values():
+                    v.div_(self._lai_total)
+        return out
+
+
+def solve_levels_dlai(scheme, cols: Columns, bands: Bands, levels, **kw):
+    """One-shot :class:`LevelsDlaiPlan`: ``{key: (ncol, nsel, nb)}`` at the sorted levels ``normalize_levels(levels, nz)``."""
+    LevelsDlaiPlan._check_dlai(scheme, **kw)  # (before any device is touched)
+    with torch.cuda.device(cols.device):
+        return LevelsDlaiPlan(scheme, cols, bands, levels, **kw)()
+
+
+def sensor_dlai(scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, **kw):
+    """The LAI derivative of :class:`SensorLevelsPlan`'s sums: per key ``(ncol, nsel, nsens)`` with
+    ``out[c, r, s] = sum_b w_s[b] * dX[c, r, b]``.  ``dX`` comes from one :class:`LevelsDlaiPlan` call (``kw`` goes there, ``per``
+    included); the contraction with the sensor set's dense weights runs in torch on the device, as in :func:`sensor_jvp`."""
+    if not isinstance(sensors, SensorSet):
+        raise TypeError("sensors must be a SensorSet")
+    LevelsDlaiPlan._check_dlai(scheme, **kw)
+    sensors.check(bands.nb, cols.device)
+    d = solve_levels_dlai(scheme, cols, bands, levels, **kw)
+    w = torch.as_tensor(sensors.dense(bands.nb)).to(cols.device)
+    return {k: torch.einsum("crb,sb->crs", v, w) for k, v in d.items()}

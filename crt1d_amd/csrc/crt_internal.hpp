@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "crt1d_hip.h"
+#include "crt1d_hip_dlai.h"
 #include "crt1d_hip_jac.h"
 #include "crt1d_hip_sensor.h"
 
@@ -928,6 +929,40 @@ static_assert(jac_tri_lanes(CRT_SCHEME_N79, 304) == 64 && jac_tri_lanes(CRT_SCHE
               "whole waves up to 304 (n79) / 311 (zq) levels, as crt1d_hip_jac.h says");
 // probe: return the status (CRT_OK / CRT_ERR_UNSUPPORTED) of the configuration without launching anything
 int launch_jac(int scheme, const SolveArgs& a, const LevArgs& la, const JacArgs& jo, hipStream_t s, bool probe);
+
+// ------------------------------------------------------------------------------------------
+// LAI derivative of the level spectra (crt_hip_levels_dlai_f64, include/crt1d_hip_dlai.h; kernels in dlai.hip)
+struct DlaiArgs {
+  double* o[4];        // d I_dr, d I_df_d, d I_df_u, d F: [ncol][nsel][nb] or NULL
+  const double* side;  // side records [ncol][dlai_side_len]: the s-tangent of the record entries the kernel reads
+};
+// doubles of a column's side record: bl the tangent of its tau_d vector; n79 / zq the tangent of every entry of the record part the
+// tridiagonal kernel stages, in the record's own layout (header included); 2s, g77, bf none (their tangents follow from the record itself)
+constexpr int dlai_side_len(int scheme, int nz) {
+  return scheme == CRT_SCHEME_BL ? nz : (scheme == CRT_SCHEME_N79 || scheme == CRT_SCHEME_ZQ) ? jac_tri_nrec(scheme, nz) : 0;
+}
+// n79 / zq: LDS bytes with W lanes per workgroup -- the staged record part twice (values | tangents), then the level states as in
+// k_jac_tri -- and the widest W out of 64, 32, 16 that fits 160 KB (0: none)
+constexpr size_t dlai_tri_lds_bytes(int scheme, int nz, int W) {
+  const size_t nst = scheme == CRT_SCHEME_N79 ? (size_t)nz : (size_t)nz + 1, ncp = (nst + JAC_TRI_CP - 1) / JAC_TRI_CP;
+  return (2 * (((size_t)jac_tri_nrec(scheme, nz) + 1) & ~(size_t)1) + ncp * 4 * W) * sizeof(double);
+}
+constexpr int dlai_tri_lanes(int scheme, int nz) {
+  for (int W = 64; W >= 16; W >>= 1)
+    if (dlai_tri_lds_bytes(scheme, nz, W) <= 160 * 1024) return W;
+  return 0;
+}
+static_assert(dlai_tri_lanes(CRT_SCHEME_N79, CRT_DLAI_MAX_NZ_N79) == 16 && dlai_tri_lanes(CRT_SCHEME_N79, CRT_DLAI_MAX_NZ_N79 + 1) == 0 &&
+                  dlai_tri_lanes(CRT_SCHEME_ZQ, CRT_DLAI_MAX_NZ_ZQ) == 16 && dlai_tri_lanes(CRT_SCHEME_ZQ, CRT_DLAI_MAX_NZ_ZQ + 1) == 0,
+              "the depth limits of crt1d_hip_dlai.h are those of the LDS layout");
+static_assert(dlai_tri_lanes(CRT_SCHEME_N79, 292) == 64 && dlai_tri_lanes(CRT_SCHEME_N79, 293) == 32 && dlai_tri_lanes(CRT_SCHEME_N79, 536) == 32 &&
+                  dlai_tri_lanes(CRT_SCHEME_N79, 537) == 16 && dlai_tri_lanes(CRT_SCHEME_ZQ, 307) == 64 && dlai_tri_lanes(CRT_SCHEME_ZQ, 308) == 32 &&
+                  dlai_tri_lanes(CRT_SCHEME_ZQ, 599) == 32 && dlai_tri_lanes(CRT_SCHEME_ZQ, 600) == 16,
+              "the lane-narrowing thresholds crt1d_hip_dlai.h states");
+// the side precompute (after K0, same stream); the derivative kernel (probe: the status of the configuration, nothing launched); tau_d'
+int launch_dlai_side(const ColArgs& ca, double* side, hipStream_t s);
+int launch_dlai(int scheme, const SolveArgs& a, const LevArgs& la, const DlaiArgs& da, hipStream_t s, bool probe);
+int launch_dtau_d(const double* kb_nodes, const double* L, long long n, int method, double* out, hipStream_t s);
 
 // launchers implemented in the .hip files
 int launch_colpre(const ColArgs& a, hipStream_t s);
