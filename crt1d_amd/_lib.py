@@ -315,6 +315,31 @@ def _dlai_signatures():
 _DLAI_SIGNATURES = _dlai_signatures()
 DLAI_EXPORTS = list(_DLAI_SIGNATURES)
 
+# leaf-angle derivative of the level spectra (include/crt1d_hip_dleaf.h), again a header and a table of their own; the outputs are a
+# CrtDlaiOut, the depth limits DLAI_MAX_NZ
+
+
+class CrtLeafTangent(ctypes.Structure):
+    """``crt_leaf_tangent``: device pointers; ``dmla`` may be NULL (zeros)."""
+
+    _fields_ = [(k, _vp) for k in ("dg_table", "dg_at_psi", "dmla")]
+
+
+def _dleaf_signatures():
+    P = ctypes.POINTER
+    i, i32, i64, sz, ok = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_int
+    return {
+        "crt_hip_levels_dleaf_workspace_bytes": (sz, [i, i32, i32, i32, i32]),
+        "crt_hip_levels_dleaf_f64": (ok, [i, P(CrtColumns), P(CrtBands), P(CrtOptions), P(i32), i32, P(CrtLeafTangent), P(CrtDlaiOut), _vp, sz,
+                                          _vp]),
+        "crt_hip_g_dparam_f64": (ok, [P(CrtColumns), _vp, _vp, _vp]),
+        "crt_hip_dtau_d_dleaf_f64": (ok, [_vp, _vp, _vp, i64, i32, _vp, _vp]),
+    }
+
+
+_DLEAF_SIGNATURES = _dleaf_signatures()
+DLEAF_EXPORTS = list(_DLEAF_SIGNATURES)
+
 _lib = None
 
 
@@ -338,7 +363,7 @@ def load():
 
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES, **_SENSOR_SIGNATURES, **_JAC_SIGNATURES,
-                                      **_DLAI_SIGNATURES}.items():
+                                      **_DLAI_SIGNATURES, **_DLEAF_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:

@@ -1475,3 +1475,147 @@ def sensor_dlai(scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet,
     d = solve_levels_dlai(scheme, cols, bands, levels, **kw)
     w = torch.as_tensor(sensors.dense(bands.nb)).to(cols.device)
     return {k: torch.einsum("crb,sb->crs", v, w) for k, v in d.items()}
+
+
+# ---- leaf-angle derivative of the level spectra (include/crt1d_hip_dleaf.h) -------------------------------------------------------------
+
+DLEAF_KEYS = LEVEL_KEYS
+DLEAF_SCHEMES = DLAI_SCHEMES
+LEAF_WRT = ("param", "mla", "a", "b")
+
+
+@dataclass
+class LeafTangent:
+    """A leaf-angle direction of every column (``crt_leaf_tangent``): the tangent of G at ``_lib.quad_nodes()`` and at the sun angle, and
+    of the mean leaf angle in degrees (2s reads it; ``None``: zeros)."""
+
+    dg_table: torch.Tensor  # (ncol, NQ)
+    dg_at_psi: torch.Tensor  # (ncol,)
+    dmla: Optional[torch.Tensor] = None  # (ncol,) degrees
+
+    def __post_init__(self):
+        self.dg_table = _f64(self.dg_table, "dg_table")
+        self.dg_at_psi = _f64(self.dg_at_psi, "dg_at_psi")
+        if self.dg_table.ndim != 2 or self.dg_table.shape[1] != _lib.NQ or self.dg_at_psi.shape != (self.dg_table.shape[0],):
+            raise ValueError(f"dg_table must be (ncol, {_lib.NQ}) and dg_at_psi (ncol,)")
+        if self.dmla is not None:
+            self.dmla = _f64(self.dmla, "dmla")
+            if self.dmla.shape != self.dg_at_psi.shape:
+                raise ValueError("dmla must be (ncol,)")
+
+    def slice(self, lo, hi):
+        return LeafTangent(self.dg_table[lo:hi], self.dg_at_psi[lo:hi], None if self.dmla is None else self.dmla[lo:hi])
+
+    def c_struct(self):
+        return _lib.CrtLeafTangent(self.dg_table.data_ptr(), self.dg_at_psi.data_ptr(), None if self.dmla is None else self.dmla.data_ptr())
+
+
+def g_dparam(cols: Columns):
+    """``dG / d g_param`` of every column in one launch (``crt_hip_g_dparam_f64``): ``(dg_table (ncol, NQ), dg_at_psi (ncol,))`` at
+    ``_lib.quad_nodes(0.501)`` and at ``cols.psi``; zeros for the parameterless kinds and for ``G_TABLE`` columns."""
+    dev = cols.device
+    dg_table = torch.empty((cols.ncol, _lib.NQ), dtype=torch.float64, device=dev)
+    dg_at_psi = torch.empty((cols.ncol,), dtype=torch.float64, device=dev)
+    c = cols.c_struct()
+    with torch.cuda.device(dev):
+        st = _lib.load().crt_hip_g_dparam_f64(ctypes.byref(c), dg_table.data_ptr(), dg_at_psi.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(st, "crt_hip_g_dparam_f64")
+    return dg_table, dg_at_psi
+
+
+def leaf_tangent(cols: Columns, wrt="param"):
+    """The :class:`LeafTangent` of a unit step of one leaf-angle parameter of every column.
+
+    ``"param"``: ``g_param`` (the ellipsoidal ``x``, Bonan's ``chi_l``) by :func:`g_dparam`, ``dmla = 0``.
+    ``"mla"``: the mean leaf angle in degrees of ellipsoidal columns whose ``x`` is tied to it by ``leaf_angle.mla_to_x_approx``:
+    :func:`g_dparam` times ``dx / dmla = -(x + 3) / (1.65 mla)``, with ``dmla = 1``.
+    ``"a"``, ``"b"``: the coefficients of ``LeafPDF.trig(a, b)`` columns.  G and the mean leaf angle are linear in the PDF, so the
+    tangent is the difference of two :func:`leaf_pdf_tables` results (``trig(1, 0)`` resp. ``trig(0, 1)`` against ``trig(0, 0)``), exact to
+    rounding and the same for every ``(a, b)``."""
+    if wrt not in LEAF_WRT:
+        raise ValueError(f"wrt must be one of {LEAF_WRT}, got {wrt!r}")
+    if wrt in ("a", "b"):
+        from .leaf_angle import PDF_TRIG
+
+        kind = torch.full((cols.ncol,), PDF_TRIG, dtype=torch.int32, device=cols.device)
+        step = torch.zeros((cols.ncol, 2), dtype=torch.float64, device=cols.device)
+        t0, p0, m0 = leaf_pdf_tables(kind, step, psi=cols.psi)
+        step[:, 0 if wrt == "a" else 1] = 1.0
+        t1, p1, m1 = leaf_pdf_tables(kind, step, psi=cols.psi)
+        return LeafTangent(t1 - t0, p1 - p0, m1 - m0)
+    dg_table, dg_at_psi = g_dparam(cols)
+    if wrt == "param":
+        return LeafTangent(dg_table, dg_at_psi)
+    if cols.mla is None:
+        raise ValueError("wrt='mla' needs cols.mla")
+    dx = -(cols.g_param + 3.0) / (1.65 * cols.mla)
+    return LeafTangent(dg_table * dx[:, None], dg_at_psi * dx, torch.ones_like(cols.mla))
+
+
+def levels_dleaf_workspace_bytes(scheme, ncol, nz, nb, nsel):
+    """Device workspace of a :class:`LevelsDleafPlan` call: the records of :func:`workspace_bytes` at the same offsets, then a side
+    record per column (the tangents of the record entries)."""
+    return int(_lib.load().crt_hip_levels_dleaf_workspace_bytes(_lib.SCHEME_IDS[scheme], ncol, nz, nb, nsel))
+
+
+class LevelsDleafPlan(_SolvePlan):
+    """Pre-validated derivative of the level spectra along a leaf-angle direction (``crt_hip_levels_dleaf_f64``): ``out[k][c, r, b]`` is
+    the exact derivative of ``X[c, levels[r], b]`` (``X`` in ``keys``, any of ``I_dr, I_df_d, I_df_u, F``: what :class:`LevelsPlan`
+    returns) along ``tangent`` (:class:`LeafTangent`, e.g. from :func:`leaf_tangent`), each ``(ncol, nsel, nb)`` float64; the sun angle,
+    the LAI and the optics are fixed.  One column precompute, one side precompute and one kernel; no finite differences.  Schemes:
+    ``DLEAF_SCHEMES`` (``4s`` and ``zq_pa`` are a ValueError; n79 / zq beyond ``_lib.DLAI_MAX_NZ`` levels a RuntimeError from the call).
+    ``FLAG_SKIP_PRECOMPUTE`` is valid only on a workspace a call of this plan has filled.  A column's result is bitwise the same alone
+    or in any batch, for any subset of ``keys`` and of ``levels``."""
+
+    _bad_dleaf_scheme = "scheme {!r} has no leaf-angle-derivative kernel; served: " + ", ".join(DLEAF_SCHEMES)
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, levels, tangent: LeafTangent, *, keys=DLEAF_KEYS, mu_s=0.501,
+                 tau_d_method="quad", out=None, workspace=None):
+        keys = self._check_dleaf(scheme, tau_d_method, keys)
+        if not isinstance(tangent, LeafTangent):
+            raise TypeError("tangent must be a LeafTangent")
+        if bands.dtype != torch.float64:
+            raise TypeError("the leaf-angle derivative has no f32 storage form: bands must be float64")
+        if tangent.dg_table.shape[0] != cols.ncol or tangent.dg_table.device != cols.device:
+            raise ValueError("the tangent must have the columns' ncol and device")
+        self.levels, self.keys, self.tangent = normalize_levels(levels, cols.nz), keys, tangent
+        self._bind(scheme, cols, bands, mu_s, tau_d_method)
+        shape = (cols.ncol, len(self.levels), bands.nb)
+        out = _outputs({k: shape for k in keys}, out, torch.float64, cols.device, "output {!r}", lacks=True)
+        self.out = {k: out[k] for k in keys}
+        self._out = _lib.CrtDlaiOut(*[out[k].data_ptr() if k in keys else None for k in DLEAF_KEYS])
+        self._lev = (ctypes.c_int32 * len(self.levels))(*self.levels)
+        self._tan = tangent.c_struct()
+        need = levels_dleaf_workspace_bytes(scheme, cols.ncol, cols.nz, bands.nb, len(self.levels))
+        self._finish("crt_hip_levels_dleaf_f64", need, workspace)
+
+    @classmethod
+    def _check_dleaf(cls, scheme, tau_d_method="quad", keys=DLEAF_KEYS, **_):
+        """The checks that need neither a column nor a device: scheme, method, keys.  -> keys"""
+        cls._check_options(cls, scheme, tau_d_method)
+        if scheme not in DLEAF_SCHEMES:
+            raise ValueError(cls._bad_dleaf_scheme.format(scheme))
+        return _level_keys(keys)
+
+    def _tail(self):
+        return self._lev, len(self.levels), ctypes.byref(self._tan), ctypes.byref(self._out)
+
+
+def solve_levels_dleaf(scheme, cols: Columns, bands: Bands, levels, tangent: LeafTangent, **kw):
+    """One-shot :class:`LevelsDleafPlan`: ``{key: (ncol, nsel, nb)}`` at the sorted levels ``normalize_levels(levels, nz)``."""
+    LevelsDleafPlan._check_dleaf(scheme, **kw)  # (before any device is touched)
+    with torch.cuda.device(cols.device):
+        return LevelsDleafPlan(scheme, cols, bands, levels, tangent, **kw)()
+
+
+def sensor_dleaf(scheme, cols: Columns, bands: Bands, levels, tangent: LeafTangent, sensors: SensorSet, **kw):
+    """The leaf-angle derivative of :class:`SensorLevelsPlan`'s sums: per key ``(ncol, nsel, nsens)`` with
+    ``out[c, r, s] = sum_b w_s[b] * dX[c, r, b]``.  ``dX`` comes from one :class:`LevelsDleafPlan` call (``kw`` goes there); the
+    contraction with the sensor set's dense weights runs in torch on the device, as in :func:`sensor_dlai`."""
+    if not isinstance(sensors, SensorSet):
+        raise TypeError("sensors must be a SensorSet")
+    LevelsDleafPlan._check_dleaf(scheme, **kw)
+    sensors.check(bands.nb, cols.device)
+    d = solve_levels_dleaf(scheme, cols, bands, levels, tangent, **kw)
+    w = torch.as_tensor(sensors.dense(bands.nb)).to(cols.device)
+    return {k: torch.einsum("crb,sb->crs", v, w) for k, v in d.items()}

@@ -730,6 +730,68 @@ int crt_hip_dtau_d_f64(const double* kb_nodes, const double* L, int64_t n, int32
   return crt::launch_dtau_d(kb_nodes, L, (long long)n, method, out, static_cast<hipStream_t>(stream));
 }
 
+// ------------------------------------------------------------------------------------------
+// Leaf-angle derivative of the level spectra (include/crt1d_hip_dleaf.h): the checks of crt_hip_levels_dlai_f64, K0, the side precompute,
+// one kernel (dleaf.hip; n79 / zq: k_dlai_tri of dlai.hip on the side record written here).
+
+static size_t dleaf_side_bytes(int scheme, int32_t ncol, int32_t nz) {
+  return (size_t)ncol * (size_t)dleaf_side_len(scheme, nz) * sizeof(double);
+}
+
+size_t crt_hip_levels_dleaf_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nsel) {
+  if (nsel < 1 || nsel > CRT_MAX_LEVEL_SELECT) return 0;
+  const size_t rec = crt_hip_workspace_bytes_nb(scheme, ncol, nz, nb);
+  return rec == 0 ? 0 : rec + dleaf_side_bytes(scheme, ncol, nz);
+}
+
+int crt_hip_levels_dleaf_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
+                             int32_t nsel, const crt_leaf_tangent* tangent, const crt_dlai_out* out, void* workspace,
+                             size_t workspace_bytes, crt_stream_t stream) {
+  if (!scheme_ok(scheme) || !cols || !levels || !out || !tangent) return CRT_ERR_BAD_ARG;
+  if (!tangent->dg_table || !tangent->dg_at_psi) return CRT_ERR_BAD_ARG;
+  if (!out->I_dr && !out->I_df_d && !out->I_df_u && !out->F) return CRT_ERR_BAD_ARG;
+  LevArgs la = {};
+  if (const int st = parse_levels(cols, levels, nsel, la)) return st;
+  SolveOpts o;
+  const crt_outputs none = {};
+  const bool sized = cols->ncol > 0 && cols->nz > 0;
+  const size_t side_bytes = sized ? dleaf_side_bytes(scheme, cols->ncol, cols->nz) : 0;
+  const int chk = check_solve(scheme, cols, bands, opts, &none, workspace, workspace_bytes, nullptr, &la, nullptr, o, side_bytes);
+  if (chk == CRT_ERR_BAD_ARG || chk == CRT_ERR_SHAPE) return chk;  // an argument error is one for every scheme
+  if (scheme == CRT_SCHEME_4S || scheme == CRT_SCHEME_ZQ_PA) return CRT_ERR_UNSUPPORTED;  // whatever the workspace
+  if (chk != CRT_OK) return chk;
+  ColArgs ca;
+  SolveArgs sa;
+  build_args(scheme, cols, bands, &none, workspace, 0, o, ca, sa);
+  double* const side = reinterpret_cast<double*>(static_cast<char*>(workspace) + crt_hip_workspace_bytes_nb(scheme, cols->ncol, cols->nz, bands->nb));
+  const DlaiArgs da = {{out->I_dr, out->I_df_d, out->I_df_u, out->F}, side};
+  const DleafTan tn = {tangent->dg_table, tangent->dg_at_psi, tangent->dmla};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (const int st = launch_dleaf(scheme, sa, la, da, s, true)) return st;  // a shape that is not served: before K0 has written anything
+  if (!(o.flags & CRT_FLAG_SKIP_PRECOMPUTE)) {
+    if (const int st = launch_colpre(ca, s)) return st;
+    if (const int st = launch_dleaf_side(ca, tn, side, s)) return st;
+  }
+  if (o.flags & CRT_FLAG_PRECOMPUTE_ONLY) {
+    note_kernel("k_colpre + k_dleaf_side");
+    return CRT_OK;
+  }
+  return launch_dleaf(scheme, sa, la, da, s, false);
+}
+
+int crt_hip_g_dparam_f64(const crt_columns* cols, double* dg_table, double* dg_at_psi, crt_stream_t stream) {
+  if (!cols || !dg_table || !dg_at_psi || !cols->psi || !cols->g_kind || cols->ncol <= 0) return CRT_ERR_BAD_ARG;
+  return crt::launch_g_dparam(cols->ncol, cols->psi, cols->g_kind, cols->g_param, dg_table, dg_at_psi, static_cast<hipStream_t>(stream));
+}
+
+int crt_hip_dtau_d_dleaf_f64(const double* kb_nodes, const double* dkb_nodes, const double* L, int64_t n, int32_t method, double* out,
+                             crt_stream_t stream) {
+  if (!kb_nodes || !dkb_nodes || !L || !out || n < 0) return CRT_ERR_BAD_ARG;
+  if (method != CRT_TAU_D_QUAD && method != CRT_TAU_D_9SKY) return CRT_ERR_BAD_ARG;
+  if (n == 0) return CRT_OK;
+  return crt::launch_dtau_d_dleaf(kb_nodes, dkb_nodes, L, (long long)n, method, out, static_cast<hipStream_t>(stream));
+}
+
 int crt_hip_bandsum_finish_f64(const crt_columns* cols, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream) {
   if (!cols || !out || !cols->psi || ngroup <= 0 || ngroup > INT_MAXG) return CRT_ERR_BAD_ARG;
   if (!out->aI || !out->aI_sl || !out->aI_sh || !out->I_dr || !out->I_df_d || !out->I_df_u || !out->F || !out->I_d) return CRT_ERR_BAD_ARG;

@@ -31,9 +31,10 @@ struct QuadConst {
   double cs9[CRT_NQ_9SKY], sn9[CRT_NQ_9SKY], sc9[CRT_NQ_9SKY];
 };
 
-// copies of the tables in the other units that read them (solve_closed.hip, dlai.hip); called by init_quadrature once per device
+// copies of the tables in the other units that read them (solve_closed.hip, dlai.hip, dleaf.hip); called by init_quadrature once per device
 int upload_quad_closed(const QuadConst& h, hipStream_t s);
 int upload_quad_dlai(const QuadConst& h, hipStream_t s);  // dlai.hip (the side precompute, k_dtau_d)
+int upload_quad_dleaf(const QuadConst& h, hipStream_t s);  // dleaf.hip (the side precompute, k_g_dparam, k_dtau_d_dleaf)
 
 namespace {
 

@@ -522,11 +522,12 @@ int init_quadrature(hipStream_t s) {
   std::lock_guard<std::mutex> lk(dev_mu);
   if (!dev_inited[dev]) {
     // first call on this device only; not capturable into a hipGraph (documented in DESIGN.md).  Every unit whose kernels read the
-    // tables has its own copy (col_record.hpp): this one (k_colpre, k_tau_d), solve_closed.hip (the 2s k_pipe's record prologue) and dlai.hip.
+    // tables has its own copy (col_record.hpp): this one (k_colpre, k_tau_d), solve_closed.hip (the 2s k_pipe's record prologue), dlai.hip and dleaf.hip.
     if (hipMemcpyToSymbolAsync(HIP_SYMBOL(qc), &h_qc, sizeof(QuadConst), 0, hipMemcpyHostToDevice, s) != hipSuccess)
       return CRT_ERR_LAUNCH;
     if (upload_quad_closed(h_qc, s) != CRT_OK) return CRT_ERR_LAUNCH;
     if (upload_quad_dlai(h_qc, s) != CRT_OK) return CRT_ERR_LAUNCH;
+    if (upload_quad_dleaf(h_qc, s) != CRT_OK) return CRT_ERR_LAUNCH;
     if (hipStreamSynchronize(s) != hipSuccess) return CRT_ERR_LAUNCH;
     dev_inited[dev] = true;
   }

@@ -9,6 +9,7 @@
 
 #include "crt1d_hip.h"
 #include "crt1d_hip_dlai.h"
+#include "crt1d_hip_dleaf.h"
 #include "crt1d_hip_jac.h"
 #include "crt1d_hip_sensor.h"
 
@@ -963,6 +964,26 @@ static_assert(dlai_tri_lanes(CRT_SCHEME_N79, 292) == 64 && dlai_tri_lanes(CRT_SC
 int launch_dlai_side(const ColArgs& ca, double* side, hipStream_t s);
 int launch_dlai(int scheme, const SolveArgs& a, const LevArgs& la, const DlaiArgs& da, hipStream_t s, bool probe);
 int launch_dtau_d(const double* kb_nodes, const double* L, long long n, int method, double* out, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------
+// Leaf-angle derivative of the level spectra (crt_hip_levels_dleaf_f64, include/crt1d_hip_dleaf.h; kernels in dleaf.hip, n79 / zq through
+// launch_dlai on the side record written here)
+struct DleafTan {
+  const double* dg_table;   // [ncol][CRT_NQ]
+  const double* dg_at_psi;  // [ncol]
+  const double* dmla;       // [ncol] or nullptr
+};
+// doubles of a column's side record: the tangent of the header and of every vector entry the scheme's kernel reads, in the layout of the
+// record part that kernel stages (bl: its tau_d vector alone follows the header)
+constexpr int dleaf_side_len(int scheme, int nz) {
+  return scheme == CRT_SCHEME_BL ? REC_HDR + nz : (scheme == CRT_SCHEME_N79 || scheme == CRT_SCHEME_ZQ) ? jac_tri_nrec(scheme, nz) : REC_HDR;
+}
+static_assert(dleaf_side_len(CRT_SCHEME_N79, 7) == dlai_side_len(CRT_SCHEME_N79, 7) && dleaf_side_len(CRT_SCHEME_ZQ, 7) == dlai_side_len(CRT_SCHEME_ZQ, 7),
+              "k_dlai_tri reads either side record");
+int launch_dleaf_side(const ColArgs& ca, const DleafTan& tn, double* side, hipStream_t s);
+int launch_dleaf(int scheme, const SolveArgs& a, const LevArgs& la, const DlaiArgs& da, hipStream_t s, bool probe);
+int launch_g_dparam(int ncol, const double* psi, const int32_t* g_kind, const double* g_param, double* dg_table, double* dg_at_psi, hipStream_t s);
+int launch_dtau_d_dleaf(const double* kb_nodes, const double* dkb_nodes, const double* L, long long n, int method, double* out, hipStream_t s);
 
 // launchers implemented in the .hip files
 int launch_colpre(const ColArgs& a, hipStream_t s);

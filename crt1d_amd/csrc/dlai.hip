@@ -22,32 +22,12 @@
 namespace crt {
 namespace {
 
-using DBand = JBandT<double>;
 struct D2s : J2sT<double, Du> {};
 struct DBl : JBlT<double, Du> {};
 template <bool BF>
 struct DG77 : JG77T<BF, double, Du> {};
 struct DN79 : JN79T<double, Du> {};
 struct DZq : JZqT<double, Du> {};
-
-__device__ __forceinline__ DBand load_dband(const SolveArgs& a, int c, int b, bool soil) {
-  const long long i = (long long)c * a.col_stride + b;
-  DBand in;
-  in.I_dr0 = static_cast<const double*>(a.I_dr0)[i];
-  in.I_df0 = static_cast<const double*>(a.I_df0)[i];
-  in.r = static_cast<const double*>(a.leaf_r)[i];
-  in.t = static_cast<const double*>(a.leaf_t)[i];
-  in.s = soil ? static_cast<const double*>(a.soil_r)[i] : 0.0;
-  return in;
-}
-
-// dI = I_dr' of the row: I_dr0 (e^{-K_b L_j})'
-__device__ __forceinline__ void dlai_store(const DlaiArgs& da, long long o, double dI, double invmu, Du dn, Du up) {
-  if (da.o[0]) da.o[0][o] = dI;
-  if (da.o[1]) da.o[1][o] = dn.d;
-  if (da.o[2]) da.o[2][o] = up.d;
-  if (da.o[3]) da.o[3][o] = __builtin_fma(dI, invmu, 2 * (up.d + dn.d));  // F = I_dr / mu + 2 (up + dn)
-}
 
 // ------------------------------------------------------------------------------------------
 // tau_d' on the rules of tau_d_quad / tau_d_9sky (colpre.hip): the integrand factor e^{-K_b L} becomes -K_b e^{-K_b L}

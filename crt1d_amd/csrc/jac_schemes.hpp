@@ -1,7 +1,9 @@
-// The per-band maths of the schemes on Du, a value with ONE tangent, written once for the two forward-mode kernel families:
+// The per-band maths of the schemes on Du, a value with ONE tangent, written once for the three forward-mode kernel families:
 //   jac.hip   d / d (leaf_r, leaf_t, soil_r):  the optics carry the tangent (P = Du), the column record is plain (R = double);
 //             zq excepted, which keeps its own struct there (its kernel is held to the code it had)
 //   dlai.hip  d / d s of lai(s) = s lai:       the optics are plain (P = double), the record entries carry the tangent (R = Du)
+//   dleaf.hip d along a leaf-angle direction:  as dlai.hip, and the header scalars K_b, mu_bar, cos^2 of the closed forms carry one too
+//             (H = Du) while the LAI entries L_j, LT do not (LaiT)
 // Every local is `auto`: an expression has the type its operands give it, so that with (P, R) = (Du, double) each line is the operation
 // the optics Jacobian has always performed.  The scheme objects of the solve kernels (Sch2s, TriZq, ...) are not touched.
 #pragma once
@@ -25,6 +27,21 @@ __device__ __forceinline__ R seed_lai(double L) {
     return Du{L, L};
   else
     return L;
+}
+// the type of the LAI entries L_j, LT: they scale with s (R) but do not depend on the leaf angles
+template <class R, class H>
+using LaiT = std::conditional_t<std::is_same_v<H, Du>, double, R>;
+// what depends on the optics (P) or on the header scalars (H)
+template <class P, class H>
+using PorH = std::conditional_t<std::is_same_v<P, Du> || std::is_same_v<H, Du>, Du, double>;
+// header scalar i as H; H = Du: the tangent lies HDR_TAN doubles behind the value (the kernel stages both)
+constexpr int HDR_TAN = 2 * REC_HDR;
+template <class H>
+__device__ __forceinline__ H hdr(const double* hd, int i) {
+  if constexpr (std::is_same_v<H, Du>)
+    return Du{hd[i], hd[HDR_TAN + i]};
+  else
+    return hd[i];
 }
 template <class T>
 __device__ __forceinline__ T cst(double v) {
@@ -124,8 +141,9 @@ struct RecV<Du> {
 // the two diffuse streams at a level with cumulative LAI L and beam fraction eK = e^{-K_b L}.
 
 // 2s  Dickinson-Sellers two-stream (crt1d/solvers/_solve_2s.py:54-156)
-template <class P, class R>
+template <class P, class R, class H = double>
 struct J2sT {
+  using LT_t = LaiT<R, H>;
   static constexpr const char* NAME = "2s";
   static constexpr bool SOIL = true;
   // up/dn = A E(L) + B e^{-hL} + C e^{+hL} with E(L) = (e^{-K_b L} - e^{-hL}) / sigma, sigma = mu_bar^2 (K_b^2 - h^2) (:85).  The reference
@@ -133,17 +151,19 @@ struct J2sT {
   //   E(L) = -e^{-hL} (L / mu_bar) phi(-delta L) g,   g = 1 / (mu_bar (K_b + h)),
   // and the sigma-proportional parts of the reference's h2, h3, h5, h6 (:99-120) are taken out the same way through
   // S2 - S1 = -delta LT S1 phi(-delta LT)  (S1 = e^{-h LT}, S2 = e^{-K_b LT}).  Same function, no removable singularity at K_b = h.
-  P h, delta, Au, Ad;
+  PorH<P, H> h, delta, Au, Ad;
   Du Bu, Cu, Bd, Cd;
-  double imb;
+  H imb;
   __device__ inline void init(const double* hd, const JBandT<P>& in, R) {
-    const double K = hd[S_KB], mu = hd[S_MU], mb = hd[S_MUBAR], cos2 = hd[S_COS2];
-    const R LT = seed_lai<R>(hd[S_LT]);
+    const H K = hdr<H>(hd, S_KB);
+    const double mu = hd[S_MU];
+    const H mb = hdr<H>(hd, S_MUBAR), cos2 = hdr<H>(hd, S_COS2);
+    const LT_t LT = seed_lai<LT_t>(hd[S_LT]);
     const auto al = in.r, ta = in.t, rs = in.s;
     const auto om = al + ta;                                              // :65
     const auto beta = 0.5 * (om + (al - ta) * cos2) / om;                 // :68
     const auto a_s = om * (0.5 * (1 - mu * log((mu + 1) / mu)));          // :73
-    const double mbK = mb * K;
+    const auto mbK = mb * K;
     const auto beta0 = (1 + mbK) / (om * mbK) * a_s;                      // :76
     const auto b = 1 - (1 - beta) * om;                                   // :80
     const auto c = om * beta;
@@ -183,7 +203,7 @@ struct J2sT {
     Bd = in.I_dr0 * h5 + in.I_df0 * h9;
     Cd = in.I_dr0 * h6 + in.I_df0 * h10;
   }
-  __device__ inline void level(R L, R, Du& dn, Du& up) const {
+  __device__ inline void level(LT_t L, R, Du& dn, Du& up) const {
     const Du em = dexp(-(h * L));
     const Du ep = 1.0 / em;
     const Du E = -(em * (L * imb) * dphi(-(delta * L)));
@@ -194,17 +214,17 @@ struct J2sT {
 
 // bl  Beer-Lambert (crt1d/solvers/_solve_bl.py:51-90): no soil, no upward stream; the sky-diffuse term I_df0 tau_d(L) has no tangent
 // with respect to the optics (the LAI derivative adds its own, dlai.hip)
-template <class P, class R>
+template <class P, class R, class H = double>
 struct JBlT {
   static constexpr const char* NAME = "bl";
   static constexpr bool SOIL = false;
-  P Kg;
+  PorH<P, H> Kg;
   double I_dr0;
   __device__ inline void init(const double* hd, const JBandT<P>& in, R) {
-    Kg = hd[S_KB] * dsqrt(1 - (in.t + in.r));                           // :58-62
+    Kg = hdr<H>(hd, S_KB) * dsqrt(1 - (in.t + in.r));                   // :58-62
     I_dr0 = in.I_dr0;
   }
-  __device__ inline void level(R L, R eK, Du& dn, Du& up) const {
+  __device__ inline void level(LaiT<R, H> L, R eK, Du& dn, Du& up) const {
     const Du tg = dexp(-(Kg * L));                                      // :65
     dn = 0.5 * (I_dr0 * (tg - eK));                                     // :70,74,79
     up = mk(0.0);                                                       // :87
@@ -212,17 +232,19 @@ struct JBlT {
 };
 
 // g77 Goudriaan 1977 (crt1d/solvers/_solve_g77.py:48-124) and bf Bodin & Franklin (crt1d/solvers/_solve_bf.py:60-140)
-template <bool BF, class P, class R>
+template <bool BF, class P, class R, class H = double>
 struct JG77T {
   static constexpr const char* NAME = BF ? "bf" : "g77";
   static constexpr bool SOIL = true;
-  double kb, I_dr0, I_df0;
-  R LT;
+  using LT_t = LaiT<R, H>;
+  H kb;
+  double I_dr0, I_df0;
+  LT_t LT;
   P r, t, kp, kd, omr, oms;
   Du gnd;
   __device__ inline void init(const double* hd, const JBandT<P>& in, R A0) {
-    kb = hd[S_KB];
-    LT = seed_lai<R>(hd[S_LT]);
+    kb = hdr<H>(hd, S_KB);
+    LT = seed_lai<LT_t>(hd[S_LT]);
     const double mu = hd[S_MU];
     I_dr0 = in.I_dr0;
     I_df0 = in.I_df0;
@@ -233,7 +255,7 @@ struct JG77T {
     const auto rho_c = ((1 - kp) / (1 + kp)) * (2 / (1 + 1.6 * mu));      // :66
     omr = BF ? cst<P>(1.0) : 1 - rho_c;                                 // bf:84 drops (1 - rho_c)
     kd = 0.8 * kp;                                                      // :69
-    const Du ed0 = dexp(-(kd * LT));
+    const Du ed0 = to_du(dexp(-(kd * LT)));
     const Du Idf0 = I_df0 * omr * ed0;
     Du Iscd0;
     if (BF)
@@ -242,9 +264,9 @@ struct JG77T {
       Iscd0 = 0.5 * (I_dr0 * omr * dexp(-(kp * (kb * LT))) - I_dr0 * oms * A0);
     gnd = in.s * (I_dr0 * A0 + Idf0 + Iscd0);                           // g77:95, bf:112
   }
-  __device__ inline void level(R L, R Asl, Du& dn, Du& up) const {
-    const Du ed = dexp(-(kd * L));
-    const Du er = dexp(-(kd * (LT - L)));
+  __device__ inline void level(LT_t L, R Asl, Du& dn, Du& up) const {
+    const Du ed = to_du(dexp(-(kd * L)));
+    const Du er = to_du(dexp(-(kd * (LT - L))));
     const Du Idf = I_df0 * omr * ed;                                    // g77:73 / bf:84
     Du Iscd, Iscu;
     if (BF) {
@@ -446,6 +468,29 @@ struct JZqT {
     xu = xul;
   }
 };
+
+// ------------------------------------------------------------------------------------------
+// shared by the kernels whose optics are plain and whose outputs are the four level quantities (dlai.hip, dleaf.hip)
+using DBand = JBandT<double>;
+
+__device__ __forceinline__ DBand load_dband(const SolveArgs& a, int c, int b, bool soil) {
+  const long long i = (long long)c * a.col_stride + b;
+  DBand in;
+  in.I_dr0 = static_cast<const double*>(a.I_dr0)[i];
+  in.I_df0 = static_cast<const double*>(a.I_df0)[i];
+  in.r = static_cast<const double*>(a.leaf_r)[i];
+  in.t = static_cast<const double*>(a.leaf_t)[i];
+  in.s = soil ? static_cast<const double*>(a.soil_r)[i] : 0.0;
+  return in;
+}
+
+// dI = I_dr' of the row: I_dr0 (e^{-K_b L_j})'
+__device__ __forceinline__ void dlai_store(const DlaiArgs& da, long long o, double dI, double invmu, Du dn, Du up) {
+  if (da.o[0]) da.o[0][o] = dI;
+  if (da.o[1]) da.o[1][o] = dn.d;
+  if (da.o[2]) da.o[2][o] = up.d;
+  if (da.o[3]) da.o[3][o] = __builtin_fma(dI, invmu, 2 * (up.d + dn.d));  // F = I_dr / mu + 2 (up + dn)
+}
 
 }  // namespace
 }  // namespace crt

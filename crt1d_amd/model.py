@@ -343,6 +343,26 @@ class Model:
         out = batched.solve_levels_dlai(scheme, cols, b, (0, -1) if levels is None else levels, per=per)
         return {k: v[0].cpu().numpy() for k, v in out.items()}
 
+    def run_leaf_angle_sensitivity(self, levels=None, wrt="param"):
+        """The exact derivative of the rows ``levels`` (default: the ground and the top) of ``I_dr, I_df_d, I_df_u, F`` with respect to
+        one leaf-angle parameter of this case (:class:`crt1d_amd.batched.LevelsDleafPlan` along ``batched.leaf_tangent(cols, wrt)``;
+        ``wrt``: ``"param"``, ``"mla"``, ``"a"``, ``"b"``): NumPy arrays ``(nsel, n_wl)`` per key.  ValueError for a scheme without the
+        kernel (``4s``, ``zq_pa``) and for any other ``wrt``.  The model's own state (``out``) is not changed."""
+        from . import batched
+
+        self._check_inputs()
+        p = self._p
+        scheme, cols, b, sun = self._series_inputs(np.atleast_1d(float(p["psi"])), None, None, "leaf-angle sensitivity")
+        if scheme not in batched.DLEAF_SCHEMES:
+            raise ValueError(f"scheme {scheme!r} has no leaf-angle-derivative kernel")
+        if wrt not in batched.LEAF_WRT:
+            raise ValueError(f"wrt must be one of {batched.LEAF_WRT}, got {wrt!r}")
+        cols = batched.Columns(psi=sun.psi[:, 0].contiguous(), lai=cols.lai, g_kind=cols.g_kind, g_param=cols.g_param, mla=cols.mla,
+                               g_at_psi=None if sun.g_at_psi is None else sun.g_at_psi[:, 0].contiguous(), g_table=cols.g_table)
+        b = batched.Bands(sun.I_dr0[:, 0].contiguous(), sun.I_df0[:, 0].contiguous(), b.leaf_r, b.leaf_t, b.soil_r)
+        out = batched.solve_levels_dleaf(scheme, cols, b, (0, -1) if levels is None else levels, batched.leaf_tangent(cols, wrt))
+        return {k: v[0].cpu().numpy() for k, v in out.items()}
+
     # ---- output container -------------------------------------------------------------------
     def _scheme_absorption_vars(self, nz):
         """The scheme's own absorption outputs (``aI*_scheme``): on levels or on layers, by their leading size."""
