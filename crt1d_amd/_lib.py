@@ -273,7 +273,8 @@ def _sensor_signatures():
 _SENSOR_SIGNATURES = _sensor_signatures()
 SENSOR_EXPORTS = list(_SENSOR_SIGNATURES)
 
-# optical-property Jacobians of the level spectra (include/crt1d_hip_jac.h), again a header and a table of their own
+# optical-property Jacobians of the level spectra (include/crt1d_hip_jac.h), again a header and a table of their own.  This and the two
+# derivative entries below run one host path in the library (api.hip: levels_deriv_impl) and one plan base (batched._LevelsDerivPlan).
 JAC_NPARAM = 3  # CRT_JAC_NPARAM: leaf_r, leaf_t, soil_r
 JAC_MAX_NZ = {"n79": 1076, "zq": 1200}  # CRT_JAC_MAX_NZ_N79, CRT_JAC_MAX_NZ_ZQ
 

@@ -1005,11 +1005,11 @@ def normalize_levels(levels, nz):
     return tuple(sorted(out))
 
 
-def _level_keys(keys):
-    """The profile selection of the level plans as a tuple of distinct names out of ``LEVEL_KEYS``."""
+def _level_keys(keys, allowed=LEVEL_KEYS):
+    """The profile selection of the level plans as a tuple of distinct names out of ``allowed``."""
     keys = (keys,) if isinstance(keys, str) else tuple(keys)
-    if not keys or any(k not in LEVEL_KEYS for k in keys) or len(set(keys)) != len(keys):
-        raise ValueError(f"keys must be distinct names out of {LEVEL_KEYS}, got {keys!r}")
+    if not keys or any(k not in allowed for k in keys) or len(set(keys)) != len(keys):
+        raise ValueError(f"keys must be distinct names out of {allowed}, got {keys!r}")
     return keys
 
 
@@ -1290,6 +1290,66 @@ def sensor_albedo(scheme, cols: Columns, bands: Bands, sensors: SensorSet, **kw)
     return r["I_df_u"][:, 0] / (r["I_dr"][:, 0] + r["I_df_d"][:, 0])
 
 
+# ---- derivatives of the level spectra: what the Jacobian, the LAI derivative and the leaf-angle derivative share -------------------------
+
+
+def _levels_deriv_workspace_bytes(query, scheme, ncol, nz, nb, nsel):
+    return int(getattr(_lib.load(), query)(_lib.SCHEME_IDS[scheme], ncol, nz, nb, nsel))
+
+
+class _LevelsDerivPlan(_SolvePlan):
+    """What the three derivative plans share: one construction sequence and one argument tail.  A subclass names its C entry
+    (``_entry_name``), its workspace query (``_ws_query``), its output struct (``_out_struct``, a name of ``_lib``) with the keys of its
+    slots (``_all_keys``), the schemes it serves (``_schemes``) and how its messages call it (``_no_kernel``, ``_what``); its own arguments
+    go through ``_check_extras(**kw)`` (what needs neither a column nor a device) and ``_bind_extras(cols, **extras)``."""
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, levels, *, keys=None, mu_s=0.501, tau_d_method="quad", out=None, workspace=None,
+                 **extras):
+        keys = self._check_static(scheme, tau_d_method, keys, **extras)
+        if bands.dtype != torch.float64:
+            raise TypeError(f"the {self._what} has no f32 storage form: bands must be float64")
+        self._bind_extras(cols, **extras)
+        self.levels, self.keys = normalize_levels(levels, cols.nz), keys
+        self._bind(scheme, cols, bands, mu_s, tau_d_method)
+        shape = (cols.ncol, len(self.levels), *self._mid, bands.nb)
+        out = _outputs({k: shape for k in keys}, out, torch.float64, cols.device, "output {!r}", lacks=True)
+        self.out = {k: out[k] for k in keys}
+        self._out = getattr(_lib, self._out_struct)(*[out[k].data_ptr() if k in keys else None for k in self._all_keys])
+        self._lev = (ctypes.c_int32 * len(self.levels))(*self.levels)
+        need = _levels_deriv_workspace_bytes(self._ws_query, scheme, cols.ncol, cols.nz, bands.nb, len(self.levels))
+        self._finish(self._entry_name, need, workspace)
+
+    @classmethod
+    def _check_static(cls, scheme, tau_d_method="quad", keys=None, **kw):
+        """The checks that need neither a column nor a device: scheme, method, keys, the plan's own arguments.  -> keys"""
+        cls._check_options(cls, scheme, tau_d_method)
+        if scheme not in cls._schemes:
+            raise ValueError(cls._no_kernel.format(scheme))
+        keys = _level_keys(cls._all_keys if keys is None else keys, cls._all_keys)
+        cls._check_extras(**kw)
+        return keys
+
+    _mid = ()  # output axes between the levels and the bands
+    _check_extras = staticmethod(lambda **_: None)
+    _bind_extras = staticmethod(lambda cols: None)
+
+    def _tail(self):
+        return self._lev, len(self.levels), ctypes.byref(self._out)
+
+
+def _sensor_contract(sensors, cols, bands, spec, before, solve):
+    """What ``sensor_jvp``, ``sensor_dlai`` and ``sensor_dleaf`` share: the SensorSet check, ``before()`` (the caller's checks that touch no
+    device), ``sensors.check``, the derivative ``solve() -> {key: array}`` and the contraction ``spec`` of every array with the set's dense
+    weights, in torch on the device."""
+    if not isinstance(sensors, SensorSet):
+        raise TypeError("sensors must be a SensorSet")
+    before()
+    sensors.check(bands.nb, cols.device)
+    d = solve()
+    w = torch.as_tensor(sensors.dense(bands.nb)).to(cols.device)
+    return {k: torch.einsum(spec, v, w) for k, v in d.items()}
+
+
 # ---- optical-property Jacobians of the level spectra (include/crt1d_hip_jac.h) --------------------------------------------------------
 
 JAC_PARAMS = ("leaf_r", "leaf_t", "soil_r")  # the parameter axis of every Jacobian, in this order
@@ -1297,19 +1357,12 @@ JAC_KEYS = ("I_df_d", "I_df_u", "F")  # I_dr does not depend on the optics
 JAC_SCHEMES = ("2s", "bl", "g77", "bf", "n79", "zq")
 
 
-def _jac_keys(keys):
-    keys = (keys,) if isinstance(keys, str) else tuple(keys)
-    if not keys or any(k not in JAC_KEYS for k in keys) or len(set(keys)) != len(keys):
-        raise ValueError(f"keys must be distinct names out of {JAC_KEYS}, got {keys!r}")
-    return keys
-
-
 def levels_jac_workspace_bytes(scheme, ncol, nz, nb, nsel):
     """Device workspace of a :class:`LevelsJacPlan` call: the records of :func:`workspace_bytes`, at the same offsets."""
-    return int(_lib.load().crt_hip_levels_jac_workspace_bytes(_lib.SCHEME_IDS[scheme], ncol, nz, nb, nsel))
+    return _levels_deriv_workspace_bytes("crt_hip_levels_jac_workspace_bytes", scheme, ncol, nz, nb, nsel)
 
 
-class LevelsJacPlan(_SolvePlan):
+class LevelsJacPlan(_LevelsDerivPlan):
     """Pre-validated Jacobian of the level spectra (``crt_hip_levels_jac_f64``): ``out[k][c, r, p, b]`` is the exact derivative of
     ``X[c, levels[r], b]`` (``X`` in ``keys``, any of ``I_df_d, I_df_u, F``: what :class:`LevelsPlan` returns) with respect to parameter
     ``JAC_PARAMS[p]`` of the SAME column and band -- bands are independent, so this diagonal is the whole Jacobian.  Each array is
@@ -1317,28 +1370,10 @@ class LevelsJacPlan(_SolvePlan):
     ValueError; n79 / zq beyond ``_lib.JAC_MAX_NZ`` levels a RuntimeError from the call).  bl has no soil and no upward stream: those slabs
     are zeros.  A column's result is bitwise the same alone or in any batch, for any subset of ``keys`` and of ``levels``."""
 
-    _bad_jac_scheme = "scheme {!r} has no Jacobian kernel; served: " + ", ".join(JAC_SCHEMES)
-
-    def __init__(self, scheme, cols: Columns, bands: Bands, levels, *, keys=JAC_KEYS, mu_s=0.501, tau_d_method="quad", out=None,
-                 workspace=None):
-        self._check_options(scheme, tau_d_method)
-        if scheme not in JAC_SCHEMES:
-            raise ValueError(self._bad_jac_scheme.format(scheme))
-        keys = _jac_keys(keys)
-        if bands.dtype != torch.float64:
-            raise TypeError("the Jacobian has no f32 storage form: bands must be float64")
-        self.levels, self.keys = normalize_levels(levels, cols.nz), keys
-        self._bind(scheme, cols, bands, mu_s, tau_d_method)
-        shape = (cols.ncol, len(self.levels), _lib.JAC_NPARAM, bands.nb)
-        out = _outputs({k: shape for k in keys}, out, torch.float64, cols.device, "output {!r}", lacks=True)
-        self.out = {k: out[k] for k in keys}
-        self._out = _lib.CrtJacOut(*[out[k].data_ptr() if k in keys else None for k in JAC_KEYS])
-        self._lev = (ctypes.c_int32 * len(self.levels))(*self.levels)
-        need = levels_jac_workspace_bytes(scheme, cols.ncol, cols.nz, bands.nb, len(self.levels))
-        self._finish("crt_hip_levels_jac_f64", need, workspace)
-
-    def _tail(self):
-        return self._lev, len(self.levels), ctypes.byref(self._out)
+    _entry_name, _ws_query, _out_struct = "crt_hip_levels_jac_f64", "crt_hip_levels_jac_workspace_bytes", "CrtJacOut"
+    _all_keys, _schemes, _what = JAC_KEYS, JAC_SCHEMES, "Jacobian"
+    _no_kernel = "scheme {!r} has no Jacobian kernel; served: " + ", ".join(JAC_SCHEMES)
+    _mid = (_lib.JAC_NPARAM,)
 
 
 def solve_levels_jac(scheme, cols: Columns, bands: Bands, levels, **kw):
@@ -1365,28 +1400,26 @@ def sensor_jvp(scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, 
     ``d_soil_r``: ``(ntan, nb)`` (the same directions for every column) or ``(ncol, ntan, nb)``, the derivatives of the three spectra with
     respect to the model's parameters; ``None`` stands for zeros.  The Jacobian ``J`` comes from one :class:`LevelsJacPlan` call
     (``kw`` goes there); the contraction runs in torch on the device."""
-    if not isinstance(sensors, SensorSet):
-        raise TypeError("sensors must be a SensorSet")
-    dirs = [_jvp_direction(d, "d_" + n, cols.ncol, bands.nb, cols.device) for n, d in zip(JAC_PARAMS, (d_leaf_r, d_leaf_t, d_soil_r))]
-    given = [d for d in dirs if d is not None]
-    if not given:
-        raise ValueError("at least one direction must be given")
-    ntan = given[0].shape[1]
-    if any(d.shape[1] != ntan for d in given):
-        raise ValueError("the directions must share ntan")
-    sensors.check(bands.nb, cols.device)
-    jac = solve_levels_jac(scheme, cols, bands, levels, **kw)
-    w = torch.as_tensor(sensors.dense(bands.nb)).to(cols.device)
-    out = {}
-    for k, J in jac.items():
-        t = None
-        for p, d in enumerate(dirs):
-            if d is None:
-                continue
-            term = J[:, :, p, None, :] * d[:, None, :, :]  # (ncol, nsel, ntan, nb)
-            t = term if t is None else t + term
-        out[k] = torch.einsum("crkb,sb->crsk", t, w)
-    return out
+    dirs = {}  # parameter index -> direction
+
+    def check_directions():
+        for p, (n, d) in enumerate(zip(JAC_PARAMS, (d_leaf_r, d_leaf_t, d_soil_r))):
+            if (d := _jvp_direction(d, "d_" + n, cols.ncol, bands.nb, cols.device)) is not None:
+                dirs[p] = d
+        if not dirs:
+            raise ValueError("at least one direction must be given")
+        if len({d.shape[1] for d in dirs.values()}) != 1:
+            raise ValueError("the directions must share ntan")
+
+    def tangents():
+        out = {}
+        for k, J in solve_levels_jac(scheme, cols, bands, levels, **kw).items():
+            for p, d in dirs.items():
+                term = J[:, :, p, None, :] * d[:, None, :, :]  # (ncol, nsel, ntan, nb)
+                out[k] = out[k] + term if k in out else term
+        return out
+
+    return _sensor_contract(sensors, cols, bands, "crkb,sb->crsk", check_directions, tangents)
 
 
 # ---- LAI derivative of the level spectra (include/crt1d_hip_dlai.h) --------------------------------------------------------------------
@@ -1405,10 +1438,10 @@ def _dlai_per(per):
 def levels_dlai_workspace_bytes(scheme, ncol, nz, nb, nsel):
     """Device workspace of a :class:`LevelsDlaiPlan` call: the records of :func:`workspace_bytes` at the same offsets, then the side
     records (the tangents of the record entries; bl, n79, zq)."""
-    return int(_lib.load().crt_hip_levels_dlai_workspace_bytes(_lib.SCHEME_IDS[scheme], ncol, nz, nb, nsel))
+    return _levels_deriv_workspace_bytes("crt_hip_levels_dlai_workspace_bytes", scheme, ncol, nz, nb, nsel)
 
 
-class LevelsDlaiPlan(_SolvePlan):
+class LevelsDlaiPlan(_LevelsDerivPlan):
     """Pre-validated derivative of the level spectra with respect to the leaf area index (``crt_hip_levels_dlai_f64``).  Every column's
     cumulative LAI profile is scaled as ``lai(s) = s * lai`` (the vertical distribution stays fixed); ``out[k][c, r, b]`` is the exact
     derivative of ``X[c, levels[r], b]`` (``X`` in ``keys``, any of ``I_dr, I_df_d, I_df_u, F``: what :class:`LevelsPlan` returns) at
@@ -1418,34 +1451,21 @@ class LevelsDlaiPlan(_SolvePlan):
     ``FLAG_SKIP_PRECOMPUTE`` is valid only on a workspace a call of this plan's entry has filled (the side records).  A column's result
     is bitwise the same alone or in any batch, for any subset of ``keys`` and of ``levels``."""
 
-    _bad_dlai_scheme = "scheme {!r} has no LAI-derivative kernel; served: " + ", ".join(DLAI_SCHEMES)
+    _entry_name, _ws_query, _out_struct = "crt_hip_levels_dlai_f64", "crt_hip_levels_dlai_workspace_bytes", "CrtDlaiOut"
+    _all_keys, _schemes, _what = DLAI_KEYS, DLAI_SCHEMES, "LAI derivative"
+    _no_kernel = "scheme {!r} has no LAI-derivative kernel; served: " + ", ".join(DLAI_SCHEMES)
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, *, keys=DLAI_KEYS, per="log", mu_s=0.501, tau_d_method="quad",
                  out=None, workspace=None):
-        keys, self.per = self._check_dlai(scheme, tau_d_method, keys, per)
-        if bands.dtype != torch.float64:
-            raise TypeError("the LAI derivative has no f32 storage form: bands must be float64")
-        self.levels, self.keys = normalize_levels(levels, cols.nz), keys
-        self._bind(scheme, cols, bands, mu_s, tau_d_method)
-        shape = (cols.ncol, len(self.levels), bands.nb)
-        out = _outputs({k: shape for k in keys}, out, torch.float64, cols.device, "output {!r}", lacks=True)
-        self.out = {k: out[k] for k in keys}
-        self._out = _lib.CrtDlaiOut(*[out[k].data_ptr() if k in keys else None for k in DLAI_KEYS])
-        self._lev = (ctypes.c_int32 * len(self.levels))(*self.levels)
+        super().__init__(scheme, cols, bands, levels, keys=keys, mu_s=mu_s, tau_d_method=tau_d_method, out=out, workspace=workspace, per=per)
+
+    @staticmethod
+    def _check_extras(per="log", **_):
+        _dlai_per(per)
+
+    def _bind_extras(self, cols, per):
+        self.per = per
         self._lai_total = cols.lai[:, 0].contiguous()[:, None, None] if per == "lai" else None
-        need = levels_dlai_workspace_bytes(scheme, cols.ncol, cols.nz, bands.nb, len(self.levels))
-        self._finish("crt_hip_levels_dlai_f64", need, workspace)
-
-    @classmethod
-    def _check_dlai(cls, scheme, tau_d_method="quad", keys=DLAI_KEYS, per="log", **_):
-        """The checks that need neither a column nor a device: scheme, method, keys, ``per``.  -> (keys, per)"""
-        cls._check_options(cls, scheme, tau_d_method)
-        if scheme not in DLAI_SCHEMES:
-            raise ValueError(cls._bad_dlai_scheme.format(scheme))
-        return _level_keys(keys), _dlai_per(per)
-
-    def _tail(self):
-        return self._lev, len(self.levels), ctypes.byref(self._out)
 
     def __call__(self, stream=None, *, flags=0):
         out = super().__call__(stream, flags=flags)
@@ -1459,7 +1479,7 @@ class LevelsDlaiPlan(_SolvePlan):
 
 def solve_levels_dlai(scheme, cols: Columns, bands: Bands, levels, **kw):
     """One-shot :class:`LevelsDlaiPlan`: ``{key: (ncol, nsel, nb)}`` at the sorted levels ``normalize_levels(levels, nz)``."""
-    LevelsDlaiPlan._check_dlai(scheme, **kw)  # (before any device is touched)
+    LevelsDlaiPlan._check_static(scheme, **kw)  # (before any device is touched)
     with torch.cuda.device(cols.device):
         return LevelsDlaiPlan(scheme, cols, bands, levels, **kw)()
 
@@ -1468,13 +1488,8 @@ def sensor_dlai(scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet,
     """The LAI derivative of :class:`SensorLevelsPlan`'s sums: per key ``(ncol, nsel, nsens)`` with
     ``out[c, r, s] = sum_b w_s[b] * dX[c, r, b]``.  ``dX`` comes from one :class:`LevelsDlaiPlan` call (``kw`` goes there, ``per``
     included); the contraction with the sensor set's dense weights runs in torch on the device, as in :func:`sensor_jvp`."""
-    if not isinstance(sensors, SensorSet):
-        raise TypeError("sensors must be a SensorSet")
-    LevelsDlaiPlan._check_dlai(scheme, **kw)
-    sensors.check(bands.nb, cols.device)
-    d = solve_levels_dlai(scheme, cols, bands, levels, **kw)
-    w = torch.as_tensor(sensors.dense(bands.nb)).to(cols.device)
-    return {k: torch.einsum("crb,sb->crs", v, w) for k, v in d.items()}
+    return _sensor_contract(sensors, cols, bands, "crb,sb->crs", lambda: LevelsDlaiPlan._check_static(scheme, **kw),
+                            lambda: solve_levels_dlai(scheme, cols, bands, levels, **kw))
 
 
 # ---- leaf-angle derivative of the level spectra (include/crt1d_hip_dleaf.h) -------------------------------------------------------------
@@ -1555,10 +1570,10 @@ def leaf_tangent(cols: Columns, wrt="param"):
 def levels_dleaf_workspace_bytes(scheme, ncol, nz, nb, nsel):
     """Device workspace of a :class:`LevelsDleafPlan` call: the records of :func:`workspace_bytes` at the same offsets, then a side
     record per column (the tangents of the record entries)."""
-    return int(_lib.load().crt_hip_levels_dleaf_workspace_bytes(_lib.SCHEME_IDS[scheme], ncol, nz, nb, nsel))
+    return _levels_deriv_workspace_bytes("crt_hip_levels_dleaf_workspace_bytes", scheme, ncol, nz, nb, nsel)
 
 
-class LevelsDleafPlan(_SolvePlan):
+class LevelsDleafPlan(_LevelsDerivPlan):
     """Pre-validated derivative of the level spectra along a leaf-angle direction (``crt_hip_levels_dleaf_f64``): ``out[k][c, r, b]`` is
     the exact derivative of ``X[c, levels[r], b]`` (``X`` in ``keys``, any of ``I_dr, I_df_d, I_df_u, F``: what :class:`LevelsPlan`
     returns) along ``tangent`` (:class:`LeafTangent`, e.g. from :func:`leaf_tangent`), each ``(ncol, nsel, nb)`` float64; the sun angle,
@@ -1567,35 +1582,24 @@ class LevelsDleafPlan(_SolvePlan):
     ``FLAG_SKIP_PRECOMPUTE`` is valid only on a workspace a call of this plan has filled.  A column's result is bitwise the same alone
     or in any batch, for any subset of ``keys`` and of ``levels``."""
 
-    _bad_dleaf_scheme = "scheme {!r} has no leaf-angle-derivative kernel; served: " + ", ".join(DLEAF_SCHEMES)
+    _entry_name, _ws_query, _out_struct = "crt_hip_levels_dleaf_f64", "crt_hip_levels_dleaf_workspace_bytes", "CrtDlaiOut"
+    _all_keys, _schemes, _what = DLEAF_KEYS, DLEAF_SCHEMES, "leaf-angle derivative"
+    _no_kernel = "scheme {!r} has no leaf-angle-derivative kernel; served: " + ", ".join(DLEAF_SCHEMES)
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, tangent: LeafTangent, *, keys=DLEAF_KEYS, mu_s=0.501,
                  tau_d_method="quad", out=None, workspace=None):
-        keys = self._check_dleaf(scheme, tau_d_method, keys)
-        if not isinstance(tangent, LeafTangent):
+        super().__init__(scheme, cols, bands, levels, keys=keys, mu_s=mu_s, tau_d_method=tau_d_method, out=out, workspace=workspace,
+                         tangent=tangent)
+
+    @staticmethod
+    def _check_extras(**kw):  # (the one-shot functions check ahead without the tangent)
+        if "tangent" in kw and not isinstance(kw["tangent"], LeafTangent):
             raise TypeError("tangent must be a LeafTangent")
-        if bands.dtype != torch.float64:
-            raise TypeError("the leaf-angle derivative has no f32 storage form: bands must be float64")
+
+    def _bind_extras(self, cols, tangent):
         if tangent.dg_table.shape[0] != cols.ncol or tangent.dg_table.device != cols.device:
             raise ValueError("the tangent must have the columns' ncol and device")
-        self.levels, self.keys, self.tangent = normalize_levels(levels, cols.nz), keys, tangent
-        self._bind(scheme, cols, bands, mu_s, tau_d_method)
-        shape = (cols.ncol, len(self.levels), bands.nb)
-        out = _outputs({k: shape for k in keys}, out, torch.float64, cols.device, "output {!r}", lacks=True)
-        self.out = {k: out[k] for k in keys}
-        self._out = _lib.CrtDlaiOut(*[out[k].data_ptr() if k in keys else None for k in DLEAF_KEYS])
-        self._lev = (ctypes.c_int32 * len(self.levels))(*self.levels)
-        self._tan = tangent.c_struct()
-        need = levels_dleaf_workspace_bytes(scheme, cols.ncol, cols.nz, bands.nb, len(self.levels))
-        self._finish("crt_hip_levels_dleaf_f64", need, workspace)
-
-    @classmethod
-    def _check_dleaf(cls, scheme, tau_d_method="quad", keys=DLEAF_KEYS, **_):
-        """The checks that need neither a column nor a device: scheme, method, keys.  -> keys"""
-        cls._check_options(cls, scheme, tau_d_method)
-        if scheme not in DLEAF_SCHEMES:
-            raise ValueError(cls._bad_dleaf_scheme.format(scheme))
-        return _level_keys(keys)
+        self.tangent, self._tan = tangent, tangent.c_struct()
 
     def _tail(self):
         return self._lev, len(self.levels), ctypes.byref(self._tan), ctypes.byref(self._out)
@@ -1603,7 +1607,7 @@ class LevelsDleafPlan(_SolvePlan):
 
 def solve_levels_dleaf(scheme, cols: Columns, bands: Bands, levels, tangent: LeafTangent, **kw):
     """One-shot :class:`LevelsDleafPlan`: ``{key: (ncol, nsel, nb)}`` at the sorted levels ``normalize_levels(levels, nz)``."""
-    LevelsDleafPlan._check_dleaf(scheme, **kw)  # (before any device is touched)
+    LevelsDleafPlan._check_static(scheme, **kw)  # (before any device is touched)
     with torch.cuda.device(cols.device):
         return LevelsDleafPlan(scheme, cols, bands, levels, tangent, **kw)()
 
@@ -1612,10 +1616,5 @@ def sensor_dleaf(scheme, cols: Columns, bands: Bands, levels, tangent: LeafTange
     """The leaf-angle derivative of :class:`SensorLevelsPlan`'s sums: per key ``(ncol, nsel, nsens)`` with
     ``out[c, r, s] = sum_b w_s[b] * dX[c, r, b]``.  ``dX`` comes from one :class:`LevelsDleafPlan` call (``kw`` goes there); the
     contraction with the sensor set's dense weights runs in torch on the device, as in :func:`sensor_dlai`."""
-    if not isinstance(sensors, SensorSet):
-        raise TypeError("sensors must be a SensorSet")
-    LevelsDleafPlan._check_dleaf(scheme, **kw)
-    sensors.check(bands.nb, cols.device)
-    d = solve_levels_dleaf(scheme, cols, bands, levels, tangent, **kw)
-    w = torch.as_tensor(sensors.dense(bands.nb)).to(cols.device)
-    return {k: torch.einsum("crb,sb->crs", v, w) for k, v in d.items()}
+    return _sensor_contract(sensors, cols, bands, "crb,sb->crs", lambda: LevelsDleafPlan._check_static(scheme, **kw),
+                            lambda: solve_levels_dleaf(scheme, cols, bands, levels, tangent, **kw))

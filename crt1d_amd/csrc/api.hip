@@ -646,81 +646,91 @@ int crt_hip_sensor_levels_series_f64(int scheme, const crt_columns* cols, const 
 }
 
 // ------------------------------------------------------------------------------------------
-// Optical-property Jacobians of the level spectra (include/crt1d_hip_jac.h): the checks of crt_hip_levels_f64, K0, one kernel of jac.hip.
+// Derivatives of the level spectra: the optics Jacobian (include/crt1d_hip_jac.h), the LAI derivative (crt1d_hip_dlai.h), the leaf-angle
+// derivative (crt1d_hip_dleaf.h).  One host path, levels_deriv_impl: the checks of crt_hip_levels_f64, K0, the entry's side precompute into
+// the side records [ncol][side_len(scheme, nz)] behind the K0 records, one derivative kernel.  An entry says what differs.
 
-size_t crt_hip_levels_jac_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nsel) {
-  if (nsel < 1 || nsel > CRT_MAX_LEVEL_SELECT) return 0;
-  return crt_hip_workspace_bytes_nb(scheme, ncol, nz, nb);  // the records; the kernels keep nothing behind them
+using SideLen = int (*)(int scheme, int nz);  // doubles of a column's side record; nullptr: the entry keeps none (jac)
+
+static size_t side_bytes(SideLen len, int scheme, int32_t ncol, int32_t nz) {
+  return len ? (size_t)ncol * (size_t)len(scheme, nz) * sizeof(double) : 0;
 }
 
-int crt_hip_levels_jac_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
-                           int32_t nsel, const crt_jac_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream) {
-  if (!scheme_ok(scheme) || !cols || !levels || !out) return CRT_ERR_BAD_ARG;
-  if (!out->I_df_d && !out->I_df_u && !out->F) return CRT_ERR_BAD_ARG;
+// the K0 records at the offsets of crt_hip_workspace_bytes_nb, then the side records
+static size_t levels_deriv_workspace_bytes(SideLen len, int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nsel) {
+  if (nsel < 1 || nsel > CRT_MAX_LEVEL_SELECT) return 0;
+  const size_t rec = crt_hip_workspace_bytes_nb(scheme, ncol, nz, nb);
+  return rec == 0 ? 0 : rec + side_bytes(len, scheme, ncol, nz);
+}
+
+}  // extern "C": closed around the one template (C++ linkage)
+
+// args_ok: the entry's own pointers are there (an output at least).  pre_report: what a CRT_FLAG_PRECOMPUTE_ONLY call reports where the
+// scheme has a side record ("k_colpre" where it has none; an entry without side_len leaves K0's report).
+// launch(sa, la, side, s, probe): the entry's derivative kernel;  side_pre(ca, side, s): its side precompute, after K0 on the same stream.
+template <class Launch, class SidePre>
+static int levels_deriv_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
+                             int32_t nsel, void* workspace, size_t workspace_bytes, crt_stream_t stream, bool args_ok, SideLen side_len,
+                             const char* pre_report, Launch launch, SidePre side_pre) {
+  if (!scheme_ok(scheme) || !cols || !levels || !args_ok) return CRT_ERR_BAD_ARG;
   LevArgs la = {};
   if (const int st = parse_levels(cols, levels, nsel, la)) return st;
   SolveOpts o;
   const crt_outputs none = {};
-  const int chk = check_solve(scheme, cols, bands, opts, &none, workspace, workspace_bytes, nullptr, &la, nullptr, o);
+  const bool sized = cols->ncol > 0 && cols->nz > 0;
+  const int chk = check_solve(scheme, cols, bands, opts, &none, workspace, workspace_bytes, nullptr, &la, nullptr, o,
+                              sized ? side_bytes(side_len, scheme, cols->ncol, cols->nz) : 0);
   if (chk == CRT_ERR_BAD_ARG || chk == CRT_ERR_SHAPE) return chk;  // an argument error is one for every scheme
   if (scheme == CRT_SCHEME_4S || scheme == CRT_SCHEME_ZQ_PA) return CRT_ERR_UNSUPPORTED;  // whatever the workspace (a follow-up: crt1d_hip_jac.h)
   if (chk != CRT_OK) return chk;
   ColArgs ca;
   SolveArgs sa;
   build_args(scheme, cols, bands, &none, workspace, 0, o, ca, sa);
-  const JacArgs jo = {{out->I_df_d, out->I_df_u, out->F}};
+  double* const side = reinterpret_cast<double*>(static_cast<char*>(workspace) + crt_hip_workspace_bytes_nb(scheme, cols->ncol, cols->nz, bands->nb));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (const int st = launch_jac(scheme, sa, la, jo, s, true)) return st;  // a shape that is not served: before K0 has written anything
+  if (const int st = launch(sa, la, side, s, true)) return st;  // a shape that is not served: before K0 has written anything
   if (const int st = k0_step(ca, o.flags, false, s)) return st;
-  if (o.flags & CRT_FLAG_PRECOMPUTE_ONLY) return CRT_OK;
-  return launch_jac(scheme, sa, la, jo, s, false);
+  if (!(o.flags & CRT_FLAG_SKIP_PRECOMPUTE))
+    if (const int st = side_pre(ca, side, s)) return st;
+  if (o.flags & CRT_FLAG_PRECOMPUTE_ONLY) {
+    if (side_len) note_kernel("%s", side_len(scheme, cols->nz) ? pre_report : "k_colpre");
+    return CRT_OK;
+  }
+  return launch(sa, la, side, s, false);
 }
 
-// ------------------------------------------------------------------------------------------
-// LAI derivative of the level spectra (include/crt1d_hip_dlai.h): the checks of crt_hip_levels_f64, K0, the side precompute, one kernel of
-// dlai.hip.
+extern "C" {
 
-// bytes of the side records [ncol][dlai_side_len] behind the K0 records
-static size_t dlai_side_bytes(int scheme, int32_t ncol, int32_t nz) {
-  return (size_t)ncol * (size_t)dlai_side_len(scheme, nz) * sizeof(double);
+size_t crt_hip_levels_jac_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nsel) {
+  return levels_deriv_workspace_bytes(nullptr, scheme, ncol, nz, nb, nsel);  // the records; the kernels keep nothing behind them
 }
+
+int crt_hip_levels_jac_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
+                           int32_t nsel, const crt_jac_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream) {
+  return levels_deriv_impl(
+      scheme, cols, bands, opts, levels, nsel, workspace, workspace_bytes, stream, out && (out->I_df_d || out->I_df_u || out->F), nullptr, nullptr,
+      [&](const SolveArgs& sa, const LevArgs& la, const double*, hipStream_t s, bool probe) {
+        return launch_jac(scheme, sa, la, JacArgs{{out->I_df_d, out->I_df_u, out->F}}, s, probe);
+      },
+      [](const ColArgs&, double*, hipStream_t) { return (int)CRT_OK; });
+}
+
+// the LAI and the leaf-angle derivative share crt_dlai_out and DlaiArgs
+static bool dlai_out_ok(const crt_dlai_out* out) { return out && (out->I_dr || out->I_df_d || out->I_df_u || out->F); }
+static DlaiArgs dlai_args(const crt_dlai_out* out, const double* side) { return {{out->I_dr, out->I_df_d, out->I_df_u, out->F}, side}; }
 
 size_t crt_hip_levels_dlai_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nsel) {
-  if (nsel < 1 || nsel > CRT_MAX_LEVEL_SELECT) return 0;
-  const size_t rec = crt_hip_workspace_bytes_nb(scheme, ncol, nz, nb);
-  return rec == 0 ? 0 : rec + dlai_side_bytes(scheme, ncol, nz);
+  return levels_deriv_workspace_bytes(dlai_side_len, scheme, ncol, nz, nb, nsel);
 }
 
 int crt_hip_levels_dlai_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
                             int32_t nsel, const crt_dlai_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream) {
-  if (!scheme_ok(scheme) || !cols || !levels || !out) return CRT_ERR_BAD_ARG;
-  if (!out->I_dr && !out->I_df_d && !out->I_df_u && !out->F) return CRT_ERR_BAD_ARG;
-  LevArgs la = {};
-  if (const int st = parse_levels(cols, levels, nsel, la)) return st;
-  SolveOpts o;
-  const crt_outputs none = {};
-  const bool sized = cols->ncol > 0 && cols->nz > 0;
-  const size_t side_bytes = sized ? dlai_side_bytes(scheme, cols->ncol, cols->nz) : 0;
-  const int chk = check_solve(scheme, cols, bands, opts, &none, workspace, workspace_bytes, nullptr, &la, nullptr, o, side_bytes);
-  if (chk == CRT_ERR_BAD_ARG || chk == CRT_ERR_SHAPE) return chk;  // an argument error is one for every scheme
-  if (scheme == CRT_SCHEME_4S || scheme == CRT_SCHEME_ZQ_PA) return CRT_ERR_UNSUPPORTED;  // whatever the workspace
-  if (chk != CRT_OK) return chk;
-  ColArgs ca;
-  SolveArgs sa;
-  build_args(scheme, cols, bands, &none, workspace, 0, o, ca, sa);
-  double* const side = reinterpret_cast<double*>(static_cast<char*>(workspace) + crt_hip_workspace_bytes_nb(scheme, cols->ncol, cols->nz, bands->nb));
-  const DlaiArgs da = {{out->I_dr, out->I_df_d, out->I_df_u, out->F}, side};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (const int st = launch_dlai(scheme, sa, la, da, s, true)) return st;  // a shape that is not served: before K0 has written anything
-  if (!(o.flags & CRT_FLAG_SKIP_PRECOMPUTE)) {
-    if (const int st = launch_colpre(ca, s)) return st;
-    if (const int st = launch_dlai_side(ca, side, s)) return st;
-  }
-  if (o.flags & CRT_FLAG_PRECOMPUTE_ONLY) {
-    note_kernel(dlai_side_len(scheme, cols->nz) ? "k_colpre + k_dlai_side" : "k_colpre");
-    return CRT_OK;
-  }
-  return launch_dlai(scheme, sa, la, da, s, false);
+  return levels_deriv_impl(
+      scheme, cols, bands, opts, levels, nsel, workspace, workspace_bytes, stream, dlai_out_ok(out), dlai_side_len, "k_colpre + k_dlai_side",
+      [&](const SolveArgs& sa, const LevArgs& la, const double* side, hipStream_t s, bool probe) {
+        return launch_dlai(scheme, sa, la, dlai_args(out, side), s, probe);
+      },
+      [](const ColArgs& ca, double* side, hipStream_t s) { return launch_dlai_side(ca, side, s); });
 }
 
 int crt_hip_dtau_d_f64(const double* kb_nodes, const double* L, int64_t n, int32_t method, double* out, crt_stream_t stream) {
@@ -730,53 +740,23 @@ int crt_hip_dtau_d_f64(const double* kb_nodes, const double* L, int64_t n, int32
   return crt::launch_dtau_d(kb_nodes, L, (long long)n, method, out, static_cast<hipStream_t>(stream));
 }
 
-// ------------------------------------------------------------------------------------------
-// Leaf-angle derivative of the level spectra (include/crt1d_hip_dleaf.h): the checks of crt_hip_levels_dlai_f64, K0, the side precompute,
-// one kernel (dleaf.hip; n79 / zq: k_dlai_tri of dlai.hip on the side record written here).
-
-static size_t dleaf_side_bytes(int scheme, int32_t ncol, int32_t nz) {
-  return (size_t)ncol * (size_t)dleaf_side_len(scheme, nz) * sizeof(double);
-}
-
 size_t crt_hip_levels_dleaf_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nsel) {
-  if (nsel < 1 || nsel > CRT_MAX_LEVEL_SELECT) return 0;
-  const size_t rec = crt_hip_workspace_bytes_nb(scheme, ncol, nz, nb);
-  return rec == 0 ? 0 : rec + dleaf_side_bytes(scheme, ncol, nz);
+  return levels_deriv_workspace_bytes(dleaf_side_len, scheme, ncol, nz, nb, nsel);
 }
 
+// (n79 / zq: k_dlai_tri of dlai.hip on the side record written here)
 int crt_hip_levels_dleaf_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
                              int32_t nsel, const crt_leaf_tangent* tangent, const crt_dlai_out* out, void* workspace,
                              size_t workspace_bytes, crt_stream_t stream) {
-  if (!scheme_ok(scheme) || !cols || !levels || !out || !tangent) return CRT_ERR_BAD_ARG;
-  if (!tangent->dg_table || !tangent->dg_at_psi) return CRT_ERR_BAD_ARG;
-  if (!out->I_dr && !out->I_df_d && !out->I_df_u && !out->F) return CRT_ERR_BAD_ARG;
-  LevArgs la = {};
-  if (const int st = parse_levels(cols, levels, nsel, la)) return st;
-  SolveOpts o;
-  const crt_outputs none = {};
-  const bool sized = cols->ncol > 0 && cols->nz > 0;
-  const size_t side_bytes = sized ? dleaf_side_bytes(scheme, cols->ncol, cols->nz) : 0;
-  const int chk = check_solve(scheme, cols, bands, opts, &none, workspace, workspace_bytes, nullptr, &la, nullptr, o, side_bytes);
-  if (chk == CRT_ERR_BAD_ARG || chk == CRT_ERR_SHAPE) return chk;  // an argument error is one for every scheme
-  if (scheme == CRT_SCHEME_4S || scheme == CRT_SCHEME_ZQ_PA) return CRT_ERR_UNSUPPORTED;  // whatever the workspace
-  if (chk != CRT_OK) return chk;
-  ColArgs ca;
-  SolveArgs sa;
-  build_args(scheme, cols, bands, &none, workspace, 0, o, ca, sa);
-  double* const side = reinterpret_cast<double*>(static_cast<char*>(workspace) + crt_hip_workspace_bytes_nb(scheme, cols->ncol, cols->nz, bands->nb));
-  const DlaiArgs da = {{out->I_dr, out->I_df_d, out->I_df_u, out->F}, side};
-  const DleafTan tn = {tangent->dg_table, tangent->dg_at_psi, tangent->dmla};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (const int st = launch_dleaf(scheme, sa, la, da, s, true)) return st;  // a shape that is not served: before K0 has written anything
-  if (!(o.flags & CRT_FLAG_SKIP_PRECOMPUTE)) {
-    if (const int st = launch_colpre(ca, s)) return st;
-    if (const int st = launch_dleaf_side(ca, tn, side, s)) return st;
-  }
-  if (o.flags & CRT_FLAG_PRECOMPUTE_ONLY) {
-    note_kernel("k_colpre + k_dleaf_side");
-    return CRT_OK;
-  }
-  return launch_dleaf(scheme, sa, la, da, s, false);
+  return levels_deriv_impl(
+      scheme, cols, bands, opts, levels, nsel, workspace, workspace_bytes, stream,
+      tangent && tangent->dg_table && tangent->dg_at_psi && dlai_out_ok(out), dleaf_side_len, "k_colpre + k_dleaf_side",
+      [&](const SolveArgs& sa, const LevArgs& la, const double* side, hipStream_t s, bool probe) {
+        return launch_dleaf(scheme, sa, la, dlai_args(out, side), s, probe);
+      },
+      [&](const ColArgs& ca, double* side, hipStream_t s) {
+        return launch_dleaf_side(ca, DleafTan{tangent->dg_table, tangent->dg_at_psi, tangent->dmla}, side, s);
+      });
 }
 
 int crt_hip_g_dparam_f64(const crt_columns* cols, double* dg_table, double* dg_at_psi, crt_stream_t stream) {

@@ -40,6 +40,11 @@ namespace {
 
 __constant__ QuadConst qc;  // internal linkage: one copy per translation unit
 
+// the tables into this unit's copy (what a unit's upload_quad_* above is; colpre.hip for its own)
+inline int upload_qc(const QuadConst& h, hipStream_t s) {
+  return hipMemcpyToSymbolAsync(HIP_SYMBOL(qc), &h, sizeof(QuadConst), 0, hipMemcpyHostToDevice, s) == hipSuccess ? (int)CRT_OK : (int)CRT_ERR_LAUNCH;
+}
+
 __device__ __forceinline__ double wave_sum64(double v) {  // fixed tree order -> bitwise reproducible
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -71,6 +76,13 @@ __device__ __forceinline__ void col_node(const ColIn& in, int q, double& kq, dou
   const double g = in.tab ? in.tab[q] : G_eval(in.kind, in.param, in.gden, qc.cs[q], qc.sn[q]);
   kq = g / qc.cs[q];
   pmb = qc.w[q] * qc.cs[q] * qc.sn[q] / g;
+}
+
+// sky angle i of the '9sky' rule: K_b = G / cos
+__device__ __forceinline__ double col_node9(const ColIn& in, int i) {
+#pragma clang fp contract(off)
+  const double g = in.tab ? in.tab[NQT + NQG + i] : G_eval(in.kind, in.param, in.gden, qc.cs9[i], qc.sn9[i]);
+  return g / qc.cs9[i];
 }
 
 // mu_bar from the node terms: lane l adds terms l and 64 + l, then the fixed-order wave sum (call with all 64 lanes of one wave)

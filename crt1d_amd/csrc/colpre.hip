@@ -215,10 +215,7 @@ __global__ __launch_bounds__(K0_BLOCK) void k_colpre(ColArgs a) {
     const double g = tab ? tab[NQT + tid] : G_eval(kind, param, gden, cos(p), sin(p));
     pg[tid] = qc.gw[i] * (hi - lo) / 2 * g * sin(p);
   }
-  if (tid < CRT_NQ_9SKY) {
-    const double g = tab ? tab[NQT + NQG + tid] : G_eval(kind, param, gden, qc.cs9[tid], qc.sn9[tid]);
-    k9[tid] = g / qc.cs9[tid];
-  }
+  if (tid < CRT_NQ_9SKY) k9[tid] = col_node9(in, tid);
   __syncthreads();
 
   // ---- header: wave 0, reductions by shuffles ----
@@ -523,11 +520,8 @@ int init_quadrature(hipStream_t s) {
   if (!dev_inited[dev]) {
     // first call on this device only; not capturable into a hipGraph (documented in DESIGN.md).  Every unit whose kernels read the
     // tables has its own copy (col_record.hpp): this one (k_colpre, k_tau_d), solve_closed.hip (the 2s k_pipe's record prologue), dlai.hip and dleaf.hip.
-    if (hipMemcpyToSymbolAsync(HIP_SYMBOL(qc), &h_qc, sizeof(QuadConst), 0, hipMemcpyHostToDevice, s) != hipSuccess)
-      return CRT_ERR_LAUNCH;
-    if (upload_quad_closed(h_qc, s) != CRT_OK) return CRT_ERR_LAUNCH;
-    if (upload_quad_dlai(h_qc, s) != CRT_OK) return CRT_ERR_LAUNCH;
-    if (upload_quad_dleaf(h_qc, s) != CRT_OK) return CRT_ERR_LAUNCH;
+    for (auto upload : {upload_qc, upload_quad_closed, upload_quad_dlai, upload_quad_dleaf})
+      if (upload(h_qc, s) != CRT_OK) return CRT_ERR_LAUNCH;
     if (hipStreamSynchronize(s) != hipSuccess) return CRT_ERR_LAUNCH;
     dev_inited[dev] = true;
   }

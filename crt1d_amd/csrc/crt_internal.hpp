@@ -909,25 +909,34 @@ int launch_tri_lev_zq_f32(const SolveArgs& a, const LevArgs& la, hipStream_t s, 
 struct JacArgs {
   double* o[3];  // d I_df_d, d I_df_u, d F: [ncol][nsel][3][nb] or NULL
 };
-// n79 / zq: the leading doubles of the record the kernel stages (header + the vectors it reads), the level states it keeps (every
-// JAC_TRI_CP-th one, 4 doubles per lane each), its LDS bytes with W lanes per workgroup, and the widest W out of 64, 32, 16 that fits 160 KB (0: none)
+// n79 / zq (k_jac_tri, k_dlai_tri): the leading doubles of the record the kernel stages (header + the vectors it reads) and the level states it
+// keeps (every JAC_TRI_CP-th one, 4 doubles per lane each).  tri_cp_lds_bytes: its LDS bytes with W lanes per workgroup and `copies` of the
+// staged record part -- 1: the values (k_jac_tri); 2: values | tangents of the side record (k_dlai_tri) -- and tri_cp_lanes: the widest W out
+// of 64, 32, 16 that fits 160 KB (0: none)
 constexpr int JAC_TRI_CP = 4;
 constexpr int jac_tri_nrec(int scheme, int nz) { return REC_HDR + (scheme == CRT_SCHEME_N79 ? 3 : 1) * nz; }
-constexpr size_t jac_tri_lds_bytes(int scheme, int nz, int W) {
+constexpr size_t tri_cp_lds_bytes(int scheme, int nz, int W, int copies) {
   const size_t nst = scheme == CRT_SCHEME_N79 ? (size_t)nz : (size_t)nz + 1, ncp = (nst + JAC_TRI_CP - 1) / JAC_TRI_CP;
-  return ((((size_t)jac_tri_nrec(scheme, nz) + 1) & ~(size_t)1) + ncp * 4 * W) * sizeof(double);
+  return (copies * (((size_t)jac_tri_nrec(scheme, nz) + 1) & ~(size_t)1) + ncp * 4 * W) * sizeof(double);
 }
-constexpr int jac_tri_lanes(int scheme, int nz) {
+constexpr int tri_cp_lanes(int scheme, int nz, int copies) {
   for (int W = 64; W >= 16; W >>= 1)
-    if (jac_tri_lds_bytes(scheme, nz, W) <= 160 * 1024) return W;
+    if (tri_cp_lds_bytes(scheme, nz, W, copies) <= 160 * 1024) return W;
   return 0;
 }
-static_assert(jac_tri_lanes(CRT_SCHEME_N79, CRT_JAC_MAX_NZ_N79) == 16 && jac_tri_lanes(CRT_SCHEME_N79, CRT_JAC_MAX_NZ_N79 + 1) == 0 &&
-                  jac_tri_lanes(CRT_SCHEME_ZQ, CRT_JAC_MAX_NZ_ZQ) == 16 && jac_tri_lanes(CRT_SCHEME_ZQ, CRT_JAC_MAX_NZ_ZQ + 1) == 0,
+static_assert(tri_cp_lanes(CRT_SCHEME_N79, CRT_JAC_MAX_NZ_N79, 1) == 16 && tri_cp_lanes(CRT_SCHEME_N79, CRT_JAC_MAX_NZ_N79 + 1, 1) == 0 &&
+                  tri_cp_lanes(CRT_SCHEME_ZQ, CRT_JAC_MAX_NZ_ZQ, 1) == 16 && tri_cp_lanes(CRT_SCHEME_ZQ, CRT_JAC_MAX_NZ_ZQ + 1, 1) == 0,
               "the depth limits of crt1d_hip_jac.h are those of the LDS layout");
-static_assert(jac_tri_lanes(CRT_SCHEME_N79, 304) == 64 && jac_tri_lanes(CRT_SCHEME_N79, 305) == 32 && jac_tri_lanes(CRT_SCHEME_ZQ, 311) == 64 &&
-                  jac_tri_lanes(CRT_SCHEME_ZQ, 312) == 32,
+static_assert(tri_cp_lanes(CRT_SCHEME_N79, 304, 1) == 64 && tri_cp_lanes(CRT_SCHEME_N79, 305, 1) == 32 && tri_cp_lanes(CRT_SCHEME_ZQ, 311, 1) == 64 &&
+                  tri_cp_lanes(CRT_SCHEME_ZQ, 312, 1) == 32,
               "whole waves up to 304 (n79) / 311 (zq) levels, as crt1d_hip_jac.h says");
+static_assert(tri_cp_lanes(CRT_SCHEME_N79, CRT_DLAI_MAX_NZ_N79, 2) == 16 && tri_cp_lanes(CRT_SCHEME_N79, CRT_DLAI_MAX_NZ_N79 + 1, 2) == 0 &&
+                  tri_cp_lanes(CRT_SCHEME_ZQ, CRT_DLAI_MAX_NZ_ZQ, 2) == 16 && tri_cp_lanes(CRT_SCHEME_ZQ, CRT_DLAI_MAX_NZ_ZQ + 1, 2) == 0,
+              "the depth limits of crt1d_hip_dlai.h are those of the LDS layout");
+static_assert(tri_cp_lanes(CRT_SCHEME_N79, 292, 2) == 64 && tri_cp_lanes(CRT_SCHEME_N79, 293, 2) == 32 && tri_cp_lanes(CRT_SCHEME_N79, 536, 2) == 32 &&
+                  tri_cp_lanes(CRT_SCHEME_N79, 537, 2) == 16 && tri_cp_lanes(CRT_SCHEME_ZQ, 307, 2) == 64 && tri_cp_lanes(CRT_SCHEME_ZQ, 308, 2) == 32 &&
+                  tri_cp_lanes(CRT_SCHEME_ZQ, 599, 2) == 32 && tri_cp_lanes(CRT_SCHEME_ZQ, 600, 2) == 16,
+              "the lane-narrowing thresholds crt1d_hip_dlai.h states");
 // probe: return the status (CRT_OK / CRT_ERR_UNSUPPORTED) of the configuration without launching anything
 int launch_jac(int scheme, const SolveArgs& a, const LevArgs& la, const JacArgs& jo, hipStream_t s, bool probe);
 
@@ -942,24 +951,6 @@ struct DlaiArgs {
 constexpr int dlai_side_len(int scheme, int nz) {
   return scheme == CRT_SCHEME_BL ? nz : (scheme == CRT_SCHEME_N79 || scheme == CRT_SCHEME_ZQ) ? jac_tri_nrec(scheme, nz) : 0;
 }
-// n79 / zq: LDS bytes with W lanes per workgroup -- the staged record part twice (values | tangents), then the level states as in
-// k_jac_tri -- and the widest W out of 64, 32, 16 that fits 160 KB (0: none)
-constexpr size_t dlai_tri_lds_bytes(int scheme, int nz, int W) {
-  const size_t nst = scheme == CRT_SCHEME_N79 ? (size_t)nz : (size_t)nz + 1, ncp = (nst + JAC_TRI_CP - 1) / JAC_TRI_CP;
-  return (2 * (((size_t)jac_tri_nrec(scheme, nz) + 1) & ~(size_t)1) + ncp * 4 * W) * sizeof(double);
-}
-constexpr int dlai_tri_lanes(int scheme, int nz) {
-  for (int W = 64; W >= 16; W >>= 1)
-    if (dlai_tri_lds_bytes(scheme, nz, W) <= 160 * 1024) return W;
-  return 0;
-}
-static_assert(dlai_tri_lanes(CRT_SCHEME_N79, CRT_DLAI_MAX_NZ_N79) == 16 && dlai_tri_lanes(CRT_SCHEME_N79, CRT_DLAI_MAX_NZ_N79 + 1) == 0 &&
-                  dlai_tri_lanes(CRT_SCHEME_ZQ, CRT_DLAI_MAX_NZ_ZQ) == 16 && dlai_tri_lanes(CRT_SCHEME_ZQ, CRT_DLAI_MAX_NZ_ZQ + 1) == 0,
-              "the depth limits of crt1d_hip_dlai.h are those of the LDS layout");
-static_assert(dlai_tri_lanes(CRT_SCHEME_N79, 292) == 64 && dlai_tri_lanes(CRT_SCHEME_N79, 293) == 32 && dlai_tri_lanes(CRT_SCHEME_N79, 536) == 32 &&
-                  dlai_tri_lanes(CRT_SCHEME_N79, 537) == 16 && dlai_tri_lanes(CRT_SCHEME_ZQ, 307) == 64 && dlai_tri_lanes(CRT_SCHEME_ZQ, 308) == 32 &&
-                  dlai_tri_lanes(CRT_SCHEME_ZQ, 599) == 32 && dlai_tri_lanes(CRT_SCHEME_ZQ, 600) == 16,
-              "the lane-narrowing thresholds crt1d_hip_dlai.h states");
 // the side precompute (after K0, same stream); the derivative kernel (probe: the status of the configuration, nothing launched); tau_d'
 int launch_dlai_side(const ColArgs& ca, double* side, hipStream_t s);
 int launch_dlai(int scheme, const SolveArgs& a, const LevArgs& la, const DlaiArgs& da, hipStream_t s, bool probe);

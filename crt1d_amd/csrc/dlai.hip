@@ -15,9 +15,10 @@
 //  k_dlai       2s, bl, g77, bf: k_jac's mapping without the parameter axis (lane <-> band, a workgroup owns one column and one band slice,
 //               plain stores of consecutive bands); L_j, LT, e^{-K_b L_j} are seeded from the record itself, O(nsel).
 //  k_dlai_tri   n79, zq: k_jac_tri's checkpoint-every-fourth-level sweep with the record entries as Du: the staged record part is in LDS
-//               twice (values | tangents of the side record), so the lanes narrow earlier (dlai_tri_lanes).
+//               twice (values | tangents of the side record), so the lanes narrow earlier (tri_cp_lanes with two copies).
 #include "col_record.hpp"
 #include "jac_schemes.hpp"
+#include "launch_forms.hpp"
 
 namespace crt {
 namespace {
@@ -53,10 +54,7 @@ __global__ __launch_bounds__(SIDE_BLOCK) void k_dlai_side(ColArgs a, double* __r
     double pmb;
     col_node(in, q, kq[q], pmb);
   }
-  if (tid < CRT_NQ_9SKY) {  // as k_colpre
-    const double g = in.tab ? in.tab[NQT + NQG + tid] : G_eval(in.kind, in.param, in.gden, qc.cs9[tid], qc.sn9[tid]);
-    k9[tid] = g / qc.cs9[tid];
-  }
+  if (tid < CRT_NQ_9SKY) k9[tid] = col_node9(in, tid);  // as k_colpre
   __syncthreads();
   const double* rec = a.ws + (long long)c * rec_len(a.scheme, nz);
   const double* lai = in.lai;
@@ -221,26 +219,11 @@ __global__ __launch_bounds__(64) void k_dlai_tri(SolveArgs a, LevArgs la, DlaiAr
 
 template <class S, bool BL = false>
 int launch_dlai_closed(const SolveArgs& a, const LevArgs& la, const DlaiArgs& da, hipStream_t s, bool probe) {
-  const LevSlices ls = lev_slices(a.nb, DLAI_BLOCK);
-  if (ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
-  if (probe) return CRT_OK;
-  const int st = launch_kernel(k_dlai<S, BL>, dim3(a.ncol, ls.nslice), ls.nthr, 0, s, a, la, da, ls.per);
-  if (st == CRT_OK) note_kernel("k_dlai<%s> nsel=%d slice=%d", S::NAME, la.nsel, ls.per);
-  return st;
+  return launch_deriv_closed(k_dlai<S, BL>, "k_dlai", S::NAME, DLAI_BLOCK, 1, a, la, da, s, probe);
 }
-
 template <class S>
 int launch_dlai_tri(const SolveArgs& a, const LevArgs& la, const DlaiArgs& da, hipStream_t s, bool probe) {
-  constexpr int scheme = S::ID;
-  const int W = dlai_tri_lanes(scheme, a.nz);
-  if (W == 0) return CRT_ERR_UNSUPPORTED;
-  const long long nslice = ((long long)a.nb + W - 1) / W;
-  if (nslice > 65535) return CRT_ERR_UNSUPPORTED;
-  if (probe) return CRT_OK;
-  const int nrec = jac_tri_nrec(scheme, a.nz), off_t = (nrec + 1) & ~1;
-  const int st = launch_kernel(k_dlai_tri<S>, dim3(a.ncol, (unsigned)nslice), 64, dlai_tri_lds_bytes(scheme, a.nz, W), s, a, la, da, W, nrec, off_t);
-  if (st == CRT_OK) note_kernel("k_dlai_tri<%s> nsel=%d slice=%d", S::NAME, la.nsel, W);
-  return st;
+  return launch_deriv_tri(k_dlai_tri<S>, "k_dlai_tri", S::NAME, S::ID, 2, 1, a, la, da, s, probe);
 }
 
 }  // namespace
@@ -265,16 +248,9 @@ int launch_dlai_side(const ColArgs& ca, double* side, hipStream_t s) {
 }
 
 int launch_dtau_d(const double* kb_nodes, const double* L, long long n, int method, double* out, hipStream_t s) {
-  const int st = init_quadrature(s);
-  if (st != CRT_OK) return st;
-  const long long nblk = (n + 255) / 256;
-  if (nblk > 0x7fffffffLL) return CRT_ERR_UNSUPPORTED;
-  return launch_kernel(k_dtau_d, dim3((unsigned)nblk), 256, 0, s, kb_nodes, L, n, method, out);
+  return launch_per_lai(k_dtau_d, n, s, kb_nodes, L, n, method, out);
 }
 
-int upload_quad_dlai(const QuadConst& h, hipStream_t s) {
-  return hipMemcpyToSymbolAsync(HIP_SYMBOL(qc), &h, sizeof(QuadConst), 0, hipMemcpyHostToDevice, s) == hipSuccess ? (int)CRT_OK
-                                                                                                                   : (int)CRT_ERR_LAUNCH;
-}
+int upload_quad_dlai(const QuadConst& h, hipStream_t s) { return upload_qc(h, s); }
 
 }  // namespace crt

@@ -20,6 +20,7 @@
 //  k_g_dparam    dG / d g_param of the parametric kinds at the nodes and at the sun angle;  k_dtau_d_dleaf  tau_d^th for arbitrary L.
 #include "col_record.hpp"
 #include "jac_schemes.hpp"
+#include "launch_forms.hpp"
 
 namespace crt {
 namespace {
@@ -57,8 +58,7 @@ __global__ __launch_bounds__(SIDE_BLOCK) void k_dleaf_side(ColArgs a, DleafTan t
     pm[q] = pmb * -(dkq[q] / kq[q]);  // -dG_q / G_q = -Kq' / Kq
   }
   if (tid < CRT_NQ_9SKY) {  // as k_colpre
-    const double g = in.tab ? in.tab[NQT + NQG + tid] : G_eval(in.kind, in.param, in.gden, qc.cs9[tid], qc.sn9[tid]);
-    k9[tid] = g / qc.cs9[tid];
+    k9[tid] = col_node9(in, tid);
     dk9[tid] = dg[NQT + NQG + tid] / qc.cs9[tid];
   }
   __syncthreads();
@@ -257,12 +257,7 @@ __global__ __launch_bounds__(DLEAF_BLOCK) void k_dleaf(SolveArgs a, LevArgs la, 
 
 template <class S, bool BL = false>
 int launch_dleaf_closed(const SolveArgs& a, const LevArgs& la, const DlaiArgs& da, hipStream_t s, bool probe) {
-  const LevSlices ls = lev_slices(a.nb, DLEAF_BLOCK);
-  if (ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
-  if (probe) return CRT_OK;
-  const int st = launch_kernel(k_dleaf<S, BL>, dim3(a.ncol, ls.nslice), ls.nthr, 0, s, a, la, da, ls.per);
-  if (st == CRT_OK) note_kernel("k_dleaf<%s> nsel=%d slice=%d", S::NAME, la.nsel, ls.per);
-  return st;
+  return launch_deriv_closed(k_dleaf<S, BL>, "k_dleaf", S::NAME, DLEAF_BLOCK, 1, a, la, da, s, probe);
 }
 
 }  // namespace
@@ -293,16 +288,9 @@ int launch_g_dparam(int ncol, const double* psi, const int32_t* g_kind, const do
 
 int launch_dtau_d_dleaf(const double* kb_nodes, const double* dkb_nodes, const double* L, long long n, int method, double* out,
                         hipStream_t s) {
-  const int st = init_quadrature(s);
-  if (st != CRT_OK) return st;
-  const long long nblk = (n + 255) / 256;
-  if (nblk > 0x7fffffffLL) return CRT_ERR_UNSUPPORTED;
-  return launch_kernel(k_dtau_d_dleaf, dim3((unsigned)nblk), 256, 0, s, kb_nodes, dkb_nodes, L, n, method, out);
+  return launch_per_lai(k_dtau_d_dleaf, n, s, kb_nodes, dkb_nodes, L, n, method, out);
 }
 
-int upload_quad_dleaf(const QuadConst& h, hipStream_t s) {
-  return hipMemcpyToSymbolAsync(HIP_SYMBOL(qc), &h, sizeof(QuadConst), 0, hipMemcpyHostToDevice, s) == hipSuccess ? (int)CRT_OK
-                                                                                                                   : (int)CRT_ERR_LAUNCH;
-}
+int upload_quad_dleaf(const QuadConst& h, hipStream_t s) { return upload_qc(h, s); }
 
 }  // namespace crt

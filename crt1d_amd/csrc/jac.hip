@@ -13,10 +13,11 @@
 //             here in plain (not projective) form on Du: e carries the matrix, f the right-hand side, so their tangents ARE the solve
 //             A x' = d' - A' x with the same matrix.  The forward sweep leaves (e, f) of every FOURTH level in LDS; the back substitution
 //             recomputes the three levels in between into registers, block by block.  8 bytes per level and lane: a whole wave up to
-//             nz = 304 (n79) / 311 (zq), then 32 and 16 lanes per workgroup (jac_tri_lanes).  One wave per workgroup, every lane in its own LDS column: no
+//             nz = 304 (n79) / 311 (zq), then 32 and 16 lanes per workgroup (tri_cp_lanes).  One wave per workgroup, every lane in its own LDS column: no
 //             barrier after the record is staged.  The reference's quirks are kept: n79's first downward row uses layer
 //             index 1, zq one dlai_mean for every layer.
 #include "jac_schemes.hpp"
+#include "launch_forms.hpp"
 
 namespace crt {
 namespace {
@@ -260,27 +261,11 @@ __global__ __launch_bounds__(64) void k_jac_tri(SolveArgs a, LevArgs la, JacArgs
 
 template <class S>
 int launch_jac_closed(const SolveArgs& a, const LevArgs& la, const JacArgs& jo, hipStream_t s, bool probe) {
-  const LevSlices ls = lev_slices(a.nb, JAC_BLOCK);
-  if (ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
-  if (probe) return CRT_OK;
-  const int st = launch_kernel(k_jac<S>, dim3(a.ncol, ls.nslice, CRT_JAC_NPARAM), ls.nthr, 0, s, a, la, jo, ls.per);
-  if (st == CRT_OK) note_kernel("k_jac<%s> nsel=%d slice=%d", S::NAME, la.nsel, ls.per);
-  return st;
+  return launch_deriv_closed(k_jac<S>, "k_jac", S::NAME, JAC_BLOCK, CRT_JAC_NPARAM, a, la, jo, s, probe);
 }
-
 template <class S>
 int launch_jac_tri(const SolveArgs& a, const LevArgs& la, const JacArgs& jo, hipStream_t s, bool probe) {
-  constexpr int scheme = S::ID;
-  const int W = jac_tri_lanes(scheme, a.nz);
-  if (W == 0) return CRT_ERR_UNSUPPORTED;
-  const long long nslice = ((long long)a.nb + W - 1) / W;
-  if (nslice > 65535) return CRT_ERR_UNSUPPORTED;
-  if (probe) return CRT_OK;
-  const int nrec = jac_tri_nrec(scheme, a.nz), off_cp = (nrec + 1) & ~1;
-  const int st = launch_kernel(k_jac_tri<S>, dim3(a.ncol, (unsigned)nslice, CRT_JAC_NPARAM), 64, jac_tri_lds_bytes(scheme, a.nz, W), s, a, la,
-                               jo, W, nrec, off_cp);
-  if (st == CRT_OK) note_kernel("k_jac_tri<%s> nsel=%d slice=%d", S::NAME, la.nsel, W);
-  return st;
+  return launch_deriv_tri(k_jac_tri<S>, "k_jac_tri", S::NAME, S::ID, 1, CRT_JAC_NPARAM, a, la, jo, s, probe);
 }
 
 }  // namespace

@@ -1,7 +1,8 @@
 // Host side of the solve launchers (no device code): the launch-bound dispatch, the "next form while unsupported" chain, and ONE launch
 // sequence per output form -- level subsets (per step, series, sensor, sensor series) and integrated sums (per step, series) -- which the
 // three kernel families (closed forms: solve_closed.hip; n79 / zq: tri_tile_impl.hpp; zq_pa: tri_zqpa.hip) fill in with a small description
-// each.  A new output form is a new sequence here plus one `launch` branch per family; a new family is a new description.
+// each.  A new output form is a new sequence here plus one `launch` branch per family; a new family is a new description.  The level
+// derivatives (jac.hip, dlai.hip, dleaf.hip) have one sequence per kernel shape at the end.
 #pragma once
 #include <cstdio>
 
@@ -146,6 +147,49 @@ int launch_int_form(const F& f, const SolveArgs& a, const IntArgs& ia, hipStream
   }
   if (st == CRT_OK) f.note(L);  // (only a launch that succeeded is reported)
   return st;
+}
+
+// ------------------------------------------------------------------------------------------
+// Level derivatives (jac.hip, dlai.hip, dleaf.hip): lane <-> band, a workgroup owns one column and one band slice, gz is the grid's third
+// extent (the Jacobian's parameter axis, else 1).  `out` is the kernel's output block (JacArgs, DlaiArgs); the report is
+// "kname<sname> nsel= slice=".  probe: the status of the configuration (CRT_OK / CRT_ERR_UNSUPPORTED), nothing launched.
+
+// closed forms: balanced slices of at most `block` lanes; kernel arguments (a, la, out, slice width)
+template <class K, class Out>
+int launch_deriv_closed(K kern, const char* kname, const char* sname, int block, unsigned gz, const SolveArgs& a, const LevArgs& la,
+                        const Out& out, hipStream_t s, bool probe) {
+  const LevSlices ls = lev_slices(a.nb, block);
+  if (ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
+  if (probe) return CRT_OK;
+  const int st = launch_kernel(kern, dim3(a.ncol, ls.nslice, gz), ls.nthr, 0, s, a, la, out, ls.per);
+  if (st == CRT_OK) note_kernel("%s<%s> nsel=%d slice=%d", kname, sname, la.nsel, ls.per);
+  return st;
+}
+
+// n79 / zq: one wave per workgroup with W = tri_cp_lanes(scheme, nz, copies) lanes at work; kernel arguments (a, la, out, W, the staged
+// record doubles, their even-rounded count = the offset of what follows them in LDS)
+template <class K, class Out>
+int launch_deriv_tri(K kern, const char* kname, const char* sname, int scheme, int copies, unsigned gz, const SolveArgs& a, const LevArgs& la,
+                     const Out& out, hipStream_t s, bool probe) {
+  const int W = tri_cp_lanes(scheme, a.nz, copies);
+  if (W == 0) return CRT_ERR_UNSUPPORTED;
+  const long long nslice = ((long long)a.nb + W - 1) / W;
+  if (nslice > 65535) return CRT_ERR_UNSUPPORTED;
+  if (probe) return CRT_OK;
+  const int nrec = jac_tri_nrec(scheme, a.nz), off = (nrec + 1) & ~1;
+  const int st = launch_kernel(kern, dim3(a.ncol, (unsigned)nslice, gz), 64, tri_cp_lds_bytes(scheme, a.nz, W, copies), s, a, la, out, W, nrec, off);
+  if (st == CRT_OK) note_kernel("%s<%s> nsel=%d slice=%d", kname, sname, la.nsel, W);
+  return st;
+}
+
+// tau_d' and its kin: one thread per LAI value, 256 per workgroup, once the quadrature tables are on the device; `args`: the kernel's
+template <class K, class... Args>
+int launch_per_lai(K kern, long long n, hipStream_t s, Args... args) {
+  const int st = init_quadrature(s);
+  if (st != CRT_OK) return st;
+  const long long nblk = (n + 255) / 256;
+  if (nblk > 0x7fffffffLL) return CRT_ERR_UNSUPPORTED;
+  return launch_kernel(kern, dim3((unsigned)nblk), 256, 0, s, args...);
 }
 
 }  // namespace crt

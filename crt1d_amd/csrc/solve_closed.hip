@@ -1359,9 +1359,6 @@ int launch_closed(int scheme, const SolveArgs& a, hipStream_t s, int force, cons
   }
 }
 
-int upload_quad_closed(const QuadConst& h, hipStream_t s) {
-  return hipMemcpyToSymbolAsync(HIP_SYMBOL(qc), &h, sizeof(QuadConst), 0, hipMemcpyHostToDevice, s) == hipSuccess ? (int)CRT_OK
-                                                                                                                   : (int)CRT_ERR_LAUNCH;
-}
+int upload_quad_closed(const QuadConst& h, hipStream_t s) { return upload_qc(h, s); }
 
 }  // namespace crt
