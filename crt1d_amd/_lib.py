@@ -341,6 +341,35 @@ def _dleaf_signatures():
 _DLEAF_SIGNATURES = _dleaf_signatures()
 DLEAF_EXPORTS = list(_DLEAF_SIGNATURES)
 
+# gradient of a weighted sum of the level spectra (include/crt1d_hip_grad.h), again a header and a table of their own: the three
+# derivatives above contracted with one set of weights in one kernel; the closed forms only
+
+
+class CrtGradWeights(ctypes.Structure):
+    """``crt_grad_weights``: d loss / d X at the selected levels, each ``[ncol][nsel][nb]`` or NULL."""
+
+    _fields_ = [(k, _vp) for k in ("I_dr", "I_df_d", "I_df_u", "F")]
+
+
+class CrtGradOut(ctypes.Structure):
+    """``crt_grad_out``: the optics gradients ``[ncol][nb]``, ``lai`` and ``leaf`` ``[ncol]``; NULL = not formed."""
+
+    _fields_ = [(k, _vp) for k in ("leaf_r", "leaf_t", "soil_r", "lai", "leaf")]
+
+
+def _grad_signatures():
+    P = ctypes.POINTER
+    i, i32, sz, ok = ctypes.c_int, ctypes.c_int32, ctypes.c_size_t, ctypes.c_int
+    return {
+        "crt_hip_levels_grad_workspace_bytes": (sz, [i, i32, i32, i32, i32]),
+        "crt_hip_levels_grad_f64": (ok, [i, P(CrtColumns), P(CrtBands), P(CrtOptions), P(i32), i32, P(CrtGradWeights), P(CrtLeafTangent),
+                                         P(CrtGradOut), _vp, sz, _vp]),
+    }
+
+
+_GRAD_SIGNATURES = _grad_signatures()
+GRAD_EXPORTS = list(_GRAD_SIGNATURES)
+
 _lib = None
 
 
@@ -364,7 +393,7 @@ def load():
 
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES, **_SENSOR_SIGNATURES, **_JAC_SIGNATURES,
-                                      **_DLAI_SIGNATURES, **_DLEAF_SIGNATURES}.items():
+                                      **_DLAI_SIGNATURES, **_DLEAF_SIGNATURES, **_GRAD_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:

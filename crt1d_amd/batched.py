@@ -1618,3 +1618,205 @@ def sensor_dleaf(scheme, cols: Columns, bands: Bands, levels, tangent: LeafTange
     contraction with the sensor set's dense weights runs in torch on the device, as in :func:`sensor_dlai`."""
     return _sensor_contract(sensors, cols, bands, "crb,sb->crs", lambda: LevelsDleafPlan._check_static(scheme, **kw),
                             lambda: solve_levels_dleaf(scheme, cols, bands, levels, tangent, **kw))
+
+
+# ---- gradient of a weighted sum of the level spectra (include/crt1d_hip_grad.h) -----------------------------------------------------------
+
+GRAD_SCHEMES = ("2s", "bl", "g77", "bf")  # the schemes k_grad serves; LevelsGradPlan composes the three plans above for n79 and zq
+GRAD_WRT = JAC_PARAMS + ("lai", "leaf")
+
+
+def levels_grad_workspace_bytes(scheme, ncol, nz, nb, nsel):
+    """Device workspace of a :class:`LevelsGradPlan` call of a scheme of ``GRAD_SCHEMES``: the records of :func:`workspace_bytes` at the
+    same offsets, the side records of the LAI and of the leaf-angle derivative, and the slice sums of ``lai`` and ``leaf``."""
+    return _levels_deriv_workspace_bytes("crt_hip_levels_grad_workspace_bytes", scheme, ncol, nz, nb, nsel)
+
+
+def _grad_weights(weights, shape=None, device=None):
+    """The weights of :class:`LevelsGradPlan` as ``{key: tensor}`` in the order of ``LEVEL_KEYS``; with ``shape``: each checked as a
+    caller-supplied array the kernel reads through a bare pointer."""
+    if not isinstance(weights, dict) or not weights or any(k not in LEVEL_KEYS for k in weights):
+        raise ValueError(f"weights must be a dict of (ncol, nsel, nb) tensors under keys out of {LEVEL_KEYS}")
+    if shape is None:
+        return weights
+    return {k: _check_profile(weights[k], f"weights[{k!r}]", shape, device) for k in LEVEL_KEYS if k in weights}
+
+
+class LevelsGradPlan(_LevelsDerivPlan):
+    """Pre-validated gradient of the scalar ``sum_X sum(weights[X] * X)`` of the level spectra ``X[c, levels[r], b]`` (what
+    :class:`LevelsPlan` returns; ``weights``: ``{key: (ncol, nsel, nb)}`` float64, any of ``I_dr, I_df_d, I_df_u, F`` -- in a retrieval
+    ``d loss / d X``) with respect to ``wrt``, any of ``GRAD_WRT``:
+
+    ``leaf_r``, ``leaf_t``, ``soil_r``  ``(ncol, nb)``: band by band, each row a column's own response (shared ``(nb,)`` spectra: their
+    gradient is the sum over the rows); ``lai``  ``(ncol,)``: per ``ln LAI`` at a fixed leaf-area profile (``per="lai"``: per LAI), the
+    convention of :class:`LevelsDlaiPlan`; ``leaf``  ``(ncol,)``: along ``tangent`` (a :class:`LeafTangent`; ``None``:
+    ``leaf_tangent(cols, "param")``).
+
+    It is the contraction of what :class:`LevelsJacPlan`, :class:`LevelsDlaiPlan` and :class:`LevelsDleafPlan` return with the weights.
+    For ``GRAD_SCHEMES`` one column precompute and ONE kernel form it (``crt_hip_levels_grad_f64``) from the same tangent bits without
+    writing a derivative array; for n79 and zq the plan runs those three plans and contracts in torch: the same result dict.  ``4s`` and
+    ``zq_pa`` are a ValueError.  The weights are read at every call: update them in place.  There is no gradient with respect to
+    ``I_dr0`` / ``I_df0`` (the spectra are linear in them).  A column's result is bitwise the same alone or in any batch and for any
+    subset of ``wrt``."""
+
+    _entry_name, _ws_query, _out_struct = "crt_hip_levels_grad_f64", "crt_hip_levels_grad_workspace_bytes", "CrtGradOut"
+    _all_keys, _schemes, _what = GRAD_WRT, DLAI_SCHEMES, "gradient"
+    _no_kernel = "scheme {!r} has no gradient; served: " + ", ".join(DLAI_SCHEMES)
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, levels, weights, *, wrt=GRAD_WRT, tangent=None, per="log", mu_s=0.501,
+                 tau_d_method="quad", out=None, workspace=None):
+        wrt = self._check_static(scheme, tau_d_method, wrt, weights=weights, tangent=tangent, per=per)
+        if bands.dtype != torch.float64:
+            raise TypeError(f"the {self._what} has no f32 storage form: bands must be float64")
+        self.levels, self.keys, self.per = normalize_levels(levels, cols.nz), wrt, per
+        self._kw = dict(mu_s=mu_s, tau_d_method=tau_d_method)
+        self._bind(scheme, cols, bands, mu_s, tau_d_method)
+        ncol, nsel, nb, dev = cols.ncol, len(self.levels), bands.nb, cols.device
+        self.weights = _grad_weights(weights, (ncol, nsel, nb), dev)
+        if "leaf" in wrt:
+            tangent = leaf_tangent(cols, "param") if tangent is None else tangent
+            if tangent.dg_table.shape[0] != ncol or tangent.dg_table.device != dev:
+                raise ValueError("the tangent must have the columns' ncol and device")
+        self.tangent = tangent if "leaf" in wrt else None
+        out = _outputs({k: (ncol, nb) if k in JAC_PARAMS else (ncol,) for k in wrt}, out, torch.float64, dev, "output {!r}", lacks=True)
+        self.out = {k: out[k] for k in wrt}
+        self._lai_total = cols.lai[:, 0].contiguous() if per == "lai" and "lai" in wrt else None
+        self._lev = (ctypes.c_int32 * nsel)(*self.levels)
+        self._composed = scheme not in GRAD_SCHEMES
+        if self._composed:
+            self._compose(workspace)
+            return
+        self._w = _lib.CrtGradWeights(*[self.weights[k].data_ptr() if k in self.weights else None for k in LEVEL_KEYS])
+        self._tan = None if self.tangent is None else self.tangent.c_struct()
+        self._out = _lib.CrtGradOut(*[out[k].data_ptr() if k in wrt else None for k in GRAD_WRT])
+        self._finish(self._entry_name, levels_grad_workspace_bytes(scheme, ncol, cols.nz, nb, nsel), workspace)
+
+    @staticmethod
+    def _check_extras(weights=None, tangent=None, per="log", **_):
+        _grad_weights(weights)
+        _dlai_per(per)
+        if tangent is not None and not isinstance(tangent, LeafTangent):
+            raise TypeError("tangent must be a LeafTangent")
+
+    def _tail(self):
+        return (self._lev, len(self.levels), ctypes.byref(self._w), None if self._tan is None else ctypes.byref(self._tan),
+                ctypes.byref(self._out))
+
+    def _compose(self, workspace):
+        """n79, zq: the plans whose outputs the call contracts (only those ``wrt`` and the weights need)."""
+        if workspace is not None:
+            raise ValueError(f"the gradient of {self.scheme} runs three plans with workspaces of their own: workspace must be None")
+        kw = self._kw
+        a = (self.scheme, self.cols, self.bands, self.levels)
+        jk = tuple(k for k in JAC_KEYS if k in self.weights)
+        lk = tuple(self.weights)
+        self._plans = {}
+        if jk and any(k in JAC_PARAMS for k in self.keys):
+            self._plans["jac"] = LevelsJacPlan(*a, keys=jk, **kw)
+        if "lai" in self.keys:
+            self._plans["lai"] = LevelsDlaiPlan(*a, keys=lk, **kw)
+        if "leaf" in self.keys:
+            self._plans["leaf"] = LevelsDleafPlan(*a, self.tangent, keys=lk, **kw)
+
+    def last_kernel(self):
+        """n79, zq: the reports of the plans of this plan's most recent call, joined by `` | ``."""
+        return self._report if self._composed else super().last_kernel()
+
+    def __call__(self, stream=None, *, flags=0):
+        s = torch.cuda.current_stream(self.cols.device) if stream is None else stream
+        if not self._composed:
+            out = super().__call__(stream, flags=flags)
+        else:
+            out = self.out
+            d, reports = {}, []
+            for n, p in self._plans.items():
+                d[n] = p(stream, flags=flags)
+                reports.append(p.last_kernel())
+            self._report = " | ".join(reports)
+            if not flags & _lib.FLAG_PRECOMPUTE_ONLY:
+                with torch.cuda.stream(s):
+                    for k in self.keys:
+                        if k in JAC_PARAMS:
+                            out[k].zero_()
+                            for x, J in d.get("jac", {}).items():
+                                out[k] += (self.weights[x] * J[:, :, JAC_PARAMS.index(k), :]).sum(1)
+                        else:
+                            out[k].zero_()
+                            for x, D in d[k].items():
+                                out[k] += (self.weights[x] * D).sum((1, 2))
+        if self._lai_total is not None and not flags & _lib.FLAG_PRECOMPUTE_ONLY:
+            with torch.cuda.stream(s):
+                out["lai"].div_(self._lai_total)
+        return out
+
+
+def solve_levels_grad(scheme, cols: Columns, bands: Bands, levels, weights, **kw):
+    """One-shot :class:`LevelsGradPlan`: ``{name: (ncol, nb) | (ncol,)}`` for the names ``wrt``."""
+    LevelsGradPlan._check_static(scheme, kw.get("tau_d_method", "quad"), kw.get("wrt", GRAD_WRT), weights=weights,
+                                 tangent=kw.get("tangent"), per=kw.get("per", "log"))  # (before any device is touched)
+    with torch.cuda.device(cols.device):
+        return LevelsGradPlan(scheme, cols, bands, levels, weights, **kw)()
+
+
+class _LevelsAD(torch.autograd.Function):
+    """``solve_levels`` with a backward pass: one :class:`LevelsGradPlan` call on the incoming ``d loss / d X``."""
+
+    @staticmethod
+    def forward(ctx, st, leaf_r, leaf_t, soil_r, lai_scale, g_param):
+        ctx.st = st
+        out = LevelsPlan(st["scheme"], st["cols"], st["bands"], st["levels"], keys=st["keys"], **st["kw"])()
+        return tuple(out[k] for k in st["keys"])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        st = ctx.st
+        names = ("leaf_r", "leaf_t", "soil_r", "lai", "leaf")
+        need = ctx.needs_input_grad[1:]
+        wrt = tuple(n for n, w in zip(names, need) if w)
+        if not wrt:
+            return (None,) * 6
+        weights = {k: g.contiguous() for k, g in zip(st["keys"], grads)}
+        g = LevelsGradPlan(st["scheme"], st["cols"], st["bands"], st["levels"], weights, wrt=wrt, **st["kw"])()
+        res = []
+        for n, t in zip(names, (st["bands"].leaf_r, st["bands"].leaf_t, st["bands"].soil_r, st["lai_scale"], st["cols"].g_param)):
+            if n not in wrt:
+                res.append(None)
+            elif n in JAC_PARAMS:  # one spectrum shared by all columns: the sum of the columns' own responses
+                res.append(g[n].sum(0, keepdim=True) if t.shape[0] == 1 and g[n].shape[0] != 1 else g[n])
+            elif n == "lai":  # d / d lai_scale = (d / d ln LAI) / lai_scale
+                res.append(g[n] / t)
+            else:
+                res.append(g[n])
+        return (None, *res)
+
+
+def solve_levels_ad(scheme, cols: Columns, bands: Bands, levels, *, keys=LEVEL_KEYS, lai_scale=None, mu_s=0.501, tau_d_method="quad"):
+    """:func:`solve_levels` attached to torch's autograd graph: ``{key: (ncol, nsel, nb)}`` whose ``.backward()`` fills ``.grad`` of
+    whichever of ``bands.leaf_r``, ``bands.leaf_t``, ``bands.soil_r``, ``lai_scale`` and ``cols.g_param`` require grad.
+
+    ``lai_scale`` ``(ncol,)``: the solve runs on ``cols.lai * lai_scale[:, None]`` (``None``: on ``cols.lai``, bitwise
+    :func:`solve_levels`).  The backward pass is one :class:`LevelsGradPlan` call on the incoming gradients (``GRAD_SCHEMES``: one
+    kernel; n79, zq: composed), once-differentiable.  Shared ``(nb,)`` spectra receive the sum over the columns, ``lai_scale`` receives
+    ``lai / lai_scale``, ``cols.g_param`` the gradient along ``leaf_tangent(cols, "param")``.  Spectra that require grad must be float64.
+    There is no gradient with respect to ``I_dr0`` / ``I_df0``: a ValueError where they require grad, as is ``4s`` / ``zq_pa``."""
+    LevelsGradPlan._check_options(LevelsGradPlan, scheme, tau_d_method)
+    if scheme not in LevelsGradPlan._schemes:
+        raise ValueError(LevelsGradPlan._no_kernel.format(scheme))
+    keys = _level_keys(keys)
+    for n in ("I_dr0", "I_df0"):
+        if getattr(bands, n).requires_grad:
+            raise ValueError(f"bands.{n} requires grad, but the level spectra have no gradient kernel with respect to it (they are linear in it)")
+    if bands.dtype != torch.float64:
+        raise TypeError("solve_levels_ad has no f32 storage form: bands must be float64")
+    cols_f = cols
+    if lai_scale is not None:
+        lai_scale = _f64(lai_scale, "lai_scale")
+        if lai_scale.shape != (cols.ncol,):
+            raise ValueError("lai_scale must be (ncol,)")
+        cols_f = Columns(cols.psi, cols.lai.detach() * lai_scale.detach()[:, None], cols.g_kind, cols.g_param, cols.mla, cols.g_at_psi, cols.g_table)
+    st = dict(scheme=scheme, cols=cols_f, bands=bands, levels=normalize_levels(levels, cols.nz), keys=keys, lai_scale=lai_scale,
+              kw=dict(mu_s=mu_s, tau_d_method=tau_d_method))
+    with torch.cuda.device(cols.device):
+        out = _LevelsAD.apply(st, bands.leaf_r, bands.leaf_t, bands.soil_r, lai_scale, cols.g_param)
+    return dict(zip(keys, out))

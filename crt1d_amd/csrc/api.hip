@@ -667,11 +667,13 @@ static size_t levels_deriv_workspace_bytes(SideLen len, int scheme, int32_t ncol
 
 // args_ok: the entry's own pointers are there (an output at least).  pre_report: what a CRT_FLAG_PRECOMPUTE_ONLY call reports where the
 // scheme has a side record ("k_colpre" where it has none; an entry without side_len leaves K0's report).
-// launch(sa, la, side, s, probe): the entry's derivative kernel;  side_pre(ca, side, s): its side precompute, after K0 on the same stream.
+// launch(sa, la, side, s, probe): the entry's derivative kernel;  side_pre(ca, side, s): its side precompute, after K0 on the same stream
+// (the gradient runs two, into two side records one behind the other).  closed_only: n79 and zq are not served either;  tail_bytes: what the
+// entry keeps behind the side records (the gradient's slice sums).
 template <class Launch, class SidePre>
 static int levels_deriv_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
                              int32_t nsel, void* workspace, size_t workspace_bytes, crt_stream_t stream, bool args_ok, SideLen side_len,
-                             const char* pre_report, Launch launch, SidePre side_pre) {
+                             const char* pre_report, Launch launch, SidePre side_pre, bool closed_only = false, size_t tail_bytes = 0) {
   if (!scheme_ok(scheme) || !cols || !levels || !args_ok) return CRT_ERR_BAD_ARG;
   LevArgs la = {};
   if (const int st = parse_levels(cols, levels, nsel, la)) return st;
@@ -679,9 +681,10 @@ static int levels_deriv_impl(int scheme, const crt_columns* cols, const crt_band
   const crt_outputs none = {};
   const bool sized = cols->ncol > 0 && cols->nz > 0;
   const int chk = check_solve(scheme, cols, bands, opts, &none, workspace, workspace_bytes, nullptr, &la, nullptr, o,
-                              sized ? side_bytes(side_len, scheme, cols->ncol, cols->nz) : 0);
+                              sized ? side_bytes(side_len, scheme, cols->ncol, cols->nz) + tail_bytes : 0);
   if (chk == CRT_ERR_BAD_ARG || chk == CRT_ERR_SHAPE) return chk;  // an argument error is one for every scheme
   if (scheme == CRT_SCHEME_4S || scheme == CRT_SCHEME_ZQ_PA) return CRT_ERR_UNSUPPORTED;  // whatever the workspace (a follow-up: crt1d_hip_jac.h)
+  if (closed_only && is_tri(scheme)) return CRT_ERR_UNSUPPORTED;                          // (the gradient: crt1d_hip_grad.h)
   if (chk != CRT_OK) return chk;
   ColArgs ca;
   SolveArgs sa;
@@ -770,6 +773,41 @@ int crt_hip_dtau_d_dleaf_f64(const double* kb_nodes, const double* dkb_nodes, co
   if (method != CRT_TAU_D_QUAD && method != CRT_TAU_D_9SKY) return CRT_ERR_BAD_ARG;
   if (n == 0) return CRT_OK;
   return crt::launch_dtau_d_dleaf(kb_nodes, dkb_nodes, L, (long long)n, method, out, static_cast<hipStream_t>(stream));
+}
+
+// the gradient of a weighted sum of the level spectra (crt1d_hip_grad.h): both side records (the dlai ones first), then the slice sums
+size_t crt_hip_levels_grad_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nsel) {
+  const size_t rec = levels_deriv_workspace_bytes(grad_side_len, scheme, ncol, nz, nb, nsel);
+  return rec == 0 ? 0 : rec + grad_part_bytes(ncol, nb);
+}
+
+int crt_hip_levels_grad_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
+                            int32_t nsel, const crt_grad_weights* w, const crt_leaf_tangent* tangent, const crt_grad_out* out,
+                            void* workspace, size_t workspace_bytes, crt_stream_t stream) {
+  const bool args_ok = w && (w->I_dr || w->I_df_d || w->I_df_u || w->F) && out &&
+                       (out->leaf_r || out->leaf_t || out->soil_r || out->lai || out->leaf) &&
+                       (!out->leaf || (tangent && tangent->dg_table && tangent->dg_at_psi));
+  // (sizes that are not positive are an argument error of the shared path: no tail then)
+  const bool sized = cols && bands && cols->ncol > 0 && cols->nz > 0 && bands->nb > 0;
+  const bool side_lai = args_ok && out->lai && sized && dlai_side_len(scheme, cols->nz) > 0, side_leaf = args_ok && out->leaf;
+  return levels_deriv_impl(
+      scheme, cols, bands, opts, levels, nsel, workspace, workspace_bytes, stream, args_ok, grad_side_len,
+      side_lai && side_leaf ? "k_colpre + k_dlai_side + k_dleaf_side" : side_lai ? "k_colpre + k_dlai_side" : side_leaf ? "k_colpre + k_dleaf_side" : "k_colpre",
+      [&](const SolveArgs& sa, const LevArgs& la, const double* side, hipStream_t s, bool probe) {
+        const double* const side2 = side + (size_t)sa.ncol * dlai_side_len(scheme, sa.nz);
+        double* const part = const_cast<double*>(side) + (size_t)sa.ncol * grad_side_len(scheme, sa.nz);
+        return launch_grad(scheme, sa, la,
+                           GradArgs{{w->I_dr, w->I_df_d, w->I_df_u, w->F}, {out->leaf_r, out->leaf_t, out->soil_r}, out->lai, out->leaf, side, side2, part}, s,
+                           probe);
+      },
+      [&](const ColArgs& ca, double* side, hipStream_t s) {
+        if (side_lai)
+          if (const int st = launch_dlai_side(ca, side, s)) return st;
+        if (!side_leaf) return (int)CRT_OK;
+        return launch_dleaf_side(ca, DleafTan{tangent->dg_table, tangent->dg_at_psi, tangent->dmla},
+                                 side + (size_t)ca.ncol * dlai_side_len(scheme, ca.nz), s);
+      },
+      true, sized ? grad_part_bytes(cols->ncol, bands->nb) : 0);
 }
 
 int crt_hip_bandsum_finish_f64(const crt_columns* cols, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream) {

@@ -10,6 +10,7 @@
 #include "crt1d_hip.h"
 #include "crt1d_hip_dlai.h"
 #include "crt1d_hip_dleaf.h"
+#include "crt1d_hip_grad.h"
 #include "crt1d_hip_jac.h"
 #include "crt1d_hip_sensor.h"
 
@@ -975,6 +976,23 @@ int launch_dleaf_side(const ColArgs& ca, const DleafTan& tn, double* side, hipSt
 int launch_dleaf(int scheme, const SolveArgs& a, const LevArgs& la, const DlaiArgs& da, hipStream_t s, bool probe);
 int launch_g_dparam(int ncol, const double* psi, const int32_t* g_kind, const double* g_param, double* dg_table, double* dg_at_psi, hipStream_t s);
 int launch_dtau_d_dleaf(const double* kb_nodes, const double* dkb_nodes, const double* L, long long n, int method, double* out, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------
+// Gradient of a weighted sum of the level spectra (crt_hip_levels_grad_f64, include/crt1d_hip_grad.h; kernels in grad.hip): 2s, bl, g77, bf
+struct GradArgs {
+  const double* w[4];       // d loss / d (I_dr, I_df_d, I_df_u, F): [ncol][nsel][nb] or NULL
+  double* o[3];             // d loss / d (leaf_r, leaf_t, soil_r): [ncol][nb] or NULL
+  double* lai;              // [ncol] or NULL
+  double* leaf;             // [ncol] or NULL
+  const double* side_lai;   // side records of k_dlai_side [ncol][dlai_side_len]   (read for bl with `lai`)
+  const double* side_leaf;  // side records of k_dleaf_side [ncol][dleaf_side_len] (read with `leaf`)
+  double* part;             // [ncol][nslice][2]: the slice sums of lai, leaf (several band slices)
+};
+constexpr int GRAD_BLOCK = 256;  // bands per slice at most
+// doubles behind the K0 records: both side records of every column (the dlai ones first), then the slice sums
+constexpr int grad_side_len(int scheme, int nz) { return dlai_side_len(scheme, nz) + dleaf_side_len(scheme, nz); }
+inline size_t grad_part_bytes(int ncol, int nb) { return (size_t)ncol * (size_t)lev_slices(nb, GRAD_BLOCK).nslice * 2 * sizeof(double); }
+int launch_grad(int scheme, const SolveArgs& a, const LevArgs& la, const GradArgs& ga, hipStream_t s, bool probe);
 
 // launchers implemented in the .hip files
 int launch_colpre(const ColArgs& a, hipStream_t s);

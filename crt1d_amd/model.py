@@ -325,6 +325,30 @@ class Model:
         out = batched.solve_levels_jac(scheme, cols, b, (0, -1) if levels is None else levels)
         return {k: v[0].cpu().numpy() for k, v in out.items()}
 
+    def run_gradient(self, weights, levels=None, wrt=("leaf_r", "leaf_t", "soil_r", "lai", "leaf")):
+        """The gradient of the scalar ``sum_X sum(weights[X] * X)`` of the rows ``levels`` (default: the ground and the top) of
+        ``I_dr, I_df_d, I_df_u, F`` -- ``weights``: ``{key: (nsel, n_wl)}``, in a retrieval ``d loss / d X`` -- with respect to the names
+        ``wrt`` (:class:`crt1d_amd.batched.LevelsGradPlan`): ``leaf_r``, ``leaf_t``, ``soil_r`` as NumPy arrays ``(n_wl,)``, ``lai`` (per
+        ``ln LAI``) and ``leaf`` (per unit of this case's leaf-angle parameter) as floats.  ValueError for ``4s`` and ``zq_pa``.  The
+        model's own state (``out``) is not changed."""
+        import torch
+
+        from . import batched
+
+        self._check_inputs()
+        p = self._p
+        scheme, cols, b, sun = self._series_inputs(np.atleast_1d(float(p["psi"])), None, None, "gradient")
+        if scheme not in batched.LevelsGradPlan._schemes:
+            raise ValueError(batched.LevelsGradPlan._no_kernel.format(scheme))
+        if not isinstance(weights, dict):
+            raise ValueError("weights must be a dict of (nsel, n_wl) arrays")
+        cols = batched.Columns(psi=sun.psi[:, 0].contiguous(), lai=cols.lai, g_kind=cols.g_kind, g_param=cols.g_param, mla=cols.mla,
+                               g_at_psi=None if sun.g_at_psi is None else sun.g_at_psi[:, 0].contiguous(), g_table=cols.g_table)
+        b = batched.Bands(sun.I_dr0[:, 0].contiguous(), sun.I_df0[:, 0].contiguous(), b.leaf_r, b.leaf_t, b.soil_r)
+        w = {k: torch.as_tensor(np.ascontiguousarray(v, dtype=np.float64)[None]).to(cols.device) for k, v in weights.items()}
+        out = batched.solve_levels_grad(scheme, cols, b, (0, -1) if levels is None else levels, w, wrt=wrt)
+        return {k: v[0].cpu().numpy() if v.ndim == 2 else float(v[0]) for k, v in out.items()}
+
     def run_lai_sensitivity(self, levels=None, per="log"):
         """The exact derivative of the rows ``levels`` (default: the ground and the top) of ``I_dr, I_df_d, I_df_u, F`` with respect to
         this case's leaf area index at a fixed leaf-area profile (:class:`crt1d_amd.batched.LevelsDlaiPlan`): NumPy arrays
