@@ -370,6 +370,36 @@ def _grad_signatures():
 _GRAD_SIGNATURES = _grad_signatures()
 GRAD_EXPORTS = list(_GRAD_SIGNATURES)
 
+# Jacobian of the sensor-band sums (include/crt1d_hip_sensjac.h), again a header and a table of their own: the three derivatives above
+# folded with a sensor set in one kernel; the closed forms only
+SENSJAC_MAX_NTAN = 8  # CRT_SENSJAC_MAX_NTAN
+
+
+class CrtOpticsDirs(ctypes.Structure):
+    """``crt_optics_dirs``: ``ntan`` directions in (leaf_r, leaf_t, soil_r), each ``[ncol or 1][ntan][nb]`` on the device or NULL (zeros)."""
+
+    _fields_ = [("ntan", ctypes.c_int32), ("col_stride", ctypes.c_int64), ("leaf_r", _vp), ("leaf_t", _vp), ("soil_r", _vp)]
+
+
+class CrtSensJacOut(ctypes.Structure):
+    """``crt_sensjac_out``: each ``[ncol][nsel][nsens][npar]`` or NULL."""
+
+    _fields_ = [(k, _vp) for k in ("I_dr", "I_df_d", "I_df_u", "F")]
+
+
+def _sensjac_signatures():
+    P = ctypes.POINTER
+    i, i32, sz, ok = ctypes.c_int, ctypes.c_int32, ctypes.c_size_t, ctypes.c_int
+    return {
+        "crt_hip_sensor_jac_workspace_bytes": (sz, [i, i32, i32, i32, i32, i32, i32]),
+        "crt_hip_sensor_jac_f64": (ok, [i, P(CrtColumns), P(CrtBands), P(CrtOptions), P(i32), i32, P(CrtSensorSet), P(CrtOpticsDirs), i,
+                                        P(CrtLeafTangent), P(CrtSensJacOut), _vp, sz, _vp]),
+    }
+
+
+_SENSJAC_SIGNATURES = _sensjac_signatures()
+SENSJAC_EXPORTS = list(_SENSJAC_SIGNATURES)
+
 _lib = None
 
 
@@ -393,7 +423,7 @@ def load():
 
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES, **_SENSOR_SIGNATURES, **_JAC_SIGNATURES,
-                                      **_DLAI_SIGNATURES, **_DLEAF_SIGNATURES, **_GRAD_SIGNATURES}.items():
+                                      **_DLAI_SIGNATURES, **_DLEAF_SIGNATURES, **_GRAD_SIGNATURES, **_SENSJAC_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:

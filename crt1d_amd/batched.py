@@ -1758,6 +1758,192 @@ def solve_levels_grad(scheme, cols: Columns, bands: Bands, levels, weights, **kw
         return LevelsGradPlan(scheme, cols, bands, levels, weights, **kw)()
 
 
+# ---- Jacobian of the sensor-band sums (include/crt1d_hip_sensjac.h) -----------------------------------------------------------------------
+
+SENSJAC_SCHEMES = GRAD_SCHEMES  # the schemes k_sens_jac serves; SensorJacPlan composes sensor_jvp, sensor_dlai and sensor_dleaf for n79 and zq
+
+
+def sensor_jac_workspace_bytes(scheme, ncol, nz, nb, nsel, nsens, npar):
+    """Device workspace of a :class:`SensorJacPlan` call of a scheme of ``SENSJAC_SCHEMES``: the records of :func:`workspace_bytes` at the
+    same offsets, the side records of the LAI and of the leaf-angle derivative, and the slice partial sums."""
+    return int(_lib.load().crt_hip_sensor_jac_workspace_bytes(_lib.SCHEME_IDS[scheme], ncol, nz, nb, nsel, nsens, npar))
+
+
+def _sensjac_ntan(d_leaf_r=None, d_leaf_t=None, d_soil_r=None):
+    """``ntan`` of the directions of a :class:`SensorJacPlan` from their shapes alone (no device): 0 with none given."""
+    import numpy as np
+
+    ntan = set()
+    for n, d in zip(JAC_PARAMS, (d_leaf_r, d_leaf_t, d_soil_r)):
+        if d is None:
+            continue
+        shape = tuple(d.shape) if hasattr(d, "shape") else np.shape(d)
+        if len(shape) not in (2, 3):
+            raise ValueError(f"`d_{n}` must be (ntan, nb) or (ncol, ntan, nb)")
+        ntan.add(int(shape[-2]))
+    if len(ntan) > 1:
+        raise ValueError("the directions must share ntan")
+    ntan = ntan.pop() if ntan else 0
+    if not 0 <= ntan <= _lib.SENSJAC_MAX_NTAN:
+        raise ValueError(f"ntan = {ntan}; one call takes 1 .. {_lib.SENSJAC_MAX_NTAN} directions")
+    return ntan
+
+
+class SensorJacPlan(_LevelsDerivPlan):
+    """Pre-validated Jacobian of the sums of :class:`SensorLevelsPlan` with respect to a parameter vector of every column
+    (``crt_hip_sensor_jac_f64``): ``out[k][c, r, s, j]`` is the derivative of ``sum_b w_s[b] * X[c, levels[r], b]`` (``X`` in ``keys``, any
+    of ``I_dr, I_df_d, I_df_u, F``) with respect to parameter ``params[j]``, each ``(ncol, nsel, nsens, npar)`` float64.  The parameters, in
+    this order: ``ntan`` directions of a leaf or soil model, given as in :func:`sensor_jvp` (``d_leaf_r``, ``d_leaf_t``, ``d_soil_r``:
+    ``(ntan, nb)`` or ``(ncol, ntan, nb)``, ``None`` = zeros; ``"dir0"``, ``"dir1"``, ...); ``"lai"`` (``lai=True``): per ``ln LAI`` at a
+    fixed leaf-area profile, the convention of :class:`LevelsDlaiPlan`; ``"leaf"``: along ``tangent`` (a :class:`LeafTangent`; ``None``:
+    no such column).
+
+    It is what :func:`sensor_jvp`, :func:`sensor_dlai` and :func:`sensor_dleaf` return, side by side.  For ``SENSJAC_SCHEMES`` one column
+    precompute and ONE kernel form it from the same tangent bits without writing a derivative array; for n79 and zq the plan calls those
+    three functions: the same result dict.  ``4s`` and ``zq_pa`` are a ValueError.  The directions are read at every call: update them
+    in place.  ``I_dr`` does not depend on the optics (zeros in its direction columns); bl has no soil and no upward stream.  The
+    workspace also holds what a :class:`SensorLevelsPlan` of the same shape needs: that plan, called on ``plan.workspace`` with
+    ``FLAG_SKIP_PRECOMPUTE`` after this one, gives the forward sums without a second column precompute.  A column's result is bitwise
+    the same alone or in any batch, for any subset of ``keys``, and a parameter column's bits do not depend on which others exist."""
+
+    _entry_name, _ws_query, _out_struct = "crt_hip_sensor_jac_f64", "crt_hip_sensor_jac_workspace_bytes", "CrtSensJacOut"
+    _all_keys, _schemes, _what = LEVEL_KEYS, DLAI_SCHEMES, "sensor Jacobian"
+    _no_kernel = "scheme {!r} has no sensor Jacobian; served: " + ", ".join(DLAI_SCHEMES)
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, *, d_leaf_r=None, d_leaf_t=None, d_soil_r=None,
+                 lai=True, tangent=None, keys=LEVEL_KEYS, mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
+        keys = self._check_static(scheme, tau_d_method, keys, sensors=sensors, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r,
+                                  lai=lai, tangent=tangent)
+        if bands.dtype != torch.float64:
+            raise TypeError(f"the {self._what} has no f32 storage form: bands must be float64")
+        ntan = _sensjac_ntan(d_leaf_r, d_leaf_t, d_soil_r)
+        self.levels, self.keys, self.sensors = normalize_levels(levels, cols.nz), keys, sensors
+        self._kw = dict(mu_s=mu_s, tau_d_method=tau_d_method)
+        sensors.check(bands.nb, cols.device)
+        self._bind(scheme, cols, bands, mu_s, tau_d_method)
+        ncol, nsel, nb, dev = cols.ncol, len(self.levels), bands.nb, cols.device
+        dirs = {n: _jvp_direction(d, "d_" + n, ncol, nb, dev) for n, d in zip(JAC_PARAMS, (d_leaf_r, d_leaf_t, d_soil_r)) if d is not None}
+        per_col = any(d.shape[0] != 1 for d in dirs.values()) and ncol != 1
+        self.dirs = {n: (d.expand(ncol, -1, -1) if per_col else d).contiguous() for n, d in dirs.items()}
+        if tangent is not None and (tangent.dg_table.shape[0] != ncol or tangent.dg_table.device != dev):
+            raise ValueError("the tangent must have the columns' ncol and device")
+        self.tangent, self.ntan = tangent, ntan
+        self.params = tuple(f"dir{k}" for k in range(ntan)) + (("lai",) if lai else ()) + (("leaf",) if tangent is not None else ())
+        npar = len(self.params)
+        out = _outputs({k: (ncol, nsel, sensors.nsens, npar) for k in keys}, out, torch.float64, dev, "output {!r}", lacks=True)
+        self.out = {k: out[k] for k in keys}
+        self._lev = (ctypes.c_int32 * nsel)(*self.levels)
+        self._composed = scheme not in SENSJAC_SCHEMES
+        if self._composed:
+            if workspace is not None:
+                raise ValueError(f"the sensor Jacobian of {scheme} runs plans with workspaces of their own: workspace must be None")
+            self._report = ""
+            return
+        self._sens = sensors.c_struct()
+        self._dirs = None
+        if ntan:
+            self._dirs = _lib.CrtOpticsDirs(ntan, ntan * nb if per_col else 0,
+                                            *[self.dirs[n].data_ptr() if n in self.dirs else None for n in JAC_PARAMS])
+        self._tan = None if tangent is None else tangent.c_struct()
+        self._out = _lib.CrtSensJacOut(*[out[k].data_ptr() if k in keys else None for k in LEVEL_KEYS])
+        need = max(sensor_jac_workspace_bytes(scheme, ncol, cols.nz, nb, nsel, sensors.nsens, npar),
+                   sensor_workspace_bytes(scheme, ncol, cols.nz, nb, nsel, sensors.nsens))
+        self._finish(self._entry_name, need, workspace)
+
+    @staticmethod
+    def _check_extras(sensors=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, tangent=None, **_):
+        if not isinstance(sensors, SensorSet):
+            raise TypeError("sensors must be a SensorSet")
+        if tangent is not None and not isinstance(tangent, LeafTangent):
+            raise TypeError("tangent must be a LeafTangent")
+        if _sensjac_ntan(d_leaf_r, d_leaf_t, d_soil_r) + bool(lai) + (tangent is not None) == 0:
+            raise ValueError("no parameter at all: give a direction, lai=True or a tangent")
+
+    def _tail(self):
+        ref = lambda x: None if x is None else ctypes.byref(x)  # noqa: E731
+        return (self._lev, len(self.levels), ctypes.byref(self._sens), ref(self._dirs), int("lai" in self.params), ref(self._tan),
+                ctypes.byref(self._out))
+
+    def last_kernel(self):
+        """n79, zq: the reports of the calls of this plan's most recent call, joined by `` | ``."""
+        return self._report if self._composed else super().last_kernel()
+
+    def __call__(self, stream=None, *, flags=0):
+        if not self._composed:
+            return super().__call__(stream, flags=flags)
+        if flags:
+            raise ValueError(f"the sensor Jacobian of {self.scheme} is composed of three calls: it takes no flags")
+        s = torch.cuda.current_stream(self.cols.device) if stream is None else stream
+        a, reports, ntan = (self.scheme, self.cols, self.bands, self.levels), [], self.ntan
+        last = lambda: reports.append(self.lib.crt_hip_last_kernel().decode())  # noqa: E731
+        with torch.cuda.stream(s):
+            for v in self.out.values():
+                v.zero_()
+            jk = tuple(k for k in JAC_KEYS if k in self.keys)
+            if ntan and jk:
+                d = sensor_jvp(*a, self.sensors, *[self.dirs.get(n) for n in JAC_PARAMS], keys=jk, **self._kw)
+                last()
+                for k, v in d.items():
+                    self.out[k][..., :ntan] = v
+            if "lai" in self.params:
+                d = sensor_dlai(*a, self.sensors, keys=self.keys, **self._kw)
+                last()
+                for k, v in d.items():
+                    self.out[k][..., ntan] = v
+            if "leaf" in self.params:
+                d = sensor_dleaf(*a, self.tangent, self.sensors, keys=self.keys, **self._kw)
+                last()
+                for k, v in d.items():
+                    self.out[k][..., len(self.params) - 1] = v
+        self._report = " | ".join(reports)
+        return self.out
+
+
+def sensor_jacobian(scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, **kw):
+    """One-shot :class:`SensorJacPlan`: ``{key: (ncol, nsel, nsens, npar)}`` at the sorted levels ``normalize_levels(levels, nz)``."""
+    SensorJacPlan._check_static(scheme, kw.get("tau_d_method", "quad"), kw.get("keys"), sensors=sensors, d_leaf_r=kw.get("d_leaf_r"),
+                                d_leaf_t=kw.get("d_leaf_t"), d_soil_r=kw.get("d_soil_r"), lai=kw.get("lai", True),
+                                tangent=kw.get("tangent"))  # (before any device is touched)
+    with torch.cuda.device(cols.device):
+        return SensorJacPlan(scheme, cols, bands, levels, sensors, **kw)()
+
+
+def gauss_newton_step(J, r, *, damping=0.0):
+    """One damped Gauss-Newton (Levenberg-Marquardt) step of every column: ``J`` ``(ncol, nobs, npar)``, ``r`` ``(ncol, nobs)`` ->
+    ``delta`` ``(ncol, npar)``, the solution of ``(J^T J + damping * diag(J^T J)) delta = -J^T r`` (``damping``: a number, or ``(ncol,)`` for a
+    damping of every column's own).  Plain torch on the tensors' device: the
+    normal equations, scaled to a unit diagonal, are solved by a Cholesky factorisation written as ``npar`` vector steps over the
+    columns (no pivoting is needed, no solver library is called).  A parameter whose Jacobian column is zero gets ``delta = 0``.  A
+    convenience for a handful of parameters, not a hot path."""
+    if J.ndim != 3 or r.shape != J.shape[:2]:
+        raise ValueError("J must be (ncol, nobs, npar) and r (ncol, nobs)")
+    lam = torch.as_tensor(damping, dtype=J.dtype, device=J.device)
+    if lam.ndim > 1 or (lam.ndim == 1 and lam.shape[0] != J.shape[0]) or bool((lam < 0).any()):
+        raise ValueError("damping must be a number or (ncol,), >= 0")
+    A = torch.einsum("coi,coj->cij", J, J)
+    g = torch.einsum("coi,co->ci", J, r)
+    n = A.shape[1]
+    diag = torch.diagonal(A, dim1=1, dim2=2)
+    dead = diag <= 0
+    sc = torch.where(dead, torch.ones_like(diag), diag).rsqrt()
+    A = A * sc[:, :, None] * sc[:, None, :]
+    A = A + torch.diag_embed(torch.where(dead, torch.ones_like(diag), lam.reshape(-1, 1).expand_as(diag)))
+    y = -g * sc
+    L = torch.zeros_like(A)
+    for j in range(n):  # A = L L^T, column by column
+        d = (A[:, j, j] - (L[:, j, :j] ** 2).sum(1)).sqrt()
+        L[:, j, j] = d
+        if j + 1 < n:
+            L[:, j + 1:, j] = (A[:, j + 1:, j] - torch.einsum("cik,ck->ci", L[:, j + 1:, :j], L[:, j, :j])) / d[:, None]
+    z = torch.zeros_like(y)
+    for j in range(n):  # L z = y
+        z[:, j] = (y[:, j] - (L[:, j, :j] * z[:, :j]).sum(1)) / L[:, j, j]
+    x = torch.zeros_like(y)
+    for j in reversed(range(n)):  # L^T x = z
+        x[:, j] = (z[:, j] - (L[:, j + 1:, j] * x[:, j + 1:]).sum(1)) / L[:, j, j]
+    return x * sc
+
+
 class _LevelsAD(torch.autograd.Function):
     """``solve_levels`` with a backward pass: one :class:`LevelsGradPlan` call on the incoming ``d loss / d X``."""
 

@@ -810,6 +810,78 @@ int crt_hip_levels_grad_f64(int scheme, const crt_columns* cols, const crt_bands
       true, sized ? grad_part_bytes(cols->ncol, bands->nb) : 0);
 }
 
+// the Jacobian of the sensor-band sums (crt1d_hip_sensjac.h): the workspace of the gradient with the slice sums of k_sens_jac as its tail
+size_t crt_hip_sensor_jac_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nsel, int32_t nsens, int32_t npar) {
+  if (nsens < 1 || nsens > CRT_MAX_SENSOR_BANDS || npar < 1 || npar > CRT_SENSJAC_MAX_NTAN + 2) return 0;
+  const size_t rec = levels_deriv_workspace_bytes(grad_side_len, scheme, ncol, nz, nb, nsel);
+  return rec == 0 ? 0 : rec + sensjac_part_bytes(ncol, nb, nsel, nsens, npar);
+}
+
+int crt_hip_sensor_jac_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
+                           int32_t nsel, const crt_sensor_set* sensors, const crt_optics_dirs* dirs, int with_lai,
+                           const crt_leaf_tangent* tangent, const crt_sensjac_out* out, void* workspace, size_t workspace_bytes,
+                           crt_stream_t stream) {
+  SensJacArgs ja = {};
+  SensArgs& sn = ja.sn;
+  const int ntan = dirs ? dirs->ntan : 0;
+  bool args_ok = sensors && sensors->first && sensors->count && sensors->w && sensors->nsens >= 1 && sensors->nsens <= CRT_MAX_SENSOR_BANDS &&
+                 bands && bands->nb > 0 && out && (out->I_dr || out->I_df_d || out->I_df_u || out->F) && ntan >= 0 &&
+                 ntan <= CRT_SENSJAC_MAX_NTAN && (ntan == 0 || dirs->leaf_r || dirs->leaf_t || dirs->soil_r) &&
+                 (ntan == 0 || dirs->col_stride == 0 || dirs->col_stride == (int64_t)ntan * bands->nb) &&
+                 (!tangent || (tangent->dg_table && tangent->dg_at_psi));
+  ja.ntan = ntan;
+  ja.lai = with_lai ? 1 : 0;
+  ja.leaf = tangent ? 1 : 0;
+  const int npar = ntan + ja.lai + ja.leaf;
+  args_ok = args_ok && npar >= 1;
+  if (args_ok) {
+    const int nb = bands->nb;
+    sn.o[0] = out->I_dr;
+    sn.o[1] = out->I_df_d;
+    sn.o[2] = out->I_df_u;
+    sn.o[3] = out->F;
+    sn.w = sensors->w;
+    sn.nsens = sensors->nsens;
+    int64_t off = 0;
+    for (int k = 0; k < sn.nsens && args_ok; ++k) {
+      const int32_t f = sensors->first[k], n = sensors->count[k];
+      if (n < 1 || f < 0 || (int64_t)f + n > nb) args_ok = false;
+      sn.first[k] = f;
+      sn.count[k] = n;
+      sn.off[k] = (int32_t)off;
+      off += n;  // (<= 64 nb: no overflow)
+    }
+    if (off > 0x7fffffffLL) args_ok = false;
+    if (ntan > 0) {
+      ja.d[0] = dirs->leaf_r;
+      ja.d[1] = dirs->leaf_t;
+      ja.d[2] = dirs->soil_r;
+      ja.dstride = dirs->col_stride;
+    }
+  }
+  // (sizes that are not positive are an argument error of the shared path: no tail then)
+  const bool sized = args_ok && cols && cols->ncol > 0 && cols->nz > 0;
+  const bool side_lai = sized && ja.lai && dlai_side_len(scheme, cols->nz) > 0, side_leaf = args_ok && ja.leaf;
+  const bool sel_ok = nsel >= 1 && nsel <= CRT_MAX_LEVEL_SELECT;
+  return levels_deriv_impl(
+      scheme, cols, bands, opts, levels, nsel, workspace, workspace_bytes, stream, args_ok, grad_side_len,
+      side_lai && side_leaf ? "k_colpre + k_dlai_side + k_dleaf_side" : side_lai ? "k_colpre + k_dlai_side" : side_leaf ? "k_colpre + k_dleaf_side" : "k_colpre",
+      [&](const SolveArgs& sa, const LevArgs& la, const double* side, hipStream_t s, bool probe) {
+        ja.side_lai = side;
+        ja.side_leaf = side + (size_t)sa.ncol * dlai_side_len(scheme, sa.nz);
+        sn.part = const_cast<double*>(side) + (size_t)sa.ncol * grad_side_len(scheme, sa.nz);
+        return launch_sens_jac(scheme, sa, la, ja, s, probe);
+      },
+      [&](const ColArgs& ca, double* side, hipStream_t s) {
+        if (side_lai)
+          if (const int st = launch_dlai_side(ca, side, s)) return st;
+        if (!side_leaf) return (int)CRT_OK;
+        return launch_dleaf_side(ca, DleafTan{tangent->dg_table, tangent->dg_at_psi, tangent->dmla},
+                                 side + (size_t)ca.ncol * dlai_side_len(scheme, ca.nz), s);
+      },
+      true, sized && sel_ok ? sensjac_part_bytes(cols->ncol, bands->nb, nsel, sn.nsens, npar) : 0);
+}
+
 int crt_hip_bandsum_finish_f64(const crt_columns* cols, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream) {
   if (!cols || !out || !cols->psi || ngroup <= 0 || ngroup > INT_MAXG) return CRT_ERR_BAD_ARG;
   if (!out->aI || !out->aI_sl || !out->aI_sh || !out->I_dr || !out->I_df_d || !out->I_df_u || !out->F || !out->I_d) return CRT_ERR_BAD_ARG;

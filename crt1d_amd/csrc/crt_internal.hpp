@@ -12,6 +12,7 @@
 #include "crt1d_hip_dleaf.h"
 #include "crt1d_hip_grad.h"
 #include "crt1d_hip_jac.h"
+#include "crt1d_hip_sensjac.h"
 #include "crt1d_hip_sensor.h"
 
 namespace crt {
@@ -868,6 +869,46 @@ __device__ __forceinline__ void sens_row(const SensArgs& sn, double* stage, cons
   __syncthreads();
 }
 
+// The fold of sens_row for rows that already lie in LDS (k_sens_jac, sensjac.hip): `rows` = [nsel][R][nthr] doubles, lane <-> band of the
+// slice; group g < ng of level r is the NR <= 4 consecutive rows row0 + g NR .. and belongs to parameter par0 + g.  Wave w serves the items
+// (r, s, g) w, w + nwave, ...: lane l adds the products w_s[b] * row[b] of the bands lo + l, lo + l + 64, ... in ascending order, wave_sum4
+// adds the 64 lane sums of the group's rows -- sens_row's order, whatever the split of the items over the waves.  A group of NR = 3 rows
+// holds quantities 1..3 (I_df_d, I_df_u, F); quantity 0 (I_dr) is then the sum of zeros.  The sums go to sn.o[q][((v nsel + r) nsens + s) npar
+// + par] (one slice; a NULL output is not written) or to sn.part[((((v nslice + slice) nsel + r) nsens + s) npar + par) 4 + q].  Call with
+// every thread of the workgroup, between two barriers of the caller's.
+template <int NR>
+__device__ __forceinline__ void sens_fold_rows(const SensArgs& sn, const double* rows, int R, int row0, int ng, int par0, int npar, int slice,
+                                               int per, int nb, int nslice, long long v, int nsel) {
+  static_assert(NR == 3 || NR == 4, "three diffuse quantities or all four");
+  const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, nsens = sn.nsens;
+  const int lo_s = slice * per, hi_s = min(lo_s + per, nb);
+  const int q = wave_sum4_slot(lane >> 4);
+  const int nitem = nsel * nsens * ng;
+  for (int it = tid >> 6; it < nitem; it += nthr >> 6) {  // (wave-uniform)
+    const int g = it % ng, s = (it / ng) % nsens, r = it / (ng * nsens);
+    const int f = sn.first[s];
+    const int lo = max(f, lo_s), hi = min(f + sn.count[s], hi_s);
+    if (lo >= hi) continue;
+    const double* w = sn.w + (sn.off[s] - f);
+    const double* x = rows + ((size_t)r * R + row0 + g * NR) * nthr - lo_s;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = lo + lane; i < hi; i += 64) {
+      const double wi = w[i];
+#pragma unroll
+      for (int j = 0; j < NR; ++j) acc[4 - NR + j] += wi * x[(size_t)j * nthr + i];
+    }
+    const double z = wave_sum4(acc[0], acc[1], acc[2], acc[3]);
+    if ((lane & 15) == 0) {
+      const int par = par0 + g;
+      if (nslice == 1) {
+        if (sn.o[q]) sn.o[q][((v * nsel + r) * nsens + s) * npar + par] = z;
+      } else {
+        sn.part[((((v * nslice + slice) * nsel + r) * nsens + s) * npar + par) * 4 + q] = z;
+      }
+    }
+  }
+}
+
 // Widest balanced band slices (lev_slices, at most 1024 lanes, halved down to 64) whose LDS `bytes(nthr)` fits `cap`; nslice = 0: none fits.
 template <class F>
 inline LevSlices lev_slices_fit(int nb, size_t cap, F bytes) {
@@ -993,6 +1034,36 @@ constexpr int GRAD_BLOCK = 256;  // bands per slice at most
 constexpr int grad_side_len(int scheme, int nz) { return dlai_side_len(scheme, nz) + dleaf_side_len(scheme, nz); }
 inline size_t grad_part_bytes(int ncol, int nb) { return (size_t)ncol * (size_t)lev_slices(nb, GRAD_BLOCK).nslice * 2 * sizeof(double); }
 int launch_grad(int scheme, const SolveArgs& a, const LevArgs& la, const GradArgs& ga, hipStream_t s, bool probe);
+
+// ------------------------------------------------------------------------------------------
+// Jacobian of the sensor-band sums (crt_hip_sensor_jac_f64, include/crt1d_hip_sensjac.h; kernels in sensjac.hip): 2s, bl, g77, bf
+struct SensJacArgs {
+  SensArgs sn;              // o: [ncol][nsel][nsens][npar] or NULL; part: [ncol][nslice][nsel][nsens][npar][4]; nq / qs unused
+  const double* d[3];       // directions in leaf_r, leaf_t, soil_r: [ncol or 1][ntan][nb] or NULL
+  long long dstride;        // 0 or ntan * nb
+  int ntan, lai, leaf;      // parameter columns: ntan directions, ln LAI (0 / 1), the leaf angle (0 / 1)
+  const double* side_lai;   // side records of k_dlai_side  (read for bl with `lai`)
+  const double* side_leaf;  // side records of k_dleaf_side (read with `leaf`)
+};
+constexpr int SENSJAC_BLOCK = 256;          // bands per slice at most
+constexpr size_t SENSJAC_STATIC_LDS = 4096;  // allowance for the kernel's static LDS (header, tangents, level entries: 2432 bytes)
+// staging rows per level: three per direction (I_df_d, I_df_u, F), or the four of the LAI / leaf-angle pass, which reuse the same area.
+// The slices follow from npar alone (every parameter taken for a direction), so that the workspace query needs no more than npar.
+constexpr int sensjac_rows(int ndir) { return 3 * ndir > 4 ? 3 * ndir : 4; }
+// the widest of 256, 128, 64 lanes whose staging rows fit; nslice = 0: none
+inline LevSlices sensjac_slices(int nb, int nsel, int npar) {
+  int wmax = SENSJAC_BLOCK;
+  while (wmax >= 64 && (size_t)nsel * sensjac_rows(npar) * wmax * sizeof(double) > 160 * 1024 - SENSJAC_STATIC_LDS) wmax >>= 1;
+  if (wmax < 64) return LevSlices{0, 0, 0};
+  return lev_slices(nb, wmax);
+}
+// bytes of the slice sums behind the side records (0 with one slice; where no slice width fits, those of 64-lane slices: the call refuses)
+inline size_t sensjac_part_bytes(int ncol, int nb, int nsel, int nsens, int npar) {
+  LevSlices ls = sensjac_slices(nb, nsel, npar);
+  if (ls.nslice == 0) ls = lev_slices(nb, 64);
+  return ls.nslice <= 1 ? 0 : (size_t)ncol * ls.nslice * nsel * nsens * npar * 4 * sizeof(double);
+}
+int launch_sens_jac(int scheme, const SolveArgs& a, const LevArgs& la, const SensJacArgs& ja, hipStream_t s, bool probe);
 
 // launchers implemented in the .hip files
 int launch_colpre(const ColArgs& a, hipStream_t s);

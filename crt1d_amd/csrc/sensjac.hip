@@ -1,0 +1,229 @@
+// Jacobian of the sensor-band sums (include/crt1d_hip_sensjac.h): the optics Jacobian (jac.hip) along ntan directions, the LAI derivative
+// (dlai.hip) and the leaf-angle derivative (dleaf.hip) folded with the spectral responses of a sensor set where they are formed, for the
+// closed forms 2s, bl, g77, bf.  Only [ncol][nsel][nsens][npar] sums leave the workgroup: the eleven derivative arrays of the composition,
+// the (ncol, nsel, ntan, nb) intermediate and the dense weights are never written or read.
+//
+//  k_sens_jac         k_grad's mapping: lane <-> band, a workgroup owns one column and one band slice; the header with its leaf-angle
+//                     tangents and the selected record entries are staged in LDS once, a lane loads its band once and runs the passes one
+//                     after the other, ONE tangent at a time (grad.hip), each with the jac_schemes.hpp instantiation k_grad uses -- the same
+//                     tangent bits (-ffp-contract=off).  Where k_grad multiplies a tangent by a weight and adds, a lane here leaves the
+//                     tangent in its entry of the staging rows [nsel][R][lanes] in LDS; three phases share the rows:
+//                       directions   rows (k, q), q = I_df_d, I_df_u, F: the unit-seed passes p = leaf_r, leaf_t, soil_r add X'_p d_p[k][b]
+//                                    in this order (a NULL direction array and bl's soil are left out) -- a lane touches its own entries
+//                                    only, so the three passes need no barrier
+//                       LAI          rows q = I_dr, I_df_d, I_df_u, F
+//                       leaf angle   the same
+//                     and each phase ends with ONE barrier and sens_fold_rows (crt_internal.hpp): a wave per (level, sensor band,
+//                     parameter) over the support inside the slice, sens_row's order.  R = max(3 ntan, 4).
+//  k_sens_jac_finish  several band slices: a thread per output element adds the slice sums in ascending order (k_sens_finish's rule).
+// No atomics anywhere: a column's result does not depend on the batch, and an output's bits do not depend on which others are asked for
+// (every quantity is staged and folded; a NULL output is only not written).
+#include "jac_schemes.hpp"
+#include "launch_forms.hpp"
+
+namespace crt {
+namespace {
+
+// optics pass | LAI pass | leaf-angle pass: the instantiations of jac.hip, dlai.hip, dleaf.hip (as grad.hip)
+struct S2s {
+  using J = J2sT<Du, double>;
+  using D = J2sT<double, Du>;
+  using F = J2sT<double, Du, Du>;
+};
+struct SBl {
+  using J = JBlT<Du, double>;
+  using D = JBlT<double, Du>;
+  using F = JBlT<double, Du, Du>;
+};
+template <bool BF>
+struct SG77 {
+  using J = JG77T<BF, Du, double>;
+  using D = JG77T<BF, double, Du>;
+  using F = JG77T<BF, double, Du, Du>;
+};
+
+// the band of load_dband with parameter p seeded (uniform)
+__device__ __forceinline__ JBandT<Du> sj_seed_band(const DBand& in, int p) {
+  return JBandT<Du>{in.I_dr0, in.I_df0, Du{in.r, p == 0 ? 1.0 : 0.0}, Du{in.t, p == 1 ? 1.0 : 0.0}, Du{in.s, p == 2 ? 1.0 : 0.0}};
+}
+
+template <class G, bool BL>
+__global__ __launch_bounds__(SENSJAC_BLOCK) void k_sens_jac(SolveArgs a, LevArgs la, SensJacArgs ja, int per, int R) {
+  using SJ = typename G::J;
+  extern __shared__ double rows[];           // [nsel][R][blockDim.x]
+  __shared__ double hd[HDR_TAN + REC_HDR];  // k_dleaf's layout: header | e^{-K_b LT} at the ground | ... | the header's leaf-angle tangents
+  __shared__ double lvL[CRT_MAX_LEVEL_SELECT], lvE[CRT_MAX_LEVEL_SELECT], lvTs[CRT_MAX_LEVEL_SELECT], lvTh[CRT_MAX_LEVEL_SELECT];
+  const int c = blockIdx.x, slice = blockIdx.y, nslice = gridDim.y, nz = a.nz, nb = a.nb, nsel = la.nsel, tid = threadIdx.x, nthr = blockDim.x;
+  const int b = slice * per + tid;
+  const bool live = tid < per && b < nb;
+  const int ntan = ja.ntan, npar = ntan + ja.lai + ja.leaf;
+  const double* rec = a.ws + (long long)c * a.reclen;
+  const double* sdl = ja.side_leaf + (long long)c * (REC_HDR + (BL ? nz : 0));
+  if (tid < REC_HDR) {
+    hd[tid] = rec[tid];
+    hd[HDR_TAN + tid] = ja.leaf ? sdl[tid] : 0.0;
+  }
+  if (tid == REC_HDR) hd[REC_HDR] = rec[REC_HDR + nz];  // e^{-K_b L} at the ground
+  for (int r = tid; r < nsel; r += nthr) {
+    const int j = la.lev[r];
+    lvL[r] = rec[REC_HDR + j];
+    lvE[r] = rec[REC_HDR + nz + j];
+    if constexpr (BL) {
+      lvTs[r] = ja.lai ? ja.side_lai[(long long)c * nz + j] : 0.0;  // L_j tau_d'(L_j)
+      lvTh[r] = ja.leaf ? sdl[REC_HDR + j] : 0.0;                   // tau_d^th(L_j)
+    }
+  }
+  __syncthreads();
+  const double invmu = hd[S_INVMU];
+  DBand in = {};
+  if (live) in = load_dband(a, c, b, SJ::SOIL);
+  double* const my = rows + tid;  // row i of level r: my[(r R + i) nthr]
+
+  // ---- the directions: the optics one parameter at a time (k_jac), each tangent times the lane's band of every direction ----
+  if (ntan > 0) {
+    if (live) {
+      bool first = true;  // (uniform)
+      for (int p = 0; p < CRT_JAC_NPARAM; ++p) {
+        if (!ja.d[p] || (!SJ::SOIL && p == 2)) continue;  // (bl has no soil)
+        const double* dp = ja.d[p] + (long long)c * ja.dstride + b;
+        double d[CRT_SENSJAC_MAX_NTAN];
+#pragma unroll
+        for (int k = 0; k < CRT_SENSJAC_MAX_NTAN; ++k) d[k] = k < ntan ? dp[(long long)k * nb] : 0.0;
+        SJ st;
+        st.init(hd, sj_seed_band(in, p), hd[REC_HDR]);
+        for (int r = 0; r < nsel; ++r) {
+          Du dn, up;
+          st.level(lvL[r], lvE[r], dn, up);
+          const double x[3] = {dn.d, up.d, 2 * (up.d + dn.d)};  // F' as jac_store
+          double* const y = my + (size_t)r * R * nthr;
+#pragma unroll
+          for (int k = 0; k < CRT_SENSJAC_MAX_NTAN; ++k)
+            if (k < ntan) {
+#pragma unroll
+              for (int q = 0; q < 3; ++q) {
+                const double t = x[q] * d[k];
+                double* const e = y + (size_t)(3 * k + q) * nthr;
+                *e = first ? t : *e + t;
+              }
+            }
+        }
+        first = false;
+      }
+      if (first)  // (bl with directions in soil_r alone: zeros)
+        for (int r = 0; r < nsel; ++r)
+          for (int i = 0; i < 3 * ntan; ++i) my[((size_t)r * R + i) * nthr] = 0.0;
+    }
+    __syncthreads();
+    sens_fold_rows<3>(ja.sn, rows, R, 0, ntan, 0, npar, slice, per, nb, nslice, c, nsel);
+    __syncthreads();
+  }
+
+  // ---- the LAI (k_dlai) ----
+  if (ja.lai) {
+    if (live) {
+      const double K = hd[S_KB];
+      typename G::D st;
+      st.init(hd, in, Du{hd[REC_HDR], -(K * hd[S_LT]) * hd[REC_HDR]});
+      for (int r = 0; r < nsel; ++r) {
+        const double L = lvL[r];
+        const Du eK = Du{lvE[r], -(K * L) * lvE[r]};
+        Du dn, up;
+        st.level(Du{L, L}, eK, dn, up);
+        if constexpr (BL) dn.d += in.I_df0 * lvTs[r];  // the sky term I_df0 tau_d(L_j)
+        const double dI = in.I_dr0 * eK.d;
+        double* const y = my + (size_t)r * R * nthr;
+        y[0] = dI;
+        y[nthr] = dn.d;
+        y[2 * nthr] = up.d;
+        y[3 * nthr] = __builtin_fma(dI, invmu, 2 * (up.d + dn.d));  // F' as dlai_store
+      }
+    }
+    __syncthreads();
+    sens_fold_rows<4>(ja.sn, rows, R, 0, 1, ntan, npar, slice, per, nb, nslice, c, nsel);
+    __syncthreads();
+  }
+
+  // ---- the leaf angles (k_dleaf) ----
+  if (ja.leaf) {
+    if (live) {
+      const double dK = hd[HDR_TAN + S_KB];
+      typename G::F st;
+      st.init(hd, in, Du{hd[REC_HDR], -(dK * hd[S_LT]) * hd[REC_HDR]});
+      for (int r = 0; r < nsel; ++r) {
+        const double L = lvL[r];
+        const Du eK = Du{lvE[r], -(dK * L) * lvE[r]};
+        Du dn, up;
+        st.level(L, eK, dn, up);
+        if constexpr (BL) dn.d += in.I_df0 * lvTh[r];  // the sky term I_df0 tau_d(L_j)
+        const double dI = in.I_dr0 * eK.d;
+        double* const y = my + (size_t)r * R * nthr;
+        y[0] = dI;
+        y[nthr] = dn.d;
+        y[2 * nthr] = up.d;
+        y[3 * nthr] = __builtin_fma(dI, invmu, 2 * (up.d + dn.d));
+      }
+    }
+    __syncthreads();
+    sens_fold_rows<4>(ja.sn, rows, R, 0, 1, ntan + ja.lai, npar, slice, per, nb, nslice, c, nsel);
+  }
+}
+
+// One thread per output element (c, r, s, par, q): the partial sums of the slices that meet the support of sensor band s, added in
+// ascending slice order -- the slices sens_fold_rows skipped are skipped here, so nothing unwritten is read.
+__global__ __launch_bounds__(256) void k_sens_jac_finish(SensArgs sn, long long ncol, int nslice, int per, int nb, int nsel, int npar) {
+  const int nsens = sn.nsens;
+  const long long n = ncol * nsel * nsens * npar * 4;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int q = (int)(i % 4);
+  const int par = (int)((i / 4) % npar);
+  const int s = (int)((i / (4LL * npar)) % nsens);
+  const int r = (int)((i / (4LL * npar * nsens)) % nsel);
+  const long long v = i / (4LL * npar * nsens * nsel);
+  double* const o = sn.o[q];
+  if (!o) return;
+  const int f = sn.first[s], e = f + sn.count[s];
+  double z = 0.0;
+  bool any = false;
+  for (int sl = 0; sl < nslice; ++sl) {
+    const int lo_s = sl * per, hi_s = min(lo_s + per, nb);
+    if (max(f, lo_s) >= min(e, hi_s)) continue;
+    const double p = sn.part[((((v * nslice + sl) * nsel + r) * nsens + s) * npar + par) * 4 + q];
+    z = any ? z + p : p;
+    any = true;
+  }
+  o[((v * nsel + r) * nsens + s) * npar + par] = z;
+}
+
+template <class G, bool BL = false>
+int launch_sens_jac_closed(const SolveArgs& a, const LevArgs& la, const SensJacArgs& ja, hipStream_t s, bool probe) {
+  const int npar = ja.ntan + ja.lai + ja.leaf, nsens = ja.sn.nsens;
+  const LevSlices ls = sensjac_slices(a.nb, la.nsel, npar);
+  if (ls.nslice == 0 || ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
+  const long long nfin = ((long long)a.ncol * la.nsel * nsens * npar * 4 + 255) / 256;
+  if (ls.nslice > 1 && nfin > 0x7fffffffLL) return CRT_ERR_UNSUPPORTED;
+  if (probe) return CRT_OK;
+  const int R = sensjac_rows(ja.ntan);
+  const size_t sh = (size_t)la.nsel * R * ls.nthr * sizeof(double);  // (<= the bound of sensjac_slices: ntan <= npar)
+  int st = launch_kernel(k_sens_jac<G, BL>, dim3(a.ncol, ls.nslice), ls.nthr, sh, s, a, la, ja, ls.per, R);
+  const bool fin = ls.nslice > 1;
+  if (st == CRT_OK && fin)
+    st = launch_kernel(k_sens_jac_finish, dim3((unsigned)nfin), 256, 0, s, ja.sn, (long long)a.ncol, ls.nslice, ls.per, a.nb, la.nsel, npar);
+  if (st == CRT_OK)
+    note_kernel("k_sens_jac<%s> nsel=%d nsens=%d npar=%d slice=%d%s", G::J::NAME, la.nsel, nsens, npar, ls.per, fin ? " + k_sens_jac_finish" : "");
+  return st;
+}
+
+}  // namespace
+
+int launch_sens_jac(int scheme, const SolveArgs& a, const LevArgs& la, const SensJacArgs& ja, hipStream_t s, bool probe) {
+  switch (scheme) {
+    case CRT_SCHEME_2S: return launch_sens_jac_closed<S2s>(a, la, ja, s, probe);
+    case CRT_SCHEME_BL: return launch_sens_jac_closed<SBl, true>(a, la, ja, s, probe);
+    case CRT_SCHEME_G77: return launch_sens_jac_closed<SG77<false>>(a, la, ja, s, probe);
+    case CRT_SCHEME_BF: return launch_sens_jac_closed<SG77<true>>(a, la, ja, s, probe);
+    default: return CRT_ERR_UNSUPPORTED;
+  }
+}
+
+}  // namespace crt

@@ -387,6 +387,37 @@ class Model:
         out = batched.solve_levels_dleaf(scheme, cols, b, (0, -1) if levels is None else levels, batched.leaf_tangent(cols, wrt))
         return {k: v[0].cpu().numpy() for k, v in out.items()}
 
+    def run_sensor_jacobian(self, weights, levels=(0, -1), directions=None, lai=True, wrt_leaf=None):
+        """The Jacobian of what :meth:`run_sensors` returns with respect to a parameter vector of this case
+        (:class:`crt1d_amd.batched.SensorJacPlan`, ``ncol = 1``).  ``directions``: ``{"leaf_r" | "leaf_t" | "soil_r": (ntan, n_wl)}``, the
+        derivatives of the spectra with respect to ``ntan`` parameters of a leaf or soil model (``None``: no such columns); ``lai``: a
+        column per ``ln LAI``; ``wrt_leaf``: a leaf-angle parameter (``"param"``, ``"mla"``, ``"a"``, ``"b"``; ``None``: no such column).
+        Returns ``{"I_dr", "I_df_d", "I_df_u", "F"}`` as NumPy arrays ``(nsel, nsens, npar)`` and ``"params"``, the names of the columns
+        (``"dir0"``, ..., ``"lai"``, ``"leaf"``).  ValueError for ``4s`` and ``zq_pa``.  The model's own state (``out``) is not changed."""
+        from . import batched
+
+        self._check_inputs()
+        p = self._p
+        scheme, cols, b, sun = self._series_inputs(np.atleast_1d(float(p["psi"])), None, None, "sensor Jacobian")
+        if scheme not in batched.SensorJacPlan._schemes:
+            raise ValueError(batched.SensorJacPlan._no_kernel.format(scheme))
+        directions = {} if directions is None else dict(directions)
+        if any(k not in batched.JAC_PARAMS for k in directions):
+            raise ValueError(f"directions must be a dict of (ntan, n_wl) arrays under keys out of {batched.JAC_PARAMS}")
+        if wrt_leaf is not None and wrt_leaf not in batched.LEAF_WRT:
+            raise ValueError(f"wrt_leaf must be None or one of {batched.LEAF_WRT}, got {wrt_leaf!r}")
+        cols = batched.Columns(psi=sun.psi[:, 0].contiguous(), lai=cols.lai, g_kind=cols.g_kind, g_param=cols.g_param, mla=cols.mla,
+                               g_at_psi=None if sun.g_at_psi is None else sun.g_at_psi[:, 0].contiguous(), g_table=cols.g_table)
+        b = batched.Bands(sun.I_dr0[:, 0].contiguous(), sun.I_df0[:, 0].contiguous(), b.leaf_r, b.leaf_t, b.soil_r)
+        d = {"d_" + k: np.ascontiguousarray(v, dtype=np.float64) for k, v in directions.items()}
+        with batched.torch.cuda.device(cols.device):
+            plan = batched.SensorJacPlan(scheme, cols, b, levels, self._sensor_set(weights, self.nwl), lai=lai,
+                                         tangent=None if wrt_leaf is None else batched.leaf_tangent(cols, wrt_leaf), **d)
+            out = plan()
+        res = {k: v[0].cpu().numpy() for k, v in out.items()}
+        res["params"] = plan.params
+        return res
+
     # ---- output container -------------------------------------------------------------------
     def _scheme_absorption_vars(self, nz):
         """The scheme's own absorption outputs (``aI*_scheme``): on levels or on layers, by their leading size."""
