@@ -400,6 +400,29 @@ def _sensjac_signatures():
 _SENSJAC_SIGNATURES = _sensjac_signatures()
 SENSJAC_EXPORTS = list(_SENSJAC_SIGNATURES)
 
+# the sun-angle series of that Jacobian (include/crt1d_hip_sensjac_series.h), again a header and a table of their own
+
+
+class CrtLeafTangentSeries(ctypes.Structure):
+    """``crt_leaf_tangent_series``: device pointers; ``dg_at_psi`` is ``[ncol][nt]``, ``dmla`` may be NULL (zeros)."""
+
+    _fields_ = [(k, _vp) for k in ("dg_table", "dg_at_psi", "dmla")]
+
+
+def _sensjac_series_signatures():
+    P = ctypes.POINTER
+    i, i32, sz, ok = ctypes.c_int, ctypes.c_int32, ctypes.c_size_t, ctypes.c_int
+    return {
+        "crt_hip_sensor_jac_series_workspace_bytes": (sz, [i, i32, i32, i32, i32, i32, i32, i32]),
+        "crt_hip_sensor_jac_series_f64": (ok, [i, P(CrtColumns), P(CrtBands), P(CrtSunSeries), P(CrtOptions), P(i32), i32, P(CrtSensorSet),
+                                               P(CrtOpticsDirs), i, P(CrtLeafTangentSeries), P(CrtSensJacOut), _vp, sz, _vp]),
+        "crt_hip_g_dparam_series_f64": (ok, [P(CrtColumns), P(CrtSunSeries), _vp, _vp, _vp]),
+    }
+
+
+_SENSJAC_SERIES_SIGNATURES = _sensjac_series_signatures()
+SENSJAC_SERIES_EXPORTS = list(_SENSJAC_SERIES_SIGNATURES)
+
 _lib = None
 
 
@@ -423,7 +446,8 @@ def load():
 
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES, **_SENSOR_SIGNATURES, **_JAC_SIGNATURES,
-                                      **_DLAI_SIGNATURES, **_DLEAF_SIGNATURES, **_GRAD_SIGNATURES, **_SENSJAC_SIGNATURES}.items():
+                                      **_DLAI_SIGNATURES, **_DLEAF_SIGNATURES, **_GRAD_SIGNATURES, **_SENSJAC_SIGNATURES,
+                                      **_SENSJAC_SERIES_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:

@@ -1812,16 +1812,26 @@ class SensorJacPlan(_LevelsDerivPlan):
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, *, d_leaf_r=None, d_leaf_t=None, d_soil_r=None,
                  lai=True, tangent=None, keys=LEVEL_KEYS, mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
+        self._build(scheme, cols, bands, None, levels, sensors, d_leaf_r, d_leaf_t, d_soil_r, lai, tangent, keys, mu_s, tau_d_method, out, workspace)
+
+    def _build(self, scheme, cols, bands, sun, levels, sensors, d_leaf_r, d_leaf_t, d_soil_r, lai, tangent, keys, mu_s, tau_d_method, out,
+               workspace):
+        """The construction of this plan (``sun`` None) and of :class:`SensorJacSeriesPlan` (outputs with a sun-state axis)."""
+        series = {} if sun is None else {"sun": sun}
         keys = self._check_static(scheme, tau_d_method, keys, sensors=sensors, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r,
-                                  lai=lai, tangent=tangent)
+                                  lai=lai, tangent=tangent, **series)
+        self._composed = scheme not in SENSJAC_SCHEMES
+        if self._composed and workspace is not None:
+            raise ValueError(f"the sensor Jacobian of {scheme} runs plans with workspaces of their own: workspace must be None")
         if bands.dtype != torch.float64:
             raise TypeError(f"the {self._what} has no f32 storage form: bands must be float64")
         ntan = _sensjac_ntan(d_leaf_r, d_leaf_t, d_soil_r)
         self.levels, self.keys, self.sensors = normalize_levels(levels, cols.nz), keys, sensors
         self._kw = dict(mu_s=mu_s, tau_d_method=tau_d_method)
         sensors.check(bands.nb, cols.device)
-        self._bind(scheme, cols, bands, mu_s, tau_d_method)
+        self._bind(scheme, cols, bands, mu_s, tau_d_method, **series)
         ncol, nsel, nb, dev = cols.ncol, len(self.levels), bands.nb, cols.device
+        nts = () if sun is None else (sun.nt,)
         dirs = {n: _jvp_direction(d, "d_" + n, ncol, nb, dev) for n, d in zip(JAC_PARAMS, (d_leaf_r, d_leaf_t, d_soil_r)) if d is not None}
         per_col = any(d.shape[0] != 1 for d in dirs.values()) and ncol != 1
         self.dirs = {n: (d.expand(ncol, -1, -1) if per_col else d).contiguous() for n, d in dirs.items()}
@@ -1830,13 +1840,10 @@ class SensorJacPlan(_LevelsDerivPlan):
         self.tangent, self.ntan = tangent, ntan
         self.params = tuple(f"dir{k}" for k in range(ntan)) + (("lai",) if lai else ()) + (("leaf",) if tangent is not None else ())
         npar = len(self.params)
-        out = _outputs({k: (ncol, nsel, sensors.nsens, npar) for k in keys}, out, torch.float64, dev, "output {!r}", lacks=True)
+        out = _outputs({k: (ncol, *nts, nsel, sensors.nsens, npar) for k in keys}, out, torch.float64, dev, "output {!r}", lacks=True)
         self.out = {k: out[k] for k in keys}
         self._lev = (ctypes.c_int32 * nsel)(*self.levels)
-        self._composed = scheme not in SENSJAC_SCHEMES
         if self._composed:
-            if workspace is not None:
-                raise ValueError(f"the sensor Jacobian of {scheme} runs plans with workspaces of their own: workspace must be None")
             self._report = ""
             return
         self._sens = sensors.c_struct()
@@ -1846,8 +1853,12 @@ class SensorJacPlan(_LevelsDerivPlan):
                                             *[self.dirs[n].data_ptr() if n in self.dirs else None for n in JAC_PARAMS])
         self._tan = None if tangent is None else tangent.c_struct()
         self._out = _lib.CrtSensJacOut(*[out[k].data_ptr() if k in keys else None for k in LEVEL_KEYS])
-        need = max(sensor_jac_workspace_bytes(scheme, ncol, cols.nz, nb, nsel, sensors.nsens, npar),
-                   sensor_workspace_bytes(scheme, ncol, cols.nz, nb, nsel, sensors.nsens))
+        if sun is None:
+            need = max(sensor_jac_workspace_bytes(scheme, ncol, cols.nz, nb, nsel, sensors.nsens, npar),
+                       sensor_workspace_bytes(scheme, ncol, cols.nz, nb, nsel, sensors.nsens))
+        else:
+            need = max(sensor_jac_series_workspace_bytes(scheme, ncol, cols.nz, nb, sun.nt, nsel, sensors.nsens, npar),
+                       sensor_series_workspace_bytes(scheme, ncol, cols.nz, nb, sun.nt, nsel, sensors.nsens))
         self._finish(self._entry_name, need, workspace)
 
     @staticmethod
@@ -1908,10 +1919,173 @@ def sensor_jacobian(scheme, cols: Columns, bands: Bands, levels, sensors: Sensor
         return SensorJacPlan(scheme, cols, bands, levels, sensors, **kw)()
 
 
+# ---- the sensor Jacobian over a sun-angle series (include/crt1d_hip_sensjac_series.h) -----------------------------------------------------
+
+
+@dataclass
+class LeafTangentSeries:
+    """A :class:`LeafTangent` for the ``nt`` sun states of a :class:`SunSeries` (``crt_leaf_tangent_series``): ``dg_table (ncol, NQ)`` and
+    ``dmla (ncol,)`` do not follow the sun; ``dg_at_psi (ncol, nt)`` is the tangent of G at ``sun.psi``."""
+
+    dg_table: torch.Tensor  # (ncol, NQ)
+    dg_at_psi: torch.Tensor  # (ncol, nt)
+    dmla: Optional[torch.Tensor] = None  # (ncol,) degrees
+
+    def __post_init__(self):
+        self.dg_table = _f64(self.dg_table, "dg_table")
+        self.dg_at_psi = _f64(self.dg_at_psi, "dg_at_psi")
+        ncol = self.dg_table.shape[0]
+        if (self.dg_table.ndim != 2 or self.dg_table.shape[1] != _lib.NQ or self.dg_at_psi.ndim != 2 or self.dg_at_psi.shape[0] != ncol
+                or self.dg_at_psi.shape[1] < 1):
+            raise ValueError(f"dg_table must be (ncol, {_lib.NQ}) and dg_at_psi (ncol, nt) with nt >= 1")
+        if self.dmla is not None:
+            self.dmla = _f64(self.dmla, "dmla")
+            if self.dmla.shape != (ncol,):
+                raise ValueError("dmla must be (ncol,)")
+
+    @property
+    def nt(self):
+        return self.dg_at_psi.shape[1]
+
+    def step(self, t):
+        """The :class:`LeafTangent` of sun state ``t``."""
+        return LeafTangent(self.dg_table, self.dg_at_psi[:, t].contiguous(), self.dmla)
+
+    def slice(self, lo, hi):
+        return LeafTangentSeries(self.dg_table[lo:hi], self.dg_at_psi[lo:hi], None if self.dmla is None else self.dmla[lo:hi])
+
+    def c_struct(self):
+        return _lib.CrtLeafTangentSeries(self.dg_table.data_ptr(), self.dg_at_psi.data_ptr(), None if self.dmla is None else self.dmla.data_ptr())
+
+
+def g_dparam_series(cols: Columns, sun: SunSeries):
+    """:func:`g_dparam` with the sun-angle entry at every ``sun.psi[c, t]`` (``crt_hip_g_dparam_series_f64``): ``(dg_table (ncol, NQ),
+    dg_at_psi (ncol, nt))``, bitwise what :func:`g_dparam` gives for columns whose ``psi`` is ``sun.psi[:, t]``.  ``cols.psi`` is not read."""
+    dev = cols.device
+    if sun.ncol != cols.ncol or sun.psi.device != dev:
+        raise ValueError("sun must have the columns' ncol and device")
+    dg_table = torch.empty((cols.ncol, _lib.NQ), dtype=torch.float64, device=dev)
+    dg_at_psi = torch.empty((cols.ncol, sun.nt), dtype=torch.float64, device=dev)
+    c, sn = cols.c_struct(), sun.c_struct()
+    with torch.cuda.device(dev):
+        st = _lib.load().crt_hip_g_dparam_series_f64(ctypes.byref(c), ctypes.byref(sn), dg_table.data_ptr(), dg_at_psi.data_ptr(),
+                                                     torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(st, "crt_hip_g_dparam_series_f64")
+    return dg_table, dg_at_psi
+
+
+def leaf_tangent_series(cols: Columns, sun: SunSeries, wrt="param"):
+    """:func:`leaf_tangent` for every sun state of ``sun``: a :class:`LeafTangentSeries` whose ``.step(t)`` is bitwise
+    ``leaf_tangent`` of columns with ``psi = sun.psi[:, t]``.  Same four ``wrt``."""
+    if wrt not in LEAF_WRT:
+        raise ValueError(f"wrt must be one of {LEAF_WRT}, got {wrt!r}")
+    if wrt in ("a", "b"):
+        from .leaf_angle import PDF_TRIG
+
+        kind = torch.full((cols.ncol,), PDF_TRIG, dtype=torch.int32, device=cols.device)
+        step = torch.zeros((cols.ncol, 2), dtype=torch.float64, device=cols.device)
+        t0, p0, m0 = leaf_pdf_tables(kind, step, psi=sun.psi)
+        step[:, 0 if wrt == "a" else 1] = 1.0
+        t1, p1, m1 = leaf_pdf_tables(kind, step, psi=sun.psi)
+        return LeafTangentSeries(t1 - t0, p1 - p0, m1 - m0)
+    dg_table, dg_at_psi = g_dparam_series(cols, sun)
+    if wrt == "param":
+        return LeafTangentSeries(dg_table, dg_at_psi)
+    if cols.mla is None:
+        raise ValueError("wrt='mla' needs cols.mla")
+    dx = -(cols.g_param + 3.0) / (1.65 * cols.mla)
+    return LeafTangentSeries(dg_table * dx[:, None], dg_at_psi * dx[:, None], torch.ones_like(cols.mla))
+
+
+def sensor_jac_series_workspace_bytes(scheme, ncol, nz, nb, nt, nsel, nsens, npar):
+    """Device workspace of a :class:`SensorJacSeriesPlan` call of a scheme of ``SENSJAC_SCHEMES``: the records of
+    :func:`levels_series_workspace_bytes` at the same offsets, the side records of the LAI and of the leaf-angle derivative, and the slice
+    partial sums of every (column, t)."""
+    return int(_lib.load().crt_hip_sensor_jac_series_workspace_bytes(_lib.SCHEME_IDS[scheme], ncol, nz, nb, nt, nsel, nsens, npar))
+
+
+class SensorJacSeriesPlan(SensorJacPlan):
+    """The Jacobian of :class:`SensorJacPlan` for the ``sun.nt`` sun states of every column in one call
+    (``crt_hip_sensor_jac_series_f64``): each output ``(ncol, nt, nsel, nsens, npar)`` float64, the Jacobian of the sums of
+    :class:`SensorLevelsSeriesPlan` with respect to ONE parameter vector per column (``.params`` as in :class:`SensorJacPlan`).
+    ``out[k][:, t]`` is bitwise what :class:`SensorJacPlan` returns with ``psi = sun.psi[:, t]`` (``g_at_psi`` likewise), the incoming
+    spectra of step ``t`` and ``tangent.step(t)``; ``cols.psi``, ``cols.g_at_psi`` and ``bands.I_dr0 / I_df0`` are not read.  ``sun``: a
+    float64 :class:`SunSeries`; ``tangent``: a :class:`LeafTangentSeries` of the same ``nt`` (e.g. :func:`leaf_tangent_series`) or ``None``.
+
+    For ``SENSJAC_SCHEMES`` the canopy part of the column precompute and the side precomputes run once per column, the sun records, one
+    Jacobian kernel and (several band slices) one finish kernel serve every (column, t).  The workspace also holds what a
+    :class:`SensorLevelsSeriesPlan` of the same shape needs: that plan, called on ``plan.workspace`` with ``FLAG_SKIP_PRECOMPUTE`` after
+    this one, gives the forward sums of the residual.  For n79 and zq the plan loops the composed path of :class:`SensorJacPlan` over ``t``
+    (no workspace, no flags); ``4s`` and ``zq_pa`` are a ValueError.  For :func:`gauss_newton_step`:
+    ``J.reshape(ncol, nt * nsel * nsens, npar)``."""
+
+    _entry_name = "crt_hip_sensor_jac_series_f64"
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, sensors: SensorSet, *, d_leaf_r=None, d_leaf_t=None,
+                 d_soil_r=None, lai=True, tangent=None, keys=LEVEL_KEYS, mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
+        keys = self._check_static(scheme, tau_d_method, keys, sensors=sensors, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r,
+                                  lai=lai, tangent=tangent, sun=sun)  # (a sun that is no SunSeries: before _build looks at it)
+        self._build(scheme, cols, bands, sun, levels, sensors, d_leaf_r, d_leaf_t, d_soil_r, lai, tangent, keys, mu_s, tau_d_method, out, workspace)
+
+    @staticmethod
+    def _check_extras(sensors=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, tangent=None, sun=None, **_):
+        if not isinstance(sensors, SensorSet):
+            raise TypeError("sensors must be a SensorSet")
+        if not isinstance(sun, SunSeries) or isinstance(sun, SunSeriesF32):
+            raise TypeError("sun must be a SunSeries (float64 spectra)")
+        if tangent is not None and not isinstance(tangent, LeafTangentSeries):
+            raise TypeError("tangent must be a LeafTangentSeries")
+        if tangent is not None and tangent.nt != sun.nt:
+            raise ValueError(f"the tangent has nt = {tangent.nt} sun states, the series {sun.nt}")
+        if _sensjac_ntan(d_leaf_r, d_leaf_t, d_soil_r) + bool(lai) + (tangent is not None) == 0:
+            raise ValueError("no parameter at all: give a direction, lai=True or a tangent")
+
+    def __call__(self, stream=None, *, flags=0):
+        if not self._composed:
+            return _SolvePlan.__call__(self, stream, flags=flags)
+        if flags:
+            raise ValueError(f"the sensor Jacobian of {self.scheme} is composed of three calls per sun state: it takes no flags")
+        s = torch.cuda.current_stream(self.cols.device) if stream is None else stream
+        sun, reports = self.sun, []
+        with torch.cuda.stream(s):
+            for t in range(sun.nt):
+                plan = SensorJacPlan(self.scheme, _step_columns(self.cols, sun, t), _step_bands(self.bands, sun, t), self.levels, self.sensors,
+                                     **{"d_" + n: d for n, d in self.dirs.items()}, lai="lai" in self.params,
+                                     tangent=None if self.tangent is None else self.tangent.step(t), keys=self.keys, **self._kw)
+                for k, v in plan().items():
+                    self.out[k][:, t] = v
+                reports.append(plan.last_kernel())
+        self._report = " | ".join(reports)
+        return self.out
+
+
+def _step_columns(cols, sun, t):
+    """``cols`` with the sun of step ``t`` of ``sun`` (views; the sun angles as contiguous copies)."""
+    return Columns(sun.psi[:, t].contiguous(), cols.lai, cols.g_kind, cols.g_param, cols.mla,
+                   None if sun.g_at_psi is None else sun.g_at_psi[:, t].contiguous(), cols.g_table)
+
+
+def _step_bands(bands, sun, t):
+    """``bands`` with the incoming spectra of step ``t`` of ``sun`` (shared rows expanded where only one side is per column)."""
+    rows = max(sun.I_dr0.shape[0], bands.leaf_r.shape[0])
+    g = lambda v: None if v is None else v.expand(rows, -1).contiguous()  # noqa: E731
+    return Bands(g(sun.I_dr0[:, t]), g(sun.I_df0[:, t]), g(bands.leaf_r), g(bands.leaf_t), g(bands.soil_r))
+
+
+def sensor_jacobian_series(scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, sensors: SensorSet, **kw):
+    """One-shot :class:`SensorJacSeriesPlan`: ``{key: (ncol, nt, nsel, nsens, npar)}`` at the sorted levels."""
+    SensorJacSeriesPlan._check_static(scheme, kw.get("tau_d_method", "quad"), kw.get("keys"), sensors=sensors, d_leaf_r=kw.get("d_leaf_r"),
+                                      d_leaf_t=kw.get("d_leaf_t"), d_soil_r=kw.get("d_soil_r"), lai=kw.get("lai", True),
+                                      tangent=kw.get("tangent"), sun=sun)  # (before any device is touched)
+    with torch.cuda.device(cols.device):
+        return SensorJacSeriesPlan(scheme, cols, bands, sun, levels, sensors, **kw)()
+
+
 def gauss_newton_step(J, r, *, damping=0.0):
     """One damped Gauss-Newton (Levenberg-Marquardt) step of every column: ``J`` ``(ncol, nobs, npar)``, ``r`` ``(ncol, nobs)`` ->
     ``delta`` ``(ncol, npar)``, the solution of ``(J^T J + damping * diag(J^T J)) delta = -J^T r`` (``damping``: a number, or ``(ncol,)`` for a
-    damping of every column's own).  Plain torch on the tensors' device: the
+    damping of every column's own).  A series Jacobian ``(ncol, nt, nsel, nsens, npar)`` of :class:`SensorJacSeriesPlan` needs nothing
+    more: ``J.reshape(ncol, nt * nsel * nsens, npar)``.  Plain torch on the tensors' device: the
     normal equations, scaled to a unit diagonal, are solved by a Cholesky factorisation written as ``npar`` vector steps over the
     columns (no pivoting is needed, no solver library is called).  A parameter whose Jacobian column is zero gets ``delta = 0``.  A
     convenience for a handful of parameters, not a hot path."""

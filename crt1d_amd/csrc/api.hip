@@ -3,6 +3,7 @@
 #include <math.h>
 
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
 
 #include "epilogue.hpp"
@@ -670,18 +671,22 @@ static size_t levels_deriv_workspace_bytes(SideLen len, int scheme, int32_t ncol
 // launch(sa, la, side, s, probe): the entry's derivative kernel;  side_pre(ca, side, s): its side precompute, after K0 on the same stream
 // (the gradient runs two, into two side records one behind the other).  closed_only: n79 and zq are not served either;  tail_bytes: what the
 // entry keeps behind the side records (the gradient's slice sums).
+// ser (crt1d_hip_sensjac_series.h): the records are those of a level series -- canopy records at `workspace`, then the sun records, the side
+// records behind both -- K0 is launch_colpre_series, and pre_report is reported as it stands; tail_bytes SIZE_MAX: a size beyond size_t.
 template <class Launch, class SidePre>
 static int levels_deriv_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
                              int32_t nsel, void* workspace, size_t workspace_bytes, crt_stream_t stream, bool args_ok, SideLen side_len,
-                             const char* pre_report, Launch launch, SidePre side_pre, bool closed_only = false, size_t tail_bytes = 0) {
+                             const char* pre_report, Launch launch, SidePre side_pre, bool closed_only = false, size_t tail_bytes = 0,
+                             const crt_sun_series* ser = nullptr) {
   if (!scheme_ok(scheme) || !cols || !levels || !args_ok) return CRT_ERR_BAD_ARG;
   LevArgs la = {};
   if (const int st = parse_levels(cols, levels, nsel, la)) return st;
   SolveOpts o;
   const crt_outputs none = {};
   const bool sized = cols->ncol > 0 && cols->nz > 0;
-  const int chk = check_solve(scheme, cols, bands, opts, &none, workspace, workspace_bytes, nullptr, &la, nullptr, o,
-                              sized ? side_bytes(side_len, scheme, cols->ncol, cols->nz) + tail_bytes : 0);
+  const size_t sides = sized ? side_bytes(side_len, scheme, cols->ncol, cols->nz) : 0;
+  const int chk = check_solve(scheme, cols, bands, opts, &none, workspace, workspace_bytes, nullptr, &la, ser, o,
+                              !sized ? 0 : tail_bytes > SIZE_MAX - sides ? SIZE_MAX : sides + tail_bytes);
   if (chk == CRT_ERR_BAD_ARG || chk == CRT_ERR_SHAPE) return chk;  // an argument error is one for every scheme
   if (scheme == CRT_SCHEME_4S || scheme == CRT_SCHEME_ZQ_PA) return CRT_ERR_UNSUPPORTED;  // whatever the workspace (a follow-up: crt1d_hip_jac.h)
   if (closed_only && is_tri(scheme)) return CRT_ERR_UNSUPPORTED;                          // (the gradient: crt1d_hip_grad.h)
@@ -689,14 +694,23 @@ static int levels_deriv_impl(int scheme, const crt_columns* cols, const crt_band
   ColArgs ca;
   SolveArgs sa;
   build_args(scheme, cols, bands, &none, workspace, 0, o, ca, sa);
-  double* const side = reinterpret_cast<double*>(static_cast<char*>(workspace) + crt_hip_workspace_bytes_nb(scheme, cols->ncol, cols->nz, bands->nb));
+  const size_t rec = ser ? crt_hip_levels_series_workspace_bytes(scheme, cols->ncol, cols->nz, ser->nt)
+                         : crt_hip_workspace_bytes_nb(scheme, cols->ncol, cols->nz, bands->nb);
+  double* const side = reinterpret_cast<double*>(static_cast<char*>(workspace) + rec);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (const int st = launch(sa, la, side, s, true)) return st;  // a shape that is not served: before K0 has written anything
-  if (const int st = k0_step(ca, o.flags, false, s)) return st;
+  if (ser) {
+    ca.psi = ser->psi;
+    ca.g_at_psi = ser->g_at_psi;
+    double* const sunrec = ca.ws + (size_t)ca.ncol * can_len(scheme, ca.nz);
+    if (const int st = (o.flags & CRT_FLAG_SKIP_PRECOMPUTE) ? init_quadrature(s) : launch_colpre_series(ca, ser->nt, sunrec, s)) return st;
+  } else if (const int st = k0_step(ca, o.flags, false, s)) {
+    return st;
+  }
   if (!(o.flags & CRT_FLAG_SKIP_PRECOMPUTE))
     if (const int st = side_pre(ca, side, s)) return st;
   if (o.flags & CRT_FLAG_PRECOMPUTE_ONLY) {
-    if (side_len) note_kernel("%s", side_len(scheme, cols->nz) ? pre_report : "k_colpre");
+    if (side_len) note_kernel("%s", ser || side_len(scheme, cols->nz) ? pre_report : "k_colpre");
     return CRT_OK;
   }
   return launch(sa, la, side, s, false);
@@ -817,10 +831,11 @@ size_t crt_hip_sensor_jac_workspace_bytes(int scheme, int32_t ncol, int32_t nz, 
   return rec == 0 ? 0 : rec + sensjac_part_bytes(ncol, nb, nsel, nsens, npar);
 }
 
-int crt_hip_sensor_jac_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
-                           int32_t nsel, const crt_sensor_set* sensors, const crt_optics_dirs* dirs, int with_lai,
-                           const crt_leaf_tangent* tangent, const crt_sensjac_out* out, void* workspace, size_t workspace_bytes,
-                           crt_stream_t stream) {
+// both forms of the sensor Jacobian; ser: the sun-angle series (crt1d_hip_sensjac_series.h), whose tangent carries dg_at_psi as [ncol][nt]
+static int sensor_jac_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_sun_series* ser, bool series,
+                           const crt_options* opts, const int32_t* levels, int32_t nsel, const crt_sensor_set* sensors,
+                           const crt_optics_dirs* dirs, int with_lai, const DleafTan* tangent, const crt_sensjac_out* out, void* workspace,
+                           size_t workspace_bytes, crt_stream_t stream) {
   SensJacArgs ja = {};
   SensArgs& sn = ja.sn;
   const int ntan = dirs ? dirs->ntan : 0;
@@ -828,7 +843,7 @@ int crt_hip_sensor_jac_f64(int scheme, const crt_columns* cols, const crt_bands*
                  bands && bands->nb > 0 && out && (out->I_dr || out->I_df_d || out->I_df_u || out->F) && ntan >= 0 &&
                  ntan <= CRT_SENSJAC_MAX_NTAN && (ntan == 0 || dirs->leaf_r || dirs->leaf_t || dirs->soil_r) &&
                  (ntan == 0 || dirs->col_stride == 0 || dirs->col_stride == (int64_t)ntan * bands->nb) &&
-                 (!tangent || (tangent->dg_table && tangent->dg_at_psi));
+                 (!tangent || (tangent->dg_table && tangent->dg_at_psi)) && (!series || ser);
   ja.ntan = ntan;
   ja.lai = with_lai ? 1 : 0;
   ja.leaf = tangent ? 1 : 0;
@@ -860,26 +875,65 @@ int crt_hip_sensor_jac_f64(int scheme, const crt_columns* cols, const crt_bands*
     }
   }
   // (sizes that are not positive are an argument error of the shared path: no tail then)
-  const bool sized = args_ok && cols && cols->ncol > 0 && cols->nz > 0;
+  const bool sized = args_ok && cols && cols->ncol > 0 && cols->nz > 0 && (!ser || ser->nt >= 1);
   const bool side_lai = sized && ja.lai && dlai_side_len(scheme, cols->nz) > 0, side_leaf = args_ok && ja.leaf;
   const bool sel_ok = nsel >= 1 && nsel <= CRT_MAX_LEVEL_SELECT;
+  const int nt = ser ? ser->nt : 1;
+  char k0[48] = "k_colpre", pre[96];  // what a CRT_FLAG_PRECOMPUTE_ONLY call reports
+  if (ser) std::snprintf(k0, sizeof k0, "k_colpre<canopy> + k_colsun nt=%d", nt);
+  std::snprintf(pre, sizeof pre, "%s%s%s", k0, side_lai ? " + k_dlai_side" : "", !side_leaf ? "" : ser ? " + k_dleaf_side<canopy>" : " + k_dleaf_side");
   return levels_deriv_impl(
-      scheme, cols, bands, opts, levels, nsel, workspace, workspace_bytes, stream, args_ok, grad_side_len,
-      side_lai && side_leaf ? "k_colpre + k_dlai_side + k_dleaf_side" : side_lai ? "k_colpre + k_dlai_side" : side_leaf ? "k_colpre + k_dleaf_side" : "k_colpre",
+      scheme, cols, bands, opts, levels, nsel, workspace, workspace_bytes, stream, args_ok, grad_side_len, pre,
       [&](const SolveArgs& sa, const LevArgs& la, const double* side, hipStream_t s, bool probe) {
         ja.side_lai = side;
         ja.side_leaf = side + (size_t)sa.ncol * dlai_side_len(scheme, sa.nz);
         sn.part = const_cast<double*>(side) + (size_t)sa.ncol * grad_side_len(scheme, sa.nz);
-        return launch_sens_jac(scheme, sa, la, ja, s, probe);
+        if (!ser) return launch_sens_jac(scheme, sa, la, ja, s, probe);
+        const SeriesArgs sr = {nt, scheme, sa.nz, can_len(scheme, sa.nz), sun_len(scheme, sa.nz), sa.ws, sa.ws + (size_t)sa.ncol * can_len(scheme, sa.nz),
+                               ser->col_stride, ser->I_dr0, ser->I_df0};
+        return launch_sens_jac(scheme, sa, la, ja, s, probe, &sr, tangent ? tangent->dg_at_psi : nullptr);
       },
       [&](const ColArgs& ca, double* side, hipStream_t s) {
         if (side_lai)
           if (const int st = launch_dlai_side(ca, side, s)) return st;
         if (!side_leaf) return (int)CRT_OK;
-        return launch_dleaf_side(ca, DleafTan{tangent->dg_table, tangent->dg_at_psi, tangent->dmla},
-                                 side + (size_t)ca.ncol * dlai_side_len(scheme, ca.nz), s);
+        return launch_dleaf_side(ca, *tangent, side + (size_t)ca.ncol * dlai_side_len(scheme, ca.nz), s, ser != nullptr);
       },
-      true, sized && sel_ok ? sensjac_part_bytes(cols->ncol, bands->nb, nsel, sn.nsens, npar) : 0);
+      true, sized && sel_ok ? sensjac_part_bytes(cols->ncol, bands->nb, nsel, sn.nsens, npar, nt) : 0, ser);
+}
+
+int crt_hip_sensor_jac_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
+                           int32_t nsel, const crt_sensor_set* sensors, const crt_optics_dirs* dirs, int with_lai,
+                           const crt_leaf_tangent* tangent, const crt_sensjac_out* out, void* workspace, size_t workspace_bytes,
+                           crt_stream_t stream) {
+  const DleafTan tn = tangent ? DleafTan{tangent->dg_table, tangent->dg_at_psi, tangent->dmla} : DleafTan{};
+  return sensor_jac_impl(scheme, cols, bands, nullptr, false, opts, levels, nsel, sensors, dirs, with_lai, tangent ? &tn : nullptr, out, workspace,
+                         workspace_bytes, stream);
+}
+
+// the sun-angle series of the two (crt1d_hip_sensjac_series.h): the records of a level series, the side records, the slice sums of every (column, t)
+size_t crt_hip_sensor_jac_series_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nt, int32_t nsel, int32_t nsens,
+                                                 int32_t npar) {
+  if (nsel < 1 || nsel > CRT_MAX_LEVEL_SELECT || nsens < 1 || nsens > CRT_MAX_SENSOR_BANDS || npar < 1 || npar > CRT_SENSJAC_MAX_NTAN + 2 || nb <= 0)
+    return 0;
+  const size_t rec = crt_hip_levels_series_workspace_bytes(scheme, ncol, nz, nt);
+  if (rec == 0) return 0;
+  const size_t sides = side_bytes(grad_side_len, scheme, ncol, nz), part = sensjac_part_bytes(ncol, nb, nsel, nsens, npar, nt);
+  return part > SIZE_MAX - rec - sides ? 0 : rec + sides + part;
+}
+
+int crt_hip_sensor_jac_series_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_sun_series* sun, const crt_options* opts,
+                                  const int32_t* levels, int32_t nsel, const crt_sensor_set* sensors, const crt_optics_dirs* dirs, int with_lai,
+                                  const crt_leaf_tangent_series* tangent, const crt_sensjac_out* out, void* workspace, size_t workspace_bytes,
+                                  crt_stream_t stream) {
+  const DleafTan tn = tangent ? DleafTan{tangent->dg_table, tangent->dg_at_psi, tangent->dmla} : DleafTan{};
+  return sensor_jac_impl(scheme, cols, bands, sun, true, opts, levels, nsel, sensors, dirs, with_lai, tangent ? &tn : nullptr, out, workspace,
+                         workspace_bytes, stream);
+}
+
+int crt_hip_g_dparam_series_f64(const crt_columns* cols, const crt_sun_series* sun, double* dg_table, double* dg_at_psi, crt_stream_t stream) {
+  if (!cols || !sun || !dg_table || !dg_at_psi || !sun->psi || sun->nt < 1 || !cols->g_kind || cols->ncol <= 0) return CRT_ERR_BAD_ARG;
+  return crt::launch_g_dparam(cols->ncol, sun->psi, cols->g_kind, cols->g_param, dg_table, dg_at_psi, static_cast<hipStream_t>(stream), sun->nt);
 }
 
 int crt_hip_bandsum_finish_f64(const crt_columns* cols, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream) {

@@ -13,6 +13,7 @@
 #include "crt1d_hip_grad.h"
 #include "crt1d_hip_jac.h"
 #include "crt1d_hip_sensjac.h"
+#include "crt1d_hip_sensjac_series.h"
 #include "crt1d_hip_sensor.h"
 
 namespace crt {
@@ -1013,9 +1014,13 @@ constexpr int dleaf_side_len(int scheme, int nz) {
 }
 static_assert(dleaf_side_len(CRT_SCHEME_N79, 7) == dlai_side_len(CRT_SCHEME_N79, 7) && dleaf_side_len(CRT_SCHEME_ZQ, 7) == dlai_side_len(CRT_SCHEME_ZQ, 7),
               "k_dlai_tri reads either side record");
-int launch_dleaf_side(const ColArgs& ca, const DleafTan& tn, double* side, hipStream_t s);
+// canopy (2s, bl, g77, bf; the sun-angle series of the sensor Jacobian): on canopy records, without the one entry that follows the sun --
+// the header tangent K_b' is written as 0 and tn.dg_at_psi is not read
+int launch_dleaf_side(const ColArgs& ca, const DleafTan& tn, double* side, hipStream_t s, bool canopy = false);
 int launch_dleaf(int scheme, const SolveArgs& a, const LevArgs& la, const DlaiArgs& da, hipStream_t s, bool probe);
-int launch_g_dparam(int ncol, const double* psi, const int32_t* g_kind, const double* g_param, double* dg_table, double* dg_at_psi, hipStream_t s);
+// psi / dg_at_psi: [ncol][nt]
+int launch_g_dparam(int ncol, const double* psi, const int32_t* g_kind, const double* g_param, double* dg_table, double* dg_at_psi, hipStream_t s,
+                    int nt = 1);
 int launch_dtau_d_dleaf(const double* kb_nodes, const double* dkb_nodes, const double* L, long long n, int method, double* out, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
@@ -1058,12 +1063,18 @@ inline LevSlices sensjac_slices(int nb, int nsel, int npar) {
   return lev_slices(nb, wmax);
 }
 // bytes of the slice sums behind the side records (0 with one slice; where no slice width fits, those of 64-lane slices: the call refuses)
-inline size_t sensjac_part_bytes(int ncol, int nb, int nsel, int nsens, int npar) {
+// nt: the sun states of a series ([ncol][nt][nslice]...); SIZE_MAX: beyond size_t
+inline size_t sensjac_part_bytes(int ncol, int nb, int nsel, int nsens, int npar, int nt = 1) {
   LevSlices ls = sensjac_slices(nb, nsel, npar);
   if (ls.nslice == 0) ls = lev_slices(nb, 64);
-  return ls.nslice <= 1 ? 0 : (size_t)ncol * ls.nslice * nsel * nsens * npar * 4 * sizeof(double);
+  if (ls.nslice <= 1) return 0;
+  const size_t per = (size_t)ls.nslice * nsel * nsens * npar * 4 * sizeof(double), nv = (size_t)ncol * (size_t)nt;
+  return nv > SIZE_MAX / per ? SIZE_MAX : nv * per;
 }
-int launch_sens_jac(int scheme, const SolveArgs& a, const LevArgs& la, const SensJacArgs& ja, hipStream_t s, bool probe);
+// sr: nullptr = k_sens_jac; else k_sens_jac_series on the same slices (crt1d_hip_sensjac_series.h): a.ws / sr->can hold canopy records,
+// sn.o / sn.part are indexed by c * nt + t, side_leaf comes from launch_dleaf_side(.., canopy = true) and dg_at_psi is [ncol][nt]
+int launch_sens_jac(int scheme, const SolveArgs& a, const LevArgs& la, const SensJacArgs& ja, hipStream_t s, bool probe,
+                    const SeriesArgs* sr = nullptr, const double* dg_at_psi = nullptr);
 
 // launchers implemented in the .hip files
 int launch_colpre(const ColArgs& a, hipStream_t s);

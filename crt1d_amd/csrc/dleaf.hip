@@ -17,7 +17,8 @@
 //                consecutive bands), O(nsel).
 //  n79, zq       k_dlai_tri (dlai.hip) through launch_dlai, on this side record: it takes every record entry as value | tangent and reads
 //                no header scalar but zq's plain mu.
-//  k_g_dparam    dG / d g_param of the parametric kinds at the nodes and at the sun angle;  k_dtau_d_dleaf  tau_d^th for arbitrary L.
+//  k_g_dparam    dG / d g_param of the parametric kinds at the nodes and at the sun angle (a series: at every sun angle of the column)
+//  k_dtau_d_dleaf  tau_d^th for arbitrary L.
 #include "col_record.hpp"
 #include "jac_schemes.hpp"
 #include "launch_forms.hpp"
@@ -44,6 +45,9 @@ __device__ inline double dtau_leaf_9sky(const double* k9, const double* dk9, dou
 
 constexpr int SIDE_BLOCK = 128;
 
+// CAN (2s, bl, g77, bf; the sun-angle series of the sensor Jacobian, sensjac.hip): a.ws holds canopy records, and the one entry that follows
+// the sun, the header tangent K_b', is left 0 -- neither the sun's slots of the record nor tn.dg_at_psi are read.
+template <bool CAN>
 __global__ __launch_bounds__(SIDE_BLOCK) void k_dleaf_side(ColArgs a, DleafTan tn, double* __restrict__ side) {
   __shared__ double kq[NQT], dkq[NQT], pm[NQT];
   __shared__ double k9[CRT_NQ_9SKY], dk9[CRT_NQ_9SKY];
@@ -67,10 +71,11 @@ __global__ __launch_bounds__(SIDE_BLOCK) void k_dleaf_side(ColArgs a, DleafTan t
     if (tid == 0) dmb = s;
   }
   __syncthreads();
-  const double* rec = a.ws + (long long)c * rec_len(a.scheme, nz);
+  const double* rec = a.ws + (long long)c * (CAN ? can_len(a.scheme, nz) : rec_len(a.scheme, nz));
   const double* lai = in.lai;
   double* sd = side + (long long)c * dleaf_side_len(a.scheme, nz);
-  const double dK = tn.dg_at_psi[c] / rec[S_MU];
+  double dK = 0.0;
+  if constexpr (!CAN) dK = tn.dg_at_psi[c] / rec[S_MU];
   if (tid < REC_HDR) {
     double t = 0.0;
     if (tid == S_KB) t = dK;
@@ -93,7 +98,7 @@ __global__ __launch_bounds__(SIDE_BLOCK) void k_dleaf_side(ColArgs a, DleafTan t
     for (int j = tid; j < nz; j += SIDE_BLOCK) v[j] = dtau_leaf_quad(kq, dkq, lai[j]);  // always 'quad', _solve_bl.py:35-37
     return;
   }
-  if (a.scheme != CRT_SCHEME_N79 && a.scheme != CRT_SCHEME_ZQ) return;  // 2s, g77, bf: the header alone
+  if (CAN || (a.scheme != CRT_SCHEME_N79 && a.scheme != CRT_SCHEME_ZQ)) return;  // 2s, g77, bf: the header alone
   const double Kb = rec[S_KB];
   const bool n79u = a.scheme == CRT_SCHEME_N79 && rec[S_UNIF] != 0.0 && nz >= 3;  // one (tb, td) serves every layer (k_colpre)
   const double dlu = rec[S_DL];
@@ -181,37 +186,43 @@ __device__ inline double dG_dparam(int kind, double x, double cs, double sn) {
 
 constexpr int GDP_BLOCK = 192;
 static_assert(CRT_NQ + 1 <= GDP_BLOCK, "a thread per node and one for the sun");
+constexpr int GDP_SUN0 = GDP_BLOCK - CRT_NQ;  // sun states served by the block of the nodes
 
-__global__ __launch_bounds__(GDP_BLOCK) void k_g_dparam(int ncol, const double* __restrict__ psi, const int32_t* __restrict__ g_kind,
+// psi / dg_at_psi: [ncol][nt].  Block y = 0 of a column: a thread per node, the others the sun states 0 .. GDP_SUN0; block y >= 1: the sun
+// states GDP_SUN0 + (y - 1) GDP_BLOCK + tid (a series with more than GDP_SUN0 states).
+__global__ __launch_bounds__(GDP_BLOCK) void k_g_dparam(int ncol, int nt, const double* __restrict__ psi, const int32_t* __restrict__ g_kind,
                                                          const double* __restrict__ g_param, double* __restrict__ dg_table,
                                                          double* __restrict__ dg_at_psi) {
   const int c = blockIdx.x, tid = threadIdx.x;
-  if (tid > CRT_NQ) return;
+  const long long t = blockIdx.y == 0 ? tid - CRT_NQ : GDP_SUN0 + (long long)(blockIdx.y - 1) * GDP_BLOCK + tid;
+  const bool node = blockIdx.y == 0 && tid < CRT_NQ;
+  if (!node && t >= nt) return;
   const int kind = g_kind[c];
   const double x = g_param ? g_param[c] : 0.0;
   double cs, sn;
-  if (tid < NQT) {
+  if (!node) {
+    const double p = psi[(long long)c * nt + t];
+    cs = cos(p);
+    sn = sin(p);
+  } else if (tid < NQT) {
     cs = qc.cs[tid];
     sn = qc.sn[tid];
   } else if (tid < NQT + NQG) {  // the nodes of crt_hip_quad_nodes(0.501, .) (colpre.hip, g4_interval)
-    const int t = tid - NQT;
+    const int g = tid - NQT;
     const double ps = acos(0.501);
-    const double lo = t < NGL ? ps : 0.0, hi = t < NGL ? 1.57079632679489661923 : ps;
-    const double p = lo + (qc.gx[t % NGL] + 1.0) * (hi - lo) / 2;
+    const double lo = g < NGL ? ps : 0.0, hi = g < NGL ? 1.57079632679489661923 : ps;
+    const double p = lo + (qc.gx[g % NGL] + 1.0) * (hi - lo) / 2;
     cs = cos(p);
     sn = sin(p);
-  } else if (tid < CRT_NQ) {
+  } else {
     cs = qc.cs9[tid - NQT - NQG];
     sn = qc.sn9[tid - NQT - NQG];
-  } else {
-    cs = cos(psi[c]);
-    sn = sin(psi[c]);
   }
   const double d = dG_dparam(kind, x, cs, sn);
-  if (tid < CRT_NQ)
+  if (node)
     dg_table[(long long)c * CRT_NQ + tid] = d;
   else
-    dg_at_psi[c] = d;
+    dg_at_psi[(long long)c * nt + t] = d;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -275,15 +286,18 @@ int launch_dleaf(int scheme, const SolveArgs& a, const LevArgs& la, const DlaiAr
 }
 
 // after K0 on the same stream (the quadrature tables are uploaded by then)
-int launch_dleaf_side(const ColArgs& ca, const DleafTan& tn, double* side, hipStream_t s) {
-  return launch_kernel(k_dleaf_side, dim3(ca.ncol), SIDE_BLOCK, 0, s, ca, tn, side);
+int launch_dleaf_side(const ColArgs& ca, const DleafTan& tn, double* side, hipStream_t s, bool canopy) {
+  if (canopy) return launch_kernel(k_dleaf_side<true>, dim3(ca.ncol), SIDE_BLOCK, 0, s, ca, tn, side);
+  return launch_kernel(k_dleaf_side<false>, dim3(ca.ncol), SIDE_BLOCK, 0, s, ca, tn, side);
 }
 
 int launch_g_dparam(int ncol, const double* psi, const int32_t* g_kind, const double* g_param, double* dg_table, double* dg_at_psi,
-                    hipStream_t s) {
+                    hipStream_t s, int nt) {
+  const long long ny = 1 + (nt > GDP_SUN0 ? ((long long)nt - GDP_SUN0 + GDP_BLOCK - 1) / GDP_BLOCK : 0);
+  if (ny > 65535) return CRT_ERR_UNSUPPORTED;
   const int st = init_quadrature(s);
   if (st != CRT_OK) return st;
-  return launch_kernel(k_g_dparam, dim3(ncol), GDP_BLOCK, 0, s, ncol, psi, g_kind, g_param, dg_table, dg_at_psi);
+  return launch_kernel(k_g_dparam, dim3(ncol, (unsigned)ny), GDP_BLOCK, 0, s, ncol, nt, psi, g_kind, g_param, dg_table, dg_at_psi);
 }
 
 int launch_dtau_d_dleaf(const double* kb_nodes, const double* dkb_nodes, const double* L, long long n, int method, double* out,

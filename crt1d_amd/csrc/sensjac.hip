@@ -15,7 +15,14 @@
 //                       leaf angle   the same
 //                     and each phase ends with ONE barrier and sens_fold_rows (crt_internal.hpp): a wave per (level, sensor band,
 //                     parameter) over the support inside the slice, sens_row's order.  R = max(3 ntan, 4).
-//  k_sens_jac_finish  several band slices: a thread per output element adds the slice sums in ascending order (k_sens_finish's rule).
+//  k_sens_jac_series  the same body (sens_jac_body) for the sun states of a series (include/crt1d_hip_sensjac_series.h): a workgroup owns one
+//                     (column, band slice, sun state) on the grid of lev_series_grid; the header, the selected entries of L_j and
+//                     e^{-K_b L_j} and the ground entry are read straight from the canopy record of the column and the sun record of
+//                     (column, t) -- the record is not assembled, the static LDS is that of k_sens_jac -- and K_b' of the leaf-angle pass
+//                     is formed here, dG(psi_t) / cos psi_t, the side record being the sun-independent one of k_dleaf_side<canopy>.
+//                     Same slices, lanes and R as k_sens_jac (sensjac_slices): slice [:, t] of the output has the per-step bits.
+//  k_sens_jac_finish  several band slices: a thread per output element adds the slice sums in ascending order (k_sens_finish's rule);
+//                     the series: ncol * nt "columns" v = c * nt + t.
 // No atomics anywhere: a column's result does not depend on the batch, and an output's bits do not depend on which others are asked for
 // (every quantity is staged and folded; a NULL output is only not written).
 #include "jac_schemes.hpp"
@@ -47,27 +54,61 @@ __device__ __forceinline__ JBandT<Du> sj_seed_band(const DBand& in, int p) {
   return JBandT<Du>{in.I_dr0, in.I_df0, Du{in.r, p == 0 ? 1.0 : 0.0}, Du{in.t, p == 1 ? 1.0 : 0.0}, Du{in.s, p == 2 ? 1.0 : 0.0}};
 }
 
-template <class G, bool BL>
-__global__ __launch_bounds__(SENSJAC_BLOCK) void k_sens_jac(SolveArgs a, LevArgs la, SensJacArgs ja, int per, int R) {
+// Where the body below finds the band-independent entries of its (column, sun state): the header scalar i, the LAI L_j and the beam
+// fraction e^{-K_b L_j} of level j (j = 0: the ground), and the tangent of header scalar i along the leaf-angle direction.
+struct RecStep {  // the record k_colpre wrote; sdl: the side record of k_dleaf_side
+  const double* rec;
+  int nz;
+  __device__ __forceinline__ double hdr(int i) const { return rec[i]; }
+  __device__ __forceinline__ double L(int j) const { return rec[REC_HDR + j]; }
+  __device__ __forceinline__ double E(int j) const { return rec[REC_HDR + nz + j]; }
+  __device__ __forceinline__ double dhdr(const double* sdl, int i) const { return sdl[i]; }
+};
+// The canopy record of the column and the sun record of (column, t) (SeriesArgs, crt_internal.hpp), each entry read where it lies -- the
+// record is not assembled.  sdl: the side record of k_dleaf_side<canopy>, which leaves out the one tangent that follows the sun:
+// K_b' = dG(psi_t) / cos psi_t, the division k_dleaf_side does.
+struct RecSeries {
+  const double *can, *sun;
+  const double* dgp;  // dG at psi of (column, t); read with a leaf-angle column only
+  int scheme, nz;
+  __device__ __forceinline__ double hdr(int i) const {
+    int si = -1;
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+      if (sun_hdr_slot(k) == i) si = k;
+    return si >= 0 ? sun[si] : can[i];
+  }
+  __device__ __forceinline__ double vec(int vc, int j) const {
+    const int sv = rec_vec_sun(scheme, vc);
+    return sv >= 0 ? sun[SUN_HDR + sv * nz + j] : can[REC_HDR + vc * nz + j];
+  }
+  __device__ __forceinline__ double L(int j) const { return vec(0, j); }
+  __device__ __forceinline__ double E(int j) const { return vec(1, j); }
+  __device__ __forceinline__ double dhdr(const double* sdl, int i) const { return i == S_KB ? *dgp / hdr(S_MU) : sdl[i]; }
+};
+
+// The work of one workgroup: column c, band slice `slice` of nslice, sums indexed by v (the column; series: c * nt + t).  `a` carries the
+// spectra of v at the column's index.
+template <class G, bool BL, class Rec>
+__device__ __forceinline__ void sens_jac_body(const SolveArgs& a, const LevArgs& la, const SensJacArgs& ja, int per, int R, int c, int slice,
+                                              int nslice, long long v, const Rec rc, double* rows) {
   using SJ = typename G::J;
-  extern __shared__ double rows[];           // [nsel][R][blockDim.x]
   __shared__ double hd[HDR_TAN + REC_HDR];  // k_dleaf's layout: header | e^{-K_b LT} at the ground | ... | the header's leaf-angle tangents
   __shared__ double lvL[CRT_MAX_LEVEL_SELECT], lvE[CRT_MAX_LEVEL_SELECT], lvTs[CRT_MAX_LEVEL_SELECT], lvTh[CRT_MAX_LEVEL_SELECT];
-  const int c = blockIdx.x, slice = blockIdx.y, nslice = gridDim.y, nz = a.nz, nb = a.nb, nsel = la.nsel, tid = threadIdx.x, nthr = blockDim.x;
+  const int nz = a.nz, nb = a.nb, nsel = la.nsel, tid = threadIdx.x, nthr = blockDim.x;
   const int b = slice * per + tid;
   const bool live = tid < per && b < nb;
   const int ntan = ja.ntan, npar = ntan + ja.lai + ja.leaf;
-  const double* rec = a.ws + (long long)c * a.reclen;
   const double* sdl = ja.side_leaf + (long long)c * (REC_HDR + (BL ? nz : 0));
   if (tid < REC_HDR) {
-    hd[tid] = rec[tid];
-    hd[HDR_TAN + tid] = ja.leaf ? sdl[tid] : 0.0;
+    hd[tid] = rc.hdr(tid);
+    hd[HDR_TAN + tid] = ja.leaf ? rc.dhdr(sdl, tid) : 0.0;
   }
-  if (tid == REC_HDR) hd[REC_HDR] = rec[REC_HDR + nz];  // e^{-K_b L} at the ground
+  if (tid == REC_HDR) hd[REC_HDR] = rc.E(0);  // e^{-K_b L} at the ground
   for (int r = tid; r < nsel; r += nthr) {
     const int j = la.lev[r];
-    lvL[r] = rec[REC_HDR + j];
-    lvE[r] = rec[REC_HDR + nz + j];
+    lvL[r] = rc.L(j);
+    lvE[r] = rc.E(j);
     if constexpr (BL) {
       lvTs[r] = ja.lai ? ja.side_lai[(long long)c * nz + j] : 0.0;  // L_j tau_d'(L_j)
       lvTh[r] = ja.leaf ? sdl[REC_HDR + j] : 0.0;                   // tau_d^th(L_j)
@@ -114,7 +155,7 @@ __global__ __launch_bounds__(SENSJAC_BLOCK) void k_sens_jac(SolveArgs a, LevArgs
           for (int i = 0; i < 3 * ntan; ++i) my[((size_t)r * R + i) * nthr] = 0.0;
     }
     __syncthreads();
-    sens_fold_rows<3>(ja.sn, rows, R, 0, ntan, 0, npar, slice, per, nb, nslice, c, nsel);
+    sens_fold_rows<3>(ja.sn, rows, R, 0, ntan, 0, npar, slice, per, nb, nslice, v, nsel);
     __syncthreads();
   }
 
@@ -139,7 +180,7 @@ __global__ __launch_bounds__(SENSJAC_BLOCK) void k_sens_jac(SolveArgs a, LevArgs
       }
     }
     __syncthreads();
-    sens_fold_rows<4>(ja.sn, rows, R, 0, 1, ntan, npar, slice, per, nb, nslice, c, nsel);
+    sens_fold_rows<4>(ja.sn, rows, R, 0, 1, ntan, npar, slice, per, nb, nslice, v, nsel);
     __syncthreads();
   }
 
@@ -164,8 +205,33 @@ __global__ __launch_bounds__(SENSJAC_BLOCK) void k_sens_jac(SolveArgs a, LevArgs
       }
     }
     __syncthreads();
-    sens_fold_rows<4>(ja.sn, rows, R, 0, 1, ntan + ja.lai, npar, slice, per, nb, nslice, c, nsel);
+    sens_fold_rows<4>(ja.sn, rows, R, 0, 1, ntan + ja.lai, npar, slice, per, nb, nslice, v, nsel);
   }
+}
+
+template <class G, bool BL>
+__global__ __launch_bounds__(SENSJAC_BLOCK) void k_sens_jac(SolveArgs a, LevArgs la, SensJacArgs ja, int per, int R) {
+  extern __shared__ double rows[];  // [nsel][R][blockDim.x]
+  const int c = blockIdx.x;
+  sens_jac_body<G, BL>(a, la, ja, per, R, c, blockIdx.y, gridDim.y, c, RecStep{a.ws + (long long)c * a.reclen, a.nz}, rows);
+}
+
+// The sun-angle series (include/crt1d_hip_sensjac_series.h): one workgroup per (column, band slice, sun state) on the grid of
+// lev_series_grid; the spectra of (column, t) as in series_lev_step.  The same body on the same slices: slice [:, t] has the per-step bits.
+template <class G, bool BL>
+__global__ __launch_bounds__(SENSJAC_BLOCK) void k_sens_jac_series(SolveArgs a, LevArgs la, SensJacArgs ja, SeriesArgs sr,
+                                                                   const double* __restrict__ dg_at_psi, int per, int R, int nslice) {
+  extern __shared__ double rows[];  // [nsel][R][blockDim.x]
+  const int c = blockIdx.x;
+  const int zt = blockIdx.z / nslice, slice = blockIdx.z - zt * nslice;
+  const long long tl = (long long)zt * gridDim.y + blockIdx.y;
+  if (tl >= sr.nt) return;  // (whole workgroup, before any barrier)
+  const long long v = (long long)c * sr.nt + tl;
+  const long long din = (long long)c * sr.col_stride + tl * a.nb - (long long)c * a.col_stride;
+  a.I_dr0 = static_cast<const double*>(sr.I_dr0) + din;
+  a.I_df0 = static_cast<const double*>(sr.I_df0) + din;
+  const RecSeries rc = {sr.can + (long long)c * sr.canlen, sr.sun + v * sr.sunlen, dg_at_psi + v, sr.scheme, sr.nz};
+  sens_jac_body<G, BL>(a, la, ja, per, R, c, slice, nslice, v, rc, rows);
 }
 
 // One thread per output element (c, r, s, par, q): the partial sums of the slices that meet the support of sensor band s, added in
@@ -195,33 +261,45 @@ __global__ __launch_bounds__(256) void k_sens_jac_finish(SensArgs sn, long long 
   o[((v * nsel + r) * nsens + s) * npar + par] = z;
 }
 
+// sr: nullptr = the per-step kernel; else the series kernel on the same slices (dg_at_psi [ncol][nt]: the series tangent, or nullptr)
 template <class G, bool BL = false>
-int launch_sens_jac_closed(const SolveArgs& a, const LevArgs& la, const SensJacArgs& ja, hipStream_t s, bool probe) {
+int launch_sens_jac_closed(const SolveArgs& a, const LevArgs& la, const SensJacArgs& ja, hipStream_t s, bool probe, const SeriesArgs* sr,
+                           const double* dg_at_psi) {
   const int npar = ja.ntan + ja.lai + ja.leaf, nsens = ja.sn.nsens;
   const LevSlices ls = sensjac_slices(a.nb, la.nsel, npar);
   if (ls.nslice == 0 || ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
-  const long long nfin = ((long long)a.ncol * la.nsel * nsens * npar * 4 + 255) / 256;
+  dim3 grid(a.ncol, ls.nslice);
+  if (sr && !lev_series_grid(a.ncol, sr->nt, ls.nslice, &grid)) return CRT_ERR_UNSUPPORTED;
+  const long long nv = (long long)a.ncol * (sr ? sr->nt : 1);
+  const long long nfin = (nv * la.nsel * nsens * npar * 4 + 255) / 256;
   if (ls.nslice > 1 && nfin > 0x7fffffffLL) return CRT_ERR_UNSUPPORTED;
   if (probe) return CRT_OK;
   const int R = sensjac_rows(ja.ntan);
   const size_t sh = (size_t)la.nsel * R * ls.nthr * sizeof(double);  // (<= the bound of sensjac_slices: ntan <= npar)
-  int st = launch_kernel(k_sens_jac<G, BL>, dim3(a.ncol, ls.nslice), ls.nthr, sh, s, a, la, ja, ls.per, R);
+  int st = sr ? launch_kernel(k_sens_jac_series<G, BL>, grid, ls.nthr, sh, s, a, la, ja, *sr, dg_at_psi, ls.per, R, ls.nslice)
+              : launch_kernel(k_sens_jac<G, BL>, grid, ls.nthr, sh, s, a, la, ja, ls.per, R);
   const bool fin = ls.nslice > 1;
   if (st == CRT_OK && fin)
-    st = launch_kernel(k_sens_jac_finish, dim3((unsigned)nfin), 256, 0, s, ja.sn, (long long)a.ncol, ls.nslice, ls.per, a.nb, la.nsel, npar);
-  if (st == CRT_OK)
-    note_kernel("k_sens_jac<%s> nsel=%d nsens=%d npar=%d slice=%d%s", G::J::NAME, la.nsel, nsens, npar, ls.per, fin ? " + k_sens_jac_finish" : "");
+    st = launch_kernel(k_sens_jac_finish, dim3((unsigned)nfin), 256, 0, s, ja.sn, nv, ls.nslice, ls.per, a.nb, la.nsel, npar);
+  if (st == CRT_OK) {
+    const char* const f = fin ? " + k_sens_jac_finish" : "";
+    if (sr)
+      note_kernel("k_sens_jac_series<%s> nt=%d nsel=%d nsens=%d npar=%d slice=%d%s", G::J::NAME, sr->nt, la.nsel, nsens, npar, ls.per, f);
+    else
+      note_kernel("k_sens_jac<%s> nsel=%d nsens=%d npar=%d slice=%d%s", G::J::NAME, la.nsel, nsens, npar, ls.per, f);
+  }
   return st;
 }
 
 }  // namespace
 
-int launch_sens_jac(int scheme, const SolveArgs& a, const LevArgs& la, const SensJacArgs& ja, hipStream_t s, bool probe) {
+int launch_sens_jac(int scheme, const SolveArgs& a, const LevArgs& la, const SensJacArgs& ja, hipStream_t s, bool probe, const SeriesArgs* sr,
+                    const double* dg_at_psi) {
   switch (scheme) {
-    case CRT_SCHEME_2S: return launch_sens_jac_closed<S2s>(a, la, ja, s, probe);
-    case CRT_SCHEME_BL: return launch_sens_jac_closed<SBl, true>(a, la, ja, s, probe);
-    case CRT_SCHEME_G77: return launch_sens_jac_closed<SG77<false>>(a, la, ja, s, probe);
-    case CRT_SCHEME_BF: return launch_sens_jac_closed<SG77<true>>(a, la, ja, s, probe);
+    case CRT_SCHEME_2S: return launch_sens_jac_closed<S2s>(a, la, ja, s, probe, sr, dg_at_psi);
+    case CRT_SCHEME_BL: return launch_sens_jac_closed<SBl, true>(a, la, ja, s, probe, sr, dg_at_psi);
+    case CRT_SCHEME_G77: return launch_sens_jac_closed<SG77<false>>(a, la, ja, s, probe, sr, dg_at_psi);
+    case CRT_SCHEME_BF: return launch_sens_jac_closed<SG77<true>>(a, la, ja, s, probe, sr, dg_at_psi);
     default: return CRT_ERR_UNSUPPORTED;
   }
 }

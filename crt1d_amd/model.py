@@ -418,6 +418,32 @@ class Model:
         res["params"] = plan.params
         return res
 
+    def run_series_sensor_jacobian(self, psi, weights, levels=(0, -1), directions=None, lai=True, wrt_leaf=None, I_dr0_all=None,
+                                   I_df0_all=None):
+        """The Jacobian of what :meth:`run_series_sensors` returns with respect to ONE parameter vector of this case, for every sun state
+        in one device call (:class:`crt1d_amd.batched.SensorJacSeriesPlan`, ``ncol = 1``).  ``psi``, ``I_dr0_all``, ``I_df0_all`` as for
+        :meth:`run_series_sensors`; ``weights``, ``levels``, ``directions``, ``lai``, ``wrt_leaf`` as for :meth:`run_sensor_jacobian`.
+        Returns ``{"I_dr", "I_df_d", "I_df_u", "F"}`` as NumPy arrays ``(nt, nsel, nsens, npar)`` and ``"params"``.  ValueError for ``4s``
+        and ``zq_pa``.  The model's own state is not changed."""
+        from . import batched
+
+        scheme, cols, b, sun = self._series_inputs(psi, I_dr0_all, I_df0_all, "sensor Jacobian")
+        if scheme not in batched.SensorJacSeriesPlan._schemes:
+            raise ValueError(batched.SensorJacSeriesPlan._no_kernel.format(scheme))
+        directions = {} if directions is None else dict(directions)
+        if any(k not in batched.JAC_PARAMS for k in directions):
+            raise ValueError(f"directions must be a dict of (ntan, n_wl) arrays under keys out of {batched.JAC_PARAMS}")
+        if wrt_leaf is not None and wrt_leaf not in batched.LEAF_WRT:
+            raise ValueError(f"wrt_leaf must be None or one of {batched.LEAF_WRT}, got {wrt_leaf!r}")
+        d = {"d_" + k: np.ascontiguousarray(v, dtype=np.float64) for k, v in directions.items()}
+        with batched.torch.cuda.device(cols.device):
+            plan = batched.SensorJacSeriesPlan(scheme, cols, b, sun, levels, self._sensor_set(weights, self.nwl), lai=lai,
+                                               tangent=None if wrt_leaf is None else batched.leaf_tangent_series(cols, sun, wrt_leaf), **d)
+            out = plan()
+        res = {k: v[0].cpu().numpy() for k, v in out.items()}
+        res["params"] = plan.params
+        return res
+
     # ---- output container -------------------------------------------------------------------
     def _scheme_absorption_vars(self, nz):
         """The scheme's own absorption outputs (``aI*_scheme``): on levels or on layers, by their leading size."""
