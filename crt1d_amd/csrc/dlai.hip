@@ -17,16 +17,16 @@
 //  k_dlai_tri   n79, zq: k_jac_tri's checkpoint-every-fourth-level sweep with the record entries as Du: the staged record part is in LDS
 //               twice (values | tangents of the side record), so the lanes narrow earlier (tri_cp_lanes with two copies).
 #include "col_record.hpp"
-#include "jac_schemes.hpp"
+#include "deriv_passes.hpp"
 #include "launch_forms.hpp"
 
 namespace crt {
 namespace {
 
-struct D2s : J2sT<double, Du> {};
-struct DBl : JBlT<double, Du> {};
+struct D2s : Sch2s::D {};
+struct DBl : SchBl::D {};
 template <bool BF>
-struct DG77 : JG77T<BF, double, Du> {};
+struct DG77 : SchG77<BF>::D {};
 struct DN79 : JN79T<double, Du> {};
 struct DZq : JZqT<double, Du> {};
 
@@ -113,30 +113,12 @@ __global__ __launch_bounds__(DLAI_BLOCK) void k_dlai(SolveArgs a, LevArgs la, Dl
   const int c = blockIdx.x, nz = a.nz, nb = a.nb, nsel = la.nsel, tid = threadIdx.x;
   const int b = blockIdx.y * per + tid;
   const bool live = tid < per && b < nb;
-  const double* rec = a.ws + (long long)c * a.reclen;
-  if (tid < REC_HDR) hd[tid] = rec[tid];
-  if (tid == REC_HDR) hd[REC_HDR] = rec[REC_HDR + nz];  // e^{-K_b L} at the ground
-  for (int r = tid; r < nsel; r += blockDim.x) {
-    const int j = la.lev[r];
-    lvL[r] = rec[REC_HDR + j];
-    lvE[r] = rec[REC_HDR + nz + j];
-    if constexpr (BL) lvT[r] = da.side[(long long)c * nz + j];  // L_j tau_d'(L_j)
-  }
-  __syncthreads();
+  stage_record<false, BL>(a.ws + (long long)c * a.reclen, nz, la, BL ? da.side + (long long)c * nz : nullptr, hd, lvL, lvE, lvT);
   if (!live) return;
-  const double K = hd[S_KB], invmu = hd[S_INVMU];
-  const DBand in = load_dband(a, c, b, S::SOIL);
-  S st;
-  st.init(hd, in, Du{hd[REC_HDR], -(K * hd[S_LT]) * hd[REC_HDR]});
+  const double invmu = hd[S_INVMU];
   const long long o0 = (long long)c * nsel * nb + b;  // row r: + r nb
-  for (int r = 0; r < nsel; ++r) {
-    const double L = lvL[r];
-    const Du eK = Du{lvE[r], -(K * L) * lvE[r]};
-    Du dn, up;
-    st.level(Du{L, L}, eK, dn, up);
-    if constexpr (BL) dn.d += in.I_df0 * lvT[r];  // the sky term I_df0 tau_d(L_j)
-    dlai_store(da, o0 + (long long)r * nb, in.I_dr0 * eK.d, invmu, dn, up);
-  }
+  pass_record<S, BL, false>(hd, lvL, lvE, lvT, nsel, load_dband(a, c, b, S::SOIL),
+                            [&](int r, double dI, Du dn, Du up) { dlai_store(da, o0 + (long long)r * nb, dI, invmu, dn, up); });
 }
 
 // LDS: the first nrec doubles of the record | their tangents (side record) | the states of every JAC_TRI_CP-th level [ncp][4][W]

@@ -20,16 +20,16 @@
 //  k_g_dparam    dG / d g_param of the parametric kinds at the nodes and at the sun angle (a series: at every sun angle of the column)
 //  k_dtau_d_dleaf  tau_d^th for arbitrary L.
 #include "col_record.hpp"
-#include "jac_schemes.hpp"
+#include "deriv_passes.hpp"
 #include "launch_forms.hpp"
 
 namespace crt {
 namespace {
 
-struct F2s : J2sT<double, Du, Du> {};
-struct FBl : JBlT<double, Du, Du> {};
+struct F2s : Sch2s::F {};
+struct FBl : SchBl::F {};
 template <bool BF>
-struct FG77 : JG77T<BF, double, Du, Du> {};
+struct FG77 : SchG77<BF>::F {};
 
 // tau_d^th on the rules of tau_d_quad / tau_d_9sky (colpre.hip): the integrand factor e^{-K L} becomes -K' L e^{-K L}
 __device__ inline double dtau_leaf_quad(const double* kq, const double* dkq, double L) {
@@ -236,34 +236,12 @@ __global__ __launch_bounds__(DLEAF_BLOCK) void k_dleaf(SolveArgs a, LevArgs la, 
   const int c = blockIdx.x, nz = a.nz, nb = a.nb, nsel = la.nsel, tid = threadIdx.x;
   const int b = blockIdx.y * per + tid;
   const bool live = tid < per && b < nb;
-  const double* rec = a.ws + (long long)c * a.reclen;
-  const double* sd = da.side + (long long)c * (REC_HDR + (BL ? nz : 0));
-  if (tid < REC_HDR) {
-    hd[tid] = rec[tid];
-    hd[HDR_TAN + tid] = sd[tid];
-  }
-  if (tid == REC_HDR) hd[REC_HDR] = rec[REC_HDR + nz];  // e^{-K_b L} at the ground
-  for (int r = tid; r < nsel; r += blockDim.x) {
-    const int j = la.lev[r];
-    lvL[r] = rec[REC_HDR + j];
-    lvE[r] = rec[REC_HDR + nz + j];
-    if constexpr (BL) lvT[r] = sd[REC_HDR + j];  // tau_d^th(L_j)
-  }
-  __syncthreads();
+  stage_record<true, BL>(a.ws + (long long)c * a.reclen, nz, la, da.side + (long long)c * (REC_HDR + (BL ? nz : 0)), hd, lvL, lvE, lvT);
   if (!live) return;
-  const double dK = hd[HDR_TAN + S_KB], invmu = hd[S_INVMU];
-  const DBand in = load_dband(a, c, b, S::SOIL);
-  S st;
-  st.init(hd, in, Du{hd[REC_HDR], -(dK * hd[S_LT]) * hd[REC_HDR]});
+  const double invmu = hd[S_INVMU];
   const long long o0 = (long long)c * nsel * nb + b;  // row r: + r nb
-  for (int r = 0; r < nsel; ++r) {
-    const double L = lvL[r];
-    const Du eK = Du{lvE[r], -(dK * L) * lvE[r]};
-    Du dn, up;
-    st.level(L, eK, dn, up);
-    if constexpr (BL) dn.d += in.I_df0 * lvT[r];  // the sky term I_df0 tau_d(L_j)
-    dlai_store(da, o0 + (long long)r * nb, in.I_dr0 * eK.d, invmu, dn, up);
-  }
+  pass_record<S, BL, true>(hd, lvL, lvE, lvT, nsel, load_dband(a, c, b, S::SOIL),
+                           [&](int r, double dI, Du dn, Du up) { dlai_store(da, o0 + (long long)r * nb, dI, invmu, dn, up); });
 }
 
 template <class S, bool BL = false>

@@ -7,44 +7,26 @@
 //  k_grad         k_jac's mapping without the parameter axis: lane <-> band, a workgroup owns one column and one band slice; the header
 //                 with its leaf-angle tangents and the selected record entries are staged in LDS once.  A lane loads its band once and runs
 //                 the passes one after the other, ONE tangent at a time (jac.hip: three at once would triple the ~40 live doubles of the 2s
-//                 constants), each with the jac_schemes.hpp instantiation of the kernel it replaces -- the same operations on the same
-//                 inputs, so the same tangent bits (-ffp-contract=off):
-//                   p = 0, 1, 2   <P = Du, R = double>           seed 1 in leaf_r, leaf_t, soil_r      (k_jac)
-//                   LAI           <P = double, R = Du>           L_j' = L_j, LT' = LT                  (k_dlai; bl: + I_df0 L_j tau_d'(L_j))
-//                   leaf angle    <P = double, R = Du, H = Du>   the header tangents of k_dleaf_side   (k_dleaf; bl: + I_df0 tau_d^th(L_j))
+//                 constants), each the pass of deriv_passes.hpp that the kernel it replaces calls -- one piece of code, so the same
+//                 tangent bits (-ffp-contract=off):
+//                   p = 0, 1, 2   pass_optics<Sch::J>        seed 1 in leaf_r, leaf_t, soil_r      (k_jac)
+//                   LAI           pass_record<Sch::D>        L_j' = L_j, LT' = LT                  (k_dlai; bl: + I_df0 L_j tau_d'(L_j))
+//                   leaf angle    pass_record<Sch::F, LEAF>  the header tangents of k_dleaf_side   (k_dleaf; bl: + I_df0 tau_d^th(L_j))
 //                 A pass whose output is NULL is skipped.  Within a pass the lane adds w.X * X' in the order (level, quantity), quantities
 //                 whose weight is NULL left out.  Optics: a plain store of consecutive bands.  LAI, leaf angle: the lanes' sums are added
 //                 over the wave by a butterfly (every lane ends with the same bits), over the waves in ascending order by thread 0.
 //  k_grad_finish  several band slices: a thread per column adds the slice sums in ascending order.
 // No atomics anywhere: a column's result does not depend on the batch, and an output's bits do not depend on which others are asked for.
-#include "jac_schemes.hpp"
+#include "deriv_passes.hpp"
 #include "launch_forms.hpp"
 
 namespace crt {
 namespace {
 
-// optics pass | LAI pass | leaf-angle pass: the instantiations of jac.hip, dlai.hip, dleaf.hip
-struct G2s {
-  using J = J2sT<Du, double>;
-  using D = J2sT<double, Du>;
-  using F = J2sT<double, Du, Du>;
-};
-struct GBl {
-  using J = JBlT<Du, double>;
-  using D = JBlT<double, Du>;
-  using F = JBlT<double, Du, Du>;
-};
+struct G2s : Sch2s {};
+struct GBl : SchBl {};
 template <bool BF>
-struct GG77 {
-  using J = JG77T<BF, Du, double>;
-  using D = JG77T<BF, double, Du>;
-  using F = JG77T<BF, double, Du, Du>;
-};
-
-// the band of load_dband with parameter p seeded (uniform)
-__device__ __forceinline__ JBandT<Du> seed_band(const DBand& in, int p) {
-  return JBandT<Du>{in.I_dr0, in.I_df0, Du{in.r, p == 0 ? 1.0 : 0.0}, Du{in.t, p == 1 ? 1.0 : 0.0}, Du{in.s, p == 2 ? 1.0 : 0.0}};
-}
+struct GG77 : SchG77<BF> {};
 
 // acc += sum_X w.X[o] X' for the tangents of one row: dI = I_dr', dn = I_df_d', up = I_df_u', dF = F'.  UP: the scheme has an upward stream
 // (bl: w.I_df_u is not read)
@@ -78,6 +60,7 @@ __global__ __launch_bounds__(GRAD_BLOCK) void k_grad(SolveArgs a, LevArgs la, Gr
   const int c = blockIdx.x, nz = a.nz, nb = a.nb, nsel = la.nsel, tid = threadIdx.x;
   const int b = blockIdx.y * per + tid;
   const bool live = tid < per && b < nb;
+  // its own staging, the tangents of both record derivatives at once: through a shared function k_grad<bl> took 8 more SGPRs
   const double* rec = a.ws + (long long)c * a.reclen;
   const double* sdl = ga.side_leaf + (long long)c * (REC_HDR + (BL ? nz : 0));
   if (tid < REC_HDR) {
@@ -105,15 +88,10 @@ __global__ __launch_bounds__(GRAD_BLOCK) void k_grad(SolveArgs a, LevArgs la, Gr
     for (int p = 0; p < CRT_JAC_NPARAM; ++p) {
       if (!ga.o[p]) continue;
       double acc = 0.0;
-      if (SJ::SOIL || p != 2) {  // (bl has no soil: zeros)
-        SJ st;
-        st.init(hd, seed_band(in, p), hd[REC_HDR]);
-        for (int r = 0; r < nsel; ++r) {
-          Du dn, up;
-          st.level(lvL[r], lvE[r], dn, up);
+      if (SJ::SOIL || p != 2)  // (bl has no soil: zeros)
+        pass_optics<SJ>(hd, lvL, lvE, nsel, seed_band(in, p), [&](int r, Du dn, Du up) {
           grad_add<SJ::SOIL>(acc, ga, o0 + (long long)r * nb, false, 0.0, dn.d, up.d, 2 * (up.d + dn.d));  // F' as jac_store
-        }
-      }
+        });
       ga.o[p][(long long)c * nb + b] = acc;
     }
   }
@@ -123,20 +101,10 @@ __global__ __launch_bounds__(GRAD_BLOCK) void k_grad(SolveArgs a, LevArgs la, Gr
   // ---- the LAI (k_dlai) ----
   if (ga.lai) {
     double acc = 0.0;
-    if (live) {
-      const double K = hd[S_KB];
-      typename G::D st;
-      st.init(hd, in, Du{hd[REC_HDR], -(K * hd[S_LT]) * hd[REC_HDR]});
-      for (int r = 0; r < nsel; ++r) {
-        const double L = lvL[r];
-        const Du eK = Du{lvE[r], -(K * L) * lvE[r]};
-        Du dn, up;
-        st.level(Du{L, L}, eK, dn, up);
-        if constexpr (BL) dn.d += in.I_df0 * lvTs[r];  // the sky term I_df0 tau_d(L_j)
-        const double dI = in.I_dr0 * eK.d;
-        grad_add<SJ::SOIL>(acc, ga, o0 + (long long)r * nb, true, dI, dn.d, up.d, __builtin_fma(dI, invmu, 2 * (up.d + dn.d)));  // F' as dlai_store
-      }
-    }
+    if (live)
+      pass_record<typename G::D, BL, false>(hd, lvL, lvE, lvTs, nsel, in, [&](int r, double dI, Du dn, Du up) {
+        grad_add<SJ::SOIL>(acc, ga, o0 + (long long)r * nb, true, dI, dn.d, up.d, flux_tan(dI, invmu, dn, up));
+      });
     const double s = block_sum(acc, red);
     if (tid == 0) (dst ? dst[0] : ga.lai[c]) = s;
   }
@@ -144,20 +112,10 @@ __global__ __launch_bounds__(GRAD_BLOCK) void k_grad(SolveArgs a, LevArgs la, Gr
   // ---- the leaf angles (k_dleaf) ----
   if (ga.leaf) {
     double acc = 0.0;
-    if (live) {
-      const double dK = hd[HDR_TAN + S_KB];
-      typename G::F st;
-      st.init(hd, in, Du{hd[REC_HDR], -(dK * hd[S_LT]) * hd[REC_HDR]});
-      for (int r = 0; r < nsel; ++r) {
-        const double L = lvL[r];
-        const Du eK = Du{lvE[r], -(dK * L) * lvE[r]};
-        Du dn, up;
-        st.level(L, eK, dn, up);
-        if constexpr (BL) dn.d += in.I_df0 * lvTh[r];  // the sky term I_df0 tau_d(L_j)
-        const double dI = in.I_dr0 * eK.d;
-        grad_add<SJ::SOIL>(acc, ga, o0 + (long long)r * nb, true, dI, dn.d, up.d, __builtin_fma(dI, invmu, 2 * (up.d + dn.d)));
-      }
-    }
+    if (live)
+      pass_record<typename G::F, BL, true>(hd, lvL, lvE, lvTh, nsel, in, [&](int r, double dI, Du dn, Du up) {
+        grad_add<SJ::SOIL>(acc, ga, o0 + (long long)r * nb, true, dI, dn.d, up.d, flux_tan(dI, invmu, dn, up));
+      });
     const double s = block_sum(acc, red);
     if (tid == 0) (dst ? dst[1] : ga.leaf[c]) = s;
   }

@@ -16,7 +16,7 @@
 //             nz = 304 (n79) / 311 (zq), then 32 and 16 lanes per workgroup (tri_cp_lanes).  One wave per workgroup, every lane in its own LDS column: no
 //             barrier after the record is staged.  The reference's quirks are kept: n79's first downward row uses layer
 //             index 1, zq one dlai_mean for every layer.
-#include "jac_schemes.hpp"
+#include "deriv_passes.hpp"
 #include "launch_forms.hpp"
 
 namespace crt {
@@ -24,10 +24,10 @@ namespace {
 
 // the scheme objects of jac_schemes.hpp with the optics as Du and the column record as plain doubles
 using JBand = JBandT<Du>;
-struct J2s : J2sT<Du, double> {};
-struct JBl : JBlT<Du, double> {};
+struct J2s : Sch2s::J {};
+struct JBl : SchBl::J {};
 template <bool BF>
-struct JG77 : JG77T<BF, Du, double> {};
+struct JG77 : SchG77<BF>::J {};
 struct JN79 : JN79T<Du, double> {};
 
 // the spectra of one (column, band), the three parameters seeded for parameter p (uniform)
@@ -63,23 +63,10 @@ __global__ __launch_bounds__(JAC_BLOCK) void k_jac(SolveArgs a, LevArgs la, JacA
       for (int r = 0; r < nsel; ++r) jac_store(jo, o0 + (long long)r * CRT_JAC_NPARAM * nb, mk(0.0), mk(0.0));
     return;
   }
-  const double* rec = a.ws + (long long)c * a.reclen;
-  if (tid < REC_HDR) hd[tid] = rec[tid];
-  if (tid == REC_HDR) hd[REC_HDR] = rec[REC_HDR + nz];  // e^{-K_b L} at the ground
-  for (int r = tid; r < nsel; r += blockDim.x) {
-    const int j = la.lev[r];
-    lvL[r] = rec[REC_HDR + j];
-    lvE[r] = rec[REC_HDR + nz + j];
-  }
-  __syncthreads();
+  stage_record<false, false>(a.ws + (long long)c * a.reclen, nz, la, nullptr, hd, lvL, lvE, nullptr);
   if (!live) return;
-  S st;
-  st.init(hd, load_jband(a, c, b, p, S::SOIL), hd[REC_HDR]);
-  for (int r = 0; r < nsel; ++r) {
-    Du dn, up;
-    st.level(lvL[r], lvE[r], dn, up);
-    jac_store(jo, o0 + (long long)r * CRT_JAC_NPARAM * nb, dn, up);
-  }
+  pass_optics<S>(hd, lvL, lvE, nsel, load_jband(a, c, b, p, S::SOIL),
+                 [&](int r, Du dn, Du up) { jac_store(jo, o0 + (long long)r * CRT_JAC_NPARAM * nb, dn, up); });
 }
 
 // ------------------------------------------------------------------------------------------

@@ -484,12 +484,14 @@ __device__ __forceinline__ DBand load_dband(const SolveArgs& a, int c, int b, bo
   return in;
 }
 
-// dI = I_dr' of the row: I_dr0 (e^{-K_b L_j})'
+// F' of a row of the LAI or leaf-angle derivative: F = I_dr / mu + 2 (up + dn); dI = I_dr' of the row, I_dr0 (e^{-K_b L_j})'
+__device__ __forceinline__ double flux_tan(double dI, double invmu, Du dn, Du up) { return __builtin_fma(dI, invmu, 2 * (up.d + dn.d)); }
+
 __device__ __forceinline__ void dlai_store(const DlaiArgs& da, long long o, double dI, double invmu, Du dn, Du up) {
   if (da.o[0]) da.o[0][o] = dI;
   if (da.o[1]) da.o[1][o] = dn.d;
   if (da.o[2]) da.o[2][o] = up.d;
-  if (da.o[3]) da.o[3][o] = __builtin_fma(dI, invmu, 2 * (up.d + dn.d));  // F = I_dr / mu + 2 (up + dn)
+  if (da.o[3]) da.o[3][o] = flux_tan(dI, invmu, dn, up);
 }
 
 }  // namespace

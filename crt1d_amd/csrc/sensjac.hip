@@ -25,34 +25,16 @@
 //                     the series: ncol * nt "columns" v = c * nt + t.
 // No atomics anywhere: a column's result does not depend on the batch, and an output's bits do not depend on which others are asked for
 // (every quantity is staged and folded; a NULL output is only not written).
-#include "jac_schemes.hpp"
+#include "deriv_passes.hpp"
 #include "launch_forms.hpp"
 
 namespace crt {
 namespace {
 
-// optics pass | LAI pass | leaf-angle pass: the instantiations of jac.hip, dlai.hip, dleaf.hip (as grad.hip)
-struct S2s {
-  using J = J2sT<Du, double>;
-  using D = J2sT<double, Du>;
-  using F = J2sT<double, Du, Du>;
-};
-struct SBl {
-  using J = JBlT<Du, double>;
-  using D = JBlT<double, Du>;
-  using F = JBlT<double, Du, Du>;
-};
+struct S2s : Sch2s {};
+struct SBl : SchBl {};
 template <bool BF>
-struct SG77 {
-  using J = JG77T<BF, Du, double>;
-  using D = JG77T<BF, double, Du>;
-  using F = JG77T<BF, double, Du, Du>;
-};
-
-// the band of load_dband with parameter p seeded (uniform)
-__device__ __forceinline__ JBandT<Du> sj_seed_band(const DBand& in, int p) {
-  return JBandT<Du>{in.I_dr0, in.I_df0, Du{in.r, p == 0 ? 1.0 : 0.0}, Du{in.t, p == 1 ? 1.0 : 0.0}, Du{in.s, p == 2 ? 1.0 : 0.0}};
-}
+struct SG77 : SchG77<BF> {};
 
 // Where the body below finds the band-independent entries of its (column, sun state): the header scalar i, the LAI L_j and the beam
 // fraction e^{-K_b L_j} of level j (j = 0: the ground), and the tangent of header scalar i along the leaf-angle direction.
@@ -99,6 +81,7 @@ __device__ __forceinline__ void sens_jac_body(const SolveArgs& a, const LevArgs&
   const int b = slice * per + tid;
   const bool live = tid < per && b < nb;
   const int ntan = ja.ntan, npar = ntan + ja.lai + ja.leaf;
+  // (staging and pass loops are this body's own, not those of deriv_passes.hpp: DESIGN 3.20)
   const double* sdl = ja.side_leaf + (long long)c * (REC_HDR + (BL ? nz : 0));
   if (tid < REC_HDR) {
     hd[tid] = rc.hdr(tid);
@@ -131,7 +114,7 @@ __device__ __forceinline__ void sens_jac_body(const SolveArgs& a, const LevArgs&
 #pragma unroll
         for (int k = 0; k < CRT_SENSJAC_MAX_NTAN; ++k) d[k] = k < ntan ? dp[(long long)k * nb] : 0.0;
         SJ st;
-        st.init(hd, sj_seed_band(in, p), hd[REC_HDR]);
+        st.init(hd, seed_band(in, p), hd[REC_HDR]);
         for (int r = 0; r < nsel; ++r) {
           Du dn, up;
           st.level(lvL[r], lvE[r], dn, up);

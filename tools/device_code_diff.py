@@ -6,7 +6,16 @@
 
 Each code object is disassembled (llvm-objdump -d --no-show-raw-insn --no-leading-addr) and split by symbol; a unit passes when both
 sides have the same symbols with identical text.  The text of a kernel that addresses a global of its unit holds its distance to it, so
-the comparison also holds the kernels to their order in the code object.  Prints one line per unit and exits 1 on any difference."""
+the comparison also holds the kernels to their order in the code object.  Prints one line per unit and exits 1 on any difference.
+
+For a kernel that differs it then says how (directories only; the resources come from the .amdgpu_metadata of the unit's *.s):
+  "distances"   nothing but the literals of s_getpc_b64 / s_add_u32 pairs, the distances to globals of the unit
+  "reordered"   equal SGPRs, VGPRs, scratch and static LDS, an equal multiset of vector floating-point opcodes (v_*_f64, v_rcp*, v_exp*,
+                v_sqrt*, v_fma*), equal counts of ds_*, global_* and buffer_* instructions, instruction counts within 1 %: what remains
+                is instruction order, registers, scalar code and waits
+  "CHANGED"     anything else
+with the instruction count and (SGPRs, VGPRs, scratch, LDS) of both sides."""
+import collections
 import glob
 import os
 import re
@@ -30,10 +39,42 @@ def symbols(path):
     return out
 
 
-def compare(a, b):
+def resources(code_obj):
+    """kernel -> (SGPRs, VGPRs, scratch bytes, static LDS bytes), from the metadata of the assembly next to the code object"""
+    text = open(code_obj[:-len(".out")] + ".s").read()
+    out = {}
+    for entry in text.split("  - .agpr_count:")[1:]:
+        f = {k: v for k, v in re.findall(r"^    \.(\w+):\s+(\S+)$", entry, re.M)}
+        out[f["name"]] = tuple(int(f[k]) for k in ("sgpr_count", "vgpr_count", "private_segment_fixed_size", "group_segment_fixed_size"))
+    return out
+
+
+FP = re.compile(r"v_\w+_f64|v_rcp|v_exp|v_sqrt|v_fma")
+MEM = re.compile(r"(ds|global|buffer)_")
+
+
+def profile(lines):
+    ops = [ln.split()[0] for ln in lines if ln]
+    return len(ops), collections.Counter(o for o in ops if FP.match(o)), collections.Counter(MEM.match(o).group(1) for o in ops if MEM.match(o))
+
+
+def verdict(la, lb, ra, rb):
+    """how two texts of one kernel differ (module docstring)"""
+    if len(la) == len(lb) and all(x == y or (x.startswith("s_add_u32") and x.split()[:3] == y.split()[:3] and i and la[i - 1].startswith("s_getpc_b64"))
+                                  for i, (x, y) in enumerate(zip(la, lb))):
+        return "distances"
+    (na, fa, ma), (nb, fb, mb) = profile(la), profile(lb)
+    ok = ra == rb and fa == fb and ma == mb and abs(nb - na) <= 0.01 * na
+    return f"{'reordered' if ok else 'CHANGED'}  instructions {na} -> {nb}  (sgpr, vgpr, scratch, lds) {ra} -> {rb}"
+
+
+def compare(a, b, explain=False):
     sa, sb = symbols(a), symbols(b)
     only = sorted(set(sa) ^ set(sb))
     diff = sorted(k for k in set(sa) & set(sb) if sa[k] != sb[k])
+    if explain and diff:
+        ra, rb = resources(a), resources(b)
+        diff = [f"{k}  {verdict(sa[k], sb[k], ra.get(k), rb.get(k))}" for k in diff]
     return len(sa), only, diff
 
 
@@ -50,7 +91,7 @@ def main():
         for u in sorted(os.listdir(a)) if os.path.isdir(os.path.join(a, u))]
     bad = 0
     for unit, fa, fb in pairs:
-        n, only, diff = compare(fa, fb)
+        n, only, diff = compare(fa, fb, explain=bool(unit))
         print(f"{unit or os.path.basename(fa):24s} symbols {n:4d}  on one side only {len(only):3d}  differing {len(diff):3d}")
         for k in only + diff:
             print("   ", k)

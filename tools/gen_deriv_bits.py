@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Writes tests/golden/deriv_bits.json: the SHA-256 digests of the outputs of every case of tests/test_gpu_deriv_bits.py.
+"""Writes tests/golden/deriv_bits.json: the SHA-256 digests of the outputs of every case of tests/test_gpu_deriv_bits.py -- the three
+level-derivative entries and the three fused ones (gradient, sensor Jacobian, its sun-angle series).
 
 Run it on the GPU from a built checkout of the commit whose bits are to be pinned, with this file and tests/test_gpu_deriv_bits.py copied
 into that checkout (the package and the library next to this file are the ones used), never from the tree under test:
