@@ -423,6 +423,52 @@ def _sensjac_series_signatures():
 _SENSJAC_SERIES_SIGNATURES = _sensjac_series_signatures()
 SENSJAC_SERIES_EXPORTS = list(_SENSJAC_SERIES_SIGNATURES)
 
+# the per-column Levenberg-Marquardt retrieval on those Jacobians (include/crt1d_hip_retrieve.h), again a header and a table of their own
+RETRIEVE_MAX_NPAR = SENSJAC_MAX_NTAN + 2  # CRT_RETRIEVE_MAX_NPAR
+LM_MAX_BLOCKS = 4  # CRT_LM_MAX_BLOCKS
+LM_RUNNING, LM_CONVERGED_X, LM_CONVERGED_F, LM_STALLED, LM_FAILED_START = range(5)  # enum crt_lm_status
+
+
+class CrtRetrieveApply(ctypes.Structure):
+    """``crt_retrieve_apply``: the base inputs, the parameter vector and the working arrays ``k_retrieve_apply`` writes."""
+
+    _fields_ = ([(k, ctypes.c_int32) for k in ("ncol", "nz", "nb", "npar", "i_lai", "i_leaf")] + [("base_stride", ctypes.c_int64)]
+                + [(k, _vp) for k in ("leaf_r0", "leaf_t0", "soil_r0", "lai0", "p", "leaf_r", "leaf_t", "soil_r", "lai_scale", "lai", "g_param")])
+
+
+class CrtLmObs(ctypes.Structure):
+    """``crt_lm_obs``: one block of observations, ``f`` / ``y`` / ``inv_sigma`` ``[ncol][nrow]``, ``J`` ``[ncol][nrow][npar]``."""
+
+    _fields_ = [("nrow", ctypes.c_int32)] + [(k, _vp) for k in ("f", "J", "y", "inv_sigma")]
+
+
+class CrtLmProblem(ctypes.Structure):
+    """``crt_lm_problem``: the sizes, the options of the algorithm, the bounds ``[npar]`` and the prior ``[ncol][npar]``."""
+
+    _fields_ = ([("ncol", ctypes.c_int32), ("npar", ctypes.c_int32)]
+                + [(k, ctypes.c_double) for k in ("lam_up", "lam_down", "lam_min", "lam_max", "xtol", "ftol")]
+                + [(k, _vp) for k in ("lo", "hi", "prior", "inv_sigma_prior")])
+
+
+class CrtLmState(ctypes.Structure):
+    """``crt_lm_state``: the caller-owned per-column state of the Levenberg-Marquardt loop."""
+
+    _fields_ = [(k, _vp) for k in ("p", "p_trial", "cost", "lam", "A", "g", "status", "naccept", "nreject")]
+
+
+def _retrieve_signatures():
+    P = ctypes.POINTER
+    i32, ok = ctypes.c_int32, ctypes.c_int
+    return {
+        "crt_hip_retrieve_apply_f64": (ok, [P(CrtRetrieveApply), P(CrtOpticsDirs), _vp]),
+        "crt_hip_lm_step_f64": (ok, [P(CrtLmProblem), P(CrtLmObs), i32, P(CrtLmState), _vp]),
+        "crt_hip_lm_covariance_f64": (ok, [i32, i32, _vp, _vp, _vp]),
+    }
+
+
+_RETRIEVE_SIGNATURES = _retrieve_signatures()
+RETRIEVE_EXPORTS = list(_RETRIEVE_SIGNATURES)
+
 _lib = None
 
 
@@ -447,7 +493,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES, **_SENSOR_SIGNATURES, **_JAC_SIGNATURES,
                                       **_DLAI_SIGNATURES, **_DLEAF_SIGNATURES, **_GRAD_SIGNATURES, **_SENSJAC_SIGNATURES,
-                                      **_SENSJAC_SERIES_SIGNATURES}.items():
+                                      **_SENSJAC_SERIES_SIGNATURES, **_RETRIEVE_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:

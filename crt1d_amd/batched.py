@@ -2118,6 +2118,249 @@ def gauss_newton_step(J, r, *, damping=0.0):
     return x * sc
 
 
+# ---- the per-column Levenberg-Marquardt retrieval (include/crt1d_hip_retrieve.h) ---------------------------------------------------------
+
+LM_RUNNING, LM_CONVERGED_X, LM_CONVERGED_F = _lib.LM_RUNNING, _lib.LM_CONVERGED_X, _lib.LM_CONVERGED_F
+LM_STALLED, LM_FAILED_START = _lib.LM_STALLED, _lib.LM_FAILED_START
+RETRIEVE_SCHEMES = DLAI_SCHEMES  # 2s, bl, g77, bf on the kernels; n79 and zq through the composed SensorJacPlan
+LM_OPTIONS = dict(lam0=1e-2, lam_up=10.0, lam_down=0.1, lam_min=1e-12, lam_max=1e12, xtol=0.0, ftol=0.0)
+
+
+def _retrieve_static(scheme, sensors, y, keys, sun=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, leaf=False, lo=None,
+                     hi=None, inv_sigma=None, tau_d_method="quad", bands=None, **opts):
+    """The checks of a :class:`RetrievalPlan` that touch no device.  -> (keys, ntan, npar, LM options)"""
+    import numpy as np
+
+    _SolvePlan._check_options(_SolvePlan, scheme, tau_d_method)
+    if scheme not in RETRIEVE_SCHEMES:
+        raise ValueError(f"scheme {scheme!r} has no retrieval; served: " + ", ".join(RETRIEVE_SCHEMES))
+    keys = _level_keys(keys)
+    if not isinstance(sensors, SensorSet):
+        raise TypeError("sensors must be a SensorSet")
+    if sun is not None and (not isinstance(sun, SunSeries) or isinstance(sun, SunSeriesF32)):
+        raise TypeError("sun must be a SunSeries (float64 spectra)")
+    for name, d in (("y", y), ("inv_sigma", inv_sigma)):
+        if d is None and name == "inv_sigma":
+            continue
+        if not isinstance(d, dict):
+            raise TypeError(f"{name} must be a dict {{key: (ncol, [nt,] nsel, nsens)}}")
+        if extra := [k for k in d if k not in keys]:
+            raise ValueError(f"{name} has the keys {extra}, which are not in keys = {keys}")
+    if missing := [k for k in keys if k not in y]:
+        raise ValueError(f"y lacks the keys {missing} of keys = {keys}")
+    ntan = _sensjac_ntan(d_leaf_r, d_leaf_t, d_soil_r)
+    npar = ntan + bool(lai) + bool(leaf)
+    if npar == 0:
+        raise ValueError("no parameter at all: give a direction, lai=True or leaf=True")
+    for name, v in (("lo", lo), ("hi", hi)):
+        if v is not None and tuple(np.shape(v)) != (npar,):
+            raise ValueError(f"{name} must be (npar,) = ({npar},), got {tuple(np.shape(v))}")
+    if unknown := [k for k in opts if k not in LM_OPTIONS]:
+        raise TypeError(f"unknown options {unknown}; the Levenberg-Marquardt options are {tuple(LM_OPTIONS)}")
+    o = {k: float(opts.get(k, v)) for k, v in LM_OPTIONS.items()}
+    if not (o["lam0"] > 0 and o["lam_up"] > 1 and 0 < o["lam_down"] <= 1 and 0 <= o["lam_min"] <= o["lam_max"] and o["xtol"] >= 0 and o["ftol"] >= 0):
+        raise ValueError("the options need lam0 > 0, lam_up > 1, 0 < lam_down <= 1, 0 <= lam_min <= lam_max, xtol >= 0 and ftol >= 0")
+    if bands is not None and bands.dtype != torch.float64:
+        raise TypeError("the retrieval has no f32 storage form: bands must be float64")
+    return keys, ntan, npar, o
+
+
+class RetrievalPlan:
+    """A Levenberg-Marquardt retrieval of a parameter vector of every column from sensor-band observations, with the whole loop on the
+    device (include/crt1d_hip_retrieve.h): no host synchronisation between steps, no allocation after construction.
+
+    ``cols``, ``bands`` (with ``sun``: a :class:`SunSeries` that supplies the sun angles and the incoming spectra) are the base state;
+    ``y[k]`` are the observations of the sums :class:`SensorLevelsPlan` (``sun``: :class:`SensorLevelsSeriesPlan`) gives for ``keys``,
+    each ``(ncol, [nt,] nsel, nsens)``; ``inv_sigma[k]`` their weights (``None`` / a missing key: ones; an entry 0: not observed, its
+    ``y`` may be NaN).  The parameters, in the order of ``SensorJacPlan.params``: the coefficients of the ``ntan`` directions
+    ``d_leaf_r / d_leaf_t / d_soil_r`` added to the base spectra; ``"lai"`` (``lai=True``): the log of a scale of the base LAI profile;
+    ``"leaf"`` (``leaf=True``): the column's ``g_param`` itself (``wrt="param"`` of :func:`leaf_tangent`; ``mla`` stays fixed).  For the
+    parameterless leaf-angle kinds and ``G_TABLE`` columns ``dG`` is zero: the parameter is dead there and stays where it started.
+    ``p0 (ncol, npar)`` or ``(npar,)``: the starting point (default: zeros, and ``cols.g_param`` for ``"leaf"``); ``lo``, ``hi`` ``(npar,)``:
+    bounds, which also keep the optics physical -- nothing else clamps them; ``prior``, ``inv_sigma_prior`` ``(ncol, npar)`` or ``(npar,)``:
+    a Gaussian prior.  ``lam0`` and the options ``lam_up, lam_down, lam_min, lam_max, xtol, ftol`` are those of the header.
+
+    :meth:`step` is five launches in a row: ``k_retrieve_apply`` writes the working :class:`Columns` / :class:`Bands` from the trial
+    point; ``crt_hip_g_dparam_f64`` refills the leaf-angle tangent; the :class:`SensorJacPlan` (``sun``: :class:`SensorJacSeriesPlan`)
+    bound to the working tensors; the forward sums on its workspace with ``FLAG_SKIP_PRECOMPUTE``; ``k_lm_step``.  The first step
+    evaluates ``p0`` and is always accepted.  n79 and zq run the composed Jacobian plan (workspaces and allocations of its own) and the
+    forward plan with its own precompute; ``4s`` and ``zq_pa`` are a ValueError.  A column's state is bitwise the same alone or in any
+    batch.  float64 only."""
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, y, *, keys, sun=None, d_leaf_r=None, d_leaf_t=None,
+                 d_soil_r=None, lai=True, leaf=False, p0=None, lo=None, hi=None, inv_sigma=None, prior=None, inv_sigma_prior=None,
+                 mu_s=0.501, tau_d_method="quad", **options):
+        keys, ntan, npar, o = _retrieve_static(scheme, sensors, y, keys, sun, d_leaf_r, d_leaf_t, d_soil_r, lai, leaf, lo, hi, inv_sigma,
+                                               tau_d_method, bands, **options)
+        if (prior is None) != (inv_sigma_prior is None):
+            raise ValueError("prior and inv_sigma_prior go together")
+        self.lib = _lib.load()
+        self.scheme, self.keys, self.sun, self.options = scheme, keys, sun, o
+        ncol, nz, nb, dev = cols.ncol, cols.nz, bands.nb, cols.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        new = lambda *shape: torch.zeros(shape, **f64)  # noqa: E731
+        # the base state and the working inputs k_retrieve_apply overwrites
+        self.base_cols, self.base_bands = cols, bands
+        self._base_stride = bands.col_stride(ncol)
+        rows = lambda v: None if v is None else v.expand(ncol, -1).contiguous()  # noqa: E731
+        self.bands = Bands(rows(bands.I_dr0), rows(bands.I_df0), new(ncol, nb), new(ncol, nb), None if bands.soil_r is None else new(ncol, nb))
+        self.cols = Columns(cols.psi, cols.lai.clone(), cols.g_kind, cols.g_param.clone(), cols.mla, cols.g_at_psi, cols.g_table)
+        self.lai_scale = torch.ones((ncol,), **f64)
+        # the leaf-angle tangent, refilled in place every step
+        self.tangent = None
+        if leaf:
+            self.tangent = (LeafTangent(new(ncol, _lib.NQ), new(ncol)) if sun is None
+                            else LeafTangentSeries(new(ncol, _lib.NQ), new(ncol, sun.nt)))
+        d = dict(d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r, lai=bool(lai), tangent=self.tangent, keys=keys, mu_s=mu_s,
+                 tau_d_method=tau_d_method)
+        f = dict(keys=keys, mu_s=mu_s, tau_d_method=tau_d_method)
+        if sun is None:
+            self.jac = SensorJacPlan(scheme, self.cols, self.bands, levels, sensors, **d)
+            self.fwd = SensorLevelsPlan(scheme, self.cols, self.bands, levels, sensors, **f, workspace=getattr(self.jac, "workspace", None))
+        else:
+            self.jac = SensorJacSeriesPlan(scheme, self.cols, self.bands, sun, levels, sensors, **d)
+            self.fwd = SensorLevelsSeriesPlan(scheme, self.cols, self.bands, sun, levels, sensors, **f,
+                                              workspace=getattr(self.jac, "workspace", None))
+        self._fwd_flags = 0 if self.jac._composed else _lib.FLAG_SKIP_PRECOMPUTE
+        self.params, self.levels, self.npar, self.ntan = self.jac.params, self.jac.levels, npar, ntan
+        assert len(self.params) == npar
+        self._dirs = None
+        if ntan:
+            by_col = ncol != 1 and any(v.shape[0] != 1 for v in self.jac.dirs.values())
+            self._dirs = _lib.CrtOpticsDirs(ntan, ntan * nb if by_col else 0,
+                                            *[self.jac.dirs[n].data_ptr() if n in self.jac.dirs else None for n in JAC_PARAMS])
+        # observations, bounds, prior
+        shape = tuple(self.fwd.out[keys[0]].shape)
+        self.nrow = int(torch.Size(shape[1:]).numel())
+
+        def obs(v, name):
+            v = torch.as_tensor(v, dtype=torch.float64).to(dev).contiguous()
+            if tuple(v.shape) != shape:
+                raise ValueError(f"{name} must be {shape}, got {tuple(v.shape)}")
+            return v
+
+        self.y = {k: obs(y[k], f"y[{k!r}]") for k in keys}
+        self.inv_sigma = {k: obs(inv_sigma[k], f"inv_sigma[{k!r}]") for k in keys if inv_sigma is not None and k in inv_sigma}
+
+        def per_col(v, name, width=npar):
+            v = torch.as_tensor(v, dtype=torch.float64).to(dev)
+            if v.ndim == 1:
+                v = v[None]
+            if v.ndim != 2 or v.shape[1] != width or v.shape[0] not in (1, ncol):
+                raise ValueError(f"{name} must be (ncol, npar) or (npar,) with ncol = {ncol}, npar = {width}")
+            return v.expand(ncol, -1).contiguous()
+
+        self.lo = None if lo is None else torch.as_tensor(lo, dtype=torch.float64).to(dev).contiguous()
+        self.hi = None if hi is None else torch.as_tensor(hi, dtype=torch.float64).to(dev).contiguous()
+        self.prior = None if prior is None else per_col(prior, "prior")
+        self.inv_sigma_prior = None if prior is None else per_col(inv_sigma_prior, "inv_sigma_prior")
+        if p0 is None:
+            p0 = new(ncol, npar)
+            if leaf:
+                p0[:, npar - 1] = cols.g_param
+        self._p0 = per_col(p0, "p0").clone()
+        # the state
+        ntri = npar * (npar + 1) // 2
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.p, self.p_trial, self.cost, self.lam = new(ncol, npar), new(ncol, npar), new(ncol), new(ncol)
+        self.A, self.g = new(ncol, ntri), new(ncol, npar)
+        self.status, self.naccept, self.nreject = (torch.zeros((ncol,), **i32) for _ in range(3))
+        self.cov = new(ncol, npar, npar)
+        # the structs of the three entries
+        ptr = lambda v: None if v is None else v.data_ptr()  # noqa: E731
+        b, w, c = bands, self.bands, self.cols
+        self._ap = _lib.CrtRetrieveApply(ncol, nz, nb, npar, ntan if lai else -1, ntan + bool(lai) if leaf else -1, self._base_stride,
+                                         ptr(b.leaf_r), ptr(b.leaf_t), ptr(b.soil_r), ptr(cols.lai), ptr(self.p_trial), ptr(w.leaf_r),
+                                         ptr(w.leaf_t), ptr(w.soil_r), ptr(self.lai_scale), ptr(c.lai), ptr(c.g_param))
+        self._prob = _lib.CrtLmProblem(ncol, npar, o["lam_up"], o["lam_down"], o["lam_min"], o["lam_max"], o["xtol"], o["ftol"], ptr(self.lo),
+                                       ptr(self.hi), ptr(self.prior), ptr(self.inv_sigma_prior))
+        self._obs = (_lib.CrtLmObs * len(keys))(*[
+            _lib.CrtLmObs(self.nrow, ptr(self.fwd.out[k]), ptr(self.jac.out[k]), ptr(self.y[k]), ptr(self.inv_sigma.get(k))) for k in keys])
+        self._state = _lib.CrtLmState(*[ptr(v) for v in (self.p, self.p_trial, self.cost, self.lam, self.A, self.g, self.status, self.naccept,
+                                                          self.nreject)])
+        self._c = c.c_struct()
+        self._s = None if sun is None else sun.c_struct()
+        self.reset()
+
+    def reset(self, p0=None):
+        """Restart the state at ``p0`` (default: the plan's starting point): ``p = p_trial = p0``, ``cost = +inf``, ``lam = lam0``."""
+        if p0 is not None:
+            v = torch.as_tensor(p0, dtype=torch.float64).to(self.p.device)
+            self._p0.copy_(v.expand_as(self._p0))
+        self.p.copy_(self._p0)
+        self.p_trial.copy_(self._p0)
+        self.cost.fill_(float("inf"))
+        self.lam.fill_(self.options["lam0"])
+        for v in (self.A, self.g, self.status, self.naccept, self.nreject):
+            v.zero_()
+        return self
+
+    def step(self, stream=None):
+        """One iteration on ``stream`` (default: torch's current stream): apply, tangent, Jacobian, forward sums, ``k_lm_step``."""
+        dev = self.cols.device
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        h, lib, ref = s.cuda_stream, self.lib, ctypes.byref
+        with torch.cuda.device(dev):
+            _lib.check(lib.crt_hip_retrieve_apply_f64(ref(self._ap), None if self._dirs is None else ref(self._dirs), h),
+                       "crt_hip_retrieve_apply_f64")
+            t = self.tangent
+            if t is not None and self.sun is None:
+                _lib.check(lib.crt_hip_g_dparam_f64(ref(self._c), t.dg_table.data_ptr(), t.dg_at_psi.data_ptr(), h), "crt_hip_g_dparam_f64")
+            elif t is not None:
+                _lib.check(lib.crt_hip_g_dparam_series_f64(ref(self._c), ref(self._s), t.dg_table.data_ptr(), t.dg_at_psi.data_ptr(), h),
+                           "crt_hip_g_dparam_series_f64")
+            self.jac(s)
+            self.fwd(s, flags=self._fwd_flags)
+            _lib.check(lib.crt_hip_lm_step_f64(ref(self._prob), self._obs, len(self.keys), ref(self._state), h), "crt_hip_lm_step_f64")
+        return self
+
+    def run(self, niter, stream=None):
+        """``niter`` steps with no host synchronisation in between."""
+        for _ in range(int(niter)):
+            self.step(stream)
+        return self
+
+    def result(self):
+        """Copies of ``p``, ``cost``, ``status`` (``LM_*``), ``lam``, ``naccept``, ``nreject``, and ``params``, the names of the columns of ``p``."""
+        r = {k: getattr(self, k).clone() for k in ("p", "cost", "status", "lam", "naccept", "nreject")}
+        r["params"] = self.params
+        return r
+
+    def nobs(self):
+        """``(ncol,)``: the rows every column is observed in (``inv_sigma != 0``), the rows of the prior included."""
+        n = torch.zeros_like(self.cost)
+        for k in self.keys:
+            n += float(self.nrow) if k not in self.inv_sigma else (self.inv_sigma[k] != 0).reshape(n.shape[0], -1).sum(1)
+        if self.inv_sigma_prior is not None:
+            n += (self.inv_sigma_prior != 0).sum(1)
+        return n
+
+    def covariance(self, scale=False, stream=None):
+        """The posterior covariance ``(ncol, npar, npar)``: the inverse of the undamped normal matrix at the accepted point
+        (``crt_hip_lm_covariance_f64``); a dead parameter has variance ``+inf`` and zero covariances.  ``scale=True`` multiplies by the
+        reduced chi-square ``2 cost / (nobs - npar)`` (for observations without error estimates)."""
+        dev = self.cols.device
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.device(dev):
+            _lib.check(self.lib.crt_hip_lm_covariance_f64(self.p.shape[0], self.npar, self.A.data_ptr(), self.cov.data_ptr(), s.cuda_stream),
+                       "crt_hip_lm_covariance_f64")
+        if not scale:
+            return self.cov.clone()
+        with torch.cuda.stream(s):
+            return self.cov * (2.0 * self.cost / (self.nobs() - self.npar))[:, None, None]
+
+
+def retrieve(scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, y, *, keys, niter=20, **kw):
+    """One-shot :class:`RetrievalPlan`: ``niter`` steps from ``p0``; what ``plan.result()`` returns, and ``"cov"``, ``plan.covariance()``."""
+    static = {k: v for k, v in kw.items() if k not in ("p0", "prior", "inv_sigma_prior", "mu_s")}
+    _retrieve_static(scheme, sensors, y, keys, bands=bands, **static)  # (before any device is touched)
+    with torch.cuda.device(cols.device):
+        plan = RetrievalPlan(scheme, cols, bands, levels, sensors, y, keys=keys, **kw).run(niter)
+        res = plan.result()
+        res["cov"] = plan.covariance()
+    return res
+
+
 class _LevelsAD(torch.autograd.Function):
     """``solve_levels`` with a backward pass: one :class:`LevelsGradPlan` call on the incoming ``d loss / d X``."""
 

@@ -444,6 +444,41 @@ class Model:
         res["params"] = plan.params
         return res
 
+    def retrieve(self, weights, y, levels=(0, -1), directions=None, lai=True, wrt_leaf=None, psi=None, niter=20, **lm_options):
+        """A Levenberg-Marquardt retrieval of a parameter vector of this case from sensor-band observations
+        (:class:`crt1d_amd.batched.RetrievalPlan`, ``ncol = 1``).  ``y``: ``{key: (nsel, nsens)}`` for keys out of ``"I_dr", "I_df_d",
+        "I_df_u", "F"``, the observed values of what :meth:`run_sensors` returns; with ``psi`` (a series of sun angles) ``{key: (nt, nsel,
+        nsens)}``, what :meth:`run_series_sensors` returns.  ``weights``, ``levels``, ``directions``, ``lai`` as for
+        :meth:`run_sensor_jacobian`; ``wrt_leaf``: ``None`` or ``"param"`` (``g_param`` itself is retrieved).  ``lm_options``: ``p0``, ``lo``,
+        ``hi``, ``prior``, ``inv_sigma_prior`` (each ``(npar,)``), ``inv_sigma`` (as ``y``), ``I_dr0_all`` / ``I_df0_all`` (with ``psi``) and
+        the options of the plan.  Returns NumPy arrays ``p (npar,)``, ``cost``, ``status``, ``lam``, ``naccept``, ``nreject``,
+        ``cov (npar, npar)`` and ``"params"``.  ValueError for ``4s`` and ``zq_pa``.  The model's own state is not changed."""
+        from . import batched
+
+        series = psi is not None
+        spectra = [lm_options.pop(k, None) for k in ("I_dr0_all", "I_df0_all")]
+        one = np.atleast_1d(float(self._p["psi"]))
+        scheme, cols, b, sun = self._series_inputs(psi if series else one, *(spectra if series else (None, None)), "retrieval")
+        directions = {} if directions is None else dict(directions)
+        if any(k not in batched.JAC_PARAMS for k in directions):
+            raise ValueError(f"directions must be a dict of (ntan, n_wl) arrays under keys out of {batched.JAC_PARAMS}")
+        if wrt_leaf not in (None, "param"):
+            raise ValueError(f"wrt_leaf must be None or 'param', got {wrt_leaf!r}")
+        if not series:
+            cols = batched.Columns(psi=sun.psi[:, 0].contiguous(), lai=cols.lai, g_kind=cols.g_kind, g_param=cols.g_param, mla=cols.mla,
+                                   g_at_psi=None if sun.g_at_psi is None else sun.g_at_psi[:, 0].contiguous(), g_table=cols.g_table)
+            b = batched.Bands(sun.I_dr0[:, 0].contiguous(), sun.I_df0[:, 0].contiguous(), b.leaf_r, b.leaf_t, b.soil_r)
+        d = {"d_" + k: np.ascontiguousarray(v, dtype=np.float64) for k, v in directions.items()}
+        keys = tuple(k for k in batched.LEVEL_KEYS if k in y)
+        lead = lambda v: {k: np.asarray(a, dtype=np.float64)[None] for k, a in v.items()}  # noqa: E731
+        if lm_options.get("inv_sigma") is not None:
+            lm_options["inv_sigma"] = lead(lm_options["inv_sigma"])
+        res = batched.retrieve(scheme, cols, b, levels, self._sensor_set(weights, self.nwl), lead(y), keys=keys or tuple(y), niter=niter,
+                               sun=sun if series else None, lai=lai, leaf=wrt_leaf is not None, **d, **lm_options)
+        out = {k: v[0].cpu().numpy() for k, v in res.items() if k != "params"}
+        out["params"] = res["params"]
+        return out
+
     # ---- output container -------------------------------------------------------------------
     def _scheme_absorption_vars(self, nz):
         """The scheme's own absorption outputs (``aI*_scheme``): on levels or on layers, by their leading size."""
