@@ -469,6 +469,43 @@ def _retrieve_signatures():
 _RETRIEVE_SIGNATURES = _retrieve_signatures()
 RETRIEVE_EXPORTS = list(_RETRIEVE_SIGNATURES)
 
+# the retrieval from the level spectra themselves (include/crt1d_hip_specfit.h), again a header and a table of their own: the normal
+# equations of the per-band misfit in one kernel and the step that consumes such sums; the closed forms only
+
+
+class CrtSpecObs(ctypes.Structure):
+    """``crt_spec_obs``: the observed level spectra and their weights, each ``[ncol][nsel][nb]`` on the device; a NULL ``y_*``: the key is
+    not observed, a NULL ``inv_sigma_*``: ones."""
+
+    _fields_ = [(p + k, _vp) for p in ("y_", "inv_sigma_") for k in ("I_dr", "I_df_d", "I_df_u", "F")]
+
+
+class CrtSpecNormalOut(ctypes.Structure):
+    """``crt_spec_normal_out``: ``A [ncol][npar (npar + 1) / 2]``, ``g [ncol][npar]``, ``c2 [ncol]`` and the optional model spectra."""
+
+    _fields_ = [(k, _vp) for k in ("A", "g", "c2", "fwd_I_dr", "fwd_I_df_d", "fwd_I_df_u", "fwd_F")]
+
+
+class CrtLmNormalBlock(ctypes.Structure):
+    """``crt_lm_normal_block``: the sums ``A``, ``g``, ``c2`` of one evaluation at the trial point."""
+
+    _fields_ = [(k, _vp) for k in ("A", "g", "c2")]
+
+
+def _specfit_signatures():
+    P = ctypes.POINTER
+    i, i32, sz, ok = ctypes.c_int, ctypes.c_int32, ctypes.c_size_t, ctypes.c_int
+    return {
+        "crt_hip_spectral_normal_workspace_bytes": (sz, [i, i32, i32, i32, i32, i32, i32]),
+        "crt_hip_spectral_normal_f64": (ok, [i, P(CrtColumns), P(CrtBands), P(CrtOptions), P(i32), i32, P(CrtOpticsDirs), i, P(CrtLeafTangent),
+                                             P(CrtSpecObs), P(CrtSpecNormalOut), _vp, sz, _vp]),
+        "crt_hip_lm_step_normal_f64": (ok, [P(CrtLmProblem), P(CrtLmNormalBlock), i32, P(CrtLmState), _vp]),
+    }
+
+
+_SPECFIT_SIGNATURES = _specfit_signatures()
+SPECFIT_EXPORTS = list(_SPECFIT_SIGNATURES)
+
 _lib = None
 
 
@@ -493,7 +530,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES, **_SENSOR_SIGNATURES, **_JAC_SIGNATURES,
                                       **_DLAI_SIGNATURES, **_DLEAF_SIGNATURES, **_GRAD_SIGNATURES, **_SENSJAC_SIGNATURES,
-                                      **_SENSJAC_SERIES_SIGNATURES, **_RETRIEVE_SIGNATURES}.items():
+                                      **_SENSJAC_SERIES_SIGNATURES, **_RETRIEVE_SIGNATURES, **_SPECFIT_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:

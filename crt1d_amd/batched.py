@@ -2361,6 +2361,297 @@ def retrieve(scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, y,
     return res
 
 
+# ---- the retrieval from the level spectra themselves (include/crt1d_hip_specfit.h) -------------------------------------------------------
+
+SPECTRAL_RETRIEVE_SCHEMES = ("2s", "bl", "g77", "bf")  # the schemes k_spec_normal serves; n79 and zq stay composable by hand
+SPECFIT_MAX_ROWS = 312  # nkey * nsel * (npar + 1) at most: the LDS limit of the header
+
+
+def spectral_normal_workspace_bytes(scheme, ncol, nz, nb, nsel, nkey, npar):
+    """Device workspace of a :class:`SpectralNormalPlan` call: the records of :func:`workspace_bytes` at the same offsets, the side
+    records of the LAI and of the leaf-angle derivative, and the slice sums."""
+    return int(_lib.load().crt_hip_spectral_normal_workspace_bytes(_lib.SCHEME_IDS[scheme], ncol, nz, nb, nsel, nkey, npar))
+
+
+def _spectral_static(scheme, y, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, leaf=False,
+                     tau_d_method="quad", bands=None):
+    """The checks of the spectral plans that touch no device.  -> (keys in ``LEVEL_KEYS`` order, ntan, npar)"""
+    import numpy as np
+
+    _SolvePlan._check_options(_SolvePlan, scheme, tau_d_method)
+    if scheme not in SPECTRAL_RETRIEVE_SCHEMES:
+        raise ValueError(f"scheme {scheme!r} has no spectral retrieval; served: " + ", ".join(SPECTRAL_RETRIEVE_SCHEMES))
+    keys = _level_keys(keys)
+    keys = tuple(k for k in LEVEL_KEYS if k in keys)
+    shapes = set()
+    for name, d in (("y", y), ("inv_sigma", inv_sigma)):
+        if d is None and name == "inv_sigma":
+            continue
+        if not isinstance(d, dict):
+            raise TypeError(f"{name} must be a dict {{key: (ncol, nsel, nb)}}")
+        if extra := [k for k in d if k not in keys]:
+            raise ValueError(f"{name} has the keys {extra}, which are not in keys = {keys}")
+        for k, v in d.items():
+            shape = tuple(v.shape) if hasattr(v, "shape") else np.shape(v)
+            if len(shape) != 3:
+                raise ValueError(f"{name}[{k!r}] must be (ncol, nsel, nb), got {shape}")
+            shapes.add(shape)
+    if missing := [k for k in keys if k not in y]:
+        raise ValueError(f"y lacks the keys {missing} of keys = {keys}")
+    if len(shapes) > 1:
+        raise ValueError(f"the arrays of y and inv_sigma must share one shape (ncol, nsel, nb), got {sorted(shapes)}")
+    ntan = _sensjac_ntan(d_leaf_r, d_leaf_t, d_soil_r)
+    npar = ntan + bool(lai) + bool(leaf)
+    if npar == 0:
+        raise ValueError("no parameter at all: give a direction, lai=True or a leaf-angle tangent")
+    if bands is not None and bands.dtype != torch.float64:
+        raise TypeError("the spectral retrieval has no f32 storage form: bands must be float64")
+    return keys, ntan, npar
+
+
+def _spectral_shapes(cols, bands, levels, y, inv_sigma, nkey, npar):
+    """The shapes of the observations against ``(ncol, nsel, nb)`` and the LDS limit; still no device.  -> the normalized levels"""
+    levels = normalize_levels(levels, cols.nz)
+    shape = (cols.ncol, len(levels), bands.nb)
+    for name, d in (("y", y), ("inv_sigma", inv_sigma or {})):
+        for k, v in d.items():
+            if tuple(v.shape) != shape:
+                raise ValueError(f"{name}[{k!r}] must be {shape}, got {tuple(v.shape)}")
+    if nkey * len(levels) * (npar + 1) > SPECFIT_MAX_ROWS:
+        raise ValueError(f"nkey * nsel * (npar + 1) = {nkey * len(levels) * (npar + 1)} exceeds {SPECFIT_MAX_ROWS}: select fewer levels or keys")
+    return levels
+
+
+class SpectralNormalPlan(_LevelsDerivPlan):
+    """Pre-validated normal equations of the per-band misfit of the level spectra (``crt_hip_spectral_normal_f64``): with ``X`` the
+    spectra of ``keys`` at ``levels``, ``r = (X - y) * inv_sigma`` and ``J`` their Jacobian with respect to the parameters of
+    :class:`SensorJacPlan` (``d_leaf_r / d_leaf_t / d_soil_r``, ``lai``, ``tangent``; ``params`` names them), one column precompute and
+    ONE kernel give ``out["A"] (ncol, npar (npar + 1) / 2)`` -- the lower triangle of ``J^T W J`` row by row --, ``out["g"] (ncol, npar)``
+    ``= J^T W r`` and ``out["c2"] (ncol,)`` ``= sum r^2``.  Neither ``J`` nor a derivative array is written.  ``y[k]``, ``inv_sigma[k]``:
+    ``(ncol, nsel, nb)`` (``inv_sigma`` ``None`` / a missing key: ones; an entry 0: the row is skipped, its ``y`` may be NaN); tensors on
+    the columns' device are read where they lie at every call.  ``fwd=True`` also keeps ``out["fwd"][k] (ncol, nsel, nb)``, the model
+    spectrum, written while ``plan.write_fwd`` is true.  A column's result is bitwise the same alone or in any batch and does not
+    depend on another column's ``inv_sigma``; ``c2`` and ``fwd`` do not depend on which parameters exist.  ``SPECTRAL_RETRIEVE_SCHEMES``
+    only; ``nkey * nsel * (npar + 1) <= SPECFIT_MAX_ROWS``."""
+
+    _entry_name, _ws_query = "crt_hip_spectral_normal_f64", "crt_hip_spectral_normal_workspace_bytes"
+    _all_keys, _schemes, _what = LEVEL_KEYS, SPECTRAL_RETRIEVE_SCHEMES, "spectral retrieval"
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None,
+                 lai=True, tangent=None, fwd=False, mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
+        if tangent is not None and not isinstance(tangent, LeafTangent):
+            raise TypeError("tangent must be a LeafTangent")
+        keys, ntan, npar = _spectral_static(scheme, y, keys, inv_sigma, d_leaf_r, d_leaf_t, d_soil_r, lai, tangent is not None, tau_d_method,
+                                            bands)
+        self.levels, self.keys = _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), npar), keys
+        ncol, nsel, nb, dev = cols.ncol, len(self.levels), bands.nb, cols.device
+        shape = (ncol, nsel, nb)
+        self._bind(scheme, cols, bands, mu_s, tau_d_method)
+        obs = lambda v: torch.as_tensor(v, dtype=torch.float64).to(dev).contiguous()  # noqa: E731
+        self.y = {k: obs(y[k]) for k in keys}
+        self.inv_sigma = {k: obs(inv_sigma[k]) for k in keys if inv_sigma is not None and k in inv_sigma}
+        dirs = {n: _jvp_direction(d, "d_" + n, ncol, nb, dev) for n, d in zip(JAC_PARAMS, (d_leaf_r, d_leaf_t, d_soil_r)) if d is not None}
+        per_col = any(d.shape[0] != 1 for d in dirs.values()) and ncol != 1
+        self.dirs = {n: (d.expand(ncol, -1, -1) if per_col else d).contiguous() for n, d in dirs.items()}
+        if tangent is not None and (tangent.dg_table.shape[0] != ncol or tangent.dg_table.device != dev):
+            raise ValueError("the tangent must have the columns' ncol and device")
+        self.tangent, self.ntan, self.npar = tangent, ntan, npar
+        self.params = tuple(f"dir{k}" for k in range(ntan)) + (("lai",) if lai else ()) + (("leaf",) if tangent is not None else ())
+        ntri = npar * (npar + 1) // 2
+        o = _outputs({"A": (ncol, ntri), "g": (ncol, npar), "c2": (ncol,)}, out, torch.float64, dev, "output {!r}", lacks=True)
+        self.out = {k: o[k] for k in ("A", "g", "c2")}
+        self.write_fwd = bool(fwd)
+        if fwd:
+            self.out["fwd"] = {k: torch.empty(shape, dtype=torch.float64, device=dev) for k in keys}
+        ptr = lambda d, k: d[k].data_ptr() if k in d else None  # noqa: E731
+        self._obs = _lib.CrtSpecObs(*[ptr(self.y, k) for k in LEVEL_KEYS], *[ptr(self.inv_sigma, k) for k in LEVEL_KEYS])
+        sums = [self.out[k].data_ptr() for k in ("A", "g", "c2")]
+        self._out_sums = _lib.CrtSpecNormalOut(*sums, None, None, None, None)
+        self._out_fwd = _lib.CrtSpecNormalOut(*sums, *[ptr(self.out.get("fwd", {}), k) for k in LEVEL_KEYS])
+        self._lev = (ctypes.c_int32 * nsel)(*self.levels)
+        self._dirs = None
+        if ntan:
+            self._dirs = _lib.CrtOpticsDirs(ntan, ntan * nb if per_col else 0,
+                                            *[self.dirs[n].data_ptr() if n in self.dirs else None for n in JAC_PARAMS])
+        self._tan = None if tangent is None else tangent.c_struct()
+        need = spectral_normal_workspace_bytes(scheme, ncol, cols.nz, nb, nsel, len(keys), npar)
+        self._finish(self._entry_name, need, workspace)
+
+    def _tail(self):
+        ref = lambda x: None if x is None else ctypes.byref(x)  # noqa: E731
+        return (self._lev, len(self.levels), ref(self._dirs), int("lai" in self.params), ref(self._tan), ctypes.byref(self._obs),
+                ctypes.byref(self._out_fwd if self.write_fwd else self._out_sums))
+
+    def dense(self):
+        """``out["A"]`` as the full symmetric matrices ``(ncol, npar, npar)`` (a new tensor)."""
+        n = self.npar
+        i, j = torch.tril_indices(n, n, device=self.out["A"].device)
+        A = self.out["A"].new_zeros((self.out["A"].shape[0], n, n))
+        A[:, i, j] = self.out["A"]
+        A[:, j, i] = self.out["A"]
+        return A
+
+
+def spectral_normal(scheme, cols: Columns, bands: Bands, levels, y, *, keys, **kw):
+    """One-shot :class:`SpectralNormalPlan`: ``{"A", "g", "c2"}`` (and ``"fwd"`` with ``fwd=True``) at the sorted levels."""
+    k, _, npar = _spectral_static(scheme, y, keys, kw.get("inv_sigma"), kw.get("d_leaf_r"), kw.get("d_leaf_t"), kw.get("d_soil_r"),
+                                  kw.get("lai", True), kw.get("tangent") is not None, kw.get("tau_d_method", "quad"), bands)
+    _spectral_shapes(cols, bands, levels, y, kw.get("inv_sigma"), len(k), npar)  # (all before any device is touched)
+    with torch.cuda.device(cols.device):
+        return SpectralNormalPlan(scheme, cols, bands, levels, y, keys=keys, **kw)()
+
+
+def _lm_options(lo, hi, npar, opts):
+    """The bounds and Levenberg-Marquardt options of a retrieval plan, checked without a device.  -> LM options"""
+    import numpy as np
+
+    for name, v in (("lo", lo), ("hi", hi)):
+        if v is not None and tuple(np.shape(v)) != (npar,):
+            raise ValueError(f"{name} must be (npar,) = ({npar},), got {tuple(np.shape(v))}")
+    if unknown := [k for k in opts if k not in LM_OPTIONS]:
+        raise TypeError(f"unknown options {unknown}; the Levenberg-Marquardt options are {tuple(LM_OPTIONS)}")
+    o = {k: float(opts.get(k, v)) for k, v in LM_OPTIONS.items()}
+    if not (o["lam0"] > 0 and o["lam_up"] > 1 and 0 < o["lam_down"] <= 1 and 0 <= o["lam_min"] <= o["lam_max"] and o["xtol"] >= 0 and o["ftol"] >= 0):
+        raise ValueError("the options need lam0 > 0, lam_up > 1, 0 < lam_down <= 1, 0 <= lam_min <= lam_max, xtol >= 0 and ftol >= 0")
+    return o
+
+
+class SpectralRetrievalPlan:
+    """:class:`RetrievalPlan` without the sensors: a Levenberg-Marquardt retrieval of a parameter vector of every column from the level
+    spectra themselves, band by band (include/crt1d_hip_specfit.h), with the whole loop on the device.  ``y[k] (ncol, nsel, nb)`` are
+    the observed spectra of ``keys`` at ``levels`` (what :class:`LevelsPlan` gives), ``inv_sigma[k]`` their weights (``None`` / a missing
+    key: ones; an entry 0: not observed -- a masked band --, its ``y`` may be NaN).  The parameters, ``p0``, ``lo``, ``hi``, ``prior``,
+    ``inv_sigma_prior`` and the options are those of :class:`RetrievalPlan`.
+
+    :meth:`step` is four launches in a row: ``k_retrieve_apply`` writes the working :class:`Columns` / :class:`Bands` from the trial
+    point; ``crt_hip_g_dparam_f64`` refills the leaf-angle tangent; the :class:`SpectralNormalPlan` bound to the working tensors forms
+    ``A``, ``g`` and ``c2``; ``crt_hip_lm_step_normal_f64`` decides.  Nothing the size of the spectrum is written, nothing is
+    allocated after construction and the host is never synchronised.  ``SPECTRAL_RETRIEVE_SCHEMES`` only; float64 only."""
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None,
+                 lai=True, leaf=False, p0=None, lo=None, hi=None, prior=None, inv_sigma_prior=None, mu_s=0.501, tau_d_method="quad",
+                 **options):
+        keys, ntan, npar = _spectral_static(scheme, y, keys, inv_sigma, d_leaf_r, d_leaf_t, d_soil_r, lai, leaf, tau_d_method, bands)
+        o = _lm_options(lo, hi, npar, options)
+        if (prior is None) != (inv_sigma_prior is None):
+            raise ValueError("prior and inv_sigma_prior go together")
+        _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), npar)
+        self.lib = _lib.load()
+        self.scheme, self.keys, self.options = scheme, keys, o
+        ncol, nz, nb, dev = cols.ncol, cols.nz, bands.nb, cols.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        new = lambda *shape: torch.zeros(shape, **f64)  # noqa: E731
+        # the base state and the working inputs k_retrieve_apply overwrites
+        self.base_cols, self.base_bands = cols, bands
+        self._base_stride = bands.col_stride(ncol)
+        rows = lambda v: None if v is None else v.expand(ncol, -1).contiguous()  # noqa: E731
+        self.bands = Bands(rows(bands.I_dr0), rows(bands.I_df0), new(ncol, nb), new(ncol, nb), None if bands.soil_r is None else new(ncol, nb))
+        self.cols = Columns(cols.psi, cols.lai.clone(), cols.g_kind, cols.g_param.clone(), cols.mla, cols.g_at_psi, cols.g_table)
+        self.lai_scale = torch.ones((ncol,), **f64)
+        self.tangent = LeafTangent(new(ncol, _lib.NQ), new(ncol)) if leaf else None  # refilled in place every step
+        self.normal = SpectralNormalPlan(scheme, self.cols, self.bands, levels, y, keys=keys, inv_sigma=inv_sigma, d_leaf_r=d_leaf_r,
+                                         d_leaf_t=d_leaf_t, d_soil_r=d_soil_r, lai=bool(lai), tangent=self.tangent, fwd=True, mu_s=mu_s,
+                                         tau_d_method=tau_d_method)
+        self.normal.write_fwd = False
+        self.params, self.levels, self.npar, self.ntan = self.normal.params, self.normal.levels, npar, ntan
+        self.y, self.inv_sigma = self.normal.y, self.normal.inv_sigma
+        self.nrow = len(self.levels) * nb
+        self._dirs = self.normal._dirs
+
+        def per_col(v, name, width=npar):
+            v = torch.as_tensor(v, dtype=torch.float64).to(dev)
+            if v.ndim == 1:
+                v = v[None]
+            if v.ndim != 2 or v.shape[1] != width or v.shape[0] not in (1, ncol):
+                raise ValueError(f"{name} must be (ncol, npar) or (npar,) with ncol = {ncol}, npar = {width}")
+            return v.expand(ncol, -1).contiguous()
+
+        self.lo = None if lo is None else torch.as_tensor(lo, dtype=torch.float64).to(dev).contiguous()
+        self.hi = None if hi is None else torch.as_tensor(hi, dtype=torch.float64).to(dev).contiguous()
+        self.prior = None if prior is None else per_col(prior, "prior")
+        self.inv_sigma_prior = None if prior is None else per_col(inv_sigma_prior, "inv_sigma_prior")
+        if p0 is None:
+            p0 = new(ncol, npar)
+            if leaf:
+                p0[:, npar - 1] = cols.g_param
+        self._p0 = per_col(p0, "p0").clone()
+        # the state
+        ntri = npar * (npar + 1) // 2
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.p, self.p_trial, self.cost, self.lam = new(ncol, npar), new(ncol, npar), new(ncol), new(ncol)
+        self.A, self.g = new(ncol, ntri), new(ncol, npar)
+        self.status, self.naccept, self.nreject = (torch.zeros((ncol,), **i32) for _ in range(3))
+        self.cov = new(ncol, npar, npar)
+        # the structs of the entries
+        ptr = lambda v: None if v is None else v.data_ptr()  # noqa: E731
+        b, w, c = bands, self.bands, self.cols
+        apply = lambda p: _lib.CrtRetrieveApply(ncol, nz, nb, npar, ntan if lai else -1, ntan + bool(lai) if leaf else -1,  # noqa: E731
+                                                self._base_stride, ptr(b.leaf_r), ptr(b.leaf_t), ptr(b.soil_r), ptr(cols.lai), ptr(p),
+                                                ptr(w.leaf_r), ptr(w.leaf_t), ptr(w.soil_r), ptr(self.lai_scale), ptr(c.lai), ptr(c.g_param))
+        self._ap, self._ap_p = apply(self.p_trial), apply(self.p)
+        self._prob = _lib.CrtLmProblem(ncol, npar, o["lam_up"], o["lam_down"], o["lam_min"], o["lam_max"], o["xtol"], o["ftol"], ptr(self.lo),
+                                       ptr(self.hi), ptr(self.prior), ptr(self.inv_sigma_prior))
+        self._blk = (_lib.CrtLmNormalBlock * 1)(_lib.CrtLmNormalBlock(*[self.normal.out[k].data_ptr() for k in ("A", "g", "c2")]))
+        self._state = _lib.CrtLmState(*[ptr(v) for v in (self.p, self.p_trial, self.cost, self.lam, self.A, self.g, self.status, self.naccept,
+                                                          self.nreject)])
+        self._c = c.c_struct()
+        self.reset()
+
+    reset = RetrievalPlan.reset
+    run = RetrievalPlan.run
+    result = RetrievalPlan.result
+    nobs = RetrievalPlan.nobs
+    covariance = RetrievalPlan.covariance
+
+    def _evaluate(self, ap, s):
+        """The working inputs from the parameters behind ``ap``, the tangent refill and the normal plan, on stream ``s``."""
+        lib, ref, h = self.lib, ctypes.byref, s.cuda_stream
+        _lib.check(lib.crt_hip_retrieve_apply_f64(ref(ap), None if self._dirs is None else ref(self._dirs), h), "crt_hip_retrieve_apply_f64")
+        t = self.tangent
+        if t is not None:
+            _lib.check(lib.crt_hip_g_dparam_f64(ref(self._c), t.dg_table.data_ptr(), t.dg_at_psi.data_ptr(), h), "crt_hip_g_dparam_f64")
+        self.normal(s)
+
+    def step(self, stream=None):
+        """One iteration on ``stream`` (default: torch's current stream): apply, tangent, normal equations, ``k_lm_step_normal``."""
+        dev = self.cols.device
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.device(dev):
+            self._evaluate(self._ap, s)
+            _lib.check(self.lib.crt_hip_lm_step_normal_f64(ctypes.byref(self._prob), self._blk, 1, ctypes.byref(self._state), s.cuda_stream),
+                       "crt_hip_lm_step_normal_f64")
+        return self
+
+    def fitted(self, stream=None):
+        """``{key: (ncol, nsel, nb)}``: the model spectra at the accepted point ``p``, by one more evaluation there (copies).  The working
+        inputs are left at ``p``; the next :meth:`step` applies its trial point again."""
+        dev = self.cols.device
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.device(dev):
+            self.normal.write_fwd = True
+            try:
+                self._evaluate(self._ap_p, s)
+            finally:
+                self.normal.write_fwd = False
+            with torch.cuda.stream(s):
+                return {k: v.clone() for k, v in self.normal.out["fwd"].items()}
+
+
+def retrieve_spectral(scheme, cols: Columns, bands: Bands, levels, y, *, keys, niter=20, **kw):
+    """One-shot :class:`SpectralRetrievalPlan`: ``niter`` steps from ``p0``; what ``plan.result()`` returns, and ``"cov"``,
+    ``plan.covariance()``."""
+    static = {k: kw[k] for k in ("inv_sigma", "d_leaf_r", "d_leaf_t", "d_soil_r", "lai", "leaf", "tau_d_method") if k in kw}
+    k, _, npar = _spectral_static(scheme, y, keys, bands=bands, **static)  # (before any device is touched)
+    _lm_options(kw.get("lo"), kw.get("hi"), npar, {n: v for n, v in kw.items() if n not in static and n not in
+                                                  ("p0", "lo", "hi", "prior", "inv_sigma_prior", "mu_s")})
+    _spectral_shapes(cols, bands, levels, y, kw.get("inv_sigma"), len(k), npar)
+    with torch.cuda.device(cols.device):
+        plan = SpectralRetrievalPlan(scheme, cols, bands, levels, y, keys=keys, **kw).run(niter)
+        res = plan.result()
+        res["cov"] = plan.covariance()
+    return res
+
+
 class _LevelsAD(torch.autograd.Function):
     """``solve_levels`` with a backward pass: one :class:`LevelsGradPlan` call on the incoming ``d loss / d X``."""
 

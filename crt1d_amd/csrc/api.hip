@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "epilogue.hpp"
+#include "specfit.hpp"
 
 namespace crt {
 namespace {
@@ -934,6 +935,73 @@ int crt_hip_sensor_jac_series_f64(int scheme, const crt_columns* cols, const crt
 int crt_hip_g_dparam_series_f64(const crt_columns* cols, const crt_sun_series* sun, double* dg_table, double* dg_at_psi, crt_stream_t stream) {
   if (!cols || !sun || !dg_table || !dg_at_psi || !sun->psi || sun->nt < 1 || !cols->g_kind || cols->ncol <= 0) return CRT_ERR_BAD_ARG;
   return crt::launch_g_dparam(cols->ncol, sun->psi, cols->g_kind, cols->g_param, dg_table, dg_at_psi, static_cast<hipStream_t>(stream), sun->nt);
+}
+
+// the normal equations of the per-band misfit (crt1d_hip_specfit.h): the workspace of the sensor Jacobian with the slice sums of k_spec_normal as
+// its tail
+size_t crt_hip_spectral_normal_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nsel, int32_t nkey, int32_t npar) {
+  if (nkey < 1 || nkey > 4 || npar < 1 || npar > CRT_RETRIEVE_MAX_NPAR) return 0;
+  const size_t rec = levels_deriv_workspace_bytes(grad_side_len, scheme, ncol, nz, nb, nsel);
+  return rec == 0 ? 0 : rec + spec_part_bytes(ncol, nb, nsel, nkey, npar);
+}
+
+int crt_hip_spectral_normal_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
+                                int32_t nsel, const crt_optics_dirs* dirs, int with_lai, const crt_leaf_tangent* tangent,
+                                const crt_spec_obs* obs, const crt_spec_normal_out* out, void* workspace, size_t workspace_bytes,
+                                crt_stream_t stream) {
+  SpecArgs sp = {};
+  const int ntan = dirs ? dirs->ntan : 0;
+  bool args_ok = obs && out && out->A && out->g && out->c2 && bands && bands->nb > 0 && ntan >= 0 && ntan <= CRT_SENSJAC_MAX_NTAN &&
+                 (ntan == 0 || dirs->leaf_r || dirs->leaf_t || dirs->soil_r) &&
+                 (ntan == 0 || dirs->col_stride == 0 || dirs->col_stride == (int64_t)ntan * bands->nb) &&
+                 (!tangent || (tangent->dg_table && tangent->dg_at_psi));
+  sp.ntan = ntan;
+  sp.lai = with_lai ? 1 : 0;
+  sp.leaf = tangent ? 1 : 0;
+  const int npar = ntan + sp.lai + sp.leaf;
+  args_ok = args_ok && npar >= 1;
+  if (args_ok) {
+    const double* const y[4] = {obs->y_I_dr, obs->y_I_df_d, obs->y_I_df_u, obs->y_F};
+    const double* const is[4] = {obs->inv_sigma_I_dr, obs->inv_sigma_I_df_d, obs->inv_sigma_I_df_u, obs->inv_sigma_F};
+    double* const fwd[4] = {out->fwd_I_dr, out->fwd_I_df_d, out->fwd_I_df_u, out->fwd_F};
+    for (int q = 0; q < 4; ++q) {
+      if (!y[q]) continue;  // (not observed: its inv_sigma and fwd are not looked at)
+      sp.y[q] = y[q];
+      sp.is[q] = is[q];
+      sp.fwd[q] = fwd[q];
+      ++sp.nkey;
+    }
+    args_ok = sp.nkey >= 1;
+    sp.A = out->A, sp.g = out->g, sp.c2 = out->c2;
+    if (ntan > 0) {
+      sp.d[0] = dirs->leaf_r;
+      sp.d[1] = dirs->leaf_t;
+      sp.d[2] = dirs->soil_r;
+      sp.dstride = dirs->col_stride;
+    }
+  }
+  // (sizes that are not positive are an argument error of the shared path: no tail then)
+  const bool sized = args_ok && cols && cols->ncol > 0 && cols->nz > 0;
+  const bool side_lai = sized && sp.lai && dlai_side_len(scheme, cols->nz) > 0, side_leaf = args_ok && sp.leaf;
+  const bool sel_ok = nsel >= 1 && nsel <= CRT_MAX_LEVEL_SELECT;
+  char pre[64];  // what a CRT_FLAG_PRECOMPUTE_ONLY call reports
+  std::snprintf(pre, sizeof pre, "k_colpre%s%s", side_lai ? " + k_dlai_side" : "", side_leaf ? " + k_dleaf_side" : "");
+  return levels_deriv_impl(
+      scheme, cols, bands, opts, levels, nsel, workspace, workspace_bytes, stream, args_ok, grad_side_len, pre,
+      [&](const SolveArgs& sa, const LevArgs& la, const double* side, hipStream_t s, bool probe) {
+        sp.side_lai = side;
+        sp.side_leaf = side + (size_t)sa.ncol * dlai_side_len(scheme, sa.nz);
+        sp.part = const_cast<double*>(side) + (size_t)sa.ncol * grad_side_len(scheme, sa.nz);
+        return launch_spec_normal(scheme, sa, la, sp, s, probe);
+      },
+      [&](const ColArgs& ca, double* side, hipStream_t s) {
+        if (side_lai)
+          if (const int st = launch_dlai_side(ca, side, s)) return st;
+        if (!side_leaf) return (int)CRT_OK;
+        return launch_dleaf_side(ca, DleafTan{tangent->dg_table, tangent->dg_at_psi, tangent->dmla}, side + (size_t)ca.ncol * dlai_side_len(scheme, ca.nz),
+                                 s);
+      },
+      true, sized && sel_ok ? spec_part_bytes(cols->ncol, bands->nb, nsel, sp.nkey, npar) : 0);
 }
 
 int crt_hip_bandsum_finish_f64(const crt_columns* cols, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream) {

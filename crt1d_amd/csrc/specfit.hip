@@ -1,0 +1,466 @@
+// Spectral normal equations and the step on them (include/crt1d_hip_specfit.h): A = J^T W J, g = J^T W r and c2 = sum r^2 of the per-band
+// misfit of the level spectra, for the closed forms 2s, bl, g77, bf.  The optics Jacobian (jac.hip) along ntan directions, the LAI
+// derivative (dlai.hip) and the leaf-angle derivative (dleaf.hip) are contracted where they are formed: the Jacobian [nsel * nb][npar] of a
+// column, the eleven derivative arrays behind it and the level spectra are never written.
+//
+//  k_spec_normal         k_grad's mapping: lane <-> band, a workgroup owns one column and one band slice; the header with its leaf-angle
+//                        tangents and the selected record entries are staged in LDS once, a lane loads its band once and runs the passes of
+//                        deriv_passes.hpp one after the other, ONE tangent at a time -- the tangent bits of the single-derivative kernels
+//                        (-ffp-contract=off).  A lane keeps (w_0 .. w_{npar-1}, r) of every (observed key, level) in LDS entries that only
+//                        it reads and writes, rows [nkey][nsel][npar + 1][lanes] -- no barrier between the passes:
+//                          primal       pass_optics<Sch::J> with no seed: X into the r entry (and to fwd); the ONE place X comes from, so r,
+//                                       c2 and fwd do not depend on which parameters exist (the unused tangents are dead code)
+//                          directions   the unit-seed passes p = leaf_r, leaf_t, soil_r add X'_p d_p[k][b] in this order (k_sens_jac's order)
+//                          LAI          pass_record<Sch::D>
+//                          leaf angle   pass_record<Sch::F, LEAF>
+//                          weights      w_i = X'_i s, r = (X - y) s; a row with s == 0 becomes a row of +0
+//                        Then the (npar + 1)(npar + 2) / 2 entries of (A | g | c2) one at a time: the lane adds its products over (key, level),
+//                        block_sum (grad.hip's: butterfly, then the waves in ascending order) adds the lanes, thread 0 stores.  The 66 sums
+//                        of npar = 10 are never live together: no accumulator sits in a register across a pass.
+//  k_spec_normal_finish  several band slices: a thread per (column, entry) adds the slice sums in ascending order (k_grad_finish's rule).
+//  k_lm_step_normal      k_lm_step (retrieve.hip) with the sums supplied instead of rows.  The scaled Cholesky and the solve are a second copy
+//                        of retrieve.hip's: sharing them would have meant editing that unit, whose device code is held to what it is.
+// No atomics anywhere: a column's result does not depend on the batch or on another column's mask.
+#include "deriv_passes.hpp"
+#include "specfit.hpp"
+
+namespace crt {
+namespace {
+
+struct P2s : Sch2s {};
+struct PBl : SchBl {};
+template <bool BF>
+struct PG77 : SchG77<BF> {};
+
+constexpr int MAXP = CRT_RETRIEVE_MAX_NPAR;     // 10
+constexpr int MAXA = MAXP + 1;                  // (w_0 .. w_{npar-1}, r)
+constexpr int MAXENT = MAXA * (MAXA + 1) / 2;   // 66 entries of (A | g | c2)
+constexpr int LM_WAVE = 64;                     // one wave per column
+
+__device__ inline int tri(int i, int j) { return i * (i + 1) / 2 + j; }  // j <= i
+
+// entry e of the lower triangle of the (npar + 1) x (npar + 1) matrix of products, row by row -> (i, j), j <= i
+__device__ inline void tri_pair(int e, int& i, int& j) {
+  i = 0;
+  while ((i + 1) * (i + 2) / 2 <= e) ++i;
+  j = e - i * (i + 1) / 2;
+}
+
+// the sum of v over the workgroup in a fixed order, valid in thread 0 (every thread calls): butterfly over the wave, then wave 0, 1, ...
+// (grad.hip's block_sum)
+__device__ __forceinline__ double block_sum(double v, double* red) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  const int tid = threadIdx.x;
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  double s = red[0];
+  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) s += red[w];
+  __syncthreads();  // (red is used again)
+  return s;
+}
+
+template <class G, bool BL>
+__global__ __launch_bounds__(SPEC_BLOCK) void k_spec_normal(SolveArgs a, LevArgs la, SpecArgs sp, int per) {
+  using SJ = typename G::J;
+  extern __shared__ double rows[];          // [nkey][nsel][npar + 1][blockDim.x]
+  __shared__ double hd[HDR_TAN + REC_HDR];  // k_dleaf's layout: header | e^{-K_b LT} at the ground | ... | the header's leaf-angle tangents
+  __shared__ double lvL[CRT_MAX_LEVEL_SELECT], lvE[CRT_MAX_LEVEL_SELECT], lvTs[CRT_MAX_LEVEL_SELECT], lvTh[CRT_MAX_LEVEL_SELECT];
+  __shared__ double lvTd[CRT_MAX_LEVEL_SELECT];  // bl: tau_d(L_j), the sky term of the primal
+  __shared__ double red[SPEC_BLOCK / 64];
+  const int c = blockIdx.x, nz = a.nz, nb = a.nb, nsel = la.nsel, tid = threadIdx.x, nthr = blockDim.x;
+  const int b = blockIdx.y * per + tid;
+  const bool live = tid < per && b < nb;
+  const int ntan = sp.ntan, npar = ntan + sp.lai + sp.leaf, na = npar + 1;
+  // k_grad's staging: the tangents of both record derivatives at once
+  const double* rec = a.ws + (long long)c * a.reclen;
+  const double* sdl = sp.side_leaf + (long long)c * (REC_HDR + (BL ? nz : 0));
+  if (tid < REC_HDR) {
+    hd[tid] = rec[tid];
+    hd[HDR_TAN + tid] = sp.leaf ? sdl[tid] : 0.0;
+  }
+  if (tid == REC_HDR) hd[REC_HDR] = rec[REC_HDR + nz];  // e^{-K_b L} at the ground
+  for (int r = tid; r < nsel; r += nthr) {
+    const int j = la.lev[r];
+    lvL[r] = rec[REC_HDR + j];
+    lvE[r] = rec[REC_HDR + nz + j];
+    if constexpr (BL) {
+      lvTs[r] = sp.lai ? sp.side_lai[(long long)c * nz + j] : 0.0;  // L_j tau_d'(L_j)
+      lvTh[r] = sp.leaf ? sdl[REC_HDR + j] : 0.0;                   // tau_d^th(L_j)
+      lvTd[r] = rec[REC_HDR + 2 * nz + j];
+    }
+  }
+  __syncthreads();
+  const double invmu = hd[S_INVMU];
+  const long long o0 = (long long)c * nsel * nb + b;  // row r of the observations: + r nb
+  double* const my = rows + tid;                      // entry i of (key kq, level r): my[((kq nsel + r) na + i) nthr]
+  const size_t lev = (size_t)na * nthr, key = lev * nsel;
+
+  if (live) {
+    const DBand in = load_dband(a, c, b, SJ::SOIL);
+
+    // ---- the primal: the closed form the passes below differentiate, no parameter seeded ----
+    pass_optics<SJ>(hd, lvL, lvE, nsel, seed_band(in, -1), [&](int r, Du dn, Du up) {
+      const double idr = in.I_dr0 * lvE[r];
+      double d = dn.v;
+      if constexpr (BL) d = in.I_df0 * lvTd[r] + d;  // the sky term I_df0 tau_d(L_j)
+      const double x[4] = {idr, d, up.v, __builtin_fma(idr, invmu, 2 * (up.v + d))};
+      double* y = my + r * lev + (size_t)npar * nthr;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (sp.y[q]) {
+          *y = x[q];
+          if (sp.fwd[q]) sp.fwd[q][o0 + (long long)r * nb] = x[q];
+          y += key;
+        }
+    });
+
+    // ---- the directions: the optics one parameter at a time (k_jac), each tangent times the lane's band of every direction ----
+    if (ntan > 0) {
+      bool first = true;  // (uniform)
+      for (int p = 0; p < CRT_JAC_NPARAM; ++p) {
+        if (!sp.d[p] || (!SJ::SOIL && p == 2)) continue;  // (bl has no soil)
+        const double* dp = sp.d[p] + (long long)c * sp.dstride + b;
+        double d[CRT_SENSJAC_MAX_NTAN];
+#pragma unroll
+        for (int k = 0; k < CRT_SENSJAC_MAX_NTAN; ++k) d[k] = k < ntan ? dp[(long long)k * nb] : 0.0;
+        pass_optics<SJ>(hd, lvL, lvE, nsel, seed_band(in, p), [&](int r, Du dn, Du up) {
+          const double x[4] = {0.0, dn.d, up.d, 2 * (up.d + dn.d)};  // F' as jac_store; I_dr does not depend on the optics
+          double* y = my + r * lev;
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (sp.y[q]) {
+#pragma unroll
+              for (int k = 0; k < CRT_SENSJAC_MAX_NTAN; ++k)
+                if (k < ntan) {
+                  double* const e = y + (size_t)k * nthr;
+                  if (q == 0) {
+                    if (first) *e = 0.0;
+                  } else {
+                    const double t = x[q] * d[k];
+                    *e = first ? t : *e + t;
+                  }
+                }
+              y += key;
+            }
+        });
+        first = false;
+      }
+      if (first)  // (bl with directions in soil_r alone: zeros)
+        for (int t = 0; t < sp.nkey * nsel; ++t)
+          for (int k = 0; k < ntan; ++k) my[t * lev + (size_t)k * nthr] = 0.0;
+    }
+
+    // ---- the LAI (k_dlai) ----
+    if (sp.lai)
+      pass_record<typename G::D, BL, false>(hd, lvL, lvE, lvTs, nsel, in, [&](int r, double dI, Du dn, Du up) {
+        const double x[4] = {dI, dn.d, up.d, flux_tan(dI, invmu, dn, up)};
+        double* y = my + r * lev + (size_t)ntan * nthr;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (sp.y[q]) {
+            *y = x[q];
+            y += key;
+          }
+      });
+
+    // ---- the leaf angles (k_dleaf) ----
+    if (sp.leaf)
+      pass_record<typename G::F, BL, true>(hd, lvL, lvE, lvTh, nsel, in, [&](int r, double dI, Du dn, Du up) {
+        const double x[4] = {dI, dn.d, up.d, flux_tan(dI, invmu, dn, up)};
+        double* y = my + r * lev + (size_t)(ntan + sp.lai) * nthr;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (sp.y[q]) {
+            *y = x[q];
+            y += key;
+          }
+      });
+
+    // ---- the weights: w_i = X'_i s and r = (X - y) s, each rounded once; a skipped row becomes a row of +0 ----
+    for (int r = 0; r < nsel; ++r) {
+      const long long o = o0 + (long long)r * nb;
+      double* y = my + r * lev;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (sp.y[q]) {
+          const double s = sp.is[q] ? sp.is[q][o] : 1.0;
+          if (s != 0.0) {
+            for (int i = 0; i < npar; ++i) y[(size_t)i * nthr] = y[(size_t)i * nthr] * s;
+            y[(size_t)npar * nthr] = (y[(size_t)npar * nthr] - sp.y[q][o]) * s;
+          } else {
+            for (int i = 0; i <= npar; ++i) y[(size_t)i * nthr] = 0.0;
+          }
+          y += key;
+        }
+    }
+  }
+
+  // ---- (A | g | c2), one entry at a time: the products of a lane in the order (key, level), then the lanes ----
+  const int ntri = npar * (npar + 1) / 2, nent = na * (na + 1) / 2, nrow = sp.nkey * nsel, nslice = gridDim.y;
+  double* const dst = nslice == 1 ? nullptr : sp.part + ((long long)c * nslice + blockIdx.y) * nent;
+  int i = 0, j = 0;
+  for (int e = 0; e < nent; ++e) {
+    double acc = 0.0;
+    if (live) {
+      const double *yi = my + (size_t)i * nthr, *yj = my + (size_t)j * nthr;
+      for (int t = 0; t < nrow; ++t) acc = acc + yi[t * lev] * yj[t * lev];
+    }
+    const double s = block_sum(acc, red);
+    if (tid == 0) {
+      if (dst) dst[e] = s;
+      else if (e < ntri) sp.A[(long long)c * ntri + e] = s;
+      else if (e < ntri + npar) sp.g[(long long)c * npar + e - ntri] = s;
+      else sp.c2[c] = s;
+    }
+    if (++j > i) {
+      ++i;
+      j = 0;
+    }
+  }
+}
+
+// One thread per (column, entry): the slice sums in ascending slice order, starting from slice 0's bits.
+__global__ __launch_bounds__(256) void k_spec_normal_finish(long long ncol, int nslice, int npar, const double* __restrict__ part,
+                                                             double* __restrict__ A, double* __restrict__ g, double* __restrict__ c2) {
+  const int ntri = npar * (npar + 1) / 2, nent = (npar + 1) * (npar + 2) / 2;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ncol * nent) return;
+  const long long c = i / nent;
+  const int e = (int)(i - c * nent);
+  const double* p = part + c * nslice * nent + e;
+  double s = p[0];
+  for (int sl = 1; sl < nslice; ++sl) s += p[(long long)sl * nent];
+  if (e < ntri) A[c * ntri + e] = s;
+  else if (e < ntri + npar) g[c * npar + e - ntri] = s;
+  else c2[c] = s;
+}
+
+template <class G, bool BL = false>
+int launch_spec_closed(const SolveArgs& a, const LevArgs& la, const SpecArgs& sp, hipStream_t s, bool probe) {
+  const int npar = sp.ntan + sp.lai + sp.leaf;
+  const LevSlices ls = spec_slices(a.nb, la.nsel, sp.nkey, npar);
+  if (ls.nslice == 0 || ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
+  if (probe) return CRT_OK;
+  const size_t sh = spec_rows(la.nsel, sp.nkey, npar) * ls.nthr * sizeof(double);  // (<= the bound of spec_slices)
+  int st = launch_kernel(k_spec_normal<G, BL>, dim3(a.ncol, ls.nslice), ls.nthr, sh, s, a, la, sp, ls.per);
+  const bool fin = ls.nslice > 1;
+  if (st == CRT_OK && fin) {
+    const long long n = (long long)a.ncol * spec_nent(npar);  // (< 2^31 * 66: the grid fits)
+    st = launch_kernel(k_spec_normal_finish, dim3((unsigned)((n + 255) / 256)), 256, 0, s, (long long)a.ncol, ls.nslice, npar, sp.part, sp.A,
+                       sp.g, sp.c2);
+  }
+  if (st == CRT_OK)
+    note_kernel("k_spec_normal<%s> nsel=%d nkey=%d npar=%d slice=%d%s", G::J::NAME, la.nsel, sp.nkey, npar, ls.per, fin ? " + k_spec_normal_finish" : "");
+  return st;
+}
+
+// ------------------------------------------------------------------------------------------
+// the step on supplied sums: k_lm_step of retrieve.hip, line by line, with the row loop replaced by the block loads
+
+struct NormalBlock {
+  const double *A, *g, *c2;
+};
+
+struct LmNormalArgs {
+  NormalBlock blk[CRT_LM_MAX_BLOCKS];
+  int nblk, npar;
+  double lam_up, lam_down, lam_min, lam_max, xtol, ftol;
+  const double *lo, *hi, *prior, *isp;
+  crt_lm_state st;
+};
+
+// By ONE lane, on LDS: sc[k] = 1 / sqrt(A_kk) (dead: 1); M = (A_ij sc_i) sc_j + (dead ? 1 : lam) [i == j], lower triangle, replaced by its
+// Cholesky factor (left-looking, as batched.gauss_newton_step).  ent: the packed lower triangle of A.
+__device__ inline void scaled_cholesky(const double* ent, int n, double lam, double* M, double* sc, bool* dead) {
+  for (int k = 0; k < n; ++k) {
+    const double d = ent[tri(k, k)];
+    dead[k] = d <= 0.0;
+    sc[k] = dead[k] ? 1.0 : 1.0 / sqrt(d);
+  }
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double m = (ent[tri(i, j)] * sc[i]) * sc[j];
+      if (i == j) m = m + (dead[i] ? 1.0 : lam);
+      M[i * MAXP + j] = m;
+    }
+  for (int j = 0; j < n; ++j) {
+    double s = 0.0;
+    for (int k = 0; k < j; ++k) s = s + M[j * MAXP + k] * M[j * MAXP + k];
+    const double d = sqrt(M[j * MAXP + j] - s);
+    M[j * MAXP + j] = d;
+    for (int i = j + 1; i < n; ++i) {
+      double t = 0.0;
+      for (int k = 0; k < j; ++k) t = t + M[i * MAXP + k] * M[j * MAXP + k];
+      M[i * MAXP + j] = (M[i * MAXP + j] - t) / d;
+    }
+  }
+}
+
+// L L^T x = x in place (x: LDS, n entries)
+__device__ inline void cholesky_solve(const double* M, int n, double* x) {
+  for (int j = 0; j < n; ++j) {
+    double s = 0.0;
+    for (int k = 0; k < j; ++k) s = s + M[j * MAXP + k] * x[k];
+    x[j] = (x[j] - s) / M[j * MAXP + j];
+  }
+  for (int j = n - 1; j >= 0; --j) {
+    double s = 0.0;
+    for (int k = j + 1; k < n; ++k) s = s + M[k * MAXP + j] * x[k];
+    x[j] = (x[j] - s) / M[j * MAXP + j];
+  }
+}
+
+// entry e of (A | g | c2) of column c in a block
+__device__ __forceinline__ double block_entry(const NormalBlock& B, long long c, int e, int ntri, int npar) {
+  return e < ntri ? B.A[c * ntri + e] : e < ntri + npar ? B.g[c * npar + e - ntri] : B.c2[c];
+}
+
+__global__ __launch_bounds__(LM_WAVE) void k_lm_step_normal(LmNormalArgs a) {
+  __shared__ double ent[MAXENT + 2];  // (A | g | 2 cost)
+  __shared__ double M[MAXP * MAXP];
+  __shared__ double sc[MAXP], dl[MAXP];
+  __shared__ bool dead[MAXP];
+  const long long c = blockIdx.x;
+  const int lane = threadIdx.x;
+  const crt_lm_state& S = a.st;
+  if (S.status[c] != CRT_LM_RUNNING) return;  // (the whole wave, before any barrier)
+  const int npar = a.npar, na = npar + 1, ntri = npar * (npar + 1) / 2, nent = na * (na + 1) / 2;
+  const int e0 = lane, e1 = lane + LM_WAVE;
+  const bool has0 = e0 < nent, has1 = e1 < nent;
+  int i0 = 0, j0 = 0, i1 = 0, j1 = 0;
+  if (has0) tri_pair(e0, i0, j0);
+  if (has1) tri_pair(e1, i1, j1);
+  double acc0 = 0.0, acc1 = 0.0;
+  if (has0) acc0 = block_entry(a.blk[0], c, e0, ntri, npar);
+  if (has1) acc1 = block_entry(a.blk[0], c, e1, ntri, npar);
+  for (int q = 1; q < a.nblk; ++q) {
+    if (has0) acc0 = acc0 + block_entry(a.blk[q], c, e0, ntri, npar);
+    if (has1) acc1 = acc1 + block_entry(a.blk[q], c, e1, ntri, npar);
+  }
+  if (a.isp) {
+    for (int k = 0; k < npar; ++k) {
+      const double s = a.isp[c * npar + k];
+      if (s == 0.0) continue;
+      const double d = (S.p_trial[c * npar + k] - a.prior[c * npar + k]) * s;
+      if (has0) {
+        if (i0 == k && j0 == k) acc0 = acc0 + s * s;
+        else if (i0 == npar && j0 == k) acc0 = acc0 + s * d;
+        else if (i0 == npar && j0 == npar) acc0 = acc0 + d * d;
+      }
+      if (has1) {
+        if (i1 == k && j1 == k) acc1 = acc1 + s * s;
+        else if (i1 == npar && j1 == k) acc1 = acc1 + s * d;
+        else if (i1 == npar && j1 == npar) acc1 = acc1 + d * d;
+      }
+    }
+  }
+  if (has0) ent[e0] = acc0;
+  if (has1) ent[e1] = acc1;
+  __syncthreads();
+
+  // ---- accept / reject: every lane takes the same decisions from the same values ----
+  const double cost_t = 0.5 * ent[nent - 1];
+  const double cost = S.cost[c];
+  double lam = S.lam[c];
+  int status = CRT_LM_RUNNING;
+  const bool accept = cost_t < cost;
+  double new_cost = cost;
+  if (accept) {
+    if (lane < npar) S.p[c * npar + lane] = S.p_trial[c * npar + lane];
+    if (has0 && e0 < ntri) S.A[c * ntri + e0] = acc0;
+    if (has0 && e0 >= ntri && e0 < ntri + npar) S.g[c * npar + e0 - ntri] = acc0;
+    if (has1 && e1 < ntri + npar) S.g[c * npar + e1 - ntri] = acc1;  // (e1 >= 64 > ntri)
+    lam = fmax(lam * a.lam_down, a.lam_min);
+    if (cost - cost_t < a.ftol * cost_t) status = CRT_LM_CONVERGED_F;
+    new_cost = cost_t;
+  } else if (cost == INFINITY) {
+    status = CRT_LM_FAILED_START;
+  } else {
+    lam = lam * a.lam_up;
+    if (lam > a.lam_max) status = CRT_LM_STALLED;
+    __syncthreads();
+    if (has0 && e0 < ntri) ent[e0] = S.A[c * ntri + e0];
+    if (has0 && e0 >= ntri && e0 < ntri + npar) ent[e0] = S.g[c * npar + e0 - ntri];
+    if (has1 && e1 < ntri + npar) ent[e1] = S.g[c * npar + e1 - ntri];
+    __syncthreads();
+  }
+
+  // ---- the next trial point ----
+  bool conv_x = false;
+  double pk = 0.0, pt = 0.0;
+  if (status == CRT_LM_RUNNING) {
+    if (lane == 0) {
+      scaled_cholesky(ent, npar, lam, M, sc, dead);
+      for (int k = 0; k < npar; ++k) dl[k] = -ent[ntri + k] * sc[k];
+      cholesky_solve(M, npar, dl);
+      for (int k = 0; k < npar; ++k) dl[k] = dl[k] * sc[k];
+    }
+    __syncthreads();
+    bool far = false;
+    if (lane < npar) {
+      pk = S.p[c * npar + lane];  // (written by this lane where the step was accepted)
+      pt = pk + dl[lane];
+      if (a.lo && pt < a.lo[lane]) pt = a.lo[lane];
+      if (a.hi && pt > a.hi[lane]) pt = a.hi[lane];
+      far = !(fabs(pt - pk) < a.xtol * (fabs(pk) + a.xtol));
+    }
+    conv_x = !__any(far);
+    if (conv_x) status = CRT_LM_CONVERGED_X;
+  } else if (lane < npar) {
+    pk = S.p[c * npar + lane];
+  }
+  if (lane < npar) S.p_trial[c * npar + lane] = status == CRT_LM_RUNNING ? pt : pk;
+  if (lane == 0) {
+    S.cost[c] = new_cost;
+    S.lam[c] = lam;
+    S.status[c] = status;
+    if (accept) S.naccept[c] += 1;
+    else if (status != CRT_LM_FAILED_START) S.nreject[c] += 1;
+  }
+}
+
+}  // namespace
+
+int launch_spec_normal(int scheme, const SolveArgs& a, const LevArgs& la, const SpecArgs& sp, hipStream_t s, bool probe) {
+  switch (scheme) {
+    case CRT_SCHEME_2S: return launch_spec_closed<P2s>(a, la, sp, s, probe);
+    case CRT_SCHEME_BL: return launch_spec_closed<PBl, true>(a, la, sp, s, probe);
+    case CRT_SCHEME_G77: return launch_spec_closed<PG77<false>>(a, la, sp, s, probe);
+    case CRT_SCHEME_BF: return launch_spec_closed<PG77<true>>(a, la, sp, s, probe);
+    default: return CRT_ERR_UNSUPPORTED;
+  }
+}
+
+}  // namespace crt
+
+using namespace crt;
+
+extern "C" {
+
+int crt_hip_lm_step_normal_f64(const crt_lm_problem* prob, const crt_lm_normal_block* blocks, int32_t nblk, const crt_lm_state* state,
+                               crt_stream_t stream) {
+  if (!prob || !blocks || !state) return CRT_ERR_BAD_ARG;
+  if (prob->ncol < 1 || prob->npar < 1 || prob->npar > CRT_RETRIEVE_MAX_NPAR || nblk < 1 || nblk > CRT_LM_MAX_BLOCKS) return CRT_ERR_BAD_ARG;
+  if (!(prob->lam_up > 1.0) || !(prob->lam_down > 0.0 && prob->lam_down <= 1.0)) return CRT_ERR_BAD_ARG;
+  if (!(prob->lam_min >= 0.0) || !(prob->lam_max >= prob->lam_min) || !(prob->xtol >= 0.0) || !(prob->ftol >= 0.0)) return CRT_ERR_BAD_ARG;
+  if (!prob->prior != !prob->inv_sigma_prior) return CRT_ERR_BAD_ARG;
+  if (!state->p || !state->p_trial || !state->cost || !state->lam || !state->A || !state->g || !state->status || !state->naccept ||
+      !state->nreject)
+    return CRT_ERR_BAD_ARG;
+  LmNormalArgs a = {};
+  for (int q = 0; q < nblk; ++q) {
+    if (!blocks[q].A || !blocks[q].g || !blocks[q].c2) return CRT_ERR_BAD_ARG;
+    a.blk[q] = NormalBlock{blocks[q].A, blocks[q].g, blocks[q].c2};
+  }
+  a.nblk = nblk, a.npar = prob->npar;
+  a.lam_up = prob->lam_up, a.lam_down = prob->lam_down, a.lam_min = prob->lam_min, a.lam_max = prob->lam_max;
+  a.xtol = prob->xtol, a.ftol = prob->ftol;
+  a.lo = prob->lo, a.hi = prob->hi, a.prior = prob->prior, a.isp = prob->inv_sigma_prior;
+  a.st = *state;
+  const int st = launch_kernel(k_lm_step_normal, dim3(prob->ncol), LM_WAVE, 0, static_cast<hipStream_t>(stream), a);
+  if (st == CRT_OK) note_kernel("k_lm_step_normal npar=%d nblk=%d", prob->npar, nblk);
+  return st;
+}
+
+}  // extern "C"
