@@ -76,12 +76,20 @@ def _G_closed_form(kind, param, psi):
     raise ValueError(f"unknown G kind {kind}")
 
 
+def _keep(a):
+    """``a`` as an array in its own dtype where that is a float or complex type of at least 8 bytes (float64, longdouble, complex128,
+    clongdouble), else as float64: real float64 input takes the path it always took, and a complex or extended-precision ``lai`` or
+    spectrum runs through the closed-form schemes as it is (tests/deriv_reference.py: complex-step derivatives)."""
+    a = np.asarray(a)
+    return a if a.dtype.kind in "fc" and a.dtype.itemsize >= 8 else a.astype(np.float64)
+
+
 class Columns:
     """Per-column geometry: psi (ncol,), lai (ncol,nz), mla (ncol,) and G description."""
 
     def __init__(self, psi, lai, *, mla=None, g_kind=None, g_param=None, G_fn=None):
         self.psi = np.atleast_1d(np.asarray(psi, dtype=np.float64))
-        self.lai = np.atleast_2d(np.asarray(lai, dtype=np.float64))
+        self.lai = np.atleast_2d(_keep(lai))
         self.ncol, self.nz = self.lai.shape
         assert self.psi.shape == (self.ncol,)
         self.mla = None if mla is None else np.broadcast_to(np.asarray(mla, dtype=np.float64), (self.ncol,))
@@ -141,7 +149,7 @@ def tau_d(cols, L, *, method="quad", exact_quad=False):
     ``L`` is ``(ncol, m)``.  common.py:30-37 ('quad'), :40-53 ('9sky'), :56-87 (dispatch;
     ``ValueError`` for other methods, :78).
     """
-    L = np.asarray(L, dtype=np.float64)
+    L = _keep(L)
     out = np.empty_like(L)
     if method == "9sky":
         psis = np.deg2rad(np.arange(5.0, 90.0, 10.0))
@@ -169,7 +177,7 @@ def one_minus_tau_d(cols, L, *, method="quad", exact_quad=False):
     integrate to one), which keeps its RELATIVE accuracy as L -> 0; n79 divides it by dlai (_solve_n79.py:146,154-155), and formed as
     1 - tau_d the ~3e-13 by which two quadrature rules differ in tau_d became ~2e-8 at dlai ~ 3e-4.  '9sky' and the reference's own
     adaptive quadrature (exact_quad) stay 1 - tau_d, as the reference computes it (_solve_n79.py:99,146)."""
-    L = np.asarray(L, dtype=np.float64)
+    L = _keep(L)
     if method != "quad" or exact_quad:
         return 1 - tau_d(cols, L, method=method, exact_quad=exact_quad)
     wts = 2 * _W_Q * np.sin(_PSI_Q) * np.cos(_PSI_Q)
@@ -221,7 +229,7 @@ def G_integrals(cols, mu_s, *, exact_quad=False):
 
 def _bc(a, ncol):
     """Per-(column, band) input -> (ncol, 1, nb) for broadcasting against (ncol, nz, 1)."""
-    a = np.asarray(a, dtype=np.float64)
+    a = _keep(a)
     if a.ndim == 1:
         a = a[None, :]
     a = np.broadcast_to(a, (ncol, a.shape[-1]))

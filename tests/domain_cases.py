@@ -184,6 +184,19 @@ def oracle_solve_device_rules(oracle, d, scheme, ref, edges=DEVICE_EDGES):
     return out
 
 
+def singular_quantities(oracle, d):
+    """What the two removable singularities of the closed forms are made of, per (column, band) [Kb: (ncol, 1)], from the oracle: 2s
+    sigma = (mu_bar K_b)^2 + c^2 - b^2 with its terms mbK = mu_bar K_b, b, c (_solve_2s.py:65-85); bf k_d = 0.8 sqrt(1 - omega) against
+    K_b (_solve_bf.py:80,95).  One place for ``domain_bars`` and for the tests that choose well-conditioned bands."""
+    oc = oracle.Columns(d["psi"], d["lai"], mla=d["mla"], g_kind=d["g_kind"], g_param=d["g_param"])
+    Kb = oc.K_b()[:, None]
+    om = d["leaf_r"] + d["leaf_t"]
+    beta = 0.5 * (om + (d["leaf_r"] - d["leaf_t"]) * np.cos(np.deg2rad(d["mla"]))[:, None] ** 2) / om
+    b_, c_ = 1 - (1 - beta) * om, om * beta
+    mbK = oracle.mu_bar(oc)[:, None] * Kb
+    return {"oc": oc, "Kb": Kb, "om": om, "b": b_, "c": c_, "mbK": mbK, "sigma": mbK ** 2 + c_**2 - b_**2, "k_d": 0.8 * np.sqrt(1 - om)}
+
+
 def domain_bars(oracle, d, uniform):
     """Allowed error of a kernel against the oracle WITH THE SAME QUADRATURE RULES (``oracle_solve_device_rules``), as a fraction of the
     profile maximum, per (column, band) [or per column, shape (ncol, 1)]:
@@ -211,13 +224,8 @@ def domain_bars(oracle, d, uniform):
     chi_l = 0.6 leaves in layers of ~2e-4 (2.4e-11: a layer's reflectance is (1 - tau_d) rho, relative error 3.5e-10); and 4s for
     ellipsoidal leaves with x = 0.2 or 10 (3.9e-11: G_int_1/2 by 16 nodes are 5e-12 off)."""
     ncol = d["psi"].shape[0]
-    oc = oracle.Columns(d["psi"], d["lai"], mla=d["mla"], g_kind=d["g_kind"], g_param=d["g_param"])
-    Kb = oc.K_b()[:, None]
-    om = d["leaf_r"] + d["leaf_t"]
-    beta = 0.5 * (om + (d["leaf_r"] - d["leaf_t"]) * np.cos(np.deg2rad(d["mla"]))[:, None] ** 2) / om
-    b_, c_ = 1 - (1 - beta) * om, om * beta
-    sigma = (oracle.mu_bar(oc)[:, None] * Kb) ** 2 + c_**2 - b_**2
-    k_d = 0.8 * np.sqrt(1 - om)
+    q = singular_quantities(oracle, d)
+    oc, Kb, om, sigma, k_d = q["oc"], q["Kb"], q["om"], q["sigma"], q["k_d"]
     G12 = oracle.G_integrals(oc, 0.501)
     mu_1, mu_2, al, be, ga, _, _ = oracle._coef_4s(om, 1.0, G12[:, :1], G12[:, 1:], 0.501)
     G1, G2 = np.broadcast_to(G12[:, :1], om.shape), np.broadcast_to(G12[:, 1:], om.shape)

@@ -207,7 +207,8 @@ def _cases():
 def test_fwd_and_normal_equations(scheme, nb, uniform):
     """fwd within FWD_TOL of LevelsPlan relative to the key's largest value; A, g and c2 within the derived bound of the composition.
     Measured on MI355X, the largest |got - ref| / bound over the cases: A 0.087 (bf, nb = 5), g 0.065, c2 0.051; from 64 bands on below
-    0.05, from 300 on below 0.006.  bl observed in I_df_u alone (nb = 1, 64, 2151) has no signal: every sum is +0."""
+    0.05, from 300 on below 0.006.  bl observed in I_df_u alone (nb = 1, 64, 2151) has no signal: every sum is +0.
+    The check of fwd, A, g and c2 against the oracle, not against other kernels: test_gpu_deriv_domain.py::test_spectral_normal_equations."""
     ncol, nz, lev, keys, ntan = _config(nb)
     plan, got = _got(scheme, nb, uniform)
     X = _reference(scheme, nb, uniform)[0]
