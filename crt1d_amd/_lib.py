@@ -506,6 +506,30 @@ def _specfit_signatures():
 _SPECFIT_SIGNATURES = _specfit_signatures()
 SPECFIT_EXPORTS = list(_SPECFIT_SIGNATURES)
 
+# those normal equations over a sun-angle series (include/series/crt1d_hip_specfit_series.h); again a table of its own
+
+
+class CrtSpecSeriesOut(ctypes.Structure):
+    """``crt_spec_series_out``: the sums over the sun states ``A [ncol][ntri]``, ``g [ncol][npar]``, ``c2 [ncol]``; the optional sums of
+    every sun state ``A_t / g_t / c2_t`` (``[ncol][nt]...``, all NULL or all set); the optional model spectra ``[ncol][nt][nsel][nb]``."""
+
+    _fields_ = [(k, _vp) for k in ("A", "g", "c2", "A_t", "g_t", "c2_t", "fwd_I_dr", "fwd_I_df_d", "fwd_I_df_u", "fwd_F")]
+
+
+def _specfit_series_signatures():
+    P = ctypes.POINTER
+    i, i32, sz, ok = ctypes.c_int, ctypes.c_int32, ctypes.c_size_t, ctypes.c_int
+    return {
+        "crt_hip_spectral_normal_series_workspace_bytes": (sz, [i, i32, i32, i32, i32, i32, i32, i32]),
+        "crt_hip_spectral_normal_series_f64": (ok, [i, P(CrtColumns), P(CrtBands), P(CrtSunSeries), P(CrtOptions), P(i32), i32,
+                                                    P(CrtOpticsDirs), i, P(CrtLeafTangentSeries), P(CrtSpecObs), P(CrtSpecSeriesOut), _vp, sz,
+                                                    _vp]),
+    }
+
+
+_SPECFIT_SERIES_SIGNATURES = _specfit_series_signatures()
+SPECFIT_SERIES_EXPORTS = list(_SPECFIT_SERIES_SIGNATURES)
+
 _lib = None
 
 
@@ -530,7 +554,8 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES, **_SENSOR_SIGNATURES, **_JAC_SIGNATURES,
                                       **_DLAI_SIGNATURES, **_DLEAF_SIGNATURES, **_GRAD_SIGNATURES, **_SENSJAC_SIGNATURES,
-                                      **_SENSJAC_SERIES_SIGNATURES, **_RETRIEVE_SIGNATURES, **_SPECFIT_SIGNATURES}.items():
+                                      **_SENSJAC_SERIES_SIGNATURES, **_RETRIEVE_SIGNATURES, **_SPECFIT_SIGNATURES,
+                                      **_SPECFIT_SERIES_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:

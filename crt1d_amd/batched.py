@@ -2374,13 +2374,17 @@ def spectral_normal_workspace_bytes(scheme, ncol, nz, nb, nsel, nkey, npar):
 
 
 def _spectral_static(scheme, y, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, leaf=False,
-                     tau_d_method="quad", bands=None):
-    """The checks of the spectral plans that touch no device.  -> (keys in ``LEVEL_KEYS`` order, ntan, npar)"""
+                     tau_d_method="quad", bands=None, sun=None):
+    """The checks of the spectral plans that touch no device (``sun``: the series forms, whose arrays carry a sun-state axis).
+    -> (keys in ``LEVEL_KEYS`` order, ntan, npar)"""
     import numpy as np
 
     _SolvePlan._check_options(_SolvePlan, scheme, tau_d_method)
     if scheme not in SPECTRAL_RETRIEVE_SCHEMES:
         raise ValueError(f"scheme {scheme!r} has no spectral retrieval; served: " + ", ".join(SPECTRAL_RETRIEVE_SCHEMES))
+    if sun is not None and (not isinstance(sun, SunSeries) or isinstance(sun, SunSeriesF32)):
+        raise TypeError("sun must be a SunSeries (float64 spectra)")
+    axes = "(ncol, nsel, nb)" if sun is None else "(ncol, nt, nsel, nb)"
     keys = _level_keys(keys)
     keys = tuple(k for k in LEVEL_KEYS if k in keys)
     shapes = set()
@@ -2388,18 +2392,18 @@ def _spectral_static(scheme, y, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=No
         if d is None and name == "inv_sigma":
             continue
         if not isinstance(d, dict):
-            raise TypeError(f"{name} must be a dict {{key: (ncol, nsel, nb)}}")
+            raise TypeError(f"{name} must be a dict {{key: {axes}}}")
         if extra := [k for k in d if k not in keys]:
             raise ValueError(f"{name} has the keys {extra}, which are not in keys = {keys}")
         for k, v in d.items():
             shape = tuple(v.shape) if hasattr(v, "shape") else np.shape(v)
-            if len(shape) != 3:
-                raise ValueError(f"{name}[{k!r}] must be (ncol, nsel, nb), got {shape}")
+            if len(shape) != (3 if sun is None else 4):
+                raise ValueError(f"{name}[{k!r}] must be {axes}, got {shape}")
             shapes.add(shape)
     if missing := [k for k in keys if k not in y]:
         raise ValueError(f"y lacks the keys {missing} of keys = {keys}")
     if len(shapes) > 1:
-        raise ValueError(f"the arrays of y and inv_sigma must share one shape (ncol, nsel, nb), got {sorted(shapes)}")
+        raise ValueError(f"the arrays of y and inv_sigma must share one shape {axes}, got {sorted(shapes)}")
     ntan = _sensjac_ntan(d_leaf_r, d_leaf_t, d_soil_r)
     npar = ntan + bool(lai) + bool(leaf)
     if npar == 0:
@@ -2409,10 +2413,11 @@ def _spectral_static(scheme, y, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=No
     return keys, ntan, npar
 
 
-def _spectral_shapes(cols, bands, levels, y, inv_sigma, nkey, npar):
-    """The shapes of the observations against ``(ncol, nsel, nb)`` and the LDS limit; still no device.  -> the normalized levels"""
+def _spectral_shapes(cols, bands, levels, y, inv_sigma, nkey, npar, sun=None):
+    """The shapes of the observations against ``(ncol, nsel, nb)`` (``sun``: ``(ncol, nt, nsel, nb)``) and the LDS limit; still no
+    device.  -> the normalized levels"""
     levels = normalize_levels(levels, cols.nz)
-    shape = (cols.ncol, len(levels), bands.nb)
+    shape = (cols.ncol, *(() if sun is None else (sun.nt,)), len(levels), bands.nb)
     for name, d in (("y", y), ("inv_sigma", inv_sigma or {})):
         for k, v in d.items():
             if tuple(v.shape) != shape:
@@ -2441,12 +2446,20 @@ class SpectralNormalPlan(_LevelsDerivPlan):
                  lai=True, tangent=None, fwd=False, mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
         if tangent is not None and not isinstance(tangent, LeafTangent):
             raise TypeError("tangent must be a LeafTangent")
+        self._build(scheme, cols, bands, None, levels, y, keys, inv_sigma, d_leaf_r, d_leaf_t, d_soil_r, lai, tangent, False, fwd, mu_s,
+                    tau_d_method, out, workspace)
+
+    def _build(self, scheme, cols, bands, sun, levels, y, keys, inv_sigma, d_leaf_r, d_leaf_t, d_soil_r, lai, tangent, per_step, fwd, mu_s,
+               tau_d_method, out, workspace):
+        """The construction of this plan (``sun`` None) and of :class:`SpectralNormalSeriesPlan` (arrays with a sun-state axis)."""
+        series = {} if sun is None else {"sun": sun}
         keys, ntan, npar = _spectral_static(scheme, y, keys, inv_sigma, d_leaf_r, d_leaf_t, d_soil_r, lai, tangent is not None, tau_d_method,
-                                            bands)
-        self.levels, self.keys = _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), npar), keys
+                                            bands, **series)
+        self.levels, self.keys = _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), npar, **series), keys
         ncol, nsel, nb, dev = cols.ncol, len(self.levels), bands.nb, cols.device
-        shape = (ncol, nsel, nb)
-        self._bind(scheme, cols, bands, mu_s, tau_d_method)
+        nts = () if sun is None else (sun.nt,)
+        shape = (ncol, *nts, nsel, nb)
+        self._bind(scheme, cols, bands, mu_s, tau_d_method, **series)
         obs = lambda v: torch.as_tensor(v, dtype=torch.float64).to(dev).contiguous()  # noqa: E731
         self.y = {k: obs(y[k]) for k in keys}
         self.inv_sigma = {k: obs(inv_sigma[k]) for k in keys if inv_sigma is not None and k in inv_sigma}
@@ -2458,23 +2471,33 @@ class SpectralNormalPlan(_LevelsDerivPlan):
         self.tangent, self.ntan, self.npar = tangent, ntan, npar
         self.params = tuple(f"dir{k}" for k in range(ntan)) + (("lai",) if lai else ()) + (("leaf",) if tangent is not None else ())
         ntri = npar * (npar + 1) // 2
-        o = _outputs({"A": (ncol, ntri), "g": (ncol, npar), "c2": (ncol,)}, out, torch.float64, dev, "output {!r}", lacks=True)
-        self.out = {k: o[k] for k in ("A", "g", "c2")}
+        shapes = {"A": (ncol, ntri), "g": (ncol, npar), "c2": (ncol,)}
+        if per_step:
+            shapes.update({"A_t": (ncol, *nts, ntri), "g_t": (ncol, *nts, npar), "c2_t": (ncol, *nts)})
+        o = _outputs(shapes, out, torch.float64, dev, "output {!r}", lacks=True)
+        self.out = {k: o[k] for k in shapes}
         self.write_fwd = bool(fwd)
         if fwd:
             self.out["fwd"] = {k: torch.empty(shape, dtype=torch.float64, device=dev) for k in keys}
         ptr = lambda d, k: d[k].data_ptr() if k in d else None  # noqa: E731
         self._obs = _lib.CrtSpecObs(*[ptr(self.y, k) for k in LEVEL_KEYS], *[ptr(self.inv_sigma, k) for k in LEVEL_KEYS])
         sums = [self.out[k].data_ptr() for k in ("A", "g", "c2")]
-        self._out_sums = _lib.CrtSpecNormalOut(*sums, None, None, None, None)
-        self._out_fwd = _lib.CrtSpecNormalOut(*sums, *[ptr(self.out.get("fwd", {}), k) for k in LEVEL_KEYS])
+        struct = _lib.CrtSpecNormalOut
+        if sun is not None:
+            struct = _lib.CrtSpecSeriesOut
+            sums += [ptr(self.out, k) for k in ("A_t", "g_t", "c2_t")]
+        self._out_sums = struct(*sums, None, None, None, None)
+        self._out_fwd = struct(*sums, *[ptr(self.out.get("fwd", {}), k) for k in LEVEL_KEYS])
         self._lev = (ctypes.c_int32 * nsel)(*self.levels)
         self._dirs = None
         if ntan:
             self._dirs = _lib.CrtOpticsDirs(ntan, ntan * nb if per_col else 0,
                                             *[self.dirs[n].data_ptr() if n in self.dirs else None for n in JAC_PARAMS])
         self._tan = None if tangent is None else tangent.c_struct()
-        need = spectral_normal_workspace_bytes(scheme, ncol, cols.nz, nb, nsel, len(keys), npar)
+        if sun is None:
+            need = spectral_normal_workspace_bytes(scheme, ncol, cols.nz, nb, nsel, len(keys), npar)
+        else:
+            need = spectral_normal_series_workspace_bytes(scheme, ncol, cols.nz, nb, sun.nt, nsel, len(keys), npar)
         self._finish(self._entry_name, need, workspace)
 
     def _tail(self):
@@ -2499,6 +2522,55 @@ def spectral_normal(scheme, cols: Columns, bands: Bands, levels, y, *, keys, **k
     _spectral_shapes(cols, bands, levels, y, kw.get("inv_sigma"), len(k), npar)  # (all before any device is touched)
     with torch.cuda.device(cols.device):
         return SpectralNormalPlan(scheme, cols, bands, levels, y, keys=keys, **kw)()
+
+
+def spectral_normal_series_workspace_bytes(scheme, ncol, nz, nb, nt, nsel, nkey, npar):
+    """Device workspace of a :class:`SpectralNormalSeriesPlan` call: the records of :func:`levels_series_workspace_bytes` at the same
+    offsets, the side records of the LAI and of the leaf-angle derivative, and the slice sums of every (column, t)."""
+    return int(_lib.load().crt_hip_spectral_normal_series_workspace_bytes(_lib.SCHEME_IDS[scheme], ncol, nz, nb, nt, nsel, nkey, npar))
+
+
+def _spectral_series_static(sun, tangent):
+    """The checks of the series form that touch no device, in front of those of :func:`_spectral_static`."""
+    if not isinstance(sun, SunSeries) or isinstance(sun, SunSeriesF32):
+        raise TypeError("sun must be a SunSeries (float64 spectra)")
+    if tangent is not None and not isinstance(tangent, LeafTangentSeries):
+        raise TypeError("tangent must be a LeafTangentSeries")
+    if tangent is not None and tangent.nt != sun.nt:
+        raise ValueError(f"the tangent has nt = {tangent.nt} sun states, the series {sun.nt}")
+
+
+class SpectralNormalSeriesPlan(SpectralNormalPlan):
+    """The normal equations of :class:`SpectralNormalPlan` for the ``sun.nt`` sun states of every column, summed over the sun states, in
+    one call (``crt_hip_spectral_normal_series_f64``): ``y[k]``, ``inv_sigma[k]`` are ``(ncol, nt, nsel, nb)``, the parameter vector, the
+    directions and the canopy are shared over ``t``, and ``out["A"]``, ``out["g"]``, ``out["c2"]`` are the sums a retrieval from a diurnal
+    course consumes -- ONE block of ``crt_hip_lm_step_normal_f64`` whatever ``nt``.  ``per_step=True`` also keeps ``out["A_t"] (ncol, nt,
+    ntri)``, ``out["g_t"] (ncol, nt, npar)`` and ``out["c2_t"] (ncol, nt)``; ``fwd=True`` ``out["fwd"][k] (ncol, nt, nsel, nb)``.  Slice
+    ``[:, t]`` of those is bitwise what :class:`SpectralNormalPlan` gives with ``psi = sun.psi[:, t]`` (``g_at_psi`` likewise), the incoming
+    spectra of step ``t``, ``tangent.step(t)`` and the observations of step ``t``; the sums are bitwise the left-to-right sum of the slices
+    over ``t``.  An ``inv_sigma`` of 0 masks a band of a sun state (its ``y`` may be NaN); a sun state masked completely contributes ``+0``.
+    ``cols.psi``, ``cols.g_at_psi`` and ``bands.I_dr0 / I_df0`` are not read.  ``sun``: a float64 :class:`SunSeries`; ``tangent``: a
+    :class:`LeafTangentSeries` of the same ``nt`` or ``None``.  The canopy part of the column precompute and the side precomputes run once
+    per column; the workspace starts with the records of a :class:`LevelsSeriesPlan`, which can run on it with ``FLAG_SKIP_PRECOMPUTE``."""
+
+    _entry_name, _ws_query = "crt_hip_spectral_normal_series_f64", "crt_hip_spectral_normal_series_workspace_bytes"
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None,
+                 d_soil_r=None, lai=True, tangent=None, per_step=False, fwd=False, mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
+        _spectral_series_static(sun, tangent)
+        self._build(scheme, cols, bands, sun, levels, y, keys, inv_sigma, d_leaf_r, d_leaf_t, d_soil_r, lai, tangent, per_step, fwd, mu_s,
+                    tau_d_method, out, workspace)
+
+
+def spectral_normal_series(scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, y, *, keys, **kw):
+    """One-shot :class:`SpectralNormalSeriesPlan`: ``{"A", "g", "c2"}`` (``per_step=True``: and ``"A_t", "g_t", "c2_t"``; ``fwd=True``: and
+    ``"fwd"``) at the sorted levels."""
+    _spectral_series_static(sun, kw.get("tangent"))
+    k, _, npar = _spectral_static(scheme, y, keys, kw.get("inv_sigma"), kw.get("d_leaf_r"), kw.get("d_leaf_t"), kw.get("d_soil_r"),
+                                  kw.get("lai", True), kw.get("tangent") is not None, kw.get("tau_d_method", "quad"), bands, sun)
+    _spectral_shapes(cols, bands, levels, y, kw.get("inv_sigma"), len(k), npar, sun)  # (all before any device is touched)
+    with torch.cuda.device(cols.device):
+        return SpectralNormalSeriesPlan(scheme, cols, bands, sun, levels, y, keys=keys, **kw)()
 
 
 def _lm_options(lo, hi, npar, opts):
@@ -2526,18 +2598,23 @@ class SpectralRetrievalPlan:
     :meth:`step` is four launches in a row: ``k_retrieve_apply`` writes the working :class:`Columns` / :class:`Bands` from the trial
     point; ``crt_hip_g_dparam_f64`` refills the leaf-angle tangent; the :class:`SpectralNormalPlan` bound to the working tensors forms
     ``A``, ``g`` and ``c2``; ``crt_hip_lm_step_normal_f64`` decides.  Nothing the size of the spectrum is written, nothing is
-    allocated after construction and the host is never synchronised.  ``SPECTRAL_RETRIEVE_SCHEMES`` only; float64 only."""
+    allocated after construction and the host is never synchronised.  ``SPECTRAL_RETRIEVE_SCHEMES`` only; float64 only.
+
+    ``sun``: a float64 :class:`SunSeries` -- the diurnal course of a tower spectrometer, which separates LAI from the leaf angle: ``y[k]``,
+    ``inv_sigma[k]`` are ``(ncol, nt, nsel, nb)``, ONE parameter vector fits every sun state, and the four launches become
+    ``k_retrieve_apply``, ``crt_hip_g_dparam_series_f64`` into a :class:`LeafTangentSeries`, the :class:`SpectralNormalSeriesPlan` and
+    ``crt_hip_lm_step_normal_f64`` with its one block.  ``cols.psi`` and ``bands.I_dr0 / I_df0`` are not read then."""
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None,
-                 lai=True, leaf=False, p0=None, lo=None, hi=None, prior=None, inv_sigma_prior=None, mu_s=0.501, tau_d_method="quad",
-                 **options):
-        keys, ntan, npar = _spectral_static(scheme, y, keys, inv_sigma, d_leaf_r, d_leaf_t, d_soil_r, lai, leaf, tau_d_method, bands)
+                 lai=True, leaf=False, p0=None, lo=None, hi=None, prior=None, inv_sigma_prior=None, sun=None, mu_s=0.501,
+                 tau_d_method="quad", **options):
+        keys, ntan, npar = _spectral_static(scheme, y, keys, inv_sigma, d_leaf_r, d_leaf_t, d_soil_r, lai, leaf, tau_d_method, bands, sun)
         o = _lm_options(lo, hi, npar, options)
         if (prior is None) != (inv_sigma_prior is None):
             raise ValueError("prior and inv_sigma_prior go together")
-        _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), npar)
+        _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), npar, sun)
         self.lib = _lib.load()
-        self.scheme, self.keys, self.options = scheme, keys, o
+        self.scheme, self.keys, self.sun, self.options = scheme, keys, sun, o
         ncol, nz, nb, dev = cols.ncol, cols.nz, bands.nb, cols.device
         f64 = dict(dtype=torch.float64, device=dev)
         new = lambda *shape: torch.zeros(shape, **f64)  # noqa: E731
@@ -2548,14 +2625,20 @@ class SpectralRetrievalPlan:
         self.bands = Bands(rows(bands.I_dr0), rows(bands.I_df0), new(ncol, nb), new(ncol, nb), None if bands.soil_r is None else new(ncol, nb))
         self.cols = Columns(cols.psi, cols.lai.clone(), cols.g_kind, cols.g_param.clone(), cols.mla, cols.g_at_psi, cols.g_table)
         self.lai_scale = torch.ones((ncol,), **f64)
-        self.tangent = LeafTangent(new(ncol, _lib.NQ), new(ncol)) if leaf else None  # refilled in place every step
-        self.normal = SpectralNormalPlan(scheme, self.cols, self.bands, levels, y, keys=keys, inv_sigma=inv_sigma, d_leaf_r=d_leaf_r,
-                                         d_leaf_t=d_leaf_t, d_soil_r=d_soil_r, lai=bool(lai), tangent=self.tangent, fwd=True, mu_s=mu_s,
-                                         tau_d_method=tau_d_method)
+        self.tangent = None  # refilled in place every step
+        if leaf:
+            self.tangent = (LeafTangent(new(ncol, _lib.NQ), new(ncol)) if sun is None
+                            else LeafTangentSeries(new(ncol, _lib.NQ), new(ncol, sun.nt)))
+        d = dict(keys=keys, inv_sigma=inv_sigma, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r, lai=bool(lai), tangent=self.tangent,
+                 fwd=True, mu_s=mu_s, tau_d_method=tau_d_method)
+        if sun is None:
+            self.normal = SpectralNormalPlan(scheme, self.cols, self.bands, levels, y, **d)
+        else:
+            self.normal = SpectralNormalSeriesPlan(scheme, self.cols, self.bands, sun, levels, y, **d)
         self.normal.write_fwd = False
         self.params, self.levels, self.npar, self.ntan = self.normal.params, self.normal.levels, npar, ntan
         self.y, self.inv_sigma = self.normal.y, self.normal.inv_sigma
-        self.nrow = len(self.levels) * nb
+        self.nrow = (1 if sun is None else sun.nt) * len(self.levels) * nb
         self._dirs = self.normal._dirs
 
         def per_col(v, name, width=npar):
@@ -2595,6 +2678,7 @@ class SpectralRetrievalPlan:
         self._state = _lib.CrtLmState(*[ptr(v) for v in (self.p, self.p_trial, self.cost, self.lam, self.A, self.g, self.status, self.naccept,
                                                           self.nreject)])
         self._c = c.c_struct()
+        self._s = None if sun is None else sun.c_struct()
         self.reset()
 
     reset = RetrievalPlan.reset
@@ -2608,8 +2692,11 @@ class SpectralRetrievalPlan:
         lib, ref, h = self.lib, ctypes.byref, s.cuda_stream
         _lib.check(lib.crt_hip_retrieve_apply_f64(ref(ap), None if self._dirs is None else ref(self._dirs), h), "crt_hip_retrieve_apply_f64")
         t = self.tangent
-        if t is not None:
+        if t is not None and self.sun is None:
             _lib.check(lib.crt_hip_g_dparam_f64(ref(self._c), t.dg_table.data_ptr(), t.dg_at_psi.data_ptr(), h), "crt_hip_g_dparam_f64")
+        elif t is not None:
+            _lib.check(lib.crt_hip_g_dparam_series_f64(ref(self._c), ref(self._s), t.dg_table.data_ptr(), t.dg_at_psi.data_ptr(), h),
+                       "crt_hip_g_dparam_series_f64")
         self.normal(s)
 
     def step(self, stream=None):
@@ -2623,7 +2710,7 @@ class SpectralRetrievalPlan:
         return self
 
     def fitted(self, stream=None):
-        """``{key: (ncol, nsel, nb)}``: the model spectra at the accepted point ``p``, by one more evaluation there (copies).  The working
+        """``{key: (ncol, [nt,] nsel, nb)}``: the model spectra at the accepted point ``p``, by one more evaluation there (copies).  The working
         inputs are left at ``p``; the next :meth:`step` applies its trial point again."""
         dev = self.cols.device
         s = torch.cuda.current_stream(dev) if stream is None else stream
@@ -2640,11 +2727,11 @@ class SpectralRetrievalPlan:
 def retrieve_spectral(scheme, cols: Columns, bands: Bands, levels, y, *, keys, niter=20, **kw):
     """One-shot :class:`SpectralRetrievalPlan`: ``niter`` steps from ``p0``; what ``plan.result()`` returns, and ``"cov"``,
     ``plan.covariance()``."""
-    static = {k: kw[k] for k in ("inv_sigma", "d_leaf_r", "d_leaf_t", "d_soil_r", "lai", "leaf", "tau_d_method") if k in kw}
+    static = {k: kw[k] for k in ("inv_sigma", "d_leaf_r", "d_leaf_t", "d_soil_r", "lai", "leaf", "tau_d_method", "sun") if k in kw}
     k, _, npar = _spectral_static(scheme, y, keys, bands=bands, **static)  # (before any device is touched)
     _lm_options(kw.get("lo"), kw.get("hi"), npar, {n: v for n, v in kw.items() if n not in static and n not in
                                                   ("p0", "lo", "hi", "prior", "inv_sigma_prior", "mu_s")})
-    _spectral_shapes(cols, bands, levels, y, kw.get("inv_sigma"), len(k), npar)
+    _spectral_shapes(cols, bands, levels, y, kw.get("inv_sigma"), len(k), npar, kw.get("sun"))
     with torch.cuda.device(cols.device):
         plan = SpectralRetrievalPlan(scheme, cols, bands, levels, y, keys=keys, **kw).run(niter)
         res = plan.result()

@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "epilogue.hpp"
+#include "series/crt1d_hip_specfit_series.h"
 #include "specfit.hpp"
 
 namespace crt {
@@ -945,41 +946,47 @@ size_t crt_hip_spectral_normal_workspace_bytes(int scheme, int32_t ncol, int32_t
   return rec == 0 ? 0 : rec + spec_part_bytes(ncol, nb, nsel, nkey, npar);
 }
 
+// The parameter axis, the directions, the observations and the sums of both spectral entries -> sp (fwd: the four model spectra, in key
+// order; tangent_ok: the entry's tangent is NULL or whole).  false: an argument error.
+static bool spec_parse(const crt_bands* bands, const crt_optics_dirs* dirs, int with_lai, bool has_tangent, bool tangent_ok,
+                       const crt_spec_obs* obs, double* A, double* g, double* c2, double* const fwd[4], SpecArgs& sp) {
+  const int ntan = dirs ? dirs->ntan : 0;
+  bool args_ok = obs && A && g && c2 && bands && bands->nb > 0 && ntan >= 0 && ntan <= CRT_SENSJAC_MAX_NTAN &&
+                 (ntan == 0 || dirs->leaf_r || dirs->leaf_t || dirs->soil_r) &&
+                 (ntan == 0 || dirs->col_stride == 0 || dirs->col_stride == (int64_t)ntan * bands->nb) && tangent_ok;
+  sp.ntan = ntan;
+  sp.lai = with_lai ? 1 : 0;
+  sp.leaf = has_tangent ? 1 : 0;
+  args_ok = args_ok && sp.ntan + sp.lai + sp.leaf >= 1;
+  if (!args_ok) return false;
+  const double* const y[4] = {obs->y_I_dr, obs->y_I_df_d, obs->y_I_df_u, obs->y_F};
+  const double* const is[4] = {obs->inv_sigma_I_dr, obs->inv_sigma_I_df_d, obs->inv_sigma_I_df_u, obs->inv_sigma_F};
+  for (int q = 0; q < 4; ++q) {
+    if (!y[q]) continue;  // (not observed: its inv_sigma and fwd are not looked at)
+    sp.y[q] = y[q];
+    sp.is[q] = is[q];
+    sp.fwd[q] = fwd[q];
+    ++sp.nkey;
+  }
+  sp.A = A, sp.g = g, sp.c2 = c2;
+  if (ntan > 0) {
+    sp.d[0] = dirs->leaf_r;
+    sp.d[1] = dirs->leaf_t;
+    sp.d[2] = dirs->soil_r;
+    sp.dstride = dirs->col_stride;
+  }
+  return sp.nkey >= 1;
+}
+
 int crt_hip_spectral_normal_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
                                 int32_t nsel, const crt_optics_dirs* dirs, int with_lai, const crt_leaf_tangent* tangent,
                                 const crt_spec_obs* obs, const crt_spec_normal_out* out, void* workspace, size_t workspace_bytes,
                                 crt_stream_t stream) {
   SpecArgs sp = {};
-  const int ntan = dirs ? dirs->ntan : 0;
-  bool args_ok = obs && out && out->A && out->g && out->c2 && bands && bands->nb > 0 && ntan >= 0 && ntan <= CRT_SENSJAC_MAX_NTAN &&
-                 (ntan == 0 || dirs->leaf_r || dirs->leaf_t || dirs->soil_r) &&
-                 (ntan == 0 || dirs->col_stride == 0 || dirs->col_stride == (int64_t)ntan * bands->nb) &&
-                 (!tangent || (tangent->dg_table && tangent->dg_at_psi));
-  sp.ntan = ntan;
-  sp.lai = with_lai ? 1 : 0;
-  sp.leaf = tangent ? 1 : 0;
-  const int npar = ntan + sp.lai + sp.leaf;
-  args_ok = args_ok && npar >= 1;
-  if (args_ok) {
-    const double* const y[4] = {obs->y_I_dr, obs->y_I_df_d, obs->y_I_df_u, obs->y_F};
-    const double* const is[4] = {obs->inv_sigma_I_dr, obs->inv_sigma_I_df_d, obs->inv_sigma_I_df_u, obs->inv_sigma_F};
-    double* const fwd[4] = {out->fwd_I_dr, out->fwd_I_df_d, out->fwd_I_df_u, out->fwd_F};
-    for (int q = 0; q < 4; ++q) {
-      if (!y[q]) continue;  // (not observed: its inv_sigma and fwd are not looked at)
-      sp.y[q] = y[q];
-      sp.is[q] = is[q];
-      sp.fwd[q] = fwd[q];
-      ++sp.nkey;
-    }
-    args_ok = sp.nkey >= 1;
-    sp.A = out->A, sp.g = out->g, sp.c2 = out->c2;
-    if (ntan > 0) {
-      sp.d[0] = dirs->leaf_r;
-      sp.d[1] = dirs->leaf_t;
-      sp.d[2] = dirs->soil_r;
-      sp.dstride = dirs->col_stride;
-    }
-  }
+  double* const fwd[4] = {out ? out->fwd_I_dr : nullptr, out ? out->fwd_I_df_d : nullptr, out ? out->fwd_I_df_u : nullptr, out ? out->fwd_F : nullptr};
+  const bool args_ok = out && spec_parse(bands, dirs, with_lai, tangent != nullptr, !tangent || (tangent->dg_table && tangent->dg_at_psi), obs,
+                                         out->A, out->g, out->c2, fwd, sp);
+  const int npar = sp.ntan + sp.lai + sp.leaf;
   // (sizes that are not positive are an argument error of the shared path: no tail then)
   const bool sized = args_ok && cols && cols->ncol > 0 && cols->nz > 0;
   const bool side_lai = sized && sp.lai && dlai_side_len(scheme, cols->nz) > 0, side_leaf = args_ok && sp.leaf;
@@ -1002,6 +1009,56 @@ int crt_hip_spectral_normal_f64(int scheme, const crt_columns* cols, const crt_b
                                  s);
       },
       true, sized && sel_ok ? spec_part_bytes(cols->ncol, bands->nb, nsel, sp.nkey, npar) : 0);
+}
+
+// the sun-angle series of the two (series/crt1d_hip_specfit_series.h): the records of a level series, the side records, the slice sums of every
+// (column, t) -- always there: the sum over t goes through them
+size_t crt_hip_spectral_normal_series_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nt, int32_t nsel, int32_t nkey,
+                                                      int32_t npar) {
+  if (crt_hip_spectral_normal_workspace_bytes(scheme, ncol, nz, nb, nsel, nkey, npar) == 0) return 0;
+  const size_t rec = crt_hip_levels_series_workspace_bytes(scheme, ncol, nz, nt);
+  if (rec == 0) return 0;
+  const size_t sides = side_bytes(grad_side_len, scheme, ncol, nz), part = spec_series_part_bytes(ncol, nb, nsel, nkey, npar, nt);
+  return part > SIZE_MAX - rec - sides ? 0 : rec + sides + part;
+}
+
+int crt_hip_spectral_normal_series_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_sun_series* sun,
+                                       const crt_options* opts, const int32_t* levels, int32_t nsel, const crt_optics_dirs* dirs,
+                                       int with_lai, const crt_leaf_tangent_series* tangent, const crt_spec_obs* obs,
+                                       const crt_spec_series_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream) {
+  SpecArgs sp = {};
+  double* const fwd[4] = {out ? out->fwd_I_dr : nullptr, out ? out->fwd_I_df_d : nullptr, out ? out->fwd_I_df_u : nullptr, out ? out->fwd_F : nullptr};
+  const bool per_t = out && (out->A_t || out->g_t || out->c2_t);
+  const bool args_ok = sun && out && (!per_t || (out->A_t && out->g_t && out->c2_t)) &&
+                       spec_parse(bands, dirs, with_lai, tangent != nullptr, !tangent || (tangent->dg_table && tangent->dg_at_psi), obs, out->A,
+                                  out->g, out->c2, fwd, sp);
+  const SpecSeriesOut so = args_ok ? SpecSeriesOut{out->A_t, out->g_t, out->c2_t} : SpecSeriesOut{};
+  const DleafTan tn = tangent ? DleafTan{tangent->dg_table, tangent->dg_at_psi, tangent->dmla} : DleafTan{};
+  const int npar = sp.ntan + sp.lai + sp.leaf;
+  const bool sized = args_ok && cols && cols->ncol > 0 && cols->nz > 0 && sun->nt >= 1;
+  const bool side_lai = sized && sp.lai && dlai_side_len(scheme, cols->nz) > 0, side_leaf = args_ok && sp.leaf;
+  const bool sel_ok = nsel >= 1 && nsel <= CRT_MAX_LEVEL_SELECT;
+  const int nt = sun ? sun->nt : 1;
+  char pre[112];  // what a CRT_FLAG_PRECOMPUTE_ONLY call reports
+  std::snprintf(pre, sizeof pre, "k_colpre<canopy> + k_colsun nt=%d%s%s", nt, side_lai ? " + k_dlai_side" : "",
+                side_leaf ? " + k_dleaf_side<canopy>" : "");
+  return levels_deriv_impl(
+      scheme, cols, bands, opts, levels, nsel, workspace, workspace_bytes, stream, args_ok, grad_side_len, pre,
+      [&](const SolveArgs& sa, const LevArgs& la, const double* side, hipStream_t s, bool probe) {
+        sp.side_lai = side;
+        sp.side_leaf = side + (size_t)sa.ncol * dlai_side_len(scheme, sa.nz);
+        sp.part = const_cast<double*>(side) + (size_t)sa.ncol * grad_side_len(scheme, sa.nz);
+        const SeriesArgs sr = {nt, scheme, sa.nz, can_len(scheme, sa.nz), sun_len(scheme, sa.nz), sa.ws, sa.ws + (size_t)sa.ncol * can_len(scheme, sa.nz),
+                               sun->col_stride, sun->I_dr0, sun->I_df0};
+        return launch_spec_normal_series(scheme, sa, la, sp, so, sr, tangent ? tangent->dg_at_psi : nullptr, s, probe);
+      },
+      [&](const ColArgs& ca, double* side, hipStream_t s) {
+        if (side_lai)
+          if (const int st = launch_dlai_side(ca, side, s)) return st;
+        if (!side_leaf) return (int)CRT_OK;
+        return launch_dleaf_side(ca, tn, side + (size_t)ca.ncol * dlai_side_len(scheme, ca.nz), s, true);
+      },
+      true, sized && sel_ok ? spec_series_part_bytes(cols->ncol, bands->nb, nsel, sp.nkey, npar, nt) : 0, sun);
 }
 
 int crt_hip_bandsum_finish_f64(const crt_columns* cols, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream) {

@@ -3,7 +3,8 @@
 // derivative (dlai.hip) and the leaf-angle derivative (dleaf.hip) are contracted where they are formed: the Jacobian [nsel * nb][npar] of a
 // column, the eleven derivative arrays behind it and the level spectra are never written.
 //
-//  k_spec_normal         k_grad's mapping: lane <-> band, a workgroup owns one column and one band slice; the header with its leaf-angle
+//  k_spec_normal         (its body: spec_normal_body of specfit_body.hpp, shared with k_spec_normal_series of specfit_series.hip)
+//                        k_grad's mapping: lane <-> band, a workgroup owns one column and one band slice; the header with its leaf-angle
 //                        tangents and the selected record entries are staged in LDS once, a lane loads its band once and runs the passes of
 //                        deriv_passes.hpp one after the other, ONE tangent at a time -- the tangent bits of the single-derivative kernels
 //                        (-ffp-contract=off).  A lane keeps (w_0 .. w_{npar-1}, r) of every (observed key, level) in LDS entries that only
@@ -15,14 +16,13 @@
 //                          leaf angle   pass_record<Sch::F, LEAF>
 //                          weights      w_i = X'_i s, r = (X - y) s; a row with s == 0 becomes a row of +0
 //                        Then the (npar + 1)(npar + 2) / 2 entries of (A | g | c2) one at a time: the lane adds its products over (key, level),
-//                        block_sum (grad.hip's: butterfly, then the waves in ascending order) adds the lanes, thread 0 stores.  The 66 sums
+//                        spec_block_sum (grad.hip's block_sum: butterfly, then the waves in ascending order) adds the lanes, thread 0 stores.  The 66 sums
 //                        of npar = 10 are never live together: no accumulator sits in a register across a pass.
 //  k_spec_normal_finish  several band slices: a thread per (column, entry) adds the slice sums in ascending order (k_grad_finish's rule).
 //  k_lm_step_normal      k_lm_step (retrieve.hip) with the sums supplied instead of rows.  The scaled Cholesky and the solve are a second copy
 //                        of retrieve.hip's: sharing them would have meant editing that unit, whose device code is held to what it is.
 // No atomics anywhere: a column's result does not depend on the batch or on another column's mask.
-#include "deriv_passes.hpp"
-#include "specfit.hpp"
+#include "specfit_body.hpp"
 
 namespace crt {
 namespace {
@@ -46,178 +46,11 @@ __device__ inline void tri_pair(int e, int& i, int& j) {
   j = e - i * (i + 1) / 2;
 }
 
-// the sum of v over the workgroup in a fixed order, valid in thread 0 (every thread calls): butterfly over the wave, then wave 0, 1, ...
-// (grad.hip's block_sum)
-__device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  const int tid = threadIdx.x;
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  double s = red[0];
-  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) s += red[w];
-  __syncthreads();  // (red is used again)
-  return s;
-}
-
+// The body (specfit_body.hpp) on the record k_colpre wrote: one column and one band slice per workgroup.
 template <class G, bool BL>
 __global__ __launch_bounds__(SPEC_BLOCK) void k_spec_normal(SolveArgs a, LevArgs la, SpecArgs sp, int per) {
-  using SJ = typename G::J;
-  extern __shared__ double rows[];          // [nkey][nsel][npar + 1][blockDim.x]
-  __shared__ double hd[HDR_TAN + REC_HDR];  // k_dleaf's layout: header | e^{-K_b LT} at the ground | ... | the header's leaf-angle tangents
-  __shared__ double lvL[CRT_MAX_LEVEL_SELECT], lvE[CRT_MAX_LEVEL_SELECT], lvTs[CRT_MAX_LEVEL_SELECT], lvTh[CRT_MAX_LEVEL_SELECT];
-  __shared__ double lvTd[CRT_MAX_LEVEL_SELECT];  // bl: tau_d(L_j), the sky term of the primal
-  __shared__ double red[SPEC_BLOCK / 64];
-  const int c = blockIdx.x, nz = a.nz, nb = a.nb, nsel = la.nsel, tid = threadIdx.x, nthr = blockDim.x;
-  const int b = blockIdx.y * per + tid;
-  const bool live = tid < per && b < nb;
-  const int ntan = sp.ntan, npar = ntan + sp.lai + sp.leaf, na = npar + 1;
-  // k_grad's staging: the tangents of both record derivatives at once
-  const double* rec = a.ws + (long long)c * a.reclen;
-  const double* sdl = sp.side_leaf + (long long)c * (REC_HDR + (BL ? nz : 0));
-  if (tid < REC_HDR) {
-    hd[tid] = rec[tid];
-    hd[HDR_TAN + tid] = sp.leaf ? sdl[tid] : 0.0;
-  }
-  if (tid == REC_HDR) hd[REC_HDR] = rec[REC_HDR + nz];  // e^{-K_b L} at the ground
-  for (int r = tid; r < nsel; r += nthr) {
-    const int j = la.lev[r];
-    lvL[r] = rec[REC_HDR + j];
-    lvE[r] = rec[REC_HDR + nz + j];
-    if constexpr (BL) {
-      lvTs[r] = sp.lai ? sp.side_lai[(long long)c * nz + j] : 0.0;  // L_j tau_d'(L_j)
-      lvTh[r] = sp.leaf ? sdl[REC_HDR + j] : 0.0;                   // tau_d^th(L_j)
-      lvTd[r] = rec[REC_HDR + 2 * nz + j];
-    }
-  }
-  __syncthreads();
-  const double invmu = hd[S_INVMU];
-  const long long o0 = (long long)c * nsel * nb + b;  // row r of the observations: + r nb
-  double* const my = rows + tid;                      // entry i of (key kq, level r): my[((kq nsel + r) na + i) nthr]
-  const size_t lev = (size_t)na * nthr, key = lev * nsel;
-
-  if (live) {
-    const DBand in = load_dband(a, c, b, SJ::SOIL);
-
-    // ---- the primal: the closed form the passes below differentiate, no parameter seeded ----
-    pass_optics<SJ>(hd, lvL, lvE, nsel, seed_band(in, -1), [&](int r, Du dn, Du up) {
-      const double idr = in.I_dr0 * lvE[r];
-      double d = dn.v;
-      if constexpr (BL) d = in.I_df0 * lvTd[r] + d;  // the sky term I_df0 tau_d(L_j)
-      const double x[4] = {idr, d, up.v, __builtin_fma(idr, invmu, 2 * (up.v + d))};
-      double* y = my + r * lev + (size_t)npar * nthr;
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (sp.y[q]) {
-          *y = x[q];
-          if (sp.fwd[q]) sp.fwd[q][o0 + (long long)r * nb] = x[q];
-          y += key;
-        }
-    });
-
-    // ---- the directions: the optics one parameter at a time (k_jac), each tangent times the lane's band of every direction ----
-    if (ntan > 0) {
-      bool first = true;  // (uniform)
-      for (int p = 0; p < CRT_JAC_NPARAM; ++p) {
-        if (!sp.d[p] || (!SJ::SOIL && p == 2)) continue;  // (bl has no soil)
-        const double* dp = sp.d[p] + (long long)c * sp.dstride + b;
-        double d[CRT_SENSJAC_MAX_NTAN];
-#pragma unroll
-        for (int k = 0; k < CRT_SENSJAC_MAX_NTAN; ++k) d[k] = k < ntan ? dp[(long long)k * nb] : 0.0;
-        pass_optics<SJ>(hd, lvL, lvE, nsel, seed_band(in, p), [&](int r, Du dn, Du up) {
-          const double x[4] = {0.0, dn.d, up.d, 2 * (up.d + dn.d)};  // F' as jac_store; I_dr does not depend on the optics
-          double* y = my + r * lev;
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            if (sp.y[q]) {
-#pragma unroll
-              for (int k = 0; k < CRT_SENSJAC_MAX_NTAN; ++k)
-                if (k < ntan) {
-                  double* const e = y + (size_t)k * nthr;
-                  if (q == 0) {
-                    if (first) *e = 0.0;
-                  } else {
-                    const double t = x[q] * d[k];
-                    *e = first ? t : *e + t;
-                  }
-                }
-              y += key;
-            }
-        });
-        first = false;
-      }
-      if (first)  // (bl with directions in soil_r alone: zeros)
-        for (int t = 0; t < sp.nkey * nsel; ++t)
-          for (int k = 0; k < ntan; ++k) my[t * lev + (size_t)k * nthr] = 0.0;
-    }
-
-    // ---- the LAI (k_dlai) ----
-    if (sp.lai)
-      pass_record<typename G::D, BL, false>(hd, lvL, lvE, lvTs, nsel, in, [&](int r, double dI, Du dn, Du up) {
-        const double x[4] = {dI, dn.d, up.d, flux_tan(dI, invmu, dn, up)};
-        double* y = my + r * lev + (size_t)ntan * nthr;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          if (sp.y[q]) {
-            *y = x[q];
-            y += key;
-          }
-      });
-
-    // ---- the leaf angles (k_dleaf) ----
-    if (sp.leaf)
-      pass_record<typename G::F, BL, true>(hd, lvL, lvE, lvTh, nsel, in, [&](int r, double dI, Du dn, Du up) {
-        const double x[4] = {dI, dn.d, up.d, flux_tan(dI, invmu, dn, up)};
-        double* y = my + r * lev + (size_t)(ntan + sp.lai) * nthr;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          if (sp.y[q]) {
-            *y = x[q];
-            y += key;
-          }
-      });
-
-    // ---- the weights: w_i = X'_i s and r = (X - y) s, each rounded once; a skipped row becomes a row of +0 ----
-    for (int r = 0; r < nsel; ++r) {
-      const long long o = o0 + (long long)r * nb;
-      double* y = my + r * lev;
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (sp.y[q]) {
-          const double s = sp.is[q] ? sp.is[q][o] : 1.0;
-          if (s != 0.0) {
-            for (int i = 0; i < npar; ++i) y[(size_t)i * nthr] = y[(size_t)i * nthr] * s;
-            y[(size_t)npar * nthr] = (y[(size_t)npar * nthr] - sp.y[q][o]) * s;
-          } else {
-            for (int i = 0; i <= npar; ++i) y[(size_t)i * nthr] = 0.0;
-          }
-          y += key;
-        }
-    }
-  }
-
-  // ---- (A | g | c2), one entry at a time: the products of a lane in the order (key, level), then the lanes ----
-  const int ntri = npar * (npar + 1) / 2, nent = na * (na + 1) / 2, nrow = sp.nkey * nsel, nslice = gridDim.y;
-  double* const dst = nslice == 1 ? nullptr : sp.part + ((long long)c * nslice + blockIdx.y) * nent;
-  int i = 0, j = 0;
-  for (int e = 0; e < nent; ++e) {
-    double acc = 0.0;
-    if (live) {
-      const double *yi = my + (size_t)i * nthr, *yj = my + (size_t)j * nthr;
-      for (int t = 0; t < nrow; ++t) acc = acc + yi[t * lev] * yj[t * lev];
-    }
-    const double s = block_sum(acc, red);
-    if (tid == 0) {
-      if (dst) dst[e] = s;
-      else if (e < ntri) sp.A[(long long)c * ntri + e] = s;
-      else if (e < ntri + npar) sp.g[(long long)c * npar + e - ntri] = s;
-      else sp.c2[c] = s;
-    }
-    if (++j > i) {
-      ++i;
-      j = 0;
-    }
-  }
+  const int c = blockIdx.x;
+  spec_normal_body<G, BL, false>(a, la, sp, per, c, blockIdx.y, c, SpecRecStep{a.ws + (long long)c * a.reclen, a.nz}, 0);
 }
 
 // One thread per (column, entry): the slice sums in ascending slice order, starting from slice 0's bits.

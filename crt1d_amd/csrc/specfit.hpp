@@ -43,4 +43,20 @@ inline size_t spec_part_bytes(int ncol, int nb, int nsel, int nkey, int npar) {
 // probe: return the status (CRT_OK / CRT_ERR_UNSUPPORTED) of the configuration without launching anything
 int launch_spec_normal(int scheme, const SolveArgs& a, const LevArgs& la, const SpecArgs& sp, hipStream_t s, bool probe);
 
+// The sun-angle series (include/series/crt1d_hip_specfit_series.h; kernels in specfit_series.hip).  sp: y / is / fwd are indexed by
+// c * nt + t, A / g / c2 are the sums over t, part is [ncol][nt][nslice][nent] and ALWAYS there: the sum over t goes through it.
+struct SpecSeriesOut {
+  double *A_t, *g_t, *c2_t;  // [ncol][nt][ntri], [ncol][nt][npar], [ncol][nt], or all NULL
+};
+// bytes of the slice sums of every (column, t), one slice included; SIZE_MAX: beyond size_t
+inline size_t spec_series_part_bytes(int ncol, int nb, int nsel, int nkey, int npar, int nt) {
+  LevSlices ls = spec_slices(nb, nsel, nkey, npar);
+  if (ls.nslice == 0) ls = lev_slices(nb, 64);
+  const size_t per = (size_t)ls.nslice * spec_nent(npar) * sizeof(double), nv = (size_t)ncol * (size_t)nt;
+  return nv > SIZE_MAX / per ? SIZE_MAX : nv * per;
+}
+// a.ws / sr.can hold canopy records, side_leaf comes from launch_dleaf_side(.., canopy = true), dg_at_psi is [ncol][nt] (or nullptr)
+int launch_spec_normal_series(int scheme, const SolveArgs& a, const LevArgs& la, const SpecArgs& sp, const SpecSeriesOut& so,
+                              const SeriesArgs& sr, const double* dg_at_psi, hipStream_t s, bool probe);
+
 }  // namespace crt

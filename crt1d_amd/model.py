@@ -479,11 +479,14 @@ class Model:
         out["params"] = res["params"]
         return out
 
-    def retrieve_spectral(self, y, levels=(-1,), directions=None, lai=True, wrt_leaf=None, niter=20, **lm_options):
+    def retrieve_spectral(self, y, levels=(-1,), directions=None, lai=True, wrt_leaf=None, niter=20, psi=None, I_dr0_all=None,
+                          I_df0_all=None, **lm_options):
         """:meth:`retrieve` from the level spectra themselves, band by band (:class:`crt1d_amd.batched.SpectralRetrievalPlan`,
         ``ncol = 1``): ``y``: ``{key: (nsel, n_wl)}`` for keys out of ``"I_dr", "I_df_d", "I_df_u", "F"``, the observed spectra at
-        ``levels`` (default: the canopy top).  ``directions``, ``lai``, ``wrt_leaf`` as for :meth:`retrieve`.  ``lm_options``: ``p0``,
-        ``lo``, ``hi``, ``prior``, ``inv_sigma_prior`` (each ``(npar,)``), ``inv_sigma`` (as ``y``; 0 masks a band) and the options of the
+        ``levels`` (default: the canopy top); with ``psi`` (a series of sun angles, and ``I_dr0_all`` / ``I_df0_all`` as for
+        :meth:`run_series`) ``{key: (nt, nsel, n_wl)}``, the spectra of every sun state, fitted by ONE parameter vector
+        (:class:`crt1d_amd.batched.SpectralNormalSeriesPlan`).  ``directions``, ``lai``, ``wrt_leaf`` as for :meth:`retrieve`.
+        ``lm_options``: ``p0``, ``lo``, ``hi``, ``prior``, ``inv_sigma_prior`` (each ``(npar,)``), ``inv_sigma`` (as ``y``; 0 masks a band) and the options of the
         plan.  Returns what :meth:`retrieve` returns.  ValueError for the schemes outside
         ``batched.SPECTRAL_RETRIEVE_SCHEMES``.  The model's own state is not changed."""
         from . import batched
@@ -493,16 +496,21 @@ class Model:
         name = self.scheme["name"] if self.scheme.get("name") in _lib.SCHEME_IDS else self.scheme.get("short_name")
         if name not in batched.SPECTRAL_RETRIEVE_SCHEMES:  # (before any device is touched)
             raise ValueError(f"scheme {name!r} has no spectral retrieval; served: " + ", ".join(batched.SPECTRAL_RETRIEVE_SCHEMES))
+        series = psi is not None
         one = np.atleast_1d(float(self._p["psi"]))
-        scheme, cols, b, sun = self._series_inputs(one, None, None, "spectral retrieval")
+        scheme, cols, b, sun = self._series_inputs(psi if series else one, *((I_dr0_all, I_df0_all) if series else (None, None)),
+                                                   "spectral retrieval")
         directions = {} if directions is None else dict(directions)
         if any(k not in batched.JAC_PARAMS for k in directions):
             raise ValueError(f"directions must be a dict of (ntan, n_wl) arrays under keys out of {batched.JAC_PARAMS}")
         if wrt_leaf not in (None, "param"):
             raise ValueError(f"wrt_leaf must be None or 'param', got {wrt_leaf!r}")
-        cols = batched.Columns(psi=sun.psi[:, 0].contiguous(), lai=cols.lai, g_kind=cols.g_kind, g_param=cols.g_param, mla=cols.mla,
-                               g_at_psi=None if sun.g_at_psi is None else sun.g_at_psi[:, 0].contiguous(), g_table=cols.g_table)
-        b = batched.Bands(sun.I_dr0[:, 0].contiguous(), sun.I_df0[:, 0].contiguous(), b.leaf_r, b.leaf_t, b.soil_r)
+        if not series:
+            cols = batched.Columns(psi=sun.psi[:, 0].contiguous(), lai=cols.lai, g_kind=cols.g_kind, g_param=cols.g_param, mla=cols.mla,
+                                   g_at_psi=None if sun.g_at_psi is None else sun.g_at_psi[:, 0].contiguous(), g_table=cols.g_table)
+            b = batched.Bands(sun.I_dr0[:, 0].contiguous(), sun.I_df0[:, 0].contiguous(), b.leaf_r, b.leaf_t, b.soil_r)
+        else:
+            lm_options["sun"] = sun
         d = {"d_" + k: np.ascontiguousarray(v, dtype=np.float64) for k, v in directions.items()}
         keys = tuple(k for k in batched.LEVEL_KEYS if k in y)
         lead = lambda v: {k: np.asarray(a, dtype=np.float64)[None] for k, a in v.items()}  # noqa: E731
