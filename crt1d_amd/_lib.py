@@ -530,6 +530,26 @@ def _specfit_series_signatures():
 _SPECFIT_SERIES_SIGNATURES = _specfit_series_signatures()
 SPECFIT_SERIES_EXPORTS = list(_SPECFIT_SERIES_SIGNATURES)
 
+# the generalised plate model of leaf optics (include_ext/crt1d_hip_leafmodel.h): the leaf model behind the leaf directions of a retrieval;
+# again a header and a table of their own
+PLATE_MAX_NABS = SENSJAC_MAX_NTAN - 1  # CRT_PLATE_MAX_NABS
+PLATE_K_MIN, PLATE_K_MAX = 1e-6, 100.0  # CRT_PLATE_K_MIN, CRT_PLATE_K_MAX
+
+
+class CrtPlateLeafModel(ctypes.Structure):
+    """``crt_plate_leaf_model``: the sizes and the per-band spectra of the model, device pointers."""
+
+    _fields_ = [(k, ctypes.c_int32) for k in ("ncol", "nb", "nabs")] + [(k, _vp) for k in ("kspec", "t_alpha", "t_90", "n")]
+
+
+def _leafmodel_signatures():
+    i32, i64, ok = ctypes.c_int32, ctypes.c_int64, ctypes.c_int
+    return {"crt_hip_plate_leaf_f64": (ok, [ctypes.POINTER(CrtPlateLeafModel), _vp, i64, _vp, _vp, i32, _vp, _vp, _vp])}
+
+
+_LEAFMODEL_SIGNATURES = _leafmodel_signatures()
+LEAFMODEL_EXPORTS = list(_LEAFMODEL_SIGNATURES)
+
 _lib = None
 
 
@@ -555,7 +575,7 @@ def load():
     for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES, **_SENSOR_SIGNATURES, **_JAC_SIGNATURES,
                                       **_DLAI_SIGNATURES, **_DLEAF_SIGNATURES, **_GRAD_SIGNATURES, **_SENSJAC_SIGNATURES,
                                       **_SENSJAC_SERIES_SIGNATURES, **_RETRIEVE_SIGNATURES, **_SPECFIT_SIGNATURES,
-                                      **_SPECFIT_SERIES_SIGNATURES}.items():
+                                      **_SPECFIT_SERIES_SIGNATURES, **_LEAFMODEL_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:

@@ -2127,7 +2127,7 @@ LM_OPTIONS = dict(lam0=1e-2, lam_up=10.0, lam_down=0.1, lam_min=1e-12, lam_max=1
 
 
 def _retrieve_static(scheme, sensors, y, keys, sun=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, leaf=False, lo=None,
-                     hi=None, inv_sigma=None, tau_d_method="quad", bands=None, **opts):
+                     hi=None, inv_sigma=None, tau_d_method="quad", bands=None, leaf_model=None, **opts):
     """The checks of a :class:`RetrievalPlan` that touch no device.  -> (keys, ntan, npar, LM options)"""
     import numpy as np
 
@@ -2148,7 +2148,7 @@ def _retrieve_static(scheme, sensors, y, keys, sun=None, d_leaf_r=None, d_leaf_t
             raise ValueError(f"{name} has the keys {extra}, which are not in keys = {keys}")
     if missing := [k for k in keys if k not in y]:
         raise ValueError(f"y lacks the keys {missing} of keys = {keys}")
-    ntan = _sensjac_ntan(d_leaf_r, d_leaf_t, d_soil_r)
+    ntan = _sensjac_ntan(d_leaf_r, d_leaf_t, d_soil_r) if leaf_model is None else _leaf_model_ntan(leaf_model, d_leaf_r, d_leaf_t, d_soil_r)
     npar = ntan + bool(lai) + bool(leaf)
     if npar == 0:
         raise ValueError("no parameter at all: give a direction, lai=True or leaf=True")
@@ -2185,13 +2185,24 @@ class RetrievalPlan:
     bound to the working tensors; the forward sums on its workspace with ``FLAG_SKIP_PRECOMPUTE``; ``k_lm_step``.  The first step
     evaluates ``p0`` and is always accepted.  n79 and zq run the composed Jacobian plan (workspaces and allocations of its own) and the
     forward plan with its own precompute; ``4s`` and ``zq_pa`` are a ValueError.  A column's state is bitwise the same alone or in any
-    batch.  float64 only."""
+    batch.  float64 only.
+
+    ``leaf_model``: a :class:`crt1d_amd.leaf_model.PlateLeafModel` -- the leaf spectra are the plate model's, and its ``nm`` parameters
+    ``leaf_model.params`` = ``("N", contents...)`` are retrieved in place of coefficients of leaf directions.  The parameter axis is then
+    the model's parameters, the ``ns`` soil directions ``d_soil_r`` (``"dir0"``, ...), ``"lai"``, ``"leaf"``, with ``nm + ns <= 8``;
+    ``d_leaf_r`` / ``d_leaf_t`` are a ValueError; ``lo`` / ``hi`` are required and must keep ``N`` inside [1, 4] and every content
+    ``>= 0``; ``p0`` is required; ``bands.leaf_r / leaf_t`` are not used.  The plan owns per-column direction arrays of ``nm + ns`` rows
+    (``3 x ncol x (nm + ns) x nb x 8`` bytes), and :meth:`step` is one launch more: ``k_retrieve_apply`` with the leaf directions left out,
+    then ``crt_hip_plate_leaf_f64`` on the same parameter array, which writes the working leaf spectra and the model's partials into
+    the leaf rows, then the launches above."""
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, y, *, keys, sun=None, d_leaf_r=None, d_leaf_t=None,
                  d_soil_r=None, lai=True, leaf=False, p0=None, lo=None, hi=None, inv_sigma=None, prior=None, inv_sigma_prior=None,
-                 mu_s=0.501, tau_d_method="quad", **options):
+                 leaf_model=None, mu_s=0.501, tau_d_method="quad", **options):
         keys, ntan, npar, o = _retrieve_static(scheme, sensors, y, keys, sun, d_leaf_r, d_leaf_t, d_soil_r, lai, leaf, lo, hi, inv_sigma,
-                                               tau_d_method, bands, **options)
+                                               tau_d_method, bands, leaf_model, **options)
+        if leaf_model is not None:
+            _leaf_model_start(leaf_model, lo, hi, p0)
         if (prior is None) != (inv_sigma_prior is None):
             raise ValueError("prior and inv_sigma_prior go together")
         self.lib = _lib.load()
@@ -2211,6 +2222,11 @@ class RetrievalPlan:
         if leaf:
             self.tangent = (LeafTangent(new(ncol, _lib.NQ), new(ncol)) if sun is None
                             else LeafTangentSeries(new(ncol, _lib.NQ), new(ncol, sun.nt)))
+        # the leaf model: the plan owns the per-column directions k_plate_leaf writes and the Jacobian plan reads
+        self.leaf_model = leaf_model
+        self._leaf = None if leaf_model is None else _PlateLeafBinding(leaf_model, ncol, nb, d_soil_r, dev)
+        if self._leaf is not None:
+            d_leaf_r, d_leaf_t, d_soil_r = self._leaf.d_leaf_r, self._leaf.d_leaf_t, self._leaf.d_soil_r
         d = dict(d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r, lai=bool(lai), tangent=self.tangent, keys=keys, mu_s=mu_s,
                  tau_d_method=tau_d_method)
         f = dict(keys=keys, mu_s=mu_s, tau_d_method=tau_d_method)
@@ -2225,7 +2241,11 @@ class RetrievalPlan:
         self.params, self.levels, self.npar, self.ntan = self.jac.params, self.jac.levels, npar, ntan
         assert len(self.params) == npar
         self._dirs = None
-        if ntan:
+        if self._leaf is not None:
+            self._leaf.bound_to(self.jac)
+            self.params = self._leaf.names + self.params[ntan:]
+            self._dirs = self._leaf.apply_dirs
+        elif ntan:
             by_col = ncol != 1 and any(v.shape[0] != 1 for v in self.jac.dirs.values())
             self._dirs = _lib.CrtOpticsDirs(ntan, ntan * nb if by_col else 0,
                                             *[self.jac.dirs[n].data_ptr() if n in self.jac.dirs else None for n in JAC_PARAMS])
@@ -2303,6 +2323,8 @@ class RetrievalPlan:
         with torch.cuda.device(dev):
             _lib.check(lib.crt_hip_retrieve_apply_f64(ref(self._ap), None if self._dirs is None else ref(self._dirs), h),
                        "crt_hip_retrieve_apply_f64")
+            if self._leaf is not None:
+                self._leaf.launch(lib, self._ap.p, self.npar, self.bands, h)
             t = self.tangent
             if t is not None and self.sun is None:
                 _lib.check(lib.crt_hip_g_dparam_f64(ref(self._c), t.dg_table.data_ptr(), t.dg_at_psi.data_ptr(), h), "crt_hip_g_dparam_f64")
@@ -2354,6 +2376,8 @@ def retrieve(scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, y,
     """One-shot :class:`RetrievalPlan`: ``niter`` steps from ``p0``; what ``plan.result()`` returns, and ``"cov"``, ``plan.covariance()``."""
     static = {k: v for k, v in kw.items() if k not in ("p0", "prior", "inv_sigma_prior", "mu_s")}
     _retrieve_static(scheme, sensors, y, keys, bands=bands, **static)  # (before any device is touched)
+    if kw.get("leaf_model") is not None:
+        _leaf_model_start(kw["leaf_model"], kw.get("lo"), kw.get("hi"), kw.get("p0"))
     with torch.cuda.device(cols.device):
         plan = RetrievalPlan(scheme, cols, bands, levels, sensors, y, keys=keys, **kw).run(niter)
         res = plan.result()
@@ -2374,7 +2398,7 @@ def spectral_normal_workspace_bytes(scheme, ncol, nz, nb, nsel, nkey, npar):
 
 
 def _spectral_static(scheme, y, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, leaf=False,
-                     tau_d_method="quad", bands=None, sun=None):
+                     tau_d_method="quad", bands=None, sun=None, leaf_model=None):
     """The checks of the spectral plans that touch no device (``sun``: the series forms, whose arrays carry a sun-state axis).
     -> (keys in ``LEVEL_KEYS`` order, ntan, npar)"""
     import numpy as np
@@ -2404,7 +2428,7 @@ def _spectral_static(scheme, y, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=No
         raise ValueError(f"y lacks the keys {missing} of keys = {keys}")
     if len(shapes) > 1:
         raise ValueError(f"the arrays of y and inv_sigma must share one shape {axes}, got {sorted(shapes)}")
-    ntan = _sensjac_ntan(d_leaf_r, d_leaf_t, d_soil_r)
+    ntan = _sensjac_ntan(d_leaf_r, d_leaf_t, d_soil_r) if leaf_model is None else _leaf_model_ntan(leaf_model, d_leaf_r, d_leaf_t, d_soil_r)
     npar = ntan + bool(lai) + bool(leaf)
     if npar == 0:
         raise ValueError("no parameter at all: give a direction, lai=True or a leaf-angle tangent")
@@ -2603,13 +2627,20 @@ class SpectralRetrievalPlan:
     ``sun``: a float64 :class:`SunSeries` -- the diurnal course of a tower spectrometer, which separates LAI from the leaf angle: ``y[k]``,
     ``inv_sigma[k]`` are ``(ncol, nt, nsel, nb)``, ONE parameter vector fits every sun state, and the four launches become
     ``k_retrieve_apply``, ``crt_hip_g_dparam_series_f64`` into a :class:`LeafTangentSeries`, the :class:`SpectralNormalSeriesPlan` and
-    ``crt_hip_lm_step_normal_f64`` with its one block.  ``cols.psi`` and ``bands.I_dr0 / I_df0`` are not read then."""
+    ``crt_hip_lm_step_normal_f64`` with its one block.  ``cols.psi`` and ``bands.I_dr0 / I_df0`` are not read then.
+
+    ``leaf_model``: as for :class:`RetrievalPlan` -- the parameters of a :class:`crt1d_amd.leaf_model.PlateLeafModel`, then the soil
+    directions, ``"lai"``, ``"leaf"``; one launch more per :meth:`step` (and per :meth:`fitted`), ``crt_hip_plate_leaf_f64`` behind
+    ``k_retrieve_apply``, with or without ``sun``."""
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None,
-                 lai=True, leaf=False, p0=None, lo=None, hi=None, prior=None, inv_sigma_prior=None, sun=None, mu_s=0.501,
+                 lai=True, leaf=False, p0=None, lo=None, hi=None, prior=None, inv_sigma_prior=None, sun=None, leaf_model=None, mu_s=0.501,
                  tau_d_method="quad", **options):
-        keys, ntan, npar = _spectral_static(scheme, y, keys, inv_sigma, d_leaf_r, d_leaf_t, d_soil_r, lai, leaf, tau_d_method, bands, sun)
+        keys, ntan, npar = _spectral_static(scheme, y, keys, inv_sigma, d_leaf_r, d_leaf_t, d_soil_r, lai, leaf, tau_d_method, bands, sun,
+                                            leaf_model)
         o = _lm_options(lo, hi, npar, options)
+        if leaf_model is not None:
+            _leaf_model_start(leaf_model, lo, hi, p0)
         if (prior is None) != (inv_sigma_prior is None):
             raise ValueError("prior and inv_sigma_prior go together")
         _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), npar, sun)
@@ -2629,6 +2660,11 @@ class SpectralRetrievalPlan:
         if leaf:
             self.tangent = (LeafTangent(new(ncol, _lib.NQ), new(ncol)) if sun is None
                             else LeafTangentSeries(new(ncol, _lib.NQ), new(ncol, sun.nt)))
+        # the leaf model: the plan owns the per-column directions k_plate_leaf writes and the normal plan reads
+        self.leaf_model = leaf_model
+        self._leaf = None if leaf_model is None else _PlateLeafBinding(leaf_model, ncol, nb, d_soil_r, dev)
+        if self._leaf is not None:
+            d_leaf_r, d_leaf_t, d_soil_r = self._leaf.d_leaf_r, self._leaf.d_leaf_t, self._leaf.d_soil_r
         d = dict(keys=keys, inv_sigma=inv_sigma, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r, lai=bool(lai), tangent=self.tangent,
                  fwd=True, mu_s=mu_s, tau_d_method=tau_d_method)
         if sun is None:
@@ -2640,6 +2676,10 @@ class SpectralRetrievalPlan:
         self.y, self.inv_sigma = self.normal.y, self.normal.inv_sigma
         self.nrow = (1 if sun is None else sun.nt) * len(self.levels) * nb
         self._dirs = self.normal._dirs
+        if self._leaf is not None:
+            self._leaf.bound_to(self.normal)
+            self.params = self._leaf.names + self.params[ntan:]
+            self._dirs = self._leaf.apply_dirs
 
         def per_col(v, name, width=npar):
             v = torch.as_tensor(v, dtype=torch.float64).to(dev)
@@ -2691,6 +2731,8 @@ class SpectralRetrievalPlan:
         """The working inputs from the parameters behind ``ap``, the tangent refill and the normal plan, on stream ``s``."""
         lib, ref, h = self.lib, ctypes.byref, s.cuda_stream
         _lib.check(lib.crt_hip_retrieve_apply_f64(ref(ap), None if self._dirs is None else ref(self._dirs), h), "crt_hip_retrieve_apply_f64")
+        if self._leaf is not None:
+            self._leaf.launch(lib, ap.p, self.npar, self.bands, h)
         t = self.tangent
         if t is not None and self.sun is None:
             _lib.check(lib.crt_hip_g_dparam_f64(ref(self._c), t.dg_table.data_ptr(), t.dg_at_psi.data_ptr(), h), "crt_hip_g_dparam_f64")
@@ -2727,11 +2769,13 @@ class SpectralRetrievalPlan:
 def retrieve_spectral(scheme, cols: Columns, bands: Bands, levels, y, *, keys, niter=20, **kw):
     """One-shot :class:`SpectralRetrievalPlan`: ``niter`` steps from ``p0``; what ``plan.result()`` returns, and ``"cov"``,
     ``plan.covariance()``."""
-    static = {k: kw[k] for k in ("inv_sigma", "d_leaf_r", "d_leaf_t", "d_soil_r", "lai", "leaf", "tau_d_method", "sun") if k in kw}
+    static = {k: kw[k] for k in ("inv_sigma", "d_leaf_r", "d_leaf_t", "d_soil_r", "lai", "leaf", "tau_d_method", "sun", "leaf_model") if k in kw}
     k, _, npar = _spectral_static(scheme, y, keys, bands=bands, **static)  # (before any device is touched)
     _lm_options(kw.get("lo"), kw.get("hi"), npar, {n: v for n, v in kw.items() if n not in static and n not in
                                                   ("p0", "lo", "hi", "prior", "inv_sigma_prior", "mu_s")})
     _spectral_shapes(cols, bands, levels, y, kw.get("inv_sigma"), len(k), npar, kw.get("sun"))
+    if kw.get("leaf_model") is not None:
+        _leaf_model_start(kw["leaf_model"], kw.get("lo"), kw.get("hi"), kw.get("p0"))
     with torch.cuda.device(cols.device):
         plan = SpectralRetrievalPlan(scheme, cols, bands, levels, y, keys=keys, **kw).run(niter)
         res = plan.result()
@@ -2801,3 +2845,128 @@ def solve_levels_ad(scheme, cols: Columns, bands: Bands, levels, *, keys=LEVEL_K
     with torch.cuda.device(cols.device):
         out = _LevelsAD.apply(st, bands.leaf_r, bands.leaf_t, bands.soil_r, lai_scale, cols.g_param)
     return dict(zip(keys, out))
+
+
+# ---- the generalised plate model of leaf optics (include_ext/crt1d_hip_leafmodel.h) ---------------------------------------------------------
+
+PLATE_LEAF_KEYS = ("leaf_r", "leaf_t", "d_leaf_r", "d_leaf_t")
+
+
+def _plate_leaf_static(model, q, partials, out):
+    """The checks of :func:`plate_leaf_optics` that touch no device.  -> ntan of the partial arrays"""
+    from .leaf_model import PlateLeafModel
+
+    if not isinstance(model, PlateLeafModel):
+        raise TypeError("model must be a PlateLeafModel")
+    _check_type(q, "q", (torch.float64,))
+    if q.ndim != 2 or q.shape[1] != model.nm or q.shape[0] < 1:
+        raise ValueError(f"q must be (ncol, nm) = (ncol, {model.nm}): {model.params}")
+    ntan = model.nm
+    if partials and out is not None and "d_leaf_r" in out:
+        ntan = int(out["d_leaf_r"].shape[1]) if out["d_leaf_r"].ndim == 3 else -1
+        if not model.nm <= ntan <= _lib.SENSJAC_MAX_NTAN:
+            raise ValueError(f"the partial arrays must be (ncol, ntan, nb) with {model.nm} <= ntan <= {_lib.SENSJAC_MAX_NTAN}")
+    return ntan
+
+
+def plate_leaf_optics(model, q, *, partials=False, out=None, stream=None):
+    """The plate model on the device (``crt_hip_plate_leaf_f64``, one launch): ``q (ncol, nm)`` float64 on the GPU, its columns named
+    ``model.params`` = ``("N", contents...)`` -> ``(leaf_r, leaf_t)``, each ``(ncol, nb)``; ``partials=True``: ``(leaf_r, leaf_t,
+    d_leaf_r, d_leaf_t)`` with the partial derivatives ``(ncol, nm, nb)`` in the order of ``model.params`` -- per-column directions
+    as the Jacobian plans read them.  ``out``: a dict of arrays to write into under the keys ``PLATE_LEAF_KEYS``; its partial arrays
+    may have ``ntan >= nm`` rows, of which the rows beyond ``nm`` are not touched.  ``N`` in [1, 4], contents ``>= 0``; ``k`` is clamped
+    to [1e-6, 100] (the header).  A column's result is bitwise the same alone or in any batch, with or without the partials."""
+    ntan = _plate_leaf_static(model, q, partials, out)
+    q = _f64(q, "q")
+    ncol, nb, dev = q.shape[0], model.nb, q.device
+    shapes = {"leaf_r": (ncol, nb), "leaf_t": (ncol, nb)}
+    if partials:
+        shapes.update({"d_leaf_r": (ncol, ntan, nb), "d_leaf_t": (ncol, ntan, nb)})
+    o = _outputs(shapes, out, torch.float64, dev, "out[{!r}]", lacks=True)
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        m = model.c_struct(ncol, dev)
+        d = [o[k].data_ptr() if partials else None for k in ("d_leaf_r", "d_leaf_t")]
+        _lib.check(_lib.load().crt_hip_plate_leaf_f64(ctypes.byref(m), q.data_ptr(), model.nm, o["leaf_r"].data_ptr(), o["leaf_t"].data_ptr(),
+                                                       ntan if partials else 0, *d, s.cuda_stream), "crt_hip_plate_leaf_f64")
+    return tuple(o[k] for k in shapes)
+
+
+class _PlateLeafAD(torch.autograd.Function):
+    """``plate_leaf_optics`` with a backward pass: the incoming gradients contracted with the stored partials."""
+
+    @staticmethod
+    def forward(ctx, model, q):
+        leaf_r, leaf_t, d_r, d_t = plate_leaf_optics(model, q.detach(), partials=True)
+        ctx.save_for_backward(d_r, d_t)
+        return leaf_r, leaf_t
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_r, g_t):
+        d_r, d_t = ctx.saved_tensors
+        return None, torch.einsum("cb,cjb->cj", g_r, d_r) + torch.einsum("cb,cjb->cj", g_t, d_t)
+
+
+def plate_leaf_ad(model, q):
+    """:func:`plate_leaf_optics` attached to torch's autograd graph: ``(leaf_r, leaf_t)`` whose ``.backward()`` fills ``q.grad`` with
+    the incoming gradients contracted with the model's partials (once-differentiable).  With :func:`solve_levels_ad` behind it -- a
+    :class:`Bands` of these spectra -- a torch optimiser fits ``q`` directly."""
+    _plate_leaf_static(model, q, False, None)
+    with torch.cuda.device(q.device):
+        return _PlateLeafAD.apply(model, q)
+
+
+def _leaf_model_ntan(leaf_model, d_leaf_r, d_leaf_t, d_soil_r):
+    """``ntan = nm + ns`` of a retrieval with a leaf model: the model's parameters, then the ``ns`` soil directions.  No device."""
+    from .leaf_model import PlateLeafModel
+
+    if not isinstance(leaf_model, PlateLeafModel):
+        raise TypeError("leaf_model must be a PlateLeafModel")
+    if d_leaf_r is not None or d_leaf_t is not None:
+        raise ValueError("d_leaf_r / d_leaf_t and leaf_model exclude each other: the model writes the leaf directions")
+    ns = _sensjac_ntan(None, None, d_soil_r)
+    if leaf_model.nm + ns > _lib.SENSJAC_MAX_NTAN:
+        raise ValueError(f"nm + ns = {leaf_model.nm} + {ns} model parameters and soil directions; one call takes {_lib.SENSJAC_MAX_NTAN}")
+    return leaf_model.nm + ns
+
+
+def _leaf_model_start(leaf_model, lo, hi, p0):
+    """The bounds and the starting point a leaf model needs.  No device."""
+    leaf_model.check_bounds(lo, hi)
+    if p0 is None:
+        raise ValueError("a leaf_model needs p0: the model has no default starting point")
+
+
+class _PlateLeafBinding:
+    """What a retrieval plan owns for its ``leaf_model``: the per-column direction arrays ``(ncol, ntan, nb)`` with ``ntan = nm + ns``
+    -- leaf rows ``0 .. nm - 1`` written by ``k_plate_leaf`` at every evaluation and ``nm ..`` zero, soil rows ``0 .. nm - 1`` zero and
+    ``nm ..`` the user's directions -- and the launch that writes the working leaf spectra and those rows from a parameter array."""
+
+    def __init__(self, model, ncol, nb, d_soil_r, device):
+        if model.nb != nb:
+            raise ValueError(f"the leaf model has {model.nb} bands, the bands {nb}")
+        ns = _sensjac_ntan(None, None, d_soil_r)
+        self.model, self.nm, self.ns, self.ntan = model, model.nm, ns, model.nm + ns
+        new = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)  # noqa: E731
+        self.d_leaf_r, self.d_leaf_t = new(ncol, self.ntan, nb), new(ncol, self.ntan, nb)
+        self.d_soil_r = None
+        if ns:
+            self.d_soil_r = new(ncol, self.ntan, nb)
+            self.d_soil_r[:, self.nm:] = _jvp_direction(d_soil_r, "d_soil_r", ncol, nb, device)
+        # what k_retrieve_apply reads: no leaf directions (the base spectra are copied), the soil directions or, with none, a zero array
+        self._zero = None if ns else new(self.ntan, nb)
+        soil = self.d_soil_r if ns else self._zero
+        self.apply_dirs = _lib.CrtOpticsDirs(self.ntan, self.ntan * nb if ns and ncol != 1 else 0, None, None, soil.data_ptr())
+        self._m = model.c_struct(ncol, device)
+        self._keep = model.tensors(device)
+        self.names = model.params + tuple(f"dir{k}" for k in range(ns))
+
+    def bound_to(self, plan):
+        """The inner Jacobian / normal plan must read the arrays this binding writes."""
+        for n in ("leaf_r", "leaf_t"):
+            assert plan.dirs[n].data_ptr() == getattr(self, "d_" + n).data_ptr()
+
+    def launch(self, lib, p_ptr, npar, bands, h):
+        _lib.check(lib.crt_hip_plate_leaf_f64(ctypes.byref(self._m), p_ptr, npar, bands.leaf_r.data_ptr(), bands.leaf_t.data_ptr(), self.ntan,
+                                              self.d_leaf_r.data_ptr(), self.d_leaf_t.data_ptr(), h), "crt_hip_plate_leaf_f64")

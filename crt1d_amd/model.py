@@ -452,7 +452,10 @@ class Model:
         :meth:`run_sensor_jacobian`; ``wrt_leaf``: ``None`` or ``"param"`` (``g_param`` itself is retrieved).  ``lm_options``: ``p0``, ``lo``,
         ``hi``, ``prior``, ``inv_sigma_prior`` (each ``(npar,)``), ``inv_sigma`` (as ``y``), ``I_dr0_all`` / ``I_df0_all`` (with ``psi``) and
         the options of the plan.  Returns NumPy arrays ``p (npar,)``, ``cost``, ``status``, ``lam``, ``naccept``, ``nreject``,
-        ``cov (npar, npar)`` and ``"params"``.  ValueError for ``4s`` and ``zq_pa``.  The model's own state is not changed."""
+        ``cov (npar, npar)`` and ``"params"``.  ValueError for ``4s`` and ``zq_pa``.  The model's own state is not changed.
+        ``leaf_model=`` (a :class:`crt1d_amd.leaf_model.PlateLeafModel` on this model's wavelengths, among ``lm_options``) retrieves the
+        plate model's parameters instead of leaf directions: ``directions`` may then hold ``"soil_r"`` only, and ``p0``, ``lo``, ``hi``
+        are required."""
         from . import batched
 
         series = psi is not None
@@ -488,7 +491,7 @@ class Model:
         (:class:`crt1d_amd.batched.SpectralNormalSeriesPlan`).  ``directions``, ``lai``, ``wrt_leaf`` as for :meth:`retrieve`.
         ``lm_options``: ``p0``, ``lo``, ``hi``, ``prior``, ``inv_sigma_prior`` (each ``(npar,)``), ``inv_sigma`` (as ``y``; 0 masks a band) and the options of the
         plan.  Returns what :meth:`retrieve` returns.  ValueError for the schemes outside
-        ``batched.SPECTRAL_RETRIEVE_SCHEMES``.  The model's own state is not changed."""
+        ``batched.SPECTRAL_RETRIEVE_SCHEMES``.  The model's own state is not changed.  ``leaf_model=`` as for :meth:`retrieve`."""
         from . import batched
 
         from . import _lib
