@@ -1758,6 +1758,102 @@ def solve_levels_grad(scheme, cols: Columns, bands: Bands, levels, weights, **kw
         return LevelsGradPlan(scheme, cols, bands, levels, weights, **kw)()
 
 
+# ---- what the inverse-problem plans share: the parameter axis and the checks that need no device (the retrieval core: _LmPlan) ----------
+
+
+def _need_sun_series(sun):
+    if not isinstance(sun, SunSeries) or isinstance(sun, SunSeriesF32):
+        raise TypeError("sun must be a SunSeries (float64 spectra)")
+
+
+def _need_f64_bands(bands, what):
+    if bands is not None and bands.dtype != torch.float64:  # (None: a check ahead of the columns)
+        raise TypeError(f"the {what} has no f32 storage form: bands must be float64")
+
+
+def _check_tangent(tangent, sun=None, series=False):
+    """``tangent``: None or a :class:`LeafTangent`; ``series``: ``sun`` a float64 :class:`SunSeries`, ``tangent`` a :class:`LeafTangentSeries`
+    of its ``nt``."""
+    if series:
+        _need_sun_series(sun)
+    kind = LeafTangentSeries if series else LeafTangent
+    if tangent is not None and not isinstance(tangent, kind):
+        raise TypeError(f"tangent must be a {kind.__name__}")
+    if series and tangent is not None and tangent.nt != sun.nt:
+        raise ValueError(f"the tangent has nt = {tangent.nt} sun states, the series {sun.nt}")
+
+
+def _check_obs(y, inv_sigma, keys, axes, rank=None):
+    """The observation dicts of a retrieval against ``keys``; ``axes``: how the messages call the arrays' shape.  ``rank``: their number of
+    axes, where the shapes can be looked at already (the spectral plans: arrays of the user's) -- they must share one shape then."""
+    import numpy as np
+
+    shapes = set()
+    for name, d in (("y", y), ("inv_sigma", inv_sigma)):
+        if d is None and name == "inv_sigma":
+            continue
+        if not isinstance(d, dict):
+            raise TypeError(f"{name} must be a dict {{key: {axes}}}")
+        if extra := [k for k in d if k not in keys]:
+            raise ValueError(f"{name} has the keys {extra}, which are not in keys = {keys}")
+        for k, v in d.items() if rank else ():
+            shape = tuple(v.shape) if hasattr(v, "shape") else np.shape(v)
+            if len(shape) != rank:
+                raise ValueError(f"{name}[{k!r}] must be {axes}, got {shape}")
+            shapes.add(shape)
+    if missing := [k for k in keys if k not in y]:
+        raise ValueError(f"y lacks the keys {missing} of keys = {keys}")
+    if len(shapes) > 1:
+        raise ValueError(f"the arrays of y and inv_sigma must share one shape {axes}, got {sorted(shapes)}")
+
+
+def _per_col(v, name, ncol, npar, device):
+    """``(ncol, npar)`` or ``(npar,)`` -> a contiguous float64 ``(ncol, npar)`` on ``device``."""
+    v = torch.as_tensor(v, dtype=torch.float64).to(device)
+    if v.ndim == 1:
+        v = v[None]
+    if v.ndim != 2 or v.shape[1] != npar or v.shape[0] not in (1, ncol):
+        raise ValueError(f"{name} must be (ncol, npar) or (npar,) with ncol = {ncol}, npar = {npar}")
+    return v.expand(ncol, -1).contiguous()
+
+
+class _ParamAxis:
+    """The parameter axis of the inverse-problem plans: the ``ntan`` directions ``d_leaf_r / d_leaf_t / d_soil_r`` (``"dir0"``, ...; with a
+    ``leaf_model``: its ``nm`` parameters by name, then the ``ns`` soil directions), then ``"lai"``, then ``"leaf"`` (``leaf=True`` or a
+    ``tangent``).  The constructor is the static half: nothing but the user's arguments -> ``ntan``, ``npar``, ``params``.  :meth:`bind`
+    is the bound half: the direction tensors, the tangent, and the C structs the entries and ``k_retrieve_apply`` read."""
+
+    def __init__(self, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, leaf=False, leaf_model=None, tangent=None):
+        self.given = {n: d for n, d in zip(JAC_PARAMS, (d_leaf_r, d_leaf_t, d_soil_r)) if d is not None}
+        if leaf_model is None:
+            self.ntan, names = _sensjac_ntan(d_leaf_r, d_leaf_t, d_soil_r), ()
+        else:
+            self.ntan, names = _leaf_model_ntan(leaf_model, d_leaf_r, d_leaf_t, d_soil_r), leaf_model.params
+        self.lai, self.leaf, self.tangent = bool(lai), bool(leaf) or tangent is not None, tangent
+        self.params = (names + tuple(f"dir{k}" for k in range(self.ntan - len(names))) + (("lai",) if self.lai else ())
+                       + (("leaf",) if self.leaf else ()))
+        self.npar = len(self.params)
+        if self.npar == 0:
+            raise ValueError("no parameter at all: give a direction, lai=True or a leaf-angle parameter (leaf=True, a tangent)")
+
+    def bind(self, ncol, nb, device):
+        """-> self, with ``dirs`` (the directions given, contiguous float64 on ``device``, per column where one of them is), the tangent
+        checked against the columns, and ``c_dirs`` / ``c_tan``, the ``CrtOpticsDirs`` and the tangent's C struct (None where there is
+        none).  The axis keeps every tensor whose address they hold.  (Not for an axis with a ``leaf_model``: :class:`_PlateLeafBinding`.)"""
+        dirs = {n: _jvp_direction(d, "d_" + n, ncol, nb, device) for n, d in self.given.items()}
+        per_col = any(d.shape[0] != 1 for d in dirs.values()) and ncol != 1
+        self.dirs = {n: (d.expand(ncol, -1, -1) if per_col else d).contiguous() for n, d in dirs.items()}
+        t = self.tangent
+        if t is not None and (t.dg_table.shape[0] != ncol or t.dg_table.device != device):
+            raise ValueError("the tangent must have the columns' ncol and device")
+        self.c_dirs = None
+        if self.ntan:
+            self.c_dirs = _lib.CrtOpticsDirs(self.ntan, self.ntan * nb if per_col else 0,
+                                             *[self.dirs[n].data_ptr() if n in self.dirs else None for n in JAC_PARAMS])
+        self.c_tan = None if t is None else t.c_struct()
+        return self
+
+
 # ---- Jacobian of the sensor-band sums (include/crt1d_hip_sensjac.h) -----------------------------------------------------------------------
 
 SENSJAC_SCHEMES = GRAD_SCHEMES  # the schemes k_sens_jac serves; SensorJacPlan composes sensor_jvp, sensor_dlai and sensor_dleaf for n79 and zq
@@ -1812,34 +1908,48 @@ class SensorJacPlan(_LevelsDerivPlan):
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, *, d_leaf_r=None, d_leaf_t=None, d_soil_r=None,
                  lai=True, tangent=None, keys=LEVEL_KEYS, mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
-        self._build(scheme, cols, bands, None, levels, sensors, d_leaf_r, d_leaf_t, d_soil_r, lai, tangent, keys, mu_s, tau_d_method, out, workspace)
+        self._build(None, scheme, cols, bands, levels, sensors, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r, lai=lai, tangent=tangent,
+                    keys=keys, mu_s=mu_s, tau_d_method=tau_d_method, out=out, workspace=workspace)
 
-    def _build(self, scheme, cols, bands, sun, levels, sensors, d_leaf_r, d_leaf_t, d_soil_r, lai, tangent, keys, mu_s, tau_d_method, out,
-               workspace):
-        """The construction of this plan (``sun`` None) and of :class:`SensorJacSeriesPlan` (outputs with a sun-state axis)."""
-        series = {} if sun is None else {"sun": sun}
-        keys = self._check_static(scheme, tau_d_method, keys, sensors=sensors, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r,
-                                  lai=lai, tangent=tangent, **series)
-        self._composed = scheme not in SENSJAC_SCHEMES
-        if self._composed and workspace is not None:
+    _series = False  # SensorJacSeriesPlan: a sun-angle series in front of the levels, outputs with a sun-state axis
+
+    @classmethod
+    def _static(cls, scheme, cols, bands, levels, sensors, **kw):
+        """The constructor's arguments (``kw``: its keywords) -> (keys, the parameter axis): every check that needs neither a column nor
+        a device."""
+        return cls._static_of(None, scheme, bands, sensors, **kw)
+
+    @classmethod
+    def _static_of(cls, sun, scheme, bands, sensors, *, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, tangent=None, keys=LEVEL_KEYS,
+                   mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
+        keys = cls._check_static(scheme, tau_d_method, keys, sensors=sensors, tangent=tangent, sun=sun)
+        axis = _ParamAxis(d_leaf_r, d_leaf_t, d_soil_r, lai, tangent=tangent)
+        if scheme not in SENSJAC_SCHEMES and workspace is not None:
             raise ValueError(f"the sensor Jacobian of {scheme} runs plans with workspaces of their own: workspace must be None")
-        if bands.dtype != torch.float64:
-            raise TypeError(f"the {self._what} has no f32 storage form: bands must be float64")
-        ntan = _sensjac_ntan(d_leaf_r, d_leaf_t, d_soil_r)
+        _need_f64_bands(bands, cls._what)
+        return keys, axis
+
+    @classmethod
+    def _check_extras(cls, sensors=None, tangent=None, sun=None):
+        if not isinstance(sensors, SensorSet):
+            raise TypeError("sensors must be a SensorSet")
+        _check_tangent(tangent, sun, cls._series)
+
+    def _build(self, sun, scheme, cols, bands, levels, sensors, *, mu_s, tau_d_method, out, workspace, **kw):
+        """The construction of this plan (``sun`` None) and of :class:`SensorJacSeriesPlan`."""
+        keys, axis = self._static_of(sun, scheme, bands, sensors, tau_d_method=tau_d_method, workspace=workspace, **kw)
+        series = {} if sun is None else {"sun": sun}
+        self._composed = scheme not in SENSJAC_SCHEMES
         self.levels, self.keys, self.sensors = normalize_levels(levels, cols.nz), keys, sensors
         self._kw = dict(mu_s=mu_s, tau_d_method=tau_d_method)
         sensors.check(bands.nb, cols.device)
         self._bind(scheme, cols, bands, mu_s, tau_d_method, **series)
         ncol, nsel, nb, dev = cols.ncol, len(self.levels), bands.nb, cols.device
         nts = () if sun is None else (sun.nt,)
-        dirs = {n: _jvp_direction(d, "d_" + n, ncol, nb, dev) for n, d in zip(JAC_PARAMS, (d_leaf_r, d_leaf_t, d_soil_r)) if d is not None}
-        per_col = any(d.shape[0] != 1 for d in dirs.values()) and ncol != 1
-        self.dirs = {n: (d.expand(ncol, -1, -1) if per_col else d).contiguous() for n, d in dirs.items()}
-        if tangent is not None and (tangent.dg_table.shape[0] != ncol or tangent.dg_table.device != dev):
-            raise ValueError("the tangent must have the columns' ncol and device")
-        self.tangent, self.ntan = tangent, ntan
-        self.params = tuple(f"dir{k}" for k in range(ntan)) + (("lai",) if lai else ()) + (("leaf",) if tangent is not None else ())
-        npar = len(self.params)
+        self._axis = axis.bind(ncol, nb, dev)  # (the composed plans too: a retrieval takes its apply-directions from here)
+        self.dirs, self.tangent, self.ntan, self.params = axis.dirs, axis.tangent, axis.ntan, axis.params
+        self._dirs, self._tan = axis.c_dirs, axis.c_tan
+        npar = axis.npar
         out = _outputs({k: (ncol, *nts, nsel, sensors.nsens, npar) for k in keys}, out, torch.float64, dev, "output {!r}", lacks=True)
         self.out = {k: out[k] for k in keys}
         self._lev = (ctypes.c_int32 * nsel)(*self.levels)
@@ -1847,11 +1957,6 @@ class SensorJacPlan(_LevelsDerivPlan):
             self._report = ""
             return
         self._sens = sensors.c_struct()
-        self._dirs = None
-        if ntan:
-            self._dirs = _lib.CrtOpticsDirs(ntan, ntan * nb if per_col else 0,
-                                            *[self.dirs[n].data_ptr() if n in self.dirs else None for n in JAC_PARAMS])
-        self._tan = None if tangent is None else tangent.c_struct()
         self._out = _lib.CrtSensJacOut(*[out[k].data_ptr() if k in keys else None for k in LEVEL_KEYS])
         if sun is None:
             need = max(sensor_jac_workspace_bytes(scheme, ncol, cols.nz, nb, nsel, sensors.nsens, npar),
@@ -1860,15 +1965,6 @@ class SensorJacPlan(_LevelsDerivPlan):
             need = max(sensor_jac_series_workspace_bytes(scheme, ncol, cols.nz, nb, sun.nt, nsel, sensors.nsens, npar),
                        sensor_series_workspace_bytes(scheme, ncol, cols.nz, nb, sun.nt, nsel, sensors.nsens))
         self._finish(self._entry_name, need, workspace)
-
-    @staticmethod
-    def _check_extras(sensors=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, tangent=None, **_):
-        if not isinstance(sensors, SensorSet):
-            raise TypeError("sensors must be a SensorSet")
-        if tangent is not None and not isinstance(tangent, LeafTangent):
-            raise TypeError("tangent must be a LeafTangent")
-        if _sensjac_ntan(d_leaf_r, d_leaf_t, d_soil_r) + bool(lai) + (tangent is not None) == 0:
-            raise ValueError("no parameter at all: give a direction, lai=True or a tangent")
 
     def _tail(self):
         ref = lambda x: None if x is None else ctypes.byref(x)  # noqa: E731
@@ -1912,9 +2008,7 @@ class SensorJacPlan(_LevelsDerivPlan):
 
 def sensor_jacobian(scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, **kw):
     """One-shot :class:`SensorJacPlan`: ``{key: (ncol, nsel, nsens, npar)}`` at the sorted levels ``normalize_levels(levels, nz)``."""
-    SensorJacPlan._check_static(scheme, kw.get("tau_d_method", "quad"), kw.get("keys"), sensors=sensors, d_leaf_r=kw.get("d_leaf_r"),
-                                d_leaf_t=kw.get("d_leaf_t"), d_soil_r=kw.get("d_soil_r"), lai=kw.get("lai", True),
-                                tangent=kw.get("tangent"))  # (before any device is touched)
+    SensorJacPlan._static(scheme, cols, bands, levels, sensors, **kw)  # (before any device is touched)
     with torch.cuda.device(cols.device):
         return SensorJacPlan(scheme, cols, bands, levels, sensors, **kw)()
 
@@ -2019,26 +2113,16 @@ class SensorJacSeriesPlan(SensorJacPlan):
     (no workspace, no flags); ``4s`` and ``zq_pa`` are a ValueError.  For :func:`gauss_newton_step`:
     ``J.reshape(ncol, nt * nsel * nsens, npar)``."""
 
-    _entry_name = "crt_hip_sensor_jac_series_f64"
+    _entry_name, _series = "crt_hip_sensor_jac_series_f64", True
 
     def __init__(self, scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, sensors: SensorSet, *, d_leaf_r=None, d_leaf_t=None,
                  d_soil_r=None, lai=True, tangent=None, keys=LEVEL_KEYS, mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
-        keys = self._check_static(scheme, tau_d_method, keys, sensors=sensors, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r,
-                                  lai=lai, tangent=tangent, sun=sun)  # (a sun that is no SunSeries: before _build looks at it)
-        self._build(scheme, cols, bands, sun, levels, sensors, d_leaf_r, d_leaf_t, d_soil_r, lai, tangent, keys, mu_s, tau_d_method, out, workspace)
+        self._build(sun, scheme, cols, bands, levels, sensors, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r, lai=lai, tangent=tangent,
+                    keys=keys, mu_s=mu_s, tau_d_method=tau_d_method, out=out, workspace=workspace)
 
-    @staticmethod
-    def _check_extras(sensors=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, tangent=None, sun=None, **_):
-        if not isinstance(sensors, SensorSet):
-            raise TypeError("sensors must be a SensorSet")
-        if not isinstance(sun, SunSeries) or isinstance(sun, SunSeriesF32):
-            raise TypeError("sun must be a SunSeries (float64 spectra)")
-        if tangent is not None and not isinstance(tangent, LeafTangentSeries):
-            raise TypeError("tangent must be a LeafTangentSeries")
-        if tangent is not None and tangent.nt != sun.nt:
-            raise ValueError(f"the tangent has nt = {tangent.nt} sun states, the series {sun.nt}")
-        if _sensjac_ntan(d_leaf_r, d_leaf_t, d_soil_r) + bool(lai) + (tangent is not None) == 0:
-            raise ValueError("no parameter at all: give a direction, lai=True or a tangent")
+    @classmethod
+    def _static(cls, scheme, cols, bands, sun, levels, sensors, **kw):
+        return cls._static_of(sun, scheme, bands, sensors, **kw)
 
     def __call__(self, stream=None, *, flags=0):
         if not self._composed:
@@ -2074,9 +2158,7 @@ def _step_bands(bands, sun, t):
 
 def sensor_jacobian_series(scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, sensors: SensorSet, **kw):
     """One-shot :class:`SensorJacSeriesPlan`: ``{key: (ncol, nt, nsel, nsens, npar)}`` at the sorted levels."""
-    SensorJacSeriesPlan._check_static(scheme, kw.get("tau_d_method", "quad"), kw.get("keys"), sensors=sensors, d_leaf_r=kw.get("d_leaf_r"),
-                                      d_leaf_t=kw.get("d_leaf_t"), d_soil_r=kw.get("d_soil_r"), lai=kw.get("lai", True),
-                                      tangent=kw.get("tangent"), sun=sun)  # (before any device is touched)
+    SensorJacSeriesPlan._static(scheme, cols, bands, sun, levels, sensors, **kw)  # (before any device is touched)
     with torch.cuda.device(cols.device):
         return SensorJacSeriesPlan(scheme, cols, bands, sun, levels, sensors, **kw)()
 
@@ -2126,32 +2208,10 @@ RETRIEVE_SCHEMES = DLAI_SCHEMES  # 2s, bl, g77, bf on the kernels; n79 and zq th
 LM_OPTIONS = dict(lam0=1e-2, lam_up=10.0, lam_down=0.1, lam_min=1e-12, lam_max=1e12, xtol=0.0, ftol=0.0)
 
 
-def _retrieve_static(scheme, sensors, y, keys, sun=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, leaf=False, lo=None,
-                     hi=None, inv_sigma=None, tau_d_method="quad", bands=None, leaf_model=None, **opts):
-    """The checks of a :class:`RetrievalPlan` that touch no device.  -> (keys, ntan, npar, LM options)"""
+def _lm_options(lo, hi, npar, opts):
+    """The bounds and Levenberg-Marquardt options of a retrieval plan, checked without a device.  -> LM options"""
     import numpy as np
 
-    _SolvePlan._check_options(_SolvePlan, scheme, tau_d_method)
-    if scheme not in RETRIEVE_SCHEMES:
-        raise ValueError(f"scheme {scheme!r} has no retrieval; served: " + ", ".join(RETRIEVE_SCHEMES))
-    keys = _level_keys(keys)
-    if not isinstance(sensors, SensorSet):
-        raise TypeError("sensors must be a SensorSet")
-    if sun is not None and (not isinstance(sun, SunSeries) or isinstance(sun, SunSeriesF32)):
-        raise TypeError("sun must be a SunSeries (float64 spectra)")
-    for name, d in (("y", y), ("inv_sigma", inv_sigma)):
-        if d is None and name == "inv_sigma":
-            continue
-        if not isinstance(d, dict):
-            raise TypeError(f"{name} must be a dict {{key: (ncol, [nt,] nsel, nsens)}}")
-        if extra := [k for k in d if k not in keys]:
-            raise ValueError(f"{name} has the keys {extra}, which are not in keys = {keys}")
-    if missing := [k for k in keys if k not in y]:
-        raise ValueError(f"y lacks the keys {missing} of keys = {keys}")
-    ntan = _sensjac_ntan(d_leaf_r, d_leaf_t, d_soil_r) if leaf_model is None else _leaf_model_ntan(leaf_model, d_leaf_r, d_leaf_t, d_soil_r)
-    npar = ntan + bool(lai) + bool(leaf)
-    if npar == 0:
-        raise ValueError("no parameter at all: give a direction, lai=True or leaf=True")
     for name, v in (("lo", lo), ("hi", hi)):
         if v is not None and tuple(np.shape(v)) != (npar,):
             raise ValueError(f"{name} must be (npar,) = ({npar},), got {tuple(np.shape(v))}")
@@ -2160,54 +2220,29 @@ def _retrieve_static(scheme, sensors, y, keys, sun=None, d_leaf_r=None, d_leaf_t
     o = {k: float(opts.get(k, v)) for k, v in LM_OPTIONS.items()}
     if not (o["lam0"] > 0 and o["lam_up"] > 1 and 0 < o["lam_down"] <= 1 and 0 <= o["lam_min"] <= o["lam_max"] and o["xtol"] >= 0 and o["ftol"] >= 0):
         raise ValueError("the options need lam0 > 0, lam_up > 1, 0 < lam_down <= 1, 0 <= lam_min <= lam_max, xtol >= 0 and ftol >= 0")
-    if bands is not None and bands.dtype != torch.float64:
-        raise TypeError("the retrieval has no f32 storage form: bands must be float64")
-    return keys, ntan, npar, o
+    return o
 
 
-class RetrievalPlan:
-    """A Levenberg-Marquardt retrieval of a parameter vector of every column from sensor-band observations, with the whole loop on the
-    device (include/crt1d_hip_retrieve.h): no host synchronisation between steps, no allocation after construction.
+def _check_start(leaf_model, lo, hi, p0, prior, inv_sigma_prior):
+    """The starting point and the prior of a retrieval, as far as no device is needed."""
+    if leaf_model is not None:
+        _leaf_model_start(leaf_model, lo, hi, p0)
+    if (prior is None) != (inv_sigma_prior is None):
+        raise ValueError("prior and inv_sigma_prior go together")
 
-    ``cols``, ``bands`` (with ``sun``: a :class:`SunSeries` that supplies the sun angles and the incoming spectra) are the base state;
-    ``y[k]`` are the observations of the sums :class:`SensorLevelsPlan` (``sun``: :class:`SensorLevelsSeriesPlan`) gives for ``keys``,
-    each ``(ncol, [nt,] nsel, nsens)``; ``inv_sigma[k]`` their weights (``None`` / a missing key: ones; an entry 0: not observed, its
-    ``y`` may be NaN).  The parameters, in the order of ``SensorJacPlan.params``: the coefficients of the ``ntan`` directions
-    ``d_leaf_r / d_leaf_t / d_soil_r`` added to the base spectra; ``"lai"`` (``lai=True``): the log of a scale of the base LAI profile;
-    ``"leaf"`` (``leaf=True``): the column's ``g_param`` itself (``wrt="param"`` of :func:`leaf_tangent`; ``mla`` stays fixed).  For the
-    parameterless leaf-angle kinds and ``G_TABLE`` columns ``dG`` is zero: the parameter is dead there and stays where it started.
-    ``p0 (ncol, npar)`` or ``(npar,)``: the starting point (default: zeros, and ``cols.g_param`` for ``"leaf"``); ``lo``, ``hi`` ``(npar,)``:
-    bounds, which also keep the optics physical -- nothing else clamps them; ``prior``, ``inv_sigma_prior`` ``(ncol, npar)`` or ``(npar,)``:
-    a Gaussian prior.  ``lam0`` and the options ``lam_up, lam_down, lam_min, lam_max, xtol, ftol`` are those of the header.
 
-    :meth:`step` is five launches in a row: ``k_retrieve_apply`` writes the working :class:`Columns` / :class:`Bands` from the trial
-    point; ``crt_hip_g_dparam_f64`` refills the leaf-angle tangent; the :class:`SensorJacPlan` (``sun``: :class:`SensorJacSeriesPlan`)
-    bound to the working tensors; the forward sums on its workspace with ``FLAG_SKIP_PRECOMPUTE``; ``k_lm_step``.  The first step
-    evaluates ``p0`` and is always accepted.  n79 and zq run the composed Jacobian plan (workspaces and allocations of its own) and the
-    forward plan with its own precompute; ``4s`` and ``zq_pa`` are a ValueError.  A column's state is bitwise the same alone or in any
-    batch.  float64 only.
+class _LmPlan:
+    """What :class:`RetrievalPlan` and :class:`SpectralRetrievalPlan` share: the base and the working :class:`Columns` / :class:`Bands`, the
+    leaf-angle tangent, the leaf-model binding, the bounds, the prior, the starting point and the Levenberg-Marquardt state, the structs
+    of ``k_retrieve_apply`` and of the step kernels, and the first launches of an evaluation.  A subclass supplies ``_inner`` -- its inner
+    plan or plans, bound to the working tensors, and its observation structs -- and ``step``, which closes an evaluation with its C
+    call."""
 
-    ``leaf_model``: a :class:`crt1d_amd.leaf_model.PlateLeafModel` -- the leaf spectra are the plate model's, and its ``nm`` parameters
-    ``leaf_model.params`` = ``("N", contents...)`` are retrieved in place of coefficients of leaf directions.  The parameter axis is then
-    the model's parameters, the ``ns`` soil directions ``d_soil_r`` (``"dir0"``, ...), ``"lai"``, ``"leaf"``, with ``nm + ns <= 8``;
-    ``d_leaf_r`` / ``d_leaf_t`` are a ValueError; ``lo`` / ``hi`` are required and must keep ``N`` inside [1, 4] and every content
-    ``>= 0``; ``p0`` is required; ``bands.leaf_r / leaf_t`` are not used.  The plan owns per-column direction arrays of ``nm + ns`` rows
-    (``3 x ncol x (nm + ns) x nb x 8`` bytes), and :meth:`step` is one launch more: ``k_retrieve_apply`` with the leaf directions left out,
-    then ``crt_hip_plate_leaf_f64`` on the same parameter array, which writes the working leaf spectra and the model's partials into
-    the leaf rows, then the launches above."""
-
-    def __init__(self, scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, y, *, keys, sun=None, d_leaf_r=None, d_leaf_t=None,
-                 d_soil_r=None, lai=True, leaf=False, p0=None, lo=None, hi=None, inv_sigma=None, prior=None, inv_sigma_prior=None,
-                 leaf_model=None, mu_s=0.501, tau_d_method="quad", **options):
-        keys, ntan, npar, o = _retrieve_static(scheme, sensors, y, keys, sun, d_leaf_r, d_leaf_t, d_soil_r, lai, leaf, lo, hi, inv_sigma,
-                                               tau_d_method, bands, leaf_model, **options)
-        if leaf_model is not None:
-            _leaf_model_start(leaf_model, lo, hi, p0)
-        if (prior is None) != (inv_sigma_prior is None):
-            raise ValueError("prior and inv_sigma_prior go together")
+    def _construct(self, keys, axis, o, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, **inner):
         self.lib = _lib.load()
         self.scheme, self.keys, self.sun, self.options = scheme, keys, sun, o
         ncol, nz, nb, dev = cols.ncol, cols.nz, bands.nb, cols.device
+        npar, ntan, lai, leaf = axis.npar, axis.ntan, axis.lai, axis.leaf
         f64 = dict(dtype=torch.float64, device=dev)
         new = lambda *shape: torch.zeros(shape, **f64)  # noqa: E731
         # the base state and the working inputs k_retrieve_apply overwrites
@@ -2217,68 +2252,30 @@ class RetrievalPlan:
         self.bands = Bands(rows(bands.I_dr0), rows(bands.I_df0), new(ncol, nb), new(ncol, nb), None if bands.soil_r is None else new(ncol, nb))
         self.cols = Columns(cols.psi, cols.lai.clone(), cols.g_kind, cols.g_param.clone(), cols.mla, cols.g_at_psi, cols.g_table)
         self.lai_scale = torch.ones((ncol,), **f64)
-        # the leaf-angle tangent, refilled in place every step
+        # the leaf-angle tangent, refilled in place at every evaluation
         self.tangent = None
         if leaf:
             self.tangent = (LeafTangent(new(ncol, _lib.NQ), new(ncol)) if sun is None
                             else LeafTangentSeries(new(ncol, _lib.NQ), new(ncol, sun.nt)))
-        # the leaf model: the plan owns the per-column directions k_plate_leaf writes and the Jacobian plan reads
+        # the leaf model: the plan owns the per-column directions k_plate_leaf writes and the inner plan reads
         self.leaf_model = leaf_model
-        self._leaf = None if leaf_model is None else _PlateLeafBinding(leaf_model, ncol, nb, d_soil_r, dev)
+        self._leaf = None if leaf_model is None else _PlateLeafBinding(leaf_model, axis, ncol, nb, dev)
+        dirs = axis.given if self._leaf is None else self._leaf.dirs
+        held = self._inner(scheme, levels, sun, **inner, **{"d_" + n: d for n, d in dirs.items()}, lai=lai, tangent=self.tangent, keys=keys)
+        self.params, self.levels, self.npar, self.ntan = axis.params, held.levels, npar, ntan
+        self._dirs = held._dirs  # what k_retrieve_apply adds to the base spectra: the inner plan's directions
         if self._leaf is not None:
-            d_leaf_r, d_leaf_t, d_soil_r = self._leaf.d_leaf_r, self._leaf.d_leaf_t, self._leaf.d_soil_r
-        d = dict(d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r, lai=bool(lai), tangent=self.tangent, keys=keys, mu_s=mu_s,
-                 tau_d_method=tau_d_method)
-        f = dict(keys=keys, mu_s=mu_s, tau_d_method=tau_d_method)
-        if sun is None:
-            self.jac = SensorJacPlan(scheme, self.cols, self.bands, levels, sensors, **d)
-            self.fwd = SensorLevelsPlan(scheme, self.cols, self.bands, levels, sensors, **f, workspace=getattr(self.jac, "workspace", None))
-        else:
-            self.jac = SensorJacSeriesPlan(scheme, self.cols, self.bands, sun, levels, sensors, **d)
-            self.fwd = SensorLevelsSeriesPlan(scheme, self.cols, self.bands, sun, levels, sensors, **f,
-                                              workspace=getattr(self.jac, "workspace", None))
-        self._fwd_flags = 0 if self.jac._composed else _lib.FLAG_SKIP_PRECOMPUTE
-        self.params, self.levels, self.npar, self.ntan = self.jac.params, self.jac.levels, npar, ntan
-        assert len(self.params) == npar
-        self._dirs = None
-        if self._leaf is not None:
-            self._leaf.bound_to(self.jac)
-            self.params = self._leaf.names + self.params[ntan:]
+            self._leaf.bound_to(held)
             self._dirs = self._leaf.apply_dirs
-        elif ntan:
-            by_col = ncol != 1 and any(v.shape[0] != 1 for v in self.jac.dirs.values())
-            self._dirs = _lib.CrtOpticsDirs(ntan, ntan * nb if by_col else 0,
-                                            *[self.jac.dirs[n].data_ptr() if n in self.jac.dirs else None for n in JAC_PARAMS])
-        # observations, bounds, prior
-        shape = tuple(self.fwd.out[keys[0]].shape)
-        self.nrow = int(torch.Size(shape[1:]).numel())
-
-        def obs(v, name):
-            v = torch.as_tensor(v, dtype=torch.float64).to(dev).contiguous()
-            if tuple(v.shape) != shape:
-                raise ValueError(f"{name} must be {shape}, got {tuple(v.shape)}")
-            return v
-
-        self.y = {k: obs(y[k], f"y[{k!r}]") for k in keys}
-        self.inv_sigma = {k: obs(inv_sigma[k], f"inv_sigma[{k!r}]") for k in keys if inv_sigma is not None and k in inv_sigma}
-
-        def per_col(v, name, width=npar):
-            v = torch.as_tensor(v, dtype=torch.float64).to(dev)
-            if v.ndim == 1:
-                v = v[None]
-            if v.ndim != 2 or v.shape[1] != width or v.shape[0] not in (1, ncol):
-                raise ValueError(f"{name} must be (ncol, npar) or (npar,) with ncol = {ncol}, npar = {width}")
-            return v.expand(ncol, -1).contiguous()
-
         self.lo = None if lo is None else torch.as_tensor(lo, dtype=torch.float64).to(dev).contiguous()
         self.hi = None if hi is None else torch.as_tensor(hi, dtype=torch.float64).to(dev).contiguous()
-        self.prior = None if prior is None else per_col(prior, "prior")
-        self.inv_sigma_prior = None if prior is None else per_col(inv_sigma_prior, "inv_sigma_prior")
+        self.prior = None if prior is None else _per_col(prior, "prior", ncol, npar, dev)
+        self.inv_sigma_prior = None if prior is None else _per_col(inv_sigma_prior, "inv_sigma_prior", ncol, npar, dev)
         if p0 is None:
             p0 = new(ncol, npar)
             if leaf:
                 p0[:, npar - 1] = cols.g_param
-        self._p0 = per_col(p0, "p0").clone()
+        self._p0 = _per_col(p0, "p0", ncol, npar, dev).clone()
         # the state
         ntri = npar * (npar + 1) // 2
         i32 = dict(dtype=torch.int32, device=dev)
@@ -2286,21 +2283,34 @@ class RetrievalPlan:
         self.A, self.g = new(ncol, ntri), new(ncol, npar)
         self.status, self.naccept, self.nreject = (torch.zeros((ncol,), **i32) for _ in range(3))
         self.cov = new(ncol, npar, npar)
-        # the structs of the three entries
+        # the structs of the entries: k_retrieve_apply at the trial point (_ap) and at the accepted point (_ap_p)
         ptr = lambda v: None if v is None else v.data_ptr()  # noqa: E731
         b, w, c = bands, self.bands, self.cols
-        self._ap = _lib.CrtRetrieveApply(ncol, nz, nb, npar, ntan if lai else -1, ntan + bool(lai) if leaf else -1, self._base_stride,
-                                         ptr(b.leaf_r), ptr(b.leaf_t), ptr(b.soil_r), ptr(cols.lai), ptr(self.p_trial), ptr(w.leaf_r),
-                                         ptr(w.leaf_t), ptr(w.soil_r), ptr(self.lai_scale), ptr(c.lai), ptr(c.g_param))
+        apply = lambda p: _lib.CrtRetrieveApply(ncol, nz, nb, npar, ntan if lai else -1, ntan + lai if leaf else -1,  # noqa: E731
+                                                self._base_stride, ptr(b.leaf_r), ptr(b.leaf_t), ptr(b.soil_r), ptr(cols.lai), ptr(p),
+                                                ptr(w.leaf_r), ptr(w.leaf_t), ptr(w.soil_r), ptr(self.lai_scale), ptr(c.lai), ptr(c.g_param))
+        self._ap, self._ap_p = apply(self.p_trial), apply(self.p)
         self._prob = _lib.CrtLmProblem(ncol, npar, o["lam_up"], o["lam_down"], o["lam_min"], o["lam_max"], o["xtol"], o["ftol"], ptr(self.lo),
                                        ptr(self.hi), ptr(self.prior), ptr(self.inv_sigma_prior))
-        self._obs = (_lib.CrtLmObs * len(keys))(*[
-            _lib.CrtLmObs(self.nrow, ptr(self.fwd.out[k]), ptr(self.jac.out[k]), ptr(self.y[k]), ptr(self.inv_sigma.get(k))) for k in keys])
         self._state = _lib.CrtLmState(*[ptr(v) for v in (self.p, self.p_trial, self.cost, self.lam, self.A, self.g, self.status, self.naccept,
                                                           self.nreject)])
         self._c = c.c_struct()
         self._s = None if sun is None else sun.c_struct()
         self.reset()
+
+    def _evaluate(self, ap, s):
+        """The launches every evaluation starts with, on stream ``s``: the working inputs from the parameters behind ``ap``, the leaf model,
+        the tangent refill.  (The caller has entered ``torch.cuda.device``.)"""
+        lib, ref, h = self.lib, ctypes.byref, s.cuda_stream
+        _lib.check(lib.crt_hip_retrieve_apply_f64(ref(ap), None if self._dirs is None else ref(self._dirs), h), "crt_hip_retrieve_apply_f64")
+        if self._leaf is not None:
+            self._leaf.launch(lib, ap.p, self.npar, self.bands, h)
+        t = self.tangent
+        if t is not None and self.sun is None:
+            _lib.check(lib.crt_hip_g_dparam_f64(ref(self._c), t.dg_table.data_ptr(), t.dg_at_psi.data_ptr(), h), "crt_hip_g_dparam_f64")
+        elif t is not None:
+            _lib.check(lib.crt_hip_g_dparam_series_f64(ref(self._c), ref(self._s), t.dg_table.data_ptr(), t.dg_at_psi.data_ptr(), h),
+                       "crt_hip_g_dparam_series_f64")
 
     def reset(self, p0=None):
         """Restart the state at ``p0`` (default: the plan's starting point): ``p = p_trial = p0``, ``cost = +inf``, ``lam = lam0``."""
@@ -2313,27 +2323,6 @@ class RetrievalPlan:
         self.lam.fill_(self.options["lam0"])
         for v in (self.A, self.g, self.status, self.naccept, self.nreject):
             v.zero_()
-        return self
-
-    def step(self, stream=None):
-        """One iteration on ``stream`` (default: torch's current stream): apply, tangent, Jacobian, forward sums, ``k_lm_step``."""
-        dev = self.cols.device
-        s = torch.cuda.current_stream(dev) if stream is None else stream
-        h, lib, ref = s.cuda_stream, self.lib, ctypes.byref
-        with torch.cuda.device(dev):
-            _lib.check(lib.crt_hip_retrieve_apply_f64(ref(self._ap), None if self._dirs is None else ref(self._dirs), h),
-                       "crt_hip_retrieve_apply_f64")
-            if self._leaf is not None:
-                self._leaf.launch(lib, self._ap.p, self.npar, self.bands, h)
-            t = self.tangent
-            if t is not None and self.sun is None:
-                _lib.check(lib.crt_hip_g_dparam_f64(ref(self._c), t.dg_table.data_ptr(), t.dg_at_psi.data_ptr(), h), "crt_hip_g_dparam_f64")
-            elif t is not None:
-                _lib.check(lib.crt_hip_g_dparam_series_f64(ref(self._c), ref(self._s), t.dg_table.data_ptr(), t.dg_at_psi.data_ptr(), h),
-                           "crt_hip_g_dparam_series_f64")
-            self.jac(s)
-            self.fwd(s, flags=self._fwd_flags)
-            _lib.check(lib.crt_hip_lm_step_f64(ref(self._prob), self._obs, len(self.keys), ref(self._state), h), "crt_hip_lm_step_f64")
         return self
 
     def run(self, niter, stream=None):
@@ -2372,17 +2361,113 @@ class RetrievalPlan:
             return self.cov * (2.0 * self.cost / (self.nobs() - self.npar))[:, None, None]
 
 
+class RetrievalPlan(_LmPlan):
+    """A Levenberg-Marquardt retrieval of a parameter vector of every column from sensor-band observations, with the whole loop on the
+    device (include/crt1d_hip_retrieve.h): no host synchronisation between steps, no allocation after construction.
+
+    ``cols``, ``bands`` (with ``sun``: a :class:`SunSeries` that supplies the sun angles and the incoming spectra) are the base state;
+    ``y[k]`` are the observations of the sums :class:`SensorLevelsPlan` (``sun``: :class:`SensorLevelsSeriesPlan`) gives for ``keys``,
+    each ``(ncol, [nt,] nsel, nsens)``; ``inv_sigma[k]`` their weights (``None`` / a missing key: ones; an entry 0: not observed, its
+    ``y`` may be NaN).  The parameters, in the order of ``SensorJacPlan.params``: the coefficients of the ``ntan`` directions
+    ``d_leaf_r / d_leaf_t / d_soil_r`` added to the base spectra; ``"lai"`` (``lai=True``): the log of a scale of the base LAI profile;
+    ``"leaf"`` (``leaf=True``): the column's ``g_param`` itself (``wrt="param"`` of :func:`leaf_tangent`; ``mla`` stays fixed).  For the
+    parameterless leaf-angle kinds and ``G_TABLE`` columns ``dG`` is zero: the parameter is dead there and stays where it started.
+    ``p0 (ncol, npar)`` or ``(npar,)``: the starting point (default: zeros, and ``cols.g_param`` for ``"leaf"``); ``lo``, ``hi`` ``(npar,)``:
+    bounds, which also keep the optics physical -- nothing else clamps them; ``prior``, ``inv_sigma_prior`` ``(ncol, npar)`` or ``(npar,)``:
+    a Gaussian prior.  ``lam0`` and the options ``lam_up, lam_down, lam_min, lam_max, xtol, ftol`` are those of the header.
+
+    :meth:`step` is five launches in a row: ``k_retrieve_apply`` writes the working :class:`Columns` / :class:`Bands` from the trial
+    point; ``crt_hip_g_dparam_f64`` refills the leaf-angle tangent; the :class:`SensorJacPlan` (``sun``: :class:`SensorJacSeriesPlan`)
+    bound to the working tensors; the forward sums on its workspace with ``FLAG_SKIP_PRECOMPUTE``; ``k_lm_step``.  The first step
+    evaluates ``p0`` and is always accepted.  n79 and zq run the composed Jacobian plan (workspaces and allocations of its own) and the
+    forward plan with its own precompute; ``4s`` and ``zq_pa`` are a ValueError.  A column's state is bitwise the same alone or in any
+    batch.  float64 only.
+
+    ``leaf_model``: a :class:`crt1d_amd.leaf_model.PlateLeafModel` -- the leaf spectra are the plate model's, and its ``nm`` parameters
+    ``leaf_model.params`` = ``("N", contents...)`` are retrieved in place of coefficients of leaf directions.  The parameter axis is then
+    the model's parameters, the ``ns`` soil directions ``d_soil_r`` (``"dir0"``, ...), ``"lai"``, ``"leaf"``, with ``nm + ns <= 8``;
+    ``d_leaf_r`` / ``d_leaf_t`` are a ValueError; ``lo`` / ``hi`` are required and must keep ``N`` inside [1, 4] and every content
+    ``>= 0``; ``p0`` is required; ``bands.leaf_r / leaf_t`` are not used.  The plan owns per-column direction arrays of ``nm + ns`` rows
+    (``3 x ncol x (nm + ns) x nb x 8`` bytes), and :meth:`step` is one launch more: ``k_retrieve_apply`` with the leaf directions left out,
+    then ``crt_hip_plate_leaf_f64`` on the same parameter array, which writes the working leaf spectra and the model's partials into
+    the leaf rows, then the launches above."""
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, y, *, keys, sun=None, d_leaf_r=None, d_leaf_t=None,
+                 d_soil_r=None, lai=True, leaf=False, p0=None, lo=None, hi=None, inv_sigma=None, prior=None, inv_sigma_prior=None,
+                 leaf_model=None, mu_s=0.501, tau_d_method="quad", **options):
+        static = self._static(scheme, cols, bands, levels, sensors, y, keys=keys, sun=sun, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t,
+                              d_soil_r=d_soil_r, lai=lai, leaf=leaf, p0=p0, lo=lo, hi=hi, inv_sigma=inv_sigma, prior=prior,
+                              inv_sigma_prior=inv_sigma_prior, leaf_model=leaf_model, tau_d_method=tau_d_method, **options)
+        self._construct(*static, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, sensors=sensors, y=y,
+                        inv_sigma=inv_sigma, mu_s=mu_s, tau_d_method=tau_d_method)
+
+    @classmethod
+    def _static(cls, scheme, cols, bands, levels, sensors, y, *, keys, sun=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True,
+                leaf=False, p0=None, lo=None, hi=None, inv_sigma=None, prior=None, inv_sigma_prior=None, leaf_model=None, mu_s=0.501,
+                tau_d_method="quad", **options):
+        """The constructor's arguments -> (keys, the parameter axis, the LM options): every check that needs neither a column nor a
+        device."""
+        _SolvePlan._check_options(_SolvePlan, scheme, tau_d_method)
+        if scheme not in RETRIEVE_SCHEMES:
+            raise ValueError(f"scheme {scheme!r} has no retrieval; served: " + ", ".join(RETRIEVE_SCHEMES))
+        keys = _level_keys(keys)
+        if not isinstance(sensors, SensorSet):
+            raise TypeError("sensors must be a SensorSet")
+        if sun is not None:
+            _need_sun_series(sun)
+        _check_obs(y, inv_sigma, keys, "(ncol, [nt,] nsel, nsens)")
+        axis = _ParamAxis(d_leaf_r, d_leaf_t, d_soil_r, lai, leaf, leaf_model)
+        o = _lm_options(lo, hi, axis.npar, options)
+        _need_f64_bands(bands, "retrieval")
+        _check_start(leaf_model, lo, hi, p0, prior, inv_sigma_prior)
+        return keys, axis, o
+
+    def _inner(self, scheme, levels, sun, sensors, y, inv_sigma, keys, mu_s, tau_d_method, **axis):
+        """The Jacobian plan and the forward plan on its workspace, the observations against the forward sums.  -> the Jacobian plan"""
+        f = dict(keys=keys, mu_s=mu_s, tau_d_method=tau_d_method)
+        a = (scheme, self.cols, self.bands) + (() if sun is None else (sun,)) + (levels, sensors)
+        self.jac = (SensorJacPlan if sun is None else SensorJacSeriesPlan)(*a, **axis, **f)
+        self.fwd = (SensorLevelsPlan if sun is None else SensorLevelsSeriesPlan)(*a, **f, workspace=getattr(self.jac, "workspace", None))
+        self._fwd_flags = 0 if self.jac._composed else _lib.FLAG_SKIP_PRECOMPUTE
+        shape = tuple(self.fwd.out[keys[0]].shape)
+        self.nrow = int(torch.Size(shape[1:]).numel())
+
+        def obs(v, name):
+            v = torch.as_tensor(v, dtype=torch.float64).to(self.cols.device).contiguous()
+            if tuple(v.shape) != shape:
+                raise ValueError(f"{name} must be {shape}, got {tuple(v.shape)}")
+            return v
+
+        self.y = {k: obs(y[k], f"y[{k!r}]") for k in keys}
+        self.inv_sigma = {k: obs(inv_sigma[k], f"inv_sigma[{k!r}]") for k in keys if inv_sigma is not None and k in inv_sigma}
+        ptr = lambda v: None if v is None else v.data_ptr()  # noqa: E731
+        self._obs = (_lib.CrtLmObs * len(keys))(*[
+            _lib.CrtLmObs(self.nrow, ptr(self.fwd.out[k]), ptr(self.jac.out[k]), ptr(self.y[k]), ptr(self.inv_sigma.get(k))) for k in keys])
+        return self.jac
+
+    def step(self, stream=None):
+        """One iteration on ``stream`` (default: torch's current stream): apply, tangent, Jacobian, forward sums, ``k_lm_step``."""
+        dev = self.cols.device
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.device(dev):
+            self._evaluate(self._ap, s)
+            self.jac(s)
+            self.fwd(s, flags=self._fwd_flags)
+            _lib.check(self.lib.crt_hip_lm_step_f64(ctypes.byref(self._prob), self._obs, len(self.keys), ctypes.byref(self._state), s.cuda_stream),
+                       "crt_hip_lm_step_f64")
+        return self
+
+
+
 def retrieve(scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, y, *, keys, niter=20, **kw):
     """One-shot :class:`RetrievalPlan`: ``niter`` steps from ``p0``; what ``plan.result()`` returns, and ``"cov"``, ``plan.covariance()``."""
-    static = {k: v for k, v in kw.items() if k not in ("p0", "prior", "inv_sigma_prior", "mu_s")}
-    _retrieve_static(scheme, sensors, y, keys, bands=bands, **static)  # (before any device is touched)
-    if kw.get("leaf_model") is not None:
-        _leaf_model_start(kw["leaf_model"], kw.get("lo"), kw.get("hi"), kw.get("p0"))
+    RetrievalPlan._static(scheme, cols, bands, levels, sensors, y, keys=keys, **kw)  # (before any device is touched)
     with torch.cuda.device(cols.device):
         plan = RetrievalPlan(scheme, cols, bands, levels, sensors, y, keys=keys, **kw).run(niter)
         res = plan.result()
         res["cov"] = plan.covariance()
     return res
+
 
 
 # ---- the retrieval from the level spectra themselves (include/crt1d_hip_specfit.h) -------------------------------------------------------
@@ -2397,44 +2482,20 @@ def spectral_normal_workspace_bytes(scheme, ncol, nz, nb, nsel, nkey, npar):
     return int(_lib.load().crt_hip_spectral_normal_workspace_bytes(_lib.SCHEME_IDS[scheme], ncol, nz, nb, nsel, nkey, npar))
 
 
-def _spectral_static(scheme, y, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, leaf=False,
-                     tau_d_method="quad", bands=None, sun=None, leaf_model=None):
-    """The checks of the spectral plans that touch no device (``sun``: the series forms, whose arrays carry a sun-state axis).
-    -> (keys in ``LEVEL_KEYS`` order, ntan, npar)"""
-    import numpy as np
-
+def _spectral_static(scheme, y, keys, inv_sigma, tau_d_method, bands, sun, **axis):
+    """The checks of the spectral plans that touch no device (``sun``: the series forms, whose arrays carry a sun-state axis; ``axis``: the
+    arguments of :class:`_ParamAxis`).  -> (keys in ``LEVEL_KEYS`` order, the parameter axis)"""
     _SolvePlan._check_options(_SolvePlan, scheme, tau_d_method)
     if scheme not in SPECTRAL_RETRIEVE_SCHEMES:
         raise ValueError(f"scheme {scheme!r} has no spectral retrieval; served: " + ", ".join(SPECTRAL_RETRIEVE_SCHEMES))
-    if sun is not None and (not isinstance(sun, SunSeries) or isinstance(sun, SunSeriesF32)):
-        raise TypeError("sun must be a SunSeries (float64 spectra)")
-    axes = "(ncol, nsel, nb)" if sun is None else "(ncol, nt, nsel, nb)"
+    if sun is not None:
+        _need_sun_series(sun)
     keys = _level_keys(keys)
     keys = tuple(k for k in LEVEL_KEYS if k in keys)
-    shapes = set()
-    for name, d in (("y", y), ("inv_sigma", inv_sigma)):
-        if d is None and name == "inv_sigma":
-            continue
-        if not isinstance(d, dict):
-            raise TypeError(f"{name} must be a dict {{key: {axes}}}")
-        if extra := [k for k in d if k not in keys]:
-            raise ValueError(f"{name} has the keys {extra}, which are not in keys = {keys}")
-        for k, v in d.items():
-            shape = tuple(v.shape) if hasattr(v, "shape") else np.shape(v)
-            if len(shape) != (3 if sun is None else 4):
-                raise ValueError(f"{name}[{k!r}] must be {axes}, got {shape}")
-            shapes.add(shape)
-    if missing := [k for k in keys if k not in y]:
-        raise ValueError(f"y lacks the keys {missing} of keys = {keys}")
-    if len(shapes) > 1:
-        raise ValueError(f"the arrays of y and inv_sigma must share one shape {axes}, got {sorted(shapes)}")
-    ntan = _sensjac_ntan(d_leaf_r, d_leaf_t, d_soil_r) if leaf_model is None else _leaf_model_ntan(leaf_model, d_leaf_r, d_leaf_t, d_soil_r)
-    npar = ntan + bool(lai) + bool(leaf)
-    if npar == 0:
-        raise ValueError("no parameter at all: give a direction, lai=True or a leaf-angle tangent")
-    if bands is not None and bands.dtype != torch.float64:
-        raise TypeError("the spectral retrieval has no f32 storage form: bands must be float64")
-    return keys, ntan, npar
+    _check_obs(y, inv_sigma, keys, "(ncol, nsel, nb)" if sun is None else "(ncol, nt, nsel, nb)", 3 if sun is None else 4)
+    axis = _ParamAxis(**axis)
+    _need_f64_bands(bands, "spectral retrieval")
+    return keys, axis
 
 
 def _spectral_shapes(cols, bands, levels, y, inv_sigma, nkey, npar, sun=None):
@@ -2468,18 +2529,30 @@ class SpectralNormalPlan(_LevelsDerivPlan):
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None,
                  lai=True, tangent=None, fwd=False, mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
-        if tangent is not None and not isinstance(tangent, LeafTangent):
-            raise TypeError("tangent must be a LeafTangent")
-        self._build(scheme, cols, bands, None, levels, y, keys, inv_sigma, d_leaf_r, d_leaf_t, d_soil_r, lai, tangent, False, fwd, mu_s,
-                    tau_d_method, out, workspace)
+        self._build(None, scheme, cols, bands, levels, y, keys=keys, inv_sigma=inv_sigma, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r,
+                    lai=lai, tangent=tangent, fwd=fwd, mu_s=mu_s, tau_d_method=tau_d_method, out=out, workspace=workspace)
 
-    def _build(self, scheme, cols, bands, sun, levels, y, keys, inv_sigma, d_leaf_r, d_leaf_t, d_soil_r, lai, tangent, per_step, fwd, mu_s,
-               tau_d_method, out, workspace):
-        """The construction of this plan (``sun`` None) and of :class:`SpectralNormalSeriesPlan` (arrays with a sun-state axis)."""
+    _series = False  # SpectralNormalSeriesPlan: a sun-angle series in front of the levels, arrays with a sun-state axis
+
+    @classmethod
+    def _static(cls, scheme, cols, bands, levels, y, **kw):
+        """The constructor's arguments (``kw``: its keywords) -> (keys in ``LEVEL_KEYS`` order, the parameter axis, the normalized
+        levels): every check that needs no device."""
+        return cls._static_of(None, scheme, cols, bands, levels, y, **kw)
+
+    @classmethod
+    def _static_of(cls, sun, scheme, cols, bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True,
+                   tangent=None, per_step=False, fwd=False, mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
+        _check_tangent(tangent, sun, cls._series)
+        keys, axis = _spectral_static(scheme, y, keys, inv_sigma, tau_d_method, bands, sun, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t,
+                                      d_soil_r=d_soil_r, lai=lai, tangent=tangent)
+        return keys, axis, _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), axis.npar, sun)
+
+    def _build(self, sun, scheme, cols, bands, levels, y, *, inv_sigma, fwd, mu_s, tau_d_method, out, workspace, per_step=False, **kw):
+        """The construction of this plan (``sun`` None) and of :class:`SpectralNormalSeriesPlan`."""
+        keys, axis, self.levels = self._static_of(sun, scheme, cols, bands, levels, y, inv_sigma=inv_sigma, tau_d_method=tau_d_method, **kw)
         series = {} if sun is None else {"sun": sun}
-        keys, ntan, npar = _spectral_static(scheme, y, keys, inv_sigma, d_leaf_r, d_leaf_t, d_soil_r, lai, tangent is not None, tau_d_method,
-                                            bands, **series)
-        self.levels, self.keys = _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), npar, **series), keys
+        self.keys = keys
         ncol, nsel, nb, dev = cols.ncol, len(self.levels), bands.nb, cols.device
         nts = () if sun is None else (sun.nt,)
         shape = (ncol, *nts, nsel, nb)
@@ -2487,13 +2560,10 @@ class SpectralNormalPlan(_LevelsDerivPlan):
         obs = lambda v: torch.as_tensor(v, dtype=torch.float64).to(dev).contiguous()  # noqa: E731
         self.y = {k: obs(y[k]) for k in keys}
         self.inv_sigma = {k: obs(inv_sigma[k]) for k in keys if inv_sigma is not None and k in inv_sigma}
-        dirs = {n: _jvp_direction(d, "d_" + n, ncol, nb, dev) for n, d in zip(JAC_PARAMS, (d_leaf_r, d_leaf_t, d_soil_r)) if d is not None}
-        per_col = any(d.shape[0] != 1 for d in dirs.values()) and ncol != 1
-        self.dirs = {n: (d.expand(ncol, -1, -1) if per_col else d).contiguous() for n, d in dirs.items()}
-        if tangent is not None and (tangent.dg_table.shape[0] != ncol or tangent.dg_table.device != dev):
-            raise ValueError("the tangent must have the columns' ncol and device")
-        self.tangent, self.ntan, self.npar = tangent, ntan, npar
-        self.params = tuple(f"dir{k}" for k in range(ntan)) + (("lai",) if lai else ()) + (("leaf",) if tangent is not None else ())
+        self._axis = axis.bind(ncol, nb, dev)
+        self.dirs, self.tangent, self.ntan, self.npar, self.params = axis.dirs, axis.tangent, axis.ntan, axis.npar, axis.params
+        self._dirs, self._tan = axis.c_dirs, axis.c_tan
+        npar = axis.npar
         ntri = npar * (npar + 1) // 2
         shapes = {"A": (ncol, ntri), "g": (ncol, npar), "c2": (ncol,)}
         if per_step:
@@ -2513,11 +2583,6 @@ class SpectralNormalPlan(_LevelsDerivPlan):
         self._out_sums = struct(*sums, None, None, None, None)
         self._out_fwd = struct(*sums, *[ptr(self.out.get("fwd", {}), k) for k in LEVEL_KEYS])
         self._lev = (ctypes.c_int32 * nsel)(*self.levels)
-        self._dirs = None
-        if ntan:
-            self._dirs = _lib.CrtOpticsDirs(ntan, ntan * nb if per_col else 0,
-                                            *[self.dirs[n].data_ptr() if n in self.dirs else None for n in JAC_PARAMS])
-        self._tan = None if tangent is None else tangent.c_struct()
         if sun is None:
             need = spectral_normal_workspace_bytes(scheme, ncol, cols.nz, nb, nsel, len(keys), npar)
         else:
@@ -2541,9 +2606,7 @@ class SpectralNormalPlan(_LevelsDerivPlan):
 
 def spectral_normal(scheme, cols: Columns, bands: Bands, levels, y, *, keys, **kw):
     """One-shot :class:`SpectralNormalPlan`: ``{"A", "g", "c2"}`` (and ``"fwd"`` with ``fwd=True``) at the sorted levels."""
-    k, _, npar = _spectral_static(scheme, y, keys, kw.get("inv_sigma"), kw.get("d_leaf_r"), kw.get("d_leaf_t"), kw.get("d_soil_r"),
-                                  kw.get("lai", True), kw.get("tangent") is not None, kw.get("tau_d_method", "quad"), bands)
-    _spectral_shapes(cols, bands, levels, y, kw.get("inv_sigma"), len(k), npar)  # (all before any device is touched)
+    SpectralNormalPlan._static(scheme, cols, bands, levels, y, keys=keys, **kw)  # (before any device is touched)
     with torch.cuda.device(cols.device):
         return SpectralNormalPlan(scheme, cols, bands, levels, y, keys=keys, **kw)()
 
@@ -2552,16 +2615,6 @@ def spectral_normal_series_workspace_bytes(scheme, ncol, nz, nb, nt, nsel, nkey,
     """Device workspace of a :class:`SpectralNormalSeriesPlan` call: the records of :func:`levels_series_workspace_bytes` at the same
     offsets, the side records of the LAI and of the leaf-angle derivative, and the slice sums of every (column, t)."""
     return int(_lib.load().crt_hip_spectral_normal_series_workspace_bytes(_lib.SCHEME_IDS[scheme], ncol, nz, nb, nt, nsel, nkey, npar))
-
-
-def _spectral_series_static(sun, tangent):
-    """The checks of the series form that touch no device, in front of those of :func:`_spectral_static`."""
-    if not isinstance(sun, SunSeries) or isinstance(sun, SunSeriesF32):
-        raise TypeError("sun must be a SunSeries (float64 spectra)")
-    if tangent is not None and not isinstance(tangent, LeafTangentSeries):
-        raise TypeError("tangent must be a LeafTangentSeries")
-    if tangent is not None and tangent.nt != sun.nt:
-        raise ValueError(f"the tangent has nt = {tangent.nt} sun states, the series {sun.nt}")
 
 
 class SpectralNormalSeriesPlan(SpectralNormalPlan):
@@ -2577,42 +2630,27 @@ class SpectralNormalSeriesPlan(SpectralNormalPlan):
     :class:`LeafTangentSeries` of the same ``nt`` or ``None``.  The canopy part of the column precompute and the side precomputes run once
     per column; the workspace starts with the records of a :class:`LevelsSeriesPlan`, which can run on it with ``FLAG_SKIP_PRECOMPUTE``."""
 
-    _entry_name, _ws_query = "crt_hip_spectral_normal_series_f64", "crt_hip_spectral_normal_series_workspace_bytes"
+    _entry_name, _ws_query, _series = "crt_hip_spectral_normal_series_f64", "crt_hip_spectral_normal_series_workspace_bytes", True
 
     def __init__(self, scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None,
                  d_soil_r=None, lai=True, tangent=None, per_step=False, fwd=False, mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
-        _spectral_series_static(sun, tangent)
-        self._build(scheme, cols, bands, sun, levels, y, keys, inv_sigma, d_leaf_r, d_leaf_t, d_soil_r, lai, tangent, per_step, fwd, mu_s,
-                    tau_d_method, out, workspace)
+        self._build(sun, scheme, cols, bands, levels, y, keys=keys, inv_sigma=inv_sigma, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r,
+                    lai=lai, tangent=tangent, per_step=per_step, fwd=fwd, mu_s=mu_s, tau_d_method=tau_d_method, out=out, workspace=workspace)
+
+    @classmethod
+    def _static(cls, scheme, cols, bands, sun, levels, y, **kw):
+        return cls._static_of(sun, scheme, cols, bands, levels, y, **kw)
 
 
 def spectral_normal_series(scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, y, *, keys, **kw):
     """One-shot :class:`SpectralNormalSeriesPlan`: ``{"A", "g", "c2"}`` (``per_step=True``: and ``"A_t", "g_t", "c2_t"``; ``fwd=True``: and
     ``"fwd"``) at the sorted levels."""
-    _spectral_series_static(sun, kw.get("tangent"))
-    k, _, npar = _spectral_static(scheme, y, keys, kw.get("inv_sigma"), kw.get("d_leaf_r"), kw.get("d_leaf_t"), kw.get("d_soil_r"),
-                                  kw.get("lai", True), kw.get("tangent") is not None, kw.get("tau_d_method", "quad"), bands, sun)
-    _spectral_shapes(cols, bands, levels, y, kw.get("inv_sigma"), len(k), npar, sun)  # (all before any device is touched)
+    SpectralNormalSeriesPlan._static(scheme, cols, bands, sun, levels, y, keys=keys, **kw)  # (before any device is touched)
     with torch.cuda.device(cols.device):
         return SpectralNormalSeriesPlan(scheme, cols, bands, sun, levels, y, keys=keys, **kw)()
 
 
-def _lm_options(lo, hi, npar, opts):
-    """The bounds and Levenberg-Marquardt options of a retrieval plan, checked without a device.  -> LM options"""
-    import numpy as np
-
-    for name, v in (("lo", lo), ("hi", hi)):
-        if v is not None and tuple(np.shape(v)) != (npar,):
-            raise ValueError(f"{name} must be (npar,) = ({npar},), got {tuple(np.shape(v))}")
-    if unknown := [k for k in opts if k not in LM_OPTIONS]:
-        raise TypeError(f"unknown options {unknown}; the Levenberg-Marquardt options are {tuple(LM_OPTIONS)}")
-    o = {k: float(opts.get(k, v)) for k, v in LM_OPTIONS.items()}
-    if not (o["lam0"] > 0 and o["lam_up"] > 1 and 0 < o["lam_down"] <= 1 and 0 <= o["lam_min"] <= o["lam_max"] and o["xtol"] >= 0 and o["ftol"] >= 0):
-        raise ValueError("the options need lam0 > 0, lam_up > 1, 0 < lam_down <= 1, 0 <= lam_min <= lam_max, xtol >= 0 and ftol >= 0")
-    return o
-
-
-class SpectralRetrievalPlan:
+class SpectralRetrievalPlan(_LmPlan):
     """:class:`RetrievalPlan` without the sensors: a Levenberg-Marquardt retrieval of a parameter vector of every column from the level
     spectra themselves, band by band (include/crt1d_hip_specfit.h), with the whole loop on the device.  ``y[k] (ncol, nsel, nb)`` are
     the observed spectra of ``keys`` at ``levels`` (what :class:`LevelsPlan` gives), ``inv_sigma[k]`` their weights (``None`` / a missing
@@ -2636,110 +2674,33 @@ class SpectralRetrievalPlan:
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None,
                  lai=True, leaf=False, p0=None, lo=None, hi=None, prior=None, inv_sigma_prior=None, sun=None, leaf_model=None, mu_s=0.501,
                  tau_d_method="quad", **options):
-        keys, ntan, npar = _spectral_static(scheme, y, keys, inv_sigma, d_leaf_r, d_leaf_t, d_soil_r, lai, leaf, tau_d_method, bands, sun,
-                                            leaf_model)
-        o = _lm_options(lo, hi, npar, options)
-        if leaf_model is not None:
-            _leaf_model_start(leaf_model, lo, hi, p0)
-        if (prior is None) != (inv_sigma_prior is None):
-            raise ValueError("prior and inv_sigma_prior go together")
-        _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), npar, sun)
-        self.lib = _lib.load()
-        self.scheme, self.keys, self.sun, self.options = scheme, keys, sun, o
-        ncol, nz, nb, dev = cols.ncol, cols.nz, bands.nb, cols.device
-        f64 = dict(dtype=torch.float64, device=dev)
-        new = lambda *shape: torch.zeros(shape, **f64)  # noqa: E731
-        # the base state and the working inputs k_retrieve_apply overwrites
-        self.base_cols, self.base_bands = cols, bands
-        self._base_stride = bands.col_stride(ncol)
-        rows = lambda v: None if v is None else v.expand(ncol, -1).contiguous()  # noqa: E731
-        self.bands = Bands(rows(bands.I_dr0), rows(bands.I_df0), new(ncol, nb), new(ncol, nb), None if bands.soil_r is None else new(ncol, nb))
-        self.cols = Columns(cols.psi, cols.lai.clone(), cols.g_kind, cols.g_param.clone(), cols.mla, cols.g_at_psi, cols.g_table)
-        self.lai_scale = torch.ones((ncol,), **f64)
-        self.tangent = None  # refilled in place every step
-        if leaf:
-            self.tangent = (LeafTangent(new(ncol, _lib.NQ), new(ncol)) if sun is None
-                            else LeafTangentSeries(new(ncol, _lib.NQ), new(ncol, sun.nt)))
-        # the leaf model: the plan owns the per-column directions k_plate_leaf writes and the normal plan reads
-        self.leaf_model = leaf_model
-        self._leaf = None if leaf_model is None else _PlateLeafBinding(leaf_model, ncol, nb, d_soil_r, dev)
-        if self._leaf is not None:
-            d_leaf_r, d_leaf_t, d_soil_r = self._leaf.d_leaf_r, self._leaf.d_leaf_t, self._leaf.d_soil_r
-        d = dict(keys=keys, inv_sigma=inv_sigma, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r, lai=bool(lai), tangent=self.tangent,
-                 fwd=True, mu_s=mu_s, tau_d_method=tau_d_method)
-        if sun is None:
-            self.normal = SpectralNormalPlan(scheme, self.cols, self.bands, levels, y, **d)
-        else:
-            self.normal = SpectralNormalSeriesPlan(scheme, self.cols, self.bands, sun, levels, y, **d)
+        keys, axis, o, levels = self._static(scheme, cols, bands, levels, y, keys=keys, inv_sigma=inv_sigma, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t,
+                                             d_soil_r=d_soil_r, lai=lai, leaf=leaf, p0=p0, lo=lo, hi=hi, prior=prior,
+                                             inv_sigma_prior=inv_sigma_prior, sun=sun, leaf_model=leaf_model, tau_d_method=tau_d_method, **options)
+        self._construct(keys, axis, o, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, y=y, inv_sigma=inv_sigma,
+                        mu_s=mu_s, tau_d_method=tau_d_method)
+
+    @classmethod
+    def _static(cls, scheme, cols, bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, leaf=False,
+                p0=None, lo=None, hi=None, prior=None, inv_sigma_prior=None, sun=None, leaf_model=None, mu_s=0.501, tau_d_method="quad",
+                **options):
+        """The constructor's arguments -> (keys in ``LEVEL_KEYS`` order, the parameter axis, the LM options, the normalized levels): every
+        check that needs no device."""
+        keys, axis = _spectral_static(scheme, y, keys, inv_sigma, tau_d_method, bands, sun, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t,
+                                      d_soil_r=d_soil_r, lai=lai, leaf=leaf, leaf_model=leaf_model)
+        o = _lm_options(lo, hi, axis.npar, options)
+        _check_start(leaf_model, lo, hi, p0, prior, inv_sigma_prior)
+        return keys, axis, o, _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), axis.npar, sun)
+
+    def _inner(self, scheme, levels, sun, y, **kw):
+        """The normal plan on the working tensors, which holds the observations (``fwd`` kept for :meth:`fitted`, not written by a step)."""
+        a = (scheme, self.cols, self.bands) + (() if sun is None else (sun,)) + (levels, y)
+        self.normal = (SpectralNormalPlan if sun is None else SpectralNormalSeriesPlan)(*a, fwd=True, **kw)
         self.normal.write_fwd = False
-        self.params, self.levels, self.npar, self.ntan = self.normal.params, self.normal.levels, npar, ntan
         self.y, self.inv_sigma = self.normal.y, self.normal.inv_sigma
-        self.nrow = (1 if sun is None else sun.nt) * len(self.levels) * nb
-        self._dirs = self.normal._dirs
-        if self._leaf is not None:
-            self._leaf.bound_to(self.normal)
-            self.params = self._leaf.names + self.params[ntan:]
-            self._dirs = self._leaf.apply_dirs
-
-        def per_col(v, name, width=npar):
-            v = torch.as_tensor(v, dtype=torch.float64).to(dev)
-            if v.ndim == 1:
-                v = v[None]
-            if v.ndim != 2 or v.shape[1] != width or v.shape[0] not in (1, ncol):
-                raise ValueError(f"{name} must be (ncol, npar) or (npar,) with ncol = {ncol}, npar = {width}")
-            return v.expand(ncol, -1).contiguous()
-
-        self.lo = None if lo is None else torch.as_tensor(lo, dtype=torch.float64).to(dev).contiguous()
-        self.hi = None if hi is None else torch.as_tensor(hi, dtype=torch.float64).to(dev).contiguous()
-        self.prior = None if prior is None else per_col(prior, "prior")
-        self.inv_sigma_prior = None if prior is None else per_col(inv_sigma_prior, "inv_sigma_prior")
-        if p0 is None:
-            p0 = new(ncol, npar)
-            if leaf:
-                p0[:, npar - 1] = cols.g_param
-        self._p0 = per_col(p0, "p0").clone()
-        # the state
-        ntri = npar * (npar + 1) // 2
-        i32 = dict(dtype=torch.int32, device=dev)
-        self.p, self.p_trial, self.cost, self.lam = new(ncol, npar), new(ncol, npar), new(ncol), new(ncol)
-        self.A, self.g = new(ncol, ntri), new(ncol, npar)
-        self.status, self.naccept, self.nreject = (torch.zeros((ncol,), **i32) for _ in range(3))
-        self.cov = new(ncol, npar, npar)
-        # the structs of the entries
-        ptr = lambda v: None if v is None else v.data_ptr()  # noqa: E731
-        b, w, c = bands, self.bands, self.cols
-        apply = lambda p: _lib.CrtRetrieveApply(ncol, nz, nb, npar, ntan if lai else -1, ntan + bool(lai) if leaf else -1,  # noqa: E731
-                                                self._base_stride, ptr(b.leaf_r), ptr(b.leaf_t), ptr(b.soil_r), ptr(cols.lai), ptr(p),
-                                                ptr(w.leaf_r), ptr(w.leaf_t), ptr(w.soil_r), ptr(self.lai_scale), ptr(c.lai), ptr(c.g_param))
-        self._ap, self._ap_p = apply(self.p_trial), apply(self.p)
-        self._prob = _lib.CrtLmProblem(ncol, npar, o["lam_up"], o["lam_down"], o["lam_min"], o["lam_max"], o["xtol"], o["ftol"], ptr(self.lo),
-                                       ptr(self.hi), ptr(self.prior), ptr(self.inv_sigma_prior))
+        self.nrow = (1 if sun is None else sun.nt) * len(self.normal.levels) * self.bands.nb
         self._blk = (_lib.CrtLmNormalBlock * 1)(_lib.CrtLmNormalBlock(*[self.normal.out[k].data_ptr() for k in ("A", "g", "c2")]))
-        self._state = _lib.CrtLmState(*[ptr(v) for v in (self.p, self.p_trial, self.cost, self.lam, self.A, self.g, self.status, self.naccept,
-                                                          self.nreject)])
-        self._c = c.c_struct()
-        self._s = None if sun is None else sun.c_struct()
-        self.reset()
-
-    reset = RetrievalPlan.reset
-    run = RetrievalPlan.run
-    result = RetrievalPlan.result
-    nobs = RetrievalPlan.nobs
-    covariance = RetrievalPlan.covariance
-
-    def _evaluate(self, ap, s):
-        """The working inputs from the parameters behind ``ap``, the tangent refill and the normal plan, on stream ``s``."""
-        lib, ref, h = self.lib, ctypes.byref, s.cuda_stream
-        _lib.check(lib.crt_hip_retrieve_apply_f64(ref(ap), None if self._dirs is None else ref(self._dirs), h), "crt_hip_retrieve_apply_f64")
-        if self._leaf is not None:
-            self._leaf.launch(lib, ap.p, self.npar, self.bands, h)
-        t = self.tangent
-        if t is not None and self.sun is None:
-            _lib.check(lib.crt_hip_g_dparam_f64(ref(self._c), t.dg_table.data_ptr(), t.dg_at_psi.data_ptr(), h), "crt_hip_g_dparam_f64")
-        elif t is not None:
-            _lib.check(lib.crt_hip_g_dparam_series_f64(ref(self._c), ref(self._s), t.dg_table.data_ptr(), t.dg_at_psi.data_ptr(), h),
-                       "crt_hip_g_dparam_series_f64")
-        self.normal(s)
+        return self.normal
 
     def step(self, stream=None):
         """One iteration on ``stream`` (default: torch's current stream): apply, tangent, normal equations, ``k_lm_step_normal``."""
@@ -2747,6 +2708,7 @@ class SpectralRetrievalPlan:
         s = torch.cuda.current_stream(dev) if stream is None else stream
         with torch.cuda.device(dev):
             self._evaluate(self._ap, s)
+            self.normal(s)
             _lib.check(self.lib.crt_hip_lm_step_normal_f64(ctypes.byref(self._prob), self._blk, 1, ctypes.byref(self._state), s.cuda_stream),
                        "crt_hip_lm_step_normal_f64")
         return self
@@ -2760,6 +2722,7 @@ class SpectralRetrievalPlan:
             self.normal.write_fwd = True
             try:
                 self._evaluate(self._ap_p, s)
+                self.normal(s)
             finally:
                 self.normal.write_fwd = False
             with torch.cuda.stream(s):
@@ -2769,13 +2732,7 @@ class SpectralRetrievalPlan:
 def retrieve_spectral(scheme, cols: Columns, bands: Bands, levels, y, *, keys, niter=20, **kw):
     """One-shot :class:`SpectralRetrievalPlan`: ``niter`` steps from ``p0``; what ``plan.result()`` returns, and ``"cov"``,
     ``plan.covariance()``."""
-    static = {k: kw[k] for k in ("inv_sigma", "d_leaf_r", "d_leaf_t", "d_soil_r", "lai", "leaf", "tau_d_method", "sun", "leaf_model") if k in kw}
-    k, _, npar = _spectral_static(scheme, y, keys, bands=bands, **static)  # (before any device is touched)
-    _lm_options(kw.get("lo"), kw.get("hi"), npar, {n: v for n, v in kw.items() if n not in static and n not in
-                                                  ("p0", "lo", "hi", "prior", "inv_sigma_prior", "mu_s")})
-    _spectral_shapes(cols, bands, levels, y, kw.get("inv_sigma"), len(k), npar, kw.get("sun"))
-    if kw.get("leaf_model") is not None:
-        _leaf_model_start(kw["leaf_model"], kw.get("lo"), kw.get("hi"), kw.get("p0"))
+    SpectralRetrievalPlan._static(scheme, cols, bands, levels, y, keys=keys, **kw)  # (before any device is touched)
     with torch.cuda.device(cols.device):
         plan = SpectralRetrievalPlan(scheme, cols, bands, levels, y, keys=keys, **kw).run(niter)
         res = plan.result()
@@ -2943,24 +2900,25 @@ class _PlateLeafBinding:
     -- leaf rows ``0 .. nm - 1`` written by ``k_plate_leaf`` at every evaluation and ``nm ..`` zero, soil rows ``0 .. nm - 1`` zero and
     ``nm ..`` the user's directions -- and the launch that writes the working leaf spectra and those rows from a parameter array."""
 
-    def __init__(self, model, ncol, nb, d_soil_r, device):
+    def __init__(self, model, axis, ncol, nb, device):
+        """``axis``: the plan's :class:`_ParamAxis` (static half), which knows ``ntan`` and the user's soil directions."""
         if model.nb != nb:
             raise ValueError(f"the leaf model has {model.nb} bands, the bands {nb}")
-        ns = _sensjac_ntan(None, None, d_soil_r)
-        self.model, self.nm, self.ns, self.ntan = model, model.nm, ns, model.nm + ns
+        self.model, self.nm, self.ns, self.ntan = model, model.nm, axis.ntan - model.nm, axis.ntan
+        ns = self.ns
         new = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=device)  # noqa: E731
         self.d_leaf_r, self.d_leaf_t = new(ncol, self.ntan, nb), new(ncol, self.ntan, nb)
         self.d_soil_r = None
         if ns:
             self.d_soil_r = new(ncol, self.ntan, nb)
-            self.d_soil_r[:, self.nm:] = _jvp_direction(d_soil_r, "d_soil_r", ncol, nb, device)
-        # what k_retrieve_apply reads: no leaf directions (the base spectra are copied), the soil directions or, with none, a zero array
-        self._zero = None if ns else new(self.ntan, nb)
-        soil = self.d_soil_r if ns else self._zero
-        self.apply_dirs = _lib.CrtOpticsDirs(self.ntan, self.ntan * nb if ns and ncol != 1 else 0, None, None, soil.data_ptr())
+            self.d_soil_r[:, self.nm:] = _jvp_direction(axis.given["soil_r"], "d_soil_r", ncol, nb, device)
+        self.dirs = {"leaf_r": self.d_leaf_r, "leaf_t": self.d_leaf_t, **({"soil_r": self.d_soil_r} if ns else {})}  # the inner plan's
+        # what k_retrieve_apply reads: no leaf directions (the base spectra are copied), the soil directions or, with none, a shared zero
+        # array -- an axis of its own, which keeps that array
+        self._apply = _ParamAxis(d_soil_r=self.d_soil_r if ns else new(self.ntan, nb), lai=False).bind(ncol, nb, device)
+        self.apply_dirs = self._apply.c_dirs
         self._m = model.c_struct(ncol, device)
         self._keep = model.tensors(device)
-        self.names = model.params + tuple(f"dir{k}" for k in range(ns))
 
     def bound_to(self, plan):
         """The inner Jacobian / normal plan must read the arrays this binding writes."""

@@ -320,15 +320,21 @@ static void build_args(int scheme, const crt_columns* cols, const crt_bands* ban
   std::memcpy(&sa.tune, o.tune, sizeof sa.tune);
 }
 
+// the records and the incoming spectra of a sun-angle series, as the series kernels read them: canopy records [ncol][can_len] at sa.ws, then
+// sun records [ncol * nt][sun_len] (SeriesArgs, crt_internal.hpp)
+static SeriesArgs series_args(int scheme, const SolveArgs& sa, const crt_sun_series* ser) {
+  return {ser->nt, scheme, sa.nz, can_len(scheme, sa.nz), sun_len(scheme, sa.nz), sa.ws, sa.ws + (size_t)sa.ncol * can_len(scheme, sa.nz),
+          ser->col_stride, ser->I_dr0, ser->I_df0};
+}
+
 // sun-angle series: K0 per column and per (column, t), then one series kernel (integrated outputs or level spectra)
 static int dispatch_series(int scheme, ColArgs ca, SolveArgs sa, int flags, const IntArgs* integ, const LevArgs* lev, const crt_sun_series* ser,
                            hipStream_t s, SensLaunch* sl) {
-  // workspace: canopy records [ncol][can_len], then sun records [ncol * nt][sun_len] (SeriesArgs, crt_internal.hpp)
   double* const sunrec = ca.ws + (size_t)ca.ncol * can_len(scheme, ca.nz);
   ca.psi = ser->psi;
   ca.g_at_psi = ser->g_at_psi;
   sa.I_dr0 = sa.I_df0 = nullptr;  // the spectra come from `sr`
-  const SeriesArgs sr = {ser->nt, scheme, ca.nz, can_len(scheme, ca.nz), sun_len(scheme, ca.nz), sa.ws, sunrec, ser->col_stride, ser->I_dr0, ser->I_df0};
+  const SeriesArgs sr = series_args(scheme, sa, ser);
   if (lev)  // every shape the level series cannot serve is found here, before K0 has written anything
     if (const int st = launch_family_lev(scheme, sa, *lev, s, &sr, true, sl)) return st;
   const int st = (flags & CRT_FLAG_SKIP_PRECOMPUTE) ? init_quadrature(s) : launch_colpre_series(ca, ser->nt, sunrec, s);
@@ -718,6 +724,68 @@ static int levels_deriv_impl(int scheme, const crt_columns* cols, const crt_band
   return launch(sa, la, side, s, false);
 }
 
+// a leaf-angle tangent of either C struct (crt_leaf_tangent, crt_leaf_tangent_series: the same three names); NULL: an empty one
+template <class Tangent>
+static DleafTan dleaf_tan(const Tangent* t) {
+  return t ? DleafTan{t->dg_table, t->dg_at_psi, t->dmla} : DleafTan{};
+}
+
+// The parameter axis of the entries that take a parameter vector (crt1d_hip_sensjac.h): ntan directions of the optics, then ln LAI, then the
+// leaf angle.  ok: the directions are usable, the tangent is NULL or whole, and there is a parameter at all.
+struct ParamAxis {
+  int ntan, lai, leaf;
+  const double* d[3];
+  int64_t dstride;
+  bool ok;
+  int npar() const { return ntan + lai + leaf; }
+  template <class KernelArgs>  // SensJacArgs, SpecArgs: the same five names
+  void put(KernelArgs& a) const {
+    a.ntan = ntan, a.lai = lai, a.leaf = leaf, a.dstride = dstride;
+    std::memcpy(a.d, d, sizeof d);
+  }
+};
+
+static ParamAxis parse_axis(const crt_bands* bands, const crt_optics_dirs* dirs, int with_lai, const DleafTan* tangent) {
+  ParamAxis p = {dirs ? dirs->ntan : 0, with_lai ? 1 : 0, tangent ? 1 : 0, {}, 0, false};
+  p.ok = bands && bands->nb > 0 && p.ntan >= 0 && p.ntan <= CRT_SENSJAC_MAX_NTAN && (p.ntan == 0 || dirs->leaf_r || dirs->leaf_t || dirs->soil_r) &&
+         (p.ntan == 0 || dirs->col_stride == 0 || dirs->col_stride == (int64_t)p.ntan * bands->nb) &&
+         (!tangent || (tangent->dg_table && tangent->dg_at_psi)) && p.npar() >= 1;
+  if (p.ok && p.ntan > 0) {
+    const double* const d[3] = {dirs->leaf_r, dirs->leaf_t, dirs->soil_r};
+    std::memcpy(p.d, d, sizeof d);
+    p.dstride = dirs->col_stride;
+  }
+  return p;
+}
+
+// The side records of the gradient, the sensor Jacobian and the spectral entries, behind the K0 records: the LAI ones [ncol][dlai_side_len]
+// (filled where ln LAI is a parameter and the scheme keeps one), the leaf-angle ones [ncol][dleaf_side_len] (filled where the leaf angle is one),
+// then the entry's slice sums.  Called as the side precompute of levels_deriv_impl; `report` is what a CRT_FLAG_PRECOMPUTE_ONLY call reports.
+struct SideRecords {
+  int scheme;
+  bool sized, lai, leaf, series;  // sized: the sizes are positive (they are an argument error of the shared path otherwise: no tail then)
+  DleafTan tan;
+  char report[112];
+
+  SideRecords(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_sun_series* ser, bool args_ok, bool want_lai, bool want_leaf,
+              const DleafTan& tan)
+      : scheme(scheme), series(ser != nullptr), tan(tan) {
+    sized = args_ok && cols && bands && cols->ncol > 0 && cols->nz > 0 && bands->nb > 0 && (!ser || ser->nt >= 1);
+    lai = sized && want_lai && dlai_side_len(scheme, cols->nz) > 0;
+    leaf = args_ok && want_leaf;
+    char k0[48] = "k_colpre";
+    if (ser) std::snprintf(k0, sizeof k0, "k_colpre<canopy> + k_colsun nt=%d", ser->nt);
+    std::snprintf(report, sizeof report, "%s%s%s", k0, lai ? " + k_dlai_side" : "", !leaf ? "" : ser ? " + k_dleaf_side<canopy>" : " + k_dleaf_side");
+  }
+  const double* side_leaf(const double* side, const SolveArgs& sa) const { return side + (size_t)sa.ncol * dlai_side_len(scheme, sa.nz); }
+  double* part(const double* side, const SolveArgs& sa) const { return const_cast<double*>(side) + (size_t)sa.ncol * grad_side_len(scheme, sa.nz); }
+  int operator()(const ColArgs& ca, double* side, hipStream_t s) const {
+    if (lai)
+      if (const int st = launch_dlai_side(ca, side, s)) return st;
+    return leaf ? launch_dleaf_side(ca, tan, side + (size_t)ca.ncol * dlai_side_len(scheme, ca.nz), s, series) : (int)CRT_OK;
+  }
+};
+
 extern "C" {
 
 size_t crt_hip_levels_jac_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nsel) {
@@ -774,7 +842,7 @@ int crt_hip_levels_dleaf_f64(int scheme, const crt_columns* cols, const crt_band
         return launch_dleaf(scheme, sa, la, dlai_args(out, side), s, probe);
       },
       [&](const ColArgs& ca, double* side, hipStream_t s) {
-        return launch_dleaf_side(ca, DleafTan{tangent->dg_table, tangent->dg_at_psi, tangent->dmla}, side, s);
+        return launch_dleaf_side(ca, dleaf_tan(tangent), side, s);
       });
 }
 
@@ -803,27 +871,16 @@ int crt_hip_levels_grad_f64(int scheme, const crt_columns* cols, const crt_bands
   const bool args_ok = w && (w->I_dr || w->I_df_d || w->I_df_u || w->F) && out &&
                        (out->leaf_r || out->leaf_t || out->soil_r || out->lai || out->leaf) &&
                        (!out->leaf || (tangent && tangent->dg_table && tangent->dg_at_psi));
-  // (sizes that are not positive are an argument error of the shared path: no tail then)
-  const bool sized = cols && bands && cols->ncol > 0 && cols->nz > 0 && bands->nb > 0;
-  const bool side_lai = args_ok && out->lai && sized && dlai_side_len(scheme, cols->nz) > 0, side_leaf = args_ok && out->leaf;
+  const SideRecords rec(scheme, cols, bands, nullptr, args_ok, args_ok && out->lai, args_ok && out->leaf, dleaf_tan(tangent));
   return levels_deriv_impl(
-      scheme, cols, bands, opts, levels, nsel, workspace, workspace_bytes, stream, args_ok, grad_side_len,
-      side_lai && side_leaf ? "k_colpre + k_dlai_side + k_dleaf_side" : side_lai ? "k_colpre + k_dlai_side" : side_leaf ? "k_colpre + k_dleaf_side" : "k_colpre",
+      scheme, cols, bands, opts, levels, nsel, workspace, workspace_bytes, stream, args_ok, grad_side_len, rec.report,
       [&](const SolveArgs& sa, const LevArgs& la, const double* side, hipStream_t s, bool probe) {
-        const double* const side2 = side + (size_t)sa.ncol * dlai_side_len(scheme, sa.nz);
-        double* const part = const_cast<double*>(side) + (size_t)sa.ncol * grad_side_len(scheme, sa.nz);
         return launch_grad(scheme, sa, la,
-                           GradArgs{{w->I_dr, w->I_df_d, w->I_df_u, w->F}, {out->leaf_r, out->leaf_t, out->soil_r}, out->lai, out->leaf, side, side2, part}, s,
-                           probe);
+                           GradArgs{{w->I_dr, w->I_df_d, w->I_df_u, w->F}, {out->leaf_r, out->leaf_t, out->soil_r}, out->lai, out->leaf, side,
+                                    rec.side_leaf(side, sa), rec.part(side, sa)},
+                           s, probe);
       },
-      [&](const ColArgs& ca, double* side, hipStream_t s) {
-        if (side_lai)
-          if (const int st = launch_dlai_side(ca, side, s)) return st;
-        if (!side_leaf) return (int)CRT_OK;
-        return launch_dleaf_side(ca, DleafTan{tangent->dg_table, tangent->dg_at_psi, tangent->dmla},
-                                 side + (size_t)ca.ncol * dlai_side_len(scheme, ca.nz), s);
-      },
-      true, sized ? grad_part_bytes(cols->ncol, bands->nb) : 0);
+      rec, true, rec.sized ? grad_part_bytes(cols->ncol, bands->nb) : 0);
 }
 
 // the Jacobian of the sensor-band sums (crt1d_hip_sensjac.h): the workspace of the gradient with the slice sums of k_sens_jac as its tail
@@ -840,17 +897,10 @@ static int sensor_jac_impl(int scheme, const crt_columns* cols, const crt_bands*
                            size_t workspace_bytes, crt_stream_t stream) {
   SensJacArgs ja = {};
   SensArgs& sn = ja.sn;
-  const int ntan = dirs ? dirs->ntan : 0;
+  const ParamAxis axis = parse_axis(bands, dirs, with_lai, tangent);
+  axis.put(ja);
   bool args_ok = sensors && sensors->first && sensors->count && sensors->w && sensors->nsens >= 1 && sensors->nsens <= CRT_MAX_SENSOR_BANDS &&
-                 bands && bands->nb > 0 && out && (out->I_dr || out->I_df_d || out->I_df_u || out->F) && ntan >= 0 &&
-                 ntan <= CRT_SENSJAC_MAX_NTAN && (ntan == 0 || dirs->leaf_r || dirs->leaf_t || dirs->soil_r) &&
-                 (ntan == 0 || dirs->col_stride == 0 || dirs->col_stride == (int64_t)ntan * bands->nb) &&
-                 (!tangent || (tangent->dg_table && tangent->dg_at_psi)) && (!series || ser);
-  ja.ntan = ntan;
-  ja.lai = with_lai ? 1 : 0;
-  ja.leaf = tangent ? 1 : 0;
-  const int npar = ntan + ja.lai + ja.leaf;
-  args_ok = args_ok && npar >= 1;
+                 out && (out->I_dr || out->I_df_d || out->I_df_u || out->F) && axis.ok && (!series || ser);
   if (args_ok) {
     const int nb = bands->nb;
     sn.o[0] = out->I_dr;
@@ -869,46 +919,27 @@ static int sensor_jac_impl(int scheme, const crt_columns* cols, const crt_bands*
       off += n;  // (<= 64 nb: no overflow)
     }
     if (off > 0x7fffffffLL) args_ok = false;
-    if (ntan > 0) {
-      ja.d[0] = dirs->leaf_r;
-      ja.d[1] = dirs->leaf_t;
-      ja.d[2] = dirs->soil_r;
-      ja.dstride = dirs->col_stride;
-    }
   }
-  // (sizes that are not positive are an argument error of the shared path: no tail then)
-  const bool sized = args_ok && cols && cols->ncol > 0 && cols->nz > 0 && (!ser || ser->nt >= 1);
-  const bool side_lai = sized && ja.lai && dlai_side_len(scheme, cols->nz) > 0, side_leaf = args_ok && ja.leaf;
+  const SideRecords rec(scheme, cols, bands, ser, args_ok, axis.lai, axis.leaf, tangent ? *tangent : DleafTan{});
   const bool sel_ok = nsel >= 1 && nsel <= CRT_MAX_LEVEL_SELECT;
-  const int nt = ser ? ser->nt : 1;
-  char k0[48] = "k_colpre", pre[96];  // what a CRT_FLAG_PRECOMPUTE_ONLY call reports
-  if (ser) std::snprintf(k0, sizeof k0, "k_colpre<canopy> + k_colsun nt=%d", nt);
-  std::snprintf(pre, sizeof pre, "%s%s%s", k0, side_lai ? " + k_dlai_side" : "", !side_leaf ? "" : ser ? " + k_dleaf_side<canopy>" : " + k_dleaf_side");
   return levels_deriv_impl(
-      scheme, cols, bands, opts, levels, nsel, workspace, workspace_bytes, stream, args_ok, grad_side_len, pre,
+      scheme, cols, bands, opts, levels, nsel, workspace, workspace_bytes, stream, args_ok, grad_side_len, rec.report,
       [&](const SolveArgs& sa, const LevArgs& la, const double* side, hipStream_t s, bool probe) {
         ja.side_lai = side;
-        ja.side_leaf = side + (size_t)sa.ncol * dlai_side_len(scheme, sa.nz);
-        sn.part = const_cast<double*>(side) + (size_t)sa.ncol * grad_side_len(scheme, sa.nz);
+        ja.side_leaf = rec.side_leaf(side, sa);
+        sn.part = rec.part(side, sa);
         if (!ser) return launch_sens_jac(scheme, sa, la, ja, s, probe);
-        const SeriesArgs sr = {nt, scheme, sa.nz, can_len(scheme, sa.nz), sun_len(scheme, sa.nz), sa.ws, sa.ws + (size_t)sa.ncol * can_len(scheme, sa.nz),
-                               ser->col_stride, ser->I_dr0, ser->I_df0};
+        const SeriesArgs sr = series_args(scheme, sa, ser);
         return launch_sens_jac(scheme, sa, la, ja, s, probe, &sr, tangent ? tangent->dg_at_psi : nullptr);
       },
-      [&](const ColArgs& ca, double* side, hipStream_t s) {
-        if (side_lai)
-          if (const int st = launch_dlai_side(ca, side, s)) return st;
-        if (!side_leaf) return (int)CRT_OK;
-        return launch_dleaf_side(ca, *tangent, side + (size_t)ca.ncol * dlai_side_len(scheme, ca.nz), s, ser != nullptr);
-      },
-      true, sized && sel_ok ? sensjac_part_bytes(cols->ncol, bands->nb, nsel, sn.nsens, npar, nt) : 0, ser);
+      rec, true, rec.sized && sel_ok ? sensjac_part_bytes(cols->ncol, bands->nb, nsel, sn.nsens, axis.npar(), ser ? ser->nt : 1) : 0, ser);
 }
 
 int crt_hip_sensor_jac_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
                            int32_t nsel, const crt_sensor_set* sensors, const crt_optics_dirs* dirs, int with_lai,
                            const crt_leaf_tangent* tangent, const crt_sensjac_out* out, void* workspace, size_t workspace_bytes,
                            crt_stream_t stream) {
-  const DleafTan tn = tangent ? DleafTan{tangent->dg_table, tangent->dg_at_psi, tangent->dmla} : DleafTan{};
+  const DleafTan tn = dleaf_tan(tangent);
   return sensor_jac_impl(scheme, cols, bands, nullptr, false, opts, levels, nsel, sensors, dirs, with_lai, tangent ? &tn : nullptr, out, workspace,
                          workspace_bytes, stream);
 }
@@ -928,7 +959,7 @@ int crt_hip_sensor_jac_series_f64(int scheme, const crt_columns* cols, const crt
                                   const int32_t* levels, int32_t nsel, const crt_sensor_set* sensors, const crt_optics_dirs* dirs, int with_lai,
                                   const crt_leaf_tangent_series* tangent, const crt_sensjac_out* out, void* workspace, size_t workspace_bytes,
                                   crt_stream_t stream) {
-  const DleafTan tn = tangent ? DleafTan{tangent->dg_table, tangent->dg_at_psi, tangent->dmla} : DleafTan{};
+  const DleafTan tn = dleaf_tan(tangent);
   return sensor_jac_impl(scheme, cols, bands, sun, true, opts, levels, nsel, sensors, dirs, with_lai, tangent ? &tn : nullptr, out, workspace,
                          workspace_bytes, stream);
 }
@@ -946,72 +977,7 @@ size_t crt_hip_spectral_normal_workspace_bytes(int scheme, int32_t ncol, int32_t
   return rec == 0 ? 0 : rec + spec_part_bytes(ncol, nb, nsel, nkey, npar);
 }
 
-// The parameter axis, the directions, the observations and the sums of both spectral entries -> sp (fwd: the four model spectra, in key
-// order; tangent_ok: the entry's tangent is NULL or whole).  false: an argument error.
-static bool spec_parse(const crt_bands* bands, const crt_optics_dirs* dirs, int with_lai, bool has_tangent, bool tangent_ok,
-                       const crt_spec_obs* obs, double* A, double* g, double* c2, double* const fwd[4], SpecArgs& sp) {
-  const int ntan = dirs ? dirs->ntan : 0;
-  bool args_ok = obs && A && g && c2 && bands && bands->nb > 0 && ntan >= 0 && ntan <= CRT_SENSJAC_MAX_NTAN &&
-                 (ntan == 0 || dirs->leaf_r || dirs->leaf_t || dirs->soil_r) &&
-                 (ntan == 0 || dirs->col_stride == 0 || dirs->col_stride == (int64_t)ntan * bands->nb) && tangent_ok;
-  sp.ntan = ntan;
-  sp.lai = with_lai ? 1 : 0;
-  sp.leaf = has_tangent ? 1 : 0;
-  args_ok = args_ok && sp.ntan + sp.lai + sp.leaf >= 1;
-  if (!args_ok) return false;
-  const double* const y[4] = {obs->y_I_dr, obs->y_I_df_d, obs->y_I_df_u, obs->y_F};
-  const double* const is[4] = {obs->inv_sigma_I_dr, obs->inv_sigma_I_df_d, obs->inv_sigma_I_df_u, obs->inv_sigma_F};
-  for (int q = 0; q < 4; ++q) {
-    if (!y[q]) continue;  // (not observed: its inv_sigma and fwd are not looked at)
-    sp.y[q] = y[q];
-    sp.is[q] = is[q];
-    sp.fwd[q] = fwd[q];
-    ++sp.nkey;
-  }
-  sp.A = A, sp.g = g, sp.c2 = c2;
-  if (ntan > 0) {
-    sp.d[0] = dirs->leaf_r;
-    sp.d[1] = dirs->leaf_t;
-    sp.d[2] = dirs->soil_r;
-    sp.dstride = dirs->col_stride;
-  }
-  return sp.nkey >= 1;
-}
-
-int crt_hip_spectral_normal_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
-                                int32_t nsel, const crt_optics_dirs* dirs, int with_lai, const crt_leaf_tangent* tangent,
-                                const crt_spec_obs* obs, const crt_spec_normal_out* out, void* workspace, size_t workspace_bytes,
-                                crt_stream_t stream) {
-  SpecArgs sp = {};
-  double* const fwd[4] = {out ? out->fwd_I_dr : nullptr, out ? out->fwd_I_df_d : nullptr, out ? out->fwd_I_df_u : nullptr, out ? out->fwd_F : nullptr};
-  const bool args_ok = out && spec_parse(bands, dirs, with_lai, tangent != nullptr, !tangent || (tangent->dg_table && tangent->dg_at_psi), obs,
-                                         out->A, out->g, out->c2, fwd, sp);
-  const int npar = sp.ntan + sp.lai + sp.leaf;
-  // (sizes that are not positive are an argument error of the shared path: no tail then)
-  const bool sized = args_ok && cols && cols->ncol > 0 && cols->nz > 0;
-  const bool side_lai = sized && sp.lai && dlai_side_len(scheme, cols->nz) > 0, side_leaf = args_ok && sp.leaf;
-  const bool sel_ok = nsel >= 1 && nsel <= CRT_MAX_LEVEL_SELECT;
-  char pre[64];  // what a CRT_FLAG_PRECOMPUTE_ONLY call reports
-  std::snprintf(pre, sizeof pre, "k_colpre%s%s", side_lai ? " + k_dlai_side" : "", side_leaf ? " + k_dleaf_side" : "");
-  return levels_deriv_impl(
-      scheme, cols, bands, opts, levels, nsel, workspace, workspace_bytes, stream, args_ok, grad_side_len, pre,
-      [&](const SolveArgs& sa, const LevArgs& la, const double* side, hipStream_t s, bool probe) {
-        sp.side_lai = side;
-        sp.side_leaf = side + (size_t)sa.ncol * dlai_side_len(scheme, sa.nz);
-        sp.part = const_cast<double*>(side) + (size_t)sa.ncol * grad_side_len(scheme, sa.nz);
-        return launch_spec_normal(scheme, sa, la, sp, s, probe);
-      },
-      [&](const ColArgs& ca, double* side, hipStream_t s) {
-        if (side_lai)
-          if (const int st = launch_dlai_side(ca, side, s)) return st;
-        if (!side_leaf) return (int)CRT_OK;
-        return launch_dleaf_side(ca, DleafTan{tangent->dg_table, tangent->dg_at_psi, tangent->dmla}, side + (size_t)ca.ncol * dlai_side_len(scheme, ca.nz),
-                                 s);
-      },
-      true, sized && sel_ok ? spec_part_bytes(cols->ncol, bands->nb, nsel, sp.nkey, npar) : 0);
-}
-
-// the sun-angle series of the two (series/crt1d_hip_specfit_series.h): the records of a level series, the side records, the slice sums of every
+// the sun-angle series of it (series/crt1d_hip_specfit_series.h): the records of a level series, the side records, the slice sums of every
 // (column, t) -- always there: the sum over t goes through them
 size_t crt_hip_spectral_normal_series_workspace_bytes(int scheme, int32_t ncol, int32_t nz, int32_t nb, int32_t nt, int32_t nsel, int32_t nkey,
                                                       int32_t npar) {
@@ -1022,43 +988,70 @@ size_t crt_hip_spectral_normal_series_workspace_bytes(int scheme, int32_t ncol, 
   return part > SIZE_MAX - rec - sides ? 0 : rec + sides + part;
 }
 
+// Both forms of the normal equations; ser: the sun-angle series, whose tangent carries dg_at_psi as [ncol][nt] and whose `out` may keep the
+// per-step sums A_t / g_t / c2_t (all three or none).  The per-step entry hands its outputs over in the series struct, those three NULL.
+static int spectral_normal_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_sun_series* ser, bool series,
+                                const crt_options* opts, const int32_t* levels, int32_t nsel, const crt_optics_dirs* dirs, int with_lai,
+                                const DleafTan* tangent, const crt_spec_obs* obs, const crt_spec_series_out* out, void* workspace,
+                                size_t workspace_bytes, crt_stream_t stream) {
+  SpecArgs sp = {};
+  const ParamAxis axis = parse_axis(bands, dirs, with_lai, tangent);
+  axis.put(sp);
+  const int per_t = out ? (out->A_t != nullptr) + (out->g_t != nullptr) + (out->c2_t != nullptr) : 0;
+  bool args_ok = obs && out && out->A && out->g && out->c2 && (per_t == 0 || per_t == 3) && axis.ok && (!series || ser);
+  if (args_ok) {
+    const double* const y[4] = {obs->y_I_dr, obs->y_I_df_d, obs->y_I_df_u, obs->y_F};
+    const double* const is[4] = {obs->inv_sigma_I_dr, obs->inv_sigma_I_df_d, obs->inv_sigma_I_df_u, obs->inv_sigma_F};
+    double* const fwd[4] = {out->fwd_I_dr, out->fwd_I_df_d, out->fwd_I_df_u, out->fwd_F};
+    for (int q = 0; q < 4; ++q) {
+      if (!y[q]) continue;  // (not observed: its inv_sigma and fwd are not looked at)
+      sp.y[q] = y[q];
+      sp.is[q] = is[q];
+      sp.fwd[q] = fwd[q];
+      ++sp.nkey;
+    }
+    sp.A = out->A, sp.g = out->g, sp.c2 = out->c2;
+    args_ok = sp.nkey >= 1;
+  }
+  const SpecSeriesOut so = args_ok ? SpecSeriesOut{out->A_t, out->g_t, out->c2_t} : SpecSeriesOut{};
+  const SideRecords rec(scheme, cols, bands, ser, args_ok, axis.lai, axis.leaf, tangent ? *tangent : DleafTan{});
+  const bool tail = rec.sized && nsel >= 1 && nsel <= CRT_MAX_LEVEL_SELECT;
+  const int npar = axis.npar();
+  return levels_deriv_impl(
+      scheme, cols, bands, opts, levels, nsel, workspace, workspace_bytes, stream, args_ok, grad_side_len, rec.report,
+      [&](const SolveArgs& sa, const LevArgs& la, const double* side, hipStream_t s, bool probe) {
+        sp.side_lai = side;
+        sp.side_leaf = rec.side_leaf(side, sa);
+        sp.part = rec.part(side, sa);
+        if (!ser) return launch_spec_normal(scheme, sa, la, sp, s, probe);
+        return launch_spec_normal_series(scheme, sa, la, sp, so, series_args(scheme, sa, ser), tangent ? tangent->dg_at_psi : nullptr, s, probe);
+      },
+      rec, true,
+      !tail  ? 0
+      : !ser ? spec_part_bytes(cols->ncol, bands->nb, nsel, sp.nkey, npar)
+             : spec_series_part_bytes(cols->ncol, bands->nb, nsel, sp.nkey, npar, ser->nt),
+      ser);
+}
+
+int crt_hip_spectral_normal_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
+                                int32_t nsel, const crt_optics_dirs* dirs, int with_lai, const crt_leaf_tangent* tangent,
+                                const crt_spec_obs* obs, const crt_spec_normal_out* out, void* workspace, size_t workspace_bytes,
+                                crt_stream_t stream) {
+  const crt_spec_series_out so = out ? crt_spec_series_out{out->A, out->g, out->c2, nullptr, nullptr, nullptr, out->fwd_I_dr, out->fwd_I_df_d,
+                                                           out->fwd_I_df_u, out->fwd_F}
+                                     : crt_spec_series_out{};
+  const DleafTan tn = dleaf_tan(tangent);
+  return spectral_normal_impl(scheme, cols, bands, nullptr, false, opts, levels, nsel, dirs, with_lai, tangent ? &tn : nullptr, obs, out ? &so : nullptr,
+                              workspace, workspace_bytes, stream);
+}
+
 int crt_hip_spectral_normal_series_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_sun_series* sun,
                                        const crt_options* opts, const int32_t* levels, int32_t nsel, const crt_optics_dirs* dirs,
                                        int with_lai, const crt_leaf_tangent_series* tangent, const crt_spec_obs* obs,
                                        const crt_spec_series_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream) {
-  SpecArgs sp = {};
-  double* const fwd[4] = {out ? out->fwd_I_dr : nullptr, out ? out->fwd_I_df_d : nullptr, out ? out->fwd_I_df_u : nullptr, out ? out->fwd_F : nullptr};
-  const bool per_t = out && (out->A_t || out->g_t || out->c2_t);
-  const bool args_ok = sun && out && (!per_t || (out->A_t && out->g_t && out->c2_t)) &&
-                       spec_parse(bands, dirs, with_lai, tangent != nullptr, !tangent || (tangent->dg_table && tangent->dg_at_psi), obs, out->A,
-                                  out->g, out->c2, fwd, sp);
-  const SpecSeriesOut so = args_ok ? SpecSeriesOut{out->A_t, out->g_t, out->c2_t} : SpecSeriesOut{};
-  const DleafTan tn = tangent ? DleafTan{tangent->dg_table, tangent->dg_at_psi, tangent->dmla} : DleafTan{};
-  const int npar = sp.ntan + sp.lai + sp.leaf;
-  const bool sized = args_ok && cols && cols->ncol > 0 && cols->nz > 0 && sun->nt >= 1;
-  const bool side_lai = sized && sp.lai && dlai_side_len(scheme, cols->nz) > 0, side_leaf = args_ok && sp.leaf;
-  const bool sel_ok = nsel >= 1 && nsel <= CRT_MAX_LEVEL_SELECT;
-  const int nt = sun ? sun->nt : 1;
-  char pre[112];  // what a CRT_FLAG_PRECOMPUTE_ONLY call reports
-  std::snprintf(pre, sizeof pre, "k_colpre<canopy> + k_colsun nt=%d%s%s", nt, side_lai ? " + k_dlai_side" : "",
-                side_leaf ? " + k_dleaf_side<canopy>" : "");
-  return levels_deriv_impl(
-      scheme, cols, bands, opts, levels, nsel, workspace, workspace_bytes, stream, args_ok, grad_side_len, pre,
-      [&](const SolveArgs& sa, const LevArgs& la, const double* side, hipStream_t s, bool probe) {
-        sp.side_lai = side;
-        sp.side_leaf = side + (size_t)sa.ncol * dlai_side_len(scheme, sa.nz);
-        sp.part = const_cast<double*>(side) + (size_t)sa.ncol * grad_side_len(scheme, sa.nz);
-        const SeriesArgs sr = {nt, scheme, sa.nz, can_len(scheme, sa.nz), sun_len(scheme, sa.nz), sa.ws, sa.ws + (size_t)sa.ncol * can_len(scheme, sa.nz),
-                               sun->col_stride, sun->I_dr0, sun->I_df0};
-        return launch_spec_normal_series(scheme, sa, la, sp, so, sr, tangent ? tangent->dg_at_psi : nullptr, s, probe);
-      },
-      [&](const ColArgs& ca, double* side, hipStream_t s) {
-        if (side_lai)
-          if (const int st = launch_dlai_side(ca, side, s)) return st;
-        if (!side_leaf) return (int)CRT_OK;
-        return launch_dleaf_side(ca, tn, side + (size_t)ca.ncol * dlai_side_len(scheme, ca.nz), s, true);
-      },
-      true, sized && sel_ok ? spec_series_part_bytes(cols->ncol, bands->nb, nsel, sp.nkey, npar, nt) : 0, sun);
+  const DleafTan tn = dleaf_tan(tangent);
+  return spectral_normal_impl(scheme, cols, bands, sun, true, opts, levels, nsel, dirs, with_lai, tangent ? &tn : nullptr, obs, out, workspace,
+                              workspace_bytes, stream);
 }
 
 int crt_hip_bandsum_finish_f64(const crt_columns* cols, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream) {

@@ -152,6 +152,14 @@ def test_sensjac_validation_without_gpu(lib, scheme):
     # a tangent must be whole
     assert call(tan=_lib.CrtLeafTangent(None, FAKE, None)) == BAD
     assert call(tan=_lib.CrtLeafTangent(FAKE, None, FAKE)) == BAD
+    assert call(tan=_lib.CrtLeafTangent(None, None, None)) == BAD
+    # the rest of the parameter-axis parse: without a direction (ntan = 0) neither the stride nor the pointers are looked at; any with_lai
+    # but 0 counts as set; sizes that are not positive are an argument error
+    assert call(dirs=_lib.CrtOpticsDirs(0, 5, None, None, None)) == WS
+    assert call(dirs=_lib.CrtOpticsDirs(0, 5, None, None, None), lai=0, tan=None) == BAD
+    assert call(dirs=None, lai=2, tan=None) == WS
+    assert call(c=_lib.CrtColumns(0, nz, FAKE, FAKE, FAKE, FAKE, FAKE, None, None)) == BAD
+    assert call(c=_lib.CrtColumns(2, 0, FAKE, FAKE, FAKE, FAKE, FAKE, None, None), levels=(0,)) == BAD
     # the sensor set, as crt_hip_sensor_levels_f64
     assert call(sens=None) == BAD
     assert call(sens=_sens([0], [nb], w=None)) == BAD

@@ -142,6 +142,17 @@ def test_series_validation_without_gpu(lib, scheme):
     # a tangent must be whole
     assert call(tan=T(None, FAKE, None)) == BAD
     assert call(tan=T(FAKE, None, FAKE)) == BAD
+    assert call(tan=T(None, None, None)) == BAD
+    # the rest of the parameter-axis parse: without a direction (ntan = 0) neither the stride nor the pointers are looked at; any with_lai
+    # but 0 counts as set; sizes that are not positive are an argument error
+    assert call(dirs=_lib.CrtOpticsDirs(0, 5, None, None, None)) == WS
+    assert call(dirs=_lib.CrtOpticsDirs(0, 5, None, None, None), lai=0, tan=None) == BAD
+    assert call(dirs=None, lai=2, tan=None) == WS
+    assert call(c=_lib.CrtColumns(0, nz, FAKE, FAKE, FAKE, FAKE, FAKE, None, None)) == BAD
+    assert call(c=_lib.CrtColumns(2, 0, FAKE, FAKE, FAKE, FAKE, FAKE, None, None), levels=(0,)) == BAD
+    for one in range(3):  # any single direction array is enough
+        assert call(dirs=_lib.CrtOpticsDirs(2, 0, *[FAKE if i == one else None for i in range(3)])) == WS
+    assert call(dirs=D(-1, 0, FAKE, FAKE, FAKE)) == BAD
     # the directions, the outputs, the sensor set: as crt_hip_sensor_jac_f64
     assert call(dirs=D(2, 0, None, None, None)) == BAD
     assert call(dirs=D(_lib.SENSJAC_MAX_NTAN + 1, 0, FAKE, FAKE, FAKE)) == BAD

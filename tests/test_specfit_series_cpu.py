@@ -163,6 +163,17 @@ def test_series_validation_without_gpu(lib, scheme):
     assert call(tan=_lib.CrtLeafTangentSeries(None, FAKE, None)) == BAD
     assert call(tan=_lib.CrtLeafTangentSeries(FAKE, None, FAKE)) == BAD
     assert call(tan=_lib.CrtLeafTangentSeries(FAKE, FAKE, FAKE)) == WS
+    assert call(tan=_lib.CrtLeafTangentSeries(None, None, None)) == BAD
+    # the rest of the parameter-axis parse: without a direction (ntan = 0) neither the stride nor the pointers are looked at; any with_lai
+    # but 0 counts as set; sizes that are not positive are an argument error
+    assert call(dirs=_lib.CrtOpticsDirs(0, 5, None, None, None)) == WS
+    assert call(dirs=_lib.CrtOpticsDirs(0, 5, None, None, None), lai=0, tan=None) == BAD
+    assert call(dirs=None, lai=2, tan=None) == WS
+    assert call(c=_lib.CrtColumns(0, nz, FAKE, FAKE, FAKE, FAKE, FAKE, None, None)) == BAD
+    assert call(c=_lib.CrtColumns(2, 0, FAKE, FAKE, FAKE, FAKE, FAKE, None, None), levels=(0,)) == BAD
+    for one in range(3):  # any single direction array is enough
+        assert call(dirs=_lib.CrtOpticsDirs(2, 0, *[FAKE if i == one else None for i in range(3)])) == WS
+    assert call(dirs=_lib.CrtOpticsDirs(0, 0, FAKE, FAKE, FAKE), lai=0, tan=None) == BAD
     # whatever the level series rejects about sun
     assert call(sun=None) == BAD
     assert call(sun=_lib.CrtSunSeries(0, FAKE, None, 0, FAKE, FAKE)) == BAD  # nt < 1
