@@ -550,6 +550,44 @@ def _leafmodel_signatures():
 _LEAFMODEL_SIGNATURES = _leafmodel_signatures()
 LEAFMODEL_EXPORTS = list(_LEAFMODEL_SIGNATURES)
 
+# the look-up-table start of a retrieval (include_lut/crt1d_hip_lut.h): the fused misfit of the observations against a table of model
+# evaluations with the selection of the best candidates; again a header and a table of their own
+LUT_MAX_BEST = 8  # CRT_LUT_MAX_BEST
+LUT_MAX_KSPLIT = 256  # CRT_LUT_MAX_KSPLIT
+
+
+class CrtLutTable(ctypes.Structure):
+    """``crt_lut_table``: ``q [K][npar]`` and ``m[b] [K][nrow_b]`` on the device."""
+
+    _fields_ = [("ncand", ctypes.c_int32), ("npar", ctypes.c_int32), ("nblk", ctypes.c_int32), ("nrow", ctypes.c_int32 * LM_MAX_BLOCKS),
+                ("q", _vp), ("m", _vp * LM_MAX_BLOCKS)]
+
+
+class CrtLutObs(ctypes.Structure):
+    """``crt_lut_obs``: ``y[b]``, ``inv_sigma[b]`` (or NULL) ``[ncol][nrow_b]``; ``prior``, ``inv_sigma_prior`` ``[ncol][npar]`` or both NULL."""
+
+    _fields_ = [("ncol", ctypes.c_int32), ("y", _vp * LM_MAX_BLOCKS), ("inv_sigma", _vp * LM_MAX_BLOCKS), ("prior", _vp),
+                ("inv_sigma_prior", _vp)]
+
+
+class CrtLutOut(ctypes.Structure):
+    """``crt_lut_out``: ``index [ncol][nbest]`` int32, ``cost [ncol][nbest]``, ``p [ncol][npar]`` or NULL; ``ksplit`` 0 = automatic."""
+
+    _fields_ = [("nbest", ctypes.c_int32), ("ksplit", ctypes.c_int32), ("index", _vp), ("cost", _vp), ("p", _vp)]
+
+
+def _lut_signatures():
+    P = ctypes.POINTER
+    i32, sz, ok = ctypes.c_int32, ctypes.c_size_t, ctypes.c_int
+    return {
+        "crt_hip_lut_match_workspace_bytes": (sz, [i32, i32, i32]),
+        "crt_hip_lut_match_f64": (ok, [P(CrtLutTable), P(CrtLutObs), P(CrtLutOut), _vp, sz, _vp]),
+    }
+
+
+_LUT_SIGNATURES = _lut_signatures()
+LUT_EXPORTS = list(_LUT_SIGNATURES)
+
 _lib = None
 
 
@@ -575,7 +613,7 @@ def load():
     for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES, **_SENSOR_SIGNATURES, **_JAC_SIGNATURES,
                                       **_DLAI_SIGNATURES, **_DLEAF_SIGNATURES, **_GRAD_SIGNATURES, **_SENSJAC_SIGNATURES,
                                       **_SENSJAC_SERIES_SIGNATURES, **_RETRIEVE_SIGNATURES, **_SPECFIT_SIGNATURES,
-                                      **_SPECFIT_SERIES_SIGNATURES, **_LEAFMODEL_SIGNATURES}.items():
+                                      **_SPECFIT_SERIES_SIGNATURES, **_LEAFMODEL_SIGNATURES, **_LUT_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:

@@ -2271,6 +2271,11 @@ class _LmPlan:
         self.hi = None if hi is None else torch.as_tensor(hi, dtype=torch.float64).to(dev).contiguous()
         self.prior = None if prior is None else _per_col(prior, "prior", ncol, npar, dev)
         self.inv_sigma_prior = None if prior is None else _per_col(inv_sigma_prior, "inv_sigma_prior", ncol, npar, dev)
+        table = p0 if isinstance(p0, LutTable) else None
+        if table is not None:  # a column without an eligible candidate gets table.p_default, else the default start (a leaf model has none: q[0])
+            if table.q.device != dev:
+                raise ValueError(f"the table lives on {table.q.device} but the columns on {dev}")
+            p0 = table.p_default if table.p_default is not None else None if leaf_model is None else table.q[0]
         if p0 is None:
             p0 = new(ncol, npar)
             if leaf:
@@ -2296,6 +2301,9 @@ class _LmPlan:
                                                           self.nreject)])
         self._c = c.c_struct()
         self._s = None if sun is None else sun.c_struct()
+        # the look-up-table start: the best candidate of every column on the plan's own observations and prior
+        self.lut = None if table is None else LutMatchPlan(table, self.y, inv_sigma=self.inv_sigma or None, prior=self.prior,
+                                                           inv_sigma_prior=self.inv_sigma_prior, p_default=self._p0)
         self.reset()
 
     def _evaluate(self, ap, s):
@@ -2313,10 +2321,14 @@ class _LmPlan:
                        "crt_hip_g_dparam_series_f64")
 
     def reset(self, p0=None):
-        """Restart the state at ``p0`` (default: the plan's starting point): ``p = p_trial = p0``, ``cost = +inf``, ``lam = lam0``."""
+        """Restart the state at ``p0`` (default: the plan's starting point): ``p = p_trial = p0``, ``cost = +inf``, ``lam = lam0``.  A plan
+        made with ``p0=`` a :class:`LutTable` and restarted without ``p0`` runs its match (``plan.lut``) on the current stream and starts
+        every column at its best candidate; the host is not synchronised."""
         if p0 is not None:
             v = torch.as_tensor(p0, dtype=torch.float64).to(self.p.device)
             self._p0.copy_(v.expand_as(self._p0))
+        elif self.lut is not None:
+            self._p0.copy_(self.lut()["p"])
         self.p.copy_(self._p0)
         self.p_trial.copy_(self._p0)
         self.cost.fill_(float("inf"))
@@ -2420,6 +2432,8 @@ class RetrievalPlan(_LmPlan):
         o = _lm_options(lo, hi, axis.npar, options)
         _need_f64_bands(bands, "retrieval")
         _check_start(leaf_model, lo, hi, p0, prior, inv_sigma_prior)
+        if isinstance(p0, LutTable):
+            _check_lut_start(p0, axis.params, keys, False, y)
         return keys, axis, o
 
     def _inner(self, scheme, levels, sun, sensors, y, inv_sigma, keys, mu_s, tau_d_method, **axis):
@@ -2690,6 +2704,8 @@ class SpectralRetrievalPlan(_LmPlan):
                                       d_soil_r=d_soil_r, lai=lai, leaf=leaf, leaf_model=leaf_model)
         o = _lm_options(lo, hi, axis.npar, options)
         _check_start(leaf_model, lo, hi, p0, prior, inv_sigma_prior)
+        if isinstance(p0, LutTable):
+            _check_lut_start(p0, axis.params, keys, True, y)
         return keys, axis, o, _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), axis.npar, sun)
 
     def _inner(self, scheme, levels, sun, y, **kw):
@@ -2928,3 +2944,259 @@ class _PlateLeafBinding:
     def launch(self, lib, p_ptr, npar, bands, h):
         _lib.check(lib.crt_hip_plate_leaf_f64(ctypes.byref(self._m), p_ptr, npar, bands.leaf_r.data_ptr(), bands.leaf_t.data_ptr(), self.ntan,
                                               self.d_leaf_r.data_ptr(), self.d_leaf_t.data_ptr(), h), "crt_hip_plate_leaf_f64")
+
+
+# ---- the look-up-table start of the retrievals (include_lut/crt1d_hip_lut.h) --------------------------------------------------------------
+
+LUT_MAX_BEST = _lib.LUT_MAX_BEST
+_HALTON_BASES = (2, 3, 5, 7, 11, 13, 17, 19, 23, 29)  # one per parameter, RETRIEVE_MAX_NPAR of them
+
+
+def lut_sample(lo, hi, ncand, *, include=None):
+    """``ncand`` candidate parameter vectors in the box ``[lo, hi]`` (each ``(npar,)``, finite): a NumPy array ``(ncand, npar)`` float64.
+    The rows of ``include`` (``(n, npar)`` or ``(npar,)``, e.g. the default starting point; taken as they are) come first; the rest is
+    the Halton sequence (bases 2, 3, 5, ..; from its index 1) scaled to the box -- deterministic, no random-number generator."""
+    import numpy as np
+
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    if lo.ndim != 1 or lo.shape != hi.shape or not 1 <= lo.shape[0] <= _lib.RETRIEVE_MAX_NPAR:
+        raise ValueError(f"lo and hi must be (npar,) with npar in 1 .. {_lib.RETRIEVE_MAX_NPAR}")
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise ValueError("a look-up table needs finite bounds lo and hi")
+    if (lo > hi).any():
+        raise ValueError("lo must not exceed hi")
+    npar = lo.shape[0]
+    inc = np.empty((0, npar)) if include is None else np.atleast_2d(np.asarray(include, dtype=np.float64))
+    if inc.ndim != 2 or inc.shape[1] != npar:
+        raise ValueError(f"include must be (n, npar) or (npar,) with npar = {npar}")
+    n = int(ncand) - inc.shape[0]
+    if int(ncand) < 1 or n < 0:
+        raise ValueError("ncand must be >= 1 and at least the number of rows of include")
+    u = np.empty((n, npar))
+    for j in range(npar):
+        b, f, r, k = _HALTON_BASES[j], 1.0, np.zeros(n), np.arange(1, n + 1)
+        while k.any():  # the radical inverse of the index in base b
+            f /= b
+            r += f * (k % b)
+            k //= b
+        u[:, j] = r
+    return np.concatenate([inc, np.clip(lo + u * (hi - lo), lo, hi)])
+
+
+def _table_axes(spectral, series):
+    return "(ncol, " + ("nt, " if series else "") + ("nsel, nb)" if spectral else "nsel, nsens)")
+
+
+class LutTable:
+    """A look-up table of a retrieval: the model evaluated once at ``K`` candidate parameter vectors on ONE template canopy.  ``q (K,
+    npar)`` the candidates and ``m[key] (K, nrow)`` the model's values (device tensors), ``params`` the names of the columns of ``q``,
+    ``keys``, ``nrow``, ``shape`` (what ``nrow`` flattens: ``([nt,] nsel, nsens)`` or ``([nt,] nsel, nb)``), ``scheme`` and ``spectral``
+    (the rows are level spectra, not sensor-band sums).  Made by :meth:`build`; matched by :class:`LutMatchPlan`; taken as ``p0=`` by
+    :class:`RetrievalPlan` and :class:`SpectralRetrievalPlan`."""
+
+    def __init__(self, q, m, *, params, keys, shape, scheme, spectral, p_default=None):
+        self.q, self.m, self.params, self.keys, self.shape = q, m, tuple(params), tuple(keys), tuple(shape)
+        self.p_default = p_default  # where a plan started from this table puts a column without an eligible candidate (None: the plan's)
+        self.scheme, self.spectral = scheme, bool(spectral)
+        self.nrow = int(torch.Size(self.shape).numel())
+
+    @property
+    def ncand(self):
+        return self.q.shape[0]
+
+    @property
+    def npar(self):
+        return self.q.shape[1]
+
+    @classmethod
+    def _static(cls, scheme, cols, bands, levels, q, *, keys, sensors=None, sun=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True,
+                leaf=False, leaf_model=None, mu_s=0.501, tau_d_method="quad", chunk=None):
+        """The arguments of :meth:`build` -> (keys, the parameter axis, the candidates as a host array, the chunk): every check that needs
+        no device, through the ``_static`` of the plan the table is for."""
+        import numpy as np
+
+        spectral = sensors is None
+        _SolvePlan._check_options(_SolvePlan, scheme, tau_d_method)
+        served = SPECTRAL_RETRIEVE_SCHEMES if spectral else RETRIEVE_SCHEMES
+        if scheme not in served:
+            raise ValueError(f"scheme {scheme!r} has no {'spectral ' if spectral else ''}look-up table; served: " + ", ".join(served))
+        keys = _level_keys(keys)
+        axis_kw = dict(d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r, lai=lai, leaf=leaf, leaf_model=leaf_model)
+        axis = _ParamAxis(**axis_kw)
+        for what, n in (("cols", getattr(cols, "ncol", 1)), ("bands", getattr(bands, "_shape", (1,))[0]), ("sun", getattr(sun, "ncol", 1))):
+            if n != 1:
+                raise ValueError(f"a look-up table is built on ONE template column: {what} has {n}")
+        qh = np.asarray(q.detach().cpu() if isinstance(q, torch.Tensor) else q, dtype=np.float64)
+        if qh.ndim != 2 or qh.shape[0] < 1 or qh.shape[1] != axis.npar:
+            raise ValueError(f"q must be (K, npar) with K >= 1 and npar = {axis.npar} for the parameters {axis.params}, got {qh.shape}")
+        if not np.isfinite(qh).all():
+            raise ValueError("q must be finite")
+        if chunk is not None and int(chunk) < 1:
+            raise ValueError("chunk must be >= 1")
+        chunk = min(qh.shape[0], 1024 if chunk is None else int(chunk))
+        start = dict(p0=qh[:1], lo=qh.min(0), hi=qh.max(0))  # (the candidates' own box: a leaf model checks N and the contents on it)
+        if spectral:
+            fake = {k: np.broadcast_to(0.0, (1,) * (3 if sun is None else 4)) for k in keys}
+            keys, axis = _spectral_static(scheme, fake, keys, None, tau_d_method, bands, sun, **axis_kw)
+            _check_start(leaf_model, start["lo"], start["hi"], start["p0"], None, None)
+        else:
+            keys, axis, _ = RetrievalPlan._static(scheme, cols, bands, levels, sensors, dict.fromkeys(keys), keys=keys, sun=sun, **axis_kw,
+                                                  **start, tau_d_method=tau_d_method)
+        return keys, axis, qh, chunk
+
+    @classmethod
+    def build(cls, scheme, cols: Columns, bands: Bands, levels, q, *, keys, sensors=None, sun=None, d_leaf_r=None, d_leaf_t=None,
+              d_soil_r=None, lai=True, leaf=False, leaf_model=None, mu_s=0.501, tau_d_method="quad", chunk=None):
+        """Evaluate the model at the candidates ``q (K, npar)`` (e.g. :func:`lut_sample`) on the template ``cols``, ``bands``, ``sun``: ONE
+        column each -- anything else is a ValueError.  All columns later matched against the table share that template (sun angle or
+        series, base LAI profile, base spectra, illumination) and differ in their observations; several classes of columns are several
+        tables.  With ``sensors`` the rows are the sensor-band sums a :class:`RetrievalPlan` compares (``RETRIEVE_SCHEMES``); without, the
+        level spectra of ``SpectralRetrievalPlan.fitted()`` (``SPECTRAL_RETRIEVE_SCHEMES``).  The parameter axis (``d_*``, ``lai``,
+        ``leaf``, ``leaf_model``) is that of the plans.  There is no second apply path: the matching retrieval plan is built on the
+        template replicated to ``chunk`` columns (default ``min(K, 1024)``) and restarted at every chunk of ``q``; row ``k`` is bitwise what
+        that plan evaluates at ``q[k]`` alone, for any ``chunk``."""
+        kw = dict(keys=keys, sensors=sensors, sun=sun, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r, lai=lai, leaf=leaf,
+                  leaf_model=leaf_model, mu_s=mu_s, tau_d_method=tau_d_method)
+        keys, axis, qh, chunk = cls._static(scheme, cols, bands, levels, q, chunk=chunk, **kw)
+        spectral, dev, K = sensors is None, cols.device, qh.shape[0]
+        rep = lambda v: None if v is None else v.expand(chunk, *v.shape[1:]).contiguous()  # noqa: E731
+        tcols = Columns(rep(cols.psi), rep(cols.lai), rep(cols.g_kind), rep(cols.g_param), rep(cols.mla), rep(cols.g_at_psi), rep(cols.g_table))
+        tsun = None if sun is None else type(sun)(rep(sun.psi), sun.I_dr0, sun.I_df0, rep(sun.g_at_psi))
+        kw.pop("sensors")
+        kw["sun"] = tsun
+        with torch.cuda.device(dev):
+            qd = torch.as_tensor(qh, device=dev).contiguous()
+            start = dict(p0=qd[:1], lo=qh.min(0), hi=qh.max(0)) if leaf_model is not None else {}
+            # zero observations of the plans' shapes: the table rows do not depend on them
+            nts, nsel = () if sun is None else (sun.nt,), len(normalize_levels(levels, cols.nz))
+            zeros = lambda n: {k: torch.zeros((chunk, *nts, nsel, n), dtype=torch.float64, device=dev) for k in keys}  # noqa: E731
+            if spectral:
+                plan = SpectralRetrievalPlan(scheme, tcols, bands, levels, zeros(bands.nb), **kw, **start)
+            else:
+                plan = RetrievalPlan(scheme, tcols, bands, levels, sensors, zeros(sensors.nsens), **kw, **start)
+            s = torch.cuda.current_stream(dev)
+            m = None
+            for i0 in range(0, K, chunk):
+                n = min(chunk, K - i0)
+                qc = qd[i0:i0 + n] if n == chunk else torch.cat([qd[i0:], qd[-1:].expand(chunk - n, -1)])  # (padded with the last row)
+                plan.reset(p0=qc)
+                if spectral:
+                    vals = plan.fitted(s)
+                else:
+                    plan._evaluate(plan._ap, s)
+                    plan.fwd(s, flags=0)  # (its own precompute)
+                    vals = plan.fwd.out
+                if m is None:
+                    shape = tuple(vals[keys[0]].shape[1:])
+                    m = {k: torch.empty((K, int(torch.Size(shape).numel())), dtype=torch.float64, device=dev) for k in keys}
+                for k in keys:
+                    m[k][i0:i0 + n] = vals[k].reshape(chunk, -1)[:n]
+        return cls(qd, m, params=axis.params, keys=keys, shape=shape, scheme=scheme, spectral=spectral)
+
+
+def _check_lut_start(table, params, keys, spectral, y):
+    """A :class:`LutTable` given as ``p0`` against the plan it starts: the parameter axis, the keys, the kind, and its rows against the
+    observations ``y`` (whose shape the plan holds to its own).  No device."""
+    import numpy as np
+
+    if tuple(table.params) != tuple(params):
+        raise ValueError(f"the table has the parameters {table.params}, the plan {tuple(params)}")
+    if tuple(table.keys) != tuple(keys):
+        raise ValueError(f"the table has the keys {table.keys}, the plan {tuple(keys)}")
+    if table.spectral != spectral:
+        kinds = ("level spectra (built without sensors)", "sensor-band sums (built with sensors)")
+        raise ValueError(f"the table holds {kinds[not table.spectral]}, the plan compares {kinds[not spectral]}")
+    for k in keys:
+        if tuple(np.shape(y[k])[1:]) != table.shape:
+            raise ValueError(f"the table's rows are {table.shape} per candidate, y[{k!r}] is {tuple(np.shape(y[k]))}")
+
+
+class LutMatchPlan:
+    """The best ``nbest`` candidates of a :class:`LutTable` for every column, in one kernel pass (``crt_hip_lut_match_f64``): the weighted
+    misfit of the observations ``y[k] (ncol, *table.shape)`` (``inv_sigma[k]`` the same shape; ``None`` / a missing key: ones; an entry 0:
+    not observed, its ``y`` may be NaN) and the prior ``prior`` / ``inv_sigma_prior`` (``(ncol, npar)`` or ``(npar,)``, both or neither)
+    against every table row, under the cost contract of the Levenberg-Marquardt step, with the selection fused: neither the costs ``ncol x
+    K`` nor the residuals are written.  Everything is bound at construction and the workspace allocated once; tensors on the table's
+    device are read where they lie at every call.  ``plan()`` is one C call and returns ``{"index" (ncol, nbest) int32, "cost" (ncol,
+    nbest), "p" (ncol, npar)}``: the candidates in ascending (cost, index), ``-1`` / ``+inf`` where fewer than ``nbest`` have a cost below
+    ``+inf``, and ``p = q[index[:, 0]]`` -- filled at every call with ``p_default`` (``(ncol, npar)`` or ``(npar,)``; default NaN) first,
+    which a column without any eligible candidate keeps.  ``ksplit``: how many workgroups share the candidates of 64 columns (0: automatic);
+    it changes no bit of the result."""
+
+    def __init__(self, table, y, *, inv_sigma=None, prior=None, inv_sigma_prior=None, nbest=1, p_default=None, ksplit=0):
+        axes = self._static(table, y, inv_sigma=inv_sigma, prior=prior, inv_sigma_prior=inv_sigma_prior, nbest=nbest, ksplit=ksplit)
+        self.lib, self.table, self.nbest = _lib.load(), table, int(nbest)
+        dev, keys, npar = table.q.device, table.keys, table.npar
+
+        def obs(v, name, ncol=None):
+            v = torch.as_tensor(v, dtype=torch.float64).to(dev).contiguous()
+            if tuple(v.shape[1:]) != table.shape or v.ndim < 2 or (ncol is not None and v.shape[0] != ncol) or v.shape[0] < 1:
+                raise ValueError(f"{name} must be {axes} = ({'ncol' if ncol is None else ncol}, {str(table.shape)[1:-1]}), got {tuple(v.shape)}")
+            return v
+
+        self.y = {keys[0]: obs(y[keys[0]], f"y[{keys[0]!r}]")}
+        ncol = self.ncol = self.y[keys[0]].shape[0]
+        self.y.update({k: obs(y[k], f"y[{k!r}]", ncol) for k in keys[1:]})
+        self.inv_sigma = {k: obs(inv_sigma[k], f"inv_sigma[{k!r}]", ncol) for k in keys if inv_sigma is not None and k in inv_sigma}
+        self.prior = None if prior is None else _per_col(prior, "prior", ncol, npar, dev)
+        self.inv_sigma_prior = None if prior is None else _per_col(inv_sigma_prior, "inv_sigma_prior", ncol, npar, dev)
+        self.index = torch.full((ncol, self.nbest), -1, dtype=torch.int32, device=dev)
+        self.cost = torch.full((ncol, self.nbest), float("inf"), dtype=torch.float64, device=dev)
+        fill = torch.full((npar,), float("nan"), dtype=torch.float64) if p_default is None else p_default
+        self._p_default = _per_col(fill, "p_default", ncol, npar, dev).clone()
+        self.p = self._p_default.clone()
+        need = int(self.lib.crt_hip_lut_match_workspace_bytes(ncol, table.ncand, self.nbest))
+        self.workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+        ptr = lambda v: None if v is None else v.data_ptr()  # noqa: E731
+        pad = lambda v: v + [None] * (_lib.LM_MAX_BLOCKS - len(v))  # noqa: E731
+        nblk = len(keys)
+        self._t = _lib.CrtLutTable(table.ncand, npar, nblk, (ctypes.c_int32 * _lib.LM_MAX_BLOCKS)(*[table.nrow] * nblk),
+                                   ptr(table.q), (ctypes.c_void_p * _lib.LM_MAX_BLOCKS)(*pad([ptr(table.m[k]) for k in keys])))
+        self._o = _lib.CrtLutObs(ncol, (ctypes.c_void_p * _lib.LM_MAX_BLOCKS)(*pad([ptr(self.y[k]) for k in keys])),
+                                 (ctypes.c_void_p * _lib.LM_MAX_BLOCKS)(*pad([ptr(self.inv_sigma.get(k)) for k in keys])),
+                                 ptr(self.prior), ptr(self.inv_sigma_prior))
+        self._out = _lib.CrtLutOut(self.nbest, int(ksplit), ptr(self.index), ptr(self.cost), ptr(self.p))
+
+    @staticmethod
+    def _static(table, y, *, inv_sigma=None, prior=None, inv_sigma_prior=None, nbest=1, p_default=None, ksplit=0):
+        """Every check that needs no device.  -> how the messages call the observations' shape"""
+        import numpy as np
+
+        if not isinstance(table, LutTable):
+            raise TypeError("table must be a LutTable")
+        if len(table.keys) > _lib.LM_MAX_BLOCKS:
+            raise ValueError(f"a match takes {_lib.LM_MAX_BLOCKS} keys at most")
+        axes = _table_axes(table.spectral, len(table.shape) == 3)
+        _check_obs(y, inv_sigma, table.keys, axes, 1 + len(table.shape))
+        if not 1 <= int(nbest) <= LUT_MAX_BEST:
+            raise ValueError(f"nbest must be in 1 .. {LUT_MAX_BEST}, got {nbest}")
+        if not 0 <= int(ksplit) <= _lib.LUT_MAX_KSPLIT:
+            raise ValueError(f"ksplit must be in 0 .. {_lib.LUT_MAX_KSPLIT}, got {ksplit}")
+        if (prior is None) != (inv_sigma_prior is None):
+            raise ValueError("prior and inv_sigma_prior go together")
+        for name, d in (("y", y), ("inv_sigma", inv_sigma or {})):
+            for k, v in d.items():
+                shape = tuple(v.shape) if hasattr(v, "shape") else np.shape(v)
+                if shape[1:] != table.shape or shape[0] < 1:
+                    raise ValueError(f"{name}[{k!r}] must be {axes} = (ncol, {str(table.shape)[1:-1]}), got {shape}")
+        return axes
+
+    def __call__(self, stream=None):
+        dev = self.table.q.device
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.device(dev):
+            with torch.cuda.stream(s):
+                self.p.copy_(self._p_default)  # (a column that has lost its last eligible candidate since the call before falls back)
+            _lib.check(self.lib.crt_hip_lut_match_f64(ctypes.byref(self._t), ctypes.byref(self._o), ctypes.byref(self._out),
+                                                      self.workspace.data_ptr(), self.workspace.numel(), s.cuda_stream), "crt_hip_lut_match_f64")
+        return {"index": self.index, "cost": self.cost, "p": self.p}
+
+    def last_kernel(self):
+        return self.lib.crt_hip_last_kernel().decode()
+
+
+def lut_match(table, y, **kw):
+    """One-shot :class:`LutMatchPlan`: ``{"index", "cost", "p"}``."""
+    LutMatchPlan._static(table, y, **kw)  # (before any device is touched)
+    with torch.cuda.device(table.q.device):
+        return LutMatchPlan(table, y, **kw)()

@@ -444,7 +444,27 @@ class Model:
         res["params"] = plan.params
         return res
 
-    def retrieve(self, weights, y, levels=(0, -1), directions=None, lai=True, wrt_leaf=None, psi=None, niter=20, **lm_options):
+    @staticmethod
+    def _lut_table(lut, lm_options, scheme, cols, b, levels, *, keys, sensors, sun, lai, leaf, **d):
+        """The look-up table of ``lut=K``: K candidates of :func:`crt1d_amd.batched.lut_sample` in ``[lo, hi]``, the default start (or the
+        ``p0`` given) first, evaluated on this model's own column."""
+        from . import batched
+
+        lo, hi, p0, leaf_model = (lm_options.get(k) for k in ("lo", "hi", "p0", "leaf_model"))
+        if lo is None or hi is None:
+            raise ValueError("lut= needs finite bounds lo and hi")
+        if p0 is None and leaf_model is None:
+            p0 = np.zeros(np.shape(lo))
+            if leaf:
+                p0[-1] = float(cols.g_param[0])
+        q = batched.lut_sample(lo, hi, int(lut), include=None if p0 is None else np.asarray(p0, dtype=np.float64).reshape(1, -1))
+        opts = {k: lm_options[k] for k in ("mu_s", "tau_d_method") if k in lm_options}
+        table = batched.LutTable.build(scheme, cols, b, levels, q, keys=keys, sensors=sensors, sun=sun, lai=lai, leaf=leaf,
+                                       leaf_model=leaf_model, **d, **opts)
+        table.p_default = None if lm_options.get("p0") is None else p0  # (the caller's p0 stays the start without an eligible candidate)
+        return table
+
+    def retrieve(self, weights, y, levels=(0, -1), directions=None, lai=True, wrt_leaf=None, psi=None, niter=20, lut=None, **lm_options):
         """A Levenberg-Marquardt retrieval of a parameter vector of this case from sensor-band observations
         (:class:`crt1d_amd.batched.RetrievalPlan`, ``ncol = 1``).  ``y``: ``{key: (nsel, nsens)}`` for keys out of ``"I_dr", "I_df_d",
         "I_df_u", "F"``, the observed values of what :meth:`run_sensors` returns; with ``psi`` (a series of sun angles) ``{key: (nt, nsel,
@@ -455,7 +475,9 @@ class Model:
         ``cov (npar, npar)`` and ``"params"``.  ValueError for ``4s`` and ``zq_pa``.  The model's own state is not changed.
         ``leaf_model=`` (a :class:`crt1d_amd.leaf_model.PlateLeafModel` on this model's wavelengths, among ``lm_options``) retrieves the
         plate model's parameters instead of leaf directions: ``directions`` may then hold ``"soil_r"`` only, and ``p0``, ``lo``, ``hi``
-        are required."""
+        are required.  ``lut=K``: a look-up-table start -- ``K`` candidates sampled in ``[lo, hi]`` (finite bounds required; the
+        default start, or the ``p0`` given, is one of them, and where no candidate has a finite cost the retrieval starts there) are evaluated on this column (:class:`crt1d_amd.batched.LutTable`) and the
+        retrieval starts from the best of them; ``lut=None``: the call as it always was."""
         from . import batched
 
         series = psi is not None
@@ -476,14 +498,18 @@ class Model:
         lead = lambda v: {k: np.asarray(a, dtype=np.float64)[None] for k, a in v.items()}  # noqa: E731
         if lm_options.get("inv_sigma") is not None:
             lm_options["inv_sigma"] = lead(lm_options["inv_sigma"])
-        res = batched.retrieve(scheme, cols, b, levels, self._sensor_set(weights, self.nwl), lead(y), keys=keys or tuple(y), niter=niter,
+        sensors = self._sensor_set(weights, self.nwl)
+        if lut is not None:
+            lm_options["p0"] = self._lut_table(lut, lm_options, scheme, cols, b, levels, keys=keys or tuple(y), sensors=sensors,
+                                               sun=sun if series else None, lai=lai, leaf=wrt_leaf is not None, **d)
+        res = batched.retrieve(scheme, cols, b, levels, sensors, lead(y), keys=keys or tuple(y), niter=niter,
                                sun=sun if series else None, lai=lai, leaf=wrt_leaf is not None, **d, **lm_options)
         out = {k: v[0].cpu().numpy() for k, v in res.items() if k != "params"}
         out["params"] = res["params"]
         return out
 
     def retrieve_spectral(self, y, levels=(-1,), directions=None, lai=True, wrt_leaf=None, niter=20, psi=None, I_dr0_all=None,
-                          I_df0_all=None, **lm_options):
+                          I_df0_all=None, lut=None, **lm_options):
         """:meth:`retrieve` from the level spectra themselves, band by band (:class:`crt1d_amd.batched.SpectralRetrievalPlan`,
         ``ncol = 1``): ``y``: ``{key: (nsel, n_wl)}`` for keys out of ``"I_dr", "I_df_d", "I_df_u", "F"``, the observed spectra at
         ``levels`` (default: the canopy top); with ``psi`` (a series of sun angles, and ``I_dr0_all`` / ``I_df0_all`` as for
@@ -491,7 +517,7 @@ class Model:
         (:class:`crt1d_amd.batched.SpectralNormalSeriesPlan`).  ``directions``, ``lai``, ``wrt_leaf`` as for :meth:`retrieve`.
         ``lm_options``: ``p0``, ``lo``, ``hi``, ``prior``, ``inv_sigma_prior`` (each ``(npar,)``), ``inv_sigma`` (as ``y``; 0 masks a band) and the options of the
         plan.  Returns what :meth:`retrieve` returns.  ValueError for the schemes outside
-        ``batched.SPECTRAL_RETRIEVE_SCHEMES``.  The model's own state is not changed.  ``leaf_model=`` as for :meth:`retrieve`."""
+        ``batched.SPECTRAL_RETRIEVE_SCHEMES``.  The model's own state is not changed.  ``leaf_model=`` and ``lut=`` as for :meth:`retrieve`."""
         from . import batched
 
         from . import _lib
@@ -519,6 +545,9 @@ class Model:
         lead = lambda v: {k: np.asarray(a, dtype=np.float64)[None] for k, a in v.items()}  # noqa: E731
         if lm_options.get("inv_sigma") is not None:
             lm_options["inv_sigma"] = lead(lm_options["inv_sigma"])
+        if lut is not None:
+            lm_options["p0"] = self._lut_table(lut, lm_options, scheme, cols, b, levels, keys=keys or tuple(y), sensors=None,
+                                               sun=lm_options.get("sun"), lai=lai, leaf=wrt_leaf is not None, **d)
         res = batched.retrieve_spectral(scheme, cols, b, levels, lead(y), keys=keys or tuple(y), niter=niter, lai=lai,
                                         leaf=wrt_leaf is not None, **d, **lm_options)
         out = {k: v[0].cpu().numpy() for k, v in res.items() if k != "params"}
