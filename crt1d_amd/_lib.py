@@ -588,6 +588,30 @@ def _lut_signatures():
 _LUT_SIGNATURES = _lut_signatures()
 LUT_EXPORTS = list(_LUT_SIGNATURES)
 
+# the look-up-table posterior (include_post/crt1d_hip_lut_posterior.h): the likelihood-weighted mean and covariance of the table's candidates;
+# the structs of the match, and again a header and a table of their own
+
+
+class CrtLutPosteriorOut(ctypes.Structure):
+    """``crt_lut_posterior_out``: ``temperature`` (finite, > 0), ``temperature_col [ncol]`` or NULL, ``ksplit`` 0 = automatic; ``index
+    [ncol]`` int32, ``cost [ncol]``, ``mean [ncol][npar]``, ``cov [ncol][npar][npar]``, ``wsum [ncol]``, ``ess [ncol]``."""
+
+    _fields_ = [("temperature", ctypes.c_double), ("temperature_col", _vp), ("ksplit", ctypes.c_int32), ("index", _vp), ("cost", _vp),
+                ("mean", _vp), ("cov", _vp), ("wsum", _vp), ("ess", _vp)]
+
+
+def _lut_posterior_signatures():
+    P = ctypes.POINTER
+    i32, sz, ok = ctypes.c_int32, ctypes.c_size_t, ctypes.c_int
+    return {
+        "crt_hip_lut_posterior_workspace_bytes": (sz, [i32, i32, i32, i32]),
+        "crt_hip_lut_posterior_f64": (ok, [P(CrtLutTable), P(CrtLutObs), P(CrtLutPosteriorOut), _vp, sz, _vp]),
+    }
+
+
+_LUT_POSTERIOR_SIGNATURES = _lut_posterior_signatures()
+LUT_POSTERIOR_EXPORTS = list(_LUT_POSTERIOR_SIGNATURES)
+
 _lib = None
 
 
@@ -613,7 +637,7 @@ def load():
     for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES, **_SENSOR_SIGNATURES, **_JAC_SIGNATURES,
                                       **_DLAI_SIGNATURES, **_DLEAF_SIGNATURES, **_GRAD_SIGNATURES, **_SENSJAC_SIGNATURES,
                                       **_SENSJAC_SERIES_SIGNATURES, **_RETRIEVE_SIGNATURES, **_SPECFIT_SIGNATURES,
-                                      **_SPECFIT_SERIES_SIGNATURES, **_LEAFMODEL_SIGNATURES, **_LUT_SIGNATURES}.items():
+                                      **_SPECFIT_SERIES_SIGNATURES, **_LEAFMODEL_SIGNATURES, **_LUT_SIGNATURES, **_LUT_POSTERIOR_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:

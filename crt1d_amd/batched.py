@@ -2304,6 +2304,7 @@ class _LmPlan:
         # the look-up-table start: the best candidate of every column on the plan's own observations and prior
         self.lut = None if table is None else LutMatchPlan(table, self.y, inv_sigma=self.inv_sigma or None, prior=self.prior,
                                                            inv_sigma_prior=self.inv_sigma_prior, p_default=self._p0)
+        self._post = None  # (temperature, the LutPosteriorPlan of lut_posterior())
         self.reset()
 
     def _evaluate(self, ap, s):
@@ -2336,6 +2337,19 @@ class _LmPlan:
         for v in (self.A, self.g, self.status, self.naccept, self.nreject):
             v.zero_()
         return self
+
+    def lut_posterior(self, temperature=1.0, stream=None):
+        """The Bayesian look-up-table estimate of a plan started with ``p0=`` a :class:`LutTable`: a :class:`LutPosteriorPlan` on the plan's
+        own ``y``, ``inv_sigma`` and prior (built at the first call, reused while ``temperature`` stays the same number or tensor), called on
+        ``stream``; its dict.  It reads the observations, not the state of the iteration.  ValueError without a table."""
+        if self.lut is None:
+            raise ValueError("lut_posterior() needs a plan started from a look-up table: p0= a LutTable")
+        held = None if self._post is None else self._post[0]
+        tensors = isinstance(temperature, torch.Tensor) or isinstance(held, torch.Tensor)
+        if self._post is None or not (held is temperature or (not tensors and held == temperature)):
+            self._post = (temperature, LutPosteriorPlan(self.lut.table, self.y, inv_sigma=self.inv_sigma or None, prior=self.prior,
+                                                        inv_sigma_prior=self.inv_sigma_prior, temperature=temperature))
+        return self._post[1](stream)
 
     def run(self, niter, stream=None):
         """``niter`` steps with no host synchronisation in between."""
@@ -2473,13 +2487,20 @@ class RetrievalPlan(_LmPlan):
 
 
 
-def retrieve(scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, y, *, keys, niter=20, **kw):
-    """One-shot :class:`RetrievalPlan`: ``niter`` steps from ``p0``; what ``plan.result()`` returns, and ``"cov"``, ``plan.covariance()``."""
+def retrieve(scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, y, *, keys, niter=20, posterior=False, **kw):
+    """One-shot :class:`RetrievalPlan`: ``niter`` steps from ``p0``; what ``plan.result()`` returns, and ``"cov"``, ``plan.covariance()``.
+    ``posterior=True`` (``p0`` a :class:`LutTable`, else ValueError) adds ``"lut_mean"``, ``"lut_cov"`` and ``"lut_ess"``, what
+    ``plan.lut_posterior()`` gives."""
+    if posterior and not isinstance(kw.get("p0"), LutTable):
+        raise ValueError("posterior=True needs a look-up table: p0= a LutTable (Model: lut=K)")
     RetrievalPlan._static(scheme, cols, bands, levels, sensors, y, keys=keys, **kw)  # (before any device is touched)
     with torch.cuda.device(cols.device):
         plan = RetrievalPlan(scheme, cols, bands, levels, sensors, y, keys=keys, **kw).run(niter)
         res = plan.result()
         res["cov"] = plan.covariance()
+        if posterior:
+            post = plan.lut_posterior()
+            res.update({"lut_" + k: post[k].clone() for k in ("mean", "cov", "ess")})
     return res
 
 
@@ -2745,14 +2766,20 @@ class SpectralRetrievalPlan(_LmPlan):
                 return {k: v.clone() for k, v in self.normal.out["fwd"].items()}
 
 
-def retrieve_spectral(scheme, cols: Columns, bands: Bands, levels, y, *, keys, niter=20, **kw):
+def retrieve_spectral(scheme, cols: Columns, bands: Bands, levels, y, *, keys, niter=20, posterior=False, **kw):
     """One-shot :class:`SpectralRetrievalPlan`: ``niter`` steps from ``p0``; what ``plan.result()`` returns, and ``"cov"``,
-    ``plan.covariance()``."""
+    ``plan.covariance()``.  ``posterior=True`` (``p0`` a :class:`LutTable`, else ValueError) adds ``"lut_mean"``, ``"lut_cov"`` and
+    ``"lut_ess"``, what ``plan.lut_posterior()`` gives."""
+    if posterior and not isinstance(kw.get("p0"), LutTable):
+        raise ValueError("posterior=True needs a look-up table: p0= a LutTable (Model: lut=K)")
     SpectralRetrievalPlan._static(scheme, cols, bands, levels, y, keys=keys, **kw)  # (before any device is touched)
     with torch.cuda.device(cols.device):
         plan = SpectralRetrievalPlan(scheme, cols, bands, levels, y, keys=keys, **kw).run(niter)
         res = plan.result()
         res["cov"] = plan.covariance()
+        if posterior:
+            post = plan.lut_posterior()
+            res.update({"lut_" + k: post[k].clone() for k in ("mean", "cov", "ess")})
     return res
 
 
@@ -3111,21 +3138,38 @@ def _check_lut_start(table, params, keys, spectral, y):
             raise ValueError(f"the table's rows are {table.shape} per candidate, y[{k!r}] is {tuple(np.shape(y[k]))}")
 
 
-class LutMatchPlan:
-    """The best ``nbest`` candidates of a :class:`LutTable` for every column, in one kernel pass (``crt_hip_lut_match_f64``): the weighted
-    misfit of the observations ``y[k] (ncol, *table.shape)`` (``inv_sigma[k]`` the same shape; ``None`` / a missing key: ones; an entry 0:
-    not observed, its ``y`` may be NaN) and the prior ``prior`` / ``inv_sigma_prior`` (``(ncol, npar)`` or ``(npar,)``, both or neither)
-    against every table row, under the cost contract of the Levenberg-Marquardt step, with the selection fused: neither the costs ``ncol x
-    K`` nor the residuals are written.  Everything is bound at construction and the workspace allocated once; tensors on the table's
-    device are read where they lie at every call.  ``plan()`` is one C call and returns ``{"index" (ncol, nbest) int32, "cost" (ncol,
-    nbest), "p" (ncol, npar)}``: the candidates in ascending (cost, index), ``-1`` / ``+inf`` where fewer than ``nbest`` have a cost below
-    ``+inf``, and ``p = q[index[:, 0]]`` -- filled at every call with ``p_default`` (``(ncol, npar)`` or ``(npar,)``; default NaN) first,
-    which a column without any eligible candidate keeps.  ``ksplit``: how many workgroups share the candidates of 64 columns (0: automatic);
-    it changes no bit of the result."""
+class _LutObsPlan:
+    """What the plans on a :class:`LutTable` share: the device-free checks of the table and the observations, and the structs
+    ``crt_lut_table`` / ``crt_lut_obs`` bound to the tensors."""
 
-    def __init__(self, table, y, *, inv_sigma=None, prior=None, inv_sigma_prior=None, nbest=1, p_default=None, ksplit=0):
-        axes = self._static(table, y, inv_sigma=inv_sigma, prior=prior, inv_sigma_prior=inv_sigma_prior, nbest=nbest, ksplit=ksplit)
-        self.lib, self.table, self.nbest = _lib.load(), table, int(nbest)
+    @staticmethod
+    def _check_table(table, y, inv_sigma):
+        """-> how the messages call the observations' shape"""
+        if not isinstance(table, LutTable):
+            raise TypeError("table must be a LutTable")
+        if len(table.keys) > _lib.LM_MAX_BLOCKS:
+            raise ValueError(f"a match takes {_lib.LM_MAX_BLOCKS} keys at most")
+        axes = _table_axes(table.spectral, len(table.shape) == 3)
+        _check_obs(y, inv_sigma, table.keys, axes, 1 + len(table.shape))
+        return axes
+
+    @staticmethod
+    def _check_rest(table, y, inv_sigma, prior, inv_sigma_prior, ksplit, axes):
+        import numpy as np
+
+        if not 0 <= int(ksplit) <= _lib.LUT_MAX_KSPLIT:
+            raise ValueError(f"ksplit must be in 0 .. {_lib.LUT_MAX_KSPLIT}, got {ksplit}")
+        if (prior is None) != (inv_sigma_prior is None):
+            raise ValueError("prior and inv_sigma_prior go together")
+        for name, d in (("y", y), ("inv_sigma", inv_sigma or {})):
+            for k, v in d.items():
+                shape = tuple(v.shape) if hasattr(v, "shape") else np.shape(v)
+                if shape[1:] != table.shape or shape[0] < 1:
+                    raise ValueError(f"{name}[{k!r}] must be {axes} = (ncol, {str(table.shape)[1:-1]}), got {shape}")
+
+    def _bind(self, table, y, inv_sigma, prior, inv_sigma_prior, axes):
+        """The observations on the table's device and the two input structs."""
+        self.lib, self.table = _lib.load(), table
         dev, keys, npar = table.q.device, table.keys, table.npar
 
         def obs(v, name, ncol=None):
@@ -3140,13 +3184,6 @@ class LutMatchPlan:
         self.inv_sigma = {k: obs(inv_sigma[k], f"inv_sigma[{k!r}]", ncol) for k in keys if inv_sigma is not None and k in inv_sigma}
         self.prior = None if prior is None else _per_col(prior, "prior", ncol, npar, dev)
         self.inv_sigma_prior = None if prior is None else _per_col(inv_sigma_prior, "inv_sigma_prior", ncol, npar, dev)
-        self.index = torch.full((ncol, self.nbest), -1, dtype=torch.int32, device=dev)
-        self.cost = torch.full((ncol, self.nbest), float("inf"), dtype=torch.float64, device=dev)
-        fill = torch.full((npar,), float("nan"), dtype=torch.float64) if p_default is None else p_default
-        self._p_default = _per_col(fill, "p_default", ncol, npar, dev).clone()
-        self.p = self._p_default.clone()
-        need = int(self.lib.crt_hip_lut_match_workspace_bytes(ncol, table.ncand, self.nbest))
-        self.workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
         ptr = lambda v: None if v is None else v.data_ptr()  # noqa: E731
         pad = lambda v: v + [None] * (_lib.LM_MAX_BLOCKS - len(v))  # noqa: E731
         nblk = len(keys)
@@ -3155,30 +3192,44 @@ class LutMatchPlan:
         self._o = _lib.CrtLutObs(ncol, (ctypes.c_void_p * _lib.LM_MAX_BLOCKS)(*pad([ptr(self.y[k]) for k in keys])),
                                  (ctypes.c_void_p * _lib.LM_MAX_BLOCKS)(*pad([ptr(self.inv_sigma.get(k)) for k in keys])),
                                  ptr(self.prior), ptr(self.inv_sigma_prior))
-        self._out = _lib.CrtLutOut(self.nbest, int(ksplit), ptr(self.index), ptr(self.cost), ptr(self.p))
+
+    def last_kernel(self):
+        return self.lib.crt_hip_last_kernel().decode()
+
+
+class LutMatchPlan(_LutObsPlan):
+    """The best ``nbest`` candidates of a :class:`LutTable` for every column, in one kernel pass (``crt_hip_lut_match_f64``): the weighted
+    misfit of the observations ``y[k] (ncol, *table.shape)`` (``inv_sigma[k]`` the same shape; ``None`` / a missing key: ones; an entry 0:
+    not observed, its ``y`` may be NaN) and the prior ``prior`` / ``inv_sigma_prior`` (``(ncol, npar)`` or ``(npar,)``, both or neither)
+    against every table row, under the cost contract of the Levenberg-Marquardt step, with the selection fused: neither the costs ``ncol x
+    K`` nor the residuals are written.  Everything is bound at construction and the workspace allocated once; tensors on the table's
+    device are read where they lie at every call.  ``plan()`` is one C call and returns ``{"index" (ncol, nbest) int32, "cost" (ncol,
+    nbest), "p" (ncol, npar)}``: the candidates in ascending (cost, index), ``-1`` / ``+inf`` where fewer than ``nbest`` have a cost below
+    ``+inf``, and ``p = q[index[:, 0]]`` -- filled at every call with ``p_default`` (``(ncol, npar)`` or ``(npar,)``; default NaN) first,
+    which a column without any eligible candidate keeps.  ``ksplit``: how many workgroups share the candidates of 64 columns (0: automatic);
+    it changes no bit of the result."""
+
+    def __init__(self, table, y, *, inv_sigma=None, prior=None, inv_sigma_prior=None, nbest=1, p_default=None, ksplit=0):
+        axes = self._static(table, y, inv_sigma=inv_sigma, prior=prior, inv_sigma_prior=inv_sigma_prior, nbest=nbest, ksplit=ksplit)
+        self.nbest = int(nbest)
+        self._bind(table, y, inv_sigma, prior, inv_sigma_prior, axes)
+        dev, npar, ncol = table.q.device, table.npar, self.ncol
+        self.index = torch.full((ncol, self.nbest), -1, dtype=torch.int32, device=dev)
+        self.cost = torch.full((ncol, self.nbest), float("inf"), dtype=torch.float64, device=dev)
+        fill = torch.full((npar,), float("nan"), dtype=torch.float64) if p_default is None else p_default
+        self._p_default = _per_col(fill, "p_default", ncol, npar, dev).clone()
+        self.p = self._p_default.clone()
+        need = int(self.lib.crt_hip_lut_match_workspace_bytes(ncol, table.ncand, self.nbest))
+        self.workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+        self._out = _lib.CrtLutOut(self.nbest, int(ksplit), self.index.data_ptr(), self.cost.data_ptr(), self.p.data_ptr())
 
     @staticmethod
     def _static(table, y, *, inv_sigma=None, prior=None, inv_sigma_prior=None, nbest=1, p_default=None, ksplit=0):
         """Every check that needs no device.  -> how the messages call the observations' shape"""
-        import numpy as np
-
-        if not isinstance(table, LutTable):
-            raise TypeError("table must be a LutTable")
-        if len(table.keys) > _lib.LM_MAX_BLOCKS:
-            raise ValueError(f"a match takes {_lib.LM_MAX_BLOCKS} keys at most")
-        axes = _table_axes(table.spectral, len(table.shape) == 3)
-        _check_obs(y, inv_sigma, table.keys, axes, 1 + len(table.shape))
+        axes = _LutObsPlan._check_table(table, y, inv_sigma)
         if not 1 <= int(nbest) <= LUT_MAX_BEST:
             raise ValueError(f"nbest must be in 1 .. {LUT_MAX_BEST}, got {nbest}")
-        if not 0 <= int(ksplit) <= _lib.LUT_MAX_KSPLIT:
-            raise ValueError(f"ksplit must be in 0 .. {_lib.LUT_MAX_KSPLIT}, got {ksplit}")
-        if (prior is None) != (inv_sigma_prior is None):
-            raise ValueError("prior and inv_sigma_prior go together")
-        for name, d in (("y", y), ("inv_sigma", inv_sigma or {})):
-            for k, v in d.items():
-                shape = tuple(v.shape) if hasattr(v, "shape") else np.shape(v)
-                if shape[1:] != table.shape or shape[0] < 1:
-                    raise ValueError(f"{name}[{k!r}] must be {axes} = (ncol, {str(table.shape)[1:-1]}), got {shape}")
+        _LutObsPlan._check_rest(table, y, inv_sigma, prior, inv_sigma_prior, ksplit, axes)
         return axes
 
     def __call__(self, stream=None):
@@ -3191,12 +3242,86 @@ class LutMatchPlan:
                                                       self.workspace.data_ptr(), self.workspace.numel(), s.cuda_stream), "crt_hip_lut_match_f64")
         return {"index": self.index, "cost": self.cost, "p": self.p}
 
-    def last_kernel(self):
-        return self.lib.crt_hip_last_kernel().decode()
-
 
 def lut_match(table, y, **kw):
     """One-shot :class:`LutMatchPlan`: ``{"index", "cost", "p"}``."""
     LutMatchPlan._static(table, y, **kw)  # (before any device is touched)
     with torch.cuda.device(table.q.device):
         return LutMatchPlan(table, y, **kw)()
+
+
+class LutPosteriorPlan(_LutObsPlan):
+    """The Bayesian look-up-table estimate of every column (``crt_hip_lut_posterior_f64``, include_post/crt1d_hip_lut_posterior.h): the
+    mean and the covariance of the ``K`` candidates of a :class:`LutTable` weighted by ``exp(-(cost - cmin) / temperature)``, with the
+    effective sample size -- a value with a global uncertainty where the Levenberg-Marquardt covariance describes one basin.  ``table``,
+    ``y``, ``inv_sigma``, ``prior``, ``inv_sigma_prior`` as for :class:`LutMatchPlan` (the cost is the same, bit for bit).
+    ``temperature``: a float (finite, > 0) or an ``(ncol,)`` tensor; a column whose value is not finite or not > 0 gets no result.  With
+    costs that are half sums of squared residuals in units of the noise, 1 is the Gaussian likelihood.  ``ksplit``: the parts the candidates
+    are summed in (0: automatic, a function of ``ncol`` and ``K``); the sums are formed in a fixed order for a given ``ksplit``, so a fixed
+    value keeps a column's bits across batch sizes, and different values agree within rounding.  ``plan()`` is one C call and returns
+    ``{"mean" (ncol, npar), "cov" (ncol, npar, npar), "ess" (ncol,), "wsum" (ncol,), "index" (ncol,) int32, "cost" (ncol,)}``: ``index`` /
+    ``cost`` the best candidate (what ``lut_match`` gives), ``wsum`` the sum of the weights (the best one's is 1) and ``ess = wsum^2 / sum
+    w^2`` the effective number of candidates behind the estimate -- a few means the table is too coarse for the noise.  ``mean`` and
+    ``cov`` are filled with NaN before every call; a column without an eligible candidate keeps that fill and gets ``index -1``, ``cost
+    +inf``, ``wsum = ess = 0``.
+
+    A temperature taken from the best cost (e.g. the reduced chi-square) needs no host synchronisation::
+
+        best = lut_match(table, y, inv_sigma=w)["cost"][:, 0]
+        post = lut_posterior(table, y, inv_sigma=w, temperature=torch.clamp(2.0 * best / nobs, min=1.0))
+    """
+
+    def __init__(self, table, y, *, inv_sigma=None, prior=None, inv_sigma_prior=None, temperature=1.0, ksplit=0):
+        axes = self._static(table, y, inv_sigma=inv_sigma, prior=prior, inv_sigma_prior=inv_sigma_prior, temperature=temperature,
+                            ksplit=ksplit)
+        self._bind(table, y, inv_sigma, prior, inv_sigma_prior, axes)
+        dev, npar, ncol = table.q.device, table.npar, self.ncol
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+        self.index = torch.full((ncol,), -1, dtype=torch.int32, device=dev)
+        self.cost, self.mean, self.cov, self.wsum, self.ess = new(ncol), new(ncol, npar), new(ncol, npar, npar), new(ncol), new(ncol)
+        self.temperature = None
+        if isinstance(temperature, torch.Tensor):  # ((ncol,): _static)
+            self.temperature = temperature.to(device=dev, dtype=torch.float64).contiguous()
+        need = int(self.lib.crt_hip_lut_posterior_workspace_bytes(ncol, table.ncand, npar, int(ksplit)))
+        self.workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+        self._out = _lib.CrtLutPosteriorOut(1.0 if self.temperature is not None else float(temperature),
+                                            None if self.temperature is None else self.temperature.data_ptr(), int(ksplit),
+                                            *[v.data_ptr() for v in (self.index, self.cost, self.mean, self.cov, self.wsum, self.ess)])
+
+    @staticmethod
+    def _static(table, y, *, inv_sigma=None, prior=None, inv_sigma_prior=None, temperature=1.0, ksplit=0):
+        """Every check that needs no device.  -> how the messages call the observations' shape"""
+        import math
+
+        axes = _LutObsPlan._check_table(table, y, inv_sigma)
+        if isinstance(temperature, torch.Tensor):
+            if temperature.ndim != 1 or not temperature.dtype.is_floating_point:
+                raise ValueError(f"temperature must be a number or a floating-point (ncol,) tensor, got {tuple(temperature.shape)}")
+        elif isinstance(temperature, bool) or not isinstance(temperature, (int, float)):
+            raise TypeError("temperature must be a number or an (ncol,) tensor")
+        elif not (math.isfinite(temperature) and temperature > 0):
+            raise ValueError(f"temperature must be finite and > 0, got {temperature}")
+        _LutObsPlan._check_rest(table, y, inv_sigma, prior, inv_sigma_prior, ksplit, axes)
+        ncol = y[table.keys[0]].shape[0]
+        if isinstance(temperature, torch.Tensor) and temperature.shape[0] != ncol:
+            raise ValueError(f"temperature must be a number or (ncol,) = ({ncol},), got {tuple(temperature.shape)}")
+        return axes
+
+    def __call__(self, stream=None):
+        dev = self.table.q.device
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.device(dev):
+            with torch.cuda.stream(s):
+                self.mean.fill_(float("nan"))
+                self.cov.fill_(float("nan"))
+            _lib.check(self.lib.crt_hip_lut_posterior_f64(ctypes.byref(self._t), ctypes.byref(self._o), ctypes.byref(self._out),
+                                                          self.workspace.data_ptr(), self.workspace.numel(), s.cuda_stream),
+                       "crt_hip_lut_posterior_f64")
+        return {k: getattr(self, k) for k in ("mean", "cov", "ess", "wsum", "index", "cost")}
+
+
+def lut_posterior(table, y, **kw):
+    """One-shot :class:`LutPosteriorPlan`: ``{"mean", "cov", "ess", "wsum", "index", "cost"}``."""
+    LutPosteriorPlan._static(table, y, **kw)  # (before any device is touched)
+    with torch.cuda.device(table.q.device):
+        return LutPosteriorPlan(table, y, **kw)()

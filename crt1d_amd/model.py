@@ -464,7 +464,8 @@ class Model:
         table.p_default = None if lm_options.get("p0") is None else p0  # (the caller's p0 stays the start without an eligible candidate)
         return table
 
-    def retrieve(self, weights, y, levels=(0, -1), directions=None, lai=True, wrt_leaf=None, psi=None, niter=20, lut=None, **lm_options):
+    def retrieve(self, weights, y, levels=(0, -1), directions=None, lai=True, wrt_leaf=None, psi=None, niter=20, lut=None, posterior=False,
+                 **lm_options):
         """A Levenberg-Marquardt retrieval of a parameter vector of this case from sensor-band observations
         (:class:`crt1d_amd.batched.RetrievalPlan`, ``ncol = 1``).  ``y``: ``{key: (nsel, nsens)}`` for keys out of ``"I_dr", "I_df_d",
         "I_df_u", "F"``, the observed values of what :meth:`run_sensors` returns; with ``psi`` (a series of sun angles) ``{key: (nt, nsel,
@@ -477,8 +478,13 @@ class Model:
         plate model's parameters instead of leaf directions: ``directions`` may then hold ``"soil_r"`` only, and ``p0``, ``lo``, ``hi``
         are required.  ``lut=K``: a look-up-table start -- ``K`` candidates sampled in ``[lo, hi]`` (finite bounds required; the
         default start, or the ``p0`` given, is one of them, and where no candidate has a finite cost the retrieval starts there) are evaluated on this column (:class:`crt1d_amd.batched.LutTable`) and the
-        retrieval starts from the best of them; ``lut=None``: the call as it always was."""
+        retrieval starts from the best of them; ``lut=None``: the call as it always was.  ``posterior=True`` (with ``lut=``, else ValueError)
+        adds the Bayesian look-up-table estimate over those candidates (:class:`crt1d_amd.batched.LutPosteriorPlan`, temperature 1):
+        ``lut_mean (npar,)``, ``lut_cov (npar, npar)`` and ``lut_ess``, the effective number of candidates behind it."""
         from . import batched
+
+        if posterior and lut is None:
+            raise ValueError("posterior=True needs lut=K: the estimate is taken over the candidates of the look-up table")
 
         series = psi is not None
         spectra = [lm_options.pop(k, None) for k in ("I_dr0_all", "I_df0_all")]
@@ -503,13 +509,14 @@ class Model:
             lm_options["p0"] = self._lut_table(lut, lm_options, scheme, cols, b, levels, keys=keys or tuple(y), sensors=sensors,
                                                sun=sun if series else None, lai=lai, leaf=wrt_leaf is not None, **d)
         res = batched.retrieve(scheme, cols, b, levels, sensors, lead(y), keys=keys or tuple(y), niter=niter,
-                               sun=sun if series else None, lai=lai, leaf=wrt_leaf is not None, **d, **lm_options)
+                               sun=sun if series else None, lai=lai, leaf=wrt_leaf is not None, posterior=posterior, **d,
+                               **lm_options)
         out = {k: v[0].cpu().numpy() for k, v in res.items() if k != "params"}
         out["params"] = res["params"]
         return out
 
     def retrieve_spectral(self, y, levels=(-1,), directions=None, lai=True, wrt_leaf=None, niter=20, psi=None, I_dr0_all=None,
-                          I_df0_all=None, lut=None, **lm_options):
+                          I_df0_all=None, lut=None, posterior=False, **lm_options):
         """:meth:`retrieve` from the level spectra themselves, band by band (:class:`crt1d_amd.batched.SpectralRetrievalPlan`,
         ``ncol = 1``): ``y``: ``{key: (nsel, n_wl)}`` for keys out of ``"I_dr", "I_df_d", "I_df_u", "F"``, the observed spectra at
         ``levels`` (default: the canopy top); with ``psi`` (a series of sun angles, and ``I_dr0_all`` / ``I_df0_all`` as for
@@ -517,8 +524,11 @@ class Model:
         (:class:`crt1d_amd.batched.SpectralNormalSeriesPlan`).  ``directions``, ``lai``, ``wrt_leaf`` as for :meth:`retrieve`.
         ``lm_options``: ``p0``, ``lo``, ``hi``, ``prior``, ``inv_sigma_prior`` (each ``(npar,)``), ``inv_sigma`` (as ``y``; 0 masks a band) and the options of the
         plan.  Returns what :meth:`retrieve` returns.  ValueError for the schemes outside
-        ``batched.SPECTRAL_RETRIEVE_SCHEMES``.  The model's own state is not changed.  ``leaf_model=`` and ``lut=`` as for :meth:`retrieve`."""
+        ``batched.SPECTRAL_RETRIEVE_SCHEMES``.  The model's own state is not changed.  ``leaf_model=``, ``lut=`` and ``posterior=`` as for :meth:`retrieve`."""
         from . import batched
+
+        if posterior and lut is None:
+            raise ValueError("posterior=True needs lut=K: the estimate is taken over the candidates of the look-up table")
 
         from . import _lib
 
@@ -549,7 +559,7 @@ class Model:
             lm_options["p0"] = self._lut_table(lut, lm_options, scheme, cols, b, levels, keys=keys or tuple(y), sensors=None,
                                                sun=lm_options.get("sun"), lai=lai, leaf=wrt_leaf is not None, **d)
         res = batched.retrieve_spectral(scheme, cols, b, levels, lead(y), keys=keys or tuple(y), niter=niter, lai=lai,
-                                        leaf=wrt_leaf is not None, **d, **lm_options)
+                                        leaf=wrt_leaf is not None, posterior=posterior, **d, **lm_options)
         out = {k: v[0].cpu().numpy() for k, v in res.items() if k != "params"}
         out["params"] = res["params"]
         return out
