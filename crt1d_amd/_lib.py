@@ -612,6 +612,44 @@ def _lut_posterior_signatures():
 _LUT_POSTERIOR_SIGNATURES = _lut_posterior_signatures()
 LUT_POSTERIOR_EXPORTS = list(_LUT_POSTERIOR_SIGNATURES)
 
+# the Levenberg-Marquardt step on a chain of coupled dates (include_chain/crt1d_hip_lm_chain.h): the sums from sensor rows, the step of a
+# pixel's nd dates under a random-walk prior, the smoothed marginal covariances; the structs of the step, a header and a table of their own
+
+LM_CHAIN_LDS_LIMIT = 160 * 1024  # CRT_LM_CHAIN_LDS_LIMIT
+
+
+def lm_chain_lds_bytes(nd, npar):
+    """``CRT_LM_CHAIN_LDS_BYTES(nd, npar)``: the dynamic LDS of one pixel of the chain kernels."""
+    return 8 * (nd * (2 * npar * npar + 4 * npar) + 4 * npar * npar + 64)
+
+
+def lm_chain_max_nd(npar):
+    """``crt_hip_lm_chain_max_nd``: the largest ``nd`` whose LDS fits the limit; 0 for a refused ``npar``.  No library is loaded."""
+    if not 1 <= npar <= RETRIEVE_MAX_NPAR:
+        return 0
+    return (LM_CHAIN_LDS_LIMIT // 8 - 4 * npar * npar - 64) // (2 * npar * npar + 4 * npar)
+
+
+class CrtLmChain(ctypes.Structure):
+    """``crt_lm_chain``: ``npix``, ``nd``; ``dyn_stride`` 0 or ``(nd - 1) * npar``; ``inv_sigma_dyn [npix or 1][nd - 1][npar]``."""
+
+    _fields_ = [("npix", ctypes.c_int32), ("nd", ctypes.c_int32), ("dyn_stride", ctypes.c_int64), ("inv_sigma_dyn", _vp)]
+
+
+def _chain_signatures():
+    P = ctypes.POINTER
+    i32, ok = ctypes.c_int32, ctypes.c_int
+    return {
+        "crt_hip_lm_normal_f64": (ok, [i32, i32, P(CrtLmObs), i32, _vp, _vp, _vp, _vp]),
+        "crt_hip_lm_step_chain_f64": (ok, [P(CrtLmChain), P(CrtLmProblem), P(CrtLmNormalBlock), i32, P(CrtLmState), _vp]),
+        "crt_hip_lm_chain_covariance_f64": (ok, [P(CrtLmChain), i32, _vp, _vp, _vp]),
+        "crt_hip_lm_chain_max_nd": (i32, [i32]),
+    }
+
+
+_CHAIN_SIGNATURES = _chain_signatures()
+CHAIN_EXPORTS = list(_CHAIN_SIGNATURES)
+
 _lib = None
 
 
@@ -637,7 +675,8 @@ def load():
     for name, (restype, argtypes) in {**_SIGNATURES, **_LEAF_SIGNATURES, **_SPECTRA_SIGNATURES, **_SENSOR_SIGNATURES, **_JAC_SIGNATURES,
                                       **_DLAI_SIGNATURES, **_DLEAF_SIGNATURES, **_GRAD_SIGNATURES, **_SENSJAC_SIGNATURES,
                                       **_SENSJAC_SERIES_SIGNATURES, **_RETRIEVE_SIGNATURES, **_SPECFIT_SIGNATURES,
-                                      **_SPECFIT_SERIES_SIGNATURES, **_LEAFMODEL_SIGNATURES, **_LUT_SIGNATURES, **_LUT_POSTERIOR_SIGNATURES}.items():
+                                      **_SPECFIT_SERIES_SIGNATURES, **_LEAFMODEL_SIGNATURES, **_LUT_SIGNATURES, **_LUT_POSTERIOR_SIGNATURES,
+                                      **_CHAIN_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:

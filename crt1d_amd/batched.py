@@ -2231,6 +2231,32 @@ def _check_start(leaf_model, lo, hi, p0, prior, inv_sigma_prior):
         raise ValueError("prior and inv_sigma_prior go together")
 
 
+def _check_chain(chain, inv_sigma_chain, ncol, npar):
+    """``chain=nd`` and ``inv_sigma_chain=`` of a retrieval plan with ``ncol`` columns (or: of the :class:`Columns` ``ncol``), as far as no
+    device is needed.  -> None (no chain) or (npix, nd)"""
+    if chain is None:
+        if inv_sigma_chain is not None:
+            raise ValueError("inv_sigma_chain needs chain= the number of dates")
+        return None
+    nd = int(chain)
+    if nd != chain or nd < 1:
+        raise ValueError(f"chain must be the number of dates, an integer >= 1, got {chain!r}")
+    ncol = ncol if isinstance(ncol, int) else ncol.ncol
+    if ncol % nd:
+        raise ValueError(f"chain = {nd} dates does not divide ncol = {ncol}: the columns are (pixel, date) pairs, pixel-major")
+    if nd > _lib.lm_chain_max_nd(npar):
+        raise ValueError(f"chain = {nd} dates is beyond the {_lib.lm_chain_max_nd(npar)} the chain kernel serves at npar = {npar}")
+    npix = ncol // nd
+    if inv_sigma_chain is None:
+        raise ValueError("a chain needs inv_sigma_chain (nd - 1, npar) or (npix, nd - 1, npar)")
+    w = torch.as_tensor(inv_sigma_chain)
+    if tuple(w.shape) not in ((nd - 1, npar), (npix, nd - 1, npar)):
+        raise ValueError(f"inv_sigma_chain must be {(nd - 1, npar)} or {(npix, nd - 1, npar)}, got {tuple(w.shape)}")
+    if not bool((w >= 0).all()):  # (false for NaN)
+        raise ValueError("inv_sigma_chain must be >= 0 (0: not coupled across that gap) and not NaN")
+    return npix, nd
+
+
 class _LmPlan:
     """What :class:`RetrievalPlan` and :class:`SpectralRetrievalPlan` share: the base and the working :class:`Columns` / :class:`Bands`, the
     leaf-angle tangent, the leaf-model binding, the bounds, the prior, the starting point and the Levenberg-Marquardt state, the structs
@@ -2238,7 +2264,10 @@ class _LmPlan:
     plan or plans, bound to the working tensors, and its observation structs -- and ``step``, which closes an evaluation with its C
     call."""
 
-    def _construct(self, keys, axis, o, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, **inner):
+    _owns_sums = True  # a chained plan allocates its block of per-column sums; False: the subclass's _inner binds ``_blk`` to its own
+
+    def _construct(self, keys, axis, o, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, chain=None,
+                   inv_sigma_chain=None, **inner):
         self.lib = _lib.load()
         self.scheme, self.keys, self.sun, self.options = scheme, keys, sun, o
         ncol, nz, nb, dev = cols.ncol, cols.nz, bands.nb, cols.device
@@ -2284,9 +2313,12 @@ class _LmPlan:
         # the state
         ntri = npar * (npar + 1) // 2
         i32 = dict(dtype=torch.int32, device=dev)
-        self.p, self.p_trial, self.cost, self.lam = new(ncol, npar), new(ncol, npar), new(ncol), new(ncol)
+        # (a chain of nd dates: the columns are (pixel, date) pairs, p, p_trial, A and g stay per column, the rest is per pixel)
+        self.nd = None if chain is None else int(chain)
+        nunit = self.npix = ncol if chain is None else ncol // self.nd
+        self.p, self.p_trial, self.cost, self.lam = new(ncol, npar), new(ncol, npar), new(nunit), new(nunit)
         self.A, self.g = new(ncol, ntri), new(ncol, npar)
-        self.status, self.naccept, self.nreject = (torch.zeros((ncol,), **i32) for _ in range(3))
+        self.status, self.naccept, self.nreject = (torch.zeros((nunit,), **i32) for _ in range(3))
         self.cov = new(ncol, npar, npar)
         # the structs of the entries: k_retrieve_apply at the trial point (_ap) and at the accepted point (_ap_p)
         ptr = lambda v: None if v is None else v.data_ptr()  # noqa: E731
@@ -2301,6 +2333,12 @@ class _LmPlan:
                                                           self.nreject)])
         self._c = c.c_struct()
         self._s = None if sun is None else sun.c_struct()
+        if chain is not None:  # the coupling weights, and the block of per-column sums of a plan that has none of its own
+            w = self.inv_sigma_chain = torch.as_tensor(inv_sigma_chain, dtype=torch.float64).to(dev).contiguous()
+            self._chain = _lib.CrtLmChain(nunit, self.nd, 0 if w.ndim == 2 else (self.nd - 1) * npar, ptr(w) if self.nd > 1 else None)
+            if self._owns_sums:
+                self.sums = (new(ncol, ntri), new(ncol, npar), new(ncol))
+                self._blk = (_lib.CrtLmNormalBlock * 1)(_lib.CrtLmNormalBlock(*[v.data_ptr() for v in self.sums]))
         # the look-up-table start: the best candidate of every column on the plan's own observations and prior
         self.lut = None if table is None else LutMatchPlan(table, self.y, inv_sigma=self.inv_sigma or None, prior=self.prior,
                                                            inv_sigma_prior=self.inv_sigma_prior, p_default=self._p0)
@@ -2320,6 +2358,11 @@ class _LmPlan:
         elif t is not None:
             _lib.check(lib.crt_hip_g_dparam_series_f64(ref(self._c), ref(self._s), t.dg_table.data_ptr(), t.dg_at_psi.data_ptr(), h),
                        "crt_hip_g_dparam_series_f64")
+
+    def _step_chain(self, s):
+        """The closing call of a chained ``step()``: ``k_lm_step_chain`` on the plan's one block of sums."""
+        _lib.check(self.lib.crt_hip_lm_step_chain_f64(ctypes.byref(self._chain), ctypes.byref(self._prob), self._blk, 1, ctypes.byref(self._state),
+                                                      s.cuda_stream), "crt_hip_lm_step_chain_f64")
 
     def reset(self, p0=None):
         """Restart the state at ``p0`` (default: the plan's starting point): ``p = p_trial = p0``, ``cost = +inf``, ``lam = lam0``.  A plan
@@ -2360,12 +2403,14 @@ class _LmPlan:
     def result(self):
         """Copies of ``p``, ``cost``, ``status`` (``LM_*``), ``lam``, ``naccept``, ``nreject``, and ``params``, the names of the columns of ``p``."""
         r = {k: getattr(self, k).clone() for k in ("p", "cost", "status", "lam", "naccept", "nreject")}
+        if self.nd is not None:  # p (npix, nd, npar); cost, status, lam and the counters per pixel
+            r["p"] = r["p"].reshape(self.npix, self.nd, self.npar)
         r["params"] = self.params
         return r
 
     def nobs(self):
         """``(ncol,)``: the rows every column is observed in (``inv_sigma != 0``), the rows of the prior included."""
-        n = torch.zeros_like(self.cost)
+        n = torch.zeros_like(self.cost) if self.nd is None else self.p.new_zeros(self.p.shape[0])
         for k in self.keys:
             n += float(self.nrow) if k not in self.inv_sigma else (self.inv_sigma[k] != 0).reshape(n.shape[0], -1).sum(1)
         if self.inv_sigma_prior is not None:
@@ -2375,9 +2420,18 @@ class _LmPlan:
     def covariance(self, scale=False, stream=None):
         """The posterior covariance ``(ncol, npar, npar)``: the inverse of the undamped normal matrix at the accepted point
         (``crt_hip_lm_covariance_f64``); a dead parameter has variance ``+inf`` and zero covariances.  ``scale=True`` multiplies by the
-        reduced chi-square ``2 cost / (nobs - npar)`` (for observations without error estimates)."""
+        reduced chi-square ``2 cost / (nobs - npar)`` (for observations without error estimates).  With a chain: ``(npix, nd, npar,
+        npar)``, the smoothed marginal covariance of every date (``crt_hip_lm_chain_covariance_f64``: the diagonal blocks of the inverse
+        of the pixel's block-tridiagonal matrix); ``scale=True`` is a ValueError then -- the coupling is a prior with a stated sigma."""
+        if self.nd is not None and scale:
+            raise ValueError("covariance(scale=True) has no meaning with a chain: the coupling is a prior with a stated sigma")
         dev = self.cols.device
         s = torch.cuda.current_stream(dev) if stream is None else stream
+        if self.nd is not None:
+            with torch.cuda.device(dev):
+                _lib.check(self.lib.crt_hip_lm_chain_covariance_f64(ctypes.byref(self._chain), self.npar, self.A.data_ptr(), self.cov.data_ptr(),
+                                                                    s.cuda_stream), "crt_hip_lm_chain_covariance_f64")
+            return self.cov.reshape(self.npix, self.nd, self.npar, self.npar).clone()
         with torch.cuda.device(dev):
             _lib.check(self.lib.crt_hip_lm_covariance_f64(self.p.shape[0], self.npar, self.A.data_ptr(), self.cov.data_ptr(), s.cuda_stream),
                        "crt_hip_lm_covariance_f64")
@@ -2416,21 +2470,32 @@ class RetrievalPlan(_LmPlan):
     ``>= 0``; ``p0`` is required; ``bands.leaf_r / leaf_t`` are not used.  The plan owns per-column direction arrays of ``nm + ns`` rows
     (``3 x ncol x (nm + ns) x nb x 8`` bytes), and :meth:`step` is one launch more: ``k_retrieve_apply`` with the leaf directions left out,
     then ``crt_hip_plate_leaf_f64`` on the same parameter array, which writes the working leaf spectra and the model's partials into
-    the leaf rows, then the launches above."""
+    the leaf rows, then the launches above.
+
+    ``chain=nd`` with ``inv_sigma_chain`` ``(nd - 1, npar)`` or ``(npix, nd - 1, npar)``: a time series (include_chain/
+    crt1d_hip_lm_chain.h).  The ``ncol = npix * nd`` columns are (pixel, date) pairs, pixel-major; ``cols``, ``bands``, ``y``, ``sun``,
+    ``leaf_model`` and ``p0`` keep their per-column meaning, so every date has its own ``psi`` and illumination; the parameter vectors of
+    consecutive dates of a pixel are coupled by a random-walk prior with the weights ``inv_sigma_chain`` (``(p_{d+1} - p_d) *
+    inv_sigma_chain[d]`` is a residual; 0: not coupled; fold the time gap in).  A date whose rows are all masked gets its value from
+    its neighbours.  The last launch of :meth:`step` becomes two: ``k_lm_normal`` writes the sums ``k_lm_step`` would have formed,
+    ``k_lm_step_chain`` accepts or rejects, damps and solves the block-tridiagonal system of every pixel.  ``result()`` then gives
+    ``p (npix, nd, npar)`` and per-pixel ``cost``, ``status``, ``lam`` and counters, ``covariance()`` the smoothed marginal covariances
+    ``(npix, nd, npar, npar)``.  ``chain=None``: the plan as it always was, call for call."""
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, y, *, keys, sun=None, d_leaf_r=None, d_leaf_t=None,
                  d_soil_r=None, lai=True, leaf=False, p0=None, lo=None, hi=None, inv_sigma=None, prior=None, inv_sigma_prior=None,
-                 leaf_model=None, mu_s=0.501, tau_d_method="quad", **options):
+                 leaf_model=None, chain=None, inv_sigma_chain=None, mu_s=0.501, tau_d_method="quad", **options):
         static = self._static(scheme, cols, bands, levels, sensors, y, keys=keys, sun=sun, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t,
                               d_soil_r=d_soil_r, lai=lai, leaf=leaf, p0=p0, lo=lo, hi=hi, inv_sigma=inv_sigma, prior=prior,
-                              inv_sigma_prior=inv_sigma_prior, leaf_model=leaf_model, tau_d_method=tau_d_method, **options)
-        self._construct(*static, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, sensors=sensors, y=y,
-                        inv_sigma=inv_sigma, mu_s=mu_s, tau_d_method=tau_d_method)
+                              inv_sigma_prior=inv_sigma_prior, leaf_model=leaf_model, chain=chain, inv_sigma_chain=inv_sigma_chain,
+                              tau_d_method=tau_d_method, **options)
+        self._construct(*static, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, chain=chain,
+                        inv_sigma_chain=inv_sigma_chain, sensors=sensors, y=y, inv_sigma=inv_sigma, mu_s=mu_s, tau_d_method=tau_d_method)
 
     @classmethod
     def _static(cls, scheme, cols, bands, levels, sensors, y, *, keys, sun=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True,
-                leaf=False, p0=None, lo=None, hi=None, inv_sigma=None, prior=None, inv_sigma_prior=None, leaf_model=None, mu_s=0.501,
-                tau_d_method="quad", **options):
+                leaf=False, p0=None, lo=None, hi=None, inv_sigma=None, prior=None, inv_sigma_prior=None, leaf_model=None, chain=None,
+                inv_sigma_chain=None, mu_s=0.501, tau_d_method="quad", **options):
         """The constructor's arguments -> (keys, the parameter axis, the LM options): every check that needs neither a column nor a
         device."""
         _SolvePlan._check_options(_SolvePlan, scheme, tau_d_method)
@@ -2448,6 +2513,7 @@ class RetrievalPlan(_LmPlan):
         _check_start(leaf_model, lo, hi, p0, prior, inv_sigma_prior)
         if isinstance(p0, LutTable):
             _check_lut_start(p0, axis.params, keys, False, y)
+        _check_chain(chain, inv_sigma_chain, cols, axis.npar)
         return keys, axis, o
 
     def _inner(self, scheme, levels, sun, sensors, y, inv_sigma, keys, mu_s, tau_d_method, **axis):
@@ -2481,6 +2547,11 @@ class RetrievalPlan(_LmPlan):
             self._evaluate(self._ap, s)
             self.jac(s)
             self.fwd(s, flags=self._fwd_flags)
+            if self.nd is not None:  # the last launch replaced by two: the sums of k_lm_step written out, then the step of every pixel
+                _lib.check(self.lib.crt_hip_lm_normal_f64(self.p.shape[0], self.npar, self._obs, len(self.keys), *[v.data_ptr() for v in self.sums],
+                                                          s.cuda_stream), "crt_hip_lm_normal_f64")
+                self._step_chain(s)
+                return self
             _lib.check(self.lib.crt_hip_lm_step_f64(ctypes.byref(self._prob), self._obs, len(self.keys), ctypes.byref(self._state), s.cuda_stream),
                        "crt_hip_lm_step_f64")
         return self
@@ -2704,21 +2775,25 @@ class SpectralRetrievalPlan(_LmPlan):
 
     ``leaf_model``: as for :class:`RetrievalPlan` -- the parameters of a :class:`crt1d_amd.leaf_model.PlateLeafModel`, then the soil
     directions, ``"lai"``, ``"leaf"``; one launch more per :meth:`step` (and per :meth:`fitted`), ``crt_hip_plate_leaf_f64`` behind
-    ``k_retrieve_apply``, with or without ``sun``."""
+    ``k_retrieve_apply``, with or without ``sun``.
+
+    ``chain=nd``, ``inv_sigma_chain``: as for :class:`RetrievalPlan` -- the columns are (pixel, date) pairs and the closing call is
+    ``crt_hip_lm_step_chain_f64`` on the block the normal plan wrote."""
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None,
-                 lai=True, leaf=False, p0=None, lo=None, hi=None, prior=None, inv_sigma_prior=None, sun=None, leaf_model=None, mu_s=0.501,
-                 tau_d_method="quad", **options):
+                 lai=True, leaf=False, p0=None, lo=None, hi=None, prior=None, inv_sigma_prior=None, sun=None, leaf_model=None, chain=None,
+                 inv_sigma_chain=None, mu_s=0.501, tau_d_method="quad", **options):
         keys, axis, o, levels = self._static(scheme, cols, bands, levels, y, keys=keys, inv_sigma=inv_sigma, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t,
                                              d_soil_r=d_soil_r, lai=lai, leaf=leaf, p0=p0, lo=lo, hi=hi, prior=prior,
-                                             inv_sigma_prior=inv_sigma_prior, sun=sun, leaf_model=leaf_model, tau_d_method=tau_d_method, **options)
-        self._construct(keys, axis, o, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, y=y, inv_sigma=inv_sigma,
-                        mu_s=mu_s, tau_d_method=tau_d_method)
+                                             inv_sigma_prior=inv_sigma_prior, sun=sun, leaf_model=leaf_model, chain=chain,
+                                             inv_sigma_chain=inv_sigma_chain, tau_d_method=tau_d_method, **options)
+        self._construct(keys, axis, o, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, chain=chain,
+                        inv_sigma_chain=inv_sigma_chain, y=y, inv_sigma=inv_sigma, mu_s=mu_s, tau_d_method=tau_d_method)
 
     @classmethod
     def _static(cls, scheme, cols, bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, leaf=False,
-                p0=None, lo=None, hi=None, prior=None, inv_sigma_prior=None, sun=None, leaf_model=None, mu_s=0.501, tau_d_method="quad",
-                **options):
+                p0=None, lo=None, hi=None, prior=None, inv_sigma_prior=None, sun=None, leaf_model=None, chain=None, inv_sigma_chain=None,
+                mu_s=0.501, tau_d_method="quad", **options):
         """The constructor's arguments -> (keys in ``LEVEL_KEYS`` order, the parameter axis, the LM options, the normalized levels): every
         check that needs no device."""
         keys, axis = _spectral_static(scheme, y, keys, inv_sigma, tau_d_method, bands, sun, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t,
@@ -2727,7 +2802,11 @@ class SpectralRetrievalPlan(_LmPlan):
         _check_start(leaf_model, lo, hi, p0, prior, inv_sigma_prior)
         if isinstance(p0, LutTable):
             _check_lut_start(p0, axis.params, keys, True, y)
-        return keys, axis, o, _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), axis.npar, sun)
+        levels = _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), axis.npar, sun)
+        _check_chain(chain, inv_sigma_chain, cols, axis.npar)
+        return keys, axis, o, levels
+
+    _owns_sums = False  # (the normal plan's A, g and c2 are the block)
 
     def _inner(self, scheme, levels, sun, y, **kw):
         """The normal plan on the working tensors, which holds the observations (``fwd`` kept for :meth:`fitted`, not written by a step)."""
@@ -2746,6 +2825,9 @@ class SpectralRetrievalPlan(_LmPlan):
         with torch.cuda.device(dev):
             self._evaluate(self._ap, s)
             self.normal(s)
+            if self.nd is not None:  # the step of every pixel on the block the normal plan wrote
+                self._step_chain(s)
+                return self
             _lib.check(self.lib.crt_hip_lm_step_normal_f64(ctypes.byref(self._prob), self._blk, 1, ctypes.byref(self._state), s.cuda_stream),
                        "crt_hip_lm_step_normal_f64")
         return self

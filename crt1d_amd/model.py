@@ -515,6 +515,53 @@ class Model:
         out["params"] = res["params"]
         return out
 
+    def retrieve_chain(self, weights, y, psi, inv_sigma_chain, levels=(0, -1), directions=None, lai=True, wrt_leaf=None, niter=20,
+                       **lm_options):
+        """:meth:`retrieve` of this one canopy observed on ``nd`` dates, the dates coupled by a random-walk prior
+        (:class:`crt1d_amd.batched.RetrievalPlan` with ``chain=nd``: one pixel, the column replicated ``nd`` times).  ``psi (nd,)``: the sun
+        angle of every date; ``y``: ``{key: (nd, nsel, nsens)}``; ``inv_sigma_chain (nd - 1, npar)``: the coupling weights of the gaps
+        between consecutive dates (0: not coupled; the time gap folded in).  ``lm_options``: ``p0``, ``prior``, ``inv_sigma_prior`` (each
+        ``(nd, npar)`` or ``(npar,)``), ``lo``, ``hi`` ``(npar,)``, ``inv_sigma`` (as ``y``; a fully masked date is a cloudy one),
+        ``I_dr0_all`` / ``I_df0_all`` ``(n_wl,)`` or ``(nd, n_wl)`` and the options of the plan.  Returns NumPy arrays ``p (nd, npar)``, the
+        pixel's ``cost``, ``status``, ``lam``, ``naccept``, ``nreject``, the smoothed marginal covariances ``cov (nd, npar, npar)`` and
+        ``"params"``.  The model's own state is not changed."""
+        from . import batched
+
+        psi = np.atleast_1d(np.asarray(psi, dtype=np.float64))
+        if psi.ndim != 1 or psi.size < 1:
+            raise ValueError("`psi` must be a non-empty 1-D series of solar zenith angles, one per date")
+        nd = psi.size
+        directions = {} if directions is None else dict(directions)
+        if any(k not in batched.JAC_PARAMS for k in directions):
+            raise ValueError(f"directions must be a dict of (ntan, n_wl) arrays under keys out of {batched.JAC_PARAMS}")
+        if wrt_leaf not in (None, "param"):
+            raise ValueError(f"wrt_leaf must be None or 'param', got {wrt_leaf!r}")
+        d = {"d_" + k: np.ascontiguousarray(v, dtype=np.float64) for k, v in directions.items()}
+        for k, v in y.items():
+            if np.ndim(v) != 3 or np.shape(v)[0] != nd:
+                raise ValueError(f"y[{k!r}] must be (nd, nsel, nsens) with nd = {nd} dates, got {np.shape(v)}")
+        npar = batched._ParamAxis(d.get("d_leaf_r"), d.get("d_leaf_t"), d.get("d_soil_r"), lai, wrt_leaf is not None,
+                                  lm_options.get("leaf_model")).npar
+        batched._check_chain(nd, inv_sigma_chain, nd, npar)  # (before any device is touched)
+        if np.ndim(inv_sigma_chain) != 2:
+            raise ValueError(f"inv_sigma_chain must be (nd - 1, npar) = {(nd - 1, npar)} for the model's one pixel")
+        spectra = [lm_options.pop(k, None) for k in ("I_dr0_all", "I_df0_all")]
+        scheme, cols, b, sun = self._series_inputs(psi, *spectra, "retrieval")
+        rep = lambda v: None if v is None else v.expand(nd, *v.shape[1:]).contiguous()  # noqa: E731  (the one column on every date)
+        cols = batched.Columns(psi=sun.psi[0].contiguous(), lai=rep(cols.lai), g_kind=rep(cols.g_kind), g_param=rep(cols.g_param),
+                               mla=rep(cols.mla), g_at_psi=None if sun.g_at_psi is None else sun.g_at_psi[0].contiguous(),
+                               g_table=rep(cols.g_table))
+        b = batched.Bands(sun.I_dr0[0].contiguous(), sun.I_df0[0].contiguous(), rep(b.leaf_r), rep(b.leaf_t), rep(b.soil_r))
+        keys = tuple(k for k in batched.LEVEL_KEYS if k in y)
+        f64 = lambda v: {k: np.asarray(a, dtype=np.float64) for k, a in v.items()}  # noqa: E731
+        if lm_options.get("inv_sigma") is not None:
+            lm_options["inv_sigma"] = f64(lm_options["inv_sigma"])
+        res = batched.retrieve(scheme, cols, b, levels, self._sensor_set(weights, self.nwl), f64(y), keys=keys or tuple(y), niter=niter,
+                               lai=lai, leaf=wrt_leaf is not None, chain=nd, inv_sigma_chain=inv_sigma_chain, **d, **lm_options)
+        out = {k: v[0].cpu().numpy() for k, v in res.items() if k != "params"}
+        out["params"] = res["params"]
+        return out
+
     def retrieve_spectral(self, y, levels=(-1,), directions=None, lai=True, wrt_leaf=None, niter=20, psi=None, I_dr0_all=None,
                           I_df0_all=None, lut=None, posterior=False, **lm_options):
         """:meth:`retrieve` from the level spectra themselves, band by band (:class:`crt1d_amd.batched.SpectralRetrievalPlan`,
