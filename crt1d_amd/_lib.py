@@ -650,6 +650,45 @@ def _chain_signatures():
 _CHAIN_SIGNATURES = _chain_signatures()
 CHAIN_EXPORTS = list(_CHAIN_SIGNATURES)
 
+# the chained step with parameters shared by all dates of a pixel (include_shared/crt1d_hip_lm_shared.h): the step on the arrowhead system
+# and the marginal covariances of (v_d, s); the structs of the chain, a header and a table of their own
+
+
+def lm_shared_lds_bytes(nd, nv, ns):
+    """``CRT_LM_SHARED_LDS_BYTES(nd, nv, ns)``: the dynamic LDS of one pixel of the shared-parameter kernels."""
+    per_date = 2 * nv * nv + 4 * nv + nv * ns if nv else 1
+    return 8 * (nd * per_date + 4 * nv * nv + 64 + 3 * ns * ns + 2 * nv * ns + 4 * ns)
+
+
+def lm_shared_max_nd(npar, ns):
+    """``crt_hip_lm_shared_max_nd``: the largest ``nd`` whose LDS fits the limit; 0 for a refused ``npar`` or ``ns``.  No library is
+    loaded."""
+    if not 1 <= npar <= RETRIEVE_MAX_NPAR or not 0 <= ns <= npar:
+        return 0
+    nv = npar - ns
+    per_date = 2 * nv * nv + 4 * nv + nv * ns if nv else 1
+    return (LM_CHAIN_LDS_LIMIT // 8 - (4 * nv * nv + 64 + 3 * ns * ns + 2 * nv * ns + 4 * ns)) // per_date
+
+
+class CrtLmShared(ctypes.Structure):
+    """``crt_lm_shared``: ``mask``, bit ``k`` set means parameter ``k`` is shared by all dates of a pixel."""
+
+    _fields_ = [("mask", ctypes.c_uint32)]
+
+
+def _shared_signatures():
+    P = ctypes.POINTER
+    i32, ok = ctypes.c_int32, ctypes.c_int
+    return {
+        "crt_hip_lm_step_shared_f64": (ok, [P(CrtLmChain), P(CrtLmShared), P(CrtLmProblem), P(CrtLmNormalBlock), i32, P(CrtLmState), _vp]),
+        "crt_hip_lm_shared_covariance_f64": (ok, [P(CrtLmChain), P(CrtLmShared), i32, _vp, _vp, _vp]),
+        "crt_hip_lm_shared_max_nd": (i32, [i32, i32]),
+    }
+
+
+_SHARED_SIGNATURES = _shared_signatures()
+SHARED_EXPORTS = list(_SHARED_SIGNATURES)
+
 _lib = None
 
 
@@ -676,7 +715,7 @@ def load():
                                       **_DLAI_SIGNATURES, **_DLEAF_SIGNATURES, **_GRAD_SIGNATURES, **_SENSJAC_SIGNATURES,
                                       **_SENSJAC_SERIES_SIGNATURES, **_RETRIEVE_SIGNATURES, **_SPECFIT_SIGNATURES,
                                       **_SPECFIT_SERIES_SIGNATURES, **_LEAFMODEL_SIGNATURES, **_LUT_SIGNATURES, **_LUT_POSTERIOR_SIGNATURES,
-                                      **_CHAIN_SIGNATURES}.items():
+                                      **_CHAIN_SIGNATURES, **_SHARED_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:

@@ -2231,9 +2231,39 @@ def _check_start(leaf_model, lo, hi, p0, prior, inv_sigma_prior):
         raise ValueError("prior and inv_sigma_prior go together")
 
 
-def _check_chain(chain, inv_sigma_chain, ncol, npar):
+def _check_shared(shared, chain, params, p0=None):
+    """``shared=`` of a retrieval plan whose parameter axis is ``params``, as far as no device is needed: a sequence of names out of
+    ``params`` or a boolean mask ``(npar,)``.  -> None (no shared set) or the mask of ``crt_lm_shared`` (bit ``k``: parameter ``k``)"""
+    import numpy as np
+
+    if shared is None:
+        return None
+    if chain is None:
+        raise ValueError("shared needs chain= the number of dates: the parameters are shared by the dates of a pixel")
+    npar = len(params)
+    if isinstance(shared, str):
+        shared = (shared,)
+    items = list(shared.tolist() if isinstance(shared, (np.ndarray, torch.Tensor)) else shared)
+    if all(isinstance(v, str) for v in items):  # (an empty sequence: no name, nothing shared)
+        unknown = [v for v in items if v not in params]
+        if unknown:
+            raise ValueError(f"shared names {unknown} are not among the parameters {tuple(params)}")
+        bits = [n in items for n in params]
+    elif all(isinstance(v, (bool, np.bool_)) for v in items):
+        if len(items) != npar:
+            raise ValueError(f"a shared mask must have one entry for each of the {npar} parameters {tuple(params)}, got {len(items)}")
+        bits = [bool(v) for v in items]
+    else:
+        raise ValueError("shared must be a sequence of parameter names or a boolean mask (npar,)")
+    if isinstance(p0, LutTable):
+        raise ValueError("a look-up-table start (p0= a LutTable) cannot be combined with shared: the dates' best candidates disagree on "
+                         "the shared parameters")
+    return sum(1 << k for k, b in enumerate(bits) if b)
+
+
+def _check_chain(chain, inv_sigma_chain, ncol, npar, shared=None):
     """``chain=nd`` and ``inv_sigma_chain=`` of a retrieval plan with ``ncol`` columns (or: of the :class:`Columns` ``ncol``), as far as no
-    device is needed.  -> None (no chain) or (npix, nd)"""
+    device is needed; ``shared``: the mask :func:`_check_shared` gave, which sets the limit on ``nd``.  -> None (no chain) or (npix, nd)"""
     if chain is None:
         if inv_sigma_chain is not None:
             raise ValueError("inv_sigma_chain needs chain= the number of dates")
@@ -2244,8 +2274,12 @@ def _check_chain(chain, inv_sigma_chain, ncol, npar):
     ncol = ncol if isinstance(ncol, int) else ncol.ncol
     if ncol % nd:
         raise ValueError(f"chain = {nd} dates does not divide ncol = {ncol}: the columns are (pixel, date) pairs, pixel-major")
-    if nd > _lib.lm_chain_max_nd(npar):
+    if shared is None and nd > _lib.lm_chain_max_nd(npar):
         raise ValueError(f"chain = {nd} dates is beyond the {_lib.lm_chain_max_nd(npar)} the chain kernel serves at npar = {npar}")
+    if shared is not None and nd > _lib.lm_shared_max_nd(npar, bin(shared).count("1")):
+        ns = bin(shared).count("1")
+        raise ValueError(f"chain = {nd} dates is beyond the {_lib.lm_shared_max_nd(npar, ns)} the shared-parameter kernel serves at "
+                         f"npar = {npar} with {ns} shared")
     npix = ncol // nd
     if inv_sigma_chain is None:
         raise ValueError("a chain needs inv_sigma_chain (nd - 1, npar) or (npix, nd - 1, npar)")
@@ -2267,7 +2301,7 @@ class _LmPlan:
     _owns_sums = True  # a chained plan allocates its block of per-column sums; False: the subclass's _inner binds ``_blk`` to its own
 
     def _construct(self, keys, axis, o, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, chain=None,
-                   inv_sigma_chain=None, **inner):
+                   inv_sigma_chain=None, shared=None, **inner):
         self.lib = _lib.load()
         self.scheme, self.keys, self.sun, self.options = scheme, keys, sun, o
         ncol, nz, nb, dev = cols.ncol, cols.nz, bands.nb, cols.device
@@ -2300,6 +2334,14 @@ class _LmPlan:
         self.hi = None if hi is None else torch.as_tensor(hi, dtype=torch.float64).to(dev).contiguous()
         self.prior = None if prior is None else _per_col(prior, "prior", ncol, npar, dev)
         self.inv_sigma_prior = None if prior is None else _per_col(inv_sigma_prior, "inv_sigma_prior", ncol, npar, dev)
+        # the parameters all dates of a pixel share: the prior of such a parameter counts once, through date 0's row
+        mask = _check_shared(shared, chain, axis.params, p0)
+        self.shared = None if mask is None else tuple(n for k, n in enumerate(axis.params) if mask >> k & 1)
+        self._shared = None if mask is None else _lib.CrtLmShared(mask)
+        self._shared_idx = None if mask is None else torch.tensor([k for k in range(npar) if mask >> k & 1], dtype=torch.int64, device=dev)
+        if mask is not None and self.inv_sigma_prior is not None and self._shared_idx.numel():
+            self.inv_sigma_prior = self.inv_sigma_prior.clone()
+            self.inv_sigma_prior.view(-1, int(chain), npar)[:, 1:, self._shared_idx] = 0.0
         table = p0 if isinstance(p0, LutTable) else None
         if table is not None:  # a column without an eligible candidate gets table.p_default, else the default start (a leaf model has none: q[0])
             if table.q.device != dev:
@@ -2360,7 +2402,12 @@ class _LmPlan:
                        "crt_hip_g_dparam_series_f64")
 
     def _step_chain(self, s):
-        """The closing call of a chained ``step()``: ``k_lm_step_chain`` on the plan's one block of sums."""
+        """The closing call of a chained ``step()``: ``k_lm_step_chain`` (with ``shared``: ``k_lm_step_shared``) on the plan's one block of
+        sums."""
+        if self._shared is not None:
+            _lib.check(self.lib.crt_hip_lm_step_shared_f64(ctypes.byref(self._chain), ctypes.byref(self._shared), ctypes.byref(self._prob),
+                                                           self._blk, 1, ctypes.byref(self._state), s.cuda_stream), "crt_hip_lm_step_shared_f64")
+            return
         _lib.check(self.lib.crt_hip_lm_step_chain_f64(ctypes.byref(self._chain), ctypes.byref(self._prob), self._blk, 1, ctypes.byref(self._state),
                                                       s.cuda_stream), "crt_hip_lm_step_chain_f64")
 
@@ -2373,6 +2420,9 @@ class _LmPlan:
             self._p0.copy_(v.expand_as(self._p0))
         elif self.lut is not None:
             self._p0.copy_(self.lut()["p"])
+        if self._shared is not None and self._shared_idx.numel():  # a shared parameter starts at date 0's value on every date
+            v = self._p0.view(self.npix, self.nd, self.npar)
+            v[:, 1:, self._shared_idx] = v[:, :1, self._shared_idx]
         self.p.copy_(self._p0)
         self.p_trial.copy_(self._p0)
         self.cost.fill_(float("inf"))
@@ -2422,11 +2472,19 @@ class _LmPlan:
         (``crt_hip_lm_covariance_f64``); a dead parameter has variance ``+inf`` and zero covariances.  ``scale=True`` multiplies by the
         reduced chi-square ``2 cost / (nobs - npar)`` (for observations without error estimates).  With a chain: ``(npix, nd, npar,
         npar)``, the smoothed marginal covariance of every date (``crt_hip_lm_chain_covariance_f64``: the diagonal blocks of the inverse
-        of the pixel's block-tridiagonal matrix); ``scale=True`` is a ValueError then -- the coupling is a prior with a stated sigma."""
+        of the pixel's block-tridiagonal matrix); ``scale=True`` is a ValueError then -- the coupling is a prior with a stated sigma.
+        With ``shared``: ``crt_hip_lm_shared_covariance_f64``, for every date the marginal covariance of its varying parameters and the
+        shared ones in the plan's parameter order; the shared-shared block has the same bits on every date."""
         if self.nd is not None and scale:
             raise ValueError("covariance(scale=True) has no meaning with a chain: the coupling is a prior with a stated sigma")
         dev = self.cols.device
         s = torch.cuda.current_stream(dev) if stream is None else stream
+        if self.nd is not None and self._shared is not None:
+            with torch.cuda.device(dev):
+                _lib.check(self.lib.crt_hip_lm_shared_covariance_f64(ctypes.byref(self._chain), ctypes.byref(self._shared), self.npar,
+                                                                     self.A.data_ptr(), self.cov.data_ptr(), s.cuda_stream),
+                           "crt_hip_lm_shared_covariance_f64")
+            return self.cov.reshape(self.npix, self.nd, self.npar, self.npar).clone()
         if self.nd is not None:
             with torch.cuda.device(dev):
                 _lib.check(self.lib.crt_hip_lm_chain_covariance_f64(ctypes.byref(self._chain), self.npar, self.A.data_ptr(), self.cov.data_ptr(),
@@ -2480,22 +2538,32 @@ class RetrievalPlan(_LmPlan):
     its neighbours.  The last launch of :meth:`step` becomes two: ``k_lm_normal`` writes the sums ``k_lm_step`` would have formed,
     ``k_lm_step_chain`` accepts or rejects, damps and solves the block-tridiagonal system of every pixel.  ``result()`` then gives
     ``p (npix, nd, npar)`` and per-pixel ``cost``, ``status``, ``lam`` and counters, ``covariance()`` the smoothed marginal covariances
-    ``(npix, nd, npar, npar)``.  ``chain=None``: the plan as it always was, call for call."""
+    ``(npix, nd, npar, npar)``.  ``chain=None``: the plan as it always was, call for call.
+
+    ``shared=`` (needs ``chain=``): the parameters that are constants of a pixel over its ``nd`` dates -- a sequence of names out of
+    ``plan.params`` (``"lai"``, ``"leaf"``, ``"dir0"``.. or leaf-model names) or a boolean mask ``(npar,)`` (include_shared/
+    crt1d_hip_lm_shared.h).  Such a parameter is ONE unknown of the pixel: the system has ``nd * nv + ns`` unknowns, the block-tridiagonal
+    matrix bordered by ``ns`` dense rows, and the closing launch is ``k_lm_step_shared`` in place of ``k_lm_step_chain`` (the number of
+    launches is unchanged).  ``result()["p"]`` stays ``(npix, nd, npar)`` with the shared columns bitwise equal over the dates;
+    ``inv_sigma_chain`` keeps its shape, its entries of shared parameters are not read.  ``p0`` / ``reset(p0)``: the shared entries of
+    the dates after the first are overwritten with date 0's.  ``prior`` / ``inv_sigma_prior``: for a shared parameter the plan keeps date
+    0's row and zeroes ``inv_sigma_prior`` on the other dates, so that the prior counts once.  ``p0=`` a :class:`LutTable` together with
+    ``shared`` is a ValueError.  ``shared=None``: the chained plan, call for call."""
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, y, *, keys, sun=None, d_leaf_r=None, d_leaf_t=None,
                  d_soil_r=None, lai=True, leaf=False, p0=None, lo=None, hi=None, inv_sigma=None, prior=None, inv_sigma_prior=None,
-                 leaf_model=None, chain=None, inv_sigma_chain=None, mu_s=0.501, tau_d_method="quad", **options):
+                 leaf_model=None, chain=None, inv_sigma_chain=None, shared=None, mu_s=0.501, tau_d_method="quad", **options):
         static = self._static(scheme, cols, bands, levels, sensors, y, keys=keys, sun=sun, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t,
                               d_soil_r=d_soil_r, lai=lai, leaf=leaf, p0=p0, lo=lo, hi=hi, inv_sigma=inv_sigma, prior=prior,
                               inv_sigma_prior=inv_sigma_prior, leaf_model=leaf_model, chain=chain, inv_sigma_chain=inv_sigma_chain,
-                              tau_d_method=tau_d_method, **options)
+                              shared=shared, tau_d_method=tau_d_method, **options)
         self._construct(*static, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, chain=chain,
-                        inv_sigma_chain=inv_sigma_chain, sensors=sensors, y=y, inv_sigma=inv_sigma, mu_s=mu_s, tau_d_method=tau_d_method)
+                        inv_sigma_chain=inv_sigma_chain, shared=shared, sensors=sensors, y=y, inv_sigma=inv_sigma, mu_s=mu_s, tau_d_method=tau_d_method)
 
     @classmethod
     def _static(cls, scheme, cols, bands, levels, sensors, y, *, keys, sun=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True,
                 leaf=False, p0=None, lo=None, hi=None, inv_sigma=None, prior=None, inv_sigma_prior=None, leaf_model=None, chain=None,
-                inv_sigma_chain=None, mu_s=0.501, tau_d_method="quad", **options):
+                inv_sigma_chain=None, shared=None, mu_s=0.501, tau_d_method="quad", **options):
         """The constructor's arguments -> (keys, the parameter axis, the LM options): every check that needs neither a column nor a
         device."""
         _SolvePlan._check_options(_SolvePlan, scheme, tau_d_method)
@@ -2513,7 +2581,7 @@ class RetrievalPlan(_LmPlan):
         _check_start(leaf_model, lo, hi, p0, prior, inv_sigma_prior)
         if isinstance(p0, LutTable):
             _check_lut_start(p0, axis.params, keys, False, y)
-        _check_chain(chain, inv_sigma_chain, cols, axis.npar)
+        _check_chain(chain, inv_sigma_chain, cols, axis.npar, _check_shared(shared, chain, axis.params, p0))
         return keys, axis, o
 
     def _inner(self, scheme, levels, sun, sensors, y, inv_sigma, keys, mu_s, tau_d_method, **axis):
@@ -2778,22 +2846,23 @@ class SpectralRetrievalPlan(_LmPlan):
     ``k_retrieve_apply``, with or without ``sun``.
 
     ``chain=nd``, ``inv_sigma_chain``: as for :class:`RetrievalPlan` -- the columns are (pixel, date) pairs and the closing call is
-    ``crt_hip_lm_step_chain_f64`` on the block the normal plan wrote."""
+    ``crt_hip_lm_step_chain_f64`` on the block the normal plan wrote.  ``shared=``: as for :class:`RetrievalPlan` -- the closing call is
+    ``crt_hip_lm_step_shared_f64``."""
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None,
                  lai=True, leaf=False, p0=None, lo=None, hi=None, prior=None, inv_sigma_prior=None, sun=None, leaf_model=None, chain=None,
-                 inv_sigma_chain=None, mu_s=0.501, tau_d_method="quad", **options):
+                 inv_sigma_chain=None, shared=None, mu_s=0.501, tau_d_method="quad", **options):
         keys, axis, o, levels = self._static(scheme, cols, bands, levels, y, keys=keys, inv_sigma=inv_sigma, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t,
                                              d_soil_r=d_soil_r, lai=lai, leaf=leaf, p0=p0, lo=lo, hi=hi, prior=prior,
                                              inv_sigma_prior=inv_sigma_prior, sun=sun, leaf_model=leaf_model, chain=chain,
-                                             inv_sigma_chain=inv_sigma_chain, tau_d_method=tau_d_method, **options)
+                                             inv_sigma_chain=inv_sigma_chain, shared=shared, tau_d_method=tau_d_method, **options)
         self._construct(keys, axis, o, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, chain=chain,
-                        inv_sigma_chain=inv_sigma_chain, y=y, inv_sigma=inv_sigma, mu_s=mu_s, tau_d_method=tau_d_method)
+                        inv_sigma_chain=inv_sigma_chain, shared=shared, y=y, inv_sigma=inv_sigma, mu_s=mu_s, tau_d_method=tau_d_method)
 
     @classmethod
     def _static(cls, scheme, cols, bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, leaf=False,
                 p0=None, lo=None, hi=None, prior=None, inv_sigma_prior=None, sun=None, leaf_model=None, chain=None, inv_sigma_chain=None,
-                mu_s=0.501, tau_d_method="quad", **options):
+                shared=None, mu_s=0.501, tau_d_method="quad", **options):
         """The constructor's arguments -> (keys in ``LEVEL_KEYS`` order, the parameter axis, the LM options, the normalized levels): every
         check that needs no device."""
         keys, axis = _spectral_static(scheme, y, keys, inv_sigma, tau_d_method, bands, sun, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t,
@@ -2803,7 +2872,7 @@ class SpectralRetrievalPlan(_LmPlan):
         if isinstance(p0, LutTable):
             _check_lut_start(p0, axis.params, keys, True, y)
         levels = _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), axis.npar, sun)
-        _check_chain(chain, inv_sigma_chain, cols, axis.npar)
+        _check_chain(chain, inv_sigma_chain, cols, axis.npar, _check_shared(shared, chain, axis.params, p0))
         return keys, axis, o, levels
 
     _owns_sums = False  # (the normal plan's A, g and c2 are the block)

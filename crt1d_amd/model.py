@@ -516,7 +516,7 @@ class Model:
         return out
 
     def retrieve_chain(self, weights, y, psi, inv_sigma_chain, levels=(0, -1), directions=None, lai=True, wrt_leaf=None, niter=20,
-                       **lm_options):
+                       shared=None, **lm_options):
         """:meth:`retrieve` of this one canopy observed on ``nd`` dates, the dates coupled by a random-walk prior
         (:class:`crt1d_amd.batched.RetrievalPlan` with ``chain=nd``: one pixel, the column replicated ``nd`` times).  ``psi (nd,)``: the sun
         angle of every date; ``y``: ``{key: (nd, nsel, nsens)}``; ``inv_sigma_chain (nd - 1, npar)``: the coupling weights of the gaps
@@ -524,7 +524,8 @@ class Model:
         ``(nd, npar)`` or ``(npar,)``), ``lo``, ``hi`` ``(npar,)``, ``inv_sigma`` (as ``y``; a fully masked date is a cloudy one),
         ``I_dr0_all`` / ``I_df0_all`` ``(n_wl,)`` or ``(nd, n_wl)`` and the options of the plan.  Returns NumPy arrays ``p (nd, npar)``, the
         pixel's ``cost``, ``status``, ``lam``, ``naccept``, ``nreject``, the smoothed marginal covariances ``cov (nd, npar, npar)`` and
-        ``"params"``.  The model's own state is not changed."""
+        ``"params"``.  ``shared``: the parameters that are constants of the canopy over the dates, names out of ``"params"`` or a boolean mask
+        (``shared=`` of the plan): one unknown each instead of one per date.  The model's own state is not changed."""
         from . import batched
 
         psi = np.atleast_1d(np.asarray(psi, dtype=np.float64))
@@ -540,9 +541,11 @@ class Model:
         for k, v in y.items():
             if np.ndim(v) != 3 or np.shape(v)[0] != nd:
                 raise ValueError(f"y[{k!r}] must be (nd, nsel, nsens) with nd = {nd} dates, got {np.shape(v)}")
-        npar = batched._ParamAxis(d.get("d_leaf_r"), d.get("d_leaf_t"), d.get("d_soil_r"), lai, wrt_leaf is not None,
-                                  lm_options.get("leaf_model")).npar
-        batched._check_chain(nd, inv_sigma_chain, nd, npar)  # (before any device is touched)
+        axis = batched._ParamAxis(d.get("d_leaf_r"), d.get("d_leaf_t"), d.get("d_soil_r"), lai, wrt_leaf is not None,
+                                  lm_options.get("leaf_model"))
+        npar = axis.npar
+        mask = batched._check_shared(shared, nd, axis.params, lm_options.get("p0"))
+        batched._check_chain(nd, inv_sigma_chain, nd, npar, mask)  # (before any device is touched)
         if np.ndim(inv_sigma_chain) != 2:
             raise ValueError(f"inv_sigma_chain must be (nd - 1, npar) = {(nd - 1, npar)} for the model's one pixel")
         spectra = [lm_options.pop(k, None) for k in ("I_dr0_all", "I_df0_all")]
@@ -557,7 +560,8 @@ class Model:
         if lm_options.get("inv_sigma") is not None:
             lm_options["inv_sigma"] = f64(lm_options["inv_sigma"])
         res = batched.retrieve(scheme, cols, b, levels, self._sensor_set(weights, self.nwl), f64(y), keys=keys or tuple(y), niter=niter,
-                               lai=lai, leaf=wrt_leaf is not None, chain=nd, inv_sigma_chain=inv_sigma_chain, **d, **lm_options)
+                               lai=lai, leaf=wrt_leaf is not None, chain=nd, inv_sigma_chain=inv_sigma_chain,
+                               **({} if shared is None else {"shared": shared}), **d, **lm_options)
         out = {k: v[0].cpu().numpy() for k, v in res.items() if k != "params"}
         out["params"] = res["params"]
         return out
