@@ -689,6 +689,34 @@ def _shared_signatures():
 _SHARED_SIGNATURES = _shared_signatures()
 SHARED_EXPORTS = list(_SHARED_SIGNATURES)
 
+# the entries a Levenberg-Marquardt loop evaluates its columns with, behind a per-column skip flag, and the decision that lets the Jacobian
+# run only where the trial point will be accepted (include_mask/crt1d_hip_masked.h); again a header and a table of their own
+
+
+class CrtColMask(ctypes.Structure):
+    """``crt_col_mask``: ``skip`` int32 ``[ncol / unit]`` on the device, column ``c`` is skipped iff ``skip[c // unit] != 0``."""
+
+    _fields_ = [("skip", _vp), ("unit", ctypes.c_int32)]
+
+
+def _masked_signatures():
+    P = ctypes.POINTER
+    i32, ok, M = ctypes.c_int32, ctypes.c_int, P(CrtColMask)
+    sib = lambda table, name: table[name][1]  # noqa: E731  (the sibling's arguments, then the mask)
+    return {
+        "crt_hip_sensor_jac_masked_f64": (ok, sib(_SENSJAC_SIGNATURES, "crt_hip_sensor_jac_f64") + [M]),
+        "crt_hip_sensor_jac_series_masked_f64": (ok, sib(_SENSJAC_SERIES_SIGNATURES, "crt_hip_sensor_jac_series_f64") + [M]),
+        "crt_hip_sensor_levels_masked_f64": (ok, sib(_SENSOR_SIGNATURES, "crt_hip_sensor_levels_f64") + [M]),
+        "crt_hip_sensor_levels_series_masked_f64": (ok, sib(_SENSOR_SIGNATURES, "crt_hip_sensor_levels_series_f64") + [M]),
+        "crt_hip_spectral_normal_masked_f64": (ok, sib(_SPECFIT_SIGNATURES, "crt_hip_spectral_normal_f64") + [M]),
+        "crt_hip_spectral_normal_series_masked_f64": (ok, sib(_SPECFIT_SERIES_SIGNATURES, "crt_hip_spectral_normal_series_f64") + [M]),
+        "crt_hip_lm_decide_f64": (ok, [P(CrtLmProblem), P(CrtLmObs), i32, P(CrtLmState), _vp, _vp, _vp]),
+    }
+
+
+_MASKED_SIGNATURES = _masked_signatures()
+MASKED_EXPORTS = list(_MASKED_SIGNATURES)
+
 _lib = None
 
 
@@ -715,7 +743,7 @@ def load():
                                       **_DLAI_SIGNATURES, **_DLEAF_SIGNATURES, **_GRAD_SIGNATURES, **_SENSJAC_SIGNATURES,
                                       **_SENSJAC_SERIES_SIGNATURES, **_RETRIEVE_SIGNATURES, **_SPECFIT_SIGNATURES,
                                       **_SPECFIT_SERIES_SIGNATURES, **_LEAFMODEL_SIGNATURES, **_LUT_SIGNATURES, **_LUT_POSTERIOR_SIGNATURES,
-                                      **_CHAIN_SIGNATURES, **_SHARED_SIGNATURES}.items():
+                                      **_CHAIN_SIGNATURES, **_SHARED_SIGNATURES, **_MASKED_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:

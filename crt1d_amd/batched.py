@@ -514,6 +514,32 @@ def alloc_outputs(scheme, ncol, nz, nb, device, dtype=torch.float64, placed=Fals
         return {k: torch.empty(s, dtype=dtype, device=device) for k, s in shapes.items()}
 
 
+MASKED_SCHEMES = ("2s", "bl", "g77", "bf")  # the schemes of include_mask/crt1d_hip_masked.h
+
+
+def _check_skip(skip, skip_unit, ncol, scheme, bands):
+    """The checks of ``skip=`` / ``skip_unit=`` that touch no device (``ncol``: the number of columns, or ``None`` where it is not known
+    yet)."""
+    if isinstance(skip_unit, bool) or not isinstance(skip_unit, int) or skip_unit < 1:
+        raise ValueError(f"skip_unit must be an integer >= 1, got {skip_unit!r}")
+    if skip is None:
+        if skip_unit != 1:
+            raise ValueError("skip_unit needs skip=")
+        return
+    if scheme not in MASKED_SCHEMES:
+        raise ValueError(f"scheme {scheme!r} has no masked kernels (skip=); served: " + ", ".join(MASKED_SCHEMES))
+    if bands.dtype != torch.float64:
+        raise ValueError("skip= needs float64 bands: the masked entries have no f32 storage form")
+    if not isinstance(skip, torch.Tensor) or skip.dtype != torch.int32:
+        raise ValueError("skip must be an int32 torch tensor on the columns' device")
+    if ncol is None:
+        return
+    if ncol % skip_unit:
+        raise ValueError(f"skip_unit = {skip_unit} does not divide ncol = {ncol}")
+    if tuple(skip.shape) != (ncol // skip_unit,) or not skip.is_contiguous():
+        raise ValueError(f"skip must be a contiguous ({ncol // skip_unit},) tensor (ncol // skip_unit), got {tuple(skip.shape)}")
+
+
 class _SolvePlan:
     """What the solve plans share: the checks of scheme, method, geometry and spectra, the argument structs of the C entry, the
     workspace, and the call.  A subclass's ``__init__`` runs ``_check_options`` (and its own checks that need no column) first, then
@@ -524,6 +550,22 @@ class _SolvePlan:
     _scheme_arg = True  # the entry takes the scheme id first (Plan's per-scheme entries do not)
     _f32_series = False  # a sun series with float32 spectra is served (LevelsSeriesPlan)
     _s = None  # crt_sun_series of the series plans
+    _mask = None  # crt_col_mask of a plan made with ``skip=`` (the six maskable plans)
+    skip, skip_unit = None, 1
+    use_skip = True  # False: the next calls evaluate every column through the plain entry (the mask stays bound)
+
+    def _bind_skip(self, skip, skip_unit, entry):
+        """``skip=`` / ``skip_unit=`` of the maskable plans, after ``_bind``: the device check, the struct and the masked entry
+        ``entry`` (include_mask/crt1d_hip_masked.h).  The flags are read on the device at every call."""
+        _check_skip(skip, skip_unit, self.cols.ncol, self.scheme, self.bands)
+        if skip is None:
+            return
+        if skip.device != self.cols.device:
+            raise ValueError(f"skip lives on {skip.device} but the columns on {self.cols.device}")
+        self.skip, self.skip_unit = skip, int(skip_unit)
+        self._mask = _lib.CrtColMask(skip.data_ptr(), int(skip_unit))
+        self._entry_masked = entry
+        self._fn_masked = getattr(self.lib, entry)
 
     def _check_options(self, scheme, tau_d_method):
         if scheme not in _lib.SCHEME_IDS:
@@ -577,9 +619,11 @@ class _SolvePlan:
         head = (c, b, o) if self._s is None else (c, b, ctypes.byref(self._s), o)
         if self._scheme_arg:
             head = (_lib.SCHEME_IDS[self.scheme],) + head
+        masked = self._mask is not None and self.use_skip
+        fn, entry, mask = (self._fn_masked, self._entry_masked, (ctypes.byref(self._mask),)) if masked else (self._fn, self._entry, ())
         with torch.cuda.device(dev):  # the launch goes to the CURRENT device: make it the one the buffers live on
-            st = self._fn(*head, *self._tail(), self.workspace.data_ptr(), self._wsb, s.cuda_stream)
-        _lib.check(st, self._entry)
+            st = fn(*head, *self._tail(), self.workspace.data_ptr(), self._wsb, s.cuda_stream, *mask)
+        _lib.check(st, entry)
         return self.out
 
 
@@ -1229,11 +1273,13 @@ class SensorLevelsPlan(_SolvePlan):
     sums are bitwise the same alone or in any batch."""
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, *, keys=LEVEL_KEYS, mu_s=0.501, tau_d_method="quad",
-                 out=None, workspace=None):
+                 out=None, workspace=None, skip=None, skip_unit=1):
         self._check_options(scheme, tau_d_method)
+        _check_skip(skip, skip_unit, getattr(cols, "ncol", None), scheme, bands)
         self._bind_sensors(scheme, cols, bands, levels, sensors, _level_keys(keys), mu_s, tau_d_method, out)
         need = sensor_workspace_bytes(scheme, cols.ncol, cols.nz, bands.nb, len(self.levels), sensors.nsens)
         self._finish(f"crt_hip_sensor_levels_{_io_suffix(bands)}", need, workspace)
+        self._bind_skip(skip, skip_unit, "crt_hip_sensor_levels_masked_f64")
 
     def _bind_sensors(self, scheme, cols, bands, levels, sensors, keys, mu_s, tau_d_method, out, sun=None):
         """``_bind`` + the level list, the sensor set and the outputs of ``keys`` (with ``sun``: of every sun state), NULL for the rest."""
@@ -1266,14 +1312,16 @@ class SensorLevelsSeriesPlan(SensorLevelsPlan):
     :class:`LevelsSeriesPlan` does.  float64 bands only."""
 
     def __init__(self, scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, sensors: SensorSet, *, keys=LEVEL_KEYS, mu_s=0.501,
-                 tau_d_method="quad", out=None, workspace=None):
+                 tau_d_method="quad", out=None, workspace=None, skip=None, skip_unit=1):
         self._check_options(scheme, tau_d_method)
         keys = _level_keys(keys)
+        _check_skip(skip, skip_unit, getattr(cols, "ncol", None), scheme, bands)
         if not isinstance(sun, SunSeries) or isinstance(sun, SunSeriesF32):
             raise TypeError("sun must be a SunSeries (float64 spectra)")
         self._bind_sensors(scheme, cols, bands, levels, sensors, keys, mu_s, tau_d_method, out, sun=sun)
         need = sensor_series_workspace_bytes(scheme, cols.ncol, cols.nz, bands.nb, sun.nt, len(self.levels), sensors.nsens)
         self._finish("crt_hip_sensor_levels_series_f64", need, workspace)
+        self._bind_skip(skip, skip_unit, "crt_hip_sensor_levels_series_masked_f64")
 
 
 def solve_sensor_levels_series(scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, sensors: SensorSet, **kw):
@@ -1900,17 +1948,24 @@ class SensorJacPlan(_LevelsDerivPlan):
     in place.  ``I_dr`` does not depend on the optics (zeros in its direction columns); bl has no soil and no upward stream.  The
     workspace also holds what a :class:`SensorLevelsPlan` of the same shape needs: that plan, called on ``plan.workspace`` with
     ``FLAG_SKIP_PRECOMPUTE`` after this one, gives the forward sums without a second column precompute.  A column's result is bitwise
-    the same alone or in any batch, for any subset of ``keys``, and a parameter column's bits do not depend on which others exist."""
+    the same alone or in any batch, for any subset of ``keys``, and a parameter column's bits do not depend on which others exist.
+
+    ``skip=``: an int32 tensor ``(ncol // skip_unit,)`` on the columns' device, read on the device at every call
+    (``crt_hip_sensor_jac_masked_f64``): column ``c`` is left alone -- its outputs and its slice sums in the workspace keep their bits --
+    iff ``skip[c // skip_unit] != 0``; an evaluated column has the bits of the plan without ``skip``.  The column precompute runs on
+    every column.  ``plan.use_skip = False`` makes the next calls evaluate everything.  Not with the composed n79 / zq plans.
+    :class:`SensorLevelsPlan`, :class:`SpectralNormalPlan` and the three series plans take the same two keywords."""
 
     _entry_name, _ws_query, _out_struct = "crt_hip_sensor_jac_f64", "crt_hip_sensor_jac_workspace_bytes", "CrtSensJacOut"
     _all_keys, _schemes, _what = LEVEL_KEYS, DLAI_SCHEMES, "sensor Jacobian"
     _no_kernel = "scheme {!r} has no sensor Jacobian; served: " + ", ".join(DLAI_SCHEMES)
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, *, d_leaf_r=None, d_leaf_t=None, d_soil_r=None,
-                 lai=True, tangent=None, keys=LEVEL_KEYS, mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
+                 lai=True, tangent=None, keys=LEVEL_KEYS, mu_s=0.501, tau_d_method="quad", out=None, workspace=None, skip=None, skip_unit=1):
         self._build(None, scheme, cols, bands, levels, sensors, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r, lai=lai, tangent=tangent,
-                    keys=keys, mu_s=mu_s, tau_d_method=tau_d_method, out=out, workspace=workspace)
+                    keys=keys, mu_s=mu_s, tau_d_method=tau_d_method, out=out, workspace=workspace, skip=skip, skip_unit=skip_unit)
 
+    _entry_masked_name = "crt_hip_sensor_jac_masked_f64"
     _series = False  # SensorJacSeriesPlan: a sun-angle series in front of the levels, outputs with a sun-state axis
 
     @classmethod
@@ -1921,8 +1976,11 @@ class SensorJacPlan(_LevelsDerivPlan):
 
     @classmethod
     def _static_of(cls, sun, scheme, bands, sensors, *, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, tangent=None, keys=LEVEL_KEYS,
-                   mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
+                   mu_s=0.501, tau_d_method="quad", out=None, workspace=None, skip=None, skip_unit=1, ncol=None):
         keys = cls._check_static(scheme, tau_d_method, keys, sensors=sensors, tangent=tangent, sun=sun)
+        if skip is not None and scheme not in SENSJAC_SCHEMES:
+            raise ValueError(f"the sensor Jacobian of {scheme} is composed of three calls: it takes no skip=")
+        _check_skip(skip, skip_unit, ncol, scheme, bands)
         axis = _ParamAxis(d_leaf_r, d_leaf_t, d_soil_r, lai, tangent=tangent)
         if scheme not in SENSJAC_SCHEMES and workspace is not None:
             raise ValueError(f"the sensor Jacobian of {scheme} runs plans with workspaces of their own: workspace must be None")
@@ -1937,7 +1995,8 @@ class SensorJacPlan(_LevelsDerivPlan):
 
     def _build(self, sun, scheme, cols, bands, levels, sensors, *, mu_s, tau_d_method, out, workspace, **kw):
         """The construction of this plan (``sun`` None) and of :class:`SensorJacSeriesPlan`."""
-        keys, axis = self._static_of(sun, scheme, bands, sensors, tau_d_method=tau_d_method, workspace=workspace, **kw)
+        skip, skip_unit = kw.get("skip"), kw.get("skip_unit", 1)
+        keys, axis = self._static_of(sun, scheme, bands, sensors, tau_d_method=tau_d_method, workspace=workspace, ncol=getattr(cols, "ncol", None), **kw)
         series = {} if sun is None else {"sun": sun}
         self._composed = scheme not in SENSJAC_SCHEMES
         self.levels, self.keys, self.sensors = normalize_levels(levels, cols.nz), keys, sensors
@@ -1965,6 +2024,7 @@ class SensorJacPlan(_LevelsDerivPlan):
             need = max(sensor_jac_series_workspace_bytes(scheme, ncol, cols.nz, nb, sun.nt, nsel, sensors.nsens, npar),
                        sensor_series_workspace_bytes(scheme, ncol, cols.nz, nb, sun.nt, nsel, sensors.nsens))
         self._finish(self._entry_name, need, workspace)
+        self._bind_skip(skip, skip_unit, self._entry_masked_name)
 
     def _tail(self):
         ref = lambda x: None if x is None else ctypes.byref(x)  # noqa: E731
@@ -2114,11 +2174,13 @@ class SensorJacSeriesPlan(SensorJacPlan):
     ``J.reshape(ncol, nt * nsel * nsens, npar)``."""
 
     _entry_name, _series = "crt_hip_sensor_jac_series_f64", True
+    _entry_masked_name = "crt_hip_sensor_jac_series_masked_f64"
 
     def __init__(self, scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, sensors: SensorSet, *, d_leaf_r=None, d_leaf_t=None,
-                 d_soil_r=None, lai=True, tangent=None, keys=LEVEL_KEYS, mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
+                 d_soil_r=None, lai=True, tangent=None, keys=LEVEL_KEYS, mu_s=0.501, tau_d_method="quad", out=None, workspace=None, skip=None,
+                 skip_unit=1):
         self._build(sun, scheme, cols, bands, levels, sensors, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r, lai=lai, tangent=tangent,
-                    keys=keys, mu_s=mu_s, tau_d_method=tau_d_method, out=out, workspace=workspace)
+                    keys=keys, mu_s=mu_s, tau_d_method=tau_d_method, out=out, workspace=workspace, skip=skip, skip_unit=skip_unit)
 
     @classmethod
     def _static(cls, scheme, cols, bands, sun, levels, sensors, **kw):
@@ -2291,6 +2353,31 @@ def _check_chain(chain, inv_sigma_chain, ncol, npar, shared=None):
     return npix, nd
 
 
+EVALUATE_MODES = ("all", "running", "accepted")
+
+
+def _check_evaluate(evaluate, scheme, chain, spectral):
+    """``evaluate=`` of the retrieval plans (no device): ``"all"`` -- every column at every step, the plan as it always was; ``"running"`` --
+    the masked entries of include_mask/crt1d_hip_masked.h skip the columns (with a chain: the pixels) that have stopped; ``"accepted"`` --
+    the forward sums first, ``crt_hip_lm_decide_f64``, then the Jacobian only where the trial point will be accepted."""
+    if evaluate not in EVALUATE_MODES:
+        raise ValueError(f"evaluate must be one of {EVALUATE_MODES}, got {evaluate!r}")
+    if evaluate == "all":
+        return
+    if evaluate == "accepted":
+        if spectral:
+            raise ValueError("evaluate='accepted' is not served by a spectral plan: the cost comes out of the kernel that forms the normal "
+                             "equations (a cost-only first pass does not exist); use evaluate='running'")
+        if chain is not None:
+            raise ValueError("evaluate='accepted' is not served by a chained plan: acceptance is per pixel and includes the coupling terms; "
+                             "use evaluate='running'")
+        if scheme not in SENSJAC_SCHEMES:
+            raise ValueError(f"evaluate='accepted' is not served by a composed plan: the sensor Jacobian of {scheme} is three calls without a "
+                             "mask")
+    if scheme not in MASKED_SCHEMES:
+        raise ValueError(f"evaluate={evaluate!r} needs the masked kernels; scheme {scheme!r} has none (served: " + ", ".join(MASKED_SCHEMES) + ")")
+
+
 class _LmPlan:
     """What :class:`RetrievalPlan` and :class:`SpectralRetrievalPlan` share: the base and the working :class:`Columns` / :class:`Bands`, the
     leaf-angle tangent, the leaf-model binding, the bounds, the prior, the starting point and the Levenberg-Marquardt state, the structs
@@ -2301,13 +2388,22 @@ class _LmPlan:
     _owns_sums = True  # a chained plan allocates its block of per-column sums; False: the subclass's _inner binds ``_blk`` to its own
 
     def _construct(self, keys, axis, o, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, chain=None,
-                   inv_sigma_chain=None, shared=None, **inner):
+                   inv_sigma_chain=None, shared=None, evaluate="all", **inner):
         self.lib = _lib.load()
         self.scheme, self.keys, self.sun, self.options = scheme, keys, sun, o
         ncol, nz, nb, dev = cols.ncol, cols.nz, bands.nb, cols.device
         npar, ntan, lai, leaf = axis.npar, axis.ntan, axis.lai, axis.leaf
         f64 = dict(dtype=torch.float64, device=dev)
         new = lambda *shape: torch.zeros(shape, **f64)  # noqa: E731
+        # the status of every unit (column; with a chain: pixel) first: with evaluate != "all" it is the skip flags of the inner plans
+        self.evaluate, self.nsteps = evaluate, 0
+        self.nd = None if chain is None else int(chain)
+        nunit = self.npix = ncol if chain is None else ncol // self.nd
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.status, self.naccept, self.nreject = (torch.zeros((nunit,), **i32) for _ in range(3))
+        self._skip = {} if evaluate == "all" else dict(skip=self.status, skip_unit=self.nd or 1)
+        if evaluate == "accepted":  # what crt_hip_lm_decide_f64 writes: the Jacobian's own skip flags and the trial cost
+            self.skip_jac, self.cost_t = torch.ones((ncol,), **i32), new(ncol)
         # the base state and the working inputs k_retrieve_apply overwrites
         self.base_cols, self.base_bands = cols, bands
         self._base_stride = bands.col_stride(ncol)
@@ -2354,13 +2450,9 @@ class _LmPlan:
         self._p0 = _per_col(p0, "p0", ncol, npar, dev).clone()
         # the state
         ntri = npar * (npar + 1) // 2
-        i32 = dict(dtype=torch.int32, device=dev)
         # (a chain of nd dates: the columns are (pixel, date) pairs, p, p_trial, A and g stay per column, the rest is per pixel)
-        self.nd = None if chain is None else int(chain)
-        nunit = self.npix = ncol if chain is None else ncol // self.nd
         self.p, self.p_trial, self.cost, self.lam = new(ncol, npar), new(ncol, npar), new(nunit), new(nunit)
         self.A, self.g = new(ncol, ntri), new(ncol, npar)
-        self.status, self.naccept, self.nreject = (torch.zeros((nunit,), **i32) for _ in range(3))
         self.cov = new(ncol, npar, npar)
         # the structs of the entries: k_retrieve_apply at the trial point (_ap) and at the accepted point (_ap_p)
         ptr = lambda v: None if v is None else v.data_ptr()  # noqa: E731
@@ -2429,6 +2521,7 @@ class _LmPlan:
         self.lam.fill_(self.options["lam0"])
         for v in (self.A, self.g, self.status, self.naccept, self.nreject):
             v.zero_()
+        self.nsteps = 0
         return self
 
     def lut_posterior(self, temperature=1.0, stream=None):
@@ -2444,10 +2537,26 @@ class _LmPlan:
                                                         inv_sigma_prior=self.inv_sigma_prior, temperature=temperature))
         return self._post[1](stream)
 
-    def run(self, niter, stream=None):
-        """``niter`` steps with no host synchronisation in between."""
-        for _ in range(int(niter)):
+    def running(self):
+        """The number of units (columns; with a chain: pixels) that are still running, a 0-d int64 tensor on the device, formed on the
+        current stream; the host is not synchronised."""
+        return (self.status == 0).sum()
+
+    def run(self, niter, stream=None, check_every=None):
+        """``niter`` steps with no host synchronisation in between.  ``check_every=k``: the count of :meth:`running` is read after every
+        ``k`` steps -- the one host synchronisation the caller asks for -- and the loop ends once it is 0; a unit that has stopped is not
+        touched by a step, so the state is bitwise that of all ``niter`` steps.  ``plan.nsteps`` counts the steps since the last
+        :meth:`reset`."""
+        if check_every is not None and (isinstance(check_every, bool) or not isinstance(check_every, int) or check_every < 1):
+            raise ValueError(f"check_every must be None or an integer >= 1, got {check_every!r}")
+        dev = self.cols.device
+        for i in range(int(niter)):
             self.step(stream)
+            if check_every is not None and (i + 1) % check_every == 0:
+                with torch.cuda.stream(torch.cuda.current_stream(dev) if stream is None else stream):
+                    left = int(self.running())
+                if left == 0:
+                    break
         return self
 
     def result(self):
@@ -2552,23 +2661,25 @@ class RetrievalPlan(_LmPlan):
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, y, *, keys, sun=None, d_leaf_r=None, d_leaf_t=None,
                  d_soil_r=None, lai=True, leaf=False, p0=None, lo=None, hi=None, inv_sigma=None, prior=None, inv_sigma_prior=None,
-                 leaf_model=None, chain=None, inv_sigma_chain=None, shared=None, mu_s=0.501, tau_d_method="quad", **options):
+                 leaf_model=None, chain=None, inv_sigma_chain=None, shared=None, evaluate="all", mu_s=0.501, tau_d_method="quad", **options):
         static = self._static(scheme, cols, bands, levels, sensors, y, keys=keys, sun=sun, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t,
                               d_soil_r=d_soil_r, lai=lai, leaf=leaf, p0=p0, lo=lo, hi=hi, inv_sigma=inv_sigma, prior=prior,
                               inv_sigma_prior=inv_sigma_prior, leaf_model=leaf_model, chain=chain, inv_sigma_chain=inv_sigma_chain,
-                              shared=shared, tau_d_method=tau_d_method, **options)
+                              shared=shared, evaluate=evaluate, tau_d_method=tau_d_method, **options)
         self._construct(*static, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, chain=chain,
-                        inv_sigma_chain=inv_sigma_chain, shared=shared, sensors=sensors, y=y, inv_sigma=inv_sigma, mu_s=mu_s, tau_d_method=tau_d_method)
+                        inv_sigma_chain=inv_sigma_chain, shared=shared, evaluate=evaluate, sensors=sensors, y=y, inv_sigma=inv_sigma, mu_s=mu_s,
+                        tau_d_method=tau_d_method)
 
     @classmethod
     def _static(cls, scheme, cols, bands, levels, sensors, y, *, keys, sun=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True,
                 leaf=False, p0=None, lo=None, hi=None, inv_sigma=None, prior=None, inv_sigma_prior=None, leaf_model=None, chain=None,
-                inv_sigma_chain=None, shared=None, mu_s=0.501, tau_d_method="quad", **options):
+                inv_sigma_chain=None, shared=None, evaluate="all", mu_s=0.501, tau_d_method="quad", **options):
         """The constructor's arguments -> (keys, the parameter axis, the LM options): every check that needs neither a column nor a
         device."""
         _SolvePlan._check_options(_SolvePlan, scheme, tau_d_method)
         if scheme not in RETRIEVE_SCHEMES:
             raise ValueError(f"scheme {scheme!r} has no retrieval; served: " + ", ".join(RETRIEVE_SCHEMES))
+        _check_evaluate(evaluate, scheme, chain, False)
         keys = _level_keys(keys)
         if not isinstance(sensors, SensorSet):
             raise TypeError("sensors must be a SensorSet")
@@ -2588,8 +2699,9 @@ class RetrievalPlan(_LmPlan):
         """The Jacobian plan and the forward plan on its workspace, the observations against the forward sums.  -> the Jacobian plan"""
         f = dict(keys=keys, mu_s=mu_s, tau_d_method=tau_d_method)
         a = (scheme, self.cols, self.bands) + (() if sun is None else (sun,)) + (levels, sensors)
-        self.jac = (SensorJacPlan if sun is None else SensorJacSeriesPlan)(*a, **axis, **f)
-        self.fwd = (SensorLevelsPlan if sun is None else SensorLevelsSeriesPlan)(*a, **f, workspace=getattr(self.jac, "workspace", None))
+        jskip = self._skip if self.evaluate != "accepted" else dict(skip=self.skip_jac, skip_unit=1)
+        self.jac = (SensorJacPlan if sun is None else SensorJacSeriesPlan)(*a, **axis, **f, **jskip)
+        self.fwd = (SensorLevelsPlan if sun is None else SensorLevelsSeriesPlan)(*a, **f, workspace=getattr(self.jac, "workspace", None), **self._skip)
         self._fwd_flags = 0 if self.jac._composed else _lib.FLAG_SKIP_PRECOMPUTE
         shape = tuple(self.fwd.out[keys[0]].shape)
         self.nrow = int(torch.Size(shape[1:]).numel())
@@ -2611,10 +2723,19 @@ class RetrievalPlan(_LmPlan):
         """One iteration on ``stream`` (default: torch's current stream): apply, tangent, Jacobian, forward sums, ``k_lm_step``."""
         dev = self.cols.device
         s = torch.cuda.current_stream(dev) if stream is None else stream
+        self.nsteps += 1
         with torch.cuda.device(dev):
             self._evaluate(self._ap, s)
-            self.jac(s)
-            self.fwd(s, flags=self._fwd_flags)
+            if self.evaluate == "accepted":
+                # the forward sums with their own precompute where the column runs, the decision k_lm_step will take, then the Jacobian
+                # (with the precompute again: the forward plan's slice sums lie on its side records) where the trial point is accepted
+                self.fwd(s, flags=0)
+                _lib.check(self.lib.crt_hip_lm_decide_f64(ctypes.byref(self._prob), self._obs, len(self.keys), ctypes.byref(self._state),
+                                                          self.skip_jac.data_ptr(), self.cost_t.data_ptr(), s.cuda_stream), "crt_hip_lm_decide_f64")
+                self.jac(s)
+            else:
+                self.jac(s)
+                self.fwd(s, flags=self._fwd_flags)
             if self.nd is not None:  # the last launch replaced by two: the sums of k_lm_step written out, then the step of every pixel
                 _lib.check(self.lib.crt_hip_lm_normal_f64(self.p.shape[0], self.npar, self._obs, len(self.keys), *[v.data_ptr() for v in self.sums],
                                                           s.cuda_stream), "crt_hip_lm_normal_f64")
@@ -2702,10 +2823,12 @@ class SpectralNormalPlan(_LevelsDerivPlan):
     _all_keys, _schemes, _what = LEVEL_KEYS, SPECTRAL_RETRIEVE_SCHEMES, "spectral retrieval"
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None,
-                 lai=True, tangent=None, fwd=False, mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
+                 lai=True, tangent=None, fwd=False, mu_s=0.501, tau_d_method="quad", out=None, workspace=None, skip=None, skip_unit=1):
         self._build(None, scheme, cols, bands, levels, y, keys=keys, inv_sigma=inv_sigma, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r,
-                    lai=lai, tangent=tangent, fwd=fwd, mu_s=mu_s, tau_d_method=tau_d_method, out=out, workspace=workspace)
+                    lai=lai, tangent=tangent, fwd=fwd, mu_s=mu_s, tau_d_method=tau_d_method, out=out, workspace=workspace, skip=skip,
+                    skip_unit=skip_unit)
 
+    _entry_masked_name = "crt_hip_spectral_normal_masked_f64"
     _series = False  # SpectralNormalSeriesPlan: a sun-angle series in front of the levels, arrays with a sun-state axis
 
     @classmethod
@@ -2716,14 +2839,16 @@ class SpectralNormalPlan(_LevelsDerivPlan):
 
     @classmethod
     def _static_of(cls, sun, scheme, cols, bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True,
-                   tangent=None, per_step=False, fwd=False, mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
+                   tangent=None, per_step=False, fwd=False, mu_s=0.501, tau_d_method="quad", out=None, workspace=None, skip=None, skip_unit=1):
         _check_tangent(tangent, sun, cls._series)
         keys, axis = _spectral_static(scheme, y, keys, inv_sigma, tau_d_method, bands, sun, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t,
                                       d_soil_r=d_soil_r, lai=lai, tangent=tangent)
+        _check_skip(skip, skip_unit, getattr(cols, "ncol", None), scheme, bands)
         return keys, axis, _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), axis.npar, sun)
 
     def _build(self, sun, scheme, cols, bands, levels, y, *, inv_sigma, fwd, mu_s, tau_d_method, out, workspace, per_step=False, **kw):
         """The construction of this plan (``sun`` None) and of :class:`SpectralNormalSeriesPlan`."""
+        skip, skip_unit = kw.get("skip"), kw.get("skip_unit", 1)
         keys, axis, self.levels = self._static_of(sun, scheme, cols, bands, levels, y, inv_sigma=inv_sigma, tau_d_method=tau_d_method, **kw)
         series = {} if sun is None else {"sun": sun}
         self.keys = keys
@@ -2762,6 +2887,7 @@ class SpectralNormalPlan(_LevelsDerivPlan):
         else:
             need = spectral_normal_series_workspace_bytes(scheme, ncol, cols.nz, nb, sun.nt, nsel, len(keys), npar)
         self._finish(self._entry_name, need, workspace)
+        self._bind_skip(skip, skip_unit, self._entry_masked_name)
 
     def _tail(self):
         ref = lambda x: None if x is None else ctypes.byref(x)  # noqa: E731
@@ -2805,11 +2931,14 @@ class SpectralNormalSeriesPlan(SpectralNormalPlan):
     per column; the workspace starts with the records of a :class:`LevelsSeriesPlan`, which can run on it with ``FLAG_SKIP_PRECOMPUTE``."""
 
     _entry_name, _ws_query, _series = "crt_hip_spectral_normal_series_f64", "crt_hip_spectral_normal_series_workspace_bytes", True
+    _entry_masked_name = "crt_hip_spectral_normal_series_masked_f64"
 
     def __init__(self, scheme, cols: Columns, bands: Bands, sun: SunSeries, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None,
-                 d_soil_r=None, lai=True, tangent=None, per_step=False, fwd=False, mu_s=0.501, tau_d_method="quad", out=None, workspace=None):
+                 d_soil_r=None, lai=True, tangent=None, per_step=False, fwd=False, mu_s=0.501, tau_d_method="quad", out=None, workspace=None,
+                 skip=None, skip_unit=1):
         self._build(sun, scheme, cols, bands, levels, y, keys=keys, inv_sigma=inv_sigma, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t, d_soil_r=d_soil_r,
-                    lai=lai, tangent=tangent, per_step=per_step, fwd=fwd, mu_s=mu_s, tau_d_method=tau_d_method, out=out, workspace=workspace)
+                    lai=lai, tangent=tangent, per_step=per_step, fwd=fwd, mu_s=mu_s, tau_d_method=tau_d_method, out=out, workspace=workspace,
+                    skip=skip, skip_unit=skip_unit)
 
     @classmethod
     def _static(cls, scheme, cols, bands, sun, levels, y, **kw):
@@ -2847,30 +2976,39 @@ class SpectralRetrievalPlan(_LmPlan):
 
     ``chain=nd``, ``inv_sigma_chain``: as for :class:`RetrievalPlan` -- the columns are (pixel, date) pairs and the closing call is
     ``crt_hip_lm_step_chain_f64`` on the block the normal plan wrote.  ``shared=``: as for :class:`RetrievalPlan` -- the closing call is
-    ``crt_hip_lm_step_shared_f64``."""
+    ``crt_hip_lm_step_shared_f64``.
+
+    ``evaluate="running"``: as for :class:`RetrievalPlan` -- the normal plan goes through its masked entry with ``status`` as the skip
+    flags; :meth:`fitted` still evaluates every column.  ``"accepted"`` is a ValueError: the cost comes out of the kernel that forms the
+    normal equations."""
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None,
                  lai=True, leaf=False, p0=None, lo=None, hi=None, prior=None, inv_sigma_prior=None, sun=None, leaf_model=None, chain=None,
-                 inv_sigma_chain=None, shared=None, mu_s=0.501, tau_d_method="quad", **options):
+                 inv_sigma_chain=None, shared=None, evaluate="all", mu_s=0.501, tau_d_method="quad", **options):
         keys, axis, o, levels = self._static(scheme, cols, bands, levels, y, keys=keys, inv_sigma=inv_sigma, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t,
                                              d_soil_r=d_soil_r, lai=lai, leaf=leaf, p0=p0, lo=lo, hi=hi, prior=prior,
                                              inv_sigma_prior=inv_sigma_prior, sun=sun, leaf_model=leaf_model, chain=chain,
-                                             inv_sigma_chain=inv_sigma_chain, shared=shared, tau_d_method=tau_d_method, **options)
+                                             inv_sigma_chain=inv_sigma_chain, shared=shared, evaluate=evaluate, tau_d_method=tau_d_method,
+                                             **options)
         self._construct(keys, axis, o, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, chain=chain,
-                        inv_sigma_chain=inv_sigma_chain, shared=shared, y=y, inv_sigma=inv_sigma, mu_s=mu_s, tau_d_method=tau_d_method)
+                        inv_sigma_chain=inv_sigma_chain, shared=shared, evaluate=evaluate, y=y, inv_sigma=inv_sigma, mu_s=mu_s,
+                        tau_d_method=tau_d_method)
 
     @classmethod
     def _static(cls, scheme, cols, bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, leaf=False,
                 p0=None, lo=None, hi=None, prior=None, inv_sigma_prior=None, sun=None, leaf_model=None, chain=None, inv_sigma_chain=None,
-                shared=None, mu_s=0.501, tau_d_method="quad", **options):
+                shared=None, evaluate="all", mu_s=0.501, tau_d_method="quad", **options):
         """The constructor's arguments -> (keys in ``LEVEL_KEYS`` order, the parameter axis, the LM options, the normalized levels): every
         check that needs no device."""
+        if evaluate not in EVALUATE_MODES:
+            raise ValueError(f"evaluate must be one of {EVALUATE_MODES}, got {evaluate!r}")
         keys, axis = _spectral_static(scheme, y, keys, inv_sigma, tau_d_method, bands, sun, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t,
                                       d_soil_r=d_soil_r, lai=lai, leaf=leaf, leaf_model=leaf_model)
         o = _lm_options(lo, hi, axis.npar, options)
         _check_start(leaf_model, lo, hi, p0, prior, inv_sigma_prior)
         if isinstance(p0, LutTable):
             _check_lut_start(p0, axis.params, keys, True, y)
+        _check_evaluate(evaluate, scheme, chain, True)
         levels = _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), axis.npar, sun)
         _check_chain(chain, inv_sigma_chain, cols, axis.npar, _check_shared(shared, chain, axis.params, p0))
         return keys, axis, o, levels
@@ -2880,7 +3018,7 @@ class SpectralRetrievalPlan(_LmPlan):
     def _inner(self, scheme, levels, sun, y, **kw):
         """The normal plan on the working tensors, which holds the observations (``fwd`` kept for :meth:`fitted`, not written by a step)."""
         a = (scheme, self.cols, self.bands) + (() if sun is None else (sun,)) + (levels, y)
-        self.normal = (SpectralNormalPlan if sun is None else SpectralNormalSeriesPlan)(*a, fwd=True, **kw)
+        self.normal = (SpectralNormalPlan if sun is None else SpectralNormalSeriesPlan)(*a, fwd=True, **kw, **self._skip)
         self.normal.write_fwd = False
         self.y, self.inv_sigma = self.normal.y, self.normal.inv_sigma
         self.nrow = (1 if sun is None else sun.nt) * len(self.normal.levels) * self.bands.nb
@@ -2891,6 +3029,7 @@ class SpectralRetrievalPlan(_LmPlan):
         """One iteration on ``stream`` (default: torch's current stream): apply, tangent, normal equations, ``k_lm_step_normal``."""
         dev = self.cols.device
         s = torch.cuda.current_stream(dev) if stream is None else stream
+        self.nsteps += 1
         with torch.cuda.device(dev):
             self._evaluate(self._ap, s)
             self.normal(s)
@@ -2907,12 +3046,12 @@ class SpectralRetrievalPlan(_LmPlan):
         dev = self.cols.device
         s = torch.cuda.current_stream(dev) if stream is None else stream
         with torch.cuda.device(dev):
-            self.normal.write_fwd = True
+            self.normal.write_fwd, self.normal.use_skip = True, False  # (every column, whatever ``evaluate``)
             try:
                 self._evaluate(self._ap_p, s)
                 self.normal(s)
             finally:
-                self.normal.write_fwd = False
+                self.normal.write_fwd, self.normal.use_skip = False, True
             with torch.cuda.stream(s):
                 return {k: v.clone() for k, v in self.normal.out["fwd"].items()}
 

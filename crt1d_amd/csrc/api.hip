@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "crt1d_hip_masked.h"
 #include "epilogue.hpp"
 #include "series/crt1d_hip_specfit_series.h"
 #include "specfit.hpp"
@@ -376,7 +377,12 @@ static int solve_impl(int scheme, const crt_columns* cols, const crt_bands* band
                       const IntArgs* integ = nullptr, const LevArgs* lev = nullptr, const crt_sun_series* ser = nullptr,
                       SensLaunch* sl = nullptr, size_t extra_ws = 0) {
   SolveOpts o;
-  if (const int st = check_solve(scheme, cols, bands, opts, out, workspace, workspace_bytes, integ, lev, ser, o, extra_ws)) return st;
+  const int chk = check_solve(scheme, cols, bands, opts, out, workspace, workspace_bytes, integ, lev, ser, o, extra_ws);
+  if (sl && sl->closed_only) {  // a masked entry: an argument error is one for every scheme, then the scheme, whatever the workspace
+    if (chk == CRT_ERR_BAD_ARG || chk == CRT_ERR_SHAPE) return chk;
+    if (scheme != CRT_SCHEME_2S && scheme != CRT_SCHEME_BL && scheme != CRT_SCHEME_G77 && scheme != CRT_SCHEME_BF) return CRT_ERR_UNSUPPORTED;
+  }
+  if (chk != CRT_OK) return chk;
   ColArgs ca;
   SolveArgs sa;
   build_args(scheme, cols, bands, out, workspace, f32, o, ca, sa);
@@ -595,15 +601,31 @@ size_t crt_hip_sensor_series_workspace_bytes(int scheme, int32_t ncol, int32_t n
   return rec == 0 || nb <= 0 ? 0 : rec + sens_partial_bytes(scheme, ncol, nz, nb, nt, nsel, nsens);
 }
 
+// The column mask of a masked entry (include_mask/crt1d_hip_masked.h).  NULL or a NULL skip: no mask, the plain launches.  ok: false for
+// unit < 1 or ncol % unit != 0 (a NULL cols is the sibling's error).
+struct MaskArg {
+  ColMask m;
+  bool ok;
+};
+static MaskArg parse_mask(const crt_col_mask* mask, const crt_columns* cols) {
+  if (!mask || !mask->skip) return {{}, true};
+  if (mask->unit < 1 || (cols && cols->ncol > 0 && cols->ncol % mask->unit != 0)) return {{}, false};
+  return {{mask->skip, mask->unit}, true};
+}
+// masked: the call comes from a masked entry, which serves 2s, bl, g77 and bf only (mask: its mask, or NULL)
 static int sensor_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels, int32_t nsel,
                        const crt_sensor_set* sensors, const crt_sensor_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream,
-                       int f32, const crt_sun_series* ser = nullptr) {
+                       int f32, const crt_sun_series* ser = nullptr, bool masked = false, const crt_col_mask* mask = nullptr) {
   if (!scheme_ok(scheme) || !cols || !bands || !sensors || !out) return CRT_ERR_BAD_ARG;
+  const MaskArg ma = parse_mask(mask, cols);
+  if (!ma.ok) return CRT_ERR_BAD_ARG;
   if (!sensors->first || !sensors->count || !sensors->w) return CRT_ERR_BAD_ARG;
   const int nsens = sensors->nsens, nb = bands->nb;
   if (nsens < 1 || nsens > CRT_MAX_SENSOR_BANDS || nb <= 0) return CRT_ERR_BAD_ARG;
   if (!out->I_dr && !out->I_df_d && !out->I_df_u && !out->F) return CRT_ERR_BAD_ARG;
   SensLaunch sl = {};
+  sl.mask = ma.m;
+  sl.closed_only = masked;
   SensArgs& sn = sl.sn;
   sn.o[0] = out->I_dr;
   sn.o[1] = out->I_df_d;
@@ -894,13 +916,14 @@ size_t crt_hip_sensor_jac_workspace_bytes(int scheme, int32_t ncol, int32_t nz, 
 static int sensor_jac_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_sun_series* ser, bool series,
                            const crt_options* opts, const int32_t* levels, int32_t nsel, const crt_sensor_set* sensors,
                            const crt_optics_dirs* dirs, int with_lai, const DleafTan* tangent, const crt_sensjac_out* out, void* workspace,
-                           size_t workspace_bytes, crt_stream_t stream) {
+                           size_t workspace_bytes, crt_stream_t stream, const crt_col_mask* mask = nullptr) {
+  const MaskArg ma = parse_mask(mask, cols);
   SensJacArgs ja = {};
   SensArgs& sn = ja.sn;
   const ParamAxis axis = parse_axis(bands, dirs, with_lai, tangent);
   axis.put(ja);
   bool args_ok = sensors && sensors->first && sensors->count && sensors->w && sensors->nsens >= 1 && sensors->nsens <= CRT_MAX_SENSOR_BANDS &&
-                 out && (out->I_dr || out->I_df_d || out->I_df_u || out->F) && axis.ok && (!series || ser);
+                 out && (out->I_dr || out->I_df_d || out->I_df_u || out->F) && axis.ok && (!series || ser) && ma.ok;
   if (args_ok) {
     const int nb = bands->nb;
     sn.o[0] = out->I_dr;
@@ -928,9 +951,9 @@ static int sensor_jac_impl(int scheme, const crt_columns* cols, const crt_bands*
         ja.side_lai = side;
         ja.side_leaf = rec.side_leaf(side, sa);
         sn.part = rec.part(side, sa);
-        if (!ser) return launch_sens_jac(scheme, sa, la, ja, s, probe);
+        if (!ser) return launch_sens_jac(scheme, sa, la, ja, s, probe, nullptr, nullptr, ma.m);
         const SeriesArgs sr = series_args(scheme, sa, ser);
-        return launch_sens_jac(scheme, sa, la, ja, s, probe, &sr, tangent ? tangent->dg_at_psi : nullptr);
+        return launch_sens_jac(scheme, sa, la, ja, s, probe, &sr, tangent ? tangent->dg_at_psi : nullptr, ma.m);
       },
       rec, true, rec.sized && sel_ok ? sensjac_part_bytes(cols->ncol, bands->nb, nsel, sn.nsens, axis.npar(), ser ? ser->nt : 1) : 0, ser);
 }
@@ -993,12 +1016,13 @@ size_t crt_hip_spectral_normal_series_workspace_bytes(int scheme, int32_t ncol, 
 static int spectral_normal_impl(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_sun_series* ser, bool series,
                                 const crt_options* opts, const int32_t* levels, int32_t nsel, const crt_optics_dirs* dirs, int with_lai,
                                 const DleafTan* tangent, const crt_spec_obs* obs, const crt_spec_series_out* out, void* workspace,
-                                size_t workspace_bytes, crt_stream_t stream) {
+                                size_t workspace_bytes, crt_stream_t stream, const crt_col_mask* mask = nullptr) {
+  const MaskArg ma = parse_mask(mask, cols);
   SpecArgs sp = {};
   const ParamAxis axis = parse_axis(bands, dirs, with_lai, tangent);
   axis.put(sp);
   const int per_t = out ? (out->A_t != nullptr) + (out->g_t != nullptr) + (out->c2_t != nullptr) : 0;
-  bool args_ok = obs && out && out->A && out->g && out->c2 && (per_t == 0 || per_t == 3) && axis.ok && (!series || ser);
+  bool args_ok = obs && out && out->A && out->g && out->c2 && (per_t == 0 || per_t == 3) && axis.ok && (!series || ser) && ma.ok;
   if (args_ok) {
     const double* const y[4] = {obs->y_I_dr, obs->y_I_df_d, obs->y_I_df_u, obs->y_F};
     const double* const is[4] = {obs->inv_sigma_I_dr, obs->inv_sigma_I_df_d, obs->inv_sigma_I_df_u, obs->inv_sigma_F};
@@ -1023,8 +1047,9 @@ static int spectral_normal_impl(int scheme, const crt_columns* cols, const crt_b
         sp.side_lai = side;
         sp.side_leaf = rec.side_leaf(side, sa);
         sp.part = rec.part(side, sa);
-        if (!ser) return launch_spec_normal(scheme, sa, la, sp, s, probe);
-        return launch_spec_normal_series(scheme, sa, la, sp, so, series_args(scheme, sa, ser), tangent ? tangent->dg_at_psi : nullptr, s, probe);
+        if (!ser) return launch_spec_normal(scheme, sa, la, sp, s, probe, ma.m);
+        return launch_spec_normal_series(scheme, sa, la, sp, so, series_args(scheme, sa, ser), tangent ? tangent->dg_at_psi : nullptr, s, probe,
+                                         ma.m);
       },
       rec, true,
       !tail  ? 0
@@ -1052,6 +1077,64 @@ int crt_hip_spectral_normal_series_f64(int scheme, const crt_columns* cols, cons
   const DleafTan tn = dleaf_tan(tangent);
   return spectral_normal_impl(scheme, cols, bands, sun, true, opts, levels, nsel, dirs, with_lai, tangent ? &tn : nullptr, obs, out, workspace,
                               workspace_bytes, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// The masked entries (include_mask/crt1d_hip_masked.h): each is its sibling's host path with the mask handed to the launcher.
+
+int crt_hip_sensor_levels_masked_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
+                                     int32_t nsel, const crt_sensor_set* sensors, const crt_sensor_out* out, void* workspace,
+                                     size_t workspace_bytes, crt_stream_t stream, const crt_col_mask* mask) {
+  return sensor_impl(scheme, cols, bands, opts, levels, nsel, sensors, out, workspace, workspace_bytes, stream, 0, nullptr, true, mask);
+}
+
+int crt_hip_sensor_levels_series_masked_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_sun_series* sun,
+                                            const crt_options* opts, const int32_t* levels, int32_t nsel, const crt_sensor_set* sensors,
+                                            const crt_sensor_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream,
+                                            const crt_col_mask* mask) {
+  if (!sun) return CRT_ERR_BAD_ARG;
+  return sensor_impl(scheme, cols, bands, opts, levels, nsel, sensors, out, workspace, workspace_bytes, stream, 0, sun, true, mask);
+}
+
+int crt_hip_sensor_jac_masked_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts, const int32_t* levels,
+                                  int32_t nsel, const crt_sensor_set* sensors, const crt_optics_dirs* dirs, int with_lai,
+                                  const crt_leaf_tangent* tangent, const crt_sensjac_out* out, void* workspace, size_t workspace_bytes,
+                                  crt_stream_t stream, const crt_col_mask* mask) {
+  const DleafTan tn = dleaf_tan(tangent);
+  return sensor_jac_impl(scheme, cols, bands, nullptr, false, opts, levels, nsel, sensors, dirs, with_lai, tangent ? &tn : nullptr, out, workspace,
+                         workspace_bytes, stream, mask);
+}
+
+int crt_hip_sensor_jac_series_masked_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_sun_series* sun,
+                                         const crt_options* opts, const int32_t* levels, int32_t nsel, const crt_sensor_set* sensors,
+                                         const crt_optics_dirs* dirs, int with_lai, const crt_leaf_tangent_series* tangent,
+                                         const crt_sensjac_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream,
+                                         const crt_col_mask* mask) {
+  const DleafTan tn = dleaf_tan(tangent);
+  return sensor_jac_impl(scheme, cols, bands, sun, true, opts, levels, nsel, sensors, dirs, with_lai, tangent ? &tn : nullptr, out, workspace,
+                         workspace_bytes, stream, mask);
+}
+
+int crt_hip_spectral_normal_masked_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_options* opts,
+                                       const int32_t* levels, int32_t nsel, const crt_optics_dirs* dirs, int with_lai,
+                                       const crt_leaf_tangent* tangent, const crt_spec_obs* obs, const crt_spec_normal_out* out, void* workspace,
+                                       size_t workspace_bytes, crt_stream_t stream, const crt_col_mask* mask) {
+  const crt_spec_series_out so = out ? crt_spec_series_out{out->A, out->g, out->c2, nullptr, nullptr, nullptr, out->fwd_I_dr, out->fwd_I_df_d,
+                                                           out->fwd_I_df_u, out->fwd_F}
+                                     : crt_spec_series_out{};
+  const DleafTan tn = dleaf_tan(tangent);
+  return spectral_normal_impl(scheme, cols, bands, nullptr, false, opts, levels, nsel, dirs, with_lai, tangent ? &tn : nullptr, obs, out ? &so : nullptr,
+                              workspace, workspace_bytes, stream, mask);
+}
+
+int crt_hip_spectral_normal_series_masked_f64(int scheme, const crt_columns* cols, const crt_bands* bands, const crt_sun_series* sun,
+                                              const crt_options* opts, const int32_t* levels, int32_t nsel, const crt_optics_dirs* dirs,
+                                              int with_lai, const crt_leaf_tangent_series* tangent, const crt_spec_obs* obs,
+                                              const crt_spec_series_out* out, void* workspace, size_t workspace_bytes, crt_stream_t stream,
+                                              const crt_col_mask* mask) {
+  const DleafTan tn = dleaf_tan(tangent);
+  return spectral_normal_impl(scheme, cols, bands, sun, true, opts, levels, nsel, dirs, with_lai, tangent ? &tn : nullptr, obs, out, workspace,
+                              workspace_bytes, stream, mask);
 }
 
 int crt_hip_bandsum_finish_f64(const crt_columns* cols, int32_t ngroup, const crt_bandsum_out* out, crt_stream_t stream) {

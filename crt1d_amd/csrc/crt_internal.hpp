@@ -819,10 +819,22 @@ struct SensArgs {
   int32_t qs[4];
   int32_t first[CRT_MAX_SENSOR_BANDS], count[CRT_MAX_SENSOR_BANDS], off[CRT_MAX_SENSOR_BANDS];
 };
-// what a sensor call adds to a level launch; nslice: the band slices the launcher chose (written by a probe too)
+// The column mask of the masked entries (include_mask/crt1d_hip_masked.h): column c is skipped iff skip[c / unit] != 0.  It travels as
+// the LAST argument of the masked kernel instantiations only -- the argument blocks of the plain kernels keep their layout -- and is
+// read once per workgroup (per thread in the finish kernels), before anything of the column.  skip == nullptr on the host: no mask, the
+// plain kernels are launched.
+struct ColMask {
+  const int32_t* skip;
+  int unit;
+};
+__device__ __forceinline__ bool col_skipped(const ColMask& m, int c) { return m.skip[c / m.unit] != 0; }
+
+// what a sensor call adds to a level launch; nslice: the band slices the launcher chose (written by a probe too); mask: the masked entries
 struct SensLaunch {
   SensArgs sn;
   int nslice;
+  ColMask mask;
+  bool closed_only;  // the call comes from a masked entry: 2s, bl, g77 and bf only (api.hip refuses the rest before any launch)
 };
 constexpr int SENS_STAGE = 4;  // LDS doubles per lane of the staging row
 
@@ -926,9 +938,10 @@ inline int sens_probe(SensLaunch* sl, const LevSlices& ls, long long nv, int nse
   if (ls.nslice > 1 && nv * nsel * 4 * sl->sn.nsens / 256 >= 0x7fffffffLL) return CRT_ERR_UNSUPPORTED;
   return CRT_OK;
 }
-int launch_sens_finish(const SensArgs& sn, long long nv, int nslice, int per, int nb, int nsel, hipStream_t s);
-inline int sens_finish(const SensLaunch* sl, const LevSlices& ls, long long nv, int nb, int nsel, hipStream_t s) {
-  return ls.nslice > 1 ? launch_sens_finish(sl->sn, nv, ls.nslice, ls.per, nb, nsel, s) : (int)CRT_OK;
+// mask (skip != nullptr): the masked finish kernel; nt: the sun states per column (the mask is indexed by the column v / nt)
+int launch_sens_finish(const SensArgs& sn, long long nv, int nslice, int per, int nb, int nsel, hipStream_t s, ColMask mask = {}, int nt = 1);
+inline int sens_finish(const SensLaunch* sl, const LevSlices& ls, long long nv, int nb, int nsel, hipStream_t s, int nt = 1) {
+  return ls.nslice > 1 ? launch_sens_finish(sl->sn, nv, ls.nslice, ls.per, nb, nsel, s, sl->mask, nt) : (int)CRT_OK;
 }
 
 // (launch_sens_finish, sensor.hip: adds the slice partial sums of sens_row in ascending slice order; nv = ncol, series: ncol * nt)
@@ -1074,7 +1087,7 @@ inline size_t sensjac_part_bytes(int ncol, int nb, int nsel, int nsens, int npar
 // sr: nullptr = k_sens_jac; else k_sens_jac_series on the same slices (crt1d_hip_sensjac_series.h): a.ws / sr->can hold canopy records,
 // sn.o / sn.part are indexed by c * nt + t, side_leaf comes from launch_dleaf_side(.., canopy = true) and dg_at_psi is [ncol][nt]
 int launch_sens_jac(int scheme, const SolveArgs& a, const LevArgs& la, const SensJacArgs& ja, hipStream_t s, bool probe,
-                    const SeriesArgs* sr = nullptr, const double* dg_at_psi = nullptr);
+                    const SeriesArgs* sr = nullptr, const double* dg_at_psi = nullptr, ColMask mask = {});
 
 // launchers implemented in the .hip files
 int launch_colpre(const ColArgs& a, hipStream_t s);

@@ -94,7 +94,7 @@ int launch_lev_form(const F& f, const SolveArgs& a, const LevArgs& la, hipStream
   } else {
     st = !L.in_lds ? go(N, N, N) : go(N, N, Y);
   }
-  if (st == CRT_OK && sens) st = sens_finish(sl, ls, nv, a.nb, la.nsel, s);
+  if (st == CRT_OK && sens) st = sens_finish(sl, ls, nv, a.nb, la.nsel, s, sr ? sr->nt : 1);
   if (st == CRT_OK) f.note(L);  // (only a launch that succeeded is reported)
   return st;
 }
@@ -105,8 +105,8 @@ inline void lev_note(const LevLaunch& L, const char* kern, const char* name, boo
   const char* io = f32 ? " f32" : "";
   const int nsel = L.la.nsel, per = L.ls.per;
   if (L.sl)
-    note_kernel("%s%s_sens%s<%s>%s%s nsel=%d nsens=%d slice=%d%s", pre, kern, L.sr ? "_series" : "", name, io, mid, nsel, L.sl->sn.nsens, per,
-                L.ls.nslice > 1 ? " + k_sens_finish" : "");
+    note_kernel("%s%s_sens%s%s<%s>%s%s nsel=%d nsens=%d slice=%d%s", pre, kern, L.sr ? "_series" : "", L.sl->mask.skip ? "_masked" : "", name, io,
+                mid, nsel, L.sl->sn.nsens, per, L.ls.nslice <= 1 ? "" : L.sl->mask.skip ? " + k_sens_finish_masked" : " + k_sens_finish");
   else if (L.sr)
     note_kernel("%s%s_series<%s>%s%s nsel=%d slice=%d nt=%d", pre, kern, name, io, mid, nsel, per, L.sr->nt);
   else

@@ -6,6 +6,7 @@
 //  k_lm_covariance   one wave per column: the inverse of the stored normal matrix by the same scaled Cholesky
 //
 // No kernel here reads or writes outside [ncol] x its own row lengths: every index is bounded by a loop over the sizes the entry checked.
+#include "crt1d_hip_masked.h"
 #include "crt1d_hip_retrieve.h"
 #include "crt_internal.hpp"
 
@@ -114,6 +115,14 @@ __device__ inline void cholesky_solve(const double* M, int n, double* x) {
   }
 }
 
+// What THE STEP, item 1, is made of -- shared by k_lm_step and k_lm_decide (include_mask/crt1d_hip_masked.h), so that the cost the two form
+// is one computation: the weight of a row, its weighted residual (a skipped row: +0) and one extension of a running sum by one product.
+// Every operation is a separately rounded fp64 one (-ffp-contract=off).  The weighted residual of a prior row, one subtraction and one
+// product, is written out in both kernels: behind a function of its own it moved k_lm_step's device code, which is held to what it was.
+__device__ __forceinline__ double lm_row_weight(const LmBlock& B, long long o) { return B.is ? B.is[o] : 1.0; }
+__device__ __forceinline__ double lm_row_residual(const LmBlock& B, long long o, double s) { return s != 0.0 ? (B.f[o] - B.y[o]) * s : 0.0; }
+__device__ __forceinline__ double lm_extend(double acc, double x, double y) { return acc + x * y; }
+
 __global__ __launch_bounds__(LM_WAVE) void k_lm_step(LmArgs a) {
   __shared__ double v[LM_WAVE * MAXA];  // the staged rows (w_o0 .. w_o,npar-1, r_o)
   __shared__ double sflag[LM_WAVE];     // inv_sigma of the staged rows; 0 = skipped (staged as a row of +0)
@@ -141,8 +150,8 @@ __global__ __launch_bounds__(LM_WAVE) void k_lm_step(LmArgs a) {
       double s = 0.0;
       if (lane < n) {
         const long long o = row0 + base + lane;
-        s = B.is ? B.is[o] : 1.0;
-        v[lane * na + npar] = s != 0.0 ? (B.f[o] - B.y[o]) * s : 0.0;
+        s = lm_row_weight(B, o);
+        v[lane * na + npar] = lm_row_residual(B, o, s);
       }
       sflag[lane] = s;
       __syncthreads();
@@ -158,8 +167,8 @@ __global__ __launch_bounds__(LM_WAVE) void k_lm_step(LmArgs a) {
 #pragma unroll 4
       for (int o = 0; o < n; ++o) {
         const double* const r = v + o * na;
-        acc0 = acc0 + r[i0] * r[j0];
-        acc1 = acc1 + r[i1] * r[j1];
+        acc0 = lm_extend(acc0, r[i0], r[j0]);
+        acc1 = lm_extend(acc1, r[i1], r[j1]);
       }
     }
   }
@@ -171,12 +180,12 @@ __global__ __launch_bounds__(LM_WAVE) void k_lm_step(LmArgs a) {
       if (has0) {
         if (i0 == k && j0 == k) acc0 = acc0 + s * s;
         else if (i0 == npar && j0 == k) acc0 = acc0 + s * d;
-        else if (i0 == npar && j0 == npar) acc0 = acc0 + d * d;
+        else if (i0 == npar && j0 == npar) acc0 = lm_extend(acc0, d, d);
       }
       if (has1) {
         if (i1 == k && j1 == k) acc1 = acc1 + s * s;
         else if (i1 == npar && j1 == k) acc1 = acc1 + s * d;
-        else if (i1 == npar && j1 == npar) acc1 = acc1 + d * d;
+        else if (i1 == npar && j1 == npar) acc1 = lm_extend(acc1, d, d);
       }
     }
   }
@@ -243,6 +252,48 @@ __global__ __launch_bounds__(LM_WAVE) void k_lm_step(LmArgs a) {
     S.status[c] = status;
     if (accept) S.naccept[c] += 1;
     else if (status != CRT_LM_FAILED_START) S.nreject[c] += 1;
+  }
+}
+
+// crt_hip_lm_decide_f64 (include_mask/crt1d_hip_masked.h): the cost entry of k_lm_step alone -- the running sum of r_o * r_o over the rows
+// of block 0, 1, ... in ascending order, then d_k * d_k over the prior rows, extended by the functions k_lm_step extends it with -- and
+// the decision k_lm_step will take from it.  One wave per column; every lane forms the same sum from the residuals staged in LDS, lane 0
+// stores.  J is never read, no state is written; a column that is not running is skipped and its cost_t keeps its bits.
+__global__ __launch_bounds__(LM_WAVE) void k_lm_decide(LmArgs a, int32_t* __restrict__ skip_jac, double* __restrict__ cost_t) {
+  __shared__ double rr[LM_WAVE];  // the weighted residuals of the staged rows (a skipped row: +0)
+  const long long c = blockIdx.x;
+  const int lane = threadIdx.x, npar = a.npar;
+  if (a.st.status[c] != CRT_LM_RUNNING) {  // (the whole wave, before any barrier)
+    if (lane == 0) skip_jac[c] = 1;
+    return;
+  }
+  double acc = 0.0;
+  for (int q = 0; q < a.nblk; ++q) {
+    const LmBlock& B = a.blk[q];
+    const long long row0 = c * B.nrow;
+    for (int base = 0; base < B.nrow; base += LM_WAVE) {
+      const int n = min(LM_WAVE, B.nrow - base);
+      __syncthreads();  // the previous rows are consumed
+      if (lane < n) {
+        const long long o = row0 + base + lane;
+        rr[lane] = lm_row_residual(B, o, lm_row_weight(B, o));
+      }
+      __syncthreads();
+      for (int o = 0; o < n; ++o) acc = lm_extend(acc, rr[o], rr[o]);
+    }
+  }
+  if (a.isp) {
+    for (int k = 0; k < npar; ++k) {
+      const double s = a.isp[c * npar + k];
+      if (s == 0.0) continue;
+      const double d = (a.st.p_trial[c * npar + k] - a.prior[c * npar + k]) * s;  // (k_lm_step's line: see above)
+      acc = lm_extend(acc, d, d);
+    }
+  }
+  if (lane == 0) {
+    const double ct = 0.5 * acc;
+    cost_t[c] = ct;
+    skip_jac[c] = ct < a.st.cost[c] ? 0 : 1;  // (NaN: skip)
   }
 }
 
@@ -313,7 +364,8 @@ int crt_hip_retrieve_apply_f64(const crt_retrieve_apply* ap, const crt_optics_di
   return st;
 }
 
-int crt_hip_lm_step_f64(const crt_lm_problem* prob, const crt_lm_obs* obs, int32_t nblk, const crt_lm_state* state, crt_stream_t stream) {
+// the argument checks of crt_hip_lm_step_f64 and the kernel's argument block (crt_hip_lm_decide_f64 shares both)
+static int lm_step_args(const crt_lm_problem* prob, const crt_lm_obs* obs, int32_t nblk, const crt_lm_state* state, LmArgs& a) {
   if (!prob || !obs || !state) return CRT_ERR_BAD_ARG;
   if (prob->ncol < 1 || prob->npar < 1 || prob->npar > CRT_RETRIEVE_MAX_NPAR || nblk < 1 || nblk > CRT_LM_MAX_BLOCKS) return CRT_ERR_BAD_ARG;
   if (!(prob->lam_up > 1.0) || !(prob->lam_down > 0.0 && prob->lam_down <= 1.0)) return CRT_ERR_BAD_ARG;
@@ -322,7 +374,7 @@ int crt_hip_lm_step_f64(const crt_lm_problem* prob, const crt_lm_obs* obs, int32
   if (!state->p || !state->p_trial || !state->cost || !state->lam || !state->A || !state->g || !state->status || !state->naccept ||
       !state->nreject)
     return CRT_ERR_BAD_ARG;
-  LmArgs a = {};
+  a = {};
   for (int q = 0; q < nblk; ++q) {
     if (obs[q].nrow < 1 || !obs[q].f || !obs[q].J || !obs[q].y) return CRT_ERR_BAD_ARG;
     a.blk[q] = LmBlock{obs[q].f, obs[q].J, obs[q].y, obs[q].inv_sigma, obs[q].nrow};
@@ -332,8 +384,24 @@ int crt_hip_lm_step_f64(const crt_lm_problem* prob, const crt_lm_obs* obs, int32
   a.xtol = prob->xtol, a.ftol = prob->ftol;
   a.lo = prob->lo, a.hi = prob->hi, a.prior = prob->prior, a.isp = prob->inv_sigma_prior;
   a.st = *state;
+  return CRT_OK;
+}
+
+int crt_hip_lm_step_f64(const crt_lm_problem* prob, const crt_lm_obs* obs, int32_t nblk, const crt_lm_state* state, crt_stream_t stream) {
+  LmArgs a;
+  if (const int st = lm_step_args(prob, obs, nblk, state, a)) return st;
   const int st = launch_kernel(k_lm_step, dim3(prob->ncol), LM_WAVE, 0, static_cast<hipStream_t>(stream), a);
   if (st == CRT_OK) note_kernel("k_lm_step npar=%d nblk=%d", prob->npar, nblk);
+  return st;
+}
+
+int crt_hip_lm_decide_f64(const crt_lm_problem* prob, const crt_lm_obs* obs, int32_t nblk, const crt_lm_state* state, int32_t* skip_jac,
+                          double* cost_t, crt_stream_t stream) {
+  LmArgs a;
+  if (const int st = lm_step_args(prob, obs, nblk, state, a)) return st;
+  if (!skip_jac || !cost_t) return CRT_ERR_BAD_ARG;
+  const int st = launch_kernel(k_lm_decide, dim3(prob->ncol), LM_WAVE, 0, static_cast<hipStream_t>(stream), a, skip_jac, cost_t);
+  if (st == CRT_OK) note_kernel("k_lm_decide npar=%d nblk=%d", prob->npar, nblk);
   return st;
 }
 

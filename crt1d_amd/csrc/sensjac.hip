@@ -218,8 +218,11 @@ __global__ __launch_bounds__(SENSJAC_BLOCK) void k_sens_jac_series(SolveArgs a, 
 }
 
 // One thread per output element (c, r, s, par, q): the partial sums of the slices that meet the support of sensor band s, added in
-// ascending slice order -- the slices sens_fold_rows skipped are skipped here, so nothing unwritten is read.
-__global__ __launch_bounds__(256) void k_sens_jac_finish(SensArgs sn, long long ncol, int nslice, int per, int nb, int nsel, int npar) {
+// ascending slice order -- the slices sens_fold_rows skipped are skipped here, so nothing unwritten is read.  MASKED: an element of a
+// skipped column (v / nt) keeps its bits, and its slice sums are not read.
+template <bool MASKED>
+__device__ __forceinline__ void sens_jac_finish_body(const SensArgs& sn, long long ncol, int nslice, int per, int nb, int nsel, int npar, ColMask m,
+                                                     int nt) {
   const int nsens = sn.nsens;
   const long long n = ncol * nsel * nsens * npar * 4;
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -229,6 +232,8 @@ __global__ __launch_bounds__(256) void k_sens_jac_finish(SensArgs sn, long long 
   const int s = (int)((i / (4LL * npar)) % nsens);
   const int r = (int)((i / (4LL * npar * nsens)) % nsel);
   const long long v = i / (4LL * npar * nsens * nsel);
+  if constexpr (MASKED)
+    if (col_skipped(m, (int)(v / nt))) return;
   double* const o = sn.o[q];
   if (!o) return;
   const int f = sn.first[s], e = f + sn.count[s];
@@ -244,10 +249,48 @@ __global__ __launch_bounds__(256) void k_sens_jac_finish(SensArgs sn, long long 
   o[((v * nsel + r) * nsens + s) * npar + par] = z;
 }
 
+__global__ __launch_bounds__(256) void k_sens_jac_finish(SensArgs sn, long long ncol, int nslice, int per, int nb, int nsel, int npar) {
+  sens_jac_finish_body<false>(sn, ncol, nslice, per, nb, nsel, npar, ColMask{}, 1);
+}
+
+// ---- the masked forms (include_mask/crt1d_hip_masked.h): every workgroup of a skipped column returns before it reads anything of the
+// column and before any barrier (the test is workgroup-uniform: the column is blockIdx.x on both grids); an evaluated column runs the body
+// of its plain sibling, so its bits are the sibling's.
+template <class G, bool BL>
+__global__ __launch_bounds__(SENSJAC_BLOCK) void k_sens_jac_masked(SolveArgs a, LevArgs la, SensJacArgs ja, int per, int R, ColMask m) {
+  extern __shared__ double rows[];  // [nsel][R][blockDim.x]
+  const int c = blockIdx.x;
+  if (col_skipped(m, c)) return;
+  sens_jac_body<G, BL>(a, la, ja, per, R, c, blockIdx.y, gridDim.y, c, RecStep{a.ws + (long long)c * a.reclen, a.nz}, rows);
+}
+
+template <class G, bool BL>
+__global__ __launch_bounds__(SENSJAC_BLOCK) void k_sens_jac_series_masked(SolveArgs a, LevArgs la, SensJacArgs ja, SeriesArgs sr,
+                                                                          const double* __restrict__ dg_at_psi, int per, int R, int nslice,
+                                                                          ColMask m) {
+  extern __shared__ double rows[];  // [nsel][R][blockDim.x]
+  const int c = blockIdx.x;
+  if (col_skipped(m, c)) return;
+  const int zt = blockIdx.z / nslice, slice = blockIdx.z - zt * nslice;
+  const long long tl = (long long)zt * gridDim.y + blockIdx.y;
+  if (tl >= sr.nt) return;  // (whole workgroup, before any barrier)
+  const long long v = (long long)c * sr.nt + tl;
+  const long long din = (long long)c * sr.col_stride + tl * a.nb - (long long)c * a.col_stride;
+  a.I_dr0 = static_cast<const double*>(sr.I_dr0) + din;
+  a.I_df0 = static_cast<const double*>(sr.I_df0) + din;
+  const RecSeries rc = {sr.can + (long long)c * sr.canlen, sr.sun + v * sr.sunlen, dg_at_psi + v, sr.scheme, sr.nz};
+  sens_jac_body<G, BL>(a, la, ja, per, R, c, slice, nslice, v, rc, rows);
+}
+
+__global__ __launch_bounds__(256) void k_sens_jac_finish_masked(SensArgs sn, long long ncol, int nslice, int per, int nb, int nsel, int npar,
+                                                                int nt, ColMask m) {
+  sens_jac_finish_body<true>(sn, ncol, nslice, per, nb, nsel, npar, m, nt);
+}
+
 // sr: nullptr = the per-step kernel; else the series kernel on the same slices (dg_at_psi [ncol][nt]: the series tangent, or nullptr)
 template <class G, bool BL = false>
 int launch_sens_jac_closed(const SolveArgs& a, const LevArgs& la, const SensJacArgs& ja, hipStream_t s, bool probe, const SeriesArgs* sr,
-                           const double* dg_at_psi) {
+                           const double* dg_at_psi, ColMask m) {
   const int npar = ja.ntan + ja.lai + ja.leaf, nsens = ja.sn.nsens;
   const LevSlices ls = sensjac_slices(a.nb, la.nsel, npar);
   if (ls.nslice == 0 || ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
@@ -259,17 +302,27 @@ int launch_sens_jac_closed(const SolveArgs& a, const LevArgs& la, const SensJacA
   if (probe) return CRT_OK;
   const int R = sensjac_rows(ja.ntan);
   const size_t sh = (size_t)la.nsel * R * ls.nthr * sizeof(double);  // (<= the bound of sensjac_slices: ntan <= npar)
-  int st = sr ? launch_kernel(k_sens_jac_series<G, BL>, grid, ls.nthr, sh, s, a, la, ja, *sr, dg_at_psi, ls.per, R, ls.nslice)
-              : launch_kernel(k_sens_jac<G, BL>, grid, ls.nthr, sh, s, a, la, ja, ls.per, R);
   const bool fin = ls.nslice > 1;
-  if (st == CRT_OK && fin)
-    st = launch_kernel(k_sens_jac_finish, dim3((unsigned)nfin), 256, 0, s, ja.sn, nv, ls.nslice, ls.per, a.nb, la.nsel, npar);
+  int st;
+  if (m.skip) {
+    st = sr ? launch_kernel(k_sens_jac_series_masked<G, BL>, grid, ls.nthr, sh, s, a, la, ja, *sr, dg_at_psi, ls.per, R, ls.nslice, m)
+            : launch_kernel(k_sens_jac_masked<G, BL>, grid, ls.nthr, sh, s, a, la, ja, ls.per, R, m);
+    if (st == CRT_OK && fin)
+      st = launch_kernel(k_sens_jac_finish_masked, dim3((unsigned)nfin), 256, 0, s, ja.sn, nv, ls.nslice, ls.per, a.nb, la.nsel, npar,
+                         sr ? sr->nt : 1, m);
+  } else {
+    st = sr ? launch_kernel(k_sens_jac_series<G, BL>, grid, ls.nthr, sh, s, a, la, ja, *sr, dg_at_psi, ls.per, R, ls.nslice)
+            : launch_kernel(k_sens_jac<G, BL>, grid, ls.nthr, sh, s, a, la, ja, ls.per, R);
+    if (st == CRT_OK && fin)
+      st = launch_kernel(k_sens_jac_finish, dim3((unsigned)nfin), 256, 0, s, ja.sn, nv, ls.nslice, ls.per, a.nb, la.nsel, npar);
+  }
   if (st == CRT_OK) {
-    const char* const f = fin ? " + k_sens_jac_finish" : "";
+    const char* const f = !fin ? "" : m.skip ? " + k_sens_jac_finish_masked" : " + k_sens_jac_finish";
+    const char* const mk = m.skip ? "_masked" : "";
     if (sr)
-      note_kernel("k_sens_jac_series<%s> nt=%d nsel=%d nsens=%d npar=%d slice=%d%s", G::J::NAME, sr->nt, la.nsel, nsens, npar, ls.per, f);
+      note_kernel("k_sens_jac_series%s<%s> nt=%d nsel=%d nsens=%d npar=%d slice=%d%s", mk, G::J::NAME, sr->nt, la.nsel, nsens, npar, ls.per, f);
     else
-      note_kernel("k_sens_jac<%s> nsel=%d nsens=%d npar=%d slice=%d%s", G::J::NAME, la.nsel, nsens, npar, ls.per, f);
+      note_kernel("k_sens_jac%s<%s> nsel=%d nsens=%d npar=%d slice=%d%s", mk, G::J::NAME, la.nsel, nsens, npar, ls.per, f);
   }
   return st;
 }
@@ -277,12 +330,12 @@ int launch_sens_jac_closed(const SolveArgs& a, const LevArgs& la, const SensJacA
 }  // namespace
 
 int launch_sens_jac(int scheme, const SolveArgs& a, const LevArgs& la, const SensJacArgs& ja, hipStream_t s, bool probe, const SeriesArgs* sr,
-                    const double* dg_at_psi) {
+                    const double* dg_at_psi, ColMask m) {
   switch (scheme) {
-    case CRT_SCHEME_2S: return launch_sens_jac_closed<S2s>(a, la, ja, s, probe, sr, dg_at_psi);
-    case CRT_SCHEME_BL: return launch_sens_jac_closed<SBl, true>(a, la, ja, s, probe, sr, dg_at_psi);
-    case CRT_SCHEME_G77: return launch_sens_jac_closed<SG77<false>>(a, la, ja, s, probe, sr, dg_at_psi);
-    case CRT_SCHEME_BF: return launch_sens_jac_closed<SG77<true>>(a, la, ja, s, probe, sr, dg_at_psi);
+    case CRT_SCHEME_2S: return launch_sens_jac_closed<S2s>(a, la, ja, s, probe, sr, dg_at_psi, m);
+    case CRT_SCHEME_BL: return launch_sens_jac_closed<SBl, true>(a, la, ja, s, probe, sr, dg_at_psi, m);
+    case CRT_SCHEME_G77: return launch_sens_jac_closed<SG77<false>>(a, la, ja, s, probe, sr, dg_at_psi, m);
+    case CRT_SCHEME_BF: return launch_sens_jac_closed<SG77<true>>(a, la, ja, s, probe, sr, dg_at_psi, m);
     default: return CRT_ERR_UNSUPPORTED;
   }
 }

@@ -7,7 +7,8 @@ namespace {
 
 // One thread per output element (v, r, q, s): the partial sums of the slices that meet the support of sensor band s, added in ascending
 // slice order -- the slices a workgroup skipped in sens_row are skipped here, so nothing unwritten is read.
-__global__ __launch_bounds__(256) void k_sens_finish(SensArgs sn, long long nv, int nslice, int per, int nb, int nsel) {
+template <bool MASKED>
+__device__ __forceinline__ void sens_finish_body(const SensArgs& sn, long long nv, int nslice, int per, int nb, int nsel, ColMask m, int nt) {
   const int nsens = sn.nsens;
   const long long n = nv * nsel * 4 * nsens;
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -16,6 +17,8 @@ __global__ __launch_bounds__(256) void k_sens_finish(SensArgs sn, long long nv, 
   const int q = (int)((i / nsens) % 4);
   const int r = (int)((i / (4LL * nsens)) % nsel);
   const long long v = i / (4LL * nsens * nsel);
+  if constexpr (MASKED)
+    if (col_skipped(m, (int)(v / nt))) return;  // (before the slice sums of the column are read)
   double* const o = sn.o[q];
   if (!o) return;
   const int f = sn.first[s], e = f + sn.count[s];
@@ -31,12 +34,23 @@ __global__ __launch_bounds__(256) void k_sens_finish(SensArgs sn, long long nv, 
   o[(v * nsel + r) * nsens + s] = z;
 }
 
+// the masked entries (include_mask/crt1d_hip_masked.h): an element of a skipped column (v / nt) keeps its bits, and its slice sums are not
+// read.  (In front of k_sens_finish, which stays the last kernel of the unit.)
+__global__ __launch_bounds__(256) void k_sens_finish_masked(SensArgs sn, long long nv, int nslice, int per, int nb, int nsel, int nt, ColMask m) {
+  sens_finish_body<true>(sn, nv, nslice, per, nb, nsel, m, nt);
+}
+
+__global__ __launch_bounds__(256) void k_sens_finish(SensArgs sn, long long nv, int nslice, int per, int nb, int nsel) {
+  sens_finish_body<false>(sn, nv, nslice, per, nb, nsel, ColMask{}, 1);
+}
+
 }  // namespace
 
-int launch_sens_finish(const SensArgs& sn, long long nv, int nslice, int per, int nb, int nsel, hipStream_t s) {
+int launch_sens_finish(const SensArgs& sn, long long nv, int nslice, int per, int nb, int nsel, hipStream_t s, ColMask mask, int nt) {
   const long long n = nv * nsel * 4 * sn.nsens;
   const long long nblk = (n + 255) / 256;
   if (nblk > 0x7fffffffLL) return CRT_ERR_UNSUPPORTED;
+  if (mask.skip) return launch_kernel(k_sens_finish_masked, dim3((unsigned)nblk), 256, 0, s, sn, nv, nslice, per, nb, nsel, nt, mask);
   return launch_kernel(k_sens_finish, dim3((unsigned)nblk), 256, 0, s, sn, nv, nslice, per, nb, nsel);
 }
 

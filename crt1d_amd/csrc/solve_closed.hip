@@ -1292,6 +1292,29 @@ __global__ __launch_bounds__(MAXT) void k_lev_sens_series(SolveArgs a, LevArgs l
   });
 }
 
+// The sensor forms behind a column mask (include_mask/crt1d_hip_masked.h; 2s, bl, g77, bf in float64): every workgroup of a skipped column
+// returns before it reads the column's record -- the test is workgroup-uniform (the column is blockIdx.x on both grids) and comes before any
+// barrier --, an evaluated column runs the body of its plain sibling.
+template <class S, int MAXT>
+__global__ __launch_bounds__(MAXT) void k_lev_sens_masked(SolveArgs a, LevArgs la, SensArgs sn, int per, int off_st, ColMask m) {
+  extern __shared__ double lds[];
+  if (col_skipped(m, blockIdx.x)) return;
+  const double* rec = a.ws + (long long)blockIdx.x * a.reclen;
+  for (int i = threadIdx.x; i < a.reclen; i += blockDim.x) lds[i] = rec[i];
+  __syncthreads();
+  lev_body<S, double, true>(a, la, per, lds, blockIdx.y, 0, &sn, lds + off_st, gridDim.y, blockIdx.x);
+}
+
+template <class S, int MAXT>
+__global__ __launch_bounds__(MAXT) void k_lev_sens_series_masked(SolveArgs a, LevArgs la, SensArgs sn, SeriesArgs sr, int per, int off_st,
+                                                                 int nslice, ColMask m) {
+  extern __shared__ double lds[];
+  if (col_skipped(m, blockIdx.x)) return;
+  series_lev_step<double>(a, la, sr, nslice, lds, [&](const SolveArgs& at, int slice, long long, long long v) {
+    lev_body<S, double, true>(at, la, per, lds, slice, 0, &sn, lds + off_st, nslice, v);
+  });
+}
+
 // the closed family's description of the level launch (launch_lev_form, launch_forms.hpp).  The record is all the LDS a workgroup needs
 // (the sensor forms add one staging row behind it, at off_st): no narrowing of the slices.  Deeper columns read their record from the
 // workspace (every nz the profile path serves): the per-step form only.
@@ -1306,6 +1329,16 @@ struct ClosedLev {
   template <int MAXT, bool SER, bool SENS, bool IN_LDS>
   int launch(const LevLaunch& L) const {
     const LevSlices& ls = L.ls;
+    if constexpr (SENS && sizeof(TIO) == 8 && !std::is_same_v<S, Sch4s>) {  // (the masked entries: float64, not 4s)
+      if (L.sl->mask.skip) {
+        const ColMask m = L.sl->mask;
+        if constexpr (SER)
+          return launch_kernel(k_lev_sens_series_masked<S, MAXT>, L.grid, ls.nthr, L.sh, L.s, a, L.la, L.sl->sn, *L.sr, ls.per, off_st(),
+                               ls.nslice, m);
+        else
+          return launch_kernel(k_lev_sens_masked<S, MAXT>, L.grid, ls.nthr, L.sh, L.s, a, L.la, L.sl->sn, ls.per, off_st(), m);
+      }
+    }
     if constexpr (SER && SENS)
       return launch_kernel(k_lev_sens_series<S, MAXT>, L.grid, ls.nthr, L.sh, L.s, a, L.la, L.sl->sn, *L.sr, ls.per, off_st(), ls.nslice);
     else if constexpr (SENS)

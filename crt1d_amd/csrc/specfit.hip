@@ -53,13 +53,17 @@ __global__ __launch_bounds__(SPEC_BLOCK) void k_spec_normal(SolveArgs a, LevArgs
   spec_normal_body<G, BL, false>(a, la, sp, per, c, blockIdx.y, c, SpecRecStep{a.ws + (long long)c * a.reclen, a.nz}, 0);
 }
 
-// One thread per (column, entry): the slice sums in ascending slice order, starting from slice 0's bits.
-__global__ __launch_bounds__(256) void k_spec_normal_finish(long long ncol, int nslice, int npar, const double* __restrict__ part,
-                                                             double* __restrict__ A, double* __restrict__ g, double* __restrict__ c2) {
+// One thread per (column, entry): the slice sums in ascending slice order, starting from slice 0's bits.  MASKED: an entry of a skipped
+// column keeps its bits, and its slice sums are not read.
+template <bool MASKED>
+__device__ __forceinline__ void spec_finish_body(long long ncol, int nslice, int npar, const double* __restrict__ part, double* __restrict__ A,
+                                                 double* __restrict__ g, double* __restrict__ c2, ColMask m) {
   const int ntri = npar * (npar + 1) / 2, nent = (npar + 1) * (npar + 2) / 2;
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ncol * nent) return;
   const long long c = i / nent;
+  if constexpr (MASKED)
+    if (col_skipped(m, (int)c)) return;
   const int e = (int)(i - c * nent);
   const double* p = part + c * nslice * nent + e;
   double s = p[0];
@@ -69,22 +73,49 @@ __global__ __launch_bounds__(256) void k_spec_normal_finish(long long ncol, int 
   else c2[c] = s;
 }
 
+__global__ __launch_bounds__(256) void k_spec_normal_finish(long long ncol, int nslice, int npar, const double* __restrict__ part,
+                                                             double* __restrict__ A, double* __restrict__ g, double* __restrict__ c2) {
+  spec_finish_body<false>(ncol, nslice, npar, part, A, g, c2, ColMask{});
+}
+
+// ---- the masked forms (include_mask/crt1d_hip_masked.h): every workgroup of a skipped column returns before it reads anything of the
+// column and before any barrier; an evaluated column runs the body of its plain sibling.
+template <class G, bool BL>
+__global__ __launch_bounds__(SPEC_BLOCK) void k_spec_normal_masked(SolveArgs a, LevArgs la, SpecArgs sp, int per, ColMask m) {
+  const int c = blockIdx.x;
+  if (col_skipped(m, c)) return;
+  spec_normal_body<G, BL, false>(a, la, sp, per, c, blockIdx.y, c, SpecRecStep{a.ws + (long long)c * a.reclen, a.nz}, 0);
+}
+
+__global__ __launch_bounds__(256) void k_spec_normal_finish_masked(long long ncol, int nslice, int npar, const double* __restrict__ part,
+                                                                    double* __restrict__ A, double* __restrict__ g, double* __restrict__ c2,
+                                                                    ColMask m) {
+  spec_finish_body<true>(ncol, nslice, npar, part, A, g, c2, m);
+}
+
 template <class G, bool BL = false>
-int launch_spec_closed(const SolveArgs& a, const LevArgs& la, const SpecArgs& sp, hipStream_t s, bool probe) {
+int launch_spec_closed(const SolveArgs& a, const LevArgs& la, const SpecArgs& sp, hipStream_t s, bool probe, ColMask m) {
   const int npar = sp.ntan + sp.lai + sp.leaf;
   const LevSlices ls = spec_slices(a.nb, la.nsel, sp.nkey, npar);
   if (ls.nslice == 0 || ls.nslice > 65535) return CRT_ERR_UNSUPPORTED;
   if (probe) return CRT_OK;
   const size_t sh = spec_rows(la.nsel, sp.nkey, npar) * ls.nthr * sizeof(double);  // (<= the bound of spec_slices)
-  int st = launch_kernel(k_spec_normal<G, BL>, dim3(a.ncol, ls.nslice), ls.nthr, sh, s, a, la, sp, ls.per);
   const bool fin = ls.nslice > 1;
-  if (st == CRT_OK && fin) {
-    const long long n = (long long)a.ncol * spec_nent(npar);  // (< 2^31 * 66: the grid fits)
-    st = launch_kernel(k_spec_normal_finish, dim3((unsigned)((n + 255) / 256)), 256, 0, s, (long long)a.ncol, ls.nslice, npar, sp.part, sp.A,
-                       sp.g, sp.c2);
+  const long long n = (long long)a.ncol * spec_nent(npar);  // (< 2^31 * 66: the grid fits)
+  const dim3 gfin((unsigned)((n + 255) / 256));
+  int st;
+  if (m.skip) {
+    st = launch_kernel(k_spec_normal_masked<G, BL>, dim3(a.ncol, ls.nslice), ls.nthr, sh, s, a, la, sp, ls.per, m);
+    if (st == CRT_OK && fin)
+      st = launch_kernel(k_spec_normal_finish_masked, gfin, 256, 0, s, (long long)a.ncol, ls.nslice, npar, sp.part, sp.A, sp.g, sp.c2, m);
+  } else {
+    st = launch_kernel(k_spec_normal<G, BL>, dim3(a.ncol, ls.nslice), ls.nthr, sh, s, a, la, sp, ls.per);
+    if (st == CRT_OK && fin)
+      st = launch_kernel(k_spec_normal_finish, gfin, 256, 0, s, (long long)a.ncol, ls.nslice, npar, sp.part, sp.A, sp.g, sp.c2);
   }
   if (st == CRT_OK)
-    note_kernel("k_spec_normal<%s> nsel=%d nkey=%d npar=%d slice=%d%s", G::J::NAME, la.nsel, sp.nkey, npar, ls.per, fin ? " + k_spec_normal_finish" : "");
+    note_kernel("k_spec_normal%s<%s> nsel=%d nkey=%d npar=%d slice=%d%s", m.skip ? "_masked" : "", G::J::NAME, la.nsel, sp.nkey, npar, ls.per,
+                !fin ? "" : m.skip ? " + k_spec_normal_finish_masked" : " + k_spec_normal_finish");
   return st;
 }
 
@@ -255,12 +286,12 @@ __global__ __launch_bounds__(LM_WAVE) void k_lm_step_normal(LmNormalArgs a) {
 
 }  // namespace
 
-int launch_spec_normal(int scheme, const SolveArgs& a, const LevArgs& la, const SpecArgs& sp, hipStream_t s, bool probe) {
+int launch_spec_normal(int scheme, const SolveArgs& a, const LevArgs& la, const SpecArgs& sp, hipStream_t s, bool probe, ColMask m) {
   switch (scheme) {
-    case CRT_SCHEME_2S: return launch_spec_closed<P2s>(a, la, sp, s, probe);
-    case CRT_SCHEME_BL: return launch_spec_closed<PBl, true>(a, la, sp, s, probe);
-    case CRT_SCHEME_G77: return launch_spec_closed<PG77<false>>(a, la, sp, s, probe);
-    case CRT_SCHEME_BF: return launch_spec_closed<PG77<true>>(a, la, sp, s, probe);
+    case CRT_SCHEME_2S: return launch_spec_closed<P2s>(a, la, sp, s, probe, m);
+    case CRT_SCHEME_BL: return launch_spec_closed<PBl, true>(a, la, sp, s, probe, m);
+    case CRT_SCHEME_G77: return launch_spec_closed<PG77<false>>(a, la, sp, s, probe, m);
+    case CRT_SCHEME_BF: return launch_spec_closed<PG77<true>>(a, la, sp, s, probe, m);
     default: return CRT_ERR_UNSUPPORTED;
   }
 }

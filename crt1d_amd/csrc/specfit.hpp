@@ -41,7 +41,8 @@ inline size_t spec_part_bytes(int ncol, int nb, int nsel, int nkey, int npar) {
   return (size_t)ncol * (size_t)ls.nslice * spec_nent(npar) * sizeof(double);
 }
 // probe: return the status (CRT_OK / CRT_ERR_UNSUPPORTED) of the configuration without launching anything
-int launch_spec_normal(int scheme, const SolveArgs& a, const LevArgs& la, const SpecArgs& sp, hipStream_t s, bool probe);
+// m (skip != nullptr): the masked kernels of include_mask/crt1d_hip_masked.h
+int launch_spec_normal(int scheme, const SolveArgs& a, const LevArgs& la, const SpecArgs& sp, hipStream_t s, bool probe, ColMask m = {});
 
 // The sun-angle series (include/series/crt1d_hip_specfit_series.h; kernels in specfit_series.hip).  sp: y / is / fwd are indexed by
 // c * nt + t, A / g / c2 are the sums over t, part is [ncol][nt][nslice][nent] and ALWAYS there: the sum over t goes through it.
@@ -57,6 +58,6 @@ inline size_t spec_series_part_bytes(int ncol, int nb, int nsel, int nkey, int n
 }
 // a.ws / sr.can hold canopy records, side_leaf comes from launch_dleaf_side(.., canopy = true), dg_at_psi is [ncol][nt] (or nullptr)
 int launch_spec_normal_series(int scheme, const SolveArgs& a, const LevArgs& la, const SpecArgs& sp, const SpecSeriesOut& so,
-                              const SeriesArgs& sr, const double* dg_at_psi, hipStream_t s, bool probe);
+                              const SeriesArgs& sr, const double* dg_at_psi, hipStream_t s, bool probe, ColMask m = {});
 
 }  // namespace crt
