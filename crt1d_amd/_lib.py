@@ -619,15 +619,14 @@ LM_CHAIN_LDS_LIMIT = 160 * 1024  # CRT_LM_CHAIN_LDS_LIMIT
 
 
 def lm_chain_lds_bytes(nd, npar):
-    """``CRT_LM_CHAIN_LDS_BYTES(nd, npar)``: the dynamic LDS of one pixel of the chain kernels."""
-    return 8 * (nd * (2 * npar * npar + 4 * npar) + 4 * npar * npar + 64)
+    """``CRT_LM_CHAIN_LDS_BYTES(nd, npar)``: the dynamic LDS of one pixel of the chain entries, which is that of the shared-parameter
+    kernels with nothing shared."""
+    return lm_shared_lds_bytes(nd, npar, 0)
 
 
 def lm_chain_max_nd(npar):
     """``crt_hip_lm_chain_max_nd``: the largest ``nd`` whose LDS fits the limit; 0 for a refused ``npar``.  No library is loaded."""
-    if not 1 <= npar <= RETRIEVE_MAX_NPAR:
-        return 0
-    return (LM_CHAIN_LDS_LIMIT // 8 - 4 * npar * npar - 64) // (2 * npar * npar + 4 * npar)
+    return lm_shared_max_nd(npar, 0)
 
 
 class CrtLmChain(ctypes.Structure):

@@ -2336,12 +2336,12 @@ def _check_chain(chain, inv_sigma_chain, ncol, npar, shared=None):
     ncol = ncol if isinstance(ncol, int) else ncol.ncol
     if ncol % nd:
         raise ValueError(f"chain = {nd} dates does not divide ncol = {ncol}: the columns are (pixel, date) pairs, pixel-major")
-    if shared is None and nd > _lib.lm_chain_max_nd(npar):
-        raise ValueError(f"chain = {nd} dates is beyond the {_lib.lm_chain_max_nd(npar)} the chain kernel serves at npar = {npar}")
-    if shared is not None and nd > _lib.lm_shared_max_nd(npar, bin(shared).count("1")):
-        ns = bin(shared).count("1")
-        raise ValueError(f"chain = {nd} dates is beyond the {_lib.lm_shared_max_nd(npar, ns)} the shared-parameter kernel serves at "
-                         f"npar = {npar} with {ns} shared")
+    ns = 0 if shared is None else bin(shared).count("1")
+    limit = _lib.lm_shared_max_nd(npar, ns)
+    if nd > limit and shared is None:
+        raise ValueError(f"chain = {nd} dates is beyond the {limit} the chain kernel serves at npar = {npar}")
+    if nd > limit:
+        raise ValueError(f"chain = {nd} dates is beyond the {limit} the shared-parameter kernel serves at npar = {npar} with {ns} shared")
     npix = ncol // nd
     if inv_sigma_chain is None:
         raise ValueError("a chain needs inv_sigma_chain (nd - 1, npar) or (npix, nd - 1, npar)")
@@ -2494,8 +2494,8 @@ class _LmPlan:
                        "crt_hip_g_dparam_series_f64")
 
     def _step_chain(self, s):
-        """The closing call of a chained ``step()``: ``k_lm_step_chain`` (with ``shared``: ``k_lm_step_shared``) on the plan's one block of
-        sums."""
+        """The closing call of a chained ``step()``: ``crt_hip_lm_step_chain_f64`` (with ``shared``: ``crt_hip_lm_step_shared_f64``; one
+        kernel behind both) on the plan's one block of sums."""
         if self._shared is not None:
             _lib.check(self.lib.crt_hip_lm_step_shared_f64(ctypes.byref(self._chain), ctypes.byref(self._shared), ctypes.byref(self._prob),
                                                            self._blk, 1, ctypes.byref(self._state), s.cuda_stream), "crt_hip_lm_step_shared_f64")
@@ -2645,14 +2645,14 @@ class RetrievalPlan(_LmPlan):
     consecutive dates of a pixel are coupled by a random-walk prior with the weights ``inv_sigma_chain`` (``(p_{d+1} - p_d) *
     inv_sigma_chain[d]`` is a residual; 0: not coupled; fold the time gap in).  A date whose rows are all masked gets its value from
     its neighbours.  The last launch of :meth:`step` becomes two: ``k_lm_normal`` writes the sums ``k_lm_step`` would have formed,
-    ``k_lm_step_chain`` accepts or rejects, damps and solves the block-tridiagonal system of every pixel.  ``result()`` then gives
+    ``crt_hip_lm_step_chain_f64`` accepts or rejects, damps and solves the block-tridiagonal system of every pixel.  ``result()`` then gives
     ``p (npix, nd, npar)`` and per-pixel ``cost``, ``status``, ``lam`` and counters, ``covariance()`` the smoothed marginal covariances
     ``(npix, nd, npar, npar)``.  ``chain=None``: the plan as it always was, call for call.
 
     ``shared=`` (needs ``chain=``): the parameters that are constants of a pixel over its ``nd`` dates -- a sequence of names out of
     ``plan.params`` (``"lai"``, ``"leaf"``, ``"dir0"``.. or leaf-model names) or a boolean mask ``(npar,)`` (include_shared/
     crt1d_hip_lm_shared.h).  Such a parameter is ONE unknown of the pixel: the system has ``nd * nv + ns`` unknowns, the block-tridiagonal
-    matrix bordered by ``ns`` dense rows, and the closing launch is ``k_lm_step_shared`` in place of ``k_lm_step_chain`` (the number of
+    matrix bordered by ``ns`` dense rows, and the closing call is ``crt_hip_lm_step_shared_f64`` in place of ``crt_hip_lm_step_chain_f64`` (the number of
     launches is unchanged).  ``result()["p"]`` stays ``(npix, nd, npar)`` with the shared columns bitwise equal over the dates;
     ``inv_sigma_chain`` keeps its shape, its entries of shared parameters are not read.  ``p0`` / ``reset(p0)``: the shared entries of
     the dates after the first are overwritten with date 0's.  ``prior`` / ``inv_sigma_prior``: for a shared parameter the plan keeps date

@@ -9,11 +9,11 @@
 #include "crt1d_hip_masked.h"
 #include "crt1d_hip_retrieve.h"
 #include "crt_internal.hpp"
+#include "lm_common.hpp"
 
 namespace crt {
 namespace {
 
-constexpr int MAXP = CRT_RETRIEVE_MAX_NPAR;            // 10
 constexpr int MAXA = MAXP + 1;                         // a row of (w_o0 .. w_o,npar-1, r_o)
 constexpr int MAXENT = MAXA * (MAXA + 1) / 2;          // 66 entries of (A | g | 2 cost)
 constexpr int LM_WAVE = 64;                            // one wave per column; also the rows staged at a time
@@ -64,56 +64,6 @@ struct LmArgs {
   const double *lo, *hi, *prior, *isp;
   crt_lm_state st;
 };
-
-__device__ inline int tri(int i, int j) { return i * (i + 1) / 2 + j; }  // j <= i
-
-// entry e of the lower triangle of the (npar + 1) x (npar + 1) matrix of products, row by row -> (i, j), j <= i
-__device__ inline void tri_pair(int e, int& i, int& j) {
-  i = 0;
-  while ((i + 1) * (i + 2) / 2 <= e) ++i;
-  j = e - i * (i + 1) / 2;
-}
-
-// By ONE lane, on LDS: sc[k] = 1 / sqrt(A_kk) (dead: 1); M = (A_ij sc_i) sc_j + (dead ? 1 : lam) [i == j], lower triangle, replaced by its
-// Cholesky factor (left-looking, as batched.gauss_newton_step).  ent: the packed lower triangle of A.
-__device__ inline void scaled_cholesky(const double* ent, int n, double lam, double* M, double* sc, bool* dead) {
-  for (int k = 0; k < n; ++k) {
-    const double d = ent[tri(k, k)];
-    dead[k] = d <= 0.0;
-    sc[k] = dead[k] ? 1.0 : 1.0 / sqrt(d);
-  }
-  for (int i = 0; i < n; ++i)
-    for (int j = 0; j <= i; ++j) {
-      double m = (ent[tri(i, j)] * sc[i]) * sc[j];
-      if (i == j) m = m + (dead[i] ? 1.0 : lam);
-      M[i * MAXP + j] = m;
-    }
-  for (int j = 0; j < n; ++j) {
-    double s = 0.0;
-    for (int k = 0; k < j; ++k) s = s + M[j * MAXP + k] * M[j * MAXP + k];
-    const double d = sqrt(M[j * MAXP + j] - s);
-    M[j * MAXP + j] = d;
-    for (int i = j + 1; i < n; ++i) {
-      double t = 0.0;
-      for (int k = 0; k < j; ++k) t = t + M[i * MAXP + k] * M[j * MAXP + k];
-      M[i * MAXP + j] = (M[i * MAXP + j] - t) / d;
-    }
-  }
-}
-
-// L L^T x = x in place (x: LDS, n entries)
-__device__ inline void cholesky_solve(const double* M, int n, double* x) {
-  for (int j = 0; j < n; ++j) {
-    double s = 0.0;
-    for (int k = 0; k < j; ++k) s = s + M[j * MAXP + k] * x[k];
-    x[j] = (x[j] - s) / M[j * MAXP + j];
-  }
-  for (int j = n - 1; j >= 0; --j) {
-    double s = 0.0;
-    for (int k = j + 1; k < n; ++k) s = s + M[k * MAXP + j] * x[k];
-    x[j] = (x[j] - s) / M[j * MAXP + j];
-  }
-}
 
 // What THE STEP, item 1, is made of -- shared by k_lm_step and k_lm_decide (include_mask/crt1d_hip_masked.h), so that the cost the two form
 // is one computation: the weight of a row, its weighted residual (a skipped row: +0) and one extension of a running sum by one product.
@@ -366,14 +316,7 @@ int crt_hip_retrieve_apply_f64(const crt_retrieve_apply* ap, const crt_optics_di
 
 // the argument checks of crt_hip_lm_step_f64 and the kernel's argument block (crt_hip_lm_decide_f64 shares both)
 static int lm_step_args(const crt_lm_problem* prob, const crt_lm_obs* obs, int32_t nblk, const crt_lm_state* state, LmArgs& a) {
-  if (!prob || !obs || !state) return CRT_ERR_BAD_ARG;
-  if (prob->ncol < 1 || prob->npar < 1 || prob->npar > CRT_RETRIEVE_MAX_NPAR || nblk < 1 || nblk > CRT_LM_MAX_BLOCKS) return CRT_ERR_BAD_ARG;
-  if (!(prob->lam_up > 1.0) || !(prob->lam_down > 0.0 && prob->lam_down <= 1.0)) return CRT_ERR_BAD_ARG;
-  if (!(prob->lam_min >= 0.0) || !(prob->lam_max >= prob->lam_min) || !(prob->xtol >= 0.0) || !(prob->ftol >= 0.0)) return CRT_ERR_BAD_ARG;
-  if (!prob->prior != !prob->inv_sigma_prior) return CRT_ERR_BAD_ARG;
-  if (!state->p || !state->p_trial || !state->cost || !state->lam || !state->A || !state->g || !state->status || !state->naccept ||
-      !state->nreject)
-    return CRT_ERR_BAD_ARG;
+  if (!obs || !lm_problem_ok(prob, nblk, state)) return CRT_ERR_BAD_ARG;
   a = {};
   for (int q = 0; q < nblk; ++q) {
     if (obs[q].nrow < 1 || !obs[q].f || !obs[q].J || !obs[q].y) return CRT_ERR_BAD_ARG;

@@ -19,9 +19,10 @@
 //                        spec_block_sum (grad.hip's block_sum: butterfly, then the waves in ascending order) adds the lanes, thread 0 stores.  The 66 sums
 //                        of npar = 10 are never live together: no accumulator sits in a register across a pass.
 //  k_spec_normal_finish  several band slices: a thread per (column, entry) adds the slice sums in ascending order (k_grad_finish's rule).
-//  k_lm_step_normal      k_lm_step (retrieve.hip) with the sums supplied instead of rows.  The scaled Cholesky and the solve are a second copy
-//                        of retrieve.hip's: sharing them would have meant editing that unit, whose device code is held to what it is.
+//  k_lm_step_normal      k_lm_step (retrieve.hip) with the sums supplied instead of rows.  The scaled Cholesky and the solve are the ones
+//                        retrieve.hip uses (lm_common.hpp).
 // No atomics anywhere: a column's result does not depend on the batch or on another column's mask.
+#include "lm_common.hpp"
 #include "specfit_body.hpp"
 
 namespace crt {
@@ -32,19 +33,9 @@ struct PBl : SchBl {};
 template <bool BF>
 struct PG77 : SchG77<BF> {};
 
-constexpr int MAXP = CRT_RETRIEVE_MAX_NPAR;     // 10
 constexpr int MAXA = MAXP + 1;                  // (w_0 .. w_{npar-1}, r)
 constexpr int MAXENT = MAXA * (MAXA + 1) / 2;   // 66 entries of (A | g | c2)
 constexpr int LM_WAVE = 64;                     // one wave per column
-
-__device__ inline int tri(int i, int j) { return i * (i + 1) / 2 + j; }  // j <= i
-
-// entry e of the lower triangle of the (npar + 1) x (npar + 1) matrix of products, row by row -> (i, j), j <= i
-__device__ inline void tri_pair(int e, int& i, int& j) {
-  i = 0;
-  while ((i + 1) * (i + 2) / 2 <= e) ++i;
-  j = e - i * (i + 1) / 2;
-}
 
 // The body (specfit_body.hpp) on the record k_colpre wrote: one column and one band slice per workgroup.
 template <class G, bool BL>
@@ -122,63 +113,13 @@ int launch_spec_closed(const SolveArgs& a, const LevArgs& la, const SpecArgs& sp
 // ------------------------------------------------------------------------------------------
 // the step on supplied sums: k_lm_step of retrieve.hip, line by line, with the row loop replaced by the block loads
 
-struct NormalBlock {
-  const double *A, *g, *c2;
-};
-
 struct LmNormalArgs {
-  NormalBlock blk[CRT_LM_MAX_BLOCKS];
+  SumBlock blk[CRT_LM_MAX_BLOCKS];
   int nblk, npar;
   double lam_up, lam_down, lam_min, lam_max, xtol, ftol;
   const double *lo, *hi, *prior, *isp;
   crt_lm_state st;
 };
-
-// By ONE lane, on LDS: sc[k] = 1 / sqrt(A_kk) (dead: 1); M = (A_ij sc_i) sc_j + (dead ? 1 : lam) [i == j], lower triangle, replaced by its
-// Cholesky factor (left-looking, as batched.gauss_newton_step).  ent: the packed lower triangle of A.
-__device__ inline void scaled_cholesky(const double* ent, int n, double lam, double* M, double* sc, bool* dead) {
-  for (int k = 0; k < n; ++k) {
-    const double d = ent[tri(k, k)];
-    dead[k] = d <= 0.0;
-    sc[k] = dead[k] ? 1.0 : 1.0 / sqrt(d);
-  }
-  for (int i = 0; i < n; ++i)
-    for (int j = 0; j <= i; ++j) {
-      double m = (ent[tri(i, j)] * sc[i]) * sc[j];
-      if (i == j) m = m + (dead[i] ? 1.0 : lam);
-      M[i * MAXP + j] = m;
-    }
-  for (int j = 0; j < n; ++j) {
-    double s = 0.0;
-    for (int k = 0; k < j; ++k) s = s + M[j * MAXP + k] * M[j * MAXP + k];
-    const double d = sqrt(M[j * MAXP + j] - s);
-    M[j * MAXP + j] = d;
-    for (int i = j + 1; i < n; ++i) {
-      double t = 0.0;
-      for (int k = 0; k < j; ++k) t = t + M[i * MAXP + k] * M[j * MAXP + k];
-      M[i * MAXP + j] = (M[i * MAXP + j] - t) / d;
-    }
-  }
-}
-
-// L L^T x = x in place (x: LDS, n entries)
-__device__ inline void cholesky_solve(const double* M, int n, double* x) {
-  for (int j = 0; j < n; ++j) {
-    double s = 0.0;
-    for (int k = 0; k < j; ++k) s = s + M[j * MAXP + k] * x[k];
-    x[j] = (x[j] - s) / M[j * MAXP + j];
-  }
-  for (int j = n - 1; j >= 0; --j) {
-    double s = 0.0;
-    for (int k = j + 1; k < n; ++k) s = s + M[k * MAXP + j] * x[k];
-    x[j] = (x[j] - s) / M[j * MAXP + j];
-  }
-}
-
-// entry e of (A | g | c2) of column c in a block
-__device__ __forceinline__ double block_entry(const NormalBlock& B, long long c, int e, int ntri, int npar) {
-  return e < ntri ? B.A[c * ntri + e] : e < ntri + npar ? B.g[c * npar + e - ntri] : B.c2[c];
-}
 
 __global__ __launch_bounds__(LM_WAVE) void k_lm_step_normal(LmNormalArgs a) {
   __shared__ double ent[MAXENT + 2];  // (A | g | 2 cost)
@@ -304,18 +245,11 @@ extern "C" {
 
 int crt_hip_lm_step_normal_f64(const crt_lm_problem* prob, const crt_lm_normal_block* blocks, int32_t nblk, const crt_lm_state* state,
                                crt_stream_t stream) {
-  if (!prob || !blocks || !state) return CRT_ERR_BAD_ARG;
-  if (prob->ncol < 1 || prob->npar < 1 || prob->npar > CRT_RETRIEVE_MAX_NPAR || nblk < 1 || nblk > CRT_LM_MAX_BLOCKS) return CRT_ERR_BAD_ARG;
-  if (!(prob->lam_up > 1.0) || !(prob->lam_down > 0.0 && prob->lam_down <= 1.0)) return CRT_ERR_BAD_ARG;
-  if (!(prob->lam_min >= 0.0) || !(prob->lam_max >= prob->lam_min) || !(prob->xtol >= 0.0) || !(prob->ftol >= 0.0)) return CRT_ERR_BAD_ARG;
-  if (!prob->prior != !prob->inv_sigma_prior) return CRT_ERR_BAD_ARG;
-  if (!state->p || !state->p_trial || !state->cost || !state->lam || !state->A || !state->g || !state->status || !state->naccept ||
-      !state->nreject)
-    return CRT_ERR_BAD_ARG;
+  if (!blocks || !lm_problem_ok(prob, nblk, state)) return CRT_ERR_BAD_ARG;
   LmNormalArgs a = {};
   for (int q = 0; q < nblk; ++q) {
     if (!blocks[q].A || !blocks[q].g || !blocks[q].c2) return CRT_ERR_BAD_ARG;
-    a.blk[q] = NormalBlock{blocks[q].A, blocks[q].g, blocks[q].c2};
+    a.blk[q] = SumBlock{blocks[q].A, blocks[q].g, blocks[q].c2};
   }
   a.nblk = nblk, a.npar = prob->npar;
   a.lam_up = prob->lam_up, a.lam_down = prob->lam_down, a.lam_min = prob->lam_min, a.lam_max = prob->lam_max;

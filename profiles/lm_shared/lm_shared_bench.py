@@ -5,8 +5,10 @@
                k_lm_step_shared on given sums (the accepted path: cost is refilled with +inf before every call, one fill of npix
                doubles that is part of the figure) and k_lm_shared_covariance; next to them crt_hip_lm_step_chain_f64 /
                crt_hip_lm_chain_covariance_f64 at the same (nd, npar) on the same sums, through the PARENT commit's library where
-               --parent-lib names one (else through this library, whose chain kernels have the parent's device code:
-               device_code_diff.txt), which solve the larger system of nd * npar unknowns.
+               --parent-lib names one, which solve the larger system of nd * npar unknowns.  (Without --parent-lib they go through
+               this library, whose chain entries since profiles/lm_unify launch the shared-parameter kernels with an empty shared set:
+               the comparison then is k_lm_step_shared at ns against the same kernel at ns = 0, not against the kernels the recorded
+               lm_shared_bench.json was measured against.)
     baseline   the torch composition of profiles/lm_chain/lm_chain_bench.py extended by the border: the pixel cost, torch.where for accept
                / reject, the dense (nd nv + ns)^2 scaled damped arrowhead matrix of every pixel assembled by indexed stores,
                torch.linalg.cholesky / cholesky_solve, the new trial point; no clamp, no xtol test, which favours the composition.

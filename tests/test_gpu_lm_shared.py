@@ -1,7 +1,9 @@
 """GPU: the chained Levenberg-Marquardt step with parameters shared by all dates of a pixel (include_shared/crt1d_hip_lm_shared.h)
 through its C entries, then through the plans.
 
-1. ns = 0: every state array and the covariance are bitwise crt_hip_lm_step_chain_f64 / crt_hip_lm_chain_covariance_f64, three steps.
+1. ns = 0: every state array and the covariance of crt_hip_lm_step_shared_f64 / crt_hip_lm_shared_covariance_f64 at mask = 0 AND of
+   crt_hip_lm_step_chain_f64 / crt_hip_lm_chain_covariance_f64 are the bytes of tests/golden/lm_chain_bits.npz, after each of three steps:
+   what the chain's own kernels gave before the two pairs became one (tools/gen_lm_chain_bits.py, through that commit's library).
 2. ns = npar, one block, no prior: p_trial of every date, cost, lam, status are bitwise crt_hip_lm_step_normal_f64 on ONE column fed
    the nd dates' sums as nd blocks.
 3. The fp64 restatement of tests/lm_shared_reference.py, bit for bit: general masks, per-pixel and shared weights, a fully masked date,
@@ -23,6 +25,7 @@ docstring derives them).  Per entry |got - ref|_r <= s_r * bound + u (|delta_r| 
    the second c is an ALLOWANCE that covers these terms with a wide margin.
  Measured on MI355X, largest error / bound: see DESIGN.md 3.29."""
 import ctypes
+import os
 
 import numpy as np
 import pytest
@@ -89,22 +92,52 @@ CASES = [(nd, npar, mask) for nd in (1, 2, 3, 7) for npar in (1, 2, 5, 10) for m
 
 
 # ---- 1. ---------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("npar", [1, 2, 5, 10])
-@pytest.mark.parametrize("nd", [1, 2, 3, 7])
-def test_nothing_shared_is_the_chain_bitwise(nd, npar):
+BITS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lm_chain_bits.npz")
+BITS_CASES = [(nd, npar) for nd in (1, 2, 3, 7) for npar in (1, 2, 5, 10)]
+
+
+def chain_bits(nd, npar, make):
+    """The case of item 1 (tools/gen_lm_chain_bits.py records it through the parent's library): three blocks, a prior with one unobserved
+    row, bounds, date 1 without any observation (nd >= 3), per-pixel weights where nd + npar is odd.  make(npix, nd, p0, w=, **extras)
+    -> a Chain.  Three steps, each on the sums at its own p_trial.  -> {"<step>/<array>"}: every array of snap() and the covariance."""
     npix = 3
     rng = np.random.default_rng(11000 + 10 * nd + npar)
     w = _weights(rng, npix, nd, npar, (nd + npar) % 2 == 1)
     sums_at = _linear_case(rng, npix, nd, npar, nblk=3, empty=1 if nd >= 3 else None)
     p0 = 0.1 * rng.normal(size=(npix * nd, npar))
     ex = _extras(rng, npix * nd, npar)
-    wt = _t(w) if nd > 1 else None
-    a, b = Chain(npix, nd, _t(p0), w=wt, **ex), Shared(npix, nd, _t(p0), 0, w=wt, **ex)
+    ch = make(npix, nd, _t(p0), w=_t(w) if nd > 1 else None, **ex)
+    out = {}
     for it in range(3):
-        sums = _dev_sums(sums_at(a.snap()["p_trial"]))
-        assert _same(a.step(sums).snap(), b.step(sums).snap()), it
-        assert a.covariance().tobytes() == b.covariance().tobytes(), it
-    assert a.snap()["naccept"].min() >= 2
+        snap = ch.step(_dev_sums(sums_at(ch.snap()["p_trial"]))).snap()
+        out.update({f"{it}/{k}": snap[k] for k in STATE})
+        out[f"{it}/cov"] = ch.covariance()
+    return out
+
+
+@pytest.fixture(scope="module")
+def golden():
+    with np.load(BITS) as f:
+        return dict(f)
+
+
+def test_golden_holds_exactly_the_cases(golden):
+    want = {f"nd{nd}_npar{npar}/{it}/{k}" for nd, npar in BITS_CASES for it in range(3) for k in STATE + ("cov",)}
+    assert set(golden) == want and len(want) == 16 * 3 * 10
+
+
+@pytest.mark.parametrize("npar", [1, 2, 5, 10])
+@pytest.mark.parametrize("nd", [1, 2, 3, 7])
+def test_nothing_shared_is_the_chain_bitwise(nd, npar, golden):
+    """Both entries against the bytes the two chain kernels of the commit before the unification left: the chain entry and the shared
+    entry at mask = 0 now launch one kernel, so comparing them with each other would compare a kernel with itself."""
+    entries = {"chain": Chain, "shared": lambda npix, nd, p0, **kw: Shared(npix, nd, p0, 0, **kw)}
+    for name, make in entries.items():
+        got = chain_bits(nd, npar, make)
+        for key, v in got.items():
+            ref = golden[f"nd{nd}_npar{npar}/{key}"]
+            assert v.dtype == ref.dtype and v.shape == ref.shape and v.tobytes() == ref.tobytes(), (name, key)
+        assert got["2/naccept"].min() >= 2, name
 
 
 # ---- 2. ---------------------------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,8 @@
 1. The header against the ctypes table: names, argument counts, the struct layout; no other table holds the names; include_chain/ holds
    this one header.
 2. Every CRT_ERR_BAD_ARG / CRT_ERR_UNSUPPORTED of the entries is found before any launch (fake device pointers).
-3. crt_hip_lm_chain_max_nd equals the header's formula and is 0 for a refused npar.
+3. crt_hip_lm_chain_max_nd equals the header's formula and is 0 for a refused npar; the LDS bytes and the limit are those of
+   include_shared/crt1d_hip_lm_shared.h with nothing shared, for every nd up to the limit.
 4. The device-free errors of the two plans and of Model.retrieve_chain.
 5. tests/lm_chain_reference.py: the long-double dense layer against a 50-digit mpmath solve of the same system.
 6. A linear-Gaussian twin: one step at lam = 0 of the reference is the Rauch-Tung-Striebel smoother, mean and marginal covariances."""
@@ -152,6 +153,19 @@ def test_max_nd_is_the_formula_of_the_header(lib):
     assert lib.crt_hip_lm_chain_max_nd(10) == 83 and lib.crt_hip_lm_chain_max_nd(5) == 290
     for npar in (0, -1, 11, 1000):
         assert lib.crt_hip_lm_chain_max_nd(npar) == 0 == _lib.lm_chain_max_nd(npar)
+
+
+def test_chain_lds_bytes_are_the_shared_bytes_with_nothing_shared(lib):
+    """The chain entries launch the shared-parameter kernels with ns = 0 and may size the LDS with either macro: the two byte counts
+    (and the macro of the chain's header, written out) agree for every nd an entry accepts, and so do the two limits."""
+    from crt1d_amd import _lib
+
+    for npar in range(1, 11):
+        limit = lib.crt_hip_lm_chain_max_nd(npar)
+        assert limit == lib.crt_hip_lm_shared_max_nd(npar, 0) == _lib.lm_shared_max_nd(npar, 0)
+        for nd in range(1, limit + 1):
+            want = 8 * (nd * (2 * npar * npar + 4 * npar) + 4 * npar * npar + 64)
+            assert _lib.lm_chain_lds_bytes(nd, npar) == _lib.lm_shared_lds_bytes(nd, npar, 0) == want <= 160 * 1024, (nd, npar)
 
 
 # ---- 4. ---------------------------------------------------------------------------------------------------------------------------------

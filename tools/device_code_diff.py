@@ -7,6 +7,9 @@
 Each code object is disassembled (llvm-objdump -d --no-show-raw-insn --no-leading-addr) and split by symbol; a unit passes when both
 sides have the same symbols with identical text.  The text of a kernel that addresses a global of its unit holds its distance to it, so
 the comparison also holds the kernels to their order in the code object.  Prints one line per unit and exits 1 on any difference.
+Where a unit or a symbol exists on one side only (a kernel moved to another unit, a unit removed), a closing section looks every such
+symbol up in all units of the other side and says whether its text is identical there; one without a counterpart anywhere is listed and
+counts as a difference.
 
 For a kernel that differs it then says how (directories only; the resources come from the .amdgpu_metadata of the unit's *.s):
   "distances"   nothing but the literals of s_getpc_b64 / s_add_u32 pairs, the distances to globals of the unit
@@ -84,18 +87,45 @@ def code_object(unit_dir):
     return found[0]
 
 
+def units(d):
+    return {u for u in os.listdir(d) if os.path.isdir(os.path.join(d, u))}
+
+
+def moved(a, b):
+    """Directories whose unit lists differ: the symbols of the units on one side only, and of their namesakes' one-sided symbols, looked
+    up in ALL units of the other side.  -> lines, the number of symbols that differ or have no counterpart anywhere"""
+    pool = [{k: (u, v) for u in sorted(units(d)) for k, v in symbols(code_object(os.path.join(d, u))).items()} for d in (a, b)]
+    lines, bad = [], 0
+    for k in sorted(set(pool[0]) | set(pool[1])):
+        (ua, ta), (ub, tb) = pool[0].get(k, (None, None)), pool[1].get(k, (None, None))
+        if ua == ub:
+            continue  # (same unit: the per-unit lines above)
+        if ua is None or ub is None:
+            lines.append(f"    {k}  in {ua or ub} on the {'first' if ub is None else 'second'} side only")
+        else:
+            lines.append(f"    {k}  {ua} -> {ub}  {'identical' if ta == tb else 'DIFFERS'}")
+        bad += ua is None or ub is None or ta != tb
+    return lines, bad
+
+
 def main():
     a, b = sys.argv[1:3]
-    pairs = [("", a, b)] if os.path.isfile(a) else [
-        (u, code_object(os.path.join(a, u)), code_object(os.path.join(b, u)))
-        for u in sorted(os.listdir(a)) if os.path.isdir(os.path.join(a, u))]
+    both = [] if os.path.isfile(a) else sorted(units(a) & units(b))
+    pairs = [("", a, b)] if os.path.isfile(a) else [(u, code_object(os.path.join(a, u)), code_object(os.path.join(b, u))) for u in both]
     bad = 0
+    shuffled = bool(both) and units(a) != units(b)
     for unit, fa, fb in pairs:
         n, only, diff = compare(fa, fb, explain=bool(unit))
         print(f"{unit or os.path.basename(fa):24s} symbols {n:4d}  on one side only {len(only):3d}  differing {len(diff):3d}")
         for k in only + diff:
             print("   ", k)
-        bad += len(only) + len(diff)
+        shuffled = shuffled or (bool(unit) and bool(only))
+        bad += len(diff) + (0 if unit else len(only))
+    if shuffled:  # a unit or a symbol on one side only: it may have moved to another unit
+        lines, n = moved(a, b)
+        print(f"symbols whose unit differs {len(lines):3d}  of them differing or without a counterpart {n:3d}")
+        print("\n".join(lines))
+        bad += n
     sys.exit(1 if bad else 0)
 
 
