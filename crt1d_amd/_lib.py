@@ -716,6 +716,31 @@ def _masked_signatures():
 _MASKED_SIGNATURES = _masked_signatures()
 MASKED_EXPORTS = list(_MASKED_SIGNATURES)
 
+# the date-by-date form of the time-series retrieval (include_seq/crt1d_hip_lm_seq.h): the sums of a Gaussian prior with a full precision
+# matrix, the hand-over of a date's posterior through one random-walk gap, the backward Rauch-Tung-Striebel sweep; the chain's struct, a
+# header and a table of their own
+
+
+class CrtLmPriorFull(ctypes.Structure):
+    """``crt_lm_prior_full``: ``ncol``, ``npar``; ``prec_stride`` 0 or ``npar (npar + 1) / 2``; ``precision [ncol or 1][ntri]`` packed
+    lower triangles, ``mean [ncol][npar]``."""
+
+    _fields_ = [("ncol", ctypes.c_int32), ("npar", ctypes.c_int32), ("prec_stride", ctypes.c_int64), ("precision", _vp), ("mean", _vp)]
+
+
+def _seq_signatures():
+    P = ctypes.POINTER
+    i32, i64, ok = ctypes.c_int32, ctypes.c_int64, ctypes.c_int
+    return {
+        "crt_hip_lm_prior_block_f64": (ok, [P(CrtLmPriorFull), _vp, _vp, _vp, _vp, _vp]),
+        "crt_hip_lm_predict_f64": (ok, [i32, i32, _vp, _vp, i64, _vp, _vp, _vp]),
+        "crt_hip_lm_rts_f64": (ok, [P(CrtLmChain), i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    }
+
+
+_SEQ_SIGNATURES = _seq_signatures()
+SEQ_EXPORTS = list(_SEQ_SIGNATURES)
+
 _lib = None
 
 
@@ -742,7 +767,7 @@ def load():
                                       **_DLAI_SIGNATURES, **_DLEAF_SIGNATURES, **_GRAD_SIGNATURES, **_SENSJAC_SIGNATURES,
                                       **_SENSJAC_SERIES_SIGNATURES, **_RETRIEVE_SIGNATURES, **_SPECFIT_SIGNATURES,
                                       **_SPECFIT_SERIES_SIGNATURES, **_LEAFMODEL_SIGNATURES, **_LUT_SIGNATURES, **_LUT_POSTERIOR_SIGNATURES,
-                                      **_CHAIN_SIGNATURES, **_SHARED_SIGNATURES, **_MASKED_SIGNATURES}.items():
+                                      **_CHAIN_SIGNATURES, **_SHARED_SIGNATURES, **_MASKED_SIGNATURES, **_SEQ_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype = restype
         if argtypes is not None:

@@ -2293,6 +2293,46 @@ def _check_start(leaf_model, lo, hi, p0, prior, inv_sigma_prior):
         raise ValueError("prior and inv_sigma_prior go together")
 
 
+def pack_lower(P):
+    """``(..., npar, npar)`` -> the lower triangles row by row ``(..., npar (npar + 1) / 2)``, the layout of ``crt_lm_state.A`` and of
+    ``plan.prior_precision``; the upper triangle is not read."""
+    i, j = torch.tril_indices(P.shape[-1], P.shape[-1])
+    return P[..., i.to(P.device), j.to(P.device)].contiguous()
+
+
+def unpack_lower(T, npar):
+    """The inverse of :func:`pack_lower`: ``(..., ntri)`` -> the symmetric ``(..., npar, npar)``."""
+    i, j = (v.to(T.device) for v in torch.tril_indices(npar, npar))
+    P = T.new_zeros(T.shape[:-1] + (npar, npar))
+    P[..., i, j] = T
+    P[..., j, i] = T
+    return P
+
+
+def _check_full_prior(prior_mean, prior_precision, chain, evaluate, ncol, npar):
+    """``prior_mean=`` / ``prior_precision=`` of a retrieval plan with ``ncol`` columns (or: of the :class:`Columns` ``ncol``), as far as
+    no device is needed.  -> whether the plan has a full Gaussian prior"""
+    import numpy as np
+
+    if prior_mean is None and prior_precision is None:
+        return False
+    if prior_mean is None or prior_precision is None:
+        raise ValueError("prior_mean and prior_precision go together: a full Gaussian prior needs its mean and its precision matrix")
+    if chain is not None:
+        raise ValueError("prior_precision cannot be combined with chain=: the chained step takes no full prior block (a date-by-date "
+                         "series with a full prior is a SequentialPlan)")
+    if evaluate == "accepted":
+        raise ValueError("prior_precision cannot be combined with evaluate='accepted': the decision kernel (k_lm_decide) takes no block of "
+                         "sums, so its cost would lack the prior; use evaluate='running'")
+    ncol = ncol if isinstance(ncol, int) else ncol.ncol
+    shape = lambda v: tuple(v.shape) if hasattr(v, "shape") else np.shape(v)  # noqa: E731
+    if shape(prior_mean) not in ((npar,), (ncol, npar)):
+        raise ValueError(f"prior_mean must be {(ncol, npar)} or {(npar,)}, got {shape(prior_mean)}")
+    if shape(prior_precision) not in ((npar, npar), (ncol, npar, npar)):
+        raise ValueError(f"prior_precision must be {(ncol, npar, npar)} or {(npar, npar)}, got {shape(prior_precision)}")
+    return True
+
+
 def _check_shared(shared, chain, params, p0=None):
     """``shared=`` of a retrieval plan whose parameter axis is ``params``, as far as no device is needed: a sequence of names out of
     ``params`` or a boolean mask ``(npar,)``.  -> None (no shared set) or the mask of ``crt_lm_shared`` (bit ``k``: parameter ``k``)"""
@@ -2388,7 +2428,7 @@ class _LmPlan:
     _owns_sums = True  # a chained plan allocates its block of per-column sums; False: the subclass's _inner binds ``_blk`` to its own
 
     def _construct(self, keys, axis, o, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, chain=None,
-                   inv_sigma_chain=None, shared=None, evaluate="all", **inner):
+                   inv_sigma_chain=None, shared=None, evaluate="all", prior_mean=None, prior_precision=None, **inner):
         self.lib = _lib.load()
         self.scheme, self.keys, self.sun, self.options = scheme, keys, sun, o
         ncol, nz, nb, dev = cols.ncol, cols.nz, bands.nb, cols.device
@@ -2473,6 +2513,19 @@ class _LmPlan:
             if self._owns_sums:
                 self.sums = (new(ncol, ntri), new(ncol, npar), new(ncol))
                 self._blk = (_lib.CrtLmNormalBlock * 1)(_lib.CrtLmNormalBlock(*[v.data_ptr() for v in self.sums]))
+        # the full Gaussian prior (include_seq/crt1d_hip_lm_seq.h): its mean and packed precision, owned by the plan and bound by pointer,
+        # the block of sums k_lm_prior_block writes, and the two blocks the closing call reads: the data's sums, then the prior's
+        self._pf = None
+        if _check_full_prior(prior_mean, prior_precision, chain, evaluate, ncol, npar):
+            self.prior_mean = _per_col(prior_mean, "prior_mean", ncol, npar, dev).clone()
+            P = torch.as_tensor(prior_precision, dtype=torch.float64).to(dev)
+            self.prior_precision = pack_lower(P.expand(ncol, npar, npar)).clone()
+            if self._owns_sums:
+                self.sums = (new(ncol, ntri), new(ncol, npar), new(ncol))
+                self._blk = (_lib.CrtLmNormalBlock * 1)(_lib.CrtLmNormalBlock(*[v.data_ptr() for v in self.sums]))
+            self.prior_sums = (new(ncol, ntri), new(ncol, npar), new(ncol))
+            self._blk2 = (_lib.CrtLmNormalBlock * 2)(self._blk[0], _lib.CrtLmNormalBlock(*[v.data_ptr() for v in self.prior_sums]))
+            self._pf = _lib.CrtLmPriorFull(ncol, npar, ntri, self.prior_precision.data_ptr(), self.prior_mean.data_ptr())
         # the look-up-table start: the best candidate of every column on the plan's own observations and prior
         self.lut = None if table is None else LutMatchPlan(table, self.y, inv_sigma=self.inv_sigma or None, prior=self.prior,
                                                            inv_sigma_prior=self.inv_sigma_prior, p_default=self._p0)
@@ -2502,6 +2555,34 @@ class _LmPlan:
             return
         _lib.check(self.lib.crt_hip_lm_step_chain_f64(ctypes.byref(self._chain), ctypes.byref(self._prob), self._blk, 1, ctypes.byref(self._state),
                                                       s.cuda_stream), "crt_hip_lm_step_chain_f64")
+
+    def _step_full_prior(self, s):
+        """The closing calls of a ``step()`` with ``prior_precision``: ``crt_hip_lm_prior_block_f64`` at the trial point, then
+        ``crt_hip_lm_step_normal_f64`` on the two blocks -- the sums of the data, the sums of the prior."""
+        h = s.cuda_stream
+        _lib.check(self.lib.crt_hip_lm_prior_block_f64(ctypes.byref(self._pf), self.p_trial.data_ptr(), *[v.data_ptr() for v in self.prior_sums], h),
+                   "crt_hip_lm_prior_block_f64")
+        _lib.check(self.lib.crt_hip_lm_step_normal_f64(ctypes.byref(self._prob), self._blk2, 2, ctypes.byref(self._state), h),
+                   "crt_hip_lm_step_normal_f64")
+
+    def averaging_kernel(self, stream=None):
+        """``(ncol, npar, npar)``: ``I - cov @ (P + diag(inv_sigma_prior^2))`` with ``cov`` of :meth:`covariance` and ``P`` the full prior
+        precision -- the sensitivity of the retrieved state to the true one (the identity where the data decide, zero where the prior
+        does; the identity without any prior).  Plain torch on :meth:`covariance`; not for a chained plan (ValueError)."""
+        if self.nd is not None:
+            raise ValueError("averaging_kernel() is not defined for a chained plan: the prior of a date includes its neighbours")
+        dev = self.cols.device
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        cov = self.covariance(stream=s)
+        with torch.cuda.stream(s):
+            H = torch.zeros_like(cov) if self._pf is None else unpack_lower(self.prior_precision, self.npar)
+            if self.inv_sigma_prior is not None:
+                H = H + torch.diag_embed(self.inv_sigma_prior * self.inv_sigma_prior)
+            return torch.eye(self.npar, dtype=cov.dtype, device=dev) - cov @ H
+
+    def dfs(self, stream=None):
+        """``(ncol,)``: the degrees of freedom for signal, the trace of :meth:`averaging_kernel`."""
+        return torch.diagonal(self.averaging_kernel(stream), dim1=1, dim2=2).sum(1)
 
     def reset(self, p0=None):
         """Restart the state at ``p0`` (default: the plan's starting point): ``p = p_trial = p0``, ``cost = +inf``, ``lam = lam0``.  A plan
@@ -2657,23 +2738,39 @@ class RetrievalPlan(_LmPlan):
     ``inv_sigma_chain`` keeps its shape, its entries of shared parameters are not read.  ``p0`` / ``reset(p0)``: the shared entries of
     the dates after the first are overwritten with date 0's.  ``prior`` / ``inv_sigma_prior``: for a shared parameter the plan keeps date
     0's row and zeroes ``inv_sigma_prior`` on the other dates, so that the prior counts once.  ``p0=`` a :class:`LutTable` together with
-    ``shared`` is a ValueError.  ``shared=None``: the chained plan, call for call."""
+    ``shared`` is a ValueError.  ``shared=None``: the chained plan, call for call.
+
+    ``prior_mean`` ``(ncol, npar)`` or ``(npar,)`` with ``prior_precision`` ``(ncol, npar, npar)`` or ``(npar, npar)`` (only the lower
+    triangle is read): a Gaussian prior with a FULL precision matrix (include_seq/crt1d_hip_lm_seq.h), independent of ``prior`` /
+    ``inv_sigma_prior`` and added to them -- a covariance another retrieval produced (``covariance()``, ``lut_posterior()["cov"]``),
+    inverted, or a trait-database prior with correlated parameters.  The plan keeps ``plan.prior_mean (ncol, npar)`` and
+    ``plan.prior_precision (ncol, ntri)`` (the packed lower triangles of :func:`pack_lower`), bound by pointer: both may be updated in
+    place between steps.  The last launch of :meth:`step` becomes three: ``k_lm_normal`` writes the sums of the data,
+    ``crt_hip_lm_prior_block_f64`` the sums of the prior at the trial point, ``crt_hip_lm_step_normal_f64`` decides on the two blocks; the
+    stored ``A`` then includes the prior, so ``covariance()`` is the posterior covariance.  With or without ``sun``, ``leaf_model`` and
+    ``evaluate="running"``; together with ``chain=`` or ``evaluate="accepted"``, or one of the two without the other: a ValueError.
+    ``p0=`` a :class:`LutTable` stays allowed, but the match and ``lut_posterior()`` see the diagonal prior only: ``plan.lut.cost`` is
+    then not the first step's cost.  :meth:`averaging_kernel` and :meth:`dfs` give the averaging kernel and the degrees of freedom for
+    signal.  Without the two arguments the plan is what it was, launch for launch."""
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, sensors: SensorSet, y, *, keys, sun=None, d_leaf_r=None, d_leaf_t=None,
                  d_soil_r=None, lai=True, leaf=False, p0=None, lo=None, hi=None, inv_sigma=None, prior=None, inv_sigma_prior=None,
-                 leaf_model=None, chain=None, inv_sigma_chain=None, shared=None, evaluate="all", mu_s=0.501, tau_d_method="quad", **options):
+                 leaf_model=None, chain=None, inv_sigma_chain=None, shared=None, evaluate="all", prior_mean=None, prior_precision=None,
+                 mu_s=0.501, tau_d_method="quad", **options):
         static = self._static(scheme, cols, bands, levels, sensors, y, keys=keys, sun=sun, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t,
                               d_soil_r=d_soil_r, lai=lai, leaf=leaf, p0=p0, lo=lo, hi=hi, inv_sigma=inv_sigma, prior=prior,
                               inv_sigma_prior=inv_sigma_prior, leaf_model=leaf_model, chain=chain, inv_sigma_chain=inv_sigma_chain,
-                              shared=shared, evaluate=evaluate, tau_d_method=tau_d_method, **options)
+                              shared=shared, evaluate=evaluate, prior_mean=prior_mean, prior_precision=prior_precision,
+                              tau_d_method=tau_d_method, **options)
         self._construct(*static, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, chain=chain,
-                        inv_sigma_chain=inv_sigma_chain, shared=shared, evaluate=evaluate, sensors=sensors, y=y, inv_sigma=inv_sigma, mu_s=mu_s,
-                        tau_d_method=tau_d_method)
+                        inv_sigma_chain=inv_sigma_chain, shared=shared, evaluate=evaluate, prior_mean=prior_mean,
+                        prior_precision=prior_precision, sensors=sensors, y=y, inv_sigma=inv_sigma, mu_s=mu_s, tau_d_method=tau_d_method)
 
     @classmethod
     def _static(cls, scheme, cols, bands, levels, sensors, y, *, keys, sun=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True,
                 leaf=False, p0=None, lo=None, hi=None, inv_sigma=None, prior=None, inv_sigma_prior=None, leaf_model=None, chain=None,
-                inv_sigma_chain=None, shared=None, evaluate="all", mu_s=0.501, tau_d_method="quad", **options):
+                inv_sigma_chain=None, shared=None, evaluate="all", prior_mean=None, prior_precision=None, mu_s=0.501, tau_d_method="quad",
+                **options):
         """The constructor's arguments -> (keys, the parameter axis, the LM options): every check that needs neither a column nor a
         device."""
         _SolvePlan._check_options(_SolvePlan, scheme, tau_d_method)
@@ -2693,6 +2790,7 @@ class RetrievalPlan(_LmPlan):
         if isinstance(p0, LutTable):
             _check_lut_start(p0, axis.params, keys, False, y)
         _check_chain(chain, inv_sigma_chain, cols, axis.npar, _check_shared(shared, chain, axis.params, p0))
+        _check_full_prior(prior_mean, prior_precision, chain, evaluate, cols, axis.npar)
         return keys, axis, o
 
     def _inner(self, scheme, levels, sun, sensors, y, inv_sigma, keys, mu_s, tau_d_method, **axis):
@@ -2740,6 +2838,11 @@ class RetrievalPlan(_LmPlan):
                 _lib.check(self.lib.crt_hip_lm_normal_f64(self.p.shape[0], self.npar, self._obs, len(self.keys), *[v.data_ptr() for v in self.sums],
                                                           s.cuda_stream), "crt_hip_lm_normal_f64")
                 self._step_chain(s)
+                return self
+            if self._pf is not None:  # the last launch replaced by three: the sums of k_lm_step written out, the prior's, the step on both
+                _lib.check(self.lib.crt_hip_lm_normal_f64(self.p.shape[0], self.npar, self._obs, len(self.keys), *[v.data_ptr() for v in self.sums],
+                                                          s.cuda_stream), "crt_hip_lm_normal_f64")
+                self._step_full_prior(s)
                 return self
             _lib.check(self.lib.crt_hip_lm_step_f64(ctypes.byref(self._prob), self._obs, len(self.keys), ctypes.byref(self._state), s.cuda_stream),
                        "crt_hip_lm_step_f64")
@@ -2980,24 +3083,29 @@ class SpectralRetrievalPlan(_LmPlan):
 
     ``evaluate="running"``: as for :class:`RetrievalPlan` -- the normal plan goes through its masked entry with ``status`` as the skip
     flags; :meth:`fitted` still evaluates every column.  ``"accepted"`` is a ValueError: the cost comes out of the kernel that forms the
-    normal equations."""
+    normal equations.
+
+    ``prior_mean``, ``prior_precision``: as for :class:`RetrievalPlan` -- a Gaussian prior with a full precision matrix; the closing
+    call becomes ``crt_hip_lm_prior_block_f64`` and ``crt_hip_lm_step_normal_f64`` on two blocks, the normal plan's sums and the
+    prior's.  The match of a ``p0=`` :class:`LutTable` and ``lut_posterior()`` see the diagonal prior only."""
 
     def __init__(self, scheme, cols: Columns, bands: Bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None,
                  lai=True, leaf=False, p0=None, lo=None, hi=None, prior=None, inv_sigma_prior=None, sun=None, leaf_model=None, chain=None,
-                 inv_sigma_chain=None, shared=None, evaluate="all", mu_s=0.501, tau_d_method="quad", **options):
+                 inv_sigma_chain=None, shared=None, evaluate="all", prior_mean=None, prior_precision=None, mu_s=0.501, tau_d_method="quad",
+                 **options):
         keys, axis, o, levels = self._static(scheme, cols, bands, levels, y, keys=keys, inv_sigma=inv_sigma, d_leaf_r=d_leaf_r, d_leaf_t=d_leaf_t,
                                              d_soil_r=d_soil_r, lai=lai, leaf=leaf, p0=p0, lo=lo, hi=hi, prior=prior,
                                              inv_sigma_prior=inv_sigma_prior, sun=sun, leaf_model=leaf_model, chain=chain,
-                                             inv_sigma_chain=inv_sigma_chain, shared=shared, evaluate=evaluate, tau_d_method=tau_d_method,
-                                             **options)
+                                             inv_sigma_chain=inv_sigma_chain, shared=shared, evaluate=evaluate, prior_mean=prior_mean,
+                                             prior_precision=prior_precision, tau_d_method=tau_d_method, **options)
         self._construct(keys, axis, o, scheme, cols, bands, levels, sun, p0, lo, hi, prior, inv_sigma_prior, leaf_model, chain=chain,
-                        inv_sigma_chain=inv_sigma_chain, shared=shared, evaluate=evaluate, y=y, inv_sigma=inv_sigma, mu_s=mu_s,
-                        tau_d_method=tau_d_method)
+                        inv_sigma_chain=inv_sigma_chain, shared=shared, evaluate=evaluate, prior_mean=prior_mean,
+                        prior_precision=prior_precision, y=y, inv_sigma=inv_sigma, mu_s=mu_s, tau_d_method=tau_d_method)
 
     @classmethod
     def _static(cls, scheme, cols, bands, levels, y, *, keys, inv_sigma=None, d_leaf_r=None, d_leaf_t=None, d_soil_r=None, lai=True, leaf=False,
                 p0=None, lo=None, hi=None, prior=None, inv_sigma_prior=None, sun=None, leaf_model=None, chain=None, inv_sigma_chain=None,
-                shared=None, evaluate="all", mu_s=0.501, tau_d_method="quad", **options):
+                shared=None, evaluate="all", prior_mean=None, prior_precision=None, mu_s=0.501, tau_d_method="quad", **options):
         """The constructor's arguments -> (keys in ``LEVEL_KEYS`` order, the parameter axis, the LM options, the normalized levels): every
         check that needs no device."""
         if evaluate not in EVALUATE_MODES:
@@ -3011,6 +3119,7 @@ class SpectralRetrievalPlan(_LmPlan):
         _check_evaluate(evaluate, scheme, chain, True)
         levels = _spectral_shapes(cols, bands, levels, y, inv_sigma, len(keys), axis.npar, sun)
         _check_chain(chain, inv_sigma_chain, cols, axis.npar, _check_shared(shared, chain, axis.params, p0))
+        _check_full_prior(prior_mean, prior_precision, chain, evaluate, cols, axis.npar)
         return keys, axis, o, levels
 
     _owns_sums = False  # (the normal plan's A, g and c2 are the block)
@@ -3035,6 +3144,9 @@ class SpectralRetrievalPlan(_LmPlan):
             self.normal(s)
             if self.nd is not None:  # the step of every pixel on the block the normal plan wrote
                 self._step_chain(s)
+                return self
+            if self._pf is not None:  # two launches in place of the last: the sums of the prior, the step on both blocks
+                self._step_full_prior(s)
                 return self
             _lib.check(self.lib.crt_hip_lm_step_normal_f64(ctypes.byref(self._prob), self._blk, 1, ctypes.byref(self._state), s.cuda_stream),
                        "crt_hip_lm_step_normal_f64")
@@ -3071,6 +3183,250 @@ def retrieve_spectral(scheme, cols: Columns, bands: Bands, levels, y, *, keys, n
             post = plan.lut_posterior()
             res.update({"lut_" + k: post[k].clone() for k in ("mean", "cov", "ess")})
     return res
+
+
+# ---- the date-by-date retrieval: filter and Rauch-Tung-Striebel sweep (include_seq/crt1d_hip_lm_seq.h) -------------------------------------
+
+
+def _check_sequential(nd, inv_sigma_dyn, ncol, plan_kwargs):
+    """The arguments of a :class:`SequentialPlan` over ``ncol`` columns (or: over the :class:`Columns` ``ncol``), as far as no device is
+    needed.  -> (npix, nd, npar)"""
+    for name in ("sun", "chain", "shared"):
+        if plan_kwargs.get(name) is not None:
+            raise ValueError(f"{name}= is not served inside a SequentialPlan: every date is one unchained column of the inner plan")
+    n = int(nd)
+    if n != nd or n < 1:
+        raise ValueError(f"nd must be the number of dates, an integer >= 1, got {nd!r}")
+    ncol = ncol if isinstance(ncol, int) else ncol.ncol
+    if ncol % n:
+        raise ValueError(f"nd = {n} dates does not divide ncol = {ncol}: the columns are (pixel, date) pairs, pixel-major")
+    npix = ncol // n
+    for name in ("d_leaf_r", "d_leaf_t", "d_soil_r"):
+        d = plan_kwargs.get(name)
+        if d is not None and len(tuple(d.shape) if hasattr(d, "shape") else ()) == 3:
+            raise ValueError(f"{name} per column is not served inside a SequentialPlan: give (ntan, nb), shared by all dates")
+    axis = _ParamAxis(*[plan_kwargs.get(k) for k in ("d_leaf_r", "d_leaf_t", "d_soil_r")], plan_kwargs.get("lai", True),
+                      plan_kwargs.get("leaf", False), plan_kwargs.get("leaf_model"))
+    npar = axis.npar
+    if inv_sigma_dyn is None:
+        raise ValueError("a SequentialPlan needs inv_sigma_dyn (nd - 1, npar) or (npix, nd - 1, npar)")
+    w = torch.as_tensor(inv_sigma_dyn)
+    if tuple(w.shape) not in ((n - 1, npar), (npix, n - 1, npar)):
+        raise ValueError(f"inv_sigma_dyn must be {(n - 1, npar)} or {(npix, n - 1, npar)}, got {tuple(w.shape)}")
+    if not bool(((w >= 0) & (w < float("inf"))).all()):  # (false for NaN)
+        raise ValueError("inv_sigma_dyn must be finite and >= 0 (0: nothing is handed over across that gap)")
+    return npix, n, npar
+
+
+class SequentialPlan:
+    """The time series of a :class:`RetrievalPlan` with ``chain=nd``, solved date by date: a forward filter that retrieves one date at a
+    time with the previous date's posterior as a full Gaussian prior, and a backward Rauch-Tung-Striebel sweep over the filtered dates
+    (include_seq/crt1d_hip_lm_seq.h).  The on-chip state is that of ONE date: any ``nd`` is served, where the chained step ends at
+    ``lm_chain_max_nd(npar)`` dates; and a new acquisition costs one date's retrieval, not a re-solve of the series.
+
+    ``cols``, ``bands``, ``y``, ``inv_sigma``, ``p0``, ``prior``, ``inv_sigma_prior`` are per (pixel, date) column, pixel-major, exactly
+    the inputs of a ``chain=nd`` plan; ``inv_sigma_dyn`` ``(nd - 1, npar)`` or ``(npix, nd - 1, npar)``, finite and ``>= 0``, has the
+    meaning of ``inv_sigma_chain`` (0: nothing is handed over across that gap).  ``sensors`` given: the inner plan is an unchained
+    :class:`RetrievalPlan` on ``npix`` columns; ``sensors=None``: a :class:`SpectralRetrievalPlan`.  ``plan_kwargs`` go to it (``keys``,
+    directions ``(ntan, nb)``, ``lai``, ``leaf``, ``leaf_model``, ``lo``, ``hi``, the options, ``evaluate="running"``); ``sun=``,
+    ``chain=`` and ``shared=`` are a ValueError.  ``prior_mean`` / ``prior_precision`` ``(npix, ..)`` apply to date 0 only.
+
+    :meth:`assimilate` ``(t)``: the strided slices of date ``t`` are copied into the inner plan's bound tensors; for ``t > 0``
+    ``crt_hip_lm_predict_f64`` pushes the stored ``A`` of date ``t - 1`` through the gap into the inner plan's ``prior_precision``, ``p``
+    of date ``t - 1`` becomes ``prior_mean`` and the start; ``reset`` and ``niter`` steps; the state goes into the history arrays.
+    :meth:`run` is ``assimilate(0 .. nd - 1)`` and the sweep (``crt_hip_lm_rts_f64``), with no host synchronisation anywhere.  For data
+    that arrive later call :meth:`assimilate` one date at a time -- the strided inputs may be filled in place before the call -- and
+    :meth:`smooth` for the sweep over the dates assimilated so far.
+
+    On a linear problem filter plus sweep is the chained solve.  On a nonlinear one the filter linearises every date once, at its own
+    filtered point, while the chain iterates all dates jointly: the two agree where every date (with the prior it inherits) determines
+    the parameters; where only the whole series does, a date can settle in another minimum and hand it on -- use ``chain=`` there."""
+
+    def __init__(self, scheme, cols: Columns, bands: Bands, levels, y, *, nd, inv_sigma_dyn, keys, sensors=None, niter=10, **plan_kwargs):
+        npix, nd, npar = _check_sequential(nd, inv_sigma_dyn, cols, plan_kwargs)
+        if isinstance(niter, bool) or int(niter) != niter or niter < 1:
+            raise ValueError(f"niter must be an integer >= 1, got {niter!r}")
+        if not isinstance(y, dict):
+            raise TypeError("y must be a dict {key: (ncol, ...)}")
+        self.npix, self.nd, self.npar, self.niter = npix, nd, npar, int(niter)
+        dev, ncol = cols.device, cols.ncol
+        kw = dict(plan_kwargs)
+        per_date = lambda v: v.view(npix, nd, *v.shape[1:])  # noqa: E731
+        full = lambda v, name: self._full(v, name, ncol, dev)  # noqa: E731
+        Y = {k: full(v, f"y[{k!r}]") for k, v in y.items()}
+        S = {k: full(v, f"inv_sigma[{k!r}]") for k, v in (kw.pop("inv_sigma", None) or {}).items()}
+        pri = {k: _per_col(kw.pop(k), k, ncol, npar, dev) for k in ("prior", "inv_sigma_prior") if kw.get(k) is not None}
+        for k in ("prior", "inv_sigma_prior"):
+            kw.pop(k, None)
+        p0 = kw.pop("p0", None)
+        self._lut = isinstance(p0, LutTable)
+        self._p0 = None if p0 is None or self._lut else per_date(_per_col(p0, "p0", ncol, npar, dev))
+        pm, pp = kw.pop("prior_mean", None), kw.pop("prior_precision", None)
+        self._own_prior = _check_full_prior(pm, pp, None, kw.get("evaluate", "all"), npix, npar)
+        first = lambda v: None if v is None else per_date(v)[:, 0].clone()  # noqa: E731
+        cfields = ("psi", "lai", "g_kind", "g_param", "mla", "g_at_psi", "g_table")
+        c0 = Columns(*[first(getattr(cols, f)) for f in cfields])
+        c0._tables_ok = getattr(cols, "_tables_ok", False)
+        bfields = ("I_dr0", "I_df0", "leaf_r", "leaf_t", "soil_r")
+        shared_bands = bands.col_stride(ncol) == 0
+        b0 = bands if shared_bands else Bands(*[first(getattr(bands, f)) for f in bfields])
+        inner_kw = dict(kw, keys=keys, inv_sigma={k: first(v) for k, v in S.items()} or None,
+                        p0=p0 if self._lut else None if self._p0 is None else self._p0[:, 0].clone(),
+                        prior_mean=pm if self._own_prior else torch.zeros((npix, npar), dtype=torch.float64, device=dev),
+                        prior_precision=pp if self._own_prior else torch.zeros((npar, npar), dtype=torch.float64, device=dev),
+                        **{k: first(v) for k, v in pri.items()})
+        y0 = {k: first(v) for k, v in Y.items()}
+        with torch.cuda.device(dev):
+            if sensors is None:
+                self.plan = SpectralRetrievalPlan(scheme, c0, b0, levels, y0, **inner_kw)
+            else:
+                self.plan = RetrievalPlan(scheme, c0, b0, levels, sensors, y0, **inner_kw)
+        plan = self.plan
+        self.params, self.lib = plan.params, plan.lib
+        # what assimilate(t) copies: (the inner plan's bound tensor, the caller's array viewed (npix, nd, ...))
+        feeds = []
+
+        def feed(dsts, src):
+            seen = set()
+            for d in dsts:
+                if d is not None and d.data_ptr() not in seen:
+                    seen.add(d.data_ptr())
+                    feeds.append((d, per_date(src)))
+
+        for f in cfields:
+            if getattr(cols, f) is not None:
+                feed((getattr(plan.base_cols, f), getattr(plan.cols, f)), getattr(cols, f))
+        if not shared_bands:
+            for f in bfields:
+                if getattr(bands, f) is not None:
+                    feed((getattr(plan.base_bands, f),) + ((getattr(plan.bands, f),) if f in ("I_dr0", "I_df0") else ()), getattr(bands, f))
+        for k in plan.keys:
+            feed((plan.y[k],), Y[k])
+            if k in S:
+                feed((plan.inv_sigma[k],), S[k])
+        for k, v in pri.items():
+            feed((getattr(plan, k),), v)
+        self._feeds = feeds
+        self._start0 = plan._p0.clone()
+        self._pm0 = plan.prior_mean.clone() if self._own_prior else None
+        self._pp0 = plan.prior_precision.clone() if self._own_prior else None
+        w = torch.as_tensor(inv_sigma_dyn, dtype=torch.float64).to(dev).contiguous()
+        self.inv_sigma_dyn = w
+        self._w3 = w if w.ndim == 3 else w[None]  # (npix or 1, nd - 1, npar)
+        f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+        ntri = npar * (npar + 1) // 2
+        self._wgap, self._Aprev = torch.zeros((npix, npar), **f64), torch.zeros((npix, ntri), **f64)
+        self._info1 = torch.zeros((npix,), **i32)
+        self.p_filtered, self.A = torch.zeros((npix, nd, npar), **f64), torch.zeros((npix, nd, ntri), **f64)
+        self.cost = torch.zeros((npix, nd), **f64)
+        self.status, self.naccept, self.nreject, self.info_predict = (torch.zeros((npix, nd), **i32) for _ in range(4))
+        self.p_smoothed, self.cov = torch.zeros((npix, nd, npar), **f64), torch.zeros((npix, nd, npar, npar), **f64)
+        self.info_smooth = torch.zeros((npix,), **i32)
+        self.ndone, self.nsmoothed = 0, 0
+
+    @staticmethod
+    def _full(v, name, ncol, dev):
+        v = torch.as_tensor(v, dtype=torch.float64).to(dev).contiguous()
+        if v.ndim < 1 or v.shape[0] != ncol:
+            raise ValueError(f"{name} must have ncol = {ncol} leading rows, one per (pixel, date) column, got {tuple(v.shape)}")
+        return v
+
+    def assimilate(self, t, stream=None):
+        """The filter step of date ``t`` (``t == 0``, or the date after the last one assimilated) on ``stream``; no host synchronisation."""
+        if not 0 <= t < self.nd or t > self.ndone:
+            raise ValueError(f"assimilate({t}): the next date is {self.ndone} of nd = {self.nd} (or 0, to start over)")
+        plan, dev = self.plan, self.plan.cols.device
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            for dst, src in self._feeds:
+                dst.copy_(src[:, t])
+            if t > 0:  # the posterior of the date before, through the gap: the prior of this date
+                self._wgap.copy_(self._w3[:, t - 1].expand_as(self._wgap))
+                self._Aprev.copy_(self.A[:, t - 1])
+                _lib.check(self.lib.crt_hip_lm_predict_f64(self.npix, self.npar, self._Aprev.data_ptr(), self._wgap.data_ptr(), self.npar,
+                                                           plan.prior_precision.data_ptr(), self._info1.data_ptr(), s.cuda_stream),
+                           "crt_hip_lm_predict_f64")
+                self.info_predict[:, t].copy_(self._info1)
+                plan.prior_mean.copy_(self.p_filtered[:, t - 1])
+                plan.reset(self.p_filtered[:, t - 1])
+            else:
+                self.info_predict[:, 0].zero_()
+                if self._own_prior:
+                    plan.prior_mean.copy_(self._pm0)
+                    plan.prior_precision.copy_(self._pp0)
+                else:
+                    plan.prior_precision.zero_()
+                if self._lut:
+                    plan.reset()
+                else:
+                    plan.reset(self._start0 if self._p0 is None else self._p0[:, 0])
+                if not self._own_prior:
+                    plan.prior_mean.copy_(plan.p)
+            for _ in range(self.niter):
+                plan.step(s)
+            for hist, v in ((self.p_filtered, plan.p), (self.A, plan.A), (self.cost, plan.cost), (self.status, plan.status),
+                            (self.naccept, plan.naccept), (self.nreject, plan.nreject)):
+                hist[:, t].copy_(v)
+        self.ndone, self.nsmoothed = t + 1, 0
+        return self
+
+    def smooth(self, stream=None):
+        """The backward sweep (``crt_hip_lm_rts_f64``) over the dates assimilated so far; fewer than ``nd``: on compact copies."""
+        m = self.ndone
+        if m < 1:
+            raise ValueError("smooth() needs at least one assimilated date")
+        dev = self.plan.cols.device
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            whole = m == self.nd
+            cut = lambda v, n=m: v if whole else v[:, :n].contiguous()  # noqa: E731
+            p_f, A_f, w = cut(self.p_filtered), cut(self.A), cut(self._w3, m - 1)
+            p_s, cov = (self.p_smoothed, self.cov) if whole else (torch.empty_like(p_f), self.cov.new_empty((self.npix, m, self.npar, self.npar)))
+            chain = _lib.CrtLmChain(self.npix, m, 0 if w.shape[0] == 1 and self.npix != 1 or m == 1 else (m - 1) * self.npar,
+                                    w.data_ptr() if m > 1 else None)
+            _lib.check(self.lib.crt_hip_lm_rts_f64(ctypes.byref(chain), self.npar, p_f.data_ptr(), A_f.data_ptr(), p_s.data_ptr(), cov.data_ptr(),
+                                                   self.info_smooth.data_ptr(), s.cuda_stream), "crt_hip_lm_rts_f64")
+            if not whole:
+                self.p_smoothed[:, :m].copy_(p_s)
+                self.cov[:, :m].copy_(cov)
+        self.nsmoothed = m
+        return self
+
+    def run(self, smooth=True, stream=None):
+        """``assimilate(0 .. nd - 1)``, then the sweep (``smooth=False``: the filter only)."""
+        for t in range(self.nd):
+            self.assimilate(t, stream)
+        return self.smooth(stream) if smooth else self
+
+    def result(self, stream=None):
+        """Copies over the ``m`` dates assimilated so far: ``p (npix, m, npar)`` -- smoothed if the sweep ran over them, else filtered --,
+        ``p_filtered``, ``cov (npix, m, npar, npar)`` -- smoothed, else the inverse of every date's stored ``A``
+        (``crt_hip_lm_covariance_f64``) --, ``cost``, ``status``, ``naccept``, ``nreject`` ``(npix, m)``; ``info``: ``(npix,)`` of the sweep
+        (0, or 1 + the last date it could not pass) if it ran, else ``(npix, m)`` of the hand-overs (1: the date started without a
+        prior); ``info_predict`` always; ``params``."""
+        m, dev = self.ndone, self.plan.cols.device
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        smoothed = self.nsmoothed == m and m > 0
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            r = {k: getattr(self, k)[:, :m].clone() for k in ("p_filtered", "cost", "status", "naccept", "nreject", "info_predict")}
+            if smoothed:
+                r["p"], r["cov"], r["info"] = self.p_smoothed[:, :m].clone(), self.cov[:, :m].clone(), self.info_smooth.clone()
+            else:
+                A = self.A[:, :m].contiguous()
+                cov = self.cov.new_empty((self.npix, m, self.npar, self.npar))
+                if m:
+                    _lib.check(self.lib.crt_hip_lm_covariance_f64(self.npix * m, self.npar, A.data_ptr(), cov.data_ptr(), s.cuda_stream),
+                               "crt_hip_lm_covariance_f64")
+                r["p"], r["cov"], r["info"] = r["p_filtered"].clone(), cov, r["info_predict"].clone()
+        r["params"] = self.params
+        return r
+
+
+def retrieve_sequential(scheme, cols: Columns, bands: Bands, levels, y, *, nd, inv_sigma_dyn, keys, sensors=None, niter=10, smooth=True, **kw):
+    """One-shot :class:`SequentialPlan`: the filter over the ``nd`` dates, the sweep (``smooth=False``: not), ``plan.result()``."""
+    _check_sequential(nd, inv_sigma_dyn, cols, kw)  # (before any device is touched)
+    return SequentialPlan(scheme, cols, bands, levels, y, nd=nd, inv_sigma_dyn=inv_sigma_dyn, keys=keys, sensors=sensors, niter=niter,
+                          **kw).run(smooth).result()
 
 
 class _LevelsAD(torch.autograd.Function):

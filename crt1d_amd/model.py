@@ -471,7 +471,8 @@ class Model:
         "I_df_u", "F"``, the observed values of what :meth:`run_sensors` returns; with ``psi`` (a series of sun angles) ``{key: (nt, nsel,
         nsens)}``, what :meth:`run_series_sensors` returns.  ``weights``, ``levels``, ``directions``, ``lai`` as for
         :meth:`run_sensor_jacobian`; ``wrt_leaf``: ``None`` or ``"param"`` (``g_param`` itself is retrieved).  ``lm_options``: ``p0``, ``lo``,
-        ``hi``, ``prior``, ``inv_sigma_prior`` (each ``(npar,)``), ``inv_sigma`` (as ``y``), ``I_dr0_all`` / ``I_df0_all`` (with ``psi``) and
+        ``hi``, ``prior``, ``inv_sigma_prior`` (each ``(npar,)``), ``prior_mean (npar,)`` with ``prior_precision (npar, npar)`` (a Gaussian
+        prior with a full precision matrix, added to the diagonal one), ``inv_sigma`` (as ``y``), ``I_dr0_all`` / ``I_df0_all`` (with ``psi``) and
         the options of the plan.  Returns NumPy arrays ``p (npar,)``, ``cost``, ``status``, ``lam``, ``naccept``, ``nreject``,
         ``cov (npar, npar)`` and ``"params"``.  ValueError for ``4s`` and ``zq_pa``.  The model's own state is not changed.
         ``leaf_model=`` (a :class:`crt1d_amd.leaf_model.PlateLeafModel` on this model's wavelengths, among ``lm_options``) retrieves the
@@ -566,6 +567,53 @@ class Model:
         out["params"] = res["params"]
         return out
 
+    def retrieve_sequential(self, weights, y_dates, psi_dates, inv_sigma_dyn, levels=(0, -1), directions=None, lai=True, wrt_leaf=None,
+                            niter=10, smooth=True, **lm_options):
+        """:meth:`retrieve_chain` solved date by date (:class:`crt1d_amd.batched.SequentialPlan`: one pixel, the column replicated ``nd``
+        times): a forward filter that hands the posterior of a date to the next one as a full Gaussian prior, then a backward
+        Rauch-Tung-Striebel sweep; any number of dates.  ``psi_dates (nd,)``; ``y_dates``: ``{key: (nd, nsel, nsens)}``; ``inv_sigma_dyn
+        (nd - 1, npar)``: the random-walk weights of the gaps (the meaning of ``inv_sigma_chain``); ``niter``: the steps of every date.
+        ``lm_options``: ``p0``, ``prior``, ``inv_sigma_prior`` (each ``(nd, npar)`` or ``(npar,)``), ``prior_mean (npar,)`` /
+        ``prior_precision (npar, npar)`` (date 0 only), ``lo``, ``hi``, ``inv_sigma`` (as ``y_dates``), ``I_dr0_all`` / ``I_df0_all`` and
+        the options of the plan.  Returns NumPy arrays ``p (nd, npar)`` (smoothed; ``smooth=False``: filtered), ``p_filtered``, ``cov (nd,
+        npar, npar)``, ``cost``, ``status``, ``naccept``, ``nreject`` ``(nd,)``, ``info``, ``info_predict`` and ``"params"``.  The model's
+        own state is not changed."""
+        from . import batched
+
+        psi = np.atleast_1d(np.asarray(psi_dates, dtype=np.float64))
+        if psi.ndim != 1 or psi.size < 1:
+            raise ValueError("`psi_dates` must be a non-empty 1-D series of solar zenith angles, one per date")
+        nd = psi.size
+        directions = {} if directions is None else dict(directions)
+        if any(k not in batched.JAC_PARAMS for k in directions):
+            raise ValueError(f"directions must be a dict of (ntan, n_wl) arrays under keys out of {batched.JAC_PARAMS}")
+        if wrt_leaf not in (None, "param"):
+            raise ValueError(f"wrt_leaf must be None or 'param', got {wrt_leaf!r}")
+        d = {"d_" + k: np.ascontiguousarray(v, dtype=np.float64) for k, v in directions.items()}
+        for k, v in y_dates.items():
+            if np.ndim(v) != 3 or np.shape(v)[0] != nd:
+                raise ValueError(f"y_dates[{k!r}] must be (nd, nsel, nsens) with nd = {nd} dates, got {np.shape(v)}")
+        kw = dict(lm_options, lai=lai, leaf=wrt_leaf is not None, **d)
+        spectra = [kw.pop(k, None) for k in ("I_dr0_all", "I_df0_all")]
+        batched._check_sequential(nd, inv_sigma_dyn, nd, kw)  # (before any device is touched)
+        if np.ndim(inv_sigma_dyn) != 2:
+            raise ValueError(f"inv_sigma_dyn must be (nd - 1, npar) for the model's one pixel, got {np.shape(inv_sigma_dyn)}")
+        scheme, cols, b, sun = self._series_inputs(psi, *spectra, "retrieval")
+        rep = lambda v: None if v is None else v.expand(nd, *v.shape[1:]).contiguous()  # noqa: E731  (the one column on every date)
+        cols = batched.Columns(psi=sun.psi[0].contiguous(), lai=rep(cols.lai), g_kind=rep(cols.g_kind), g_param=rep(cols.g_param),
+                               mla=rep(cols.mla), g_at_psi=None if sun.g_at_psi is None else sun.g_at_psi[0].contiguous(),
+                               g_table=rep(cols.g_table))
+        b = batched.Bands(sun.I_dr0[0].contiguous(), sun.I_df0[0].contiguous(), rep(b.leaf_r), rep(b.leaf_t), rep(b.soil_r))
+        keys = tuple(k for k in batched.LEVEL_KEYS if k in y_dates)
+        f64 = lambda v: {k: np.asarray(a, dtype=np.float64) for k, a in v.items()}  # noqa: E731
+        if kw.get("inv_sigma") is not None:
+            kw["inv_sigma"] = f64(kw["inv_sigma"])
+        res = batched.retrieve_sequential(scheme, cols, b, levels, f64(y_dates), nd=nd, inv_sigma_dyn=inv_sigma_dyn, keys=keys or tuple(y_dates),
+                                          sensors=self._sensor_set(weights, self.nwl), niter=niter, smooth=smooth, **kw)
+        out = {k: v[0].cpu().numpy() for k, v in res.items() if k != "params"}
+        out["params"] = res["params"]
+        return out
+
     def retrieve_spectral(self, y, levels=(-1,), directions=None, lai=True, wrt_leaf=None, niter=20, psi=None, I_dr0_all=None,
                           I_df0_all=None, lut=None, posterior=False, **lm_options):
         """:meth:`retrieve` from the level spectra themselves, band by band (:class:`crt1d_amd.batched.SpectralRetrievalPlan`,
@@ -573,8 +621,8 @@ class Model:
         ``levels`` (default: the canopy top); with ``psi`` (a series of sun angles, and ``I_dr0_all`` / ``I_df0_all`` as for
         :meth:`run_series`) ``{key: (nt, nsel, n_wl)}``, the spectra of every sun state, fitted by ONE parameter vector
         (:class:`crt1d_amd.batched.SpectralNormalSeriesPlan`).  ``directions``, ``lai``, ``wrt_leaf`` as for :meth:`retrieve`.
-        ``lm_options``: ``p0``, ``lo``, ``hi``, ``prior``, ``inv_sigma_prior`` (each ``(npar,)``), ``inv_sigma`` (as ``y``; 0 masks a band) and the options of the
-        plan.  Returns what :meth:`retrieve` returns.  ValueError for the schemes outside
+        ``lm_options``: ``p0``, ``lo``, ``hi``, ``prior``, ``inv_sigma_prior`` (each ``(npar,)``), ``prior_mean`` / ``prior_precision`` (as for
+        :meth:`retrieve`), ``inv_sigma`` (as ``y``; 0 masks a band) and the options of the plan.  Returns what :meth:`retrieve` returns.  ValueError for the schemes outside
         ``batched.SPECTRAL_RETRIEVE_SCHEMES``.  The model's own state is not changed.  ``leaf_model=``, ``lut=`` and ``posterior=`` as for :meth:`retrieve`."""
         from . import batched
 
